@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the EEG -> LSTM distillation training step (BASELINE.json metric).
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One "step" = one pass of the hot path over one batch of synthetic input already resident in
@@ -9,7 +9,11 @@ HBM: fused band-pass + z-score -> 2-layer LSTM (hidden 768) forward -> fc -> cos
 distillation loss -> backward -> gradient all-reduce (RCCL, N>1) -> RMSprop step.
 Workload = BASELINE.json configs[1]: per-GPU batch 256, 128 ch x 500 samples, DINOv2 dim 384,
 bf16 MFMA operands with f32 accumulate/state.  Weak scaling: per-GPU work is fixed.
-Rank 0 prints ONE JSON line (metric, roofline of the dominant kernel, CPU baseline).
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps, writes the last
+step's outputs (--dump-outputs) and prints the metric.  --full adds the companions that take runs
+of their own: the fixture parity check before the timed region, the roofline of the dominant kernel
+(HIP events in the last timed step), the retrieval acceptance, the exact-f32 path and the CPU
+baseline (each can still be left out with its --no-* switch).
 """
 import argparse
 import json
@@ -114,12 +118,21 @@ def parse(argv=None):
     ap.add_argument("--loss", default="cosine", choices=["cosine", "barlow"],
                     help="cosine = the headline distillation step; barlow = BASELINE.json configs[4]: Barlow-Twins "
                          "cross-correlation loss on the LSTM embeddings (HIP off-diagonal reduction) + LARS")
-    ap.add_argument("--no-retrieval", action="store_true", help="skip the bf16-vs-CPU-reference retrieval acceptance")
-    ap.add_argument("--no-f32-line", action="store_true", help="skip the short measurement of the exact-f32 path")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true", help="skip the fixture check of the f32 / bf16 loss before the timed region")
-    ap.add_argument("--no-kernel-timing", action="store_true")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's loss, gradients and updated parameters as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the companions: fixture parity, roofline, retrieval acceptance, exact-f32 path, CPU baseline")
+    ap.add_argument("--no-retrieval", action="store_true", help="(--full) skip the bf16-vs-CPU-reference retrieval acceptance")
+    ap.add_argument("--no-f32-line", action="store_true", help="(--full) skip the short measurement of the exact-f32 path")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-parity", action="store_true", help="(--full) skip the fixture check of the f32 / bf16 loss before the timed region")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="(--full) skip the roofline's HIP events in the last timed step")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:     # a plain run does only what the headline needs
+        args.no_parity = args.no_retrieval = args.no_f32_line = args.no_cpu_baseline = args.no_kernel_timing = True
+    return args
 
 
 def launcher_command(n_gpus, argv, port=None):
@@ -186,6 +199,42 @@ def synthetic_pool(n, C, T, D, rank, device):
 
 def log(msg):
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
+
+
+def flat_parameters(trainer):
+    """The model's parameters as one vector, in the order of the trainer's flat gradient buffer."""
+    g = trainer.grads
+    return g.flat_params if g.flat_params is not None else torch.cat([p.detach().reshape(-1) for p in g.params])
+
+
+DUMP_LIMIT_BYTES = 64_000_000      # --dump-outputs: all files together
+NPY_HEADER_BYTES = 256             # (an upper bound of np.save's header for a 1-D or 0-D array)
+
+
+def write_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """Writes every array as out_dir/<name>.npy in float32 (float64 stays float64).  When all of them would exceed
+    `limit` bytes, each array of more than 2^20 elements is replaced by the same seeded sample of its flattened elements
+    (sorted indices; the sample depends on the array's size only), so that runs with the same arguments -- of two builds
+    too -- can be compared element for element.  Returns {name: number of elements written}."""
+    arrays = {k: np.asarray(a) for k, a in arrays.items()}
+    arrays = {k: a if a.dtype == np.float64 else a.astype(np.float32, copy=False) for k, a in arrays.items()}
+    big = sorted(k for k, a in arrays.items() if a.size > 1 << 20)
+    fixed = sum(arrays[k].nbytes for k in arrays if k not in big) + NPY_HEADER_BYTES * len(arrays)
+    if big and fixed + sum(arrays[k].nbytes for k in big) > limit:
+        frac = (limit - fixed) / sum(arrays[k].nbytes for k in big)
+        for k in big:
+            a = arrays[k].reshape(-1)
+            idx = np.sort(np.random.default_rng(20240).choice(a.size, int(a.size * frac), replace=False))
+            arrays[k] = a[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+        written[k] = a.size
+    total = sum(os.path.getsize(os.path.join(out_dir, k + ".npy")) for k in arrays)
+    if total > limit:
+        raise RuntimeError(f"--dump-outputs wrote {total} bytes, more than {limit}")
+    return written
 
 
 def retrieval_acceptance(model_bf16, filt, device, tag="cfg2"):
@@ -304,9 +353,7 @@ def main():
         # start every rank must hold the same parameter bits (the checksum is an exact integer sum of the f32 words)
         ones = torch.ones(1, device=device, dtype=torch.float64)
         dist.all_reduce(ones)
-        pbuf = trainer.grads.flat_params if trainer.grads.flat_params is not None else torch.cat(
-            [p.detach().reshape(-1) for p in trainer.grads.params])
-        csum = pbuf.view(torch.int32).to(torch.int64).sum().reshape(1)
+        csum = flat_parameters(trainer).view(torch.int32).to(torch.int64).sum().reshape(1)
         lo, hi = csum.clone(), csum.clone()
         dist.all_reduce(lo, op=dist.ReduceOp.MIN)
         dist.all_reduce(hi, op=dist.ReduceOp.MAX)
@@ -324,6 +371,13 @@ def main():
     trainer.check_device_status()       # a timed-out in-kernel hand-off would invalidate the run: fail loudly
     log(f"timed region done: {elapsed:.3f}s for {args.steps} steps; losses " +
         " ".join(f"{float(l):.4f}" for l in step_losses))
+    if rank == 0 and args.dump_outputs:
+        # what the last timed step computed: its loss, the gradients it left in the parameters' .grad (one flat
+        # buffer, all-reduced over the ranks) and the parameters after its optimiser update
+        n = write_outputs(args.dump_outputs, {"loss": loss.reshape(1).float().cpu().numpy(),
+                                              "gradients": trainer.grads.flat.cpu().numpy(),
+                                              "parameters": flat_parameters(trainer).float().cpu().numpy()})
+        log(f"outputs of the last timed step in {args.dump_outputs}: {n} elements")
 
     if rank == 0:
         seg_per_s = world * B * args.steps / elapsed

@@ -478,14 +478,14 @@ def test_fused_flat_rmsprop_matches_torch(cuda):
 
 
 def test_bench_line_schema(cuda):
-    """bench.py's contract with the driver: ONE JSON line on stdout with the metric of BASELINE.json, the roofline
-    object of the dominant kernel (measured with HIP events inside the run) and no model keys in `config`."""
+    """bench.py's contract with the driver: ONE JSON line on stdout with the metric of BASELINE.json, with --full the
+    roofline object of the dominant kernel (measured with HIP events inside the run) and no model keys in `config`."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--full",
                           "--no-cpu-baseline", "--no-retrieval", "--no-f32-line", "--no-parity"],
                          capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -503,3 +503,30 @@ def test_bench_line_schema(cuda):
     assert r["bound"] in ("hbm", "mfma") and r["unit"] in ("GB/s", "TFLOP/s")
     assert abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-9 and 0.0 < r["frac"] < 1.0
     assert r["us_per_launch"]["fwd"] > 0 and r["us_per_launch"]["bwd"] > 0
+
+
+def test_bench_plain_run_dumps_its_last_step(cuda, tmp_path):
+    """A plain bench.py run prints the headline line without the --full companions, and --dump-outputs writes what its
+    last timed step computed -- loss, gradients, updated parameters -- as float32 files, whole at cfg2, within 64 MB."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=root)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["dtype"] == "bf16" and d["higher_is_better"] is True
+    assert abs(d["value"] - 256 * 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+    for k in ("parity", "roofline", "retrieval", "f32_path", "cpu_baseline"):
+        assert k not in d, k
+    C, H, L, D = 128, 768, 2, 384
+    n_params = sum(4 * H * ((C if l == 0 else H) + H) + 8 * H for l in range(L)) + D * H + D
+    loss, g, p = (np.load(os.path.join(str(tmp_path), f"{k}.npy")) for k in ("loss", "gradients", "parameters"))
+    assert loss.dtype == g.dtype == p.dtype == np.float32
+    assert loss.shape == (1,) and float(loss[0]) == d["final_loss"]
+    assert g.shape == p.shape == (n_params,) and np.isfinite(g).all() and np.isfinite(p).all() and np.abs(g).max() > 0
+    assert sum(os.path.getsize(os.path.join(str(tmp_path), f)) for f in os.listdir(str(tmp_path))) <= 64_000_000

@@ -412,3 +412,47 @@ def test_bench_launcher_argv_env_and_rank_count_refusals():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"], env=dict(clean, WORLD_SIZE="2", RANK="0"),
                        capture_output=True, text=True, timeout=300)
     assert r.returncode != 0 and r.stdout.strip() == ""
+
+
+def test_bench_plain_run_leaves_the_companions_to_full():
+    """A plain `bench.py` run does only what its headline needs; --full brings back every companion (parity, roofline
+    events, retrieval, exact-f32 path, CPU baseline), each of which its --no-* switch still leaves out; --steps is the
+    number of timed steps and must be at least 1."""
+    sys.path.insert(0, ROOT)
+    import bench
+    companions = ("no_parity", "no_retrieval", "no_f32_line", "no_cpu_baseline", "no_kernel_timing")
+    plain = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert plain.steps == 7 and plain.warmup == 2 and not plain.full and plain.dump_outputs is None
+    assert all(getattr(plain, k) for k in companions)
+    full = bench.parse(["--full"])
+    assert full.full and not any(getattr(full, k) for k in companions)
+    part = bench.parse(["--full", "--no-cpu-baseline", "--dump-outputs", "out"])
+    assert part.no_cpu_baseline and not part.no_parity and part.dump_outputs == "out"
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse(bad)
+
+
+def test_bench_write_outputs_float_files_within_the_limit(tmp_path):
+    """--dump-outputs: float32 / float64 .npy files; over the byte limit the large arrays become the same seeded sample of
+    their elements in every run, and the files together stay within the limit."""
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(0)
+    small = {"loss": np.array([0.5], np.float32), "h": rng.standard_normal((3, 4)), "i": np.arange(5)}
+    assert bench.write_outputs(str(tmp_path / "a"), small) == {"loss": 1, "h": 12, "i": 5}
+    for k, a in small.items():
+        got = np.load(tmp_path / "a" / f"{k}.npy")
+        assert got.dtype == (np.float64 if a.dtype == np.float64 else np.float32) and got.shape == a.shape
+        np.testing.assert_array_equal(got, a)
+    big = {"loss": np.array([0.5], np.float32), "g": rng.standard_normal(3 << 20).astype(np.float32),
+           "p": rng.standard_normal(2 << 20).astype(np.float32)}
+    limit = 12_000_000                                                    # < the 20 MiB the arrays hold
+    n1 = bench.write_outputs(str(tmp_path / "b"), big, limit=limit)
+    n2 = bench.write_outputs(str(tmp_path / "c"), big, limit=limit)
+    assert n1 == n2 and n1["loss"] == 1 and 0 < n1["g"] < 3 << 20 and 0 < n1["p"] < 2 << 20
+    assert sum(os.path.getsize(tmp_path / "b" / f"{k}.npy") for k in big) <= limit
+    for k in big:
+        b, c = np.load(tmp_path / "b" / f"{k}.npy"), np.load(tmp_path / "c" / f"{k}.npy")
+        np.testing.assert_array_equal(b, c)
+        assert np.isin(b, big[k]).all()
