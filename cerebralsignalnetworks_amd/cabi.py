@@ -278,7 +278,7 @@ class LstmPlan:
                                                       else None, None))
 
     def dgates_copies(self):
-        """Copies of the gate gradients the last backward wrote per step (csn_hip.h): 1, 2, or 0 before any backward."""
+        """Copies of the gate gradients the last backward wrote per step (csn_hip.h): 2, or 0 before any backward."""
         return load().csn_lstm_plan_dgates_copies(self._plan)
 
     def forward(self, x_bti, w_ih, w_hh, b_ih, b_hh, want_all=False):

@@ -44,7 +44,7 @@ struct LayerWs {
 };
 struct WsLayout {
   LayerWs layer[8];
-  size_t x_c, x_blk, wih0_blk, dy_tm, tn_scratch, colsum, tn_scratch2, colsum2, status, agree, agree_b, tile_ctr, zeros_bh, f32_bias_part, total;
+  size_t x_c, x_blk, wih0_blk, dy_tm, tn_scratch, colsum, status, agree, agree_b, zeros_bh, f32_bias_part, total;
   // weight-stationary paths: everything that must be zero at the start of a forward / a backward sits in ONE block each
   size_t zero_fwd, zero_fwd_bytes, zero_bwd, zero_bwd_bytes;
   bool fuse_x;
@@ -144,10 +144,10 @@ static WsLayout make_layout(const csnLstmDesc& d, int training, const Options& o
   }
   if (w.persist) {
     w.zero_fwd = off;
-    // (x 4: the wave-specialised forward body keeps one flag line per 16-row chain, the half-pipelined one per 32-row half)
+    // (x 4: room for four flag lines per (slot, M-tile), which the forward kernels of this library do not use; kept so
+    // that the layout of everything behind it stays where it was)
     for (int l = 0; l < d.L; ++l) w.layer[l].counters = take(((size_t)d.T + 1) * (Bpad / 64) * 4 * kPersistFlagLine * 4);
     w.agree = take(((size_t)d.T + 8) * 8 * sizeof(unsigned long long));   // 8 words per launch
-    w.tile_ctr = take(((size_t)d.T + 8) * 4 * sizeof(unsigned));          // GEMM tile counters, 4 per launch
     w.zero_fwd_bytes = off - w.zero_fwd;
   }
   if (w.persist_bwd) {
@@ -163,10 +163,6 @@ static WsLayout make_layout(const csnLstmDesc& d, int training, const Options& o
     w.dy_tm = take(TB * H * 4);
     w.tn_scratch = take(tn_bytes);
     w.colsum = take(colsum_scratch_bytes(G));
-    if (w.persist_bwd && d.L > 1) {     // weight gradients of the upper layers run beside the last backward launches
-      w.tn_scratch2 = take(tn_bytes);
-      w.colsum2 = take(colsum_scratch_bytes(G));
-    }
   }
   w.total = off;
   return w;
@@ -237,7 +233,6 @@ static inline unsigned grid_for(int64_t n) {
 struct SideCtx {
   hipStream_t side = nullptr;           // GEMMs
   hipStream_t layer[8] = {nullptr};     // weight-stationary forward: one stream per layer >= 1
-  hipStream_t wgrad = nullptr;          // LOWEST priority: weight-gradient GEMMs of finished layers beside the last backward launches
   std::vector<hipEvent_t> events;
   size_t next = 0;
 };
@@ -246,9 +241,6 @@ static int side_ctx(SideCtx& c) {
   if (c.side == nullptr) {
     CSN_HIP_CHECK(hipStreamCreateWithFlags(&c.side, hipStreamNonBlocking));
     for (int l = 1; l < 8; ++l) CSN_HIP_CHECK(hipStreamCreateWithFlags(&c.layer[l], hipStreamNonBlocking));
-    int lo = 0, hi = 0;                 // (numerically: lo = least urgent)
-    CSN_HIP_CHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-    CSN_HIP_CHECK(hipStreamCreateWithPriority(&c.wgrad, hipStreamNonBlocking, lo));
   }
   c.next = 0;
   return CSN_OK;
@@ -358,7 +350,6 @@ extern "C" void csn_lstm_plan_destroy(csnLstmPlan* P) {
   const bool switched = hipGetDevice(&cur) == hipSuccess && cur != P->device && hipSetDevice(P->device) == hipSuccess;
   for (hipEvent_t e : P->sc.events) (void)hipEventDestroy(e);
   if (P->sc.side) (void)hipStreamDestroy(P->sc.side);
-  if (P->sc.wgrad) (void)hipStreamDestroy(P->sc.wgrad);
   for (int l = 1; l < 8; ++l)
     if (P->sc.layer[l]) (void)hipStreamDestroy(P->sc.layer[l]);
   for (int i = 0; i < 4; ++i)
@@ -391,7 +382,7 @@ extern "C" const char* csn_lstm_plan_kernel_name(const csnLstmPlan* P, int which
   const bool ks = (P->d.dtype == CSN_F32 ? P->d.H % 128 == 0 : P->d.H % 256 == 0);      // K-split cell kernels (lstm_cell.hip)
   if (P->w.f32_persist) return which == 0 ? "lstm_fwd_f32_persist_kernel" : (which == 1 ? "lstm_bwd_f32_persist_kernel" : nullptr);
   if (which == 0) {
-    if (P->w.fwd_ns) return P->opt.fwd_ws && P->d.H == 768 ? "lstm_fwd_ws_kernel" : "lstm_fwd_ns_kernel";
+    if (P->w.fwd_ns) return "lstm_fwd_ns_kernel";
     if (P->w.persist) return "lstm_fwd_persist_kernel";
     if (P->w.il) return "lstm_cell_fwd_il_kernel";
     return ks ? "lstm_cell_fwd_ks_kernel" : "lstm_cell_fwd_kernel";
@@ -909,7 +900,7 @@ static int forward_persist(Plan& P, char* ws, int training, hipStream_t st, Side
   const int Cz = P.opt.chunk;
   const int nch = (T + Cz - 1) / Cz;
   int rc;
-  // one fill: the flag lines of every layer, the XCD agreement words, the GEMM tile counters
+  // one fill: the flag lines of every layer, the XCD agreement words
   CSN_HIP_CHECK(hipMemsetAsync(ws + w.zero_fwd, 0, w.zero_fwd_bytes, st));
   auto fill_slot = [&](PersistFwdSlot& S, int l, int c) {
     const LayerWs& L = w.layer[l];
@@ -924,7 +915,6 @@ static int forward_persist(Plan& P, char* ws, int training, hipStream_t st, Side
     S.wih_blk = nullptr;
     S.bias = nullptr;
     S.I = 0;
-    S.xproj_bf16 = 0;
     if (l == 0 && w.fuse_x) {
       S.x_blk = (const bf16_t*)(ws + w.x_blk);
       S.wih_blk = (const bf16_t*)(ws + w.wih0_blk);
@@ -955,77 +945,38 @@ static int forward_persist(Plan& P, char* ws, int training, hipStream_t st, Side
   if (a.data_polls)        // the ring of 4 hand-off slabs of every layer starts as sentinel (lstm_fwd_persist.hip)
     for (int l = 0; l < NL; ++l)
       CSN_HIP_CHECK(hipMemsetAsync(ws + w.layer[l].h_blk_all, 0xff, (size_t)4 * Bpad * H * 2, st));
-  a.chains = (w.fwd_ns && H == 768 && P.opt.fwd_ws) ? 4 : 1;
-  a.half_tiles = (w.fwd_ns && H == 768 && P.opt.fwd_halves && a.chains == 1) ? 1 : 0;
   int n_launch = 0;
 
   const int max_slots = NL < nch ? NL : nch;
   const int fwd_slices = w.fwd_ns ? fwd_ns_slices(H) : fwd_persist_slices(H);
   auto launch_fwd = [&](const PersistFwdArgs& args, hipStream_t on) {
-#ifdef CSN_EXPERIMENTS
-    if (args.chains == 4) return launch_fwd_ws(args, on);
-#endif
     return w.fwd_ns ? launch_fwd_ns(args, on) : launch_fwd_persist(args, on);
   };
   const bool grouped = max_slots <= 4 && max_slots * MT <= 8 && fwd_slices <= 32 &&
                        !P.opt.persist_streams;
   if (grouped) {
-    // CSN_BESIDE_FWD (N-split kernel, H <= 768): 24 of the 32 CUs of an XCD carry a group, the 8 others (and every CU
-    // of an XCD without a group) walk the input-projection GEMM xproj_{l+1}[chunk] = h_l[chunk] W_ih^T + b of the chunk
-    // layer l finished ONE LAUNCH AGO (gemm_beside.h): both of its dependencies are then kernel boundaries, and the
-    // layer above lags two chunks -- the arrangement of the backward launches.  Measured at cfg2 (profiles/r02_c): the
-    // GEMM needs 17 k CU-us as a kernel of its own (67 us on 256 CUs) but 26 k beside the recurrence (4-wave tiles,
-    // per-CU load bandwidth shared with nothing but itself), and a forward launch leaves only 64 CUs x 215 us = 14 k:
-    // the launches stretch to 263 us and the step ends where it started (10.98 vs 10.96 ms).  Not the default.
-    const bool beside = w.fwd_ns && NL > 1 && fwd_slices <= 28 && H % 64 == 0 && P.opt.beside_fwd;
-    const bool xproj_bf16 = beside && P.opt.xproj_bf16;
-    const int lag = beside ? 2 : 1;
-    const int ndiag = nch + lag * (NL - 1);
+    const int ndiag = nch + NL - 1;
     const bool try_local = !P.opt.no_xcd_local;
-    BesideGemm pending[3];
-    int npending = 0;
-    a.grid_slices = 32;
     if ((rc = prof_mark(g_prof, 0, st))) return rc;
     for (int dg = 0; dg < ndiag; ++dg) {
       int lay[4], chk[4], ns = 0;
       for (int l = 0; l < NL; ++l) {
-        const int c = dg - lag * l;
+        const int c = dg - l;
         if (c < 0 || c >= nch) continue;
         lay[ns] = l;
         chk[ns] = c;
         fill_slot(a.slot[ns], l, c);
-        a.slot[ns].xproj_bf16 = (l > 0 && xproj_bf16) ? 1 : 0;
         ++ns;
       }
       a.nslots = ns;
       a.xcd_groups = 1;
-      a.ngemm = npending;
-      for (int i = 0; i < npending; ++i) a.gemm[i] = pending[i];
-      npending = 0;
       a.agree = try_local ? (unsigned long long*)(ws + w.agree) + (size_t)dg * 8 : nullptr;
-      if (ns == 0 && a.ngemm == 0) continue;
       if ((rc = prof_pair(g_prof, 0, false, st))) return rc;
       if ((rc = launch_fwd(a, st))) return rc;
       if ((rc = prof_pair(g_prof, 0, true, st))) return rc;
       ++n_launch;
-      for (int i = 0; i < ns; ++i) {
-        const int l = lay[i];
-        if (l + 1 >= NL) continue;
-        if (!beside) {
-          if ((rc = xproj_gemm(l, chk[i], st))) return rc;
-          continue;
-        }
-        const LayerWs& L = w.layer[l];
-        const LayerWs& Ln = w.layer[l + 1];
-        const int t0 = chk[i] * Cz, nst = (t0 + Cz <= T) ? Cz : T - t0;
-        // (xproj in bf16: half the GEMM's C stream and half of what the recurrence reads back per step; the tile
-        // counter lets the recurrence workgroups take tiles once their chunk is done)
-        float* Cx = xproj_bf16 ? (float*)((bf16_t*)(ws + Ln.xproj) + (size_t)t0 * B * G) : (float*)(ws + Ln.xproj) + (size_t)t0 * B * G;
-        pending[npending] = BesideGemm{(const bf16_t*)(ws + L.h_all) + (size_t)(t0 + 1) * B * H, (const bf16_t*)(ws + Ln.wih),
-                                       Cx, nst * B, (int)G, H, (const float*)(ws + Ln.bias),
-                                       (unsigned*)(ws + w.tile_ctr) + (size_t)dg * 4 + npending, xproj_bf16 ? 1 : 0};
-        ++npending;
-      }
+      for (int i = 0; i < ns; ++i)      // layer l finished chunk c -> xproj_{l+1}[chunk c], before the next launch
+        if (lay[i] + 1 < NL && (rc = xproj_gemm(lay[i], chk[i], st))) return rc;
     }
     if ((rc = prof_mark(g_prof, 1, st))) return rc;
     g_prof.launches[0] = n_launch;
@@ -1239,44 +1190,29 @@ static int backward_persist(Plan& P, char* ws, const float* dy_last,
   CSN_HIP_CHECK(hipMemsetAsync(ws + w.zero_bwd, 0, w.zero_bwd_bytes, st));
   const bool try_local = !P.opt.no_xcd_local;
 
-  int single_copy = 0;       // (decided below, before the first launch)
-  // weight / bias gradients of one layer (its recurrence complete): four launches on stream `on`
-  auto weight_grads = [&](int l, hipStream_t on, size_t scratch_off, size_t colsum_off) -> int {
+  // weight / bias gradients of one layer (its recurrence complete): four launches on the caller's stream
+  auto weight_grads = [&](int l) -> int {
     const LayerWs& L = w.layer[l];
     const int64_t I = l == 0 ? d->I : H;
     const void* inp = l == 0 ? (const void*)(ws + w.x_c)
                              : (const void*)((const bf16_t*)(ws + w.layer[l - 1].h_all) + (size_t)B * H);
-    float* slabs = (float*)(ws + scratch_off);
+    float* slabs = (float*)(ws + w.tn_scratch);
     int S = 1, r;
     int cs_done = 0, S_cs = 1;
-    const int blocked = single_copy;
-    const char* dgm = ws + (blocked ? L.dg_blk_all : L.dgates);
-    if ((r = launch_gemm_tn_slabs(dgm, ws + L.h_all, slabs, G, H, TB, CSN_BF16, on, &S, (float*)(ws + colsum_off), &cs_done, P.opt, blocked))) return r;
+    if ((r = launch_gemm_tn_slabs(ws + L.dgates, ws + L.h_all, slabs, G, H, TB, CSN_BF16, st, &S, (float*)(ws + w.colsum), &cs_done, P.opt))) return r;
     S_cs = S;
-    if ((r = launch_reduce_slabs_unperm(slabs, G * H, S, H, H, dw_hh[l], on))) return r;
-    if ((r = launch_gemm_tn_slabs(dgm, inp, slabs, G, I, TB, CSN_BF16, on, &S, nullptr, nullptr, P.opt, blocked))) return r;
-    if ((r = launch_reduce_slabs_unperm(slabs, G * I, S, H, I, dw_ih[l], on))) return r;
+    if ((r = launch_reduce_slabs_unperm(slabs, G * H, S, H, H, dw_hh[l], st))) return r;
+    if ((r = launch_gemm_tn_slabs(ws + L.dgates, inp, slabs, G, I, TB, CSN_BF16, st, &S, nullptr, nullptr, P.opt))) return r;
+    if ((r = launch_reduce_slabs_unperm(slabs, G * I, S, H, I, dw_ih[l], st))) return r;
     // bias gradient = column sums of dgates: partial sums come out of the dW_hh GEMM when its kernel provides them
     if (!cs_done) {
-      if (blocked) return fail(CSN_ERR_UNSUPPORTED, "backward_persist: single-copy mode without the weight-gradient kernel's column sums");
-      if ((r = launch_colsum_partial(ws + L.dgates, TB, G, CSN_BF16, ws + colsum_off, on))) return r;
+      if ((r = launch_colsum_partial(ws + L.dgates, TB, G, CSN_BF16, ws + w.colsum, st))) return r;
       S_cs = colsum_chunks();
     }
-    if ((r = launch_reduce_slabs_unperm((const float*)(ws + colsum_off), G, S_cs, H, 1, db_ih[l], on))) return r;
-    CSN_HIP_CHECK(hipMemcpyAsync(db_hh[l], db_ih[l], (size_t)G * 4, hipMemcpyDeviceToDevice, on));
+    if ((r = launch_reduce_slabs_unperm((const float*)(ws + w.colsum), G, S_cs, H, 1, db_ih[l], st))) return r;
+    CSN_HIP_CHECK(hipMemcpyAsync(db_hh[l], db_ih[l], (size_t)G * 4, hipMemcpyDeviceToDevice, st));
     return CSN_OK;
   };
-  // CSN_WGRAD_OVERLAP (off by default -- measured, and worse): an upper layer is done `lag` launches before the
-  // bottom one; its weight-gradient GEMMs can go to a LOWEST-priority stream of the plan right then, to fill the CUs
-  // the last launches leave free (the XCDs of the finished layer's groups + the 8 spare CUs of the others).  On
-  // MI355X the stream priority does not keep the GEMM's workgroups off the CUs the next recurrence launch needs: its
-  // workgroups (one per CU, all of a group resident before anyone advances) wait for GEMM workgroups to retire --
-  // 14.4 vs 11.0 ms per step at cfg2.
-  bool wg_done[8] = {false, false, false, false, false, false, false, false};
-  const bool wg_overlap = NL > 1 && w.tn_scratch2 != 0 && P.opt.wgrad_overlap;
-  bool wg_side = false;
-  if (wg_overlap && (rc = side_ctx(P.sc))) return rc;
-
   PersistBwdArgs a{};
   a.error_flag = (unsigned*)(ws + w.status);
   a.B = B; a.H = H; a.T = T; a.Bpad = Bpad; a.MT = MT;
@@ -1287,24 +1223,9 @@ static int backward_persist(Plan& P, char* ws, const float* dy_last,
 #ifdef CSN_SLAB_TAGS
   if (a.data_polls && P.opt.tags_no_rearm) a.data_polls |= 4;
 #endif
-  // CSN_BWD_SINGLE_COPY (experiments library only): ONE copy of dgates (lstm_bwd_persist.hip, SINGLE) --
-  // the hand-off slabs, one per step, fragment-major, are what the GEMMs after the recurrence read, and the row-major
-  // copy is not written (4 of the 12 store instructions of a step).  Possible when every reader of dgates takes the
-  // block layout: the weight gradients on the 256 x 256 kernel (which also delivers the bias gradient), the input
-  // gradients of the upper layers inside the launch (gemm_beside.h), and nobody wants dx of layer 0.
-  const int64_t I0 = d->I;
-  const bool single = a.data_polls != 0 && P.opt.bwd_single_copy && dx == nullptr && !wg_overlap && B == Bpad &&
-                      (NL == 1 || (beside && nch > lag)) && (int64_t)T * Bpad * G * 2 < ((int64_t)1 << 31) &&
-                      gemm_tn_takes_blocked_a(G, H, TB, P.opt) && gemm_tn_takes_blocked_a(G, I0, TB, P.opt);
-  a.single_copy = single_copy = single ? 1 : 0;
-  P.dgates_copies = single ? 1 : 2;
-  if (a.data_polls) {
-    // the hand-off slabs that are polled before a kernel has armed them start as sentinel: the ring of 4, or (single
-    // copy) the slabs of steps T-1 and T-2 -- slab s <= T-3 is armed by its producers at step s+2
-    const int first = single ? (T >= 2 ? T - 2 : 0) : 0, count = single ? T - first : 4;
-    for (int l = 0; l < NL; ++l)
-      CSN_HIP_CHECK(hipMemsetAsync(ws + w.layer[l].dg_blk_all + (size_t)first * Bpad * G * 2, 0xff, (size_t)count * Bpad * G * 2, st));
-  }
+  P.dgates_copies = 2;     // hand-off slabs + the row-major copy the GEMMs read (csn_lstm_plan_dgates_copies)
+  if (a.data_polls)        // the ring of 4 hand-off slabs of every layer starts as sentinel
+    for (int l = 0; l < NL; ++l) CSN_HIP_CHECK(hipMemsetAsync(ws + w.layer[l].dg_blk_all, 0xff, (size_t)4 * Bpad * G * 2, st));
   int n_launch = 0;
   BesideGemm pending[3];           // GEMMs of the chunks finished by the previous launch
   int npending = 0;
@@ -1342,8 +1263,7 @@ static int backward_persist(Plan& P, char* ws, const float* dy_last,
       // to recur over, but the input-gradient GEMMs the previous launch left for "the next launch" still have to run
       for (int i = 0; i < npending; ++i) {
         const BesideGemm& g = pending[i];
-        if (g.a_blocked) return fail(CSN_ERR_UNSUPPORTED, "backward_persist: fragment-major dgates without a launch to carry their GEMM");
-        if ((rc = gemm_nt(g.A, g.Bt, g.bias, g.C, g.M, g.N, g.K, CSN_BF16, CSN_F32, 0, st, P.opt))) return rc;
+        if ((rc = gemm_nt(g.A, g.Bt, nullptr, g.C, g.M, g.N, g.K, CSN_BF16, CSN_F32, 0, st, P.opt))) return rc;
       }
       npending = 0;
       continue;
@@ -1363,23 +1283,13 @@ static int backward_persist(Plan& P, char* ws, const float* dy_last,
       // dx_l[chunk] = dgates_l[chunk] (interleaved K) * W_ih;  Bt = W_ih^T [I, 4H']
       const LayerWs& L = w.layer[l];
       const int t_hi = T - 1 - chk[i] * Cz, t_lo = t_hi - a.slot[i].nsteps + 1;
-      const bf16_t* Ag = (const bf16_t*)(ws + (a.single_copy ? L.dg_blk_all : L.dgates)) + (size_t)t_lo * B * G;
+      const bf16_t* Ag = (const bf16_t*)(ws + L.dgates) + (size_t)t_lo * B * G;
       float* Cg = (float*)(ws + L.dx) + (size_t)t_lo * B * H;
       const int64_t Mg = (int64_t)(t_hi - t_lo + 1) * B;
       if (beside) {
-        pending[npending++] = BesideGemm{Ag, (const bf16_t*)(ws + L.wiht), Cg, (int)Mg, H, (int)G, nullptr, nullptr, 0, a.single_copy};
+        pending[npending++] = BesideGemm{Ag, (const bf16_t*)(ws + L.wiht), Cg, (int)Mg, H, (int)G};
       } else {
         if ((rc = gemm_nt(Ag, ws + L.wiht, nullptr, Cg, Mg, H, G, CSN_BF16, CSN_F32, 0, st, P.opt))) return rc;
-      }
-    }
-    if (wg_overlap) {
-      for (int i = 0; i < ns; ++i) {
-        const int l = lay[i];
-        if (l == 0 || chk[i] != nch - 1) continue;          // layer l has just walked its last chunk (dgates_l complete)
-        if ((rc = hand_off(&P.sc, st, P.sc.wgrad))) return rc;
-        if ((rc = weight_grads(l, P.sc.wgrad, w.tn_scratch2, w.colsum2))) return rc;
-        wg_done[l] = true;
-        wg_side = true;
       }
     }
   }
@@ -1399,13 +1309,8 @@ static int backward_persist(Plan& P, char* ws, const float* dy_last,
   // (every recurrence launch has been enqueued by now: what a gradient-ready callback starts -- a collective on another
   // stream -- runs beside the remaining layers' weight-gradient GEMMs, never beside a one-workgroup-per-CU launch)
   for (int l = NL - 1; l >= 0; --l) {
-    if (wg_done[l]) continue;
-    if ((rc = weight_grads(l, st, w.tn_scratch, w.colsum))) return rc;
-    if (!wg_side) P.grads_ready(l);
-  }
-  if (wg_side) {
-    if ((rc = hand_off(&P.sc, P.sc.wgrad, st))) return rc;     // the caller's stream resumes after the side work
-    for (int l = NL - 1; l >= 0; --l) P.grads_ready(l);
+    if ((rc = weight_grads(l))) return rc;
+    P.grads_ready(l);
   }
   return CSN_OK;
 }

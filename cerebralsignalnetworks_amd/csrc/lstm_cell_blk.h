@@ -50,7 +50,7 @@ struct CellBwdArgs {
 // own chunk of timesteps (a wavefront diagonal over chunks).
 struct PersistFwdSlot {
   const bf16_t* w_blk;     // fragment-major W_hh, interleaved rows [4H, H]
-  const float* xproj;      // [T, B, 4H] interleaved (float32; bf16 when xproj_bf16)
+  const float* xproj;      // [T, B, 4H] interleaved
   bf16_t* gates;           // [T, B, 4H] interleaved, or null
   float* c_all;            // [T+1, B, H]  (slot t+1 = c_t)
   bf16_t* h_all;           // [T+1, B, H]  row-major
@@ -63,32 +63,20 @@ struct PersistFwdSlot {
   const float* bias;       // [4H] interleaved b_ih + b_hh
   int I;
   int t0, nsteps;
-  int xproj_bf16;          // N-split kernel only: xproj holds bf16 (written by the GEMM the previous launch carried)
 };
-// C[M,N] (f32) = A[M,K] * Bt[N,K]^T (+ bias[N]), bf16 operands: run by the workgroups of a weight-stationary launch
-// that have no recurrence work (gemm_beside.h)
+// C[M,N] (f32) = A[M,K] * Bt[N,K]^T, bf16 operands, row-major: run by the workgroups of a weight-stationary backward
+// launch that have no recurrence work (gemm_beside.h)
 struct BesideGemm {
   const bf16_t* A;
   const bf16_t* Bt;
   float* C;
   int M, N, K;
-  const float* bias;       // [N] added to every row, or null
-  unsigned* counter;       // atomic tile counter (zeroed by the host), or null: tiles dealt round-robin to the workers
-  int c_bf16;              // != 0: C is bf16 (the forward's input projection, consumed only by lstm_fwd_ns.hip)
-  int a_blocked;           // != 0: A is in the fragment-major 16 x 32 block layout (blk_offset; M % 16 == 0), not row-major
 };
 static constexpr int kPersistFlagLine = 32;    // one 128-byte line per (slot, M-tile): at most 32 slices
 struct PersistFwdArgs {
   PersistFwdSlot slot[4];
   int nslots;
-  // N-split kernel only (lstm_fwd_ns.hip): input-projection GEMMs of the chunks the layers below finished one
-  // launch ago, walked by the workgroups of the launch that have no recurrence work; the grid is 8 * grid_slices
-  BesideGemm gemm[3];
-  int ngemm;
-  int grid_slices;
-  int half_tiles;          // K2 x N2 body pipelined over 32-row halves: the flag lines are [T+1][MT][2][line]
   int data_polls;          // K-split kernel: hand-off by sentinel data in a ring of 4 slabs (no flags, no store drain); the host fills the 4 slabs with 0xff per forward
-  int chains;              // 4: the wave-specialised body (lstm_fwd_ws.hip), four 16-row chains per tile: flag lines [T+1][MT][4][line]
   // xcd_groups != 0: 1-D grid of 8 * nslices workgroups; the workgroups that share (blockIdx.x % 8) form one
   // hand-off group (a slot's M-tile) -- under the round-robin dispatch they share an XCD, which each group
   // verifies at run time through agree[group] (zeroed, one set of 8 words per launch) before it uses the
@@ -104,7 +92,6 @@ bool fwd_persist_supported(int B, int H, int dtype, const Options& opt);
 bool fwd_ns_supported(int B, int H, int dtype, const Options& opt);
 int fwd_ns_slices(int H);
 int launch_fwd_ns(const PersistFwdArgs& a, hipStream_t st);
-int launch_fwd_ws(const PersistFwdArgs& a, hipStream_t st);   // H = 768, a.chains == 4
 int fwd_persist_slices(int H);   // workgroups per hand-off group
 int launch_fwd_persist(const PersistFwdArgs& a, hipStream_t st);
 
@@ -132,9 +119,6 @@ struct PersistBwdArgs {
   int xcd_groups;
   int rotate;              // != 0: each workgroup walks the k-blocks from its own offset (changes the summation order)
   int data_polls;          // hand-off by sentinel data in a ring of 4 slabs (the host fills them with 0xff per backward)
-  int single_copy;         // (experiments library) != 0: ONE copy of dgates -- every step's hand-off slab has an address of its own (dg_blk_all[t],
-                           // sentinel-armed two steps ahead by its producer) and IS what the weight- and input-gradient
-                           // GEMMs read; the row-major copy is not written (4 of the 12 store instructions of a step)
   unsigned long long* agree;
   unsigned* error_flag;
   int B, H, T, Bpad, MT;

@@ -26,14 +26,12 @@
 // identical to lstm_fwd_persist.hip (L2-local inside an XCD-resident group, verified per launch; placement-
 // independent write-through otherwise).
 //
-// 32 units per workgroup: H/32 workgroups per hand-off group (24 at H = 768, leaving 8 CUs per XCD to the layer-1
-// input-projection GEMM carried by the launch, see gemm_beside.h; 32 at H = 1024).
+// 32 units per workgroup: H/32 workgroups per hand-off group (32 at H = 1024).
 #include <algorithm>
 
 #include "csn_common.h"
 #include "lstm_cell_common.h"
 #include "lstm_cell_blk.h"
-#include "gemm_beside.h"
 #include "lstm_ns_util.h"
 
 #ifdef CSN_PSTAMPS
@@ -161,11 +159,10 @@ __device__ __forceinline__ void ns_recurrence(const PersistFwdArgs& a, const Per
   // (8 x 16 B), the fused layer 0 the x fragments of all 64 rows (16 x 16 B).  Buffer loads: the block offsets are
   // wave-uniform (SGPRs), the per-lane part is one register per row group.
   f32x4 nxt[P];
-  const bool xbf = !FUSED && __builtin_amdgcn_readfirstlane(S.xproj_bf16) != 0;
   const unsigned xslab = FUSED ? (unsigned)a.Bpad * (unsigned)S.I : 0u;
   // Buffer resources are based at THIS LAUNCH's first step and sized for its steps: byte offsets inside them are 32-bit
   // (the float32 projection is 4 MB per step at B = 256, H = 1024 -- 4 GiB, where offsets from step 0 wrapped, at T = 1024)
-  const size_t in_step_bytes = FUSED ? (size_t)xslab * 2 : (size_t)B * H * (xbf ? 8 : 16);
+  const size_t in_step_bytes = FUSED ? (size_t)xslab * 2 : (size_t)B * H * 16;
   const __amdgpu_buffer_rsrc_t in_rsrc = __builtin_amdgcn_make_buffer_rsrc(
       (void*)ns_uniform((FUSED ? (const char*)S.x_blk : (const char*)S.xproj) + (size_t)t_first * in_step_bytes), 0,
       __builtin_amdgcn_readfirstlane((int)((size_t)nsteps * in_step_bytes)), 0x00020000);
@@ -180,17 +177,6 @@ __device__ __forceinline__ void ns_recurrence(const PersistFwdArgs& a, const Per
       for (int rg = 0; rg < 4; ++rg)
 #pragma unroll
         for (int kb = 0; kb < 4; ++kb) nxt[rg * 4 + kb] = ns_bload_nt_f32x4(in_rsrc, lane * 16 + (rg * 4 + kb) * 1024, sbase);
-    } else if (xbf) {
-      // bf16 projection: 8 bytes per cell, widened on arrival
-      const int sbase = __builtin_amdgcn_readfirstlane((int)((size_t)(t - t_first) * B * 8 * H));
-#pragma unroll
-      for (int rg = 0; rg < 4; ++rg)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const nu32x2 v = __builtin_amdgcn_raw_buffer_load_b64(in_rsrc, (xvoff[rg] >> 1) + j * 32, sbase, 2);
-          nxt[rg * 2 + j] = (f32x4){__builtin_bit_cast(float, v[0] << 16), __builtin_bit_cast(float, v[0] & 0xffff0000u),
-                                    __builtin_bit_cast(float, v[1] << 16), __builtin_bit_cast(float, v[1] & 0xffff0000u)};
-        }
     } else {
       const int sbase = __builtin_amdgcn_readfirstlane((int)((size_t)(t - t_first) * B * 16 * H));
 #pragma unroll
@@ -241,6 +227,11 @@ __device__ __forceinline__ void ns_recurrence(const PersistFwdArgs& a, const Per
     __builtin_amdgcn_sched_barrier(0);
   };
   if constexpr (FUSED) start_from_x();        // (the launch's first step: the one place that waits for x)
+  // Everything loaded so far (the weights, the first step's input) lands before the step loop, in a wait the compiler can
+  // see -- the inline-asm waits of this file are opaque to it.  Without one, the first MFMA that reads the AGPR-resident
+  // weights INSIDE the loop got a vmcnt wait of the compiler's own, which in the plain layers held every step's first MFMA
+  // group behind all four h groups (cfg4: 258 instead of 253 us per forward launch).
+  __builtin_amdgcn_s_waitcnt(0x0f70);         // vmcnt(0); expcnt, lgkmcnt not waited for
 
   for (int s = 0; s < nsteps; ++s) {
     const int t = t_first + s;
@@ -472,16 +463,9 @@ __device__ __forceinline__ void ns_recurrence(const PersistFwdArgs& a, const Per
   }
 }
 
-#ifdef CSN_EXPERIMENTS
-#include "experiments/lstm_fwd_kn.inc.h"
-#endif
-
-static constexpr int kKnLdsExtra = 4 * 6144 + 64 * (208 + 112 + 80);      // exchange + transpose area behind the h tile
-
 // FUSE: may a slot of this launch be the fused layer 0?  Whether a workgroup's slot IS fused is a run-time,
 // workgroup-uniform fact (one launch advances layer 0 and the layers above it).
-// KN: the K2 x N2 body (24 units per workgroup) instead of the N-split one (32 units)
-template <int KB, bool FUSE, bool KN>
+template <int KB, bool FUSE>
 __global__ void __launch_bounds__(256) lstm_fwd_ns_kernel(PersistFwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];   // [4 rg][KB] 1 KB blocks of h, then the 28 KB transpose
   const int H = a.H, MT = a.MT;
@@ -489,25 +473,12 @@ __global__ void __launch_bounds__(256) lstm_fwd_ns_kernel(PersistFwdArgs a) {
 #ifdef CSN_PSTAMPS
   const unsigned long long t_entry_ = wall_clock64();
 #endif
-  const int nslices = KN ? H / 24 : H >> 5;
+  const int nslices = H >> 5;
   int grp, slice;
   if (a.xcd_groups) {
     grp = blockIdx.x & 7;
     slice = blockIdx.x >> 3;
-    const int ngroups = a.nslots * MT, gs = a.grid_slices;
-    if (grp >= ngroups || slice >= nslices) {
-      // no recurrence work for this workgroup: it walks the tiles of the launch's input-projection GEMMs (the chunk
-      // the layer below finished one launch ago); workers of one XCD get consecutive indices
-      if (a.ngemm > 0) {
-        const int idle_here = gs - nslices;
-        const unsigned base = grp <= ngroups ? (unsigned)(grp * idle_here)
-                                             : (unsigned)(ngroups * idle_here + (grp - ngroups) * gs);
-        const unsigned worker = base + (unsigned)(grp < ngroups ? slice - nslices : slice);
-        const unsigned nworkers = (unsigned)(ngroups * idle_here + (8 - ngroups) * gs);
-        for (int i = 0; i < a.ngemm; ++i) beside_gemm_tiles(a.gemm[i], smem, worker, nworkers);
-      }
-      return;
-    }
+    if (grp >= a.nslots * MT) return;      // an XCD without a hand-off group: no work for this workgroup
   } else {
     grp = blockIdx.x / nslices;
     slice = blockIdx.x % nslices;
@@ -545,28 +516,11 @@ __global__ void __launch_bounds__(256) lstm_fwd_ns_kernel(PersistFwdArgs a) {
   bool done = false;
   if constexpr (FUSE) {
     if (__builtin_amdgcn_readfirstlane((int)(S.x_blk != nullptr)) != 0) {
-#ifdef CSN_EXPERIMENTS
-      if constexpr (KN) {
-        if (a.half_tiles) kp_recurrence<KB, true>(a, S, smem, slice, mt, local);
-        else kn_recurrence<KB, true>(a, S, smem, slice, mt, local);
-      } else
-#endif
-        ns_recurrence<KB, true>(a, S, smem, slice, mt, local);
+      ns_recurrence<KB, true>(a, S, smem, slice, mt, local);
       done = true;
     }
   }
-  if (!done) {
-#ifdef CSN_EXPERIMENTS
-    if constexpr (KN) {
-      if (a.half_tiles) kp_recurrence<KB, false>(a, S, smem, slice, mt, local);
-      else kn_recurrence<KB, false>(a, S, smem, slice, mt, local);
-    } else
-#endif
-      ns_recurrence<KB, false>(a, S, smem, slice, mt, local);
-  }
-  // chunk finished: take tiles of the launch's GEMMs that are still unclaimed (counter mode only)
-  for (int i = 0; i < a.ngemm; ++i)
-    if (a.gemm[i].counter != nullptr) beside_gemm_tiles(a.gemm[i], smem, 0u, 1u);
+  if (!done) ns_recurrence<KB, false>(a, S, smem, slice, mt, local);
 }
 
 static bool ns_device_has_256_cus() {
@@ -575,51 +529,36 @@ static bool ns_device_has_256_cus() {
   return hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus >= 256;
 }
 
-int fwd_ns_slices(int H);
 // all workgroups of a launch co-resident, each alone on its CU
 bool fwd_ns_supported(int B, int H, int dtype, const Options& opt) {
   if (dtype != CSN_BF16 || opt.no_persist || opt.fwd_ksplit) return false;
   if (!(H == 128 || H == 256 || H == 384 || H == 512 || H == 768 || H == 1024)) return false;
   // where both forward kernels exist they are equally fast (cfg2: 11.2 vs 11.0 ms per step, profiles/r02_c): the
   // K-split one stays the default there; the N-split one is the only weight-stationary forward at H = 1024
-  if (H != 1024 && !opt.fwd_nsplit && !(opt.fwd_ws && H == 768)) return false;
-#ifndef CSN_EXPERIMENTS
-  if (H == 768) return false;      // the K2 x N2 body lives in `make experiments` only; the K-split kernel is the one at H = 768
-#endif
+  if (H != 1024 && !opt.fwd_nsplit) return false;
+  if (H == 768) return false;      // no N-split instantiation at H = 768: the K-split kernel is the one there
   if (!ns_device_has_256_cus()) return false;
   return fwd_ns_slices(H) * ((B + 63) / 64) <= 128;
 }
 
-template <int KB, bool FUSE, bool KN>
+template <int KB, bool FUSE>
 static int launch_ns_t(const PersistFwdArgs& a, hipStream_t st) {
-  size_t lds = (size_t)KB * 4096 + (KN ? kKnLdsExtra : kNsStageBytes);
-  if (int rc = ensure_dyn_lds<&lstm_fwd_ns_kernel<KB, FUSE, KN>>((int)(lds > kBesideLdsBytes + 64 ? lds : kBesideLdsBytes + 64))) return rc;
-  const unsigned nslices = (unsigned)(KN ? a.H / 24 : a.H / 32);
-  PersistFwdArgs b = a;
-  if (b.xcd_groups) {
-    if (b.ngemm > 0) {
-      if (lds < kBesideLdsBytes + 64) lds = kBesideLdsBytes + 64;     // the GEMM workers' staging ring + the claim word
-      if (b.grid_slices < (int)nslices) b.grid_slices = (int)nslices;
-    } else {
-      b.grid_slices = (int)nslices;
-    }
-  }
-  const unsigned grid = b.xcd_groups ? 8u * (unsigned)b.grid_slices : nslices * (unsigned)(b.MT * b.nslots);
-  lstm_fwd_ns_kernel<KB, FUSE, KN><<<dim3(grid), 256, lds, st>>>(b);
+  const size_t lds = (size_t)KB * 4096 + kNsStageBytes;
+  if (int rc = ensure_dyn_lds<&lstm_fwd_ns_kernel<KB, FUSE>>((int)lds)) return rc;
+  const unsigned nslices = (unsigned)(a.H / 32);
+  const unsigned grid = a.xcd_groups ? 8u * nslices : nslices * (unsigned)(a.MT * a.nslots);
+  lstm_fwd_ns_kernel<KB, FUSE><<<dim3(grid), 256, lds, st>>>(a);
   CSN_LAUNCH_CHECK();
   return CSN_OK;
 }
 
-// which body runs: the K2 x N2 one at H = 768 (32 workgroups per group), else the N-split one
-static bool ns_use_kn(int H) { return H == 768; }
-int fwd_ns_slices(int H) { return ns_use_kn(H) ? H / 24 : H / 32; }
+int fwd_ns_slices(int H) { return H / 32; }
 
 int launch_fwd_ns(const PersistFwdArgs& a, hipStream_t st) {
-  CSN_REQUIRE(a.nslots >= (a.ngemm > 0 ? 0 : 1) && a.nslots <= 4 && a.MT >= 1, "launch_fwd_ns: bad slot count");
+  CSN_REQUIRE(a.nslots >= 1 && a.nslots <= 4 && a.MT >= 1, "launch_fwd_ns: bad slot count");
   const int ns = fwd_ns_slices(a.H);
   CSN_REQUIRE(ns <= kPersistFlagLine, "launch_fwd_ns: H=%d gives %d slices", a.H, ns);
   if (a.xcd_groups) CSN_REQUIRE(a.nslots * a.MT <= 8, "launch_fwd_ns: groups do not fit 8 XCDs");
-  CSN_REQUIRE(a.ngemm >= 0 && a.ngemm <= 3 && (a.ngemm == 0 || a.xcd_groups), "launch_fwd_ns: bad GEMM list");
   bool fused = false;          // does any slot of the launch multiply x_t itself?
   for (int i = 0; i < a.nslots; ++i) {
     fused = fused || a.slot[i].x_blk != nullptr;
@@ -634,12 +573,9 @@ int launch_fwd_ns(const PersistFwdArgs& a, hipStream_t st) {
     CSN_REQUIRE(worst < (1ull << 32), "launch_fwd_ns: %llu steps per launch at B=%d H=%d address %llu bytes from the launch's base "
                 "(32-bit offsets): lower CSN_LSTM_CHUNK", n, a.B, a.H, worst);
   }
-#ifdef CSN_EXPERIMENTS
-  if (a.H == 768) return fused ? launch_ns_t<24, true, true>(a, st) : launch_ns_t<24, false, true>(a, st);
-#endif
 #define CSN_NS_CASE(KBV)                                                   \
   case KBV * 32:                                                           \
-    return fused ? launch_ns_t<KBV, true, false>(a, st) : launch_ns_t<KBV, false, false>(a, st)
+    return fused ? launch_ns_t<KBV, true>(a, st) : launch_ns_t<KBV, false>(a, st)
   switch (a.H) {
     CSN_NS_CASE(4);
     CSN_NS_CASE(8);

@@ -1,4 +1,4 @@
-// Device helpers shared by the N-split family of weight-stationary forward kernels (lstm_fwd_ns.hip, lstm_fwd_ws.hip).
+// Device helpers of the N-split weight-stationary forward kernel (lstm_fwd_ns.hip).
 #pragma once
 #include "csn_common.h"
 
@@ -8,7 +8,6 @@ static constexpr unsigned long long kNsSpinTimeoutTicks = 20000000ull;   // 0.2 
 static constexpr int kNsStageBytes = 64 * (288 + 144 + 80);               // padded rows of gates (bf16 x 4) + c (f32) + h (bf16) of 64 x 32 cells
 
 typedef __attribute__((ext_vector_type(4))) unsigned nu32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned nu32x2;
 
 // (OFF: instruction offset, added to the global AND the LDS address: four consecutive 1 KB pieces share one M0 / soffset;
 // AUX: cache policy bits of the load -- 16 = sc1 for hand-off data, 0 = default for data that should stay in L2)

@@ -105,9 +105,9 @@ size_t csn_lstm_plan_workspace_bytes(const csnLstmPlan* plan);
  * block of batch rows; its workspace also holds fragment-major copies of h and of the gate gradients). */
 int csn_lstm_plan_path(const csnLstmPlan* plan);
 /* Copies of the gate gradients the plan's LAST csn_lstm_backward wrote per step: 2 = the fragment-major hand-off slab
- * and a row-major copy for the GEMMs behind the recurrence (always, in this library); 1 = the hand-off slabs alone,
- * read in place by those GEMMs (experiments library under CSN_BWD_SINGLE_COPY); 0 = no backward has
- * run, or a path without hand-off slabs.  Diagnostic: lets a test see which form it compared. */
+ * and a row-major copy for the GEMMs behind the recurrence, which every weight-stationary bf16 backward writes; 0 = no
+ * backward has run, or a path without hand-off slabs.  Kept for ABI stability: it never returns anything else (the
+ * single-copy form that returned 1 was removed). */
 int csn_lstm_plan_dgates_copies(const csnLstmPlan* plan);
 /* Name of the device function that advances the recurrence on this plan's path: which = 0 forward, 1 backward
  * ("lstm_fwd_persist_kernel", "lstm_fwd_ns_kernel", "lstm_bwd_persist_kernel", "lstm_cell_fwd_il_kernel", ... -- the

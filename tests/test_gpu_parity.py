@@ -451,7 +451,7 @@ def test_end_to_end_step_loss_within_1e4(cuda):
 # ----------------------------------------------------------------------------------------------
 # bf16 fast path ("il": fragment-major, gate-interleaved, layer wavefront, side-stream GEMMs)
 # ----------------------------------------------------------------------------------------------
-def _run_lstm(p, x, dy_all, dy_last, C, H, L, dtype, cuda, env=None, want_dx=True, info=None):
+def _run_lstm(p, x, dy_all, dy_last, C, H, L, dtype, cuda, env=None, want_dx=True):
     env = env or {}
     old = {k: os.environ.get(k) for k in env}
     os.environ.update(env)
@@ -467,8 +467,6 @@ def _run_lstm(p, x, dy_all, dy_last, C, H, L, dtype, cuda, env=None, want_dx=Tru
         out = dict(y_all=y_all.detach().cpu().numpy())
         if want_dx:
             out["dx"] = xt.grad.cpu().numpy()
-        if info is not None:
-            info["dgates_copies"] = [plan.dgates_copies() for plan in m.lstm.all_plans()]
         for n, q in m.lstm.named_parameters():
             out[n] = q.grad.cpu().numpy()
         return out
@@ -574,8 +572,7 @@ def test_fast_path_matches_oracle_and_v1(cuda, B, T, C, H, L, chunk):
     norot = run(**exact)
     # the N-split forward kernel (lstm_fwd_ns.hip; the default at H = 1024, behind CSN_FWD_NSPLIT at H <= 512): one launch
     # per layer on its own stream gives the bits of the grouped launch, and it agrees with the K-split kernel to bf16
-    # rounding.  (Its losing variants -- K2 x N2 body at H = 768, half-pipelined, GEMM carried inside, wave-specialised
-    # forward -- live in `make experiments` and tests/test_gpu_experiments.py, outside the product library.)
+    # rounding.
     if H != 768:
         ns = run(CSN_FWD_NSPLIT="1")
         _assert_same_bits(ns["y_all"], run(CSN_FWD_NSPLIT="1", CSN_PERSIST_STREAMS="1")["y_all"], "ns streams: y_all")
@@ -1124,8 +1121,7 @@ def test_f32_weight_stationary_recurrence(cuda, B, T, C, H, L):
     dy = dy_all.astype(np.float64).copy()
     dy[:, -1] += dy_last
     dx_ref, g_ref = lstm.lstm_backward(dy, lp, saved, L)
-    names = {}
-    ws = _run_lstm(p, x, dy_all, dy_last, C, H, L, torch.float32, cuda, info=names)
+    ws = _run_lstm(p, x, dy_all, dy_last, C, H, L, torch.float32, cuda)
     per_step = _run_lstm(p, x, dy_all, dy_last, C, H, L, torch.float32, cuda, {"CSN_NO_PERSIST": "1"})
     _assert_same_bits(ws["y_all"], per_step["y_all"], "weight-stationary vs per-step float32 forward: y_all")
     for k in ws:

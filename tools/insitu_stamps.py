@@ -18,23 +18,11 @@ lib = cabi.load()
 lib.csn_debug_read_pstamps.argtypes = [ctypes.POINTER(ctypes.c_ulonglong)]
 lib.csn_debug_read_bstamps.argtypes = [ctypes.POINTER(ctypes.c_ulonglong)]
 lib.csn_debug_read_nstamps.argtypes = [ctypes.POINTER(ctypes.c_ulonglong)]
-has_ws = hasattr(lib, "csn_debug_read_wstamps")      # (wave-specialised forward: experiments library only)
-if has_ws:
-    lib.csn_debug_read_wstamps.argtypes = [ctypes.POINTER(ctypes.c_ulonglong)]
 buf = (ctypes.c_ulonglong * 16)()
 for it in range(4):
     tr.train_step(x, tg)
     torch.cuda.synchronize()
     # the stamping workgroup (blockIdx.x == 11) belongs to ONE layer's group: sums are over that layer's T steps
-    if has_ws:
-        lib.csn_debug_read_wstamps(buf)
-    if has_ws and sum(buf) != 0:
-        w = [buf[i] * 0.01 / T for i in range(16)]
-        print("step %d fwd-ws per-step us, MFMA wave 0 (4 chains): wait ready %.2f | lds reads + mfma %.2f | tiles to lds + bump %.2f | sum %.2f"
-              % (it, w[0], w[1], w[2], sum(w[:3])))
-        print("          gate wave 0 (chain 0): input wait %.2f | x mfma %.2f | wait tiles %.2f | sum+gate math %.2f | stores %.2f | drain %.2f | flag + watch next line %.2f | h tile to LDS %.2f | sum %.2f"
-              % (w[8], w[9], w[10], w[11], w[12], w[13], w[15], w[14], sum(w[8:16])), flush=True)
-        print("          shader clock during the chunk: %.0f MHz" % (100.0 * buf[5] / max(buf[6], 1)), flush=True)
     for name, fn in (("fwd-ksplit", lib.csn_debug_read_pstamps), ("fwd-nsplit", lib.csn_debug_read_nstamps),
                      ("bwd", lib.csn_debug_read_bstamps)):
         fn(buf)
