@@ -782,10 +782,17 @@ static int forward_il(Plan& P, char* ws, const float* x, int64_t xsb, int64_t xs
   const size_t Bpad = ((size_t)B + 63) / 64 * 64;
   const int Cz = P.opt.chunk, lag = 2 * Cz;
 
-  // all layout preparation in one launch (prep_multi_kernel)
+  // all layout preparation in one launch (prep_multi_kernel); a training plan with more than 6 layers has more jobs
+  // than one launch holds (1 + 5 L): a full batch is launched and a new one started -- the jobs are independent
   PrepArgs pa{};
+  int prep_rc = CSN_OK;
   auto job = [&](int kind, const float* a_, const float* b_, void* dst, int64_t n0, int64_t n1, int64_t n2, int64_t s0,
                  int64_t s1, int64_t Hh, int pr, int pk, int64_t work) {
+    if (prep_rc != CSN_OK) return;
+    if (pa.njobs == kPrepMaxJobs) {
+      if ((prep_rc = launch_prep_multi(pa, st)) != CSN_OK) return;
+      pa.njobs = 0;
+    }
     PrepJob& J = pa.job[pa.njobs++];
     J = PrepJob{kind, a_, b_, dst, n0, n1, n2, s0, s1, Hh, pr, pk, work, 0u, 0u};
   };
@@ -815,6 +822,7 @@ static int forward_il(Plan& P, char* ws, const float* x, int64_t xsb, int64_t xs
     job(kPrepBlockifyX, x, nullptr, ws + w.x_blk, B, T, d->I, xsb, xst, (int64_t)Bpad, 0, 0, (int64_t)T * Bpad * d->I / 8);
     job(kPrepBlockify, w_ih[0], nullptr, ws + w.wih0_blk, G, d->I, 0, d->I, 1, H, 1, 0, G * d->I / 8);
   }
+  if (prep_rc != CSN_OK) return prep_rc;
   if ((rc = launch_prep_multi(pa, st))) return rc;
   if (!w.fuse_x) {
     // layer 0 input projection for every step, main stream
@@ -839,6 +847,12 @@ static int forward_il(Plan& P, char* ws, const float* x, int64_t xsb, int64_t xs
       const int t = dg - lag * l;
       if (t < 0 || t >= T) continue;
       const LayerWs& L = w.layer[l];
+      if (np == 4) {       // (more than 4 layers on one diagonal, L >= 5: a second launch, the problems are independent)
+        if ((rc = launch_cell_fwd_il(a, np, st, P.opt.fwd_nk))) return rc;
+        ++n_launch;
+        n_cells += np;
+        np = 0;
+      }
       if (l > 0 && t % Cz == 0) CSN_HIP_CHECK(hipStreamWaitEvent(st, xproj_ready[(size_t)l * nch + t / Cz], 0));
       CellFwdProb& P = a.p[np++];
       P.h_prev_blk = t == 0 ? nullptr : (const bf16_t*)(ws + L.hblk[t & 1]);
@@ -1096,6 +1110,12 @@ static int backward_il(Plan& P, char* ws, const float* dy_last, const float* dy_
       const int t = T - 1 - r;
       const LayerWs& L = w.layer[l];
       const bool top = (l == NL - 1);
+      if (np == 4) {       // (more than 4 layers on one diagonal, L >= 5: a second launch, the problems are independent)
+        if ((rc = launch_cell_bwd_il(a, np, st))) return rc;
+        ++n_launch;
+        n_cells += np;
+        np = 0;
+      }
       if (!top && r % Cz == 0) CSN_HIP_CHECK(hipStreamWaitEvent(st, dx_ready[(size_t)(l + 1) * nch + r / Cz], 0));
       CellBwdProb& P = a.p[np++];
       P.dg_next_blk = (t == T - 1) ? nullptr : (const bf16_t*)(ws + L.dgblk[(t + 1) & 1]);

@@ -205,3 +205,137 @@ def init_params(input_size, hidden, num_layers, out_features, n_classes=None, se
         p["class_pred.weight"] = rng.uniform(-kc, kc, (n_classes, out_features)).astype(dtype)
         p["class_pred.bias"] = rng.uniform(-kc, kc, (n_classes,)).astype(dtype)
     return p
+
+
+# ----------------------------------------------------------------------------------------------
+# bf16-faithful emulation of the HIP kernels' bf16 path
+# ----------------------------------------------------------------------------------------------
+# The float64 oracle above rounds nothing, so the bf16 kernels can only be held to it within the ~2e-3 (of the norm)
+# that bf16 quantisation alone costs.  The functions below round exactly where the bf16 kernels round and compute in
+# float64 everywhere else, so what is left between a kernel and them is float32 accumulation order, the fast
+# exp2 / rcp activations and the bf16 rounding flips those cause -- 10-100 x less than the quantisation.
+# Rounding points (the same in every bf16 kernel: lstm_cell.hip v1 cells, lstm_cell_blk.hip per-diagonal cells,
+# lstm_fwd_persist.hip K-split, lstm_fwd_ns.hip N-split, fused x or projection GEMM, lstm_bwd_persist.hip):
+#   * x, W_ih, W_hh -> bf16 (round to nearest even, float32 -> bf16); bias = b_ih + b_hh summed in float32;
+#   * forward: the pre-activations and gates are float32 (not rounded), c is float32, h_t is rounded to bf16 and that
+#     value is the next step's recurrent operand, the next layer's input and the output (y_all / y_last);
+#   * the gates saved for the backward are the post-activation gates rounded to bf16;
+#   * backward: bf16 saved gates, tanh(c) recomputed from the float32 c, dc carried in float32, the gate gradients
+#     (dgates) rounded to bf16 -- that bf16 value feeds dh_{t-1} = dgates W_hh, dx = dgates W_ih (float32 out, the dy
+#     of the layer below), dW_ih = dgates^T inp (bf16 layer input), dW_hh = dgates^T h_{t-1} (bf16) and db.
+# With ``rounding=False`` every rounding is the identity and the results are those of lstm_forward / lstm_backward.
+
+def bf16_round(a):
+    """Round to the nearest bf16 value (ties to even) the way the kernels' ``(bf16_t)float`` cast does: the value is
+    first a float32 (what the kernel holds), then the low 16 bits are rounded away.  Returns float64.  NaN stays NaN,
+    +-inf stay, finite values past the largest bf16 round to +-inf, float32 subnormals round like any other value."""
+    f = np.ascontiguousarray(np.asarray(a, np.float64).astype(np.float32))
+    u = f.view(np.uint32).astype(np.uint64)
+    r = ((u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000).astype(np.uint32)
+    out = r.view(np.float32).astype(np.float64)
+    nan = np.isnan(f)
+    if nan.any():
+        out[nan] = np.nan
+    return out.reshape(np.shape(a))
+
+
+def f32_round(a):
+    return np.asarray(a, np.float64).astype(np.float32).astype(np.float64)
+
+
+def _rounders(rounding):
+    if rounding:
+        return bf16_round, f32_round
+    ident = lambda v: np.asarray(v, np.float64)      # noqa: E731
+    return ident, ident
+
+
+def lstm_forward_bf16(x_btc, params, num_layers, rounding=True, acc=np.float64, defect=None):
+    """Forward of the bf16 kernels (rounding points above).  x[B,T,I]; params with torch.nn.LSTM key names.
+    Returns (y[B,T,H] of the top layer -- bf16 values --, saved) for :func:`lstm_backward_bf16`.
+
+    For the tests of the tests: ``acc=np.float32`` runs the two products in float32 (a stand-in for a kernel's own
+    accumulation noise); ``defect(kind, l, t, value, hs)`` may replace the recurrent operand (kind "h_prev", value
+    h_{t-1}, hs = the layer's h of the steps before), the gates (kind "gates", value (i, f, g, o)) or the h a step
+    publishes (kind "h", value h_t); it returns the value to use."""
+    rb, rf = _rounders(rounding)
+    inp = rb(x_btc)
+    B, T, _ = inp.shape
+    saved = []
+    for l in range(num_layers):
+        w_ih = rb(params[f"weight_ih_l{l}"])
+        w_hh = rb(params[f"weight_hh_l{l}"])
+        if rounding:
+            bias = (np.asarray(params[f"bias_ih_l{l}"], np.float32) + np.asarray(params[f"bias_hh_l{l}"], np.float32)).astype(np.float64)
+        else:
+            bias = np.asarray(params[f"bias_ih_l{l}"], np.float64) + np.asarray(params[f"bias_hh_l{l}"], np.float64)
+        H = w_hh.shape[1]
+        h = np.zeros((B, H))
+        c = np.zeros((B, H))
+        hs = np.empty((B, T, H))
+        gates = np.empty((B, T, 4 * H))
+        cs = np.empty((B, T, H))
+        xp = (inp.reshape(B * T, -1).astype(acc) @ w_ih.T.astype(acc)).astype(np.float64).reshape(B, T, 4 * H)
+        w_hh_t = w_hh.T.astype(acc)
+        for t in range(T):
+            hp = h if defect is None else defect("h_prev", l, t, h, hs[:, :t])
+            a = xp[:, t] + (hp.astype(acc) @ w_hh_t).astype(np.float64) + bias
+            i = _sigmoid(a[:, 0 * H:1 * H])
+            f = _sigmoid(a[:, 1 * H:2 * H])
+            g = np.tanh(a[:, 2 * H:3 * H])
+            o = _sigmoid(a[:, 3 * H:4 * H])
+            if defect is not None:
+                i, f, g, o = defect("gates", l, t, (i, f, g, o), None)
+            c = rf(f * c + i * g)
+            h = rb(o * np.tanh(c))
+            if defect is not None:
+                h = defect("h", l, t, h, hs[:, :t])
+            hs[:, t] = h
+            cs[:, t] = c
+            gates[:, t, 0 * H:1 * H] = i
+            gates[:, t, 1 * H:2 * H] = f
+            gates[:, t, 2 * H:3 * H] = g
+            gates[:, t, 3 * H:4 * H] = o
+        saved.append(dict(inp=inp, hs=hs, cs=cs, gates=rb(gates), w_ih=w_ih, w_hh=w_hh))
+        inp = hs
+    return inp, saved
+
+
+def lstm_backward_bf16(dy_bth, saved, num_layers, rounding=True):
+    """Backward of the bf16 kernels.  dy[B,T,H] = dLoss/dy of the top layer (float32 values, as the caller hands them
+    over).  Returns (dx[B,T,I], grads with torch key names, dgates per layer [B,T,4H] (bf16 values))."""
+    rb, rf = _rounders(rounding)
+    grads, dgates = {}, {}
+    dout = np.asarray(dy_bth, np.float64)
+    for l in reversed(range(num_layers)):
+        s = saved[l]
+        inp, hs, cs, gates, w_ih, w_hh = s["inp"], s["hs"], s["cs"], s["gates"], s["w_ih"], s["w_hh"]
+        B, T, H = hs.shape
+        dh_rec = np.zeros((B, H))
+        dc_next = np.zeros((B, H))
+        da_all = np.empty((B, T, 4 * H))
+        for t in reversed(range(T)):
+            i = gates[:, t, 0 * H:1 * H]
+            f = gates[:, t, 1 * H:2 * H]
+            g = gates[:, t, 2 * H:3 * H]
+            o = gates[:, t, 3 * H:4 * H]
+            c = cs[:, t]
+            c_prev = cs[:, t - 1] if t > 0 else np.zeros_like(c)
+            tc = np.tanh(c)
+            dh = dout[:, t] + dh_rec
+            do = dh * tc
+            dc = dh * o * (1.0 - tc * tc) + dc_next
+            da = rb(np.concatenate([dc * g * i * (1 - i), dc * c_prev * f * (1 - f), dc * i * (1 - g * g),
+                                    do * o * (1 - o)], axis=1))
+            da_all[:, t] = da
+            dh_rec = da @ w_hh
+            dc_next = rf(dc * f)
+        da2 = da_all.reshape(B * T, 4 * H)
+        h_prev = np.concatenate([np.zeros((B, 1, H)), hs[:, :-1]], axis=1).reshape(B * T, H)
+        grads[f"weight_ih_l{l}"] = da2.T @ inp.reshape(B * T, -1)
+        grads[f"weight_hh_l{l}"] = da2.T @ h_prev
+        grads[f"bias_ih_l{l}"] = da2.sum(axis=0)
+        grads[f"bias_hh_l{l}"] = da2.sum(axis=0)
+        dgates[l] = da_all
+        dout = rf(da2 @ w_ih).reshape(B, T, -1)
+    return dout, grads, dgates

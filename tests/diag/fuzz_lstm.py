@@ -1,5 +1,6 @@
-"""Randomised LSTM plans (both dtypes, 1-4 layers, odd batch / length / channel counts, hidden sizes on and off the
-weight-stationary list, chunk lengths, with and without per-step output gradients and dx) against the float64 oracle.
+"""Randomised LSTM plans (both dtypes, 1-8 layers, odd batch / length / channel counts, hidden sizes on and off the
+weight-stationary list, chunk lengths, with and without per-step output gradients and dx) against the float64 oracle, and the bf16 cases also
+against the bf16-faithful emulator (bounds oracle.compare.BF16_EMU_BOUNDS).
 A bug hunt: one line per case, exit code 1 on a failure.      python tests/diag/fuzz_lstm.py [cases] [seed]"""
 import os
 import sys
@@ -11,7 +12,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-from oracle import lstm      # noqa: E402  (tools/ and tests/ may use the oracle; the product never does)
+from oracle import compare, lstm      # noqa: E402  (tools/ and tests/ may use the oracle; the product never does)
 from cerebralsignalnetworks_amd import Model      # noqa: E402
 
 dev = torch.device("cuda:0")
@@ -30,7 +31,7 @@ for i in range(n_cases):
     B = int(rng.integers(1, 40 if big else 140))
     T = int(rng.integers(1, 40 if big else 75))
     C = int(rng.choice([1, 3, 8, 16, 24, 32, 64, 100, 128, 130]))
-    L = int(rng.integers(1, 5))
+    L = int(rng.integers(1, 9))
     chunk = str(int(rng.choice([1, 2, 3, 4, 7, 8, 16, 32, 64])))
     want_all, want_dx = bool(rng.integers(0, 2)), bool(rng.integers(0, 2))
     dt = torch.bfloat16 if rng.integers(0, 3) else torch.float32
@@ -70,6 +71,21 @@ for i in range(n_cases):
         tol = 2e-2 if dt == torch.bfloat16 else 2e-5
         worst = max(errs, key=errs.get)
         ok = all(s == 0 for s in st) and all(np.isfinite(v) and v < tol for v in errs.values())
+        if dt == torch.bfloat16:
+            ye, se = lstm.lstm_forward_bf16(x, lp, L)
+            dxe, ge, _ = lstm.lstm_backward_bf16(dy, se, L)
+            got = {"y_last": y_last.detach().cpu().numpy(), **{n: q.grad.cpu().numpy() for n, q in m.lstm.named_parameters()}}
+            want = {"y_last": ye[:, -1], "y_all": ye, "dx": dxe, **ge}
+            if want_all:
+                got["y_all"] = y_all.detach().cpu().numpy()
+            if want_dx:
+                got["dx"] = xt.grad.cpu().numpy()
+            for k, v in got.items():
+                try:
+                    compare.check(k, v, want[k], *compare.bf16_emu_bound(k), layout=compare.layout_of(k))
+                except AssertionError as e:
+                    print(f"  emulator: {e}", flush=True)
+                    ok = False
         print(f"{'ok  ' if ok else 'FAIL'} {name}: path {[pl.path() for pl in m.lstm.all_plans()]} worst {worst} {errs[worst]:.2e} status {st}", flush=True)
         bad += 0 if ok else 1
     except Exception as e:      # noqa: BLE001

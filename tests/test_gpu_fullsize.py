@@ -150,6 +150,28 @@ def test_training_step_matches_reference_fixture(cuda, golden, tag, dtype):
         assert errs["loss_abs"] < b["loss"], errs
         for n, e in errs["grad_rel"].items():
             assert e < b["grad"], (n, e, errs)
+        _check_bf16_emulator(p, x8, tgt8, L, f[:B8], dx[:B8], grads, tag)
+
+
+def _check_bf16_emulator(p, x8, tgt8, L, feat, dx, grads, tag):
+    """The 8 distinct segments against the bf16-faithful emulator (oracle.lstm.lstm_forward_bf16 / lstm_backward_bf16, bounds
+    oracle.compare.BF16_EMU_BOUNDS).  The batch is 32 copies of them and the loss a mean over the batch: the LSTM gradients
+    equal those of the 8-segment loss, the input gradient of a row is 1/32 of it (exact: a power of 2)."""
+    from oracle import compare
+    lp = {k[len("lstm."):]: v for k, v in p.items() if k.startswith("lstm.")}
+    y, saved = lstm.lstm_forward_bf16(x8, lp, L)
+    wf = np.asarray(p["fc.weight"], np.float64)
+    feat_e = y[:, -1] @ wf.T + np.asarray(p["fc.bias"], np.float64)
+    dy = np.zeros(y.shape)
+    dy[:, -1] = losses.cosine_similarity_loss_grad(feat_e, tgt8) @ wf
+    dx_e, g_e, _ = lstm.lstm_backward_bf16(dy, saved, L)
+    got = {"feat": feat, "dx": dx * COPIES, **{n: grads["lstm." + n] for n in g_e}}
+    want = {"feat": feat_e, "dx": dx_e, **g_e}
+    measured = {k: compare.errors(v, want[k]) for k, v in got.items()}
+    _write_report(f"emulator_{tag}_bf16.json", measured)
+    print(f"measured {tag} bf16 vs emulator (rel, elem):", measured)
+    for k, v in got.items():
+        compare.check(f"{tag} {k}", v, want[k], *compare.bf16_emu_bound(k), layout="bh" if k == "feat" else compare.layout_of(k))
 
 
 def test_cfg2_three_layers_stays_co_resident(cuda):

@@ -503,6 +503,18 @@ def test_short_sequences_and_tiny_batches(cuda, B, T, C, H, L):
         assert _rel(out["y_all"], y) < tol and _rel(out["dx"], dx_ref) < tol, (dt, _rel(out["y_all"], y), _rel(out["dx"], dx_ref))
         for n, gref in g_ref.items():
             assert _rel(out[n], gref) < tol, (dt, n, _rel(out[n], gref))
+        if dt == torch.bfloat16:
+            _check_bf16_emulator(p, x, dy_all, dy_last, L, out, f"B{B} T{T} H{H} L{L}")
+
+
+def _check_bf16_emulator(p, x, dy_all, dy_last, L, out, what):
+    """Every output of a bf16 run (_run_lstm) against the bf16-faithful emulator, bounds oracle.compare.BF16_EMU_BOUNDS."""
+    from oracle import compare
+    want = _emu_case(p, x, dy_all, dy_last, L, True)
+    print(f"measured bf16 vs emulator {what} (rel/elem): " +
+          " ".join(f"{k} {r:.2e}/{e:.2e}" for k, (r, e) in ((k, compare.errors(v, want[k])) for k, v in out.items())))
+    for k, v in out.items():
+        compare.check(f"{what}: {k}", v, want[k], *compare.bf16_emu_bound(k), layout=compare.layout_of(k))
 
 
 def _assert_same_bits(a, b, what):
@@ -593,6 +605,8 @@ def test_fast_path_matches_oracle_and_v1(cuda, B, T, C, H, L, chunk):
         # same bf16 arithmetic, different layouts / activations: much closer to each other than to f64
         assert _rel(fast[k], slow[k]) < 2e-2, (k, _rel(fast[k], slow[k]))
     assert np.abs(fast["y_all"] - slow["y_all"]).max() < 2e-2
+    _check_bf16_emulator(p, x, dy_all, dy_last, L, fast, f"default path B{B} T{T} H{H} L{L} chunk {chunk}")
+    _check_bf16_emulator(p, x, dy_all, dy_last, L, slow, f"CSN_CELL_V1 B{B} T{T} H{H} L{L}")
 
 
 def test_cli_spampinato_trainer_surface(cuda, tmp_path):
@@ -1184,3 +1198,163 @@ def test_two_weight_stationary_plans_on_two_streams(cuda, dt):
     out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "diag", "two_streams.py"), "4", dt],
                          capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-2000:]
+
+
+# ----------------------------------------------------------------------------------------------
+# bf16 paths against the bf16-faithful emulator (oracle.lstm.lstm_forward_bf16 / lstm_backward_bf16)
+# ----------------------------------------------------------------------------------------------
+# The emulator rounds where the kernels round, so what separates a kernel from it is float32 accumulation order, the
+# fast activations and the bf16 rounding flips they cause.  The bounds (oracle.compare.BF16_EMU_BOUNDS, 2 x measured, the
+# measurements are listed there) are 6 - 7 x tighter in the norm than the float64 bounds above and per element 2 - 6 x;
+# tight enough for a stale hand-off of one row tile at one step, a stale unit slice or a wrong gate mapping in one slice,
+# which the float64 bounds pass (tests/test_oracle_bf16_cpu.py checks both).  The saturated case has bounds of its own.
+def _emu_case(p, x, dy_all, dy_last, L, want_all):
+    lp = {k[len("lstm."):]: v for k, v in p.items() if k.startswith("lstm.")}
+    y, saved = lstm.lstm_forward_bf16(x, lp, L)
+    dy = np.zeros(y.shape) if dy_all is None else dy_all.astype(np.float64)
+    dy[:, -1] += dy_last
+    dx, g, _ = lstm.lstm_backward_bf16(dy, saved, L)
+    want = dict(y_last=y[:, -1], dx=dx, **{k: v for k, v in g.items()})
+    if want_all:
+        want["y_all"] = y
+    return want
+
+
+def _run_bf16(p, x, dy_all, dy_last, C, H, L, cuda, env, want_all, want_dx, infer):
+    """One plan of the HIP LSTM under `env`: outputs (y_last, y_all if asked, dx if asked, every gradient unless `infer`),
+    and the plan's (path, forward kernel, backward kernel)."""
+    old = {k: os.environ.get(k) for k in env}
+    os.environ.update(env)
+    try:
+        m = _model_from_params(p, C, H, L, 8, None, torch.bfloat16, cuda)
+        xt = dev_t(x, cuda).requires_grad_(want_dx and not infer)
+        out = {}
+        with torch.set_grad_enabled(not infer):
+            if want_all:
+                y_all, y_last = m.lstm(xt, want_all=True)
+                out["y_all"] = y_all.detach().cpu().numpy()
+            else:
+                y_last = m.lstm(xt)
+            out["y_last"] = y_last.detach().cpu().numpy()
+            if not infer:
+                loss = (y_last * dev_t(dy_last, cuda)).sum()
+                if want_all:
+                    loss = loss + (y_all * dev_t(dy_all, cuda)).sum()
+                loss.backward()
+        torch.cuda.synchronize()
+        plans = m.lstm.all_plans()
+        assert len(plans) == 1
+        assert plans[0].status() == 0, "an in-kernel hand-off timed out"
+        if want_dx and not infer:
+            out["dx"] = xt.grad.cpu().numpy()
+        if not infer:
+            for n, q in m.lstm.named_parameters():
+                out[n] = q.grad.cpu().numpy()
+        return out, (plans[0].path(), *plans[0].kernel_names())
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
+_V1F, _V1B = "lstm_cell_fwd_kernel", "lstm_cell_bwd_kernel"
+_KSF, _KSB = "lstm_cell_fwd_ks_kernel", "lstm_cell_bwd_ks_kernel"
+_ILF, _ILB = "lstm_cell_fwd_il_kernel", "lstm_cell_bwd_il_kernel"
+_PF, _NSF, _PB = "lstm_fwd_persist_kernel", "lstm_fwd_ns_kernel", "lstm_bwd_persist_kernel"
+# id: (B, T, I, H, L, env, options, expected (path, forward kernel, backward kernel)).  options: "all" y_all + per-step
+# gradients, "dx" input gradient, "infer" no_grad plan (forward only), "x20" inputs x 20 (saturated gates), "fb5" +5 forget
+# bias (c grows, tanh(c) saturates)
+_BF16_MATRIX = {
+    # generic cells (path 0): H not a multiple of 128, and CSN_CELL_V1 at a K-split width
+    "v1_h96": (63, 33, 24, 96, 2, {}, "all dx", (0, _V1F, _V1B)),
+    "v1_env_h256": (65, 31, 32, 256, 2, {"CSN_CELL_V1": "1"}, "dx", (0, _KSF, _KSB)),
+    # per-diagonal launches (path 1): switched, too many M-tiles for a co-resident launch, and L = 5..8 (more layers on
+    # one diagonal than one launch holds; more prep jobs than one launch holds at L >= 7)
+    "p1_env": (129, 33, 32, 256, 2, {"CSN_NO_PERSIST": "1"}, "all dx", (1, _ILF, _ILB)),
+    "p1_b512_h768": (512, 4, 128, 768, 2, {}, "all", (1, _ILF, _ILB)),
+    "p1_l5_t300": (16, 300, 24, 128, 5, {}, "all dx", (1, _ILF, _ILB)),
+    "p1_l6_chunk1": (33, 20, 16, 128, 6, {"CSN_LSTM_CHUNK": "1"}, "all dx", (1, _ILF, _ILB)),
+    "p1_l7_chunk2": (65, 40, 24, 256, 7, {"CSN_LSTM_CHUNK": "2"}, "dx", (1, _ILF, _ILB)),
+    "p1_l8_t300": (8, 300, 24, 128, 8, {}, "all dx", (1, _ILF, _ILB)),
+    # weight-stationary forward only (path 2): inference plan, and CSN_NO_PERSIST_BWD
+    "p2_infer": (65, 33, 32, 256, 2, {}, "all infer", (2, _PF, _ILB)),
+    "p2_nopersist_bwd": (64, 40, 128, 768, 2, {"CSN_NO_PERSIST_BWD": "1"}, "all dx", (2, _PF, _ILB)),
+    # weight-stationary forward and backward (path 3), per forward kernel
+    "ks_fused_h768_t32": (256, 32, 128, 768, 2, {}, "all dx", (3, _PF, _PB)),
+    "ks_fused_h256_t65": (63, 65, 32, 256, 2, {}, "dx", (3, _PF, _PB)),
+    "ks_gemm_i24_t31": (1, 31, 24, 128, 2, {}, "all dx", (3, _PF, _PB)),
+    "ks_gemm_i500_view": (8, 128, 500, 768, 2, {}, "dx", (3, _PF, _PB)),
+    "ns_fused_h1024_t33": (65, 33, 128, 1024, 2, {}, "all dx", (3, _NSF, _PB)),
+    "ns_gemm_h1024_t4": (3, 4, 24, 1024, 2, {}, "all", (3, _NSF, _PB)),
+    "ns_env_h128_t3": (129, 3, 16, 128, 2, {"CSN_FWD_NSPLIT": "1"}, "all dx", (3, _NSF, _PB)),
+    "ns_env_h512_t32": (256, 32, 128, 512, 2, {"CSN_FWD_NSPLIT": "1"}, "dx", (3, _NSF, _PB)),
+    "t1": (65, 1, 32, 256, 2, {}, "all dx", (3, _PF, _PB)),
+    "t4_l3": (63, 4, 32, 128, 3, {}, "all dx", (3, _PF, _PB)),
+    "sat_x20": (63, 40, 32, 256, 2, {}, "all dx x20", (3, _PF, _PB)),
+    "forget_bias_t200": (65, 200, 24, 128, 2, {}, "all dx fb5", (3, _PF, _PB)),
+}
+
+
+@pytest.mark.parametrize("case", list(_BF16_MATRIX))
+def test_bf16_paths_match_bf16_emulator(cuda, case):
+    from oracle import compare
+    B, T, C, H, L, env, opts, expect = _BF16_MATRIX[case]
+    opts = opts.split()
+    want_all, want_dx, infer = "all" in opts, "dx" in opts, "infer" in opts
+    rng = np.random.default_rng(B * 1000 + T * 10 + L)
+    p = lstm.init_params(C, H, L, 8, None, seed=B + T + H)
+    if "fb5" in opts:
+        for l in range(L):
+            p[f"lstm.bias_ih_l{l}"][H:2 * H] += 5.0
+    x = rng.standard_normal((B, T, C)).astype(np.float32) * (20.0 if "x20" in opts else 1.0)
+    dy_all = (rng.standard_normal((B, T, H)) * 0.1).astype(np.float32) if want_all else None
+    dy_last = rng.standard_normal((B, H)).astype(np.float32)
+    got, plan = _run_bf16(p, x, dy_all, dy_last, C, H, L, cuda, env, want_all, want_dx, infer)
+    assert plan == expect, (case, plan, expect)
+    want = _emu_case(p, x, dy_all, dy_last, L, want_all)
+    measured = {k: compare.errors(v, want[k]) for k, v in got.items()}
+    print(f"measured bf16 vs emulator {case} (rel/elem): " + " ".join(f"{k} {r:.2e}/{e:.2e}" for k, (r, e) in measured.items()))
+    for k, v in got.items():
+        compare.check(f"{case}: {k}", v, want[k], *compare.bf16_emu_bound(k, "fb5" in opts), layout=compare.layout_of(k))
+
+
+@pytest.mark.parametrize("L", [5, 6, 7, 8])
+@pytest.mark.parametrize("env,expect", [({}, (4, "lstm_fwd_f32_persist_kernel", "lstm_bwd_f32_persist_kernel")),
+                                        ({"CSN_CELL_V1": "1"}, (0, _KSF, _KSB))])
+def test_f32_paths_five_to_eight_layers(cuda, L, env, expect):
+    """The float32 paths at L = 5..8 (the ABI's range; every other test stops at 4) against the float64 oracle with the
+    float32 bounds of test_f32_weight_stationary_recurrence."""
+    B, T, C, H = 70, 37, 24, 128
+    rng = np.random.default_rng(L)
+    p = lstm.init_params(C, H, L, 8, None, seed=L)
+    lp = {k[len("lstm."):]: v for k, v in p.items() if k.startswith("lstm.")}
+    x = rng.standard_normal((B, T, C)).astype(np.float32)
+    dy_all = (rng.standard_normal((B, T, H)) * 0.1).astype(np.float32)
+    dy_last = rng.standard_normal((B, H)).astype(np.float32)
+    y, saved = lstm.lstm_forward(x, lp, L, return_saved=True)
+    dy = dy_all.astype(np.float64).copy()
+    dy[:, -1] += dy_last
+    dx_ref, g_ref = lstm.lstm_backward(dy, lp, saved, L)
+    old = {k: os.environ.get(k) for k in env}
+    os.environ.update(env)
+    try:
+        m = _model_from_params(p, C, H, L, 8, None, torch.float32, cuda)
+        xt = dev_t(x, cuda).requires_grad_(True)
+        y_all, y_last = m.lstm(xt, want_all=True)
+        ((y_all * dev_t(dy_all, cuda)).sum() + (y_last * dev_t(dy_last, cuda)).sum()).backward()
+        torch.cuda.synchronize()
+        (plan,) = m.lstm.all_plans()
+        assert plan.status() == 0
+        assert (plan.path(), *plan.kernel_names()) == expect
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+    assert np.abs(y_all.detach().cpu().numpy() - y).max() < 2e-5
+    assert _rel(xt.grad.cpu().numpy(), dx_ref) < 1e-5
+    for n, q in m.lstm.named_parameters():
+        assert _rel(q.grad.cpu().numpy(), g_ref[n]) < 1e-5, (n, _rel(q.grad.cpu().numpy(), g_ref[n]))
