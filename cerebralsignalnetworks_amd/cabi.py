@@ -15,7 +15,8 @@ LIB_PATH = os.environ.get("CSN_LIB_PATH") or os.path.join(_HERE, "lib", "libcsn_
 
 CSN_F32, CSN_BF16 = 0, 1
 STATUS_TIMEOUT, STATUS_NONFINITE, STATUS_STALE_SLOT = 1, 2, 4      # bits of csn_lstm_status_read (include/csn_hip.h)
-ABI_VERSION = 5
+ABI_VERSION = 6
+LSTM_STATE = 0x100      # csn_lstm_plan_create flag CSN_LSTM_STATE (include/csn_hip.h)
 
 _c_void_p, _c_int, _c_i64, _c_size_t, _c_float = (ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
                                                   ctypes.c_size_t, ctypes.c_float)
@@ -47,11 +48,15 @@ SIGNATURES = {
     "csn_lstm_forward": (_c_int, [_c_void_p, _c_void_p, _c_i64, _c_i64,
                                   ctypes.POINTER(_c_void_p), ctypes.POINTER(_c_void_p),
                                   ctypes.POINTER(_c_void_p), ctypes.POINTER(_c_void_p),
-                                  _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
-    "csn_lstm_backward": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                                  _c_void_p, _c_void_p,                        # h0, c0
+                                  _c_void_p, _c_void_p, _c_void_p,             # workspace, y_last, y_all
+                                  _c_void_p, _c_void_p, _c_void_p]),           # h_n, c_n, stream
+    "csn_lstm_backward": (_c_int, [_c_void_p, _c_void_p, _c_void_p,
+                                   _c_void_p, _c_void_p,                       # dh_n, dc_n
+                                   _c_void_p,
                                    ctypes.POINTER(_c_void_p), ctypes.POINTER(_c_void_p),
                                    ctypes.POINTER(_c_void_p), ctypes.POINTER(_c_void_p),
-                                   _c_void_p, _c_void_p]),
+                                   _c_void_p, _c_void_p, _c_void_p, _c_void_p]),   # dx, dh0, dc0, stream
     "csn_lstm_workspace_init": (_c_int, [_c_void_p, _c_void_p, _c_void_p]),
     "csn_lstm_status_clear": (_c_int, [_c_void_p, _c_void_p, _c_void_p]),
     "csn_lstm_status_read": (_c_int, [_c_void_p, _c_void_p, ctypes.POINTER(_c_int)]),
@@ -231,14 +236,18 @@ class LstmPlan:
     -- all per plan, the library has no global state) + one workspace; forward()/backward() enqueue on the
     current stream."""
 
-    def __init__(self, B, T, I, H, L, dtype, device, training=True):
+    def __init__(self, B, T, I, H, L, dtype, device, training=True, state=False):
+        """state=True: a CSN_LSTM_STATE plan, which takes the state keywords of forward() / backward() (and runs the
+        per-step cell kernels, path 0 or 1)."""
         self.desc = LstmDesc(B, T, I, H, L, _dt(dtype))
         self.training = bool(training)
+        self.state = bool(state)
         self.device = torch.device(device)
         lib = load()
         handle = _c_void_p()
         with torch.cuda.device(self.device):
-            _check(lib.csn_lstm_plan_create(ctypes.byref(self.desc), int(self.training), ctypes.byref(handle)))
+            _check(lib.csn_lstm_plan_create(ctypes.byref(self.desc), int(self.training) | (LSTM_STATE if self.state else 0),
+                                            ctypes.byref(handle)))
         self._plan = handle
         nbytes = lib.csn_lstm_plan_workspace_bytes(self._plan)
         self.workspace = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
@@ -255,7 +264,7 @@ class LstmPlan:
 
     def key(self):
         d = self.desc
-        return (d.B, d.T, d.I, d.H, d.L, d.dtype, self.training)
+        return (d.B, d.T, d.I, d.H, d.L, d.dtype, self.training) + ((True,) if self.state else ())
 
     def path(self):
         """0 generic cells, 1 per-diagonal bf16 launches, 2 weight-stationary forward, 3 + weight-stationary backward, 4 the
@@ -281,7 +290,9 @@ class LstmPlan:
         """Copies of the gate gradients the last backward wrote per step (csn_hip.h): 2, or 0 before any backward."""
         return load().csn_lstm_plan_dgates_copies(self._plan)
 
-    def forward(self, x_bti, w_ih, w_hh, b_ih, b_hh, want_all=False):
+    def forward(self, x_bti, w_ih, w_hh, b_ih, b_hh, want_all=False, h0=None, c0=None, want_state=False):
+        """-> (y_last, y_all); with want_state=True -> (y_last, y_all, h_n, c_n).  h0 / c0: [L,B,H] initial state or
+        None (zeros); the state keywords need a plan created with state=True."""
         d = self.desc
         _need_cuda(x_bti)
         if x_bti.dtype != torch.float32 or x_bti.stride(2) != 1:
@@ -293,22 +304,44 @@ class LstmPlan:
         for group in ws:
             for p in group:
                 assert p.dtype == torch.float32 and p.is_contiguous() and p.is_cuda
+        h0, c0 = self._state_in(h0), self._state_in(c0)
+        h_n = torch.empty((d.L, d.B, d.H), dtype=torch.float32, device=x_bti.device) if want_state else None
+        c_n = torch.empty((d.L, d.B, d.H), dtype=torch.float32, device=x_bti.device) if want_state else None
         with torch.cuda.device(self.device):
             _check(load().csn_lstm_forward(self._plan, _ptr(x_bti), x_bti.stride(0), x_bti.stride(1),
                                            _ptr_array(ws[0]), _ptr_array(ws[1]), _ptr_array(ws[2]), _ptr_array(ws[3]),
-                                           self._ws_ptr, _ptr(y_last), _ptr(y_all), _stream()))
+                                           _ptr(h0), _ptr(c0), self._ws_ptr, _ptr(y_last), _ptr(y_all),
+                                           _ptr(h_n), _ptr(c_n), _stream()))
+        if want_state:
+            return y_last, y_all, h_n, c_n
         return y_last, y_all
 
-    def backward(self, dy_last, dy_all, grads, dx=None):
-        """grads: 4 lists (dw_ih, dw_hh, db_ih, db_hh) of float32 device tensors, overwritten."""
+    def _state_in(self, t):
+        """[L,B,H] state / state gradient -> dense float32 on the plan's device (None stays None)."""
+        if t is None:
+            return None
+        d = self.desc
+        t = t.detach()
+        if tuple(t.shape) != (d.L, d.B, d.H):
+            raise CsnError(f"LSTM state must be [L, B, H] = {[d.L, d.B, d.H]}, got {list(t.shape)}")
+        return t.to(device=self.device, dtype=torch.float32).contiguous()
+
+    def backward(self, dy_last, dy_all, grads, dx=None, dh_n=None, dc_n=None, dh0=None, dc0=None):
+        """grads: 4 lists (dw_ih, dw_hh, db_ih, db_hh) of float32 device tensors, overwritten.  dh_n / dc_n: [L,B,H]
+        incoming gradients of the final state or None; dh0 / dc0: [L,B,H] float32 outputs (overwritten) or None."""
         if dy_last is not None:
             dy_last = dy_last.float().contiguous()
         if dy_all is not None:
             dy_all = dy_all.float().contiguous()
+        dh_n, dc_n = self._state_in(dh_n), self._state_in(dc_n)
+        for out in (dh0, dc0):
+            if out is not None:
+                assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == (self.desc.L, self.desc.B,
+                                                                                            self.desc.H)
         with torch.cuda.device(self.device):
-            _check(load().csn_lstm_backward(self._plan, _ptr(dy_last), _ptr(dy_all), self._ws_ptr,
+            _check(load().csn_lstm_backward(self._plan, _ptr(dy_last), _ptr(dy_all), _ptr(dh_n), _ptr(dc_n), self._ws_ptr,
                                             _ptr_array(grads[0]), _ptr_array(grads[1]), _ptr_array(grads[2]),
-                                            _ptr_array(grads[3]), _ptr(dx), _stream()))
+                                            _ptr_array(grads[3]), _ptr(dx), _ptr(dh0), _ptr(dc0), _stream()))
 
     # ---- sticky status word of the workspace ------------------------------------------------------
     def clear_status(self):

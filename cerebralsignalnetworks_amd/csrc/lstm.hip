@@ -28,6 +28,7 @@
 
 #include "csn_common.h"
 #include "lstm_cell_blk.h"
+#include "lstm_cell_common.h"
 #include "lstm_f32_persist.h"
 
 namespace csn {
@@ -214,6 +215,53 @@ __global__ void add_rows_kernel(const float* __restrict__ src, float* __restrict
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) dst[i] += src[i];
 }
 
+// Gradient w.r.t. the initial hidden state of one layer (CSN_LSTM_STATE plans):
+//   out[b][j] = sum_k dg[b][k] Wt(j, k),  k in [0, 4H), dg = dgates at t = 0 [B, 4H] row-major,
+//   Wt = W_hh^T [H, 4H]: row-major (BLK = false, generic path) or fragment-major (BLK = true, per-diagonal path, 4H axis
+//   gate-interleaved like dg).  The operands the recurrence multiplies (bf16 or float32), float32 accumulate in a fixed
+//   k order.  Tile 32 rows x 64 units per workgroup, k in blocks of 32 through LDS.
+template <typename T, bool BLK>
+__global__ void __launch_bounds__(256) lstm_dh0_kernel(const T* __restrict__ dg, const T* __restrict__ wt, int B, int H,
+                                                       float* __restrict__ out) {
+  __shared__ float As[32][33];
+  __shared__ float Ws[32][65];
+  const int64_t G = 4 * (int64_t)H;
+  const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+  const int b0 = blockIdx.y * 32, j0 = blockIdx.x * 64;
+  float acc[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+  for (int64_t k0 = 0; k0 < G; k0 += 32) {
+    for (int i = threadIdx.x; i < 32 * 32; i += 256) {
+      const int r = i >> 5, k = i & 31;
+      As[r][k] = b0 + r < B ? to_f32(dg[(int64_t)(b0 + r) * G + k0 + k]) : 0.f;
+    }
+    for (int i = threadIdx.x; i < 64 * 32; i += 256) {
+      const int j = i >> 5, k = i & 31;
+      float v = 0.f;
+      if (j0 + j < H) v = to_f32(wt[BLK ? blk_offset(j0 + j, k0 + k, G) : (int64_t)(j0 + j) * G + k0 + k]);
+      Ws[k][j] = v;
+    }
+    __syncthreads();
+#pragma unroll 8
+    for (int k = 0; k < 32; ++k) {
+      const float a0 = As[ty][k], a1 = As[ty + 16][k];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const float wv = Ws[k][tx + 16 * c];
+        acc[0][c] = fmaf(a0, wv, acc[0][c]);
+        acc[1][c] = fmaf(a1, wv, acc[1][c]);
+      }
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int r = 0; r < 2; ++r)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const int b = b0 + ty + 16 * r, j = j0 + tx + 16 * c;
+      if (b < B && j < H) out[(int64_t)b * H + j] = acc[r][c];
+    }
+}
+
 // out[n] = part[0][n] + part[1][n] + ... (fixed order): the row groups' bias-gradient partial sums of the float32 backward
 __global__ void sum_rows_kernel(const float* __restrict__ part, int P, int64_t n, float* __restrict__ out, float* __restrict__ out2) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -304,6 +352,8 @@ static int prof_pair(Prof& g_prof, int k, bool end, hipStream_t st) {   // k: 0 
 struct csnLstmPlan {
   csnLstmDesc d;
   int training;
+  int state;                  // created with CSN_LSTM_STATE: accepts (h0, c0) / (h_n, c_n) and their gradients
+  bool state_seen = false;    // a forward with a state has run: stateless forwards re-zero slot 0 (weight-stationary paths)
   int device;
   csn::Options opt;
   csn::WsLayout w;
@@ -325,12 +375,15 @@ extern "C" int csn_lstm_plan_create(const csnLstmDesc* d, int training, csnLstmP
   CSN_REQUIRE(out != nullptr, "csn_lstm_plan_create: null output pointer");
   Plan* P = new Plan();
   P->d = *d;
-  P->training = training != 0;
+  P->state = (training & CSN_LSTM_STATE) != 0;
+  P->training = (training & ~CSN_LSTM_STATE) != 0;
   if (hipGetDevice(&P->device) != hipSuccess) {
     delete P;
     return fail(CSN_ERR_HIP, "csn_lstm_plan_create: hipGetDevice failed");
   }
   P->opt = options_from_env();
+  // (the exact-float32 weight-stationary path (4) takes no state: a float32 state plan runs the per-step cells)
+  if (P->state && d->dtype == CSN_F32) P->opt.no_persist = true;
   {
     // the weight-stationary kernels address the steps of ONE launch with 32-bit byte offsets from the launch's base
     // (lstm_fwd_ns.hip; launch_fwd_ns refuses more): a CSN_LSTM_CHUNK that large is clamped here, not left to wrap
@@ -489,7 +542,9 @@ extern "C" int csn_lstm_status_read(const csnLstmPlan* P, const void* workspace,
 
 extern "C" size_t csn_lstm_workspace_bytes(const csnLstmDesc* d, int training) {
   if (check_desc("csn_lstm_workspace_bytes", d) != CSN_OK) return 0;
-  return make_layout(*d, training, options_from_env()).total;
+  Options opt = options_from_env();
+  if ((training & CSN_LSTM_STATE) && d->dtype == CSN_F32) opt.no_persist = true;
+  return make_layout(*d, (training & ~CSN_LSTM_STATE) != 0, opt).total;
 }
 
 // C[M,N] = A[K,M]^T B[K,N] through the split-K slabs + their fixed-order reduction (the body of csn_gemm_tn)
@@ -509,7 +564,7 @@ static int gemm_tn_full(const void* A, const void* B, float* C, int64_t M, int64
 // chunk (GEMM over `chunk` steps on the same stream), so lag = chunk.
 static int forward_v1(Plan& P, char* ws, const float* x, int64_t xsb, int64_t xst,
                       const float* const* w_ih, const float* const* w_hh, const float* const* b_ih,
-                      const float* const* b_hh, int training, csnStream_t stream) {
+                      const float* const* b_hh, const float* h0, const float* c0, int training, csnStream_t stream) {
   const csnLstmDesc* d = &P.d;
   const WsLayout& w = P.w;
   hipStream_t st = as_stream(stream);
@@ -529,8 +584,16 @@ static int forward_v1(Plan& P, char* ws, const float* x, int64_t xsb, int64_t xs
       if ((rc = launch_transpose_cast(w_ih[l], G, I, ws + L.wiht, dt, st))) return rc;
     }
     if ((rc = launch_add_vec(b_ih[l], b_hh[l], (float*)(ws + L.bias), G, st))) return rc;
-    CSN_HIP_CHECK(hipMemsetAsync(ws + L.h_all, 0, (size_t)B * H * es, st));
-    CSN_HIP_CHECK(hipMemsetAsync(ws + L.c_all, 0, (size_t)B * H * 4, st));
+    // slot 0 = the initial state (the cells read it at t = 0; the dW_hh GEMM reads h_all slot 0 too)
+    if (h0) {
+      if ((rc = launch_cast(h0 + (size_t)l * B * H, ws + L.h_all, (int64_t)B * H, dt, st))) return rc;
+    } else {
+      CSN_HIP_CHECK(hipMemsetAsync(ws + L.h_all, 0, (size_t)B * H * es, st));
+    }
+    if (c0)
+      CSN_HIP_CHECK(hipMemcpyAsync(ws + L.c_all, c0 + (size_t)l * B * H, (size_t)B * H * 4, hipMemcpyDeviceToDevice, st));
+    else
+      CSN_HIP_CHECK(hipMemsetAsync(ws + L.c_all, 0, (size_t)B * H * 4, st));
   }
   // layer 0: projection of every step in one GEMM
   if ((rc = gemm_nt(ws + w.x_c, ws + w.layer[0].wih, (const float*)(ws + w.layer[0].bias), ws + w.layer[0].xproj, TB, G,
@@ -568,7 +631,7 @@ static int forward_v1(Plan& P, char* ws, const float* x, int64_t xsb, int64_t xs
   return CSN_OK;
 }
 
-static int backward_v1(Plan& P, char* ws, const float* dy_last, const float* dy_tm,
+static int backward_v1(Plan& P, char* ws, const float* dy_last, const float* dy_tm, const float* dh_n, const float* dc_n,
                        float* const* dw_ih, float* const* dw_hh, float* const* db_ih, float* const* db_hh, float* dx,
                        csnStream_t stream) {
   const csnLstmDesc* d = &P.d;
@@ -579,7 +642,12 @@ static int backward_v1(Plan& P, char* ws, const float* dy_last, const float* dy_
   const size_t es = dtype_size(dt);
   const int Cz = P.opt.chunk, lag = Cz;
   int rc;
-  for (int l = 0; l < NL; ++l) CSN_HIP_CHECK(hipMemsetAsync(ws + w.layer[l].dc_carry, 0, (size_t)B * H * 4, st));
+  for (int l = 0; l < NL; ++l) {
+    if (dc_n)      // the carried dc starts as the gradient w.r.t. c_n; after step 0 it is the gradient w.r.t. c0
+      CSN_HIP_CHECK(hipMemcpyAsync(ws + w.layer[l].dc_carry, dc_n + (size_t)l * B * H, (size_t)B * H * 4, hipMemcpyDeviceToDevice, st));
+    else
+      CSN_HIP_CHECK(hipMemsetAsync(ws + w.layer[l].dc_carry, 0, (size_t)B * H * 4, st));
+  }
   // diagonal d: layer l at reverse step d - lag * (L - 1 - l); the gradient w.r.t. a layer's input (= dy of the layer
   // below) follows chunk by chunk
   const int D = T + lag * (NL - 1);
@@ -612,6 +680,11 @@ static int backward_v1(Plan& P, char* ws, const float* dy_last, const float* dy_
       if ((rc = gemm_nt(ws + L.dgates + (size_t)t_lo * B * G * es, ws + L.wiht, nullptr, (float*)(ws + L.dx) + (size_t)t_lo * B * H,
                         (int64_t)(t_hi - t_lo + 1) * B, H, G, dt, CSN_F32, 0, st, P.opt)))
         return rc;
+      if (dh_n && t_hi == T - 1) {      // gradient w.r.t. h_n of the layer below joins its dy at t = T-1
+        add_rows_kernel<<<grid_for((int64_t)B * H), 256, 0, st>>>(dh_n + (size_t)(l - 1) * B * H,
+                                                                   (float*)(ws + L.dx) + (size_t)(T - 1) * B * H, (int64_t)B * H);
+        CSN_LAUNCH_CHECK();
+      }
     }
   }
   for (int l = NL - 1; l >= 0; --l) {
@@ -764,11 +837,12 @@ static int backward_f32p(Plan& P, char* ws, const float* dy_last, const float* d
 // =============================================================================================
 // il fast path (wavefront over layers, GEMMs on the side stream)
 // =============================================================================================
-static int forward_persist(Plan& P, char* ws, int training, hipStream_t st, SideCtx* sc, hipStream_t side);
+static int forward_persist(Plan& P, char* ws, const float* h0, const float* c0, int training, hipStream_t st, SideCtx* sc,
+                           hipStream_t side);
 
 static int forward_il(Plan& P, char* ws, const float* x, int64_t xsb, int64_t xst,
                       const float* const* w_ih, const float* const* w_hh, const float* const* b_ih,
-                      const float* const* b_hh, int training, csnStream_t stream) {
+                      const float* const* b_hh, const float* h0, const float* c0, int training, csnStream_t stream) {
   const csnLstmDesc* d = &P.d;
   const WsLayout& w = P.w;
   Prof& g_prof = P.prof;
@@ -814,6 +888,14 @@ static int forward_il(Plan& P, char* ws, const float* x, int64_t xsb, int64_t xs
       // (weight-stationary paths: slot 0 is never written, csn_lstm_workspace_init zeroed it)
       CSN_HIP_CHECK(hipMemsetAsync(ws + L.h_all, 0, (size_t)B * H * 2, st));
       CSN_HIP_CHECK(hipMemsetAsync(ws + L.c_all, 0, (size_t)B * H * 4, st));
+      // initial state (CSN_LSTM_STATE plans, never weight-stationary): bf16 h0 fragment-major into the ping-pong buffer
+      // step 0 reads, and row-major into h_all slot 0 for the dW_hh GEMM; c0 into c_all slot 0 (behind the memsets)
+      if (h0) {
+        if ((rc = launch_blockify_x(h0 + (size_t)l * B * H, H, 0, B, 1, H, ws + L.hblk[0], st))) return rc;
+        if ((rc = launch_cast(h0 + (size_t)l * B * H, ws + L.h_all, (int64_t)B * H, CSN_BF16, st))) return rc;
+      }
+      if (c0)
+        CSN_HIP_CHECK(hipMemcpyAsync(ws + L.c_all, c0 + (size_t)l * B * H, (size_t)B * H * 4, hipMemcpyDeviceToDevice, st));
     }
   }
   if (w.fuse_x) {
@@ -830,7 +912,7 @@ static int forward_il(Plan& P, char* ws, const float* x, int64_t xsb, int64_t xs
                           TB, G, d->I, CSN_BF16, CSN_F32, 0, st, P.opt)))
       return rc;
   }
-  if (w.persist) return forward_persist(P, ws, training, st, sc, side);
+  if (w.persist) return forward_persist(P, ws, h0, c0, training, st, sc, side);
   if (NL > 1 && (rc = hand_off(sc, st, side))) return rc;   // side stream sees the prepared weights
 
   const int nch = (T + Cz - 1) / Cz;
@@ -855,10 +937,10 @@ static int forward_il(Plan& P, char* ws, const float* x, int64_t xsb, int64_t xs
       }
       if (l > 0 && t % Cz == 0) CSN_HIP_CHECK(hipStreamWaitEvent(st, xproj_ready[(size_t)l * nch + t / Cz], 0));
       CellFwdProb& P = a.p[np++];
-      P.h_prev_blk = t == 0 ? nullptr : (const bf16_t*)(ws + L.hblk[t & 1]);
+      P.h_prev_blk = (t == 0 && !h0) ? nullptr : (const bf16_t*)(ws + L.hblk[t & 1]);
       P.w_blk = (const bf16_t*)(ws + L.whh_blk);
       P.xproj = (const float*)(ws + L.xproj) + (size_t)t * B * G;
-      P.c_prev = t == 0 ? nullptr : (const float*)(ws + L.c_all) + (size_t)t * B * H;
+      P.c_prev = (t == 0 && !c0) ? nullptr : (const float*)(ws + L.c_all) + (size_t)t * B * H;
       P.gates_out = training ? (bf16_t*)(ws + L.gates) + (size_t)t * B * G : nullptr;
       P.c_out = (float*)(ws + L.c_all) + (size_t)(t + 1) * B * H;
       P.h_out = (bf16_t*)(ws + L.h_all) + (size_t)(t + 1) * B * H;
@@ -904,7 +986,8 @@ static int forward_il(Plan& P, char* ws, const float* x, int64_t xsb, int64_t xs
 //
 // Stream form (any number of layers / M-tiles): layer l runs chunk after chunk on its own stream, the GEMMs
 // on the side stream, ordered by events; placement-independent hand-off.
-static int forward_persist(Plan& P, char* ws, int training, hipStream_t st, SideCtx* sc, hipStream_t side) {
+static int forward_persist(Plan& P, char* ws, const float* h0, const float* c0, int training, hipStream_t st, SideCtx* sc,
+                           hipStream_t side) {
   const csnLstmDesc* d = &P.d;
   const WsLayout& w = P.w;
   Prof& g_prof = P.prof;
@@ -959,6 +1042,25 @@ static int forward_persist(Plan& P, char* ws, int training, hipStream_t st, Side
   if (a.data_polls)        // the ring of 4 hand-off slabs of every layer starts as sentinel (lstm_fwd_persist.hip)
     for (int l = 0; l < NL; ++l)
       CSN_HIP_CHECK(hipMemsetAsync(ws + w.layer[l].h_blk_all, 0xff, (size_t)4 * Bpad * H * 2, st));
+  // initial state: h0 fragment-major into hand-off slot 0 (behind the ring's sentinel fill) and row-major into h_all
+  // slot 0 (the dW_hh GEMM), c0 into c_all slot 0 (the forward's step 0 and the backward's df_0).  A stateless forward
+  // of a plan that has seen a state re-zeroes both slots 0, which it does not otherwise write.
+  a.state = (h0 || c0) ? 1 : 0;
+  if (a.state) P.state_seen = true;
+  for (int l = 0; l < NL && P.state_seen; ++l) {
+    const LayerWs& L = w.layer[l];
+    if (h0) {
+      if ((rc = launch_blockify_x(h0 + (size_t)l * B * H, H, 0, B, 1, H, ws + L.h_blk_all, st))) return rc;
+      if ((rc = launch_cast(h0 + (size_t)l * B * H, ws + L.h_all, (int64_t)B * H, CSN_BF16, st))) return rc;
+    } else {
+      if (a.state) CSN_HIP_CHECK(hipMemsetAsync(ws + L.h_blk_all, 0, (size_t)Bpad * H * 2, st));
+      CSN_HIP_CHECK(hipMemsetAsync(ws + L.h_all, 0, (size_t)B * H * 2, st));
+    }
+    if (c0)
+      CSN_HIP_CHECK(hipMemcpyAsync(ws + L.c_all, c0 + (size_t)l * B * H, (size_t)B * H * 4, hipMemcpyDeviceToDevice, st));
+    else
+      CSN_HIP_CHECK(hipMemsetAsync(ws + L.c_all, 0, (size_t)B * H * 4, st));
+  }
   int n_launch = 0;
 
   const int max_slots = NL < nch ? NL : nch;
@@ -1040,18 +1142,18 @@ static int forward_persist(Plan& P, char* ws, int training, hipStream_t st, Side
   return CSN_OK;
 }
 
-static int backward_persist(Plan& P, char* ws, const float* dy_last,
-                            const float* dy_tm, float* const* dw_ih, float* const* dw_hh, float* const* db_ih,
+static int backward_persist(Plan& P, char* ws, const float* dy_last, const float* dy_tm, const float* dh_n,
+                            const float* dc_n, float* const* dw_ih, float* const* dw_hh, float* const* db_ih,
                             float* const* db_hh, float* dx, hipStream_t st);
 
-static int backward_il(Plan& P, char* ws, const float* dy_last, const float* dy_tm,
+static int backward_il(Plan& P, char* ws, const float* dy_last, const float* dy_tm, const float* dh_n, const float* dc_n,
                        float* const* dw_ih, float* const* dw_hh, float* const* db_ih, float* const* db_hh, float* dx,
                        csnStream_t stream) {
   const csnLstmDesc* d = &P.d;
   const WsLayout& w = P.w;
   Prof& g_prof = P.prof;
   hipStream_t st = as_stream(stream);
-  if (bwd_grouped(&P)) return backward_persist(P, ws, dy_last, dy_tm, dw_ih, dw_hh, db_ih, db_hh, dx, st);
+  if (bwd_grouped(&P)) return backward_persist(P, ws, dy_last, dy_tm, dh_n, dc_n, dw_ih, dw_hh, db_ih, db_hh, dx, st);
   SideCtx* sc = &P.sc;
   int rc;
   if ((rc = side_ctx(P.sc))) return rc;
@@ -1061,10 +1163,14 @@ static int backward_il(Plan& P, char* ws, const float* dy_last, const float* dy_
   const size_t Bpad = ((size_t)B + 63) / 64 * 64;
   const int Cz = P.opt.chunk, lag = 2 * Cz;
   const int nch = (T + Cz - 1) / Cz;
+  const bool state = P.state != 0;
 
   for (int l = 0; l < NL; ++l) {
     const LayerWs& L = w.layer[l];
-    CSN_HIP_CHECK(hipMemsetAsync(ws + L.dc_carry, 0, (size_t)B * H * 4, st));
+    if (dc_n)      // the carried dc starts as the gradient w.r.t. c_n; after step 0 it is the gradient w.r.t. c0
+      CSN_HIP_CHECK(hipMemcpyAsync(ws + L.dc_carry, dc_n + (size_t)l * B * H, (size_t)B * H * 4, hipMemcpyDeviceToDevice, st));
+    else
+      CSN_HIP_CHECK(hipMemsetAsync(ws + L.dc_carry, 0, (size_t)B * H * 4, st));
     CSN_HIP_CHECK(hipMemsetAsync(ws + L.dgblk[0], 0, Bpad * G * 2, st));
     CSN_HIP_CHECK(hipMemsetAsync(ws + L.dgblk[1], 0, Bpad * G * 2, st));
   }
@@ -1128,7 +1234,8 @@ static int backward_il(Plan& P, char* ws, const float* dy_last, const float* dy_
       P.dy_ld = H;
       P.gates = (const bf16_t*)(ws + L.gates) + (size_t)t * B * G;
       P.c = (const float*)(ws + L.c_all) + (size_t)(t + 1) * B * H;
-      P.c_prev = t == 0 ? nullptr : (const float*)(ws + L.c_all) + (size_t)t * B * H;
+      // (a CSN_LSTM_STATE plan reads c_all slot 0 at t = 0: c0, or the zeros its forward wrote there)
+      P.c_prev = (t == 0 && !state) ? nullptr : (const float*)(ws + L.c_all) + (size_t)t * B * H;
       P.dc_carry = (float*)(ws + L.dc_carry);
       P.dg_out = (bf16_t*)(ws + L.dgates) + (size_t)t * B * G;
       P.dg_out_blk = (bf16_t*)(ws + L.dgblk[t & 1]);
@@ -1156,6 +1263,11 @@ static int backward_il(Plan& P, char* ws, const float* dy_last, const float* dy_
                          (float*)(ws + L.dx) + (size_t)t_lo * B * I, (int64_t)(t_hi - t_lo + 1) * B, I, G, CSN_BF16,
                          CSN_F32, 0, side, P.opt);
         if (rc) return rc;
+        if (dh_n && t_hi == T - 1) {      // gradient w.r.t. h_n of the layer below joins its dy at t = T-1
+          add_rows_kernel<<<grid_for((int64_t)B * H), 256, 0, side>>>(dh_n + (size_t)(l - 1) * B * H,
+                                                                       (float*)(ws + L.dx) + (size_t)(T - 1) * B * H, (int64_t)B * H);
+          CSN_LAUNCH_CHECK();
+        }
         hipEvent_t ev;
         if ((rc = next_event(sc, &ev))) return rc;
         CSN_HIP_CHECK(hipEventRecord(ev, side));
@@ -1191,8 +1303,8 @@ static int backward_il(Plan& P, char* ws, const float* dy_last, const float* dy_
 // the launch was measured too: the event waits between the streams cost ~30 us per launch, most of the gain.)
 // CSN_NO_BESIDE: lag one chunk, GEMM between two launches.
 // The weight / bias gradients follow once the recurrence is complete.
-static int backward_persist(Plan& P, char* ws, const float* dy_last,
-                            const float* dy_tm, float* const* dw_ih, float* const* dw_hh, float* const* db_ih,
+static int backward_persist(Plan& P, char* ws, const float* dy_last, const float* dy_tm, const float* dh_n,
+                            const float* dc_n, float* const* dw_ih, float* const* dw_hh, float* const* db_ih,
                             float* const* db_hh, float* dx, hipStream_t st) {
   const csnLstmDesc* d = &P.d;
   const WsLayout& w = P.w;
@@ -1208,6 +1320,20 @@ static int backward_persist(Plan& P, char* ws, const float* dy_last,
   int rc;
   // one fill: carried dc and flag lines of every layer, the XCD agreement words (zeros_bh: csn_lstm_workspace_init)
   CSN_HIP_CHECK(hipMemsetAsync(ws + w.zero_bwd, 0, w.zero_bwd_bytes, st));
+  // gradient w.r.t. c_n: the carried dc every layer starts from (the kernel reads it at launch start and writes it back at
+  // launch end, so after the last launch it holds the gradient w.r.t. c0)
+  if (dc_n)
+    for (int l = 0; l < NL; ++l)
+      CSN_HIP_CHECK(hipMemcpyAsync(ws + w.layer[l].dc_carry, dc_n + (size_t)l * B * H, (size_t)B * H * 4,
+                                   hipMemcpyDeviceToDevice, st));
+  // gradient w.r.t. h_n of layer l - 1: added to row T-1 of layer l's input gradient once the GEMM of that chunk has
+  // run (inline, or beside the recurrence in the next launch), before the launch that runs layer l - 1's first chunk
+  auto add_dh_n = [&](int l) -> int {
+    add_rows_kernel<<<grid_for((int64_t)B * H), 256, 0, st>>>(dh_n + (size_t)(l - 1) * B * H,
+                                                               (float*)(ws + w.layer[l].dx) + (size_t)(T - 1) * B * H, (int64_t)B * H);
+    CSN_LAUNCH_CHECK();
+    return CSN_OK;
+  };
   const bool try_local = !P.opt.no_xcd_local;
 
   // weight / bias gradients of one layer (its recurrence complete): four launches on the caller's stream
@@ -1248,6 +1374,7 @@ static int backward_persist(Plan& P, char* ws, const float* dy_last,
     for (int l = 0; l < NL; ++l) CSN_HIP_CHECK(hipMemsetAsync(ws + w.layer[l].dg_blk_all, 0xff, (size_t)4 * Bpad * G * 2, st));
   int n_launch = 0;
   BesideGemm pending[3];           // GEMMs of the chunks finished by the previous launch
+  int pending_add[3] = {0, 0, 0};  // layer whose dh_n term follows pending[i] (its first chunk), or 0
   int npending = 0;
   if ((rc = prof_mark(g_prof, 2, st))) return rc;
   for (int dg = 0; dg < ndiag; ++dg) {
@@ -1284,19 +1411,26 @@ static int backward_persist(Plan& P, char* ws, const float* dy_last,
       for (int i = 0; i < npending; ++i) {
         const BesideGemm& g = pending[i];
         if ((rc = gemm_nt(g.A, g.Bt, nullptr, g.C, g.M, g.N, g.K, CSN_BF16, CSN_F32, 0, st, P.opt))) return rc;
+        if (pending_add[i] && (rc = add_dh_n(pending_add[i]))) return rc;
       }
       npending = 0;
       continue;
     }
     a.nslots = ns;
     a.ngemm = npending;
-    for (int i = 0; i < npending; ++i) a.gemm[i] = pending[i];
+    int launch_adds[3], nadds = 0;
+    for (int i = 0; i < npending; ++i) {
+      a.gemm[i] = pending[i];
+      if (pending_add[i]) launch_adds[nadds++] = pending_add[i];
+    }
     npending = 0;
     a.agree = try_local ? (unsigned long long*)(ws + w.agree_b) + (size_t)dg * 8 : nullptr;
     if ((rc = prof_pair(g_prof, 1, false, st))) return rc;
     if ((rc = launch_bwd_persist(a, st))) return rc;
     if ((rc = prof_pair(g_prof, 1, true, st))) return rc;
     ++n_launch;
+    for (int i = 0; i < nadds; ++i)
+      if ((rc = add_dh_n(launch_adds[i]))) return rc;
     for (int i = 0; i < ns; ++i) {
       const int l = lay[i];
       if (l == 0) continue;
@@ -1306,10 +1440,13 @@ static int backward_persist(Plan& P, char* ws, const float* dy_last,
       const bf16_t* Ag = (const bf16_t*)(ws + L.dgates) + (size_t)t_lo * B * G;
       float* Cg = (float*)(ws + L.dx) + (size_t)t_lo * B * H;
       const int64_t Mg = (int64_t)(t_hi - t_lo + 1) * B;
+      const int add = (dh_n && chk[i] == 0) ? l : 0;
       if (beside) {
+        pending_add[npending] = add;
         pending[npending++] = BesideGemm{Ag, (const bf16_t*)(ws + L.wiht), Cg, (int)Mg, H, (int)G};
       } else {
         if ((rc = gemm_nt(Ag, ws + L.wiht, nullptr, Cg, Mg, H, G, CSN_BF16, CSN_F32, 0, st, P.opt))) return rc;
+        if (add && (rc = add_dh_n(add))) return rc;
       }
     }
   }
@@ -1336,16 +1473,31 @@ static int backward_persist(Plan& P, char* ws, const float* dy_last,
 }
 
 // =============================================================================================
+// state arguments ([L,B,H] float32): only on a CSN_LSTM_STATE plan, 16-B aligned (read / written as float4)
+static int check_state_args(const Plan& P, const char* fn, const void* const* ptrs, const char* const* names, int n) {
+  for (int i = 0; i < n; ++i) {
+    if (ptrs[i] == nullptr) continue;
+    CSN_REQUIRE(P.state, "%s: %s given, but the plan was created without CSN_LSTM_STATE", fn, names[i]);
+    CSN_REQUIRE((reinterpret_cast<uintptr_t>(ptrs[i]) & 15) == 0, "%s: %s must be 16-B aligned", fn, names[i]);
+  }
+  return CSN_OK;
+}
+
 extern "C" int csn_lstm_forward(csnLstmPlan* Pp, const float* x, int64_t x_stride_b, int64_t x_stride_t,
                                 const float* const* w_ih, const float* const* w_hh, const float* const* b_ih,
-                                const float* const* b_hh, void* workspace, float* y_last, float* y_all,
-                                csnStream_t stream) {
+                                const float* const* b_hh, const float* h0, const float* c0, void* workspace,
+                                float* y_last, float* y_all, float* h_n, float* c_n, csnStream_t stream) {
   CSN_REQUIRE(Pp != nullptr, "csn_lstm_forward: null plan");
   Plan& P = *Pp;
   const csnLstmDesc* d = &P.d;
   CSN_REQUIRE(x && w_ih && w_hh && b_ih && b_hh && workspace, "csn_lstm_forward: null pointer");
   CSN_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "csn_lstm_forward: workspace must be 256-B aligned");
-  CSN_REQUIRE(y_last || y_all, "csn_lstm_forward: no output requested");
+  CSN_REQUIRE(y_last || y_all || h_n || c_n, "csn_lstm_forward: no output requested");
+  {
+    const void* ptrs[4] = {h0, c0, h_n, c_n};
+    const char* names[4] = {"h0", "c0", "h_n", "c_n"};
+    if (int rc = check_state_args(P, "csn_lstm_forward", ptrs, names, 4)) return rc;
+  }
   for (int l = 0; l < d->L; ++l)
     CSN_REQUIRE(w_ih[l] && w_hh[l] && b_ih[l] && b_hh[l], "csn_lstm_forward: null parameter pointer, layer %d", l);
   int dev = -1;
@@ -1361,12 +1513,21 @@ extern "C" int csn_lstm_forward(csnLstmPlan* Pp, const float* x, int64_t x_strid
   // (the status word is NOT cleared here: it stays raised from the first timed-out hand-off until
   // csn_lstm_status_clear, so a check at the end of an epoch / a timed region covers every step in it)
   if (w.il)
-    rc = forward_il(P, ws, x, x_stride_b, x_stride_t, w_ih, w_hh, b_ih, b_hh, training, stream);
+    rc = forward_il(P, ws, x, x_stride_b, x_stride_t, w_ih, w_hh, b_ih, b_hh, h0, c0, training, stream);
   else if (w.f32_persist)
     rc = forward_f32p(P, ws, x, x_stride_b, x_stride_t, w_ih, w_hh, b_ih, b_hh, training, stream);
   else
-    rc = forward_v1(P, ws, x, x_stride_b, x_stride_t, w_ih, w_hh, b_ih, b_hh, training, stream);
+    rc = forward_v1(P, ws, x, x_stride_b, x_stride_t, w_ih, w_hh, b_ih, b_hh, h0, c0, training, stream);
   if (rc) return rc;
+  // final state of every layer: slot T of h_all (upcast of the h the next layer consumed) and of c_all
+  for (int l = 0; l < d->L && (h_n || c_n); ++l) {
+    const LayerWs& L = w.layer[l];
+    if (h_n && (rc = launch_upcast(ws + L.h_all + (size_t)T * B * H * es, dt, h_n + (size_t)l * B * H, (int64_t)B * H, st)))
+      return rc;
+    if (c_n)
+      CSN_HIP_CHECK(hipMemcpyAsync(c_n + (size_t)l * B * H, ws + L.c_all + (size_t)T * B * H * 4, (size_t)B * H * 4,
+                                   hipMemcpyDeviceToDevice, st));
+  }
   const LayerWs& top = w.layer[d->L - 1];
   if (y_last)
     if ((rc = launch_upcast(ws + top.h_all + (size_t)T * B * H * es, dt, y_last, (int64_t)B * H, st))) return rc;
@@ -1381,15 +1542,21 @@ extern "C" int csn_lstm_forward(csnLstmPlan* Pp, const float* x, int64_t x_strid
   return CSN_OK;
 }
 
-extern "C" int csn_lstm_backward(csnLstmPlan* Pp, const float* dy_last, const float* dy_all, void* workspace,
-                                 float* const* dw_ih, float* const* dw_hh, float* const* db_ih, float* const* db_hh,
-                                 float* dx, csnStream_t stream) {
+extern "C" int csn_lstm_backward(csnLstmPlan* Pp, const float* dy_last, const float* dy_all, const float* dh_n,
+                                 const float* dc_n, void* workspace, float* const* dw_ih, float* const* dw_hh,
+                                 float* const* db_ih, float* const* db_hh, float* dx, float* dh0, float* dc0,
+                                 csnStream_t stream) {
   CSN_REQUIRE(Pp != nullptr, "csn_lstm_backward: null plan");
   Plan& P = *Pp;
   const csnLstmDesc* d = &P.d;
   CSN_REQUIRE(P.training, "csn_lstm_backward: the plan was created with training = 0");
   CSN_REQUIRE(workspace && dw_ih && dw_hh && db_ih && db_hh, "csn_lstm_backward: null pointer");
-  CSN_REQUIRE(dy_last || dy_all, "csn_lstm_backward: no incoming gradient");
+  CSN_REQUIRE(dy_last || dy_all || dh_n || dc_n, "csn_lstm_backward: no incoming gradient");
+  {
+    const void* ptrs[4] = {dh_n, dc_n, dh0, dc0};
+    const char* names[4] = {"dh_n", "dc_n", "dh0", "dc0"};
+    if (int rc = check_state_args(P, "csn_lstm_backward", ptrs, names, 4)) return rc;
+  }
   for (int l = 0; l < d->L; ++l)
     CSN_REQUIRE(dw_ih[l] && dw_hh[l] && db_ih[l] && db_hh[l], "csn_lstm_backward: null gradient pointer, layer %d", l);
   int dev = -1;
@@ -1413,7 +1580,47 @@ extern "C" int csn_lstm_backward(csnLstmPlan* Pp, const float* dy_last, const fl
     }
     dy_tm = buf;
   }
-  if (w.il) return backward_il(P, ws, dy_last, dy_tm, dw_ih, dw_hh, db_ih, db_hh, dx, stream);
-  if (w.f32_persist) return backward_f32p(P, ws, dy_last, dy_tm, dw_ih, dw_hh, db_ih, db_hh, dx, stream);
-  return backward_v1(P, ws, dy_last, dy_tm, dw_ih, dw_hh, db_ih, db_hh, dx, stream);
+  // gradient w.r.t. the top layer's h_n: one more term of its dy at t = T-1 (dy_last is caller memory: added into a
+  // workspace copy of it, in the dy_tm region that is unused when dy_all is NULL)
+  if (dh_n) {
+    const float* dh_top = dh_n + (size_t)(d->L - 1) * B * H;
+    if (dy_tm) {
+      add_rows_kernel<<<grid_for((int64_t)B * H), 256, 0, st>>>(dh_top, (float*)dy_tm + (size_t)(T - 1) * B * H, (int64_t)B * H);
+      CSN_LAUNCH_CHECK();
+    } else if (dy_last) {
+      float* buf = (float*)(ws + w.dy_tm);
+      CSN_HIP_CHECK(hipMemcpyAsync(buf, dy_last, (size_t)B * H * 4, hipMemcpyDeviceToDevice, st));
+      add_rows_kernel<<<grid_for((int64_t)B * H), 256, 0, st>>>(dh_top, buf, (int64_t)B * H);
+      CSN_LAUNCH_CHECK();
+      dy_last = buf;
+    } else {
+      dy_last = dh_top;
+    }
+  }
+  int rc;
+  if (w.il)
+    rc = backward_il(P, ws, dy_last, dy_tm, dh_n, dc_n, dw_ih, dw_hh, db_ih, db_hh, dx, stream);
+  else if (w.f32_persist)
+    rc = backward_f32p(P, ws, dy_last, dy_tm, dw_ih, dw_hh, db_ih, db_hh, dx, stream);
+  else
+    rc = backward_v1(P, ws, dy_last, dy_tm, dh_n, dc_n, dw_ih, dw_hh, db_ih, db_hh, dx, stream);
+  if (rc) return rc;
+  // gradients w.r.t. the initial state (CSN_LSTM_STATE plans only: paths 0 and 1, everything on `stream` by now)
+  for (int l = 0; l < d->L && (dh0 || dc0); ++l) {
+    const LayerWs& L = w.layer[l];
+    if (dh0) {
+      const dim3 grid((unsigned)((H + 63) / 64), (unsigned)((B + 31) / 32));
+      float* out = dh0 + (size_t)l * B * H;
+      if (w.il)
+        lstm_dh0_kernel<bf16_t, true><<<grid, 256, 0, st>>>((const bf16_t*)(ws + L.dgates), (const bf16_t*)(ws + L.whht_blk), B, H, out);
+      else if (d->dtype == CSN_BF16)
+        lstm_dh0_kernel<bf16_t, false><<<grid, 256, 0, st>>>((const bf16_t*)(ws + L.dgates), (const bf16_t*)(ws + L.whht), B, H, out);
+      else
+        lstm_dh0_kernel<float, false><<<grid, 256, 0, st>>>((const float*)(ws + L.dgates), (const float*)(ws + L.whht), B, H, out);
+      CSN_LAUNCH_CHECK();
+    }
+    if (dc0)
+      CSN_HIP_CHECK(hipMemcpyAsync(dc0 + (size_t)l * B * H, ws + L.dc_carry, (size_t)B * H * 4, hipMemcpyDeviceToDevice, st));
+  }
+  return CSN_OK;
 }

@@ -86,6 +86,9 @@ struct PersistFwdArgs {
   unsigned long long* agree;
   unsigned* error_flag;    // sticky: a bounded spin gave up
   int B, H, T, Bpad, MT;
+  // != 0: an initial state (CSN_LSTM_STATE): step 0 multiplies h_{-1} = h0 from hand-off slot 0 (written by an earlier
+  // kernel on the stream: read without a wait) and starts from c_all slot 0; 0: step 0 has no recurrent term, c = 0
+  int state;
 };
 bool fwd_persist_supported(int B, int H, int dtype, const Options& opt);
 // N-split weight-stationary forward (lstm_fwd_ns.hip): the default where it applies

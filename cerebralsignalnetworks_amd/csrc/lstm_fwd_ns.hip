@@ -148,7 +148,7 @@ __device__ __forceinline__ void ns_recurrence(const PersistFwdArgs& a, const Per
   for (int rg = 0; rg < 4; ++rg)
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      const float c0 = t_first > 0 ? c_all[((size_t)t_first * B + rowc[rg]) * H + unit_q + 4 * j] : 0.0f;
+      const float c0 = (t_first > 0 || a.state) ? c_all[((size_t)t_first * B + rowc[rg]) * H + unit_q + 4 * j] : 0.0f;
       if constexpr (CLDS)
         *reinterpret_cast<float*>(stage + 64 * 288 + (rg * 16 + (lane & 15)) * 144 + (8 * wave + 4 * j + (lane >> 4)) * 4) = c0;
       else
@@ -266,9 +266,10 @@ __device__ __forceinline__ void ns_recurrence(const PersistFwdArgs& a, const Per
         kb_next = kb_next + 1 == KB ? 0 : kb_next + 1;
       }
     };
-    if (t > 0) {
-      // wait for h_{t-1} (slot t): every wave polls the group's flag line (lane i the flag of slice i; sc1 loads)
-      {
+    if (t > 0 || a.state) {
+      // wait for h_{t-1} (slot t): every wave polls the group's flag line (lane i the flag of slice i; sc1 loads).
+      // (t = 0 with a state: h0 in slot 0 was written before the launch -- no wait)
+      if (t > 0) {
         const unsigned* fl = flags + (size_t)t * flag_step + (lane < nslices ? lane : 0);
         const unsigned long long t_begin = wall_clock64();
         while (!__all(__hip_atomic_load(fl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u)) {
@@ -307,7 +308,7 @@ __device__ __forceinline__ void ns_recurrence(const PersistFwdArgs& a, const Per
       __builtin_amdgcn_sched_barrier(0);
     }
 
-    if (t > 0) {
+    if (t > 0 || a.state) {
       // MFMAs of one group: fragment reads in inline asm with counted lgkmcnt waits, two k-blocks ahead (one ahead
       // left every read's latency half exposed: 0.70 us per group of 48 MFMAs instead of 0.33)
       // (the fused body at H = 1024 keeps two: with three it is no faster, and its registers are the tightest of the library)

@@ -279,7 +279,7 @@ __global__ void __launch_bounds__(256) lstm_fwd_persist_kernel(PersistFwdArgs a)
     puq[ps] = u0 + 4 * pj[ps];                  // (the quad's first unit, also in the split pass)
     pok[ps] = p < NPAIR && prow[ps] < B;
     cst[ps] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (pok[ps] && t_first > 0) {
+    if (pok[ps] && (t_first > 0 || a.state)) {
       const float* cp = c_all + ((size_t)t_first * B + prow[ps]) * H + puq[ps];
       if (hp) {
         const f32x2 c2 = *reinterpret_cast<const f32x2*>(cp + 2 * hq);
@@ -354,11 +354,13 @@ __global__ void __launch_bounds__(256) lstm_fwd_persist_kernel(PersistFwdArgs a)
       }
     }
 
-    if (t > 0) {
+    if (t > 0 || a.state) {
       // Wait for h_{t-1} (slot t).  A wave only multiplies its K quarter of h, i.e. the units of the
       // nslices/4 producer slices [wave * nslices/4, ...): it polls exactly those flags of the group's flag
       // line, lane i the flag of its i-th producer (sc1 loads: L1 bypassed, L2-served), and then loads --
-      // no workgroup barrier, the polling wave is the loading wave.
+      // no workgroup barrier, the polling wave is the loading wave.  (t = 0 with a state: h0 in slot 0 was written
+      // before the launch -- no wait, and no check of the pieces: an h0 whose bf16 bits are the sentinel is data)
+      const bool wait = t > 0;
       {
         const int npw = nslices >> 2;
         // flags: word i of the (t, M-tile) line.  Data polls: four words per producer, one from the LAST store
@@ -380,7 +382,7 @@ __global__ void __launch_bounds__(256) lstm_fwd_persist_kernel(PersistFwdArgs a)
         const unsigned not_yet = dpoll ? 0xffffffffu : 0u;
         const unsigned long long t_begin = wall_clock64();
         // (data_polls == 2, a test switch: no hint, load straight away -- every step then goes through the re-read path)
-        while (!(dpoll && CSN_DPOLL_MODE(a.data_polls) == 2) && !__all(__hip_atomic_load(fl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != not_yet)) {
+        while (wait && !(dpoll && CSN_DPOLL_MODE(a.data_polls) == 2) && !__all(__hip_atomic_load(fl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != not_yet)) {
           __builtin_amdgcn_s_sleep(1);
           if (__hip_atomic_load(a.error_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) break;
           if (wall_clock64() - t_begin > kSpinTimeoutTicks) {
@@ -430,7 +432,7 @@ __global__ void __launch_bounds__(256) lstm_fwd_persist_kernel(PersistFwdArgs a)
             }
             return __all(ok);
           };
-          if (__builtin_expect(!whole(), 0)) {
+          if (wait && __builtin_expect(!whole(), 0)) {
             const unsigned long long t_begin = wall_clock64();
             do {
               __builtin_amdgcn_s_sleep(1);
@@ -444,7 +446,7 @@ __global__ void __launch_bounds__(256) lstm_fwd_persist_kernel(PersistFwdArgs a)
           }
         }
 #ifdef CSN_SLAB_TAGS
-        if (dpoll) {        // h_{t-1} was tagged with bit 2 of t - 1; anything else in a non-sentinel piece is a stale occupant
+        if (dpoll && wait) {        // h_{t-1} was tagged with bit 2 of t - 1; anything else in a non-sentinel piece is a stale occupant
           const unsigned want = (unsigned)(((t - 1) >> 2) & 1);
           bool stale = false;
 #pragma unroll

@@ -87,6 +87,7 @@ class HipLSTM(nn.Module):
     """
 
     MAX_IDLE_PLANS = 4      # workspaces are large (10 GB at cfg2): keep only a few idle ones
+    _STATE_PLANS = False    # LSTM: plans created with CSN_LSTM_STATE
 
     def __init__(self, input_size, hidden_size, num_layers=1, compute_dtype=torch.bfloat16):
         super().__init__()
@@ -112,7 +113,7 @@ class HipLSTM(nn.Module):
             k, pl = idle.pop(0)
             self._plans[k].remove(pl)
         plan = cabi.LstmPlan(B, T, self.input_size, self.hidden_size, self.num_layers, self.compute_dtype, device,
-                             training=training)
+                             training=training, state=self._STATE_PLANS)
         pool.append(plan)
         return plan
 
@@ -128,6 +129,90 @@ class HipLSTM(nn.Module):
         training = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))
         y_last, y_all = _LstmFunction.apply(x, self, want_all, training, L, *params)
         return (y_all, y_last) if want_all else y_last
+
+
+class _LstmStateFunction(torch.autograd.Function):
+    """Stacked LSTM with an initial state in and the final state out: (x, h0, c0, params) -> (y_all, h_n, c_n).
+    The gradients always go to temporaries (never HipLSTM's direct_grads path, whose "one forward per step" contract
+    does not hold when the chunks of one recording are chained through their state)."""
+
+    @staticmethod
+    def forward(ctx, x, h0, c0, owner, training, L, *params):
+        w_ih, w_hh, b_ih, b_hh = params[0:L], params[L:2 * L], params[2 * L:3 * L], params[3 * L:4 * L]
+        plan = owner._checkout(x.shape[0], x.shape[1], x.device, training)
+        _, y_all, h_n, c_n = plan.forward(x, w_ih, w_hh, b_ih, b_hh, want_all=True, h0=h0, c0=c0, want_state=True)
+        ctx.lease, ctx.L = _Lease(plan), L
+        ctx.need = (x.requires_grad, h0 is not None and h0.requires_grad, c0 is not None and c0.requires_grad)
+        ctx.x_shape = x.shape
+        ctx.param_like = params
+        if not training:
+            ctx.lease.release()
+        return y_all, h_n, c_n
+
+    @staticmethod
+    def backward(ctx, dy_all, dh_n, dc_n):
+        L, plan = ctx.L, ctx.lease.plan
+        if plan is None:
+            raise RuntimeError("LSTM: second backward through one forward -- its workspace was handed back after the "
+                               "first (retain_graph / double backward are not supported)")
+        grads = [[torch.empty_like(p) for p in ctx.param_like[g * L:(g + 1) * L]] for g in range(4)]
+        dev = ctx.param_like[0].device
+        need_dx, need_dh0, need_dc0 = ctx.need
+        d = plan.desc
+        dx = torch.empty(ctx.x_shape, dtype=torch.float32, device=dev) if need_dx else None
+        dh0 = torch.empty((L, d.B, d.H), dtype=torch.float32, device=dev) if need_dh0 else None
+        dc0 = torch.empty((L, d.B, d.H), dtype=torch.float32, device=dev) if need_dc0 else None
+        plan.set_grad_callback(None)
+        plan.backward(None, dy_all, grads, dx=dx, dh_n=dh_n, dc_n=dc_n, dh0=dh0, dc0=dc0)
+        ctx.lease.release()
+        flat = [g for group in grads for g in group]
+        return (dx, dh0, dc0, None, None, None, *flat)
+
+
+class LSTM(HipLSTM):
+    """Drop-in for ``torch.nn.LSTM(input_size, hidden_size, num_layers, batch_first=True)`` on the HIP path, with the
+    whole of its call contract: ``forward(x[B,T,I], hx=None) -> (output[B,T,H], (h_n[L,B,H], c_n[L,B,H]))``, hx =
+    (h0, c0) or None (zeros); gradients reach x, h0, c0 and every parameter.  Parameter names, shapes and init are
+    nn.LSTM's, so state_dicts load both ways.  ``compute_dtype`` as in HipLSTM.
+
+    Runs on CSN_LSTM_STATE plans (include/csn_hip.h): with bf16 compute the path HipLSTM takes for the shape (the
+    weight-stationary kernels where they apply), with float32 the per-step cells (path 0).  With bf16 compute, h0 is rounded to bf16 as
+    every h is and c stays float32, so (h_n, c_n) fed back as hx continues a sequence exactly.
+    """
+
+    _STATE_PLANS = True
+
+    def __init__(self, input_size, hidden_size, num_layers=1, bias=True, batch_first=True, dropout=0.0,
+                 bidirectional=False, proj_size=0, compute_dtype=torch.bfloat16):
+        unsupported = [name for name, bad in (("bias=False", not bias), ("batch_first=False", not batch_first),
+                                              ("dropout != 0", dropout != 0), ("bidirectional=True", bidirectional),
+                                              ("proj_size != 0", proj_size != 0)) if bad]
+        if unsupported:
+            raise ValueError(f"LSTM: {', '.join(unsupported)} is not supported (batch-first, biased, unidirectional "
+                             f"stacks without projection or inter-layer dropout only)")
+        super().__init__(input_size, hidden_size, num_layers, compute_dtype=compute_dtype)
+        self.bias, self.batch_first, self.dropout, self.bidirectional, self.proj_size = True, True, 0.0, False, 0
+
+    def forward(self, x, hx=None):
+        if x.dim() != 3:
+            raise ValueError(f"LSTM: input must be batched [B, T, {self.input_size}] (batch_first); got shape "
+                             f"{list(x.shape)} (unbatched input is not supported)")
+        if x.shape[2] != self.input_size:
+            raise ValueError(f"LSTM: input has {x.shape[2]} features, expected {self.input_size}")
+        B, L, H = x.shape[0], self.num_layers, self.hidden_size
+        h0 = c0 = None
+        if hx is not None:
+            h0, c0 = hx
+            for name, t in (("h0", h0), ("c0", c0)):
+                if tuple(t.shape) != (L, B, H):
+                    raise ValueError(f"LSTM: {name} must be [num_layers, B, hidden_size] = {[L, B, H]}, got {list(t.shape)}")
+        if not x.is_cuda:
+            raise cabi.CsnError("LSTM runs on the GPU only (no CPU fallback); move the module and input to cuda")
+        params = [getattr(self, f"{n}_l{k}") for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh") for k in range(L)]
+        training = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params) or
+                                                any(t is not None and t.requires_grad for t in (h0, c0)))
+        y_all, h_n, c_n = _LstmStateFunction.apply(x, h0, c0, self, training, L, *params)
+        return y_all, (h_n, c_n)
 
 
 class Model(nn.Module):

@@ -36,7 +36,7 @@ enum csnStatus {
 enum csnDtype { CSN_F32 = 0, CSN_BF16 = 1 };
 
 /* ABI version of this header; bumped on any signature change. */
-#define CSN_ABI_VERSION 5
+#define CSN_ABI_VERSION 6
 int csn_abi_version(void);
 /* Thread-local message for the last non-zero status returned on this thread. */
 const char* csn_last_error(void);
@@ -72,7 +72,8 @@ int csn_eeg_filtfilt(const float* x, int S, int T, int C, const double* sos, int
                      float* y, void* scratch, csnStream_t stream);
 
 /* ------------------------------------------------------------------------------------
- * K3  stacked LSTM, zero initial state, gate order i,f,g,o, nn.LSTM parameter layout.
+ * K3  stacked LSTM, gate order i,f,g,o, nn.LSTM parameter layout; zero initial state, or (h0, c0) on a plan
+ * created with CSN_LSTM_STATE.
  * Replaces: nn.LSTM(input, hidden, num_layers, batch_first=True) forward/backward at
  * LSTMDistill.py:118,132 and LSTMDistillRetreival.py:91,103 (the body of the absent
  * models.lstm.Model, LstmDistillFromDinoV2Train.py:323).
@@ -94,6 +95,12 @@ typedef struct csnLstmDesc {
  * csn_lstm_backward needs.  (There is nothing like this in the reference: torch's nn.LSTM hides the same state in
  * cuDNN/MIOpen descriptors and the autograd graph.) */
 typedef struct csnLstmPlan csnLstmPlan;
+/* `training` may carry CSN_LSTM_STATE: the plan accepts the state arguments of csn_lstm_forward / csn_lstm_backward
+ * (h0, c0, h_n, c_n, dh_n, dc_n, dh0, dc0).  A CSN_BF16 state plan takes the path a plan without the bit takes
+ * (0-3); a CSN_F32 one runs as under CSN_NO_PERSIST (path 0): the exact-float32 weight-stationary path (4) takes no
+ * state.  A plan without the bit rejects every state argument and runs exactly as before.  The remaining bits:
+ * != 0 = training. */
+#define CSN_LSTM_STATE 0x100
 int csn_lstm_plan_create(const csnLstmDesc* d, int training, csnLstmPlan** out);
 void csn_lstm_plan_destroy(csnLstmPlan* plan);
 /* Bytes of device scratch ("workspace") a forward (+ backward) of this plan needs; 256-B aligned base.  The
@@ -125,24 +132,44 @@ int csn_lstm_workspace_init(const csnLstmPlan* plan, void* workspace, csnStream_
 /* x: element (b,t,i) at x[b*x_stride_b + t*x_stride_t + i] (float32).
  * w_ih/w_hh/b_ih/b_hh: [host] arrays of L device pointers to float32 parameters
  *   weight_ih_l{k}[4H,I_k], weight_hh_l{k}[4H,H], bias_ih_l{k}[4H], bias_hh_l{k}[4H].
+ * h0, c0: optional [L,B,H] float32 initial state (NULL = zeros), dense, 16-B aligned.
  * y_last: [B,H] float32 = output of the top layer at t = T-1.
- * y_all : optional (may be NULL) [B,T,H] float32, every step of the top layer. */
+ * y_all : optional (may be NULL) [B,T,H] float32, every step of the top layer.
+ * h_n, c_n: optional [L,B,H] float32 final state of every layer (may be NULL), dense, 16-B aligned.
+ * At least one of y_last, y_all, h_n, c_n must be given.
+ * State (only on a CSN_LSTM_STATE plan; any non-NULL state argument on another plan is CSN_ERR_INVALID_ARGUMENT):
+ *   CSN_BF16: h0 is rounded to bf16 as every h is; c0 stays float32.  h_n[l] is the upcast of the bf16 h that layer
+ *   l+1 and y_all consumed, so h_n[L-1] == y_last bit for bit; c_n is the float32 cell state.  Feeding (h_n, c_n) of
+ *   one call into the next as (h0, c0) is therefore exact: a sequence run as consecutive chunks carries the same
+ *   state as one run over all of it.  CSN_F32: everything float32.
+ *   With every state argument NULL, a CSN_BF16 state plan computes the same bits as a plan without the bit (a float32
+ *   one those of a plan under CSN_NO_PERSIST); once it has run a forward with a state, its later stateless forwards
+ *   on paths 2-3 re-zero slot 0 of h and c (two memsets per layer). */
 int csn_lstm_forward(csnLstmPlan* plan,
                      const float* x, int64_t x_stride_b, int64_t x_stride_t,
                      const float* const* w_ih, const float* const* w_hh,
                      const float* const* b_ih, const float* const* b_hh,
-                     void* workspace, float* y_last, float* y_all, csnStream_t stream);
+                     const float* h0, const float* c0,
+                     void* workspace, float* y_last, float* y_all,
+                     float* h_n, float* c_n, csnStream_t stream);
 
 /* dy_last: [B,H] float32 gradient w.r.t. y_last (may be NULL).
  * dy_all : optional [B,T,H] float32 gradient w.r.t. y_all (may be NULL).
+ * dh_n, dc_n: optional [L,B,H] float32 gradients w.r.t. h_n / c_n (may be NULL).
+ * At least one of dy_last, dy_all, dh_n, dc_n must be given.
  * dw_ih/dw_hh/db_ih/db_hh: [host] arrays of L device pointers, float32, OVERWRITTEN.
- * dx: optional [B,T,I] float32 (dense), gradient w.r.t. x (may be NULL). */
+ * dx: optional [B,T,I] float32 (dense), gradient w.r.t. x (may be NULL).
+ * dh0, dc0: optional [L,B,H] float32 gradients w.r.t. h0 / c0, OVERWRITTEN (may be NULL); written whether or not the
+ *   forward had a state (the gradient w.r.t. a zero state).  dh0[l] = dgates_l[t=0] W_hh_l from the operands the
+ *   recurrence uses (bf16 on CSN_BF16), float32 accumulate; dc0[l] = the cell-state gradient carried past step 0.
+ *   dW_hh includes dgates_0^T h0 and df_0 uses c0.  State arguments need a CSN_LSTM_STATE plan; all 16-B aligned. */
 int csn_lstm_backward(csnLstmPlan* plan,
                       const float* dy_last, const float* dy_all,
+                      const float* dh_n, const float* dc_n,
                       void* workspace,
                       float* const* dw_ih, float* const* dw_hh,
                       float* const* db_ih, float* const* db_hh,
-                      float* dx, csnStream_t stream);
+                      float* dx, float* dh0, float* dc0, csnStream_t stream);
 
 /* Gradient-ready notification (data-parallel training: the reference gets the overlap of its gradient all-reduce with
  * the backward from DistributedDataParallel's autograd hooks, LstmDistillation.py:445; this is the same hook at the C
