@@ -223,7 +223,20 @@ def init_params(input_size, hidden, num_layers, out_features, n_classes=None, se
 #   * backward: bf16 saved gates, tanh(c) recomputed from the float32 c, dc carried in float32, the gate gradients
 #     (dgates) rounded to bf16 -- that bf16 value feeds dh_{t-1} = dgates W_hh, dx = dgates W_ih (float32 out, the dy
 #     of the layer below), dW_ih = dgates^T inp (bf16 layer input), dW_hh = dgates^T h_{t-1} (bf16) and db.
-# With ``rounding=False`` every rounding is the identity and the results are those of lstm_forward / lstm_backward.
+# State (CSN_LSTM_STATE plans; the same on every path -- v1 cells, per-diagonal cells, weight-stationary -- so no switch):
+#   * h0 -> bf16 where the host writes slot 0 of h_all (lstm.hip:589 forward_v1, :894-895 forward_il, :1053-1054
+#     forward_persist); that value is step 0's recurrent operand and the h_{-1} of dW_hh (lstm.hip:695, :1188, :1348);
+#   * c0 float32, copied into slot 0 of c_all (lstm.hip:594, :898, :1060): step 0's c_prev and the backward's df_0
+#     (lstm.hip:671 v1, :1238 per-diagonal, lstm_bwd_persist.hip:204);
+#   * h_n = the bf16 h of slot T upcast (lstm.hip:1525), c_n = the float32 c of slot T (lstm.hip:1528);
+#   * dh_n[L-1] is added in float32 to row T-1 of the top layer's dy, after dy_last (lstm.hip:1588, :1593; it IS that row
+#     when dy_all and dy_last are NULL, :1597); dh_n[l < L-1] is added in float32 to row T-1 of layer l+1's float32 dx,
+#     i.e. the dy of layer l (lstm.hip:684, :1267, :1332);
+#   * dc_n seeds the float32 carried dc (lstm.hip:647, :1171, :1327); dc0 = that carry after step 0 (lstm.hip:1623);
+#   * dh0 = bf16 dgates_0 . bf16 W_hh with a float32 result (lstm_dh0_kernel, lstm.hip:224, launched at :1615-1619).
+#   NULL means zeros for every one of them.
+# With ``rounding=False`` every rounding is the identity and the results are those of lstm_forward / lstm_backward (with
+# a state: those of float64 torch.nn.LSTM given (h0, c0)).
 
 def bf16_round(a):
     """Round to the nearest bf16 value (ties to even) the way the kernels' ``(bf16_t)float`` cast does: the value is
@@ -250,9 +263,10 @@ def _rounders(rounding):
     return ident, ident
 
 
-def lstm_forward_bf16(x_btc, params, num_layers, rounding=True, acc=np.float64, defect=None):
-    """Forward of the bf16 kernels (rounding points above).  x[B,T,I]; params with torch.nn.LSTM key names.
-    Returns (y[B,T,H] of the top layer -- bf16 values --, saved) for :func:`lstm_backward_bf16`.
+def lstm_forward_bf16(x_btc, params, num_layers, rounding=True, acc=np.float64, defect=None, h0=None, c0=None):
+    """Forward of the bf16 kernels (rounding points above).  x[B,T,I]; params with torch.nn.LSTM key names; h0, c0:
+    [L,B,H] initial state or None (zeros).  Returns (y[B,T,H] of the top layer -- bf16 values --, saved) for
+    :func:`lstm_backward_bf16`; :func:`final_state` gives (h_n, c_n) from `saved`.
 
     For the tests of the tests: ``acc=np.float32`` runs the two products in float32 (a stand-in for a kernel's own
     accumulation noise); ``defect(kind, l, t, value, hs)`` may replace the recurrent operand (kind "h_prev", value
@@ -270,12 +284,13 @@ def lstm_forward_bf16(x_btc, params, num_layers, rounding=True, acc=np.float64, 
         else:
             bias = np.asarray(params[f"bias_ih_l{l}"], np.float64) + np.asarray(params[f"bias_hh_l{l}"], np.float64)
         H = w_hh.shape[1]
-        h = np.zeros((B, H))
-        c = np.zeros((B, H))
+        h = np.zeros((B, H)) if h0 is None else rb(np.asarray(h0)[l])
+        c = np.zeros((B, H)) if c0 is None else rf(np.asarray(c0)[l])
+        h_init, c_init = h, c
         hs = np.empty((B, T, H))
         gates = np.empty((B, T, 4 * H))
         cs = np.empty((B, T, H))
-        xp = (inp.reshape(B * T, -1).astype(acc) @ w_ih.T.astype(acc)).astype(np.float64).reshape(B, T, 4 * H)
+        xp =(inp.reshape(B * T, -1).astype(acc) @ w_ih.T.astype(acc)).astype(np.float64).reshape(B, T, 4 * H)
         w_hh_t = w_hh.T.astype(acc)
         for t in range(T):
             hp = h if defect is None else defect("h_prev", l, t, h, hs[:, :t])
@@ -296,23 +311,33 @@ def lstm_forward_bf16(x_btc, params, num_layers, rounding=True, acc=np.float64, 
             gates[:, t, 1 * H:2 * H] = f
             gates[:, t, 2 * H:3 * H] = g
             gates[:, t, 3 * H:4 * H] = o
-        saved.append(dict(inp=inp, hs=hs, cs=cs, gates=rb(gates), w_ih=w_ih, w_hh=w_hh))
+        saved.append(dict(inp=inp, hs=hs, cs=cs, gates=rb(gates), w_ih=w_ih, w_hh=w_hh, h0=h_init, c0=c_init))
         inp = hs
     return inp, saved
 
 
-def lstm_backward_bf16(dy_bth, saved, num_layers, rounding=True):
+def final_state(saved):
+    """(h_n, c_n) [L,B,H] of a :func:`lstm_forward_bf16` run: each layer's h (bf16 values) and c after the last step."""
+    return np.stack([s["hs"][:, -1] for s in saved]), np.stack([s["cs"][:, -1] for s in saved])
+
+
+def lstm_backward_bf16(dy_bth, saved, num_layers, rounding=True, dh_n=None, dc_n=None, return_state=False):
     """Backward of the bf16 kernels.  dy[B,T,H] = dLoss/dy of the top layer (float32 values, as the caller hands them
-    over).  Returns (dx[B,T,I], grads with torch key names, dgates per layer [B,T,4H] (bf16 values))."""
+    over: dy_all with dy_last added to row T-1); dh_n, dc_n: [L,B,H] gradients w.r.t. h_n / c_n or None (zeros).
+    Returns (dx[B,T,I], grads with torch key names, dgates per layer [B,T,4H] (bf16 values)); with ``return_state``
+    also dh0 and dc0 [L,B,H], the gradients w.r.t. the initial state (zero or not)."""
     rb, rf = _rounders(rounding)
     grads, dgates = {}, {}
-    dout = np.asarray(dy_bth, np.float64)
+    dout = np.array(dy_bth, np.float64)
+    B, T, H = saved[-1]["hs"].shape
+    dh0, dc0 = np.empty((num_layers, B, H)), np.empty((num_layers, B, H))
     for l in reversed(range(num_layers)):
+        if dh_n is not None:        # layer l's dy row T-1: dy_all + dy_last (top) or layer l+1's dx, then + dh_n[l]
+            dout[:, T - 1] = rf(dout[:, T - 1] + np.asarray(dh_n, np.float64)[l])
         s = saved[l]
         inp, hs, cs, gates, w_ih, w_hh = s["inp"], s["hs"], s["cs"], s["gates"], s["w_ih"], s["w_hh"]
-        B, T, H = hs.shape
         dh_rec = np.zeros((B, H))
-        dc_next = np.zeros((B, H))
+        dc_next = np.zeros((B, H)) if dc_n is None else rf(np.asarray(dc_n)[l])
         da_all = np.empty((B, T, 4 * H))
         for t in reversed(range(T)):
             i = gates[:, t, 0 * H:1 * H]
@@ -320,7 +345,7 @@ def lstm_backward_bf16(dy_bth, saved, num_layers, rounding=True):
             g = gates[:, t, 2 * H:3 * H]
             o = gates[:, t, 3 * H:4 * H]
             c = cs[:, t]
-            c_prev = cs[:, t - 1] if t > 0 else np.zeros_like(c)
+            c_prev = cs[:, t - 1] if t > 0 else s["c0"]
             tc = np.tanh(c)
             dh = dout[:, t] + dh_rec
             do = dh * tc
@@ -330,12 +355,15 @@ def lstm_backward_bf16(dy_bth, saved, num_layers, rounding=True):
             da_all[:, t] = da
             dh_rec = da @ w_hh
             dc_next = rf(dc * f)
+        dh0[l], dc0[l] = rf(dh_rec), dc_next          # past step 0
         da2 = da_all.reshape(B * T, 4 * H)
-        h_prev = np.concatenate([np.zeros((B, 1, H)), hs[:, :-1]], axis=1).reshape(B * T, H)
+        h_prev = np.concatenate([s["h0"][:, None], hs[:, :-1]], axis=1).reshape(B * T, H)
         grads[f"weight_ih_l{l}"] = da2.T @ inp.reshape(B * T, -1)
         grads[f"weight_hh_l{l}"] = da2.T @ h_prev
         grads[f"bias_ih_l{l}"] = da2.sum(axis=0)
         grads[f"bias_hh_l{l}"] = da2.sum(axis=0)
         dgates[l] = da_all
         dout = rf(da2 @ w_ih).reshape(B, T, -1)
+    if return_state:
+        return dout, grads, dgates, dh0, dc0
     return dout, grads, dgates

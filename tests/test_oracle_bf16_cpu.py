@@ -117,3 +117,19 @@ def test_report_names_gate_and_slice_of_a_weight_gradient():
         compare.check("dW", got, want, 1e-6, 1e-6, layout=compare.layout_of("lstm.weight_ih_l0"))
     assert "gate g units 64-95 cols 32-39" in str(e.value).split("worst blocks:\n")[1].splitlines()[0]
     assert "1 of " in str(e.value)
+
+
+@pytest.mark.parametrize("key", ["h_n", "c_n", "dh0", "dc0"])
+def test_state_layout_names_layer_and_row_tile(key):
+    """A defect planted in one row tile of one layer of a [L, B, H] state tensor (the ragged tile, rows 64-69, of layer
+    1), under accumulation-size noise everywhere: the emulator bound flags it and the report names that layer and tile."""
+    assert compare.layout_of(key) == "lbh"
+    rng = np.random.default_rng(5)
+    want = rng.standard_normal((3, B, H))
+    got = want * (1 + 1e-5 * rng.standard_normal(want.shape))
+    got[1, 64:] += 0.02 * np.abs(want).max() * rng.standard_normal((B - 64, H))
+    compare.check(key, got[[0, 2]], want[[0, 2]], *compare.bf16_emu_bound(key), layout="lbh")     # the other layers pass
+    with pytest.raises(AssertionError) as e:
+        compare.check(key, got, want, *compare.bf16_emu_bound(key), layout=compare.layout_of(key))
+    worst = str(e.value).split("worst blocks:\n")[1].splitlines()
+    assert all("layer 1 rows 64-69 units " in w for w in worst[:H // 32]), str(e.value)
