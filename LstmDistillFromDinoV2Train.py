@@ -96,6 +96,10 @@ def build_parser(flavour=PERILS):
     p.add_argument('--time_low', type=int, default=20)
     p.add_argument('--time_high', type=int, default=480)
     p.add_argument('--validation_frequency', type=int, default=5)
+    p.add_argument('--accum_steps', type=int, default=1,
+                   help='micro-batches per optimiser step: each batch runs as this many equal parts whose gradients are '
+                        'summed on the device (batch_size must be a multiple; a shorter last batch of an epoch is cut '
+                        'to one)')
     p.add_argument('--compat_label_bug', action='store_true',
                    help='reproduce the batch-local label lookup of transformEEGDataLSTMByList')
     return p
@@ -149,6 +153,8 @@ def main(argv=None, flavour=PERILS):
     from cerebralsignalnetworks_amd.losses import HyperParams
 
     FLAGS, _unparsed = build_parser(flavour).parse_known_args(argv)
+    if FLAGS.accum_steps < 1 or FLAGS.batch_size % FLAGS.accum_steps != 0:
+        raise SystemExit(f"--accum_steps {FLAGS.accum_steps}: must be >= 1 and divide --batch_size {FLAGS.batch_size}")
     rank, world, local = init_distributed()
     is_main = rank == 0
     if is_main:
@@ -195,12 +201,16 @@ def main(argv=None, flavour=PERILS):
         model.load_state_dict(sd, strict=False)
     sos = EEGFilters(FLAGS.fs, order=FLAGS.filter_order).sos if FLAGS.filter_order else None
     trainer = DistillTrainer(model, sos, loss=FLAGS.loss, lr=FLAGS.learning_rate, optimizer=FLAGS.optimizer,
-                             nepochs=max(FLAGS.num_epochs, HyperParams.warmup_teacher_temp_epochs + 1), kd_params=kd)
+                             nepochs=max(FLAGS.num_epochs, HyperParams.warmup_teacher_temp_epochs + 1), kd_params=kd,
+                             accum_steps=FLAGS.accum_steps)
 
-    def batches(idx, epoch, shuffle):
+    def batches(idx, epoch, shuffle, multiple_of=1):
         shard = idx[shard_indices(len(idx), epoch, FLAGS.seed, rank, world, shuffle=shuffle).to(device)]
         for s in range(0, len(shard), FLAGS.batch_size):
-            yield shard[s:s + FLAGS.batch_size]
+            b = shard[s:s + FLAGS.batch_size]
+            b = b[:len(b) - len(b) % multiple_of]       # (a shorter last batch: whole micro-batches only)
+            if len(b):
+                yield b
 
     def labels_of(ix):
         return [dataset.getLabelbyIndex(int(i)) for i in ix.cpu()]
@@ -208,7 +218,7 @@ def main(argv=None, flavour=PERILS):
     best_val_loss, best_val_loss_epoch, history = None, -1, []
     for EPOCH in range(FLAGS.num_epochs):
         losses = []
-        for b in batches(train_idx, EPOCH, True):
+        for b in batches(train_idx, EPOCH, True, FLAGS.accum_steps):
             losses.append(trainer.train_step(dataset.eeg_all[b], dataset.features_all[b], dataset.labels_dev[b], EPOCH))
         trainer.check_device_status()      # per epoch: a timed-out in-kernel hand-off must not pass silently
         epoch_loss = float(torch.stack(losses).mean().item())                    # one sync per epoch, not per step

@@ -66,6 +66,7 @@ def main(argv=None):
     from cerebralsignalnetworks_amd.dataset import EEGDataset
     from cerebralsignalnetworks_amd.dino import (DINOHead, DINOLoss, MultiCropWrapper, cosine_scheduler, ema_update,
                                                  temporal_crops)
+    from cerebralsignalnetworks_amd.lstm_model import HipLSTM
     from cerebralsignalnetworks_amd.trainer import FlatGrads, check_device_status, shard_indices, split_indices
 
     FLAGS, _ = build_parser().parse_known_args(argv)
@@ -98,6 +99,11 @@ def main(argv=None):
         for p in student.parameters():
             dist.broadcast(p.data, src=0)
     grads = FlatGrads(student.parameters())
+    # the student runs 2 + local_crops_number forwards per step through one set of parameters: each backward adds its
+    # LSTM gradients straight into the flat buffer (CSN_GRAD_ACCUMULATE) instead of 4 L temporaries + autograd's adds
+    for mod in student.modules():
+        if isinstance(mod, HipLSTM):
+            mod.direct_grads = "accumulate"
 
     dino_loss = DINOLoss(FLAGS.out_dim, FLAGS.local_crops_number + 2, FLAGS.warmup_teacher_temp, FLAGS.teacher_temp,
                          FLAGS.warmup_teacher_temp_epochs, FLAGS.epochs).to(device)

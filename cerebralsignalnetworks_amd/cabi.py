@@ -17,6 +17,7 @@ CSN_F32, CSN_BF16 = 0, 1
 STATUS_TIMEOUT, STATUS_NONFINITE, STATUS_STALE_SLOT = 1, 2, 4      # bits of csn_lstm_status_read (include/csn_hip.h)
 ABI_VERSION = 6
 LSTM_STATE = 0x100      # csn_lstm_plan_create flag CSN_LSTM_STATE (include/csn_hip.h)
+GRAD_OVERWRITE, GRAD_ACCUMULATE = 0, 1      # csn_lstm_plan_set_grad_mode (include/csn_hip.h)
 
 _c_void_p, _c_int, _c_i64, _c_size_t, _c_float = (ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
                                                   ctypes.c_size_t, ctypes.c_float)
@@ -44,6 +45,7 @@ SIGNATURES = {
     "csn_lstm_plan_dgates_copies": (_c_int, [_c_void_p]),
     "csn_lstm_plan_kernel_name": (ctypes.c_char_p, [_c_void_p, _c_int]),
     "csn_lstm_plan_set_grad_callback": (_c_int, [_c_void_p, _c_void_p, _c_void_p]),
+    "csn_lstm_plan_set_grad_mode": (_c_int, [_c_void_p, _c_int]),
     "csn_lstm_workspace_bytes": (_c_size_t, [ctypes.POINTER(LstmDesc), _c_int]),
     "csn_lstm_forward": (_c_int, [_c_void_p, _c_void_p, _c_i64, _c_i64,
                                   ctypes.POINTER(_c_void_p), ctypes.POINTER(_c_void_p),
@@ -286,6 +288,12 @@ class LstmPlan:
         _check(load().csn_lstm_plan_set_grad_callback(self._plan, ctypes.cast(self._grad_cb, _c_void_p) if fn is not None
                                                       else None, None))
 
+    def set_grad_mode(self, accumulate):
+        """accumulate=True: later backward() calls ADD the weight / bias gradients to what their tensors hold (every
+        element becomes fl32(prev + g), g the value the overwriting mode stores: the bits of ``p.grad += g``); False (the
+        plan's default): they overwrite.  Sticky until set again."""
+        _check(load().csn_lstm_plan_set_grad_mode(self._plan, GRAD_ACCUMULATE if accumulate else GRAD_OVERWRITE))
+
     def dgates_copies(self):
         """Copies of the gate gradients the last backward wrote per step (csn_hip.h): 2, or 0 before any backward."""
         return load().csn_lstm_plan_dgates_copies(self._plan)
@@ -327,8 +335,9 @@ class LstmPlan:
         return t.to(device=self.device, dtype=torch.float32).contiguous()
 
     def backward(self, dy_last, dy_all, grads, dx=None, dh_n=None, dc_n=None, dh0=None, dc0=None):
-        """grads: 4 lists (dw_ih, dw_hh, db_ih, db_hh) of float32 device tensors, overwritten.  dh_n / dc_n: [L,B,H]
-        incoming gradients of the final state or None; dh0 / dc0: [L,B,H] float32 outputs (overwritten) or None."""
+        """grads: 4 lists (dw_ih, dw_hh, db_ih, db_hh) of float32 device tensors: overwritten, or added to after
+        set_grad_mode(True) -- the mode governs these four groups only.  dx and dh0 / dc0 ([L,B,H] float32 outputs, or
+        None) are overwritten in both modes.  dh_n / dc_n: [L,B,H] incoming gradients of the final state or None."""
         if dy_last is not None:
             dy_last = dy_last.float().contiguous()
         if dy_all is not None:

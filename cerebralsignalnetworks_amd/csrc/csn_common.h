@@ -152,11 +152,13 @@ int launch_cast(const float* src, void* dst, int64_t n, int dtype, hipStream_t s
 // dst(f32) = (float)src(T)
 int launch_upcast(const void* src, int dtype, float* dst, int64_t n, hipStream_t st);
 int launch_add_vec(const float* a, const float* b, float* out, int64_t n, hipStream_t st);
-// out[i] = (accumulate ? out[i] : 0) + sum_s slabs[s*stride + i]
-int launch_reduce_slabs(const float* slabs, int64_t stride, int S, float* out, int64_t n, int accumulate, hipStream_t st);
-// out[N] = column sums of X[R,N] (dtype), deterministic; scratch >= colsum_scratch_bytes(N)
+// g = sum_s slabs[s*stride + i] (fixed order); out[i] = accumulate ? out[i] + g : g, and the same into out2 (may be NULL)
+int launch_reduce_slabs(const float* slabs, int64_t stride, int S, float* out, float* out2, int64_t n, int accumulate,
+                        hipStream_t st);
+// out[N] (and out2[N], may be NULL) = or += column sums of X[R,N] (dtype), deterministic; scratch >= colsum_scratch_bytes(N)
 size_t colsum_scratch_bytes(int64_t N);
-int launch_colsum(const void* X, int64_t R, int64_t N, int dtype, float* out, void* scratch, hipStream_t st);
+int launch_colsum(const void* X, int64_t R, int64_t N, int dtype, float* out, float* out2, int accumulate, void* scratch,
+                  hipStream_t st);
 int colsum_chunks();
 int launch_colsum_partial(const void* X, int64_t R, int64_t N, int dtype, void* scratch, hipStream_t st);
 // split-K slabs of C[M,N] = A[K,M]^T B[K,N] into `slabs` ([S][M*N] f32); returns S through S_out

@@ -1384,5 +1384,5 @@ extern "C" int csn_gemm_tn(const void* A, const void* B, float* C, int64_t M, in
   hipStream_t st = as_stream(stream);
   int S = 1;
   if (int rc = launch_gemm_tn_slabs(A, B, (float*)scratch, M, N, K, dtype, st, &S, nullptr, nullptr, options_from_env())) return rc;
-  return launch_reduce_slabs((const float*)scratch, M * N, S, C, M * N, 0, st);
+  return launch_reduce_slabs((const float*)scratch, M * N, S, C, nullptr, M * N, 0, st);
 }

@@ -262,14 +262,15 @@ __global__ void __launch_bounds__(256) lstm_dh0_kernel(const T* __restrict__ dg,
     }
 }
 
-// out[n] = part[0][n] + part[1][n] + ... (fixed order): the row groups' bias-gradient partial sums of the float32 backward
-__global__ void sum_rows_kernel(const float* __restrict__ part, int P, int64_t n, float* __restrict__ out, float* __restrict__ out2) {
+// out[n] = part[0][n] + part[1][n] + ... (fixed order): the row groups' bias-gradient partial sums of the float32 backward;
+// accumulate: each destination's own previous contents join last
+__global__ void sum_rows_kernel(const float* __restrict__ part, int P, int64_t n, float* out, float* out2, int accumulate) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   float s = 0.f;
   for (int p = 0; p < P; ++p) s += part[(int64_t)p * n + i];
-  out[i] = s;
-  out2[i] = s;
+  out[i] = accumulate ? out[i] + s : s;
+  out2[i] = accumulate ? out2[i] + s : s;
 }
 
 static inline unsigned grid_for(int64_t n) {
@@ -362,6 +363,7 @@ struct csnLstmPlan {
   int dgates_copies = 0;      // what the last backward wrote per step (csn_lstm_plan_dgates_copies)
   csnGradReadyFn grad_cb = nullptr;      // csn_lstm_plan_set_grad_callback
   void* grad_cb_user = nullptr;
+  int grad_accumulate = 0;               // csn_lstm_plan_set_grad_mode: dw / db are added to, not overwritten
   void grads_ready(int layer) const {
     if (grad_cb != nullptr) grad_cb(grad_cb_user, layer);
   }
@@ -452,6 +454,13 @@ extern "C" int csn_lstm_plan_set_grad_callback(csnLstmPlan* P, csnGradReadyFn fn
   CSN_REQUIRE(P != nullptr, "csn_lstm_plan_set_grad_callback: null plan");
   P->grad_cb = fn;
   P->grad_cb_user = fn ? user : nullptr;
+  return CSN_OK;
+}
+
+extern "C" int csn_lstm_plan_set_grad_mode(csnLstmPlan* P, int mode) {
+  CSN_REQUIRE(P != nullptr, "csn_lstm_plan_set_grad_mode: null plan");
+  CSN_REQUIRE(mode == CSN_GRAD_OVERWRITE || mode == CSN_GRAD_ACCUMULATE, "csn_lstm_plan_set_grad_mode: unknown mode %d", mode);
+  P->grad_accumulate = mode == CSN_GRAD_ACCUMULATE;
   return CSN_OK;
 }
 
@@ -548,11 +557,12 @@ extern "C" size_t csn_lstm_workspace_bytes(const csnLstmDesc* d, int training) {
 }
 
 // C[M,N] = A[K,M]^T B[K,N] through the split-K slabs + their fixed-order reduction (the body of csn_gemm_tn)
+// accumulate: C's previous contents join the reduced sum last (CSN_GRAD_ACCUMULATE)
 static int gemm_tn_full(const void* A, const void* B, float* C, int64_t M, int64_t N, int64_t K, int dtype, void* scratch,
-                        hipStream_t st, const Options& opt) {
+                        int accumulate, hipStream_t st, const Options& opt) {
   int S = 1;
   if (int rc = launch_gemm_tn_slabs(A, B, (float*)scratch, M, N, K, dtype, st, &S, nullptr, nullptr, opt)) return rc;
-  return launch_reduce_slabs((const float*)scratch, M * N, S, C, M * N, 0, st);
+  return launch_reduce_slabs((const float*)scratch, M * N, S, C, nullptr, M * N, accumulate, st);
 }
 
 // =============================================================================================
@@ -641,6 +651,7 @@ static int backward_v1(Plan& P, char* ws, const float* dy_last, const float* dy_
   const int64_t G = 4 * (int64_t)H, TB = (int64_t)T * B;
   const size_t es = dtype_size(dt);
   const int Cz = P.opt.chunk, lag = Cz;
+  const int acc = P.grad_accumulate;
   int rc;
   for (int l = 0; l < NL; ++l) {
     if (dc_n)      // the carried dc starts as the gradient w.r.t. c_n; after step 0 it is the gradient w.r.t. c0
@@ -692,10 +703,10 @@ static int backward_v1(Plan& P, char* ws, const float* dy_last, const float* dy_
     const int64_t I = l == 0 ? d->I : H;
     const void* inp = l == 0 ? (const void*)(ws + w.x_c)
                              : (const void*)(ws + w.layer[l - 1].h_all + (size_t)B * H * es);
-    if ((rc = gemm_tn_full(ws + L.dgates, ws + L.h_all, dw_hh[l], G, H, TB, dt, ws + w.tn_scratch, st, P.opt))) return rc;
-    if ((rc = gemm_tn_full(ws + L.dgates, inp, dw_ih[l], G, I, TB, dt, ws + w.tn_scratch, st, P.opt))) return rc;
-    if ((rc = launch_colsum(ws + L.dgates, TB, G, dt, db_ih[l], ws + w.colsum, st))) return rc;
-    CSN_HIP_CHECK(hipMemcpyAsync(db_hh[l], db_ih[l], (size_t)G * 4, hipMemcpyDeviceToDevice, st));
+    if ((rc = gemm_tn_full(ws + L.dgates, ws + L.h_all, dw_hh[l], G, H, TB, dt, ws + w.tn_scratch, acc, st, P.opt))) return rc;
+    if ((rc = gemm_tn_full(ws + L.dgates, inp, dw_ih[l], G, I, TB, dt, ws + w.tn_scratch, acc, st, P.opt))) return rc;
+    // db_ih and db_hh both come out of the reduction (each adds to its own previous contents under CSN_GRAD_ACCUMULATE)
+    if ((rc = launch_colsum(ws + L.dgates, TB, G, dt, db_ih[l], db_hh[l], acc, ws + w.colsum, st))) return rc;
     P.grads_ready(l);
   }
   if (dx) {
@@ -808,7 +819,7 @@ static int backward_f32p(Plan& P, char* ws, const float* dy_last, const float* d
       ++n_launch;
     }
     // bias gradients: the row groups' partial sums in fixed order (db_ih = db_hh)
-    sum_rows_kernel<<<(unsigned)((G + 255) / 256), 256, 0, st>>>((const float*)(ws + w.f32_bias_part), MTt * 4, G, db_ih[l], db_hh[l]);
+    sum_rows_kernel<<<(unsigned)((G + 255) / 256), 256, 0, st>>>((const float*)(ws + w.f32_bias_part), MTt * 4, G, db_ih[l], db_hh[l], P.grad_accumulate);
     CSN_LAUNCH_CHECK();
     // gradient w.r.t. this layer's input = dy of the layer below, whole sequence
     if (l > 0 && (rc = gemm_nt(ws + L.dgates, ws + L.wiht, nullptr, ws + L.dx, TB, H, G, CSN_F32, CSN_F32, 0, st, P.opt))) return rc;
@@ -821,8 +832,8 @@ static int backward_f32p(Plan& P, char* ws, const float* dy_last, const float* d
     const LayerWs& L = w.layer[l];
     const int64_t I = l == 0 ? d->I : H;
     const void* inp = l == 0 ? (const void*)(ws + w.x_c) : (const void*)(ws + w.layer[l - 1].h_all + (size_t)B * H * 4);
-    if ((rc = gemm_tn_full(ws + L.dgates, ws + L.h_all, dw_hh[l], G, H, TB, CSN_F32, ws + w.tn_scratch, st, P.opt))) return rc;
-    if ((rc = gemm_tn_full(ws + L.dgates, inp, dw_ih[l], G, I, TB, CSN_F32, ws + w.tn_scratch, st, P.opt))) return rc;
+    if ((rc = gemm_tn_full(ws + L.dgates, ws + L.h_all, dw_hh[l], G, H, TB, CSN_F32, ws + w.tn_scratch, P.grad_accumulate, st, P.opt))) return rc;
+    if ((rc = gemm_tn_full(ws + L.dgates, inp, dw_ih[l], G, I, TB, CSN_F32, ws + w.tn_scratch, P.grad_accumulate, st, P.opt))) return rc;
     P.grads_ready(l);
   }
   if (dx) {
@@ -1183,21 +1194,22 @@ static int backward_il(Plan& P, char* ws, const float* dy_last, const float* dy_
     const void* inp = l == 0 ? (const void*)(ws + w.x_c)
                              : (const void*)((const bf16_t*)(ws + w.layer[l - 1].h_all) + (size_t)B * H);
     float* slabs = (float*)(ws + w.tn_scratch);
+    const int acc = P.grad_accumulate;
     int S = 1, r;
     int cs_done = 0, S_cs = 1;
     if ((r = launch_gemm_tn_slabs(ws + L.dgates, ws + L.h_all, slabs, G, H, TB, CSN_BF16, side, &S, (float*)(ws + w.colsum), &cs_done, P.opt))) return r;
     S_cs = S;
-    if ((r = launch_reduce_slabs_unperm(slabs, G * H, S, H, H, dw_hh[l], side))) return r;
+    if ((r = launch_reduce_slabs_unperm(slabs, G * H, S, H, H, dw_hh[l], nullptr, acc, side))) return r;
     if ((r = launch_gemm_tn_slabs(ws + L.dgates, inp, slabs, G, I, TB, CSN_BF16, side, &S, nullptr, nullptr, P.opt))) return r;
-    if ((r = launch_reduce_slabs_unperm(slabs, G * I, S, H, I, dw_ih[l], side))) return r;
+    if ((r = launch_reduce_slabs_unperm(slabs, G * I, S, H, I, dw_ih[l], nullptr, acc, side))) return r;
     // bias gradient = column sums of dgates: partial sums come out of the dW_hh GEMM when its kernel provides them
     if (!cs_done) {
       if ((r = launch_colsum_partial(ws + L.dgates, TB, G, CSN_BF16, ws + w.colsum, side))) return r;
       S_cs = colsum_chunks();
     }
-    if ((r = launch_reduce_slabs_unperm((const float*)(ws + w.colsum), G, S_cs, H, 1, db_ih[l], side)))
+    // db_ih and db_hh both come out of the reduction (each adds to its own previous contents under CSN_GRAD_ACCUMULATE)
+    if ((r = launch_reduce_slabs_unperm((const float*)(ws + w.colsum), G, S_cs, H, 1, db_ih[l], db_hh[l], acc, side)))
       return r;
-    CSN_HIP_CHECK(hipMemcpyAsync(db_hh[l], db_ih[l], (size_t)G * 4, hipMemcpyDeviceToDevice, side));
     return CSN_OK;
   };
 
@@ -1343,20 +1355,21 @@ static int backward_persist(Plan& P, char* ws, const float* dy_last, const float
     const void* inp = l == 0 ? (const void*)(ws + w.x_c)
                              : (const void*)((const bf16_t*)(ws + w.layer[l - 1].h_all) + (size_t)B * H);
     float* slabs = (float*)(ws + w.tn_scratch);
+    const int acc = P.grad_accumulate;
     int S = 1, r;
     int cs_done = 0, S_cs = 1;
     if ((r = launch_gemm_tn_slabs(ws + L.dgates, ws + L.h_all, slabs, G, H, TB, CSN_BF16, st, &S, (float*)(ws + w.colsum), &cs_done, P.opt))) return r;
     S_cs = S;
-    if ((r = launch_reduce_slabs_unperm(slabs, G * H, S, H, H, dw_hh[l], st))) return r;
+    if ((r = launch_reduce_slabs_unperm(slabs, G * H, S, H, H, dw_hh[l], nullptr, acc, st))) return r;
     if ((r = launch_gemm_tn_slabs(ws + L.dgates, inp, slabs, G, I, TB, CSN_BF16, st, &S, nullptr, nullptr, P.opt))) return r;
-    if ((r = launch_reduce_slabs_unperm(slabs, G * I, S, H, I, dw_ih[l], st))) return r;
+    if ((r = launch_reduce_slabs_unperm(slabs, G * I, S, H, I, dw_ih[l], nullptr, acc, st))) return r;
     // bias gradient = column sums of dgates: partial sums come out of the dW_hh GEMM when its kernel provides them
     if (!cs_done) {
       if ((r = launch_colsum_partial(ws + L.dgates, TB, G, CSN_BF16, ws + w.colsum, st))) return r;
       S_cs = colsum_chunks();
     }
-    if ((r = launch_reduce_slabs_unperm((const float*)(ws + w.colsum), G, S_cs, H, 1, db_ih[l], st))) return r;
-    CSN_HIP_CHECK(hipMemcpyAsync(db_hh[l], db_ih[l], (size_t)G * 4, hipMemcpyDeviceToDevice, st));
+    // db_ih and db_hh both come out of the reduction (each adds to its own previous contents under CSN_GRAD_ACCUMULATE)
+    if ((r = launch_reduce_slabs_unperm((const float*)(ws + w.colsum), G, S_cs, H, 1, db_ih[l], db_hh[l], acc, st))) return r;
     return CSN_OK;
   };
   PersistBwdArgs a{};
@@ -1557,8 +1570,12 @@ extern "C" int csn_lstm_backward(csnLstmPlan* Pp, const float* dy_last, const fl
     const char* names[4] = {"dh_n", "dc_n", "dh0", "dc0"};
     if (int rc = check_state_args(P, "csn_lstm_backward", ptrs, names, 4)) return rc;
   }
-  for (int l = 0; l < d->L; ++l)
+  for (int l = 0; l < d->L; ++l) {
     CSN_REQUIRE(dw_ih[l] && dw_hh[l] && db_ih[l] && db_hh[l], "csn_lstm_backward: null gradient pointer, layer %d", l);
+    // (accumulating, one buffer for both biases would receive the sum twice)
+    CSN_REQUIRE(!P.grad_accumulate || db_ih[l] != db_hh[l],
+                "csn_lstm_backward: db_ih and db_hh of layer %d are one buffer under CSN_GRAD_ACCUMULATE", l);
+  }
   int dev = -1;
   CSN_HIP_CHECK(hipGetDevice(&dev));
   CSN_REQUIRE(dev == P.device, "csn_lstm_backward: plan was created on device %d, current device is %d", P.device, dev);

@@ -159,6 +159,6 @@ int launch_permute_rows_cast(const float* src, int64_t H, int64_t I, void* dst, 
 int launch_transpose_perm_cast(const float* src, int64_t H, int64_t I, void* dst, hipStream_t st);
 int launch_bias_perm_sum(const float* a, const float* b, int64_t H, float* dst, hipStream_t st);
 int launch_reduce_slabs_unperm(const float* slabs, int64_t slab_stride, int S, int64_t H, int64_t C, float* out,
-                               hipStream_t st);
+                               float* out2, int accumulate, hipStream_t st);
 
 }  // namespace csn

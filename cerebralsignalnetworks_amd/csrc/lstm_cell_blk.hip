@@ -100,16 +100,19 @@ __global__ void bias_perm_sum_kernel(const float* __restrict__ a, const float* _
   if (i < 4 * H) dst[i] = a[std_row(i, H)] + b[std_row(i, H)];
 }
 
-// out[std_row(n')][c] = sum_s slabs[s][n'][c]        (un-permute weight / bias gradients)
+// out[std_row(n')][c] = sum_s slabs[s][n'][c]        (un-permute weight / bias gradients); accumulate: the previous
+// contents join last (out = prev + sum); out2 (may be NULL): a second destination with its own previous contents
 __global__ void reduce_slabs_unperm_kernel(const float* __restrict__ slabs, int64_t slab_stride, int S, int64_t H,
-                                           int64_t C, float* __restrict__ out) {
+                                           int64_t C, float* out, float* out2, int accumulate) {
   const int64_t total = 4 * H * C;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
     const int64_t n = i / C, c = i % C;
     float acc = 0.0f;
     for (int s = 0; s < S; ++s) acc += slabs[(int64_t)s * slab_stride + i];
-    out[std_row(n, H) * C + c] = acc;
+    const int64_t o = std_row(n, H) * C + c;
+    out[o] = accumulate ? out[o] + acc : acc;
+    if (out2 != nullptr) out2[o] = accumulate ? out2[o] + acc : acc;
   }
 }
 
@@ -330,8 +333,8 @@ int launch_bias_perm_sum(const float* a, const float* b, int64_t H, float* dst, 
   return CSN_OK;
 }
 int launch_reduce_slabs_unperm(const float* slabs, int64_t slab_stride, int S, int64_t H, int64_t C, float* out,
-                               hipStream_t st) {
-  reduce_slabs_unperm_kernel<<<cap_grid(4 * H * C), 256, 0, st>>>(slabs, slab_stride, S, H, C, out);
+                               float* out2, int accumulate, hipStream_t st) {
+  reduce_slabs_unperm_kernel<<<cap_grid(4 * H * C), 256, 0, st>>>(slabs, slab_stride, S, H, C, out, out2, accumulate);
   CSN_LAUNCH_CHECK();
   return CSN_OK;
 }

@@ -133,19 +133,23 @@ int launch_add_vec(const float* a, const float* b, float* out, int64_t n, hipStr
 }
 
 // ---- slab reduction (split-K combine), fixed summation order => bitwise reproducible ---------
-__global__ void reduce_slabs_kernel(const float* __restrict__ slabs, int64_t stride_s, int S, float* __restrict__ out,
+// accumulate: the previous contents join LAST, out = fl32(prev + sum_s slabs) -- what `p.grad += g` computes from the
+// value the overwriting form stores (CSN_GRAD_ACCUMULATE, csn_hip.h).  out2 (may be NULL): a second destination with its
+// own previous contents (db_hh beside db_ih).
+__global__ void reduce_slabs_kernel(const float* __restrict__ slabs, int64_t stride_s, int S, float* out, float* out2,
                                     int64_t n, int accumulate) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    float acc = accumulate ? out[i] : 0.0f;
+    float acc = 0.0f;
     for (int s = 0; s < S; ++s) acc += slabs[(int64_t)s * stride_s + i];
-    out[i] = acc;
+    out[i] = accumulate ? out[i] + acc : acc;
+    if (out2 != nullptr) out2[i] = accumulate ? out2[i] + acc : acc;
   }
 }
 
-int launch_reduce_slabs(const float* slabs, int64_t stride, int S, float* out, int64_t n, int accumulate,
+int launch_reduce_slabs(const float* slabs, int64_t stride, int S, float* out, float* out2, int64_t n, int accumulate,
                         hipStream_t st) {
-  reduce_slabs_kernel<<<capped_grid(n, 256), 256, 0, st>>>(slabs, stride, S, out, n, accumulate);
+  reduce_slabs_kernel<<<capped_grid(n, 256), 256, 0, st>>>(slabs, stride, S, out, out2, n, accumulate);
   CSN_LAUNCH_CHECK();
   return CSN_OK;
 }
@@ -211,9 +215,10 @@ int launch_colsum_partial(const void* X, int64_t R, int64_t N, int dtype, void* 
   return CSN_OK;
 }
 
-int launch_colsum(const void* X, int64_t R, int64_t N, int dtype, float* out, void* scratch, hipStream_t st) {
+int launch_colsum(const void* X, int64_t R, int64_t N, int dtype, float* out, float* out2, int accumulate, void* scratch,
+                  hipStream_t st) {
   if (int rc = launch_colsum_partial(X, R, N, dtype, scratch, st)) return rc;
-  return launch_reduce_slabs((const float*)scratch, N, kColsumChunks, out, N, 0, st);
+  return launch_reduce_slabs((const float*)scratch, N, kColsumChunks, out, out2, N, accumulate, st);
 }
 
 }  // namespace csn

@@ -32,6 +32,16 @@ class _Lease:
     __del__ = release
 
 
+def _direct_grads(owner, params):
+    """-> (direct, accumulate): does this backward write into the parameters' .grad, and does it add to them?
+    ``owner.direct_grads``: False = temporaries handed to autograd; True = overwrite .grad (one forward per step);
+    "accumulate" = add to .grad in the library (any number of forwards between two zeroings of the buffer)."""
+    mode = owner.direct_grads
+    if not mode or not all(p.grad is not None and p.grad.is_contiguous() and p.grad.dtype == torch.float32 for p in params):
+        return False, False
+    return True, mode == "accumulate"
+
+
 class _LstmFunction(torch.autograd.Function):
     """Stacked LSTM over libcsn_hip.  A training forward keeps its state in a workspace that stays
     checked out until the matching backward has run, so several forwards (e.g. the multi-crop views of
@@ -60,17 +70,18 @@ class _LstmFunction(torch.autograd.Function):
             raise RuntimeError("HipLSTM: second backward through one forward -- its workspace was handed back after the "
                                "first (retain_graph / double backward are not supported)")
         owner = ctx.owner
-        direct = owner.direct_grads and all(p.grad is not None and p.grad.is_contiguous() and p.grad.dtype == torch.float32
-                                            for p in ctx.param_like)
+        direct, accumulate = _direct_grads(owner, ctx.param_like)
         if direct:
-            # the library OVERWRITES its gradient outputs: written straight into the parameters' .grad (the views into the
-            # trainer's flat buffer) this forward's contribution needs no temporaries and no accumulation pass -- valid
-            # while this is the only forward of the step that uses these parameters (the trainer's contract)
+            # written straight into the parameters' .grad (the views into the trainer's flat buffer) this forward's
+            # contribution needs no temporaries and no accumulation pass.  direct_grads = True: the library OVERWRITES --
+            # valid while this is the only forward of the step that uses these parameters; "accumulate": it adds
+            # (CSN_GRAD_ACCUMULATE: the bits of autograd's p.grad += g), for any number of forwards per step
             grads = [[p.grad for p in ctx.param_like[g * L:(g + 1) * L]] for g in range(4)]
         else:
             grads = [[torch.empty_like(p) for p in ctx.param_like[g * L:(g + 1) * L]] for g in range(4)]
         dx = torch.empty(ctx.x_shape, dtype=torch.float32, device=dy_last.device) if ctx.need_dx else None
         plan.set_grad_callback(owner.grad_ready_hook if direct else None)
+        plan.set_grad_mode(accumulate)      # on every backward: plans are shared between calls
         plan.backward(dy_last, dy_all if ctx.want_all else None, grads, dx=dx)
         ctx.lease.release()
         if direct:
@@ -99,6 +110,8 @@ class HipLSTM(nn.Module):
         self._plans = {}        # key -> list of plans; plan.busy marks a forward awaiting its backward
         # set by a trainer that owns the gradient buffers (trainer.DistillTrainer): the backward writes each parameter's
         # gradient straight into its .grad and calls grad_ready_hook(layer) as soon as a layer's gradients are enqueued
+        # direct_grads: False = temporaries; True = .grad is overwritten (one forward per step); "accumulate" = .grad is
+        # added to in the library, so several forwards per step (views, micro-batches, chunks of a recording) are summed
         self.direct_grads = False
         self.grad_ready_hook = None
 
@@ -133,15 +146,16 @@ class HipLSTM(nn.Module):
 
 class _LstmStateFunction(torch.autograd.Function):
     """Stacked LSTM with an initial state in and the final state out: (x, h0, c0, params) -> (y_all, h_n, c_n).
-    The gradients always go to temporaries (never HipLSTM's direct_grads path, whose "one forward per step" contract
-    does not hold when the chunks of one recording are chained through their state)."""
+    The gradients go to temporaries, or with ``direct_grads = "accumulate"`` are added straight to the parameters' .grad
+    (never the overwriting ``direct_grads = True`` form, whose "one forward per step" contract does not hold when the
+    chunks of one recording are chained through their state)."""
 
     @staticmethod
     def forward(ctx, x, h0, c0, owner, training, L, *params):
         w_ih, w_hh, b_ih, b_hh = params[0:L], params[L:2 * L], params[2 * L:3 * L], params[3 * L:4 * L]
         plan = owner._checkout(x.shape[0], x.shape[1], x.device, training)
         _, y_all, h_n, c_n = plan.forward(x, w_ih, w_hh, b_ih, b_hh, want_all=True, h0=h0, c0=c0, want_state=True)
-        ctx.lease, ctx.L = _Lease(plan), L
+        ctx.lease, ctx.L, ctx.owner = _Lease(plan), L, owner
         ctx.need = (x.requires_grad, h0 is not None and h0.requires_grad, c0 is not None and c0.requires_grad)
         ctx.x_shape = x.shape
         ctx.param_like = params
@@ -155,16 +169,24 @@ class _LstmStateFunction(torch.autograd.Function):
         if plan is None:
             raise RuntimeError("LSTM: second backward through one forward -- its workspace was handed back after the "
                                "first (retain_graph / double backward are not supported)")
-        grads = [[torch.empty_like(p) for p in ctx.param_like[g * L:(g + 1) * L]] for g in range(4)]
+        direct, accumulate = _direct_grads(ctx.owner, ctx.param_like)
+        direct = direct and accumulate
+        if direct:
+            grads = [[p.grad for p in ctx.param_like[g * L:(g + 1) * L]] for g in range(4)]
+        else:
+            grads = [[torch.empty_like(p) for p in ctx.param_like[g * L:(g + 1) * L]] for g in range(4)]
         dev = ctx.param_like[0].device
         need_dx, need_dh0, need_dc0 = ctx.need
         d = plan.desc
         dx = torch.empty(ctx.x_shape, dtype=torch.float32, device=dev) if need_dx else None
         dh0 = torch.empty((L, d.B, d.H), dtype=torch.float32, device=dev) if need_dh0 else None
         dc0 = torch.empty((L, d.B, d.H), dtype=torch.float32, device=dev) if need_dc0 else None
-        plan.set_grad_callback(None)
+        plan.set_grad_callback(ctx.owner.grad_ready_hook if direct else None)
+        plan.set_grad_mode(direct)
         plan.backward(None, dy_all, grads, dx=dx, dh_n=dh_n, dc_n=dc_n, dh0=dh0, dc0=dc0)
         ctx.lease.release()
+        if direct:
+            return (dx, dh0, dc0, None, None, None, *([None] * (4 * L)))
         flat = [g for group in grads for g in group]
         return (dx, dh0, dc0, None, None, None, *flat)
 

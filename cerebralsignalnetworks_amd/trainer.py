@@ -226,7 +226,17 @@ def check_device_status(model, collective=True):
 
 class DistillTrainer:
     def __init__(self, model, sos, ddof=0, loss="cosine", lr=1e-3, optimizer="rmsprop", nepochs=100,
-                 kd_params=None, preprocess=True):
+                 kd_params=None, preprocess=True, accum_steps=1):
+        """``accum_steps = k > 1``: train_step splits its batch into k equal micro-batches and sums their gradients (each
+        loss scaled by 1 / k) in the flat buffer before the one all-reduce and optimiser step -- the step of the whole
+        batch in 1 / k of the workspace.  That equals the full batch only for a loss that is a mean over rows (cosine,
+        featdist, kd); barlow normalises with batch statistics and is refused."""
+        if not isinstance(accum_steps, int) or isinstance(accum_steps, bool) or accum_steps < 1:
+            raise ValueError(f"accum_steps must be an integer >= 1, got {accum_steps!r}")
+        if accum_steps > 1 and loss == "barlow":
+            raise ValueError("accum_steps > 1 needs a loss that is a mean over the batch rows (cosine, featdist, kd): barlow "
+                             "normalises with the statistics of the batch, so micro-batches do not sum to the full batch")
+        self.accum_steps = accum_steps
         self.model = model
         self.sos, self.ddof, self.preprocess = sos, ddof, preprocess
         self.loss_name = loss
@@ -257,17 +267,21 @@ class DistillTrainer:
         self._wire_lstm_gradients(world)
 
     def _wire_lstm_gradients(self, world):
-        """The model's HIP LSTM writes its gradients straight into the flat buffer (one forward per step uses it: no
-        temporaries, no accumulation pass), and -- data-parallel -- tells the buffer which layer's gradients are
-        enqueued, so that their all-reduce overlaps the weight-gradient GEMMs of the layers below (FlatGrads)."""
+        """The model's HIP LSTM adds its gradients straight into the flat buffer (CSN_GRAD_ACCUMULATE: no temporaries, no
+        accumulation pass; the buffer is zeroed at the start of a step and 0 + g == g, so one forward per step leaves the
+        bits the overwriting form left, and a second forward or a micro-batch is summed instead of lost), and --
+        data-parallel -- tells the buffer which layer's gradients are enqueued, so that their all-reduce overlaps the
+        weight-gradient GEMMs of the layers below (FlatGrads)."""
         import os
         from .lstm_model import HipLSTM
         lstms = [m for m in self.model.modules() if isinstance(m, HipLSTM)]
         self._hook_error = None
+        self._lstm = None
         if len(lstms) != 1 or not self.grads.flat.is_cuda:
             return
         lstm = lstms[0]
-        lstm.direct_grads = True
+        self._lstm = lstm
+        lstm.direct_grads = "accumulate"
         L = lstm.num_layers
         first = [self.grads.offsets[id(getattr(lstm, f"weight_ih_l{k}"))][0] for k in range(L)]
         last = self.grads.offsets[id(getattr(lstm, f"bias_hh_l{L - 1}"))]
@@ -326,21 +340,54 @@ class DistillTrainer:
         raise ValueError(self.loss_name)
 
     def train_step(self, eeg_bct, targets, labels=None, epoch=0):
-        """One optimisation step on this rank's shard of the global batch; returns the (device) loss."""
+        """One optimisation step on this rank's shard of the global batch; returns the (device) loss.  With
+        ``accum_steps = k > 1`` the shard runs as k equal micro-batches whose gradients are summed in the flat buffer (the
+        returned loss is the sum of their losses / k); all-reduce and optimiser step follow the last one."""
+        k = self.accum_steps
+        B = eeg_bct.shape[0]
+        if B % k != 0:
+            raise ValueError(f"train_step: batch of {B} rows does not split into accum_steps = {k} equal micro-batches")
         self.model.train()
         self.grads.zero()
-        if self.grads.segments is not None:
-            self._others_left = self._n_others
-        x = self.embed(eeg_bct)
-        out = self.model(x)
-        loss = self.compute_loss(out, targets, labels, epoch)
-        loss.backward()
+        if k == 1:
+            if self.grads.segments is not None:
+                self._others_left = self._n_others
+            x = self.embed(eeg_bct)
+            out = self.model(x)
+            loss = self.compute_loss(out, targets, labels, epoch)
+            loss.backward()
+        else:
+            loss = self._micro_batches(eeg_bct, targets, labels, epoch, k)
         if self._hook_error is not None:
             err, self._hook_error = self._hook_error, None
             raise err
         self.grads.all_reduce_mean()
         self.opt.step()
         return loss.detach()
+
+    def _micro_batches(self, eeg_bct, targets, labels, epoch, k):
+        """embed -> forward -> loss / k -> backward per micro-batch, all into the flat buffer.  The gradient-ready hook is
+        armed for the last backward only: an overlapped all-reduce must not start on partial sums."""
+        mb = eeg_bct.shape[0] // k
+        lstm = self._lstm
+        hook = lstm.grad_ready_hook if lstm is not None else None
+        total = None
+        try:
+            for j in range(k):
+                rows = slice(j * mb, (j + 1) * mb)
+                last = j == k - 1
+                if lstm is not None:
+                    lstm.grad_ready_hook = hook if last else None
+                if last and self.grads.segments is not None:
+                    self._others_left = self._n_others
+                out = self.model(self.embed(eeg_bct[rows]))
+                loss = self.compute_loss(out, targets[rows], None if labels is None else labels[rows], epoch) / k
+                loss.backward()
+                total = loss.detach() if total is None else total + loss.detach()
+        finally:
+            if lstm is not None:
+                lstm.grad_ready_hook = hook
+        return total
 
     def check_device_status(self):
         """The model's sticky device status (time-outs; non-finite gradients where the weight-stationary backward saw

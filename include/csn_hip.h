@@ -35,7 +35,8 @@ enum csnStatus {
 
 enum csnDtype { CSN_F32 = 0, CSN_BF16 = 1 };
 
-/* ABI version of this header; bumped on any signature change. */
+/* ABI version of this header; bumped on any signature change.  A symbol added beside the existing ones
+ * (csn_lstm_plan_set_grad_mode) breaks no caller and does not bump it. */
 #define CSN_ABI_VERSION 6
 int csn_abi_version(void);
 /* Thread-local message for the last non-zero status returned on this thread. */
@@ -157,7 +158,8 @@ int csn_lstm_forward(csnLstmPlan* plan,
  * dy_all : optional [B,T,H] float32 gradient w.r.t. y_all (may be NULL).
  * dh_n, dc_n: optional [L,B,H] float32 gradients w.r.t. h_n / c_n (may be NULL).
  * At least one of dy_last, dy_all, dh_n, dc_n must be given.
- * dw_ih/dw_hh/db_ih/db_hh: [host] arrays of L device pointers, float32, OVERWRITTEN.
+ * dw_ih/dw_hh/db_ih/db_hh: [host] arrays of L device pointers, float32, OVERWRITTEN, or added to under
+ *   CSN_GRAD_ACCUMULATE (csn_lstm_plan_set_grad_mode).
  * dx: optional [B,T,I] float32 (dense), gradient w.r.t. x (may be NULL).
  * dh0, dc0: optional [L,B,H] float32 gradients w.r.t. h0 / c0, OVERWRITTEN (may be NULL); written whether or not the
  *   forward had a state (the gradient w.r.t. a zero state).  dh0[l] = dgates_l[t=0] W_hh_l from the operands the
@@ -182,6 +184,20 @@ int csn_lstm_backward(csnLstmPlan* plan,
  * back into this plan.  fn = NULL removes it. */
 typedef void (*csnGradReadyFn)(void* user, int layer);
 int csn_lstm_plan_set_grad_callback(csnLstmPlan* plan, csnGradReadyFn fn, void* user);
+
+/* Gradient mode of the plan's later csn_lstm_backward calls; sticky until set again.  It governs dw_ih, dw_hh, db_ih and
+ * db_hh only: dx, dh0 and dc0 are overwritten in both modes.  CSN_GRAD_OVERWRITE (the default) stores each gradient g.
+ * CSN_GRAD_ACCUMULATE stores fl32(prev + g) into every element, where g is exactly the float32 value the overwrite mode
+ * stores for the same inputs and prev is what the buffer held: one rounding, prev joins last -- bit for bit what
+ * `p.grad += g` gives, so a backward that writes straight into a gradient buffer cannot be told from one that goes through
+ * a temporary.  db_ih and db_hh each add to their OWN previous contents (in this mode one buffer for both is refused on the host).
+ * Every path (csn_lstm_plan_path 0-4), with and without CSN_LSTM_STATE and the gradient-ready callback, whose meaning
+ * is unchanged: the accumulating kernels of a layer are enqueued before it fires for that layer.  Uses: several forwards
+ * through one set of parameters in a step (multi-crop views), micro-batches summed into one optimiser step, the chunks
+ * of a recording chained through their state.  Null plan / unknown mode: CSN_ERR_INVALID_ARGUMENT. */
+#define CSN_GRAD_OVERWRITE  0
+#define CSN_GRAD_ACCUMULATE 1
+int csn_lstm_plan_set_grad_mode(csnLstmPlan* plan, int mode);
 
 /* The workspace's status word: 0 = ok.  Bit CSN_STATUS_TIMEOUT: a bounded in-kernel wait of a weight-stationary
  * kernel gave up at some point since the word was last cleared (the results of that forward / backward and of every
