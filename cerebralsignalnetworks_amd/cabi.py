@@ -412,9 +412,12 @@ def rmsprop_step(params_flat, grads_flat, square_avg_flat, lr, alpha=0.99, eps=1
 
 def barlow_offdiag_sqsum(c):
     _need_cuda(c)
+    if c.dim() != 2 or c.shape[0] != c.shape[1]:
+        raise CsnError(f"barlow_offdiag_sqsum expects a square matrix, got shape {tuple(c.shape)}")
     c = c.float().contiguous()
     out = torch.empty(2, dtype=torch.float32, device=c.device)
-    _check(load().csn_barlow_offdiag_sqsum(_ptr(c), c.shape[0], _ptr(out), _stream()))
+    with torch.cuda.device(c.device):
+        _check(load().csn_barlow_offdiag_sqsum(_ptr(c), c.shape[0], _ptr(out), _stream()))
     return out
 
 

@@ -287,7 +287,8 @@ int csn_barlow_offdiag_sqsum(const float* c, int D, float* out, csnStream_t stre
  * K8  exact squared-L2 top-k.  Replaces: faiss.IndexFlatL2(d).add / .search(k),
  * utils/Utilities.py:45-55.  gallery [Ng,D], query [Nq,D] float32; out_idx [Nq,k]
  * int64, out_dist [Nq,k] float32, ascending, ties -> lower gallery index.
- * scratch: device buffer of csn_l2_topk_scratch_bytes(Ng,Nq) bytes.  k <= 64.
+ * scratch: device buffer of csn_l2_topk_scratch_bytes(Ng,Nq) bytes.  1 <= k <= min(64, Ng): anything else is refused.
+ * The selection runs on the float64 distances; out_dist is their float32 rounding (inf where that overflows).
  * ---------------------------------------------------------------------------------- */
 size_t csn_l2_topk_scratch_bytes(int64_t Ng, int64_t Nq);
 int csn_l2_topk(const float* gallery, const float* query, int64_t Ng, int64_t Nq, int D, int k,

@@ -66,6 +66,55 @@ def zscore_rows(y, ddof=0):
     return (y - mean) / std
 
 
+def _cascade_steps(sos, v, s):
+    """One cascade step per column of v[..., n] from the state s[..., 2*nsec] (updated in place); returns the outputs."""
+    out = np.empty_like(v)
+    for n in range(v.shape[-1]):
+        cur = v[..., n]
+        for k, (b0, b1, b2, a0, a1, a2) in enumerate(sos):
+            yk = b0 / a0 * cur + s[..., 2 * k]
+            s[..., 2 * k] = b1 / a0 * cur - a1 / a0 * yk + s[..., 2 * k + 1]
+            s[..., 2 * k + 1] = b2 / a0 * cur - a2 / a0 * yk
+            cur = yk
+        out[..., n] = cur
+    return out
+
+
+def scan_emulator(x_rows, sos, ddof=0, chunks=16, length=32):
+    """The arithmetic of the chunk-parallel filter kernel (the "scan" comment block of csrc/eeg_filter.hip), in numpy:
+    x[R,T] float32, T <= chunks*length -> z-scored float32 [R,T].  Every phase computes in float64, the samples are
+    float32 BETWEEN the phases, the row is right-aligned in its ``chunks`` chunks of ``length`` samples (leading zeros):
+      2. each chunk filtered from a zero state -> zero-state response (rounded to float32) + end state e_k,
+      3. S_k = A S_{k-1} + e_k by a Kogge-Stone scan with the powers A^(2^m) of the ``length``-step transition,
+      4. y[n] += sum_i S_{k-1,i} phi_i[n] (rounded to float32); sum / sum of squares from the unrounded values,
+      5. (float32 y - mean) * (1 / sqrt(var)), rounded to float32.
+    It exists to bound, without a GPU, what that arithmetic loses against ``zscore_rows(sosfilt_rows(...))``."""
+    sos = np.asarray(sos, np.float64).reshape(-1, 6)
+    x = np.asarray(x_rows, np.float32)
+    R, T = x.shape
+    ns = 2 * len(sos)
+    v = np.zeros((R, chunks * length))
+    v[:, chunks * length - T:] = x
+    v = v.reshape(R, chunks, length)
+    if ns:
+        S = np.zeros((R, chunks, ns))
+        v = _cascade_steps(sos, v, S).astype(np.float32).astype(np.float64)
+        unit = np.eye(ns)                                                  # row i = the state e_i
+        phi = _cascade_steps(sos, np.zeros((ns, length)), unit)           # [i][n]; unit is now A e_i: A[j][i] = unit[i][j]
+        A, m = unit.T.copy(), 1
+        while m < chunks:
+            S[:, m:] = S[:, m:] + S[:, :-m] @ A.T
+            A, m = A @ A, 2 * m
+        prev = np.concatenate([np.zeros((R, 1, ns)), S[:, :-1]], axis=1)   # S_{k-1}
+        v = v + prev @ phi
+    v = v.reshape(R, -1)
+    total, sq = v.sum(1, keepdims=True), (v * v).sum(1, keepdims=True)
+    mean = total / T
+    inv = 1.0 / np.sqrt((sq - total * mean) / (T - ddof))
+    z = (v.astype(np.float32).astype(np.float64) - mean) * inv
+    return z[:, chunks * length - T:].astype(np.float32)
+
+
 def dataset_item(raw_ct, time_low, time_high, filter_channels=(), channel_wise_norm=False, mean=None, std=None,
                  means_c=None, stds_c=None):
     """The EEG part of ``EEGDataset.__getitem__`` (utils/PerilsEEGDataset.py:541-573; utils/EEGDataset.py:539-567):
