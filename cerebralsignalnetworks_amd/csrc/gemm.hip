@@ -952,7 +952,7 @@ __device__ __forceinline__ bf16x8 tr_read_pair(unsigned addr) {
   return u.b;
 }
 
-template <int NSTAGE, bool COLSUM, bool STAGGER = false>
+template <int NSTAGE, bool COLSUM>
 __global__ void __launch_bounds__(512)
 gemm_tn_256_kernel(const bf16_t* __restrict__ A, const bf16_t* __restrict__ Bm, float* __restrict__ slabs,
                    int64_t M, int64_t N, int64_t K, int64_t k_per_split, float* __restrict__ colsum) {
@@ -1030,72 +1030,6 @@ gemm_tn_256_kernel(const bf16_t* __restrict__ A, const bf16_t* __restrict__ Bm, 
     for (int j = 0; j < 4; ++j) b_addr[j] = (unsigned)tn256_lds_off(8 * g + q, wn * 64 + j * 16 + 4 * pp);
   }
 
-  if constexpr (STAGGER) {
-    // Two wave groups (waves 0-3 / 4-7: one wave of each per SIMD) run the same k-steps ONE BARRIER INTERVAL apart: a
-    // k-step is  A = {retire stage h+1, request stage h+3, issue the 24 fragment reads of stage h} | barrier |
-    // B = {32 MFMAs} | barrier,  so while one group's waves multiply, the other group's waves on the same SIMDs issue
-    // their DMA pieces and LDS reads (with one common phase per k-step both waves of a SIMD want the MFMA pipe, then
-    // the LDS pipe, at the same time: MFMA busy 48 %).  Intervals I_n between barriers n and n+1: the leading group
-    // does A_h in I_2h, B_h in I_2h+1, the lagging group A_h in I_2h+1, B_h in I_2h+2.
-    //   read-after-DMA : a wave retires ITS pieces of stage s at the start of its A_(s-1) (counted vmcnt), i.e. before
-    //                    barrier 2s-1 (leading) / 2s (lagging); the first read of stage s is in I_2s.
-    //   DMA-after-read : the last reads of stage h retire inside the lagging group's B_h (I_2h+2); its slot takes
-    //                    stage h+5, requested in A_(h+2) = I_2h+4 / I_2h+5.  Hence 5 stages, prefetch distance 3.
-    static_assert(!STAGGER || NSTAGE == 5, "staggered form: ring of 5 stages");
-    const int grp = __builtin_amdgcn_readfirstlane(wave >> 2);
-#pragma unroll
-    for (int h = 0; h < 3; ++h)
-      if (h < nh) issue(h);
-    if (nh >= 3) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if (nh == 2) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    if (grp == 1) __builtin_amdgcn_s_barrier();
-    for (int h = 0; h < nh; ++h) {
-      if (h + 2 < nh) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#if !defined(CSN_TN_ABL) || CSN_TN_ABL != 1     // (ablation 1, timing only: no DMA after the prologue)
-      if (h + 3 < nh) issue(h + 3);
-#endif
-      const unsigned sb = (unsigned)(h % NSTAGE) * 32768u;
-      bf16x8 af[8], bfr[4];
-#if defined(CSN_TN_ABL) && CSN_TN_ABL == 2       // (ablation 2, timing only: no LDS reads)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) bfr[j] = __builtin_bit_cast(bf16x8, (f32x4){(float)sb, 1.f, 2.f, (float)j});
-#pragma unroll
-      for (int i = 0; i < 8; ++i) af[i] = __builtin_bit_cast(bf16x8, (f32x4){(float)sb, 3.f, 2.f, (float)i});
-#else
-#pragma unroll
-      for (int j = 0; j < 4; ++j) bfr[j] = tr_read_pair(b_addr[j] + sb + 16384u);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) af[i] = tr_read_pair(a_addr[i] + sb);
-#endif
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_barrier();
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        // reads behind the ones MFMA group i needs: the pairs of A fragments i+1 .. 7
-        if (i == 0) asm volatile("s_waitcnt lgkmcnt(14)" ::: "memory");
-        else if (i == 1) asm volatile("s_waitcnt lgkmcnt(12)" ::: "memory");
-        else if (i == 2) asm volatile("s_waitcnt lgkmcnt(10)" ::: "memory");
-        else if (i == 3) asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");
-        else if (i == 4) asm volatile("s_waitcnt lgkmcnt(6)" ::: "memory");
-        else if (i == 5) asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory");
-        else if (i == 6) asm volatile("s_waitcnt lgkmcnt(2)" ::: "memory");
-        else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j], af[i], acc[i][j], 0, 0, 0);
-        if constexpr (COLSUM)
-          if (do_colsum && (i >> 1) == wn_s) acc_cs[i & 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, af[i], acc_cs[i & 1], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      __builtin_amdgcn_s_barrier();
-    }
-    if (grp == 0) __builtin_amdgcn_s_barrier();
-  } else {
 #pragma unroll
   for (int h = 0; h < NSTAGE - 1; ++h)
     if (h < nh) issue(h);
@@ -1143,8 +1077,6 @@ gemm_tn_256_kernel(const bf16_t* __restrict__ A, const bf16_t* __restrict__ Bm, 
     }
   }
 
-  }
-
   if (COLSUM && do_colsum && (lane >> 4) == 0) {       // D[n][m]: every row n holds the same sum; lanes 0..15 write column m
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
@@ -1161,6 +1093,286 @@ gemm_tn_256_kernel(const bf16_t* __restrict__ A, const bf16_t* __restrict__ Bm, 
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int64_t n = n0 + wn * 64 + j * 16 + (lane >> 4) * 4;
+      if (n + 3 < N && (N & 3) == 0) {
+        *reinterpret_cast<float4*>(C + m * N + n) = make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
+      } else {
+        for (int r = 0; r < 4; ++r)
+          if (n + r < N) C[m * N + n + r] = acc[i][j][r];
+      }
+    }
+  }
+}
+
+// The same tile on FOUR waves (2 along M x 2 along N), the default: a wave owns 128 x BN/2 outputs, so at BN = 256 the
+// 256 accumulator registers fill the AGPR half and a 32-row k-step reads 4 x (128 + 128) x 32 x 2 B = 64 KB of LDS
+// for 1024 MFMA cycles per SIMD (the 8-wave form above reads 96 KB for the same MFMAs).  Stage image, swizzle, k walk,
+// K splits and slab layout are those of gemm_tn_256_kernel, and every output element sees the same 16 x 16 x 32 MFMA
+// k-blocks in the same order: the slabs and the column sums are bit-identical to the 8-wave kernels'.
+// BN = 128 (N <= 128, the layer-0 input weight gradient): a 256 x 128 tile whose B stage is 8 KB of 256-byte k-rows
+// (same block swizzle: a row is still a whole number of bank sets), so no clamped duplicate columns are staged,
+// read or multiplied.
+// One wave per SIMD: nothing hides a stall of that wave, so the overlap has to come from inside it (the k-loop below):
+// every fragment register is refilled for the next stage right behind the last MFMA that uses it, and the 4 A + BN/64 B
+// DMA pieces of stage h + PF are issued two to an MFMA group instead of in one burst behind the barrier.
+// Measured (3072 x 768 x 128 000): 8-wave staggered ring 541 us, this kernel 523; N = 128: 208 -> 156.
+// A ring of 4 stages beats one of 5 at every prefetch distance tried (537 against 553 - 558 us on one box).
+#ifndef CSN_TN_W4_NSTAGE      // ring depth and prefetch distance (timing experiments override them: tools/abl_build.sh)
+#define CSN_TN_W4_NSTAGE 4
+#endif
+#ifndef CSN_TN_W4_PF
+#define CSN_TN_W4_PF 3
+#endif
+// A fragment as the kernel below carries it from one k-step into the next: four plain dwords.  (As a loop-carried
+// bf16x8 the compiler rebuilds it from 16-bit halves with VALU instructions placed right behind the inline-asm read,
+// which it cannot know to be asynchronous -- before the data has landed.)  ROW4: bytes from k-row q to k-row q + 4.
+typedef int i32x2 __attribute__((ext_vector_type(2)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+template <int ROW4>
+__device__ __forceinline__ i32x4 tr_read_frag(unsigned addr) {
+  union { i32x2 s[2]; i32x4 v; } u;
+  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(u.s[0]) : "v"(addr) : "memory");
+  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(u.s[1]) : "v"(addr), "n"(ROW4) : "memory");
+  return u.v;
+}
+
+template <int NSTAGE, int PF, bool COLSUM, int BN>
+__global__ void __launch_bounds__(256)
+gemm_tn_256w4_kernel(const bf16_t* __restrict__ A, const bf16_t* __restrict__ Bm, float* __restrict__ slabs,
+                     int64_t M, int64_t N, int64_t K, int64_t k_per_split, float* __restrict__ colsum) {
+  static_assert(BN == 256 || BN == 128, "256 x 256 or 256 x 128 tile");
+  static_assert(PF >= 2 && PF <= 4 && PF < NSTAGE, "stage h + 1 is read in step h: its slot and stage h's are no DMA targets");
+  constexpr bool NARROW = BN == 128;
+  constexpr int NJ = BN / 32;                  // B fragments per wave
+  constexpr int NBP = BN / 64;                 // B pieces per wave and stage
+  constexpr int NP = 4 + NBP;                  // LDS-DMA instructions per wave and stage
+  constexpr unsigned B_OFF = 16384u;
+  constexpr unsigned STAGE = 16384u + BN * 64u;
+  extern __shared__ __attribute__((aligned(1024))) char smem[];  // NSTAGE x (A 16 KB + B 16 / 8 KB)
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);       // scalar: the LDS address of a DMA piece goes to M0
+  const int wm = wave >> 1, wn = wave & 1;
+  const unsigned ntn = (unsigned)((N + 255) / 256), ntm = (unsigned)((M + 255) / 256);
+  const unsigned lid = xcd_remap(blockIdx.x, gridDim.x);
+  const unsigned zsplit = lid / (ntm * ntn), rem = lid % (ntm * ntn);
+  const int64_t m0 = (int64_t)(rem / ntn) * 256, n0 = (int64_t)(rem % ntn) * 256;
+  const int64_t kbeg = (int64_t)zsplit * k_per_split;
+  const int64_t kend = (kbeg + k_per_split < K) ? kbeg + k_per_split : K;
+  const int nh = __builtin_amdgcn_readfirstlane(kend > kbeg ? (int)((kend - kbeg) / 32) : 0);     // stages of 32 k-rows
+
+  // staging: A instruction i (0..3) of wave w fills k-rows 2 (4 i + w), +1 of a stage, as in gemm_tn_256_kernel; at
+  // BN = 128 B instruction i (0..1) of wave w fills the four 256-byte k-rows 4 (4 i + w) .. + 3: lane -> k-row
+  // lane >> 4, chunk position c = lane & 15 <- global columns ((c >> 1) ^ s) * 16 + (c & 1) * 8
+  const bf16_t* a_src[4];
+  const bf16_t* b_src[NBP];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int kr = 2 * (4 * i + wave) + (lane >> 5);
+    const int c = lane & 31;
+    const int sw = (kr & 3) | (((kr >> 3) & 1) << 2);
+    const int col = (((c >> 1) ^ sw) << 4) + (c & 1) * 8;
+    int64_t am = m0 + col;
+    am = am + 8 <= M ? am : M - 8;
+    a_src[i] = A + (kbeg + kr) * M + am;
+    if constexpr (!NARROW) {
+      int64_t bn = n0 + col;
+      bn = bn + 8 <= N ? bn : N - 8;
+      b_src[i] = Bm + (kbeg + kr) * N + bn;
+    }
+  }
+  if constexpr (NARROW) {
+#pragma unroll
+    for (int i = 0; i < NBP; ++i) {
+      const int kr = 4 * (4 * i + wave) + (lane >> 4);
+      const int c = lane & 15;
+      const int sw = (kr & 3) | (((kr >> 3) & 1) << 2);
+      int64_t bn = n0 + (((c >> 1) ^ sw) << 4) + (c & 1) * 8;
+      bn = bn + 8 <= N ? bn : N - 8;
+      b_src[i] = Bm + (kbeg + kr) * N + bn;
+    }
+  }
+  // piece p of stage h: p even -> A piece p / 2, p odd -> B piece p / 2 while B pieces last, then the A pieces left
+  auto issue_piece = [&](int h, int p) {
+    char* a_s = smem + (unsigned)(h % NSTAGE) * STAGE;
+    const int ib = p >> 1;
+    const bool is_b = (p & 1) && ib < NBP;
+    if (is_b) glds16(b_src[ib] + (int64_t)h * 32 * N, a_s + B_OFF + (4 * ib + wave) * 1024);
+    else {
+      const int ia = p < 2 * NBP ? ib : p - NBP;
+      glds16(a_src[ia] + (int64_t)h * 32 * M, a_s + (4 * ia + wave) * 1024);
+    }
+  };
+
+  f32x4 acc[8][NJ];
+#pragma unroll
+  for (int i = 0; i < 8; ++i)
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  // column sums of A (the bias gradient), one more MFMA per owned A fragment and k-step against a fragment of ones,
+  // behind a scalar branch.  Every workgroup of a tile row stages the same A rows, so the eight fragments of a wave
+  // row are dealt out over ALL its column tiles' waves -- fragment i to slot i mod min(2 ntn, 8), slot = 2 x column
+  // tile + wn: at three column tiles a wave owns at most two (with one wave per SIMD nothing hides the extra MFMAs;
+  // four per wave in the first column tile's workgroups held the whole launch back).  Same fragment, same k order:
+  // the same bits whoever computes them.
+  unsigned own_cs = 0;
+  if (COLSUM && colsum != nullptr) {
+    const unsigned nslots = 2 * ntn < 8 ? 2 * ntn : 8, slot = 2 * (rem % ntn) + (unsigned)wn;
+#pragma unroll
+    for (unsigned i = 0; i < 8; ++i) own_cs |= (i % nslots == slot ? 1u : 0u) << i;
+  }
+  own_cs = __builtin_amdgcn_readfirstlane(own_cs);
+  // (the fragment of ones goes through an empty asm: a constant the compiler can re-materialise it rebuilds with v_mov
+  // right in front of every inline-asm MFMA that reads it, closer than the hardware allows -- tools/check_asm_hazards.py)
+  i32x4 ones = {0x3f803f80, 0x3f803f80, 0x3f803f80, 0x3f803f80};      // eight bf16 1.0
+  asm volatile("" : "+v"(ones));
+  f32x4 acc_cs[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) acc_cs[e] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+  unsigned a_addr[8], b_addr[NJ];
+  {
+    const int g = lane >> 4, q = (lane & 15) >> 2, pp = lane & 3;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) a_addr[i] = (unsigned)tn256_lds_off(8 * g + q, wm * 128 + i * 16 + 4 * pp);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const int col = wn * (BN / 2) + j * 16 + 4 * pp;
+      b_addr[j] = B_OFF + (unsigned)(NARROW ? tn256_lds_off(8 * g + q, col) - (8 * g + q) * 256 : tn256_lds_off(8 * g + q, col));
+    }
+  }
+
+#if defined(CSN_TN_ABL) && CSN_TN_ABL == 2       // (ablation 2, timing only: no LDS reads)
+#define W4_READ_A(i, sb) __builtin_bit_cast(i32x4, (f32x4){(float)(sb), 3.f, 2.f, (float)(i)})
+#define W4_READ_B(j, sb) __builtin_bit_cast(i32x4, (f32x4){(float)(sb), 1.f, 2.f, (float)(j)})
+#else
+#define W4_READ_A(i, sb) tr_read_frag<2048>(a_addr[i] + (sb))
+#define W4_READ_B(j, sb) tr_read_frag<NARROW ? 1024 : 2048>(b_addr[j] + (sb))
+#endif
+  // A burst of fragment reads in front of the MFMAs that need them is exposed in full here (the B fragments read behind
+  // the barrier cost the first form of this kernel a quarter of the k-step).  So the reads are spread evenly over the
+  // step -- one pair about every fourth MFMA -- and every fragment register is refilled from stage h + 1 (') as soon
+  // as the last MFMA of stage h that uses it has been issued.  That takes two traversals:
+  //   first half : A row-blocks 0 .. 3 one after the other against all B fragments  (A i is free behind group i),
+  //   second half: B fragments one after the other against A row-blocks 4 .. 7       (B j is free behind column j);
+  // A 4 .. 7 of stage h are read during the first half.  Reads of a step in issue order (pairs, BN = 256; 128 alike):
+  //   A4 A5 | A0' A6 | A1' A7 | A2' || A3' | B0' | B1' | .. | B6' B7'
+  // LDS reads retire in order, and the counted wait in front of an MFMA is the number of reads issued behind the last
+  // pair it needs: only group 0 (B j' may still be in flight) and the first MFMA of the second half (A7) wait.
+  //   read-after-DMA : a wave retires ITS pieces of stage h + 1 (counted vmcnt) in front of step h's barrier; the
+  //                    first read of stage h + 1 is behind that barrier.
+  //   DMA-after-read : stage s is last read in step s (A 4 .. 7, retired before the second half); its slot takes
+  //                    stage s + NSTAGE, requested in step s + NSTAGE - PF >= s + 1, behind that step's barrier.
+  // (The last step reads "stage nh" too, from a slot nobody fills any more, and nobody uses it: one sequence of reads,
+  // one set of counted waits.)
+  if (nh > 0) {
+#pragma unroll
+    for (int h = 0; h < PF; ++h)
+      if (h < nh) {
+#pragma unroll
+        for (int p = 0; p < NP; ++p) issue_piece(h, p);
+      }
+    // stage 0: stages issued after it and still allowed in flight: min(PF, nh) - 1
+    if (nh >= PF) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NP * (PF - 1)) : "memory");
+    else if (PF > 2 && nh == PF - 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NP * (PF - 2)) : "memory");
+    else if (PF > 3 && nh == PF - 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NP * (PF - 3)) : "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    i32x4 af[8], bfr[NJ];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) af[i] = W4_READ_A(i, 0u);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) bfr[j] = W4_READ_B(j, 0u);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    for (int h = 0; h < nh; ++h) {
+      // stage h + 1: stages issued after it and still allowed in flight: min(PF - 2, nh - 2 - h)
+      const int ahead = nh - 2 - h;
+      if (ahead >= PF - 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NP * (PF - 2)) : "memory");
+      else if (PF > 3 && ahead == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NP) : "memory");
+      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+#if defined(CSN_TN_ABL) && CSN_TN_ABL == 1       // (ablation 1, timing only: no DMA after the prologue)
+      const bool more = false;
+#else
+      const bool more = h + PF < nh;
+#endif
+      const unsigned sb = (unsigned)(h % NSTAGE) * STAGE, sbn = (unsigned)((h + 1) % NSTAGE) * STAGE;
+#if defined(CSN_TN_W4_BURST)                     // (timing experiment: the stage's pieces in one burst behind the barrier)
+      if (more) {
+#pragma unroll
+        for (int p = 0; p < NP; ++p) issue_piece(h + PF, p);
+      }
+#endif
+      // ---- first half: A row-blocks 0 .. 3
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+          // behind B j' of the last step: B j+1' .. ; of this step: A4 (from MFMA 1 on), A5 (from MFMA NJ / 2 + 1 on)
+          if (i == 0) asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(2 * (NJ - 1 - j + (j >= 1) + (j >= NJ / 2 + 1))) : "memory");
+          __builtin_amdgcn_sched_barrier(0);
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, bfr[j]), __builtin_bit_cast(bf16x8, af[i]), acc[i][j], 0, 0, 0);
+          __builtin_amdgcn_sched_barrier(0);
+          if (j == 0) {
+            if (i == 0) af[4] = W4_READ_A(4, sb);
+            else af[i - 1] = W4_READ_A(i - 1, sbn);
+          }
+          if (j == NJ / 2 && i < 3) af[5 + i] = W4_READ_A(5 + i, sb);
+          __builtin_amdgcn_sched_barrier(0);
+#if !defined(CSN_TN_W4_BURST)
+          // two DMA pieces of stage h + PF inside each group, behind MFMAs that wait for nothing new
+          if (j == NJ / 4 && 2 * i < NP && more) issue_piece(h + PF, 2 * i);
+          if (j == (3 * NJ) / 4 && 2 * i + 1 < NP && more) issue_piece(h + PF, 2 * i + 1);
+          __builtin_amdgcn_sched_barrier(0);
+#endif
+        }
+        if constexpr (COLSUM)
+          if (own_cs & (1u << i))     // (inline asm: the builtin's accumulator would have to be an AGPR, and all 256 are taken)
+            asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc_cs[i]) : "v"(ones), "v"(af[i]));
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      // ---- second half: B fragments 0 .. NJ - 1 against A row-blocks 4 .. 7 (A7 has A2' behind it)
+      asm volatile("s_waitcnt lgkmcnt(2)" ::: "memory");
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          acc[4 + k][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, bfr[j]), __builtin_bit_cast(bf16x8, af[4 + k]), acc[4 + k][j], 0, 0, 0);
+          __builtin_amdgcn_sched_barrier(0);
+          if (k == 0) {
+            if (j == 0) af[3] = W4_READ_A(3, sbn);
+            else bfr[j - 1] = W4_READ_B(j - 1, sbn);
+          }
+          if (k == 3 && j == NJ - 1) bfr[j] = W4_READ_B(j, sbn);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        if constexpr (COLSUM)
+          if (j < 4 && (own_cs & (16u << j)))
+            asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc_cs[4 + j]) : "v"(ones), "v"(af[4 + j]));
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the unused reads of "stage nh"
+  }
+#undef W4_READ_A
+#undef W4_READ_B
+
+  if (COLSUM && (lane >> 4) == 0) {       // D[n][m]: every row n holds the same sum; lanes 0..15 write column m
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int64_t m = m0 + wm * 128 + e * 16 + (lane & 15);
+      if ((own_cs & (1u << e)) && m < M) colsum[(int64_t)zsplit * M + m] = acc_cs[e][0];
+    }
+  }
+
+  float* C = slabs + (int64_t)zsplit * M * N;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const int64_t m = m0 + wm * 128 + i * 16 + (lane & 15);
+    if (m >= M) continue;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const int64_t n = n0 + wn * (BN / 2) + j * 16 + (lane >> 4) * 4;
       if (n + 3 < N && (N & 3) == 0) {
         *reinterpret_cast<float4*>(C + m * N + n) = make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
       } else {
@@ -1342,11 +1554,23 @@ int launch_gemm_tn_slabs(const void* A, const void* B, float* slabs, int64_t M, 
     const int nst = opt.tn_stages;
     const bf16_t* Ab = (const bf16_t*)A;
     const bf16_t* Bb = (const bf16_t*)B;
-    if (!opt.tn_no_stagger && nst == 4) {      // (the default; CSN_TN_STAGES selects one of the single-phase rings)
-      if (int rc = ensure_dyn_lds<&gemm_tn_256_kernel<5, false, true>>(5 * 32768)) return rc;
-      if (int rc = ensure_dyn_lds<&gemm_tn_256_kernel<5, true, true>>(5 * 32768)) return rc;
-      if (colsum) gemm_tn_256_kernel<5, true, true><<<grid, 512, 5 * 32768, st>>>(Ab, Bb, slabs, M, N, K, kper2, colsum);
-      else gemm_tn_256_kernel<5, false, true><<<grid, 512, 5 * 32768, st>>>(Ab, Bb, slabs, M, N, K, kper2, nullptr);
+    // the default: the four-wave kernel.  CSN_TN_NO_STAGGER (a name from when the default was a staggered 8-wave ring)
+    // and CSN_TN_STAGES=3|5 select the 8-wave single-phase rings, the reference form the tests compare it with.
+    if (!opt.tn_no_stagger && nst == 4) {
+      constexpr int NS = CSN_TN_W4_NSTAGE, PF = CSN_TN_W4_PF;
+      if (N <= 128) {                          // 256 x 128 tile body: no clamped duplicate columns
+        constexpr int lds = NS * (16384 + 8192);
+        if (int rc = ensure_dyn_lds<&gemm_tn_256w4_kernel<NS, PF, false, 128>>(lds)) return rc;
+        if (int rc = ensure_dyn_lds<&gemm_tn_256w4_kernel<NS, PF, true, 128>>(lds)) return rc;
+        if (colsum) gemm_tn_256w4_kernel<NS, PF, true, 128><<<grid, 256, lds, st>>>(Ab, Bb, slabs, M, N, K, kper2, colsum);
+        else gemm_tn_256w4_kernel<NS, PF, false, 128><<<grid, 256, lds, st>>>(Ab, Bb, slabs, M, N, K, kper2, nullptr);
+      } else {
+        constexpr int lds = NS * 32768;
+        if (int rc = ensure_dyn_lds<&gemm_tn_256w4_kernel<NS, PF, false, 256>>(lds)) return rc;
+        if (int rc = ensure_dyn_lds<&gemm_tn_256w4_kernel<NS, PF, true, 256>>(lds)) return rc;
+        if (colsum) gemm_tn_256w4_kernel<NS, PF, true, 256><<<grid, 256, lds, st>>>(Ab, Bb, slabs, M, N, K, kper2, colsum);
+        else gemm_tn_256w4_kernel<NS, PF, false, 256><<<grid, 256, lds, st>>>(Ab, Bb, slabs, M, N, K, kper2, nullptr);
+      }
     } else if (colsum) gemm_tn_256_kernel<4, true><<<grid, 512, 4 * 32768, st>>>(Ab, Bb, slabs, M, N, K, kper2, colsum);
     else if (nst == 3) gemm_tn_256_kernel<3, false><<<grid, 512, 3 * 32768, st>>>(Ab, Bb, slabs, M, N, K, kper2, nullptr);
     else if (nst == 5) gemm_tn_256_kernel<5, false><<<grid, 512, 5 * 32768, st>>>(Ab, Bb, slabs, M, N, K, kper2, nullptr);
