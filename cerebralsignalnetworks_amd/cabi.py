@@ -46,6 +46,7 @@ SIGNATURES = {
     "csn_lstm_plan_kernel_name": (ctypes.c_char_p, [_c_void_p, _c_int]),
     "csn_lstm_plan_set_grad_callback": (_c_int, [_c_void_p, _c_void_p, _c_void_p]),
     "csn_lstm_plan_set_grad_mode": (_c_int, [_c_void_p, _c_int]),
+    "csn_lstm_plan_set_lengths": (_c_int, [_c_void_p, ctypes.POINTER(ctypes.c_int32)]),
     "csn_lstm_workspace_bytes": (_c_size_t, [ctypes.POINTER(LstmDesc), _c_int]),
     "csn_lstm_forward": (_c_int, [_c_void_p, _c_void_p, _c_i64, _c_i64,
                                   ctypes.POINTER(_c_void_p), ctypes.POINTER(_c_void_p),
@@ -293,6 +294,18 @@ class LstmPlan:
         element becomes fl32(prev + g), g the value the overwriting mode stores: the bits of ``p.grad += g``); False (the
         plan's default): they overwrite.  Sticky until set again."""
         _check(load().csn_lstm_plan_set_grad_mode(self._plan, GRAD_ACCUMULATE if accumulate else GRAD_OVERWRITE))
+
+    def set_lengths(self, lengths):
+        """Per-row numbers of valid steps for the following forward() / backward() calls (csn_lstm_plan_set_lengths):
+        a sequence of B ints in [0, T] (or a CPU int tensor), or None = every row is T.  Sticky until set again; a
+        backward must run with the lengths of its forward.  Needs a plan created with state=True."""
+        if lengths is None:
+            _check(load().csn_lstm_plan_set_lengths(self._plan, None))
+            return
+        vals = [int(v) for v in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
+        if len(vals) != self.desc.B:
+            raise CsnError(f"LSTM lengths: {len(vals)} entries for a batch of {self.desc.B}")
+        _check(load().csn_lstm_plan_set_lengths(self._plan, (ctypes.c_int32 * len(vals))(*vals)))
 
     def dgates_copies(self):
         """Copies of the gate gradients the last backward wrote per step (csn_hip.h): 2, or 0 before any backward."""

@@ -138,8 +138,20 @@ struct CellBwdOne {
   const float* c_prev; float* dc_carry; void* dg_out;
 };
 struct CellBwdBatch { CellBwdOne p[4]; };
+// Variable-length batches (csn_lstm_plan_set_lengths): the LAST argument of the backward cell kernels.  The masked
+// instantiations (MASK = true) get the rows' lengths and the timestep of each problem of the launch: a cell of row b at
+// step t >= lengths[b] stores zero gate gradients and leaves the carried dc as it is.  The unmasked instantiations take
+// the empty form behind their unchanged arguments and are the code they were.
+struct CellMask {
+  const int* lengths;      // [B], device
+  int t[4];                // timestep of problem i
+};
+struct CellNoMask {};
+template <bool MASK> struct CellMaskArg { typedef CellNoMask type; };
+template <> struct CellMaskArg<true> { typedef CellMask type; };
 int launch_cell_fwd_batch(const CellFwdBatch& b, int np, int B, int H, int dtype, hipStream_t st);
-int launch_cell_bwd_batch(const CellBwdBatch& b, int np, int B, int H, int dtype, hipStream_t st);
+int launch_cell_bwd_batch(const CellBwdBatch& b, int np, int B, int H, int dtype, hipStream_t st,
+                          const CellMask* mask = nullptr);
 
 // ---- internal launchers shared across translation units --------------------------------
 // out[r*ldo + c] = (T)in[strided]; generic strided cast used for the time-major input copy.

@@ -24,6 +24,7 @@
 //              buffers of h and dgates.  In the fast path every 4H axis is gate-interleaved
 //              (n' = 4 unit + gate); parameters and their gradients are (un)permuted at the API.
 #include <algorithm>
+#include <cstring>
 #include <vector>
 
 #include "csn_common.h"
@@ -215,6 +216,82 @@ __global__ void add_rows_kernel(const float* __restrict__ src, float* __restrict
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) dst[i] += src[i];
 }
 
+// ---- variable-length batches (csn_lstm_plan_set_lengths): len[b] in [0, T] valid steps of row b ----
+// buf[t][b][:] = 0 where t >= len[b]  (time-major input copy: padding is never multiplied)
+template <typename T>
+__global__ void mask_tm_kernel(T* __restrict__ buf, const int* __restrict__ len, int B, int Tn, int W) {
+  const int64_t total = (int64_t)B * Tn * W;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+    const int64_t r = i / W, b = r % B, t = r / B;
+    if (t >= len[b]) buf[i] = from_f32<T>(0.f);
+  }
+}
+// the same on the fragment-major slabs [Tn][Bpad * I] of the fused input projection, one 16-byte piece per thread and trip
+__global__ void mask_x_blk_kernel(bf16_t* __restrict__ x_blk, const int* __restrict__ len, int B, int64_t Bpad, int Tn, int I) {
+  const int64_t per_t = Bpad * I / 8, kblocks = I >> 5;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t ci = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; ci < per_t * Tn; ci += stride) {
+    const int64_t t = ci / per_t, c = ci % per_t, blk = c >> 6, lane = c & 63;
+    const int64_t r = (blk / kblocks) * 16 + (lane & 15);
+    if (r < B && t >= len[r]) *reinterpret_cast<uint4*>(x_blk + ci * 8) = make_uint4(0u, 0u, 0u, 0u);
+  }
+}
+// out[b][h] (f32) = all[len[b]][b][h]: slot n of h_all / c_all is the state after step n-1, slot 0 the initial state
+template <typename T>
+__global__ void gather_state_kernel(const T* __restrict__ all, const int* __restrict__ len, float* __restrict__ out, int B, int H) {
+  const int64_t total = (int64_t)B * H;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+    const int64_t b = i / H;
+    out[i] = to_f32(all[(int64_t)len[b] * B * H + i]);
+  }
+}
+// gather_y_all_kernel with zeros at t >= len[b] (steps at or beyond the longest row were never run: not read)
+template <typename T>
+__global__ void gather_y_all_len_kernel(const T* __restrict__ h_all, float* __restrict__ y, const int* __restrict__ len, int B, int Tn, int H) {
+  const int64_t total = (int64_t)B * Tn * H;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+    const int64_t h = i % H, r = i / H, t = r % Tn, b = r / Tn;
+    y[i] = t < len[b] ? to_f32(h_all[((t + 1) * B + b) * (int64_t)H + h]) : 0.f;
+  }
+}
+// dst[t][b][h], t < Te  =  t < len[b] && src ? src[b][t][h] : 0   (src batch-first with Tn steps per row, or null)
+__global__ void bt_to_tb_len_kernel(const float* __restrict__ src, float* __restrict__ dst, const int* __restrict__ len, int B, int Tn, int Te, int H) {
+  const int64_t total = (int64_t)B * Te * H;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+    const int64_t h = i % H, r = i / H, b = r % B, t = r / B;
+    dst[i] = (src != nullptr && t < len[b]) ? src[(b * Tn + t) * (int64_t)H + h] : 0.f;
+  }
+}
+// dst[len[b]-1][b][:] += src[b][:] for the rows whose last step lies in [t_lo, t_hi]: a gradient that enters at the row's end
+__global__ void add_at_end_kernel(const float* __restrict__ src, float* __restrict__ dst_tm, const int* __restrict__ len, int t_lo, int t_hi, int B, int H) {
+  const int64_t total = (int64_t)B * H;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+    const int t = len[i / H] - 1;
+    if (t >= t_lo && t <= t_hi) dst_tm[(int64_t)t * B * H + i] += src[i];
+  }
+}
+// dst[b][:] += src[b][:] for the rows of length 0 (their dh0 is dh_n)
+__global__ void add_rows_len0_kernel(const float* __restrict__ src, float* __restrict__ dst, const int* __restrict__ len, int B, int H) {
+  const int64_t total = (int64_t)B * H;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride)
+    if (len[i / H] == 0) dst[i] += src[i];
+}
+// dst[b][t][i] (Tn steps per row) = t < Te ? src[t][b][i] : 0
+__global__ void tb_to_bt_len_kernel(const float* __restrict__ src, float* __restrict__ dst, int B, int Tn, int Te, int H) {
+  const int64_t total = (int64_t)B * Tn * H;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+    const int64_t h = i % H, r = i / H, t = r % Tn, b = r / Tn;
+    dst[i] = t < Te ? src[(t * B + b) * (int64_t)H + h] : 0.f;
+  }
+}
+
 // Gradient w.r.t. the initial hidden state of one layer (CSN_LSTM_STATE plans):
 //   out[b][j] = sum_k dg[b][k] Wt(j, k),  k in [0, 4H), dg = dgates at t = 0 [B, 4H] row-major,
 //   Wt = W_hh^T [H, 4H]: row-major (BLK = false, generic path) or fragment-major (BLK = true, per-diagonal path, 4H axis
@@ -364,6 +441,17 @@ struct csnLstmPlan {
   csnGradReadyFn grad_cb = nullptr;      // csn_lstm_plan_set_grad_callback
   void* grad_cb_user = nullptr;
   int grad_accumulate = 0;               // csn_lstm_plan_set_grad_mode: dw / db are added to, not overwritten
+  // csn_lstm_plan_set_lengths (empty = every row is T).  A call with lengths runs every path with d.T lowered to the
+  // longest row for its duration (all saved tensors are time-major, so T enters extents only, never a stride); T_full is
+  // the T of the caller's batch-first tensors and dlen the device copy of the lengths while a call with lengths is in
+  // progress (len_dev: [B] int32 owned by the plan -- a state plan's workspace is laid out exactly as a plain plan's)
+  std::vector<int32_t> lengths;
+  int t_eff = 0;
+  int T_full = 0;
+  const int* dlen = nullptr;
+  int32_t* len_dev = nullptr;
+  int32_t* len_pin = nullptr;            // pinned staging of the upload, and the event behind its last copy
+  hipEvent_t len_ev = nullptr;
   void grads_ready(int layer) const {
     if (grad_cb != nullptr) grad_cb(grad_cb_user, layer);
   }
@@ -395,6 +483,7 @@ extern "C" int csn_lstm_plan_create(const csnLstmDesc* d, int training, csnLstmP
     if (cmax >= 3 && (unsigned long long)P->opt.chunk > cmax - 2) P->opt.chunk = (int)(cmax - 2);
   }
   P->w = make_layout(*d, P->training, P->opt);
+  P->T_full = d->T;
   *out = P;
   return CSN_OK;
 }
@@ -411,6 +500,9 @@ extern "C" void csn_lstm_plan_destroy(csnLstmPlan* P) {
     if (P->prof.ev[i]) (void)hipEventDestroy(P->prof.ev[i]);
   for (int k = 0; k < 2; ++k)
     for (hipEvent_t e : P->prof.pair[k]) (void)hipEventDestroy(e);
+  if (P->len_ev) (void)hipEventDestroy(P->len_ev);
+  if (P->len_pin) (void)hipHostFree(P->len_pin);
+  if (P->len_dev) (void)hipFree(P->len_dev);
   if (switched) (void)hipSetDevice(cur);
   delete P;
 }
@@ -461,6 +553,75 @@ extern "C" int csn_lstm_plan_set_grad_mode(csnLstmPlan* P, int mode) {
   CSN_REQUIRE(P != nullptr, "csn_lstm_plan_set_grad_mode: null plan");
   CSN_REQUIRE(mode == CSN_GRAD_OVERWRITE || mode == CSN_GRAD_ACCUMULATE, "csn_lstm_plan_set_grad_mode: unknown mode %d", mode);
   P->grad_accumulate = mode == CSN_GRAD_ACCUMULATE;
+  return CSN_OK;
+}
+
+extern "C" int csn_lstm_plan_set_lengths(csnLstmPlan* P, const int32_t* lengths) {
+  CSN_REQUIRE(P != nullptr, "csn_lstm_plan_set_lengths: null plan");
+  CSN_REQUIRE(P->state, "csn_lstm_plan_set_lengths: the plan was created without CSN_LSTM_STATE");
+  if (lengths == nullptr) {
+    P->lengths.clear();
+    P->t_eff = 0;
+    return CSN_OK;
+  }
+  int longest = 0;
+  for (int b = 0; b < P->d.B; ++b) {
+    CSN_REQUIRE(lengths[b] >= 0 && lengths[b] <= P->d.T, "csn_lstm_plan_set_lengths: lengths[%d] = %d outside [0, %d]", b,
+                (int)lengths[b], P->d.T);
+    longest = std::max(longest, (int)lengths[b]);
+  }
+  P->lengths.assign(lengths, lengths + P->d.B);
+  P->t_eff = longest;
+  return CSN_OK;
+}
+
+// for the duration of a call with lengths: the plan's T is the longest row
+struct EffectiveT {
+  csnLstmDesc& d;
+  const int T;
+  EffectiveT(csnLstmDesc& d_, int Te) : d(d_), T(d_.T) { d.T = Te; }
+  ~EffectiveT() { d.T = T; }
+};
+// lengths of the call in progress -> the plan's device array, in stream order (every forward and backward that runs with
+// lengths uploads what the plan holds, so the kernels of a call read the lengths of that call)
+static int upload_lengths(csnLstmPlan* P, hipStream_t st) {
+  P->dlen = nullptr;
+  if (P->lengths.empty()) return CSN_OK;
+  // through a pinned staging array of the plan: the copy is asynchronous, and the array is rewritten only once the copy
+  // before has left it (long ago, as a rule: the wait is for one small copy, not for the stream)
+  const size_t bytes = (size_t)P->d.B * 4;
+  if (P->len_pin == nullptr) {
+    CSN_HIP_CHECK(hipMalloc((void**)&P->len_dev, bytes));
+    CSN_HIP_CHECK(hipHostMalloc((void**)&P->len_pin, bytes, hipHostMallocDefault));
+    CSN_HIP_CHECK(hipEventCreateWithFlags(&P->len_ev, hipEventDisableTiming));
+  } else {
+    CSN_HIP_CHECK(hipEventSynchronize(P->len_ev));
+  }
+  memcpy(P->len_pin, P->lengths.data(), bytes);
+  CSN_HIP_CHECK(hipMemcpyAsync(P->len_dev, P->len_pin, bytes, hipMemcpyHostToDevice, st));
+  CSN_HIP_CHECK(hipEventRecord(P->len_ev, st));
+  P->dlen = P->len_dev;
+  return CSN_OK;
+}
+// input gradient out of its time-major workspace form; with lengths the caller's rows have T_full steps, zeros behind the longest
+static int emit_dx(const csnLstmPlan& P, const float* dx_tm, float* dx, int64_t I, hipStream_t st) {
+  const int B = P.d.B, T = P.d.T;
+  if (P.dlen != nullptr) tb_to_bt_len_kernel<<<csn::grid_for((int64_t)P.T_full * B * I), 256, 0, st>>>(dx_tm, dx, B, P.T_full, T, (int)I);
+  else csn::tb_to_bt_kernel<<<csn::grid_for((int64_t)T * B * I), 256, 0, st>>>(dx_tm, dx, B, T, (int)I);
+  CSN_LAUNCH_CHECK();
+  return CSN_OK;
+}
+// gradient w.r.t. h_n of the layer below, into this layer's time-major input gradient `dx_tm` whose steps [t_lo, t_hi] were
+// just written: at T-1 without lengths, at each row's own last step with them
+static int add_dh_n_rows(const csnLstmPlan& P, const float* dh_below, float* dx_tm, int t_lo, int t_hi, hipStream_t st) {
+  const int B = P.d.B, H = P.d.H, T = P.d.T;
+  if (P.dlen != nullptr) {
+    add_at_end_kernel<<<csn::grid_for((int64_t)B * H), 256, 0, st>>>(dh_below, dx_tm, P.dlen, t_lo, t_hi, B, H);
+  } else {
+    if (t_hi != T - 1) return CSN_OK;
+    csn::add_rows_kernel<<<csn::grid_for((int64_t)B * H), 256, 0, st>>>(dh_below, dx_tm + (size_t)(T - 1) * B * H, (int64_t)B * H);
+  }
+  CSN_LAUNCH_CHECK();
   return CSN_OK;
 }
 
@@ -565,6 +726,22 @@ static int gemm_tn_full(const void* A, const void* B, float* C, int64_t M, int64
   return launch_reduce_slabs((const float*)scratch, M * N, S, C, nullptr, M * N, accumulate, st);
 }
 
+// lengths: zeros over the padding of the re-laid-out input (x_c, and the fragment-major slabs of the fused projection)
+static int mask_x(const csnLstmPlan& P, char* ws, hipStream_t st) {
+  if (P.dlen == nullptr) return CSN_OK;
+  const csnLstmDesc& d = P.d;
+  const int64_t n = (int64_t)d.T * d.B * d.I;
+  if (d.dtype == CSN_BF16) mask_tm_kernel<bf16_t><<<grid_for(n), 256, 0, st>>>((bf16_t*)(ws + P.w.x_c), P.dlen, d.B, d.T, d.I);
+  else mask_tm_kernel<float><<<grid_for(n), 256, 0, st>>>((float*)(ws + P.w.x_c), P.dlen, d.B, d.T, d.I);
+  CSN_LAUNCH_CHECK();
+  if (P.w.fuse_x) {
+    const int64_t Bpad = ((int64_t)d.B + 63) / 64 * 64;
+    mask_x_blk_kernel<<<grid_for((int64_t)d.T * Bpad * d.I / 8), 256, 0, st>>>((bf16_t*)(ws + P.w.x_blk), P.dlen, d.B, Bpad, d.T, d.I);
+    CSN_LAUNCH_CHECK();
+  }
+  return CSN_OK;
+}
+
 // =============================================================================================
 // v1 path
 // =============================================================================================
@@ -584,6 +761,7 @@ static int forward_v1(Plan& P, char* ws, const float* x, int64_t xsb, int64_t xs
   const int Cz = P.opt.chunk, lag = Cz;
   int rc;
   if ((rc = launch_cast_strided(x, xsb, xst, B, T, d->I, ws + w.x_c, dt, st))) return rc;
+  if ((rc = mask_x(P, ws, st))) return rc;
   for (int l = 0; l < NL; ++l) {
     const LayerWs& L = w.layer[l];
     const int64_t I = l == 0 ? d->I : H;
@@ -664,6 +842,8 @@ static int backward_v1(Plan& P, char* ws, const float* dy_last, const float* dy_
   const int D = T + lag * (NL - 1);
   for (int dg = 0; dg < D; ++dg) {
     CellBwdBatch b{};
+    CellMask mask{P.dlen, {0, 0, 0, 0}};
+    const CellMask* mk = P.dlen ? &mask : nullptr;
     int np = 0;
     for (int l = NL - 1; l >= 0; --l) {
       const int r = dg - lag * (NL - 1 - l);
@@ -672,9 +852,10 @@ static int backward_v1(Plan& P, char* ws, const float* dy_last, const float* dy_
       const LayerWs& L = w.layer[l];
       const bool top = (l == NL - 1);
       if (np == 4) {
-        if ((rc = launch_cell_bwd_batch(b, np, B, H, dt, st))) return rc;
+        if ((rc = launch_cell_bwd_batch(b, np, B, H, dt, st, mk))) return rc;
         np = 0;
       }
+      mask.t[np] = t;
       const float* dy_t = top ? (dy_tm ? dy_tm + (size_t)t * B * H : (t == T - 1 ? dy_last : nullptr))
                               : (const float*)(ws + w.layer[l + 1].dx) + (size_t)t * B * H;
       b.p[np++] = CellBwdOne{(t == T - 1) ? nullptr : (const void*)(ws + L.dgates + (size_t)(t + 1) * B * G * es), ws + L.whht, dy_t, H,
@@ -682,7 +863,7 @@ static int backward_v1(Plan& P, char* ws, const float* dy_last, const float* dy_
                              (const float*)(ws + L.c_all) + (size_t)t * B * H, (float*)(ws + L.dc_carry),
                              ws + L.dgates + (size_t)t * B * G * es};
     }
-    if (np > 0 && (rc = launch_cell_bwd_batch(b, np, B, H, dt, st))) return rc;
+    if (np > 0 && (rc = launch_cell_bwd_batch(b, np, B, H, dt, st, mk))) return rc;
     for (int l = NL - 1; l >= 1; --l) {
       const int r = dg - lag * (NL - 1 - l);
       if (r < 0 || r >= T || ((r + 1) % Cz != 0 && r != T - 1)) continue;
@@ -691,11 +872,8 @@ static int backward_v1(Plan& P, char* ws, const float* dy_last, const float* dy_
       if ((rc = gemm_nt(ws + L.dgates + (size_t)t_lo * B * G * es, ws + L.wiht, nullptr, (float*)(ws + L.dx) + (size_t)t_lo * B * H,
                         (int64_t)(t_hi - t_lo + 1) * B, H, G, dt, CSN_F32, 0, st, P.opt)))
         return rc;
-      if (dh_n && t_hi == T - 1) {      // gradient w.r.t. h_n of the layer below joins its dy at t = T-1
-        add_rows_kernel<<<grid_for((int64_t)B * H), 256, 0, st>>>(dh_n + (size_t)(l - 1) * B * H,
-                                                                   (float*)(ws + L.dx) + (size_t)(T - 1) * B * H, (int64_t)B * H);
-        CSN_LAUNCH_CHECK();
-      }
+      // gradient w.r.t. h_n of the layer below joins its dy at t = T-1 (with lengths: at each row's last step)
+      if (dh_n && (rc = add_dh_n_rows(P, dh_n + (size_t)(l - 1) * B * H, (float*)(ws + L.dx), t_lo, t_hi, st))) return rc;
     }
   }
   for (int l = NL - 1; l >= 0; --l) {
@@ -712,8 +890,7 @@ static int backward_v1(Plan& P, char* ws, const float* dy_last, const float* dy_
   if (dx) {
     const LayerWs& L = w.layer[0];
     if ((rc = gemm_nt(ws + L.dgates, ws + L.wiht, nullptr, ws + L.dx, TB, d->I, G, dt, CSN_F32, 0, st, P.opt))) return rc;
-    tb_to_bt_kernel<<<grid_for(TB * d->I), 256, 0, st>>>((const float*)(ws + L.dx), dx, B, T, d->I);
-    CSN_LAUNCH_CHECK();
+    if ((rc = emit_dx(P, (const float*)(ws + L.dx), dx, d->I, st))) return rc;
   }
   return CSN_OK;
 }
@@ -917,6 +1094,7 @@ static int forward_il(Plan& P, char* ws, const float* x, int64_t xsb, int64_t xs
   }
   if (prep_rc != CSN_OK) return prep_rc;
   if ((rc = launch_prep_multi(pa, st))) return rc;
+  if ((rc = mask_x(P, ws, st))) return rc;
   if (!w.fuse_x) {
     // layer 0 input projection for every step, main stream
     if ((rc = gemm_nt(ws + w.x_c, ws + w.layer[0].wih, (const float*)(ws + w.layer[0].bias), ws + w.layer[0].xproj,
@@ -1221,6 +1399,8 @@ static int backward_il(Plan& P, char* ws, const float* dy_last, const float* dy_
     CellBwdArgs a{};
     a.B = B;
     a.H = H;
+    CellMask mask{P.dlen, {0, 0, 0, 0}};
+    const CellMask* mk = P.dlen ? &mask : nullptr;
     int np = 0;
     for (int l = NL - 1; l >= 0; --l) {
       const int r = dg - lag * (NL - 1 - l);      // reverse step index of layer l on this diagonal
@@ -1229,11 +1409,12 @@ static int backward_il(Plan& P, char* ws, const float* dy_last, const float* dy_
       const LayerWs& L = w.layer[l];
       const bool top = (l == NL - 1);
       if (np == 4) {       // (more than 4 layers on one diagonal, L >= 5: a second launch, the problems are independent)
-        if ((rc = launch_cell_bwd_il(a, np, st))) return rc;
+        if ((rc = launch_cell_bwd_il(a, np, st, mk))) return rc;
         ++n_launch;
         n_cells += np;
         np = 0;
       }
+      mask.t[np] = t;
       if (!top && r % Cz == 0) CSN_HIP_CHECK(hipStreamWaitEvent(st, dx_ready[(size_t)(l + 1) * nch + r / Cz], 0));
       CellBwdProb& P = a.p[np++];
       P.dg_next_blk = (t == T - 1) ? nullptr : (const bf16_t*)(ws + L.dgblk[(t + 1) & 1]);
@@ -1253,7 +1434,7 @@ static int backward_il(Plan& P, char* ws, const float* dy_last, const float* dy_
       P.dg_out_blk = (bf16_t*)(ws + L.dgblk[t & 1]);
     }
     if (np == 0) continue;
-    if ((rc = launch_cell_bwd_il(a, np, st))) return rc;
+    if ((rc = launch_cell_bwd_il(a, np, st, mk))) return rc;
     ++n_launch;
     n_cells += np;
     for (int l = NL - 1; l >= 0; --l) {
@@ -1275,11 +1456,8 @@ static int backward_il(Plan& P, char* ws, const float* dy_last, const float* dy_
                          (float*)(ws + L.dx) + (size_t)t_lo * B * I, (int64_t)(t_hi - t_lo + 1) * B, I, G, CSN_BF16,
                          CSN_F32, 0, side, P.opt);
         if (rc) return rc;
-        if (dh_n && t_hi == T - 1) {      // gradient w.r.t. h_n of the layer below joins its dy at t = T-1
-          add_rows_kernel<<<grid_for((int64_t)B * H), 256, 0, side>>>(dh_n + (size_t)(l - 1) * B * H,
-                                                                       (float*)(ws + L.dx) + (size_t)(T - 1) * B * H, (int64_t)B * H);
-          CSN_LAUNCH_CHECK();
-        }
+        // gradient w.r.t. h_n of the layer below joins its dy at t = T-1 (with lengths: at each row's last step)
+        if (dh_n && (rc = add_dh_n_rows(P, dh_n + (size_t)(l - 1) * B * H, (float*)(ws + L.dx), t_lo, t_hi, side))) return rc;
         hipEvent_t ev;
         if ((rc = next_event(sc, &ev))) return rc;
         CSN_HIP_CHECK(hipEventRecord(ev, side));
@@ -1288,8 +1466,7 @@ static int backward_il(Plan& P, char* ws, const float* dy_last, const float* dy_
         rc = gemm_nt(ws + L.dgates, ws + L.wiht, nullptr, ws + L.dx, TB, I, G, CSN_BF16, CSN_F32, 0,
                          side, P.opt);
         if (rc) return rc;
-        tb_to_bt_kernel<<<grid_for(TB * I), 256, 0, side>>>((const float*)(ws + L.dx), dx, B, T, (int)I);
-        CSN_LAUNCH_CHECK();
+        if ((rc = emit_dx(P, (const float*)(ws + L.dx), dx, I, side))) return rc;
       }
       if (last && (rc = weight_grads(l))) return rc;
     }
@@ -1340,11 +1517,10 @@ static int backward_persist(Plan& P, char* ws, const float* dy_last, const float
                                    hipMemcpyDeviceToDevice, st));
   // gradient w.r.t. h_n of layer l - 1: added to row T-1 of layer l's input gradient once the GEMM of that chunk has
   // run (inline, or beside the recurrence in the next launch), before the launch that runs layer l - 1's first chunk
-  auto add_dh_n = [&](int l) -> int {
-    add_rows_kernel<<<grid_for((int64_t)B * H), 256, 0, st>>>(dh_n + (size_t)(l - 1) * B * H,
-                                                               (float*)(ws + w.layer[l].dx) + (size_t)(T - 1) * B * H, (int64_t)B * H);
-    CSN_LAUNCH_CHECK();
-    return CSN_OK;
+  // (with lengths: after the GEMM of EVERY chunk, at the rows whose last step lies in it)
+  struct DhAdd { int l, t_lo, t_hi; };       // l = 0: none
+  auto add_dh_n = [&](const DhAdd& q) -> int {
+    return add_dh_n_rows(P, dh_n + (size_t)(q.l - 1) * B * H, (float*)(ws + w.layer[q.l].dx), q.t_lo, q.t_hi, st);
   };
   const bool try_local = !P.opt.no_xcd_local;
 
@@ -1387,7 +1563,7 @@ static int backward_persist(Plan& P, char* ws, const float* dy_last, const float
     for (int l = 0; l < NL; ++l) CSN_HIP_CHECK(hipMemsetAsync(ws + w.layer[l].dg_blk_all, 0xff, (size_t)4 * Bpad * G * 2, st));
   int n_launch = 0;
   BesideGemm pending[3];           // GEMMs of the chunks finished by the previous launch
-  int pending_add[3] = {0, 0, 0};  // layer whose dh_n term follows pending[i] (its first chunk), or 0
+  DhAdd pending_add[3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};  // dh_n term that follows pending[i] (layer 0: none)
   int npending = 0;
   if ((rc = prof_mark(g_prof, 2, st))) return rc;
   for (int dg = 0; dg < ndiag; ++dg) {
@@ -1424,22 +1600,23 @@ static int backward_persist(Plan& P, char* ws, const float* dy_last, const float
       for (int i = 0; i < npending; ++i) {
         const BesideGemm& g = pending[i];
         if ((rc = gemm_nt(g.A, g.Bt, nullptr, g.C, g.M, g.N, g.K, CSN_BF16, CSN_F32, 0, st, P.opt))) return rc;
-        if (pending_add[i] && (rc = add_dh_n(pending_add[i]))) return rc;
+        if (pending_add[i].l && (rc = add_dh_n(pending_add[i]))) return rc;
       }
       npending = 0;
       continue;
     }
     a.nslots = ns;
     a.ngemm = npending;
-    int launch_adds[3], nadds = 0;
+    DhAdd launch_adds[3];
+    int nadds = 0;
     for (int i = 0; i < npending; ++i) {
       a.gemm[i] = pending[i];
-      if (pending_add[i]) launch_adds[nadds++] = pending_add[i];
+      if (pending_add[i].l) launch_adds[nadds++] = pending_add[i];
     }
     npending = 0;
     a.agree = try_local ? (unsigned long long*)(ws + w.agree_b) + (size_t)dg * 8 : nullptr;
     if ((rc = prof_pair(g_prof, 1, false, st))) return rc;
-    if ((rc = launch_bwd_persist(a, st))) return rc;
+    if ((rc = launch_bwd_persist(a, st, P.dlen))) return rc;
     if ((rc = prof_pair(g_prof, 1, true, st))) return rc;
     ++n_launch;
     for (int i = 0; i < nadds; ++i)
@@ -1453,13 +1630,13 @@ static int backward_persist(Plan& P, char* ws, const float* dy_last, const float
       const bf16_t* Ag = (const bf16_t*)(ws + L.dgates) + (size_t)t_lo * B * G;
       float* Cg = (float*)(ws + L.dx) + (size_t)t_lo * B * H;
       const int64_t Mg = (int64_t)(t_hi - t_lo + 1) * B;
-      const int add = (dh_n && chk[i] == 0) ? l : 0;
+      const DhAdd add{(dh_n && (chk[i] == 0 || P.dlen)) ? l : 0, t_lo, t_hi};
       if (beside) {
         pending_add[npending] = add;
         pending[npending++] = BesideGemm{Ag, (const bf16_t*)(ws + L.wiht), Cg, (int)Mg, H, (int)G};
       } else {
         if ((rc = gemm_nt(Ag, ws + L.wiht, nullptr, Cg, Mg, H, G, CSN_BF16, CSN_F32, 0, st, P.opt))) return rc;
-        if (add && (rc = add_dh_n(add))) return rc;
+        if (add.l && (rc = add_dh_n(add))) return rc;
       }
     }
   }
@@ -1473,8 +1650,7 @@ static int backward_persist(Plan& P, char* ws, const float* dy_last, const float
     if ((rc = gemm_nt(ws + L.dgates, ws + L.wiht, nullptr, ws + L.dx, TB, d->I, G, CSN_BF16, CSN_F32, 0,
                           st, P.opt)))
       return rc;
-    tb_to_bt_kernel<<<grid_for(TB * d->I), 256, 0, st>>>((const float*)(ws + L.dx), dx, B, T, d->I);
-    CSN_LAUNCH_CHECK();
+    if ((rc = emit_dx(P, (const float*)(ws + L.dx), dx, d->I, st))) return rc;
   }
   // (every recurrence launch has been enqueued by now: what a gradient-ready callback starts -- a collective on another
   // stream -- runs beside the remaining layers' weight-gradient GEMMs, never beside a one-workgroup-per-CU launch)
@@ -1525,6 +1701,54 @@ extern "C" int csn_lstm_forward(csnLstmPlan* Pp, const float* x, int64_t x_strid
   int rc;
   // (the status word is NOT cleared here: it stays raised from the first timed-out hand-off until
   // csn_lstm_status_clear, so a check at the end of an epoch / a timed region covers every step in it)
+  if ((rc = upload_lengths(Pp, st))) return rc;
+  if (P.dlen != nullptr) {
+    // Variable-length batch: every path runs its unchanged kernels over steps 0 .. max(lengths)-1 of ALL rows (short rows
+    // run on over zeroed padding), then each row's results are selected: slot n of h_all / c_all is its final state
+    if (P.t_eff > 0) {
+      EffectiveT scope(P.d, P.t_eff);
+      rc = w.il ? forward_il(P, ws, x, x_stride_b, x_stride_t, w_ih, w_hh, b_ih, b_hh, h0, c0, training, stream)
+                : forward_v1(P, ws, x, x_stride_b, x_stride_t, w_ih, w_hh, b_ih, b_hh, h0, c0, training, stream);
+      if (rc) return rc;
+    } else {
+      // every row is empty: no recurrence launch; slot 0 (the initial state) is all the gathers below read
+      for (int l = 0; l < d->L; ++l) {
+        const LayerWs& L = w.layer[l];
+        if (h0) {
+          if ((rc = launch_cast(h0 + (size_t)l * B * H, ws + L.h_all, (int64_t)B * H, dt, st))) return rc;
+        } else {
+          CSN_HIP_CHECK(hipMemsetAsync(ws + L.h_all, 0, (size_t)B * H * es, st));
+        }
+        if (c0)
+          CSN_HIP_CHECK(hipMemcpyAsync(ws + L.c_all, c0 + (size_t)l * B * H, (size_t)B * H * 4, hipMemcpyDeviceToDevice, st));
+        else
+          CSN_HIP_CHECK(hipMemsetAsync(ws + L.c_all, 0, (size_t)B * H * 4, st));
+      }
+      if (h0 || c0) P.state_seen = true;      // (slot 0 is no longer the zeros csn_lstm_workspace_init left)
+      P.prof.have[0] = false;
+    }
+    const unsigned gbh = grid_for((int64_t)B * H);
+    auto gather_h = [&](const LayerWs& L, float* out) {
+      if (dt == CSN_BF16) gather_state_kernel<bf16_t><<<gbh, 256, 0, st>>>((const bf16_t*)(ws + L.h_all), P.dlen, out, B, H);
+      else gather_state_kernel<float><<<gbh, 256, 0, st>>>((const float*)(ws + L.h_all), P.dlen, out, B, H);
+    };
+    for (int l = 0; l < d->L; ++l) {
+      const LayerWs& L = w.layer[l];
+      if (h_n) gather_h(L, h_n + (size_t)l * B * H);
+      if (c_n) gather_state_kernel<float><<<gbh, 256, 0, st>>>((const float*)(ws + L.c_all), P.dlen, c_n + (size_t)l * B * H, B, H);
+    }
+    const LayerWs& top = w.layer[d->L - 1];
+    if (y_last) gather_h(top, y_last);
+    if (y_all) {
+      const int64_t n = (int64_t)T * B * H;
+      if (dt == CSN_BF16)
+        gather_y_all_len_kernel<bf16_t><<<grid_for(n), 256, 0, st>>>((const bf16_t*)(ws + top.h_all), y_all, P.dlen, B, T, H);
+      else
+        gather_y_all_len_kernel<float><<<grid_for(n), 256, 0, st>>>((const float*)(ws + top.h_all), y_all, P.dlen, B, T, H);
+    }
+    CSN_LAUNCH_CHECK();
+    return CSN_OK;
+  }
   if (w.il)
     rc = forward_il(P, ws, x, x_stride_b, x_stride_t, w_ih, w_hh, b_ih, b_hh, h0, c0, training, stream);
   else if (w.f32_persist)
@@ -1585,6 +1809,73 @@ extern "C" int csn_lstm_backward(csnLstmPlan* Pp, const float* dy_last, const fl
   const int B = d->B, T = d->T, H = d->H;
   const int64_t TB = (int64_t)T * B;
 
+  int rc;
+  if ((rc = upload_lengths(Pp, st))) return rc;
+  if (P.dlen != nullptr) {
+    // Variable-length batch (the lengths of the matching forward): the backward of the steps the forward ran, with the
+    // masked cell kernels; every gradient that enters at a row's end is added at that row's own last step
+    const int L_ = d->L, dt = d->dtype;
+    const int64_t G = 4 * (int64_t)H;
+    if (P.t_eff > 0) {
+      const int Te = P.t_eff;
+      float* buf = (float*)(ws + w.dy_tm);       // dense time-major dy of the top layer, zeros over the padding
+      bt_to_tb_len_kernel<<<grid_for((int64_t)Te * B * H), 256, 0, st>>>(dy_all, buf, P.dlen, B, T, Te, H);
+      if (dy_last) add_at_end_kernel<<<grid_for((int64_t)B * H), 256, 0, st>>>(dy_last, buf, P.dlen, 0, Te - 1, B, H);
+      if (dh_n) add_at_end_kernel<<<grid_for((int64_t)B * H), 256, 0, st>>>(dh_n + (size_t)(L_ - 1) * B * H, buf, P.dlen, 0, Te - 1, B, H);
+      CSN_LAUNCH_CHECK();
+      {
+        EffectiveT scope(P.d, Te);
+        rc = w.il ? backward_il(P, ws, nullptr, buf, dh_n, dc_n, dw_ih, dw_hh, db_ih, db_hh, dx, stream)
+                  : backward_v1(P, ws, nullptr, buf, dh_n, dc_n, dw_ih, dw_hh, db_ih, db_hh, dx, stream);
+      }
+      if (rc) return rc;
+    } else {
+      // every row is empty: no recurrence, no parameter contribution
+      if (dx) CSN_HIP_CHECK(hipMemsetAsync(dx, 0, (size_t)T * B * d->I * 4, st));
+      for (int l = L_ - 1; l >= 0; --l) {
+        if (!P.grad_accumulate) {
+          const int64_t I = l == 0 ? d->I : H;
+          CSN_HIP_CHECK(hipMemsetAsync(dw_ih[l], 0, (size_t)(G * I) * 4, st));
+          CSN_HIP_CHECK(hipMemsetAsync(dw_hh[l], 0, (size_t)(G * H) * 4, st));
+          CSN_HIP_CHECK(hipMemsetAsync(db_ih[l], 0, (size_t)G * 4, st));
+          CSN_HIP_CHECK(hipMemsetAsync(db_hh[l], 0, (size_t)G * 4, st));
+        }
+        P.grads_ready(l);
+      }
+      P.prof.have[1] = false;
+    }
+    for (int l = 0; l < L_ && (dh0 || dc0); ++l) {
+      const LayerWs& L = w.layer[l];
+      if (dh0) {
+        float* out = dh0 + (size_t)l * B * H;
+        if (P.t_eff > 0) {
+          const dim3 grid((unsigned)((H + 63) / 64), (unsigned)((B + 31) / 32));
+          if (w.il)
+            lstm_dh0_kernel<bf16_t, true><<<grid, 256, 0, st>>>((const bf16_t*)(ws + L.dgates), (const bf16_t*)(ws + L.whht_blk), B, H, out);
+          else if (dt == CSN_BF16)
+            lstm_dh0_kernel<bf16_t, false><<<grid, 256, 0, st>>>((const bf16_t*)(ws + L.dgates), (const bf16_t*)(ws + L.whht), B, H, out);
+          else
+            lstm_dh0_kernel<float, false><<<grid, 256, 0, st>>>((const float*)(ws + L.dgates), (const float*)(ws + L.whht), B, H, out);
+        } else {
+          CSN_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)B * H * 4, st));
+        }
+        // an empty row's dgates are zero at step 0: its dh0 is the gradient w.r.t. its h_n
+        if (dh_n) add_rows_len0_kernel<<<grid_for((int64_t)B * H), 256, 0, st>>>(dh_n + (size_t)l * B * H, out, P.dlen, B, H);
+        CSN_LAUNCH_CHECK();
+      }
+      if (dc0) {
+        // the carried dc: an empty row's passed every (masked) step as it was
+        if (P.t_eff > 0)
+          CSN_HIP_CHECK(hipMemcpyAsync(dc0 + (size_t)l * B * H, ws + L.dc_carry, (size_t)B * H * 4, hipMemcpyDeviceToDevice, st));
+        else if (dc_n)
+          CSN_HIP_CHECK(hipMemcpyAsync(dc0 + (size_t)l * B * H, dc_n + (size_t)l * B * H, (size_t)B * H * 4, hipMemcpyDeviceToDevice, st));
+        else
+          CSN_HIP_CHECK(hipMemsetAsync(dc0 + (size_t)l * B * H, 0, (size_t)B * H * 4, st));
+      }
+    }
+    return CSN_OK;
+  }
+
   // gradient w.r.t. the top layer's outputs, time-major.  With only dy_last, no buffer is needed.
   const float* dy_tm = nullptr;
   if (dy_all) {
@@ -1614,7 +1905,6 @@ extern "C" int csn_lstm_backward(csnLstmPlan* Pp, const float* dy_last, const fl
       dy_last = dh_top;
     }
   }
-  int rc;
   if (w.il)
     rc = backward_il(P, ws, dy_last, dy_tm, dh_n, dc_n, dw_ih, dw_hh, db_ih, db_hh, dx, stream);
   else if (w.f32_persist)

@@ -70,8 +70,15 @@ __device__ __forceinline__ void bstore_b128(__amdgpu_buffer_rsrc_t rsrc, unsigne
   __builtin_amdgcn_raw_buffer_store_b128(cvt.u, rsrc, (int)byte_off, soff, WT ? 16 : 0);   // sc1 = write-through
 }
 
-template <int NUT, int KS, bool DPOLL>
-__global__ void __launch_bounds__(256) lstm_bwd_persist_kernel(PersistBwdArgs a) {
+// MASK (variable-length batches): `lens` = the rows' lengths [B]; a cell at t >= lengths[row] publishes zero gate gradients
+// and keeps the carried dc.  The row's length is loaded once per launch, beside the carried dc.
+struct PersistLens { const int* lengths; };
+struct PersistNoLens {};
+template <bool MASK> struct PersistLensArg { typedef PersistNoLens type; };
+template <> struct PersistLensArg<true> { typedef PersistLens type; };
+
+template <int NUT, int KS, bool DPOLL, bool MASK = false>
+__global__ void __launch_bounds__(256) lstm_bwd_persist_kernel(PersistBwdArgs a, typename PersistLensArg<MASK>::type lens) {
 #ifndef CSN_BWD_RING
 #define CSN_BWD_RING 5
 #endif
@@ -173,6 +180,7 @@ __global__ void __launch_bounds__(256) lstm_bwd_persist_kernel(PersistBwdArgs a)
   int prow[NPASS], puq[NPASS], prl[NPASS], pjq[NPASS];
   bool pok[NPASS];
   float4 dcn[NPASS], cc[NPASS];
+  int plen[NPASS];             // (MASK only)
 #pragma unroll
   for (int ps = 0; ps < NPASS; ++ps) {
     const int p = tid + ps * 256;
@@ -183,6 +191,10 @@ __global__ void __launch_bounds__(256) lstm_bwd_persist_kernel(PersistBwdArgs a)
     pok[ps] = prow[ps] < B;
     dcn[ps] = make_float4(0.f, 0.f, 0.f, 0.f);
     cc[ps] = make_float4(0.f, 0.f, 0.f, 0.f);
+    plen[ps] = 0;
+    if constexpr (MASK) {
+      if (pok[ps]) plen[ps] = lens.lengths[prow[ps]];
+    }
     if (pok[ps]) {
       dcn[ps] = *reinterpret_cast<const float4*>(S.dc_carry + (size_t)prow[ps] * H + puq[ps]);
       cc[ps] = *reinterpret_cast<const float4*>(c_all + ((size_t)(t_hi + 1) * B + prow[ps]) * H + puq[ps]);
@@ -492,6 +504,13 @@ __global__ void __launch_bounds__(256) lstm_bwd_persist_kernel(PersistBwdArgs a)
         out[4 * q + 3] = d_o * go * (1.0f - go);
         dcarry[q] = dc * gf;
       }
+      if constexpr (MASK) {
+        const bool dead = t >= plen[ps];
+#pragma unroll
+        for (int e = 0; e < 16; ++e) out[e] = dead ? 0.f : out[e];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) dcarry[q] = dead ? dcv[q] : dcarry[q];
+      }
       bf16x8 lo, hi;
 #pragma unroll
       for (int e = 0; e < 8; ++e) { lo[e] = (bf16_t)out[e]; hi[e] = (bf16_t)out[8 + e]; }
@@ -545,10 +564,15 @@ bool bwd_persist_supported(int B, int H, int dtype, const Options& opt) {
 int bwd_persist_slices(int H) { return H / 32; }
 
 template <int NUT, int KS>
-static int launch_bwd_persist_t(const PersistBwdArgs& a, hipStream_t st) {
+static int launch_bwd_persist_t(const PersistBwdArgs& a, hipStream_t st, const int* lengths) {
   size_t lds = (size_t)4 * 4 * NUT * kBwdRedTile * sizeof(float4);
-  if (int rc = ensure_dyn_lds<&lstm_bwd_persist_kernel<NUT, KS, false>>((int)kBesideLdsBytes)) return rc;
-  if (int rc = ensure_dyn_lds<&lstm_bwd_persist_kernel<NUT, KS, true>>((int)kBesideLdsBytes)) return rc;
+  if (lengths != nullptr) {
+    if (int rc = ensure_dyn_lds<&lstm_bwd_persist_kernel<NUT, KS, false, true>>((int)kBesideLdsBytes)) return rc;
+    if (int rc = ensure_dyn_lds<&lstm_bwd_persist_kernel<NUT, KS, true, true>>((int)kBesideLdsBytes)) return rc;
+  } else {
+    if (int rc = ensure_dyn_lds<&lstm_bwd_persist_kernel<NUT, KS, false>>((int)kBesideLdsBytes)) return rc;
+    if (int rc = ensure_dyn_lds<&lstm_bwd_persist_kernel<NUT, KS, true>>((int)kBesideLdsBytes)) return rc;
+  }
   const unsigned nslices = (unsigned)(a.H / (16 * NUT));
   PersistBwdArgs b = a;
   if (b.xcd_groups) {
@@ -560,13 +584,17 @@ static int launch_bwd_persist_t(const PersistBwdArgs& a, hipStream_t st) {
     }
   }
   const unsigned grid = b.xcd_groups ? 8u * (unsigned)b.grid_slices : nslices * (unsigned)(b.MT * b.nslots);
-  if (b.data_polls) lstm_bwd_persist_kernel<NUT, KS, true><<<dim3(grid), 256, lds, st>>>(b);
-  else lstm_bwd_persist_kernel<NUT, KS, false><<<dim3(grid), 256, lds, st>>>(b);
+  if (lengths != nullptr) {
+    const PersistLens pl{lengths};
+    if (b.data_polls) lstm_bwd_persist_kernel<NUT, KS, true, true><<<dim3(grid), 256, lds, st>>>(b, pl);
+    else lstm_bwd_persist_kernel<NUT, KS, false, true><<<dim3(grid), 256, lds, st>>>(b, pl);
+  } else if (b.data_polls) lstm_bwd_persist_kernel<NUT, KS, true><<<dim3(grid), 256, lds, st>>>(b, PersistNoLens{});
+  else lstm_bwd_persist_kernel<NUT, KS, false><<<dim3(grid), 256, lds, st>>>(b, PersistNoLens{});
   CSN_LAUNCH_CHECK();
   return CSN_OK;
 }
 
-int launch_bwd_persist(const PersistBwdArgs& a, hipStream_t st) {
+int launch_bwd_persist(const PersistBwdArgs& a, hipStream_t st, const int* lengths) {
   CSN_REQUIRE(a.nslots >= 1 && a.nslots <= 4 && a.MT >= 1, "launch_bwd_persist: bad slot count");
   const int ns = bwd_persist_slices(a.H);
   CSN_REQUIRE(ns % 4 == 0 && ns <= kPersistFlagLine, "launch_bwd_persist: H=%d gives %d slices", a.H, ns);
@@ -575,12 +603,12 @@ int launch_bwd_persist(const PersistBwdArgs& a, hipStream_t st) {
   for (int i = 0; i < a.ngemm; ++i)
     CSN_REQUIRE(a.gemm[i].K % 64 == 0 && a.gemm[i].N % 4 == 0 && a.gemm[i].M > 0, "launch_bwd_persist: GEMM %d shape", i);
   switch (a.H) {
-    case 1024: return launch_bwd_persist_t<2, 32>(a, st);
-    case 768: return launch_bwd_persist_t<2, 24>(a, st);
-    case 512: return launch_bwd_persist_t<2, 16>(a, st);
-    case 384: return launch_bwd_persist_t<2, 12>(a, st);
-    case 256: return launch_bwd_persist_t<2, 8>(a, st);
-    case 128: return launch_bwd_persist_t<2, 4>(a, st);
+    case 1024: return launch_bwd_persist_t<2, 32>(a, st, lengths);
+    case 768: return launch_bwd_persist_t<2, 24>(a, st, lengths);
+    case 512: return launch_bwd_persist_t<2, 16>(a, st, lengths);
+    case 384: return launch_bwd_persist_t<2, 12>(a, st, lengths);
+    case 256: return launch_bwd_persist_t<2, 8>(a, st, lengths);
+    case 128: return launch_bwd_persist_t<2, 4>(a, st, lengths);
   }
   return fail(CSN_ERR_UNSUPPORTED, "launch_bwd_persist: no kernel for H=%d", a.H);
 }

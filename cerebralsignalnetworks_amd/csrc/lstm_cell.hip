@@ -133,9 +133,11 @@ lstm_cell_fwd_kernel(CellFwdBatch batch, int B, int H) {
 // ------------------------------------------------------------------------------------------
 // backward
 // ------------------------------------------------------------------------------------------
-template <typename T>
+// MASK (variable-length batches, CellMask in csn_common.h): a cell at t >= lengths[row] stores zero gate gradients and
+// keeps the carried dc -- a select on the results, so nothing the dead step read (NaN included) reaches an output
+template <typename T, bool MASK = false>
 __global__ void __launch_bounds__(256)
-lstm_cell_bwd_kernel(CellBwdBatch batch, int B, int H) {
+lstm_cell_bwd_kernel(CellBwdBatch batch, int B, int H, typename CellMaskArg<MASK>::type mask) {
   CSN_CELL_BWD_BIND;
   typedef Frag<T> F;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -184,6 +186,15 @@ lstm_cell_bwd_kernel(CellBwdBatch batch, int B, int H) {
     dag[r] = dc * gi[r] * (1.0f - gg[r] * gg[r]);
     dao[r] = d_o * go[r] * (1.0f - go[r]);
     dcarry[r] = dc * gf[r];
+  }
+  if constexpr (MASK) {
+    if (mask.t[blockIdx.z] >= mask.lengths[mrow]) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        dai[r] = daf[r] = dag[r] = dao[r] = 0.f;
+        dcarry[r] = dcn[r];
+      }
+    }
   }
   T* op = dg_out + (int64_t)mrow * K + ub;
   Vec4<T>::store(op, dai);
@@ -329,9 +340,9 @@ lstm_cell_fwd_ks_kernel(CellFwdBatch batch, int B, int H) {
   cell_fwd_epilogue<T>(mine, mrow, u0 + (lane >> 4) * 4, xproj, xproj_ld, c_prev, gates_out, c_out, h_out, H);
 }
 
-template <typename T>
+template <typename T, bool MASK = false>
 __global__ void __launch_bounds__(512)
-lstm_cell_bwd_ks_kernel(CellBwdBatch batch, int B, int H) {
+lstm_cell_bwd_ks_kernel(CellBwdBatch batch, int B, int H, typename CellMaskArg<MASK>::type mask) {
   CSN_CELL_BWD_BIND;
   typedef Frag<T> F;
   // 32 rows x 32 units per workgroup, K = 4H in 8 slices (one per wave): 192 workgroups at B 256 / H 768 -- 64 x 32 tiles
@@ -446,6 +457,15 @@ lstm_cell_bwd_ks_kernel(CellBwdBatch batch, int B, int H) {
     dao[r] = d_o * go[r] * (1.0f - go[r]);
     dcarry[r] = dc * gf[r];
   }
+  if constexpr (MASK) {
+    if (mask.t[blockIdx.z] >= mask.lengths[mrow]) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        dai[r] = daf[r] = dag[r] = dao[r] = 0.f;
+        dcarry[r] = dcn[r];
+      }
+    }
+  }
   T* op = dg_out + (int64_t)mrow * K + ub;
   Vec4<T>::store(op, dai);
   Vec4<T>::store(op + H, daf);
@@ -478,16 +498,23 @@ int launch_cell_fwd(const void* h_prev, const void* w_hh, const float* xproj, in
   return launch_cell_fwd_batch(b, 1, B, H, dtype, st);
 }
 
-int launch_cell_bwd_batch(const CellBwdBatch& b, int np, int B, int H, int dtype, hipStream_t st) {
+int launch_cell_bwd_batch(const CellBwdBatch& b, int np, int B, int H, int dtype, hipStream_t st, const CellMask* mask) {
   CSN_REQUIRE(np >= 1 && np <= 4, "launch_cell_bwd_batch: %d problems", np);
+  const CellNoMask none{};
   if (cell_ks_ok(H, dtype)) {
     dim3 gridk((unsigned)(H / 32), (unsigned)((B + 31) / 32), (unsigned)np);
-    if (dtype == CSN_BF16) lstm_cell_bwd_ks_kernel<bf16_t><<<gridk, 512, 0, st>>>(b, B, H);
-    else lstm_cell_bwd_ks_kernel<float><<<gridk, 512, 0, st>>>(b, B, H);
+    if (mask != nullptr) {
+      if (dtype == CSN_BF16) lstm_cell_bwd_ks_kernel<bf16_t, true><<<gridk, 512, 0, st>>>(b, B, H, *mask);
+      else lstm_cell_bwd_ks_kernel<float, true><<<gridk, 512, 0, st>>>(b, B, H, *mask);
+    } else if (dtype == CSN_BF16) lstm_cell_bwd_ks_kernel<bf16_t><<<gridk, 512, 0, st>>>(b, B, H, none);
+    else lstm_cell_bwd_ks_kernel<float><<<gridk, 512, 0, st>>>(b, B, H, none);
   } else {
     dim3 grid((unsigned)(H / 16), (unsigned)((B + 63) / 64), (unsigned)np);
-    if (dtype == CSN_BF16) lstm_cell_bwd_kernel<bf16_t><<<grid, 256, 0, st>>>(b, B, H);
-    else lstm_cell_bwd_kernel<float><<<grid, 256, 0, st>>>(b, B, H);
+    if (mask != nullptr) {
+      if (dtype == CSN_BF16) lstm_cell_bwd_kernel<bf16_t, true><<<grid, 256, 0, st>>>(b, B, H, *mask);
+      else lstm_cell_bwd_kernel<float, true><<<grid, 256, 0, st>>>(b, B, H, *mask);
+    } else if (dtype == CSN_BF16) lstm_cell_bwd_kernel<bf16_t><<<grid, 256, 0, st>>>(b, B, H, none);
+    else lstm_cell_bwd_kernel<float><<<grid, 256, 0, st>>>(b, B, H, none);
   }
   CSN_LAUNCH_CHECK();
   return CSN_OK;

@@ -128,7 +128,8 @@ struct PersistBwdArgs {
 };
 bool bwd_persist_supported(int B, int H, int dtype, const Options& opt);
 int bwd_persist_slices(int H);
-int launch_bwd_persist(const PersistBwdArgs& a, hipStream_t st);
+// lengths != NULL (variable-length batches): [B] device array; the masked instantiation of the kernel
+int launch_bwd_persist(const PersistBwdArgs& a, hipStream_t st, const int* lengths = nullptr);
 
 // one launch for all layout-preparation jobs of a forward (lstm_cell_blk.hip: prep_multi_kernel)
 enum { kPrepBlockify = 0, kPrepPermRows, kPrepTransPerm, kPrepBias, kPrepCastX, kPrepBlockifyX };
@@ -151,7 +152,7 @@ int launch_prep_multi(PrepArgs& A, hipStream_t st);
 
 bool cell_blk_supported(int H, int dtype, const Options& opt);
 int launch_cell_fwd_il(const CellFwdArgs& a, int nprob, hipStream_t st, int max_nk);
-int launch_cell_bwd_il(const CellBwdArgs& a, int nprob, hipStream_t st);
+int launch_cell_bwd_il(const CellBwdArgs& a, int nprob, hipStream_t st, const CellMask* mask = nullptr);
 int launch_blockify_x(const float* x, int64_t xsb, int64_t xst, int B, int T, int I, void* dst, hipStream_t st);
 int launch_blockify(const float* src, int64_t ld_r, int64_t ld_k, int64_t R, int64_t K, int perm_r, int perm_k,
                     int64_t H, void* dst, hipStream_t st);

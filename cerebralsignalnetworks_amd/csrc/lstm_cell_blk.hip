@@ -482,8 +482,10 @@ __global__ void __launch_bounds__(256) lstm_cell_fwd_il_kernel(CellFwdArgs a) {
 // ------------------------------------------------------------------------------------------
 // backward: tile = 32 rows x 16*NUG units; K' = 4H (interleaved); wave w contracts k' in [w H, (w+1) H)
 // ------------------------------------------------------------------------------------------
-template <int NUG, int NK>
-__global__ void __launch_bounds__(256) lstm_cell_bwd_il_kernel(CellBwdArgs a) {
+// MASK (variable-length batches, CellMask in csn_common.h): a cell at t >= lengths[row] stores zero gate gradients and
+// keeps the carried dc
+template <int NUG, int NK, bool MASK = false>
+__global__ void __launch_bounds__(256) lstm_cell_bwd_il_kernel(CellBwdArgs a, typename CellMaskArg<MASK>::type mask) {
   constexpr int NT = 2 * NUG;
   constexpr int NPAIR = 32 * 4 * NUG;                // (row, unit-quad) pairs
   constexpr int NPASS = (NPAIR + 255) / 256;
@@ -608,6 +610,14 @@ __global__ void __launch_bounds__(256) lstm_cell_bwd_il_kernel(CellBwdArgs a) {
       out[4 * q + 3] = d_o * go * (1.0f - go);
       dcarry[q] = dc * gf;
     }
+    if constexpr (MASK) {
+      if (mask.t[blockIdx.z] >= mask.lengths[row]) {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) out[e] = 0.f;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) dcarry[q] = dcv[q];
+      }
+    }
     bf16x8 lo, hi;
 #pragma unroll
     for (int e = 0; e < 8; ++e) { lo[e] = (bf16_t)out[e]; hi[e] = (bf16_t)out[8 + e]; }
@@ -657,19 +667,20 @@ int launch_cell_fwd_il(const CellFwdArgs& a, int nprob, hipStream_t st, int max_
 }
 
 template <int NUG, int NK>
-static int launch_bwd_t(const CellBwdArgs& a, int nprob, hipStream_t st) {
+static int launch_bwd_t(const CellBwdArgs& a, int nprob, hipStream_t st, const CellMask* mask) {
   dim3 grid((unsigned)(a.H / (16 * NUG)), (unsigned)((a.B + 31) / 32), (unsigned)nprob);
-  lstm_cell_bwd_il_kernel<NUG, NK><<<grid, 256, 0, st>>>(a);
+  if (mask != nullptr) lstm_cell_bwd_il_kernel<NUG, NK, true><<<grid, 256, 0, st>>>(a, *mask);
+  else lstm_cell_bwd_il_kernel<NUG, NK><<<grid, 256, 0, st>>>(a, CellNoMask{});
   CSN_LAUNCH_CHECK();
   return CSN_OK;
 }
 
-int launch_cell_bwd_il(const CellBwdArgs& a, int nprob, hipStream_t st) {
+int launch_cell_bwd_il(const CellBwdArgs& a, int nprob, hipStream_t st, const CellMask* mask) {
   const int H = a.H;
   const int steps = H / 32;
   const int nug = (H % 48 == 0) ? 3 : ((H % 64 == 0) ? 4 : 2);
   const int nk = pick_nk(steps, 4);
-#define CSN_CASE(NUG, NK) if (nug == NUG && nk == NK) return launch_bwd_t<NUG, NK>(a, nprob, st)
+#define CSN_CASE(NUG, NK) if (nug == NUG && nk == NK) return launch_bwd_t<NUG, NK>(a, nprob, st, mask)
   CSN_CASE(3, 4); CSN_CASE(3, 3); CSN_CASE(3, 2); CSN_CASE(3, 1);
   CSN_CASE(4, 4); CSN_CASE(4, 2); CSN_CASE(4, 1);
   CSN_CASE(2, 4); CSN_CASE(2, 2); CSN_CASE(2, 1);

@@ -151,11 +151,13 @@ class _LstmStateFunction(torch.autograd.Function):
     chunks of one recording are chained through their state)."""
 
     @staticmethod
-    def forward(ctx, x, h0, c0, owner, training, L, *params):
+    def forward(ctx, x, h0, c0, owner, training, lengths, L, *params):
         w_ih, w_hh, b_ih, b_hh = params[0:L], params[L:2 * L], params[2 * L:3 * L], params[3 * L:4 * L]
         plan = owner._checkout(x.shape[0], x.shape[1], x.device, training)
+        plan.set_lengths(lengths)           # on every forward: plans are shared between calls (None = every row is T)
         _, y_all, h_n, c_n = plan.forward(x, w_ih, w_hh, b_ih, b_hh, want_all=True, h0=h0, c0=c0, want_state=True)
         ctx.lease, ctx.L, ctx.owner = _Lease(plan), L, owner
+        ctx.lengths = lengths               # kept with the node: the backward runs with the lengths of its forward
         ctx.need = (x.requires_grad, h0 is not None and h0.requires_grad, c0 is not None and c0.requires_grad)
         ctx.x_shape = x.shape
         ctx.param_like = params
@@ -183,12 +185,13 @@ class _LstmStateFunction(torch.autograd.Function):
         dc0 = torch.empty((L, d.B, d.H), dtype=torch.float32, device=dev) if need_dc0 else None
         plan.set_grad_callback(ctx.owner.grad_ready_hook if direct else None)
         plan.set_grad_mode(direct)
+        plan.set_lengths(ctx.lengths)
         plan.backward(None, dy_all, grads, dx=dx, dh_n=dh_n, dc_n=dc_n, dh0=dh0, dc0=dc0)
         ctx.lease.release()
         if direct:
-            return (dx, dh0, dc0, None, None, None, *([None] * (4 * L)))
+            return (dx, dh0, dc0, None, None, None, None, *([None] * (4 * L)))
         flat = [g for group in grads for g in group]
-        return (dx, dh0, dc0, None, None, None, *flat)
+        return (dx, dh0, dc0, None, None, None, None, *flat)
 
 
 class LSTM(HipLSTM):
@@ -196,6 +199,14 @@ class LSTM(HipLSTM):
     whole of its call contract: ``forward(x[B,T,I], hx=None) -> (output[B,T,H], (h_n[L,B,H], c_n[L,B,H]))``, hx =
     (h0, c0) or None (zeros); gradients reach x, h0, c0 and every parameter.  Parameter names, shapes and init are
     nn.LSTM's, so state_dicts load both ways.  ``compute_dtype`` as in HipLSTM.
+
+    Variable-length batches: ``forward(x, hx, lengths=...)`` with B ints (a sequence or a CPU int tensor, as
+    ``pack_padded_sequence`` takes them) gives what nn.LSTM gives on the packed batch, padded back to T: the output is
+    zero past each row's length, (h_n, c_n) are each row's state after its last step, and nothing in the padding is read
+    or receives a gradient.  A length of 0 (beyond torch) passes the row's state through.  ``x`` may also be a
+    ``PackedSequence``; the output is then a PackedSequence with the same batch_sizes and indices and (h_n, c_n) come
+    back in the original batch order, as from nn.LSTM.  The plan is still keyed by (B, T): lengths are per call, and the
+    work follows the longest row.
 
     Runs on CSN_LSTM_STATE plans (include/csn_hip.h): with bf16 compute the path HipLSTM takes for the shape (the
     weight-stationary kernels where they apply), with float32 the per-step cells (path 0).  With bf16 compute, h0 is rounded to bf16 as
@@ -215,7 +226,18 @@ class LSTM(HipLSTM):
         super().__init__(input_size, hidden_size, num_layers, compute_dtype=compute_dtype)
         self.bias, self.batch_first, self.dropout, self.bidirectional, self.proj_size = True, True, 0.0, False, 0
 
-    def forward(self, x, hx=None):
+    def forward(self, x, hx=None, lengths=None):
+        if isinstance(x, nn.utils.rnn.PackedSequence):
+            if lengths is not None:
+                raise ValueError("LSTM: lengths given together with a PackedSequence (it carries its own)")
+            padded, lens = nn.utils.rnn.pad_packed_sequence(x, batch_first=True)
+            output, state = self.forward(padded, hx, lengths=lens)
+            # pad_packed_sequence gave the rows in the original batch order: back into the input's own (sorted) order, so
+            # that the data lines up with its batch_sizes whatever order it gave to rows of equal length
+            if x.sorted_indices is not None:
+                output, lens = output.index_select(0, x.sorted_indices), lens[x.sorted_indices.cpu()]
+            packed = nn.utils.rnn.pack_padded_sequence(output, lens, batch_first=True, enforce_sorted=True)
+            return nn.utils.rnn.PackedSequence(packed.data, x.batch_sizes, x.sorted_indices, x.unsorted_indices), state
         if x.dim() != 3:
             raise ValueError(f"LSTM: input must be batched [B, T, {self.input_size}] (batch_first); got shape "
                              f"{list(x.shape)} (unbatched input is not supported)")
@@ -228,12 +250,26 @@ class LSTM(HipLSTM):
             for name, t in (("h0", h0), ("c0", c0)):
                 if tuple(t.shape) != (L, B, H):
                     raise ValueError(f"LSTM: {name} must be [num_layers, B, hidden_size] = {[L, B, H]}, got {list(t.shape)}")
+        if lengths is not None:
+            if isinstance(lengths, torch.Tensor):
+                if lengths.is_cuda:
+                    raise ValueError("LSTM: lengths must be a CPU int tensor or a sequence of ints (pass CPU lengths, as "
+                                     "pack_padded_sequence takes them)")
+                if lengths.dim() != 1 or lengths.dtype.is_floating_point or lengths.dtype in (torch.bool,):
+                    raise ValueError(f"LSTM: lengths must be a 1-d int tensor, got {lengths.dtype} of shape {list(lengths.shape)}")
+                lengths = lengths.tolist()
+            lengths = tuple(int(n) for n in lengths)
+            if len(lengths) != B:
+                raise ValueError(f"LSTM: {len(lengths)} lengths for a batch of {B}")
+            bad = [n for n in lengths if n < 0 or n > x.shape[1]]
+            if bad:
+                raise ValueError(f"LSTM: length {bad[0]} outside [0, T = {x.shape[1]}]")
         if not x.is_cuda:
             raise cabi.CsnError("LSTM runs on the GPU only (no CPU fallback); move the module and input to cuda")
         params = [getattr(self, f"{n}_l{k}") for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh") for k in range(L)]
         training = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params) or
                                                 any(t is not None and t.requires_grad for t in (h0, c0)))
-        y_all, h_n, c_n = _LstmStateFunction.apply(x, h0, c0, self, training, L, *params)
+        y_all, h_n, c_n = _LstmStateFunction.apply(x, h0, c0, self, training, lengths, L, *params)
         return y_all, (h_n, c_n)
 
 

@@ -36,7 +36,7 @@ enum csnStatus {
 enum csnDtype { CSN_F32 = 0, CSN_BF16 = 1 };
 
 /* ABI version of this header; bumped on any signature change.  A symbol added beside the existing ones
- * (csn_lstm_plan_set_grad_mode) breaks no caller and does not bump it. */
+ * (csn_lstm_plan_set_grad_mode, csn_lstm_plan_set_lengths) breaks no caller and does not bump it. */
 #define CSN_ABI_VERSION 6
 int csn_abi_version(void);
 /* Thread-local message for the last non-zero status returned on this thread. */
@@ -198,6 +198,25 @@ int csn_lstm_plan_set_grad_callback(csnLstmPlan* plan, csnGradReadyFn fn, void* 
 #define CSN_GRAD_OVERWRITE  0
 #define CSN_GRAD_ACCUMULATE 1
 int csn_lstm_plan_set_grad_mode(csnLstmPlan* plan, int mode);
+
+/* Variable-length batches: per-row numbers of valid steps.  `lengths` is a HOST array of B
+ * entries, each in [0, T]; NULL = every row is T (the default; such a plan runs exactly the kernels it ran before this
+ * symbol existed).  Sticky until set again, like the gradient mode.  Only on a CSN_LSTM_STATE plan.
+ * Semantics = nn.LSTM on pack_padded_sequence(enforce_sorted=False) + pad_packed_sequence(total_length=T).  For row b,
+ * n = lengths[b]:  y_all[b, t >= n] = 0;  h_n[l, b], c_n[l, b] = the state after step n-1 (CSN_BF16: the bf16 h every
+ * consumer saw);  y_last[b] = h_n[L-1, b];  nothing at t >= n enters any gradient: dx[b, t >= n] = 0, dy_all[b, t >= n]
+ * is ignored, dh_n[l, b] / dc_n[l, b] / dy_last[b] enter at step n-1.  n = 0 (beyond torch): the row passes through --
+ * h_n = h0 (bf16-rounded on CSN_BF16), c_n = c0, zero output, dh0 = dh_n, dc0 = dc_n, no parameter contribution; with
+ * every row 0 no recurrence kernel is launched.  x[b, t >= n] and dy_all[b, t >= n] are never read as data: whatever
+ * they hold (NaN, Inf), every result has the bits of the same call with zeros there.
+ * The recurrence and every GEMM behind it cover max(lengths) steps, not T.
+ * Contract: a forward uses the lengths the plan holds when it is called and uploads them to the device in stream order
+ * (into a [B] array the plan owns: a state plan's workspace stays laid out as a plain plan's); the matching backward must
+ * be called with the same lengths set, and uploads them again (a wrapper that shares plans between calls keeps them with
+ * the forward's autograd node and sets them again before the backward).  Calls of one plan that carry lengths are
+ * ordered on one stream, or by the caller.
+ * Null plan, a plan without CSN_LSTM_STATE, an entry outside [0, T]: CSN_ERR_INVALID_ARGUMENT (the setting is kept). */
+int csn_lstm_plan_set_lengths(csnLstmPlan* plan, const int32_t* lengths);
 
 /* The workspace's status word: 0 = ok.  Bit CSN_STATUS_TIMEOUT: a bounded in-kernel wait of a weight-stationary
  * kernel gave up at some point since the word was last cleared (the results of that forward / backward and of every
