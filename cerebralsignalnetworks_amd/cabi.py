@@ -43,6 +43,7 @@ SIGNATURES = {
     "csn_lstm_plan_workspace_bytes": (_c_size_t, [_c_void_p]),
     "csn_lstm_plan_path": (_c_int, [_c_void_p]),
     "csn_lstm_plan_dgates_copies": (_c_int, [_c_void_p]),
+    "csn_lstm_plan_half_tile_launches": (_c_int, [_c_void_p, _c_int]),
     "csn_lstm_plan_kernel_name": (ctypes.c_char_p, [_c_void_p, _c_int]),
     "csn_lstm_plan_set_grad_callback": (_c_int, [_c_void_p, _c_void_p, _c_void_p]),
     "csn_lstm_plan_set_grad_mode": (_c_int, [_c_void_p, _c_int]),
@@ -310,6 +311,11 @@ class LstmPlan:
     def dgates_copies(self):
         """Copies of the gate gradients the last backward wrote per step (csn_hip.h): 2, or 0 before any backward."""
         return load().csn_lstm_plan_dgates_copies(self._plan)
+
+    def half_tile_launches(self, which):
+        """Recurrence launches of the last forward (which = 0) / backward (which = 1) that ran on 32-row hand-off groups
+        (csn_hip.h); 0 under CSN_NO_HALF_TILES=1."""
+        return load().csn_lstm_plan_half_tile_launches(self._plan, which)
 
     def forward(self, x_bti, w_ih, w_hh, b_ih, b_hh, want_all=False, h0=None, c0=None, want_state=False):
         """-> (y_last, y_all); with want_state=True -> (y_last, y_all, h_n, c_n).  h0 / c0: [L,B,H] initial state or

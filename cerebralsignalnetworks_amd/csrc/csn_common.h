@@ -48,7 +48,7 @@ int fail(int status, const char* fmt, ...);
 // library keeps no mutable global state, so plans on different streams / threads / devices never share any.
 struct Options {
   bool cell_v1, no_persist, no_persist_bwd, persist_streams, no_xcd_local, no_rotate, no_fuse_x, no_beside,
-      no_side_stream, gemm_slot, fwd_ksplit, fwd_nsplit, fwd_flags, bwd_flags, dpoll_no_hint, fwd_hint, gemm_no_dma, gemm_no_256, gemm_generic, gemm_lds64, tn_no_tr, tn_no_stagger, filter_v1, tags_no_rearm, gemm_no_192;
+      no_side_stream, gemm_slot, fwd_ksplit, fwd_nsplit, fwd_flags, bwd_flags, dpoll_no_hint, fwd_hint, gemm_no_dma, gemm_no_256, gemm_generic, gemm_lds64, tn_no_tr, tn_no_stagger, filter_v1, tags_no_rearm, gemm_no_192, no_half_tiles;
   int chunk;       // timesteps per weight-stationary launch
   int tn_stages;   // LDS-DMA ring depth of the 256 x 256 weight-gradient kernel
   int fwd_nk;
@@ -68,6 +68,7 @@ static inline Options options_from_env() {
   o.no_rotate = on("CSN_NO_ROTATE");
   o.no_fuse_x = on("CSN_NO_FUSE_X");
   o.no_beside = on("CSN_NO_BESIDE");
+  o.no_half_tiles = on("CSN_NO_HALF_TILES");
   o.no_side_stream = on("CSN_NO_SIDE_STREAM");
   o.gemm_slot = on("CSN_GEMM_SLOT");
   o.fwd_ksplit = on("CSN_FWD_KSPLIT");

@@ -146,8 +146,8 @@ static WsLayout make_layout(const csnLstmDesc& d, int training, const Options& o
   }
   if (w.persist) {
     w.zero_fwd = off;
-    // (x 4: room for four flag lines per (slot, M-tile), which the forward kernels of this library do not use; kept so
-    // that the layout of everything behind it stays where it was)
+    // (x 4: room for four flag lines per (slot, M-tile): the first holds the lines of the 64-row tiles, the next two
+    // those of the 32-row tiles of launches with few groups, twice as many; the last is unused)
     for (int l = 0; l < d.L; ++l) w.layer[l].counters = take(((size_t)d.T + 1) * (Bpad / 64) * 4 * kPersistFlagLine * 4);
     w.agree = take(((size_t)d.T + 8) * 8 * sizeof(unsigned long long));   // 8 words per launch
     w.zero_fwd_bytes = off - w.zero_fwd;
@@ -156,7 +156,8 @@ static WsLayout make_layout(const csnLstmDesc& d, int training, const Options& o
     w.zero_bwd = off;
     for (int l = 0; l < d.L; ++l) {
       w.layer[l].dc_carry = take((size_t)d.B * H * 4);
-      w.layer[l].bflags = take((size_t)d.T * (Bpad / 64) * kPersistFlagLine * 4);
+      // (x 3: the lines of the 64-row tiles, then those of the 32-row tiles of launches with few groups -- twice as many)
+      w.layer[l].bflags = take((size_t)d.T * (Bpad / 64) * 3 * kPersistFlagLine * 4);
     }
     w.agree_b = take(((size_t)d.T + 8) * 8 * sizeof(unsigned long long));
     w.zero_bwd_bytes = off - w.zero_bwd;
@@ -438,6 +439,7 @@ struct csnLstmPlan {
   csn::SideCtx sc;
   csn::Prof prof;
   int dgates_copies = 0;      // what the last backward wrote per step (csn_lstm_plan_dgates_copies)
+  int half_launches[2] = {0, 0};   // recurrence launches of the last forward / backward on 32-row groups (csn_lstm_plan_half_tile_launches)
   csnGradReadyFn grad_cb = nullptr;      // csn_lstm_plan_set_grad_callback
   void* grad_cb_user = nullptr;
   int grad_accumulate = 0;               // csn_lstm_plan_set_grad_mode: dw / db are added to, not overwritten
@@ -515,6 +517,10 @@ extern "C" int csn_lstm_plan_path(const csnLstmPlan* P) {
 }
 
 extern "C" int csn_lstm_plan_dgates_copies(const csnLstmPlan* P) { return P == nullptr ? -1 : P->dgates_copies; }
+
+extern "C" int csn_lstm_plan_half_tile_launches(const csnLstmPlan* P, int which) {
+  return (P == nullptr || which < 0 || which > 1) ? -1 : P->half_launches[which];
+}
 
 // does the backward of this plan take the grouped weight-stationary form (backward_il's dispatch)?
 static bool bwd_grouped(const csnLstmPlan* P) {
@@ -1251,6 +1257,7 @@ static int forward_persist(Plan& P, char* ws, const float* h0, const float* c0, 
       CSN_HIP_CHECK(hipMemsetAsync(ws + L.c_all, 0, (size_t)B * H * 4, st));
   }
   int n_launch = 0;
+  P.half_launches[0] = 0;
 
   const int max_slots = NL < nch ? NL : nch;
   const int fwd_slices = w.fwd_ns ? fwd_ns_slices(H) : fwd_persist_slices(H);
@@ -1275,6 +1282,15 @@ static int forward_persist(Plan& P, char* ws, const float* h0, const float* c0, 
       }
       a.nslots = ns;
       a.xcd_groups = 1;
+      // few groups (the wavefront's fill and drain, small batches): 32-row groups, twice as many, so that the launch
+      // spreads over all eight XCDs and every step of its chain handles half the rows (K-split kernel only)
+      const bool half = !w.fwd_ns && !P.opt.no_half_tiles && 2 * ns * MT <= 8;
+      a.half_tiles = half ? 1 : 0;
+      a.MT = half ? 2 * MT : MT;
+      if (half) {
+        for (int i = 0; i < ns; ++i) a.slot[i].flags += ((size_t)T + 1) * MT * kPersistFlagLine;
+        ++P.half_launches[0];
+      }
       a.agree = try_local ? (unsigned long long*)(ws + w.agree) + (size_t)dg * 8 : nullptr;
       if ((rc = prof_pair(g_prof, 0, false, st))) return rc;
       if ((rc = launch_fwd(a, st))) return rc;
@@ -1305,6 +1321,8 @@ static int forward_persist(Plan& P, char* ws, const float* h0, const float* c0, 
   a.nslots = 1;
   a.xcd_groups = 0;
   a.agree = nullptr;
+  a.half_tiles = 0;
+  a.MT = MT;
   for (int c = 0; c < nch; ++c) {
     for (int l = 0; l < NL; ++l) {
       fill_slot(a.slot[0], l, c);
@@ -1562,6 +1580,7 @@ static int backward_persist(Plan& P, char* ws, const float* dy_last, const float
   if (a.data_polls)        // the ring of 4 hand-off slabs of every layer starts as sentinel
     for (int l = 0; l < NL; ++l) CSN_HIP_CHECK(hipMemsetAsync(ws + w.layer[l].dg_blk_all, 0xff, (size_t)4 * Bpad * G * 2, st));
   int n_launch = 0;
+  P.half_launches[1] = 0;
   BesideGemm pending[3];           // GEMMs of the chunks finished by the previous launch
   DhAdd pending_add[3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};  // dh_n term that follows pending[i] (layer 0: none)
   int npending = 0;
@@ -1607,6 +1626,15 @@ static int backward_persist(Plan& P, char* ws, const float* dy_last, const float
     }
     a.nslots = ns;
     a.ngemm = npending;
+    // few groups: 32-row groups, twice as many (forward_persist).  The grid and the GEMM workers stay what they are --
+    // 8 groups of 24 slices leave the same 8 x 8 workgroups for the tiles.  A batch with lengths stays on 64 rows.
+    const bool half = !P.opt.no_half_tiles && P.dlen == nullptr && 2 * ns * MT <= 8;
+    a.half_tiles = half ? 1 : 0;
+    a.MT = half ? 2 * MT : MT;
+    if (half) {
+      for (int i = 0; i < ns; ++i) a.slot[i].flags += (size_t)T * MT * kPersistFlagLine;
+      ++P.half_launches[1];
+    }
     DhAdd launch_adds[3];
     int nadds = 0;
     for (int i = 0; i < npending; ++i) {

@@ -4,10 +4,10 @@
 //
 // Per step and layer:  dh_t = dgates_{t+1} W_hh + dy_t,  then the gate derivatives dgates_t [B, 4H] from dh_t,
 // the carried dc and the saved forward tensors.  In the per-diagonal launches of lstm_cell_blk.hip every
-// workgroup re-reads its W_hh^T slice (295 KB) every step; here a workgroup owns a (64 rows x 16*NUT units)
-// tile for a whole chunk, keeps its W_hh^T slice in registers (each wave: its quarter of K' = 4H for all
+// workgroup re-reads its W_hh^T slice (295 KB) every step; here a workgroup owns a (16*RG rows x 16*NUT units)
+// tile for a whole chunk (RG = 4 row groups: 64 rows; RG = 2: the 32-row groups of launches with few groups, see below), keeps its W_hh^T slice in registers (each wave: its quarter of K' = 4H for all
 // 16*NUT units = KS*NUT fragments, 192 VGPRs at H = 768) and the carried dc in registers, and per step
-// streams only the 64 rows of dgates_{t+1} (a ring of RING k-blocks in flight per wave).
+// streams only the tile's rows of dgates_{t+1} (a ring of RING k-blocks in flight per wave).
 //
 // The step-to-step hand-off of dgates between the workgroups of a group (one layer's 64-row M-tile) is the
 // one of lstm_fwd_persist.hip, both forms (L2-local per XCD group, verified at run time; placement-
@@ -16,6 +16,11 @@
 // wave's vector-memory pipe ahead of its polls (the saved tensors of step t-1 are requested behind the
 // MFMAs of step t).  All workgroups of a launch must be co-resident (1 per CU); every spin is bounded and
 // raises the sticky error flag instead of hanging.
+//
+// Tile height (RG): a launch whose groups would fill only half of the XCDs (one layer in range at B = 256) runs on
+// 32-row groups instead, 2 MT tiles per layer -- MFMA issue, the reduction and the epilogue's store issue of a step
+// all halve.  A row's arithmetic does not depend on the rows beside it, a workgroup writes and re-arms exactly the
+// (row, unit) pieces it owns at either height, and the height changes only between launches: same bits, same ring.
 #include "csn_common.h"
 #include "lstm_cell_common.h"
 #include "lstm_cell_blk.h"
@@ -77,18 +82,19 @@ struct PersistNoLens {};
 template <bool MASK> struct PersistLensArg { typedef PersistNoLens type; };
 template <> struct PersistLensArg<true> { typedef PersistLens type; };
 
-template <int NUT, int KS, bool DPOLL, bool MASK = false>
+template <int NUT, int KS, bool DPOLL, bool MASK = false, int RG = 4>
 __global__ void __launch_bounds__(256) lstm_bwd_persist_kernel(PersistBwdArgs a, typename PersistLensArg<MASK>::type lens) {
 #ifndef CSN_BWD_RING
 #define CSN_BWD_RING 5
 #endif
   constexpr int RING = KS >= 32 ? 3 : (KS < CSN_BWD_RING ? KS : CSN_BWD_RING);   // k-blocks of dgates in flight per wave (3 at H = 1024: register budget)
-  constexpr int NT = 4 * NUT;                    // accumulator tiles per wave (4 row groups x NUT unit tiles)
+  static_assert(RG == 4 || RG == 2, "tiles of 64 or 32 rows");
+  constexpr int NT = RG * NUT;                   // accumulator tiles per wave (RG row groups x NUT unit tiles)
   constexpr int QPR = 4 * NUT;                   // unit quads per row of the tile
-  constexpr int NPAIR = 64 * QPR;                // (row, unit-quad) pairs
+  constexpr int NPAIR = 16 * RG * QPR;           // (row, unit-quad) pairs
   constexpr int NPASS = NPAIR / 256;
   static_assert(NPAIR % 256 == 0, "tile must split evenly over the 256 threads");
-  extern __shared__ __attribute__((aligned(16))) float4 red[];   // [4][NT][kBwdRedTile]
+  extern __shared__ __attribute__((aligned(16))) float4 red[];   // [4 waves][NT][kBwdRedTile]
   const int B = a.B, H = a.H, MT = a.MT, T = a.T;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 #ifdef CSN_PSTAMPS
@@ -119,7 +125,7 @@ __global__ void __launch_bounds__(256) lstm_bwd_persist_kernel(PersistBwdArgs a,
   }
   const PersistBwdSlot& S = a.slot[grp / MT];
   const int mt = grp % MT;
-  const int u0 = slice * 16 * NUT, m0 = mt * 64;
+  const int u0 = slice * 16 * NUT, m0 = mt * 16 * RG;
   const int K = 4 * H, kblocks = K >> 5;
   const int ks_beg = wave * KS;                         // KS = kblocks / 4 k-blocks per wave
   const size_t slab = (size_t)a.Bpad * K;               // elements of one fragment-major dgates slab
@@ -261,9 +267,9 @@ __global__ void __launch_bounds__(256) lstm_bwd_persist_kernel(PersistBwdArgs a,
       dyv[ps] = dy_n[ps];
     }
 
-    f32x4 acc[4][NUT];
+    f32x4 acc[RG][NUT];
 #pragma unroll
-    for (int rg = 0; rg < 4; ++rg)
+    for (int rg = 0; rg < RG; ++rg)
 #pragma unroll
       for (int ut = 0; ut < NUT; ++ut) acc[rg][ut] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
@@ -288,7 +294,9 @@ __global__ void __launch_bounds__(256) lstm_bwd_persist_kernel(PersistBwdArgs a,
         const unsigned not_yet = dpoll ? 0xffffffffu : 0u;
         const unsigned long long t_begin = wall_clock64();
         // (data_polls == 2, a test switch: no hint, load straight away -- every step then goes through the re-read path)
-        while (!(dpoll && CSN_DPOLL_MODE(a.data_polls) == 2) && !__all(__hip_atomic_load(fl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != not_yet)) {
+        // (flags: the first step of a launch reads what an EARLIER launch published -- a kernel boundary, no wait; the
+        // flag lines of the two tile heights are separate, so a launch never polls a line of the other height)
+        while (!(dpoll && CSN_DPOLL_MODE(a.data_polls) == 2) && (dpoll || s > 0) && !__all(__hip_atomic_load(fl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != not_yet)) {
           __builtin_amdgcn_s_sleep(1);
           if (__hip_atomic_load(a.error_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) break;
           if (wall_clock64() - t_begin > kBwdSpinTimeoutTicks) {
@@ -319,16 +327,16 @@ __global__ void __launch_bounds__(256) lstm_bwd_persist_kernel(PersistBwdArgs a,
         if (again) {
           __builtin_amdgcn_s_sleep(1);
 #pragma unroll
-          for (int rg = 0; rg < 4; ++rg)
+          for (int rg = 0; rg < RG; ++rg)
 #pragma unroll
             for (int ut = 0; ut < NUT; ++ut) acc[rg][ut] = (f32x4){0.f, 0.f, 0.f, 0.f};
         }
-        bf16x8 df[RING][4];
+        bf16x8 df[RING][RG];
         // (the rotated k-block walk as ONE running scalar offset: k-block (i + rot) % KS of the i-th group issued)
         int kbo = rot_t * 1024;
         auto issue_group = [&](int slot) {
 #pragma unroll
-          for (int rg = 0; rg < 4; ++rg)
+          for (int rg = 0; rg < RG; ++rg)
             df[slot][rg] = bload_sc1_b128(slabs_rsrc, base + (unsigned)(rg * kblocks) * 1024u, src_off + kbo);
           kbo = kbo + 1024 == KS * 1024 ? 0 : kbo + 1024;
         };
@@ -350,7 +358,7 @@ __global__ void __launch_bounds__(256) lstm_bwd_persist_kernel(PersistBwdArgs a,
           if constexpr (dpoll) {
             const unsigned want = (unsigned)(((t + 1) >> 2) & 1);
 #pragma unroll
-            for (int rg = 0; rg < 4; ++rg) {
+            for (int rg = 0; rg < RG; ++rg) {
               const u32x4 u = __builtin_bit_cast(u32x4, df[kb % RING][rg]);
               const bool bad = u[0] != 0xffffffffu && (u[0] & 1u) != want;
 #ifdef CSN_SLAB_TAGS_DUMP
@@ -361,7 +369,7 @@ __global__ void __launch_bounds__(256) lstm_bwd_persist_kernel(PersistBwdArgs a,
           }
 #endif
 #pragma unroll
-          for (int rg = 0; rg < 4; ++rg)
+          for (int rg = 0; rg < RG; ++rg)
 #pragma unroll
             for (int ut = 0; ut < NUT; ++ut)   // D[row = unit][col = batch row]
               acc[rg][ut] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wreg[kb][ut], df[kb % RING][rg], acc[rg][ut], 0, 0, 0);
@@ -391,7 +399,7 @@ __global__ void __launch_bounds__(256) lstm_bwd_persist_kernel(PersistBwdArgs a,
           // poisoned every accumulator element of its batch row -- one sum over the 32 accumulator registers finds it
           float chk = 0.f;
 #pragma unroll
-          for (int rg = 0; rg < 4; ++rg)
+          for (int rg = 0; rg < RG; ++rg)
 #pragma unroll
             for (int ut = 0; ut < NUT; ++ut) chk += (acc[rg][ut][0] + acc[rg][ut][1]) + (acc[rg][ut][2] + acc[rg][ut][3]);
           if (__builtin_expect(!__all(chk == chk), 0)) {
@@ -412,7 +420,7 @@ __global__ void __launch_bounds__(256) lstm_bwd_persist_kernel(PersistBwdArgs a,
 #pragma unroll 1
                 for (int kb = 0; kb < KS; ++kb) {
 #pragma unroll
-                  for (int rg = 0; rg < 4; ++rg) {
+                  for (int rg = 0; rg < RG; ++rg) {
                     const u32x4 u = __builtin_bit_cast(u32x4, bload_sc1_b128(slabs_rsrc, base + (unsigned)(rg * kblocks) * 1024u, src_off + kbo2));
                     sentinel |= (u[0] == 0xffffffffu) | (u[3] == 0xffffffffu);
                   }
@@ -437,7 +445,7 @@ __global__ void __launch_bounds__(256) lstm_bwd_persist_kernel(PersistBwdArgs a,
 
     // lane holds batch row (lane & 15) of row group rg, units 16 ut + (lane >> 4) * 4 + r
 #pragma unroll
-    for (int rg = 0; rg < 4; ++rg)
+    for (int rg = 0; rg < RG; ++rg)
 #pragma unroll
       for (int ut = 0; ut < NUT; ++ut)
         red[(wave * NT + rg * NUT + ut) * kBwdRedTile + bwd_red_pos(lane & 15, lane >> 4)] = make_float4(acc[rg][ut][0], acc[rg][ut][1], acc[rg][ut][2], acc[rg][ut][3]);
@@ -563,12 +571,18 @@ bool bwd_persist_supported(int B, int H, int dtype, const Options& opt) {
 }
 int bwd_persist_slices(int H) { return H / 32; }
 
+// 32-row groups (a.half_tiles): every instantiation holds W_hh^T in more than 256 registers (KS * NUT fragments plus the
+// ring), so a SIMD takes one wave and a CU one workgroup whatever the LDS request.  The masked kernel has no 32-row
+// instantiation: plans with lengths stay on 64 rows (the host never asks).
 template <int NUT, int KS>
 static int launch_bwd_persist_t(const PersistBwdArgs& a, hipStream_t st, const int* lengths) {
-  size_t lds = (size_t)4 * 4 * NUT * kBwdRedTile * sizeof(float4);
+  size_t lds = (size_t)4 * (a.half_tiles ? 2 : 4) * NUT * kBwdRedTile * sizeof(float4);
   if (lengths != nullptr) {
     if (int rc = ensure_dyn_lds<&lstm_bwd_persist_kernel<NUT, KS, false, true>>((int)kBesideLdsBytes)) return rc;
     if (int rc = ensure_dyn_lds<&lstm_bwd_persist_kernel<NUT, KS, true, true>>((int)kBesideLdsBytes)) return rc;
+  } else if (a.half_tiles) {
+    if (int rc = ensure_dyn_lds<&lstm_bwd_persist_kernel<NUT, KS, false, false, 2>>((int)kBesideLdsBytes)) return rc;
+    if (int rc = ensure_dyn_lds<&lstm_bwd_persist_kernel<NUT, KS, true, false, 2>>((int)kBesideLdsBytes)) return rc;
   } else {
     if (int rc = ensure_dyn_lds<&lstm_bwd_persist_kernel<NUT, KS, false>>((int)kBesideLdsBytes)) return rc;
     if (int rc = ensure_dyn_lds<&lstm_bwd_persist_kernel<NUT, KS, true>>((int)kBesideLdsBytes)) return rc;
@@ -588,6 +602,9 @@ static int launch_bwd_persist_t(const PersistBwdArgs& a, hipStream_t st, const i
     const PersistLens pl{lengths};
     if (b.data_polls) lstm_bwd_persist_kernel<NUT, KS, true, true><<<dim3(grid), 256, lds, st>>>(b, pl);
     else lstm_bwd_persist_kernel<NUT, KS, false, true><<<dim3(grid), 256, lds, st>>>(b, pl);
+  } else if (b.half_tiles) {
+    if (b.data_polls) lstm_bwd_persist_kernel<NUT, KS, true, false, 2><<<dim3(grid), 256, lds, st>>>(b, PersistNoLens{});
+    else lstm_bwd_persist_kernel<NUT, KS, false, false, 2><<<dim3(grid), 256, lds, st>>>(b, PersistNoLens{});
   } else if (b.data_polls) lstm_bwd_persist_kernel<NUT, KS, true><<<dim3(grid), 256, lds, st>>>(b, PersistNoLens{});
   else lstm_bwd_persist_kernel<NUT, KS, false><<<dim3(grid), 256, lds, st>>>(b, PersistNoLens{});
   CSN_LAUNCH_CHECK();
@@ -599,6 +616,9 @@ int launch_bwd_persist(const PersistBwdArgs& a, hipStream_t st, const int* lengt
   const int ns = bwd_persist_slices(a.H);
   CSN_REQUIRE(ns % 4 == 0 && ns <= kPersistFlagLine, "launch_bwd_persist: H=%d gives %d slices", a.H, ns);
   if (a.xcd_groups) CSN_REQUIRE(a.nslots * a.MT <= 8, "launch_bwd_persist: groups do not fit 8 XCDs");
+  CSN_REQUIRE(a.MT * (a.half_tiles ? 32 : 64) == a.Bpad, "launch_bwd_persist: %d tiles of %d rows are not Bpad=%d", a.MT,
+              a.half_tiles ? 32 : 64, a.Bpad);
+  CSN_REQUIRE(!a.half_tiles || (a.xcd_groups && lengths == nullptr), "launch_bwd_persist: 32-row groups need the grouped form and no lengths");
   CSN_REQUIRE(a.ngemm >= 0 && a.ngemm <= 3 && (a.ngemm == 0 || a.xcd_groups), "launch_bwd_persist: bad GEMM list");
   for (int i = 0; i < a.ngemm; ++i)
     CSN_REQUIRE(a.gemm[i].K % 64 == 0 && a.gemm[i].N % 4 == 0 && a.gemm[i].M > 0, "launch_bwd_persist: GEMM %d shape", i);

@@ -89,6 +89,10 @@ struct PersistFwdArgs {
   // != 0: an initial state (CSN_LSTM_STATE): step 0 multiplies h_{-1} = h0 from hand-off slot 0 (written by an earlier
   // kernel on the stream: read without a wait) and starts from c_all slot 0; 0: step 0 has no recurrent term, c = 0
   int state;
+  // != 0: hand-off groups of 32 rows (MT = Bpad / 32) instead of 64; K-split kernel, grouped form only.  A workgroup
+  // writes and re-arms exactly the (row, unit) pieces it owns at either height, so launches of both heights follow each
+  // other on the same ring of slabs; the flag lines of the two heights are separate (slot.flags is the height's own)
+  int half_tiles;
 };
 bool fwd_persist_supported(int B, int H, int dtype, const Options& opt);
 // N-split weight-stationary forward (lstm_fwd_ns.hip): the default where it applies
@@ -110,7 +114,7 @@ struct PersistBwdSlot {
   float* dc_carry;         // [B, H] carried dc, in/out across launches
   bf16_t* dgates;          // [T, B, 4H] interleaved, row-major (GEMM operand)
   bf16_t* dg_blk_all;      // [T][Bpad * 4H] fragment-major slabs (slot t = dgates_t); never reused in a backward
-  unsigned* flags;         // [T][MT][kPersistFlagLine], zeroed per backward
+  unsigned* flags;         // [T][MT][kPersistFlagLine], zeroed per backward (MT = tiles of the launch's height; the two heights use lines of their own)
   int t_hi, nsteps;        // steps t_hi, t_hi - 1, ..., t_hi - nsteps + 1
 };
 struct PersistBwdArgs {
@@ -124,7 +128,8 @@ struct PersistBwdArgs {
   int data_polls;          // hand-off by sentinel data in a ring of 4 slabs (the host fills them with 0xff per backward)
   unsigned long long* agree;
   unsigned* error_flag;
-  int B, H, T, Bpad, MT;
+  int B, H, T, Bpad, MT;   // MT: M-tiles per layer at the launch's tile height
+  int half_tiles;          // != 0: hand-off groups of 32 rows (MT = Bpad / 32), else 64 (MT = Bpad / 64); grouped form only
 };
 bool bwd_persist_supported(int B, int H, int dtype, const Options& opt);
 int bwd_persist_slices(int H);

@@ -557,6 +557,7 @@ int fwd_ns_slices(int H) { return H / 32; }
 
 int launch_fwd_ns(const PersistFwdArgs& a, hipStream_t st) {
   CSN_REQUIRE(a.nslots >= 1 && a.nslots <= 4 && a.MT >= 1, "launch_fwd_ns: bad slot count");
+  CSN_REQUIRE(!a.half_tiles, "launch_fwd_ns: the N-split kernel has no 32-row groups");
   const int ns = fwd_ns_slices(a.H);
   CSN_REQUIRE(ns <= kPersistFlagLine, "launch_fwd_ns: H=%d gives %d slices", a.H, ns);
   if (a.xcd_groups) CSN_REQUIRE(a.nslots * a.MT <= 8, "launch_fwd_ns: groups do not fit 8 XCDs");

@@ -8,7 +8,8 @@
 // H = 768) and its cell state c in registers, and per step only streams its 64 rows of h_{t-1}.
 //
 // One launch advances up to 4 layers, each through its own chunk (a wavefront diagonal over chunks).  A
-// hand-off GROUP is one layer's M-tile (64 batch rows): its nslices workgroups exchange h every step,
+// hand-off GROUP is one layer's M-tile (64 batch rows; 32 in launches whose 64-row groups would leave half of
+// the XCDs without one -- template parameter RG, 16-row row groups per tile -- see lstm_bwd_persist.hip): its nslices workgroups exchange h every step,
 // different groups never talk.  Two hand-off forms, same kernel, bit-identical results:
 //
 //  * L2-local (grouped launch, xcd_groups != 0): group = blockIdx.x % 8.  The hardware deals consecutive
@@ -150,19 +151,21 @@ __device__ __forceinline__ T bounded_poll(const T* p, unsigned* error_flag, Pred
 #ifndef CSN_FWD_RING
 #define CSN_FWD_RING 4
 #endif
-template <int NQ, int KS, bool DPOLL>
+template <int NQ, int KS, bool DPOLL, int RG = 4>
 __global__ void __launch_bounds__(256) lstm_fwd_persist_kernel(PersistFwdArgs a) {
-  constexpr int NT = 4 * NQ;
-  constexpr int NPAIR = 64 * NQ;
+  static_assert(RG == 4 || RG == 2, "tiles of 64 or 32 rows");
+  constexpr int NT = RG * NQ;
+  constexpr int NPAIR = 16 * RG * NQ;
   constexpr int NPASS = (NPAIR + 255) / 256;
   // The epilogue's work items are (row, unit-quad) pairs, one per thread and pass.  At NQ = 6 there are 384 of them: a full
   // pass and 128 left over -- as a second pass of whole pairs those kept waves 0 and 1 busy for a full pass while waves 2
   // and 3 waited at the barrier (an ablation without them: 212 -> 185 us per launch).  HALFQ: the 128 quads of that last
   // pass are split into unit PAIRS over all 256 threads (thread t: quad 256 NFULL + t / 2, units 2 (t & 1), +1), so every
   // wave runs half a pass; the two lanes of a quad meet through a DPP swap for the one 8-byte hand-off piece.
+  // (32-row tiles: NPAIR = 192 at NQ = 6 -- one pass of whole pairs on three waves -- and 256 at NQ = 8)
   constexpr bool HALFQ = (NPAIR % 256) == 128;
   constexpr int NFULL = NPAIR / 256;
-  extern __shared__ __attribute__((aligned(16))) float4 red[];   // [4][NT][kRedTile], then [NQ][4] bias
+  extern __shared__ __attribute__((aligned(16))) float4 red[];   // [4 waves][NT][kRedTile], then [NQ][4] bias
   const int B = a.B, H = a.H, MT = a.MT;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 #ifdef CSN_PSTAMPS
@@ -186,7 +189,7 @@ __global__ void __launch_bounds__(256) lstm_fwd_persist_kernel(PersistFwdArgs a)
   }
   const PersistFwdSlot& S = a.slot[grp / MT];
   const int mt = grp % MT;
-  const int u0 = slice * 4 * NQ, m0 = mt * 64;
+  const int u0 = slice * 4 * NQ, m0 = mt * 16 * RG;
   const int kblocks = H >> 5;
   const int ks_beg = wave * KS;                        // KS = kblocks / 4 k-steps per wave
   const size_t slab = (size_t)a.Bpad * H;              // elements of one fragment-major h slab
@@ -302,7 +305,7 @@ __global__ void __launch_bounds__(256) lstm_fwd_persist_kernel(PersistFwdArgs a)
     if (fused) {
       if (xwave) {
 #pragma unroll
-        for (int rg = 0; rg < 4; ++rg)
+        for (int rg = 0; rg < RG; ++rg)
           nxt[rg] = nt_load(reinterpret_cast<const f32x4*>(x_blk + (size_t)t * xslab + ((size_t)((m0 >> 4) + rg) * xkb + wave) * 512 + lane * 8));
       }
       return;
@@ -327,10 +330,10 @@ __global__ void __launch_bounds__(256) lstm_fwd_persist_kernel(PersistFwdArgs a)
     // this step's input projection (or input) was requested a step ago (below, behind the MFMAs): nothing may sit
     // in the vector-memory queue ahead of the flag polls and the h loads -- results return in issue order, so a
     // queued HBM read would add its latency to every hand-off (measured: wait 2.5 -> 0.5 us per step)
-    bf16x8 xf[4];
+    bf16x8 xf[RG];
     if (fused) {
 #pragma unroll
-      for (int rg = 0; rg < 4; ++rg) xf[rg] = __builtin_bit_cast(bf16x8, nxt[rg]);
+      for (int rg = 0; rg < RG; ++rg) xf[rg] = __builtin_bit_cast(bf16x8, nxt[rg]);
     } else {
 #pragma unroll
       for (int i = 0; i < 8; ++i) cur[i] = nxt[i];
@@ -340,9 +343,9 @@ __global__ void __launch_bounds__(256) lstm_fwd_persist_kernel(PersistFwdArgs a)
     const size_t slot_in = dpoll ? (size_t)(t & 3) : (size_t)t;
     const size_t slot_out = dpoll ? (size_t)((t + 1) & 3) : (size_t)(t + 1);
 
-    f32x4 acc[4][NQ];
+    f32x4 acc[RG][NQ];
 #pragma unroll
-    for (int rg = 0; rg < 4; ++rg)
+    for (int rg = 0; rg < RG; ++rg)
 #pragma unroll
       for (int j = 0; j < NQ; ++j) acc[rg][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
     if (fused && wave == 0) {                 // one wave's partial sum starts from the bias
@@ -350,7 +353,7 @@ __global__ void __launch_bounds__(256) lstm_fwd_persist_kernel(PersistFwdArgs a)
       for (int j = 0; j < NQ; ++j) {
         const float4 bz = reinterpret_cast<const float4*>(bias_lds)[j * 4 + (lane >> 4)];
 #pragma unroll
-        for (int rg = 0; rg < 4; ++rg) acc[rg][j] = (f32x4){bz.x, bz.y, bz.z, bz.w};
+        for (int rg = 0; rg < RG; ++rg) acc[rg][j] = (f32x4){bz.x, bz.y, bz.z, bz.w};
       }
     }
 
@@ -360,7 +363,9 @@ __global__ void __launch_bounds__(256) lstm_fwd_persist_kernel(PersistFwdArgs a)
       // line, lane i the flag of its i-th producer (sc1 loads: L1 bypassed, L2-served), and then loads --
       // no workgroup barrier, the polling wave is the loading wave.  (t = 0 with a state: h0 in slot 0 was written
       // before the launch -- no wait, and no check of the pieces: an h0 whose bf16 bits are the sentinel is data)
-      const bool wait = t > 0;
+      // (flags: the first step of a launch reads what an EARLIER launch published -- a kernel boundary, no wait; the
+      // flag lines of the two tile heights are separate, so a launch never polls a line of the other height)
+      const bool wait = t > 0 && (dpoll || s > 0);
       {
         const int npw = nslices >> 2;
         // flags: word i of the (t, M-tile) line.  Data polls: four words per producer, one from the LAST store
@@ -369,7 +374,7 @@ __global__ void __launch_bounds__(256) lstm_fwd_persist_kernel(PersistFwdArgs a)
         const unsigned* fl;
         if constexpr (dpoll) {
           const int pi = lane < 4 * npw ? lane >> 2 : 0, pw = lane & 3;
-          int pp = 64 * pw + 63;
+          int pp = 64 * pw + 63 < NPAIR ? 64 * pw + 63 : NPAIR - 1;      // (a wave without a pair: the last storing wave's)
 #pragma unroll
           for (int ps = 1; ps < NPASS; ++ps)
             if (64 * pw + 63 + ps * 256 < NPAIR) pp = 64 * pw + 63 + ps * 256;
@@ -402,7 +407,7 @@ __global__ void __launch_bounds__(256) lstm_fwd_persist_kernel(PersistFwdArgs a)
       // scratch use in these kernels (tools/check_spills.py).
       constexpr int RING_MAX = (NQ == 8 && KS == 4) ? 2 : ((NQ == 6 && KS == 6 && !DPOLL) ? 3 : CSN_FWD_RING);
       constexpr int RING = KS > RING_MAX ? RING_MAX : KS;
-      bf16x8 hf[RING][4];
+      bf16x8 hf[RING][RG];
       // (the rotated k-block walk as ONE running scalar offset: k-block (i + rot) % KS of the i-th group issued; as
       // per-load constants the compiler kept them in SGPRs across the steps)
       int rot_t = rot;
@@ -410,7 +415,7 @@ __global__ void __launch_bounds__(256) lstm_fwd_persist_kernel(PersistFwdArgs a)
       int kbo = rot_t * 1024;
       auto issue_group = [&](int slot) {
 #pragma unroll
-        for (int rg = 0; rg < 4; ++rg) hf[slot][rg] = load_sc1_b128(hsrc, base + rg * kblocks * 1024, kbo);
+        for (int rg = 0; rg < RG; ++rg) hf[slot][rg] = load_sc1_b128(hsrc, base + rg * kblocks * 1024, kbo);
         kbo = kbo + 1024 == KS * 1024 ? 0 : kbo + 1024;
       };
 #pragma unroll
@@ -426,7 +431,7 @@ __global__ void __launch_bounds__(256) lstm_fwd_persist_kernel(PersistFwdArgs a)
           auto whole = [&]() {
             bool ok = true;
 #pragma unroll
-            for (int rg = 0; rg < 4; ++rg) {
+            for (int rg = 0; rg < RG; ++rg) {
               const u32x4 u = __builtin_bit_cast(u32x4, hf[ks % RING][rg]);
               ok = ok && u[0] != 0xffffffffu && u[2] != 0xffffffffu;
             }
@@ -437,7 +442,7 @@ __global__ void __launch_bounds__(256) lstm_fwd_persist_kernel(PersistFwdArgs a)
             do {
               __builtin_amdgcn_s_sleep(1);
 #pragma unroll
-              for (int rg = 0; rg < 4; ++rg) hf[ks % RING][rg] = load_sc1_b128(hsrc, base + (rg * kblocks + (ks + rot) % KS) * 1024);
+              for (int rg = 0; rg < RG; ++rg) hf[ks % RING][rg] = load_sc1_b128(hsrc, base + (rg * kblocks + (ks + rot) % KS) * 1024);
               if (wall_clock64() - t_begin > kSpinTimeoutTicks) {
                 __hip_atomic_store(a.error_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 break;
@@ -450,7 +455,7 @@ __global__ void __launch_bounds__(256) lstm_fwd_persist_kernel(PersistFwdArgs a)
           const unsigned want = (unsigned)(((t - 1) >> 2) & 1);
           bool stale = false;
 #pragma unroll
-          for (int rg = 0; rg < 4; ++rg) {
+          for (int rg = 0; rg < RG; ++rg) {
             const u32x4 u = __builtin_bit_cast(u32x4, hf[ks % RING][rg]);
             stale |= (u[0] != 0xffffffffu && (u[0] & 1u) != want) | (u[2] != 0xffffffffu && (u[2] & 1u) != want);
           }
@@ -458,7 +463,7 @@ __global__ void __launch_bounds__(256) lstm_fwd_persist_kernel(PersistFwdArgs a)
         }
 #endif
 #pragma unroll
-        for (int rg = 0; rg < 4; ++rg)
+        for (int rg = 0; rg < RG; ++rg)
 #pragma unroll
           for (int j = 0; j < NQ; ++j)
             acc[rg][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wreg[ks][j], hf[ks % RING][rg], acc[rg][j], 0, 0, 0);
@@ -471,7 +476,7 @@ __global__ void __launch_bounds__(256) lstm_fwd_persist_kernel(PersistFwdArgs a)
     }
     if (xwave) {                               // x_t W_ih^T, requested a step ago
 #pragma unroll
-      for (int rg = 0; rg < 4; ++rg)
+      for (int rg = 0; rg < RG; ++rg)
 #pragma unroll
         for (int j = 0; j < NQ; ++j)
           acc[rg][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, cur[j]), xf[rg], acc[rg][j], 0, 0, 0);
@@ -484,7 +489,7 @@ __global__ void __launch_bounds__(256) lstm_fwd_persist_kernel(PersistFwdArgs a)
     CSN_PSTAMP(1);     // h loads + MFMA
 
 #pragma unroll
-    for (int rg = 0; rg < 4; ++rg)
+    for (int rg = 0; rg < RG; ++rg)
 #pragma unroll
       for (int j = 0; j < NQ; ++j)
         red[(wave * NT + rg * NQ + j) * kRedTile + lane] = make_float4(acc[rg][j][0], acc[rg][j][1], acc[rg][j][2], acc[rg][j][3]);
@@ -657,12 +662,20 @@ int fwd_persist_slices(int H) { return H / (4 * ((H % 24 == 0) ? 6 : 8)); }
 
 template <int NQ, int KS>
 static int launch_persist_t(const PersistFwdArgs& a, hipStream_t st) {
+  // (the 32-row instantiations ask for the 64-row tile's LDS, more than half a CU's, although they use half of it: their
+  // register counts would let two workgroups share a CU, and a launch of 8 groups needs every CU for a workgroup of its own)
   const size_t lds = (size_t)(4 * 4 * NQ * kRedTile + 4 * NQ) * sizeof(float4);
+  static_assert((4 * 4 * NQ * kRedTile + 4 * NQ) * sizeof(float4) > 80 * 1024, "the LDS request no longer keeps a workgroup alone on its CU");
   if (int rc = ensure_dyn_lds<&lstm_fwd_persist_kernel<NQ, KS, false>>((int)lds)) return rc;
   if (int rc = ensure_dyn_lds<&lstm_fwd_persist_kernel<NQ, KS, true>>((int)lds)) return rc;
   const unsigned nslices = (unsigned)(a.H / (4 * NQ));
   const unsigned grid = a.xcd_groups ? 8u * nslices : nslices * (unsigned)(a.MT * a.nslots);
-  if (a.data_polls) lstm_fwd_persist_kernel<NQ, KS, true><<<dim3(grid), 256, lds, st>>>(a);
+  if (a.half_tiles) {
+    if (int rc = ensure_dyn_lds<&lstm_fwd_persist_kernel<NQ, KS, false, 2>>((int)lds)) return rc;
+    if (int rc = ensure_dyn_lds<&lstm_fwd_persist_kernel<NQ, KS, true, 2>>((int)lds)) return rc;
+    if (a.data_polls) lstm_fwd_persist_kernel<NQ, KS, true, 2><<<dim3(grid), 256, lds, st>>>(a);
+    else lstm_fwd_persist_kernel<NQ, KS, false, 2><<<dim3(grid), 256, lds, st>>>(a);
+  } else if (a.data_polls) lstm_fwd_persist_kernel<NQ, KS, true><<<dim3(grid), 256, lds, st>>>(a);
   else lstm_fwd_persist_kernel<NQ, KS, false><<<dim3(grid), 256, lds, st>>>(a);
   CSN_LAUNCH_CHECK();
   return CSN_OK;
@@ -675,6 +688,9 @@ int launch_fwd_persist(const PersistFwdArgs& a, hipStream_t st) {
               kPersistFlagLine);
   if (a.xcd_groups)
     CSN_REQUIRE(a.nslots * a.MT <= 8 && fwd_persist_slices(a.H) <= 32, "launch_fwd_persist: groups do not fit 8 XCDs");
+  CSN_REQUIRE(a.MT * (a.half_tiles ? 32 : 64) == a.Bpad, "launch_fwd_persist: %d tiles of %d rows are not Bpad=%d", a.MT,
+              a.half_tiles ? 32 : 64, a.Bpad);
+  CSN_REQUIRE(!a.half_tiles || a.xcd_groups, "launch_fwd_persist: 32-row groups need the grouped form");
   const int nq = (a.H % 24 == 0) ? 6 : 8, ks = a.H / 128;
   if (nq == 6 && ks == 6) return launch_persist_t<6, 6>(a, st);
   if (nq == 6 && ks == 3) return launch_persist_t<6, 3>(a, st);

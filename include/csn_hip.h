@@ -36,7 +36,7 @@ enum csnStatus {
 enum csnDtype { CSN_F32 = 0, CSN_BF16 = 1 };
 
 /* ABI version of this header; bumped on any signature change.  A symbol added beside the existing ones
- * (csn_lstm_plan_set_grad_mode, csn_lstm_plan_set_lengths) breaks no caller and does not bump it. */
+ * (csn_lstm_plan_set_grad_mode, csn_lstm_plan_set_lengths, csn_lstm_plan_half_tile_launches) breaks no caller and does not bump it. */
 #define CSN_ABI_VERSION 6
 int csn_abi_version(void);
 /* Thread-local message for the last non-zero status returned on this thread. */
@@ -117,6 +117,10 @@ int csn_lstm_plan_path(const csnLstmPlan* plan);
  * backward has run, or a path without hand-off slabs.  Kept for ABI stability: it never returns anything else (the
  * single-copy form that returned 1 was removed). */
 int csn_lstm_plan_dgates_copies(const csnLstmPlan* plan);
+/* How many weight-stationary recurrence launches of the plan's LAST forward (which = 0) / backward (which = 1) ran on
+ * hand-off groups of 32 rows instead of 64 (launches whose 64-row groups would cover at most half of the XCDs;
+ * CSN_NO_HALF_TILES=1 keeps 64 rows everywhere: 0).  Diagnostic; -1 for a null plan / other `which`. */
+int csn_lstm_plan_half_tile_launches(const csnLstmPlan* plan, int which);
 /* Name of the device function that advances the recurrence on this plan's path: which = 0 forward, 1 backward
  * ("lstm_fwd_persist_kernel", "lstm_fwd_ns_kernel", "lstm_bwd_persist_kernel", "lstm_cell_fwd_il_kernel", ... -- the
  * names a rocprofv3 kernel trace shows, without template arguments).  Diagnostic: bench.py labels its roofline object
