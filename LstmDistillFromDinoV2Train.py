@@ -100,6 +100,8 @@ def build_parser(flavour=PERILS):
                    help='micro-batches per optimiser step: each batch runs as this many equal parts whose gradients are '
                         'summed on the device (batch_size must be a multiple; a shorter last batch of an epoch is cut '
                         'to one)')
+    p.add_argument('--fused_optimizer', action='store_true',
+                   help='adamw / adam / lars as fused HIP steps over the flat parameter buffer (rmsprop always is)')
     p.add_argument('--compat_label_bug', action='store_true',
                    help='reproduce the batch-local label lookup of transformEEGDataLSTMByList')
     return p
@@ -202,7 +204,7 @@ def main(argv=None, flavour=PERILS):
     sos = EEGFilters(FLAGS.fs, order=FLAGS.filter_order).sos if FLAGS.filter_order else None
     trainer = DistillTrainer(model, sos, loss=FLAGS.loss, lr=FLAGS.learning_rate, optimizer=FLAGS.optimizer,
                              nepochs=max(FLAGS.num_epochs, HyperParams.warmup_teacher_temp_epochs + 1), kd_params=kd,
-                             accum_steps=FLAGS.accum_steps)
+                             accum_steps=FLAGS.accum_steps, fused_optimizer=FLAGS.fused_optimizer)
 
     def batches(idx, epoch, shuffle, multiple_of=1):
         shard = idx[shard_indices(len(idx), epoch, FLAGS.seed, rank, world, shuffle=shuffle).to(device)]

@@ -57,6 +57,8 @@ def build_parser():
     p.add_argument('--dtype', type=str, default="bf16", choices=["bf16", "f32"])
     p.add_argument('--time_low', type=int, default=0)
     p.add_argument('--time_high', type=int, default=495)
+    p.add_argument('--fused_optimizer', action='store_true',
+                   help='per-tensor clip + AdamW as one fused HIP step over the flat parameter buffer')
     return p
 
 
@@ -98,7 +100,7 @@ def main(argv=None):
     if world > 1:
         for p in student.parameters():
             dist.broadcast(p.data, src=0)
-    grads = FlatGrads(student.parameters())
+    grads = FlatGrads(student.parameters(), flatten_params=FLAGS.fused_optimizer)
     # the student runs 2 + local_crops_number forwards per step through one set of parameters: each backward adds its
     # LSTM gradients straight into the flat buffer (CSN_GRAD_ACCUMULATE) instead of 4 L temporaries + autograd's adds
     for mod in student.modules():
@@ -109,7 +111,11 @@ def main(argv=None):
                          FLAGS.warmup_teacher_temp_epochs, FLAGS.epochs).to(device)
     regularized = [p for n, p in student.named_parameters() if p.requires_grad and not (n.endswith(".bias") or p.ndim == 1)]
     not_reg = [p for n, p in student.named_parameters() if p.requires_grad and (n.endswith(".bias") or p.ndim == 1)]
-    optimizer = torch.optim.AdamW([{"params": regularized}, {"params": not_reg, "weight_decay": 0.}])
+    if FLAGS.fused_optimizer:       # the clip loop and the two-group AdamW below as three launches (flat_optim.FlatAdamW)
+        from cerebralsignalnetworks_amd.flat_optim import FlatAdamW
+        optimizer = FlatAdamW(grads, no_decay=not_reg, clip=FLAGS.clip_grad or None)
+    else:
+        optimizer = torch.optim.AdamW([{"params": regularized}, {"params": not_reg, "weight_decay": 0.}])
     per_rank = len(shard_indices(len(train_idx), 0, FLAGS.seed, rank, world))
     niter = max(1, per_rank // FLAGS.batch_size_per_gpu)                  # drop_last=True
     lr_schedule = cosine_scheduler(FLAGS.lr * (FLAGS.batch_size_per_gpu * world) / 256., FLAGS.min_lr, FLAGS.epochs,
@@ -138,7 +144,7 @@ def main(argv=None):
             grads.zero()
             loss.backward()
             grads.all_reduce_mean()
-            if FLAGS.clip_grad:
+            if FLAGS.clip_grad and not FLAGS.fused_optimizer:     # (fused: inside optimizer.step(); a zeroed slice stays zero)
                 for p in student.parameters():
                     if p.grad is not None:
                         clip_coef = FLAGS.clip_grad / (p.grad.norm(2) + 1e-6)

@@ -7,3 +7,4 @@ from .lstm_model import Model, LSTMModel, CustomModel, LSTM  # noqa: F401
 from .losses import (CosineSimilarityLoss, FeatureDistributionLoss, loss_fn_kd,  # noqa: F401
                      BarlowTwinsLoss, HyperParams)
 from .retrieval import evaluate, l2_search  # noqa: F401
+from .flat_optim import FlatAdamW, FlatLARS, flat_clip_gradients  # noqa: F401

@@ -18,9 +18,11 @@ STATUS_TIMEOUT, STATUS_NONFINITE, STATUS_STALE_SLOT = 1, 2, 4      # bits of csn
 ABI_VERSION = 6
 LSTM_STATE = 0x100      # csn_lstm_plan_create flag CSN_LSTM_STATE (include/csn_hip.h)
 GRAD_OVERWRITE, GRAD_ACCUMULATE = 0, 1      # csn_lstm_plan_set_grad_mode (include/csn_hip.h)
+SEG_DECAYED, SEG_SCALED = 1, 2              # per-segment flags of csn_flat_segments_prepare (include/csn_hip.h)
 
 _c_void_p, _c_int, _c_i64, _c_size_t, _c_float = (ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
                                                   ctypes.c_size_t, ctypes.c_float)
+_c_double = ctypes.c_double
 
 
 class LstmDesc(ctypes.Structure):
@@ -80,6 +82,16 @@ SIGNATURES = {
     "csn_cosine_loss_scratch_bytes": (_c_size_t, [_c_int]),
     "csn_cosine_loss": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_void_p, _c_void_p, _c_float, _c_void_p, _c_void_p]),
     "csn_rmsprop_step": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_i64, _c_float, _c_float, _c_float, _c_void_p]),
+    "csn_flat_segments_scratch_bytes": (_c_size_t, [_c_int, _c_i64]),
+    "csn_flat_segments_prepare": (_c_int, [ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32), _c_int, _c_i64,
+                                           _c_void_p, _c_void_p]),
+    "csn_flat_segment_norms": (_c_int, [_c_void_p, _c_void_p, _c_float, _c_i64, _c_int, _c_void_p, _c_void_p, _c_void_p]),
+    "csn_flat_clip": (_c_int, [_c_void_p, _c_i64, _c_int, _c_void_p, _c_float, _c_void_p, _c_void_p]),
+    "csn_adam_step": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_i64, _c_int, _c_void_p, _c_i64,
+                               _c_double, _c_double, _c_double, _c_double, _c_double, _c_int, _c_double, _c_void_p,
+                               _c_void_p]),
+    "csn_lars_step": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_i64, _c_int, _c_void_p, _c_double, _c_double,
+                               _c_double, _c_double, _c_void_p]),
     "csn_barlow_offdiag_sqsum": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_void_p]),
     "csn_l2_topk_scratch_bytes": (_c_size_t, [_c_i64, _c_i64]),
     "csn_l2_topk": (_c_int, [_c_void_p, _c_void_p, _c_i64, _c_i64, _c_int, _c_int, _c_void_p, _c_void_p,
@@ -427,6 +439,78 @@ def rmsprop_step(params_flat, grads_flat, square_avg_flat, lr, alpha=0.99, eps=1
     with torch.cuda.device(params_flat.device):
         _check(load().csn_rmsprop_step(_ptr(params_flat), _ptr(grads_flat), _ptr(square_avg_flat), n, float(lr), float(alpha),
                                        float(eps), _stream()))
+
+
+# ---- optimiser tails over flat segmented buffers (csrc/optim.hip) ---------------------------------------------------------
+class SegmentTable:
+    """The device table of csn_flat_segments_prepare for a flat float32 buffer of ``n`` elements cut at ``seg_end``
+    (exclusive ends, one per tensor) with per-segment ``flags`` (SEG_DECAYED | SEG_SCALED).  Caller-owned scratch, like
+    every other scratch of the library; built once, on the current stream."""
+
+    def __init__(self, seg_end, flags, device):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise CsnError("libcsn_hip needs device tensors (no CPU fallback)")
+        self.seg_end, self.flags = [int(e) for e in seg_end], [int(f) for f in flags]
+        self.nseg, self.n = len(self.seg_end), (self.seg_end[-1] if self.seg_end else 0)
+        if len(self.flags) != self.nseg:
+            raise CsnError(f"SegmentTable: {len(self.flags)} flags for {self.nseg} segments")
+        lib = load()
+        nbytes = lib.csn_flat_segments_scratch_bytes(self.nseg, self.n)
+        if nbytes == 0:
+            raise CsnError(f"libcsn_hip: {lib.csn_last_error().decode()}")
+        self.buf = torch.empty(nbytes // 8, dtype=torch.float64, device=device)       # (torch allocations are 256-B aligned)
+        ends = (ctypes.c_int64 * self.nseg)(*self.seg_end)
+        flg = (ctypes.c_int32 * self.nseg)(*self.flags)
+        with torch.cuda.device(device):
+            _check(lib.csn_flat_segments_prepare(ends, flg, self.nseg, self.n, _ptr(self.buf), _stream()))
+
+
+def _flat_check(table, *bufs):
+    _need_cuda(*bufs)
+    for b in bufs:
+        if b is not None and (b.dtype != torch.float32 or b.numel() != table.n or not b.is_contiguous()):
+            raise CsnError(f"flat buffers must be contiguous float32 of {table.n} elements")
+
+
+def flat_segment_norms(table, a, b=None, weight_decay=0.0):
+    """Per-segment L2 norms of ``a`` ([nseg] float32, device); with ``b`` also of d = b + weight_decay a on decayed
+    segments, b elsewhere ([2, nseg]).  Deterministic: two runs give the same bits."""
+    _flat_check(table, a, b)
+    out = torch.empty((2, table.nseg) if b is not None else (table.nseg,), dtype=torch.float32, device=a.device)
+    with torch.cuda.device(a.device):
+        _check(load().csn_flat_segment_norms(_ptr(a), _ptr(b), float(weight_decay), table.n, table.nseg, _ptr(table.buf),
+                                             _ptr(out), _stream()))
+    return out
+
+
+def flat_clip(table, grads, clip):
+    """grads_s <- min(1, clip / (|grads_s| + 1e-6)) grads_s in place; returns the pre-clip norms ([nseg], device)."""
+    _flat_check(table, grads)
+    out = torch.empty(table.nseg, dtype=torch.float32, device=grads.device)
+    with torch.cuda.device(grads.device):
+        _check(load().csn_flat_clip(_ptr(grads), table.n, table.nseg, _ptr(table.buf), float(clip), _ptr(out), _stream()))
+    return out
+
+
+def adam_step(table, params, grads, exp_avg, exp_avg_sq, step, lr, beta1, beta2, eps, weight_decay, decoupled, clip=None,
+              norms_out=None):
+    """One fused Adam / AdamW step in place on the current stream (csn_adam_step); ``clip``: per-tensor clip of the
+    gradient used by the step (``grads`` itself is not written), pre-clip norms into ``norms_out``."""
+    _flat_check(table, params, grads, exp_avg, exp_avg_sq)
+    _need_cuda(norms_out)
+    with torch.cuda.device(params.device):
+        _check(load().csn_adam_step(_ptr(params), _ptr(grads), _ptr(exp_avg), _ptr(exp_avg_sq), table.n, table.nseg,
+                                    _ptr(table.buf), int(step), float(lr), float(beta1), float(beta2), float(eps),
+                                    float(weight_decay), int(bool(decoupled)), float(clip or 0.0), _ptr(norms_out), _stream()))
+
+
+def lars_step(table, params, grads, mu, lr, weight_decay, momentum, eta):
+    """One fused LARS step in place on the current stream (csn_lars_step: the norm pass and the update)."""
+    _flat_check(table, params, grads, mu)
+    with torch.cuda.device(params.device):
+        _check(load().csn_lars_step(_ptr(params), _ptr(grads), _ptr(mu), table.n, table.nseg, _ptr(table.buf), float(lr),
+                                    float(weight_decay), float(momentum), float(eta), _stream()))
 
 
 def barlow_offdiag_sqsum(c):

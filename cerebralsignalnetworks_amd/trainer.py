@@ -58,6 +58,7 @@ class FlatGrads:
         self.offsets = {}       # id(param) -> (first element, number of elements)
         self.segments = None    # [(start, end)] in readiness order, or None = one blocking collective
         self._pending, self._works = None, []
+        self.clip_table = None  # flat_optim.flat_clip_gradients' segment table, built on its first call
         off = 0
         for p in self.params:
             n = p.numel()
@@ -226,8 +227,11 @@ def check_device_status(model, collective=True):
 
 class DistillTrainer:
     def __init__(self, model, sos, ddof=0, loss="cosine", lr=1e-3, optimizer="rmsprop", nepochs=100,
-                 kd_params=None, preprocess=True, accum_steps=1):
-        """``accum_steps = k > 1``: train_step splits its batch into k equal micro-batches and sums their gradients (each
+                 kd_params=None, preprocess=True, accum_steps=1, fused_optimizer=False):
+        """``fused_optimizer=True`` (on a GPU): adamw / adam / lars step the flat buffers in one to three HIP launches
+        (flat_optim.FlatAdamW / FlatLARS) instead of the torch optimisers; rmsprop is fused either way.
+
+        ``accum_steps = k > 1``: train_step splits its batch into k equal micro-batches and sums their gradients (each
         loss scaled by 1 / k) in the flat buffer before the one all-reduce and optimiser step -- the step of the whole
         batch in 1 / k of the workspace.  That equals the full batch only for a loss that is a mean over rows (cosine,
         featdist, kd); barlow normalises with batch statistics and is refused."""
@@ -241,10 +245,19 @@ class DistillTrainer:
         self.sos, self.ddof, self.preprocess = sos, ddof, preprocess
         self.loss_name = loss
         on_gpu = next(model.parameters()).is_cuda
-        self.grads = FlatGrads(model.parameters(), flatten_params=(optimizer == "rmsprop" and on_gpu))
+        fused = bool(fused_optimizer) and on_gpu and optimizer in ("adamw", "adam", "lars")
+        self.grads = FlatGrads(model.parameters(), flatten_params=((optimizer == "rmsprop" or fused) and on_gpu))
         params = self.grads.params
         if optimizer == "rmsprop" and on_gpu:   # LstmDistillFromDinoV2Train.py:329 -- one fused pass over the flat buffers
             self.opt = FlatRMSprop(self.grads, lr=lr)
+        elif fused:                             # the same optimisers as below, arguments included, on the flat buffers
+            from .flat_optim import FlatAdamW, FlatLARS
+            if optimizer == "adamw":
+                self.opt = FlatAdamW(self.grads, lr=lr)
+            elif optimizer == "adam":
+                self.opt = FlatAdamW(self.grads, lr=lr, decoupled=False, weight_decay=0)
+            else:
+                self.opt = FlatLARS(self.grads, lr=lr, weight_decay=1e-6, weight_decay_filter=True, lars_adaptation_filter=True)
         elif optimizer == "rmsprop":
             self.opt = torch.optim.RMSprop(params, lr=lr)
         elif optimizer == "adamw":      # LstmDistillFromDinoV2TrainSpampinato.py:378

@@ -36,7 +36,8 @@ enum csnStatus {
 enum csnDtype { CSN_F32 = 0, CSN_BF16 = 1 };
 
 /* ABI version of this header; bumped on any signature change.  A symbol added beside the existing ones
- * (csn_lstm_plan_set_grad_mode, csn_lstm_plan_set_lengths, csn_lstm_plan_half_tile_launches) breaks no caller and does not bump it. */
+ * (csn_lstm_plan_set_grad_mode, csn_lstm_plan_set_lengths, csn_lstm_plan_half_tile_launches, the csn_flat_* family,
+ * csn_adam_step, csn_lars_step) breaks no caller and does not bump it. */
 #define CSN_ABI_VERSION 6
 int csn_abi_version(void);
 /* Thread-local message for the last non-zero status returned on this thread. */
@@ -298,6 +299,50 @@ int csn_cosine_loss(const float* student, const float* teacher, int B, int D,
  * ---------------------------------------------------------------------------------- */
 int csn_rmsprop_step(float* params, const float* grads, float* square_avg, int64_t n,
                      float lr, float alpha, float eps, csnStream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * Optimiser tails over flat float32 buffers cut into SEGMENTS, one per parameter tensor (trainer.FlatGrads packs
+ * tensors back to back: a segment boundary is an arbitrary element offset; only the buffer bases are 16-byte aligned).
+ * Every call takes (n, nseg, table): n elements, nseg segments, and a SEGMENT TABLE in caller-owned device memory of
+ * csn_flat_segments_scratch_bytes(nseg, n) bytes (16-byte aligned), filled once by csn_flat_segments_prepare and then
+ * used by any number of calls ordered behind it.  It also holds the float64 partial sums of the norm passes, so two
+ * calls that share a table must be ordered on one stream (one table per optimiser).  The library keeps no state.
+ * Per-segment flags: CSN_SEG_DECAYED = weight decay applies, CSN_SEG_SCALED = the clip (Adam) / the LARS trust ratio
+ * applies.  All sums of squares are two-stage: one float64 partial per (segment, 2048-element chunk), added per segment
+ * in a fixed order -- no floating-point atomics, two runs on the same input give the same bits.
+ * ---------------------------------------------------------------------------------- */
+#define CSN_SEG_DECAYED 1
+#define CSN_SEG_SCALED  2
+size_t csn_flat_segments_scratch_bytes(int nseg, int64_t n);
+/* seg_end: [host] nseg exclusive end offsets, strictly ascending from above 0, the last one == n.  flags: [host] nseg
+ * flag words, or NULL = both flags on every segment.  Enqueues the table's construction on `stream`. */
+int csn_flat_segments_prepare(const int64_t* seg_end, const int32_t* flags, int nseg, int64_t n, void* table,
+                              csnStream_t stream);
+/* Per-segment L2 norms.  b == NULL: |a_s|.  b != NULL: |a_s| and |d_s|, d = b + weight_decay a on decayed segments and
+ * d = b elsewhere (LARS: a = params, b = grads).  norms_out: optional [nseg] (b == NULL) or [2, nseg] float32.
+ * Replaces: torch._foreach_norm / p.grad.norm(2) per parameter, utils/utils.py:136, EEG-BarlowNetworks/optim.py:30-31. */
+int csn_flat_segment_norms(const float* a, const float* b, float weight_decay, int64_t n, int nseg, void* table,
+                           float* norms_out, csnStream_t stream);
+/* g_s <- min(1, clip / (|g_s| + 1e-6)) g_s in place on every segment; norms_out: optional [nseg] float32 pre-clip norms
+ * (stays on the device: no host round trip).  Replaces: clip_gradients, utils/utils.py:132-141. */
+int csn_flat_clip(float* grads, int64_t n, int nseg, void* table, float clip, float* norms_out, csnStream_t stream);
+/* One Adam (decoupled == 0) / AdamW (decoupled != 0) step, t >= 1 the number of this step, with the arithmetic of
+ * torch's single-tensor path:  m <- m + (1 - beta1)(g - m);  v <- beta2 v + (1 - beta2) g^2;
+ * p <- p - (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps), bc_i = 1 - beta_i^t (the scalar quotients are formed here in
+ * double and rounded to float once); on decayed segments p <- p (1 - lr weight_decay) first (AdamW) or
+ * g <- g + weight_decay p (Adam).  clip > 0: a norm pass over grads runs first and the step uses
+ * g <- min(1, clip / (|g_s| + 1e-6)) g on scaled segments (the DINO per-tensor clip); norms_out as in csn_flat_clip.
+ * grads is read, never written.  One launch (three with clip).
+ * Replaces: torch.optim.AdamW(...).step(), LstmDistillFromDinoV2TrainSpampinato.py:378 and LstmDistillation.py:150
+ * (behind the clip loop of utils/utils.py:132-141); torch.optim.Adam(...).step(), LSTMDistill.py:322. */
+int csn_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, int nseg,
+                  void* table, int64_t t, double lr, double beta1, double beta2, double eps, double weight_decay,
+                  int decoupled, double clip, float* norms_out, csnStream_t stream);
+/* One LARS step: d = g + weight_decay p (decayed segments); d <- d eta |p_s| / |d_s| where both norms are > 0 (scaled
+ * segments); mu <- momentum mu + d; p <- p - lr mu.  The norm pass and the step: three launches.
+ * Replaces: LARS.step, EEG-BarlowNetworks/optim.py:17-44. */
+int csn_lars_step(float* params, const float* grads, float* mu, int64_t n, int nseg, void* table, double lr,
+                  double weight_decay, double momentum, double eta, csnStream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * K7  Barlow-Twins reduction over the cross-correlation matrix c[D,D] (float32):
