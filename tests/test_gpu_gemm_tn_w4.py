@@ -1,31 +1,14 @@
 """The four-wave 256 x 256 / 256 x 128 weight-gradient kernel (the default TN path where the 256-tile kernels apply)
 against the 8-wave single-phase ring it replaces (CSN_TN_NO_STAGGER=1): same 32-row MFMA k-blocks in the same order
 inside the same K splits, hence the same bits -- slabs, reduced gradients and column sums (bias gradients)."""
-import os
-
 import numpy as np
 import pytest
 import torch
 
 from cerebralsignalnetworks_amd import cabi
+from gemm_tn_helpers import env as _env, float64_product as _float64_product, plan_gradients as _plan_gradients
 
 pytestmark = pytest.mark.gpu
-
-
-class _env:
-    def __init__(self, **kv):
-        self.kv = kv
-
-    def __enter__(self):
-        self.old = {k: os.environ.get(k) for k in self.kv}
-        os.environ.update(self.kv)
-
-    def __exit__(self, *exc):
-        for k, v in self.old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 def _operands(cuda, M, N, K, seed):
@@ -33,15 +16,6 @@ def _operands(cuda, M, N, K, seed):
     a = torch.randn(K, M, device=cuda, generator=g).to(torch.bfloat16)
     b = torch.randn(K, N, device=cuda, generator=g).to(torch.bfloat16)
     return a, b
-
-
-def _float64_product(a, b, rows=512):
-    """a^T b in float64 from the bf16 operands, by row blocks of the result (the float64 copies stay small)."""
-    b64 = b.double()
-    out = torch.empty(a.shape[1], b.shape[1], dtype=torch.float64, device=a.device)
-    for m in range(0, a.shape[1], rows):
-        out[m:m + rows] = a[:, m:m + rows].double().t() @ b64
-    return out
 
 
 @pytest.mark.parametrize("M,N,K", [(3072, 768, 128000), (3072, 128, 128000),
@@ -63,32 +37,6 @@ def test_w4_matches_single_phase_ring_bit_for_bit(cuda, M, N, K):
     np.testing.assert_array_equal(got.cpu().numpy(), ring.cpu().numpy())
     np.testing.assert_array_equal(got.cpu().numpy(), again.cpu().numpy())
     np.testing.assert_allclose(got.cpu().numpy(), want.cpu().numpy(), rtol=0, atol=2e-4 * np.sqrt(K))
-
-
-def _plan_gradients(cuda, B, T, C, H, L, env):
-    """Weight and bias gradients of one bf16 LSTM plan created under `env` (a plan reads its options once)."""
-    g = torch.Generator(device=cuda).manual_seed(B + T + H)
-    k = 1.0 / np.sqrt(H)
-
-    def uni(*s):
-        return (torch.rand(*s, device=cuda, generator=g) * 2 - 1) * k
-
-    w_ih = [uni(4 * H, C if l == 0 else H) for l in range(L)]
-    w_hh = [uni(4 * H, H) for l in range(L)]
-    b_ih = [uni(4 * H) for l in range(L)]
-    b_hh = [uni(4 * H) for l in range(L)]
-    x = torch.randn(B, T, C, device=cuda, generator=g)
-    dy_all = torch.randn(B, T, H, device=cuda, generator=g) * 0.1
-    dy_last = torch.randn(B, H, device=cuda, generator=g)
-    with _env(**env):
-        plan = cabi.LstmPlan(B, T, C, H, L, torch.bfloat16, cuda)
-    plan.forward(x, w_ih, w_hh, b_ih, b_hh, want_all=True)
-    grads = [[torch.full_like(p, float("nan")) for p in group] for group in (w_ih, w_hh, b_ih, b_hh)]
-    plan.backward(dy_last, dy_all, grads)
-    torch.cuda.synchronize()
-    assert plan.status() == 0
-    return {f"{name}_l{l}": t.cpu().numpy() for name, group in zip(("dw_ih", "dw_hh", "db_ih", "db_hh"), grads)
-            for l, t in enumerate(group)}
 
 
 @pytest.mark.parametrize("B,T,C,H,L", [(64, 160, 128, 768, 2), (64, 128, 128, 1024, 2),
