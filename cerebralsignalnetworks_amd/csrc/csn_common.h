@@ -48,10 +48,9 @@ int fail(int status, const char* fmt, ...);
 // library keeps no mutable global state, so plans on different streams / threads / devices never share any.
 struct Options {
   bool cell_v1, no_persist, no_persist_bwd, persist_streams, no_xcd_local, no_rotate, no_fuse_x, no_beside,
-      no_side_stream, gemm_slot, fwd_ksplit, fwd_nsplit, fwd_flags, bwd_flags, dpoll_no_hint, fwd_hint, gemm_no_dma, gemm_no_256, gemm_generic, gemm_lds64, tn_no_tr, tn_no_stagger, filter_v1, tags_no_rearm, gemm_no_192, no_half_tiles;
+      no_side_stream, fwd_ksplit, fwd_nsplit, fwd_flags, bwd_flags, dpoll_no_hint, fwd_hint, gemm_no_dma, gemm_no_256, gemm_generic, tn_no_tr, tn_no_stagger, filter_v1, tags_no_rearm, gemm_no_192, no_half_tiles;
   int chunk;       // timesteps per weight-stationary launch
   int tn_stages;   // LDS-DMA ring depth of the 256 x 256 weight-gradient kernel
-  int fwd_nk;
 };
 static inline Options options_from_env() {
   auto on = [](const char* name) { return getenv(name) != nullptr; };
@@ -70,7 +69,6 @@ static inline Options options_from_env() {
   o.no_beside = on("CSN_NO_BESIDE");
   o.no_half_tiles = on("CSN_NO_HALF_TILES");
   o.no_side_stream = on("CSN_NO_SIDE_STREAM");
-  o.gemm_slot = on("CSN_GEMM_SLOT");
   o.fwd_ksplit = on("CSN_FWD_KSPLIT");
   o.fwd_nsplit = on("CSN_FWD_NSPLIT");
   o.fwd_flags = on("CSN_FWD_FLAGS");
@@ -82,7 +80,6 @@ static inline Options options_from_env() {
   o.gemm_no_256 = on("CSN_GEMM_NO_256");
   o.gemm_no_192 = on("CSN_GEMM_NO_192");
   o.gemm_generic = on("CSN_GEMM_GENERIC");
-  o.gemm_lds64 = on("CSN_GEMM_LDS64");
   o.tn_no_tr = on("CSN_TN_NO_TR");
   o.filter_v1 = on("CSN_FILTER_V1");
 #ifdef CSN_SLAB_TAGS
@@ -91,7 +88,6 @@ static inline Options options_from_env() {
   o.chunk = num("CSN_LSTM_CHUNK", 32);
   if (o.chunk < 1) o.chunk = 1;
   o.tn_stages = num("CSN_TN_STAGES", 4);
-  o.fwd_nk = num("CSN_FWD_NK", 1);
   return o;
 }
 
@@ -175,8 +171,6 @@ int launch_colsum(const void* X, int64_t R, int64_t N, int dtype, float* out, fl
 int colsum_chunks();
 int launch_colsum_partial(const void* X, int64_t R, int64_t N, int dtype, void* scratch, hipStream_t st);
 // split-K slabs of C[M,N] = A[K,M]^T B[K,N] into `slabs` ([S][M*N] f32); returns S through S_out
-int launch_gemm_nt_beside(const void* A, const void* Bt, const float* bias, float* C, int64_t M, int64_t N, int64_t K,
-                          int max_wgs, hipStream_t st);
 int launch_gemm_tn_slabs(const void* A, const void* B, float* slabs, int64_t M, int64_t N, int64_t K, int dtype,
                          hipStream_t st, int* S_out, float* colsum, int* colsum_done, const Options& opt);
 // C[M,N] (+)= A[M,K] Bt[N,K]^T (+ bias): the body of csn_gemm_nt with the switches passed in

@@ -1478,14 +1478,10 @@ int gemm_nt(const void* A, const void* Bt, const float* bias, void* C, int64_t M
     CSN_LAUNCH_CHECK();
     return CSN_OK;
   }
-  const bool two = opt.gemm_lds64;
-  if (out_dtype == CSN_BF16) {
-    if (two) gemm_nt_bf16_kernel<bf16_t, 2><<<grid, 256, 65536, st>>>((const bf16_t*)A, (const bf16_t*)Bt, bias, (bf16_t*)C, M, N, K, 0);
-    else gemm_nt_bf16_kernel<bf16_t, 1><<<grid, 256, 32768, st>>>((const bf16_t*)A, (const bf16_t*)Bt, bias, (bf16_t*)C, M, N, K, 0);
-  } else {
-    if (two) gemm_nt_bf16_kernel<float, 2><<<grid, 256, 65536, st>>>((const bf16_t*)A, (const bf16_t*)Bt, bias, (float*)C, M, N, K, accumulate);
-    else gemm_nt_bf16_kernel<float, 1><<<grid, 256, 32768, st>>>((const bf16_t*)A, (const bf16_t*)Bt, bias, (float*)C, M, N, K, accumulate);
-  }
+  if (out_dtype == CSN_BF16)
+    gemm_nt_bf16_kernel<bf16_t, 1><<<grid, 256, 32768, st>>>((const bf16_t*)A, (const bf16_t*)Bt, bias, (bf16_t*)C, M, N, K, 0);
+  else
+    gemm_nt_bf16_kernel<float, 1><<<grid, 256, 32768, st>>>((const bf16_t*)A, (const bf16_t*)Bt, bias, (float*)C, M, N, K, accumulate);
   CSN_LAUNCH_CHECK();
   return CSN_OK;
 }
@@ -1498,29 +1494,6 @@ extern "C" int csn_gemm_nt(const void* A, const void* Bt, const float* bias, voi
                            int dtype, int out_dtype, int accumulate, csnStream_t stream) {
   return gemm_nt(A, Bt, bias, C, M, N, K, dtype, out_dtype, accumulate, as_stream(stream), options_from_env());
 }
-
-namespace csn {
-// NT GEMM on at most `max_wgs` workgroups, each alone on its CU (96 KB of LDS requested), walking the 128 x 128
-// tiles: runs beside a persistent LSTM launch on the CUs that launch leaves idle.  bf16 operands, K % 64 == 0.
-int launch_gemm_nt_beside(const void* A, const void* Bt, const float* bias, float* C, int64_t M, int64_t N, int64_t K,
-                          int max_wgs, hipStream_t st) {
-  CSN_REQUIRE(K % 64 == 0 && N % 4 == 0 && max_wgs >= 1, "launch_gemm_nt_beside: unsupported shape");
-  if (int rc = ensure_dyn_lds<&gemm_nt_256_kernel<float, 3>>(3 * 49152)) return rc;
-  if (int rc = ensure_dyn_lds<&gemm_nt_dma_kernel<float>>(98304)) return rc;
-  if (M >= 256 && N >= 128 && K >= 256) {
-    // 256 x 128 tiles, 8 waves, 144 KB of LDS: alone on a CU this kernel runs at twice the rate of the 4-wave one
-    const int64_t tiles = ((N + 127) / 128) * ((M + 255) / 256);
-    dim3 grid((unsigned)(tiles < max_wgs ? tiles : max_wgs));
-    gemm_nt_256_kernel<float, 3><<<grid, 512, 3 * 49152, st>>>((const bf16_t*)A, (const bf16_t*)Bt, bias, C, M, N, K, 0);
-  } else {
-    const int64_t tiles = ((N + 127) / 128) * ((M + 127) / 128);
-    dim3 grid((unsigned)(tiles < max_wgs ? tiles : max_wgs));
-    gemm_nt_dma_kernel<float><<<grid, 256, 98304, st>>>((const bf16_t*)A, (const bf16_t*)Bt, bias, C, M, N, K, 0);
-  }
-  CSN_LAUNCH_CHECK();
-  return CSN_OK;
-}
-}  // namespace csn
 
 namespace csn {
 size_t gemm_tn_scratch_bytes(int64_t M, int64_t N, int64_t K, const Options& opt) {

@@ -2,26 +2,34 @@
 // Replaces nn.LSTM(batch_first=True).forward / autograd backward as called at
 // /root/reference/LSTMDistill.py:118,132 and /root/reference/LSTMDistillRetreival.py:91,103.
 //
-// Two paths share the C entry points:
+// Five paths share the C entry points (csn_lstm_plan_path; make_layout decides at plan creation):
 //
-//  * "il" fast path (bf16, H % 128 == 0): lstm_cell_blk.hip kernels.  The layers advance as a
-//    WAVEFRONT: one launch per diagonal runs layer 0 at step d, layer 1 at step d - lag, ...
-//    (lag = 2 chunks), so a launch boundary (~2 us) and the launch ramp are paid once per
-//    diagonal, not once per layer-step, and a 2-layer diagonal is exactly one workgroup per CU.
-//    The non-recurrent contractions are big GEMMs on a second, library-owned HIP stream:
-//      forward : xproj_{l+1}[chunk] = h_l[chunk] W_ih^T + b   as soon as layer l finished a chunk;
-//      backward: dx_l[chunk] = dgates_l[chunk] W_ih (input gradient of layer l = dy of layer l-1),
-//                then dW_hh, dW_ih, db of layer l once its recurrence is done
-//    and HIP events order the two streams, so the MFMA-bound GEMMs run beside the
-//    latency/bandwidth-bound recurrence of the other layer instead of after it.
-//  * "v1" path (exact-f32 parity path, or shapes the fast path does not cover): layer after
-//    layer, generic cell kernels of lstm_cell.hip.
+//  0  generic (forward_v1 / backward_v1): float32, or bf16 shapes the fast paths do not cover; cell kernels of
+//     lstm_cell.hip, the layers as a wavefront of one launch per diagonal, lag = 1 chunk, everything on the caller's stream.
+//  1  per-diagonal fast path (forward_il / backward_il; bf16, H % 128 == 0): lstm_cell_blk.hip kernels.  The layers
+//     advance as a WAVEFRONT: one launch per diagonal runs layer 0 at step d, layer 1 at step d - lag, ...
+//     (lag = 2 chunks), so a launch boundary (~2 us) and the launch ramp are paid once per
+//     diagonal, not once per layer-step, and a 2-layer diagonal is exactly one workgroup per CU.
+//     The non-recurrent contractions are big GEMMs on a second, plan-owned HIP stream:
+//       forward : xproj_{l+1}[chunk] = h_l[chunk] W_ih^T + b   as soon as layer l finished a chunk;
+//       backward: dx_l[chunk] = dgates_l[chunk] W_ih (input gradient of layer l = dy of layer l-1),
+//                 then dW_hh, dW_ih, db of layer l once its recurrence is done
+//     and HIP events order the two streams, so the MFMA-bound GEMMs run beside the
+//     latency/bandwidth-bound recurrence of the other layer instead of after it.
+//  2  weight-stationary forward (forward_persist: lstm_fwd_persist.hip or lstm_fwd_ns.hip, one launch per chunk
+//     diagonal, or per layer and chunk on streams of their own), backward of path 1.
+//  3  path 2 with the weight-stationary backward (backward_persist: lstm_bwd_persist.hip, one launch per chunk diagonal,
+//     the input-gradient GEMM inside the next launch) where its grouped form applies (bwd_grouped), else backward_il.
+//  4  exact float32, weight-stationary (forward_f32p / backward_f32p: lstm_f32_persist.hip), layer after layer.
+//
+// Each path is one function over the per-call context (struct Call) and the caller's pointers (FwdArgs / BwdArgs); what
+// more than one of them does -- slot 0, weight gradients, chunk GEMMs, dx out, the profile epilogue -- is one helper each.
 //
 // Layout in HBM (inside the caller's workspace; [T,B,*] time-major so one timestep is one slab):
 //   per layer: compute-dtype weight copies (+ transposes / fragment-major forms), bias,
 //              xproj[T,B,4H] f32, gates[T,B,4H], c_all[T+1,B,H] f32, h_all[T+1,B,H],
-//              dgates[T,B,4H], dx[T,B,I_l] f32; fast path adds the fragment-major ping-pong
-//              buffers of h and dgates.  In the fast path every 4H axis is gate-interleaved
+//              dgates[T,B,4H], dx[T,B,I_l] f32; the fast paths add the fragment-major ping-pong / ring
+//              buffers of h and dgates.  In paths 1 - 3 every 4H axis is gate-interleaved
 //              (n' = 4 unit + gate); parameters and their gradients are (un)permuted at the API.
 #include <algorithm>
 #include <cstring>
@@ -33,12 +41,6 @@
 #include "lstm_f32_persist.h"
 
 namespace csn {
-
-int launch_cell_fwd(const void* h_prev, const void* w_hh, const float* xproj, int64_t xproj_ld, const float* c_prev,
-                    void* gates_out, float* c_out, void* h_out, int B, int H, int dtype, hipStream_t st);
-int launch_cell_bwd(const void* dg_next, const void* w_hh_t, const float* dy, int64_t dy_ld, const void* gates,
-                    const float* c, const float* c_prev, float* dc_carry, void* dg_out, int B, int H, int dtype,
-                    hipStream_t st);
 
 struct LayerWs {
   size_t wih, whh, whht, wiht, whh_blk, whht_blk, bias, xproj, gates, c_all, h_all, dgates, dx, dc_carry, hblk[2],
@@ -443,14 +445,11 @@ struct csnLstmPlan {
   csnGradReadyFn grad_cb = nullptr;      // csn_lstm_plan_set_grad_callback
   void* grad_cb_user = nullptr;
   int grad_accumulate = 0;               // csn_lstm_plan_set_grad_mode: dw / db are added to, not overwritten
-  // csn_lstm_plan_set_lengths (empty = every row is T).  A call with lengths runs every path with d.T lowered to the
-  // longest row for its duration (all saved tensors are time-major, so T enters extents only, never a stride); T_full is
-  // the T of the caller's batch-first tensors and dlen the device copy of the lengths while a call with lengths is in
-  // progress (len_dev: [B] int32 owned by the plan -- a state plan's workspace is laid out exactly as a plain plan's)
+  // csn_lstm_plan_set_lengths (empty = every row is T): the lengths of the next calls and the longest of them.  What a
+  // call in progress derives from them lives in its Call, not here.  (len_dev: [B] int32 owned by the plan -- a state
+  // plan's workspace is laid out exactly as a plain plan's)
   std::vector<int32_t> lengths;
   int t_eff = 0;
-  int T_full = 0;
-  const int* dlen = nullptr;
   int32_t* len_dev = nullptr;
   int32_t* len_pin = nullptr;            // pinned staging of the upload, and the event behind its last copy
   hipEvent_t len_ev = nullptr;
@@ -485,7 +484,6 @@ extern "C" int csn_lstm_plan_create(const csnLstmDesc* d, int training, csnLstmP
     if (cmax >= 3 && (unsigned long long)P->opt.chunk > cmax - 2) P->opt.chunk = (int)(cmax - 2);
   }
   P->w = make_layout(*d, P->training, P->opt);
-  P->T_full = d->T;
   *out = P;
   return CSN_OK;
 }
@@ -522,10 +520,11 @@ extern "C" int csn_lstm_plan_half_tile_launches(const csnLstmPlan* P, int which)
   return (P == nullptr || which < 0 || which > 1) ? -1 : P->half_launches[which];
 }
 
-// does the backward of this plan take the grouped weight-stationary form (backward_il's dispatch)?
-static bool bwd_grouped(const csnLstmPlan* P) {
+// does a backward of this plan over T steps take the grouped weight-stationary form?  (a call passes the steps it runs --
+// with lengths the longest row --, csn_lstm_plan_kernel_name the plan's T)
+static bool bwd_grouped(const csnLstmPlan* P, int T) {
   if (!P->w.persist_bwd) return false;
-  const int MTg = (P->d.B + 63) / 64, nchg = (P->d.T + P->opt.chunk - 1) / P->opt.chunk;
+  const int MTg = (P->d.B + 63) / 64, nchg = (T + P->opt.chunk - 1) / P->opt.chunk;
   const int slots = P->d.L < nchg ? P->d.L : nchg;
   return slots <= 4 && slots * MTg <= 8 && !P->opt.persist_streams;
 }
@@ -541,7 +540,7 @@ extern "C" const char* csn_lstm_plan_kernel_name(const csnLstmPlan* P, int which
     return ks ? "lstm_cell_fwd_ks_kernel" : "lstm_cell_fwd_kernel";
   }
   if (which == 1) {
-    if (bwd_grouped(P)) return "lstm_bwd_persist_kernel";
+    if (bwd_grouped(P, P->d.T)) return "lstm_bwd_persist_kernel";
     if (P->w.il) return "lstm_cell_bwd_il_kernel";
     return ks ? "lstm_cell_bwd_ks_kernel" : "lstm_cell_bwd_kernel";
   }
@@ -581,17 +580,11 @@ extern "C" int csn_lstm_plan_set_lengths(csnLstmPlan* P, const int32_t* lengths)
   return CSN_OK;
 }
 
-// for the duration of a call with lengths: the plan's T is the longest row
-struct EffectiveT {
-  csnLstmDesc& d;
-  const int T;
-  EffectiveT(csnLstmDesc& d_, int Te) : d(d_), T(d_.T) { d.T = Te; }
-  ~EffectiveT() { d.T = T; }
-};
 // lengths of the call in progress -> the plan's device array, in stream order (every forward and backward that runs with
-// lengths uploads what the plan holds, so the kernels of a call read the lengths of that call)
-static int upload_lengths(csnLstmPlan* P, hipStream_t st) {
-  P->dlen = nullptr;
+// lengths uploads what the plan holds, so the kernels of a call read the lengths of that call); *dlen: that array, or null
+// for a plan without lengths
+static int upload_lengths(csnLstmPlan* P, hipStream_t st, const int** dlen) {
+  *dlen = nullptr;
   if (P->lengths.empty()) return CSN_OK;
   // through a pinned staging array of the plan: the copy is asynchronous, and the array is rewritten only once the copy
   // before has left it (long ago, as a rule: the wait is for one small copy, not for the stream)
@@ -606,23 +599,69 @@ static int upload_lengths(csnLstmPlan* P, hipStream_t st) {
   memcpy(P->len_pin, P->lengths.data(), bytes);
   CSN_HIP_CHECK(hipMemcpyAsync(P->len_dev, P->len_pin, bytes, hipMemcpyHostToDevice, st));
   CSN_HIP_CHECK(hipEventRecord(P->len_ev, st));
-  P->dlen = P->len_dev;
+  *dlen = P->len_dev;
   return CSN_OK;
 }
+
+// One forward or backward call: lives on the stack of csn_lstm_forward / csn_lstm_backward and is handed to every path and
+// helper below.  What holds for the duration of a call only is here, not in the plan: P.d is never written after
+// csn_lstm_plan_create.  A call with lengths runs every path over the steps of the longest row (all saved tensors are
+// time-major, so T enters extents only, never a stride -- the workspace layout is that of d.T).
+struct Call {
+  Plan& P;
+  const csnLstmDesc& d;
+  const WsLayout& w;
+  char* ws;
+  hipStream_t st;       // the caller's stream
+  const int* dlen;      // device copy of the lengths ([B] int32, owned by the plan), null without lengths
+  int T;                // the steps this call runs: the longest row with lengths, else d.T
+  int T_full;           // d.T: the steps per row of the caller's batch-first tensors
+  int B, H, NL, dt, Cz; // Cz: steps per chunk
+  int64_t G, TB;        // 4 H; T * B
+  size_t es;            // bytes per element of the compute dtype
+  Call(Plan& P_, void* workspace, hipStream_t st_, const int* dlen_)
+      : P(P_), d(P_.d), w(P_.w), ws((char*)workspace), st(st_), dlen(dlen_), T(dlen_ ? P_.t_eff : P_.d.T), T_full(P_.d.T),
+        B(P_.d.B), H(P_.d.H), NL(P_.d.L), dt(P_.d.dtype), Cz(P_.opt.chunk), G(4 * (int64_t)P_.d.H), TB((int64_t)T * P_.d.B),
+        es(dtype_size(P_.d.dtype)) {}
+  int64_t in_width(int l) const { return l == 0 ? d.I : H; }
+};
+// what the caller passes to a forward / a backward (state pointers null unless the plan takes them)
+struct FwdArgs {
+  const float* x;
+  int64_t xsb, xst;
+  const float* const* w_ih;
+  const float* const* w_hh;
+  const float* const* b_ih;
+  const float* const* b_hh;
+  const float* h0;
+  const float* c0;
+};
+struct BwdArgs {
+  const float* dy_last;       // gradient w.r.t. the top layer's output: at the last step, and / or
+  const float* dy_tm;         // time-major for every step (workspace copy)
+  const float* dh_n;
+  const float* dc_n;
+  float* const* dw_ih;
+  float* const* dw_hh;
+  float* const* db_ih;
+  float* const* db_hh;
+  float* dx;
+};
+
 // input gradient out of its time-major workspace form; with lengths the caller's rows have T_full steps, zeros behind the longest
-static int emit_dx(const csnLstmPlan& P, const float* dx_tm, float* dx, int64_t I, hipStream_t st) {
-  const int B = P.d.B, T = P.d.T;
-  if (P.dlen != nullptr) tb_to_bt_len_kernel<<<csn::grid_for((int64_t)P.T_full * B * I), 256, 0, st>>>(dx_tm, dx, B, P.T_full, T, (int)I);
+static int emit_dx(const Call& C, const float* dx_tm, float* dx, int64_t I, hipStream_t st) {
+  const int B = C.B, T = C.T;
+  if (C.dlen != nullptr) tb_to_bt_len_kernel<<<csn::grid_for((int64_t)C.T_full * B * I), 256, 0, st>>>(dx_tm, dx, B, C.T_full, T, (int)I);
   else csn::tb_to_bt_kernel<<<csn::grid_for((int64_t)T * B * I), 256, 0, st>>>(dx_tm, dx, B, T, (int)I);
   CSN_LAUNCH_CHECK();
   return CSN_OK;
 }
 // gradient w.r.t. h_n of the layer below, into this layer's time-major input gradient `dx_tm` whose steps [t_lo, t_hi] were
 // just written: at T-1 without lengths, at each row's own last step with them
-static int add_dh_n_rows(const csnLstmPlan& P, const float* dh_below, float* dx_tm, int t_lo, int t_hi, hipStream_t st) {
-  const int B = P.d.B, H = P.d.H, T = P.d.T;
-  if (P.dlen != nullptr) {
-    add_at_end_kernel<<<csn::grid_for((int64_t)B * H), 256, 0, st>>>(dh_below, dx_tm, P.dlen, t_lo, t_hi, B, H);
+static int add_dh_n_rows(const Call& C, const float* dh_below, float* dx_tm, int t_lo, int t_hi, hipStream_t st) {
+  const int B = C.B, H = C.H, T = C.T;
+  if (C.dlen != nullptr) {
+    add_at_end_kernel<<<csn::grid_for((int64_t)B * H), 256, 0, st>>>(dh_below, dx_tm, C.dlen, t_lo, t_hi, B, H);
   } else {
     if (t_hi != T - 1) return CSN_OK;
     csn::add_rows_kernel<<<csn::grid_for((int64_t)B * H), 256, 0, st>>>(dh_below, dx_tm + (size_t)(T - 1) * B * H, (int64_t)B * H);
@@ -733,65 +772,210 @@ static int gemm_tn_full(const void* A, const void* B, float* C, int64_t M, int64
 }
 
 // lengths: zeros over the padding of the re-laid-out input (x_c, and the fragment-major slabs of the fused projection)
-static int mask_x(const csnLstmPlan& P, char* ws, hipStream_t st) {
-  if (P.dlen == nullptr) return CSN_OK;
-  const csnLstmDesc& d = P.d;
-  const int64_t n = (int64_t)d.T * d.B * d.I;
-  if (d.dtype == CSN_BF16) mask_tm_kernel<bf16_t><<<grid_for(n), 256, 0, st>>>((bf16_t*)(ws + P.w.x_c), P.dlen, d.B, d.T, d.I);
-  else mask_tm_kernel<float><<<grid_for(n), 256, 0, st>>>((float*)(ws + P.w.x_c), P.dlen, d.B, d.T, d.I);
+static int mask_x(const Call& C, hipStream_t st) {
+  if (C.dlen == nullptr) return CSN_OK;
+  const csnLstmDesc& d = C.d;
+  char* ws = C.ws;
+  const int64_t n = (int64_t)C.T * d.B * d.I;
+  if (d.dtype == CSN_BF16) mask_tm_kernel<bf16_t><<<grid_for(n), 256, 0, st>>>((bf16_t*)(ws + C.w.x_c), C.dlen, d.B, C.T, d.I);
+  else mask_tm_kernel<float><<<grid_for(n), 256, 0, st>>>((float*)(ws + C.w.x_c), C.dlen, d.B, C.T, d.I);
   CSN_LAUNCH_CHECK();
-  if (P.w.fuse_x) {
+  if (C.w.fuse_x) {
     const int64_t Bpad = ((int64_t)d.B + 63) / 64 * 64;
-    mask_x_blk_kernel<<<grid_for((int64_t)d.T * Bpad * d.I / 8), 256, 0, st>>>((bf16_t*)(ws + P.w.x_blk), P.dlen, d.B, Bpad, d.T, d.I);
+    mask_x_blk_kernel<<<grid_for((int64_t)C.T * Bpad * d.I / 8), 256, 0, st>>>((bf16_t*)(ws + C.w.x_blk), C.dlen, d.B, Bpad, C.T, d.I);
     CSN_LAUNCH_CHECK();
   }
   return CSN_OK;
 }
 
 // =============================================================================================
-// v1 path
+// jobs every path shares
 // =============================================================================================
-// Wavefront over the layers, as in the fast path: diagonal d runs layer l at step d - l * lag in ONE launch (blockIdx.z =
+// what layer l multiplies by W_ih, time-major from step 0: the re-laid-out x, or the outputs of the layer below (h_all from slot 1)
+static const void* layer_input(const Call& C, int l) {
+  return l == 0 ? (const void*)(C.ws + C.w.x_c) : (const void*)(C.ws + C.w.layer[l - 1].h_all + (size_t)C.B * C.H * C.es);
+}
+
+// slot 0 of h_all / c_all of layer l = the initial state (the cells read it at t = 0; the dW_hh GEMM reads h_all slot 0
+// too): the caller's (h0, c0), or zeros
+static int install_slot0(const Call& C, int l, const float* h0, const float* c0) {
+  const LayerWs& L = C.w.layer[l];
+  const size_t BH = (size_t)C.B * C.H;
+  if (h0) {
+    if (int rc = launch_cast(h0 + l * BH, C.ws + L.h_all, (int64_t)BH, C.dt, C.st)) return rc;
+  } else {
+    CSN_HIP_CHECK(hipMemsetAsync(C.ws + L.h_all, 0, BH * C.es, C.st));
+  }
+  if (c0)
+    CSN_HIP_CHECK(hipMemcpyAsync(C.ws + L.c_all, c0 + l * BH, BH * 4, hipMemcpyDeviceToDevice, C.st));
+  else
+    CSN_HIP_CHECK(hipMemsetAsync(C.ws + L.c_all, 0, BH * 4, C.st));
+  return CSN_OK;
+}
+
+// the carried dc of layer l starts as the gradient w.r.t. c_n; after step 0 it is the gradient w.r.t. c0
+// (zeroed: a fill of the workspace has cleared it already)
+static int seed_dc_carry(const Call& C, int l, const float* dc_n, bool zeroed) {
+  const size_t BH = (size_t)C.B * C.H;
+  if (dc_n)
+    CSN_HIP_CHECK(hipMemcpyAsync(C.ws + C.w.layer[l].dc_carry, dc_n + l * BH, BH * 4, hipMemcpyDeviceToDevice, C.st));
+  else if (!zeroed)
+    CSN_HIP_CHECK(hipMemsetAsync(C.ws + C.w.layer[l].dc_carry, 0, BH * 4, C.st));
+  return CSN_OK;
+}
+
+// Row-major paths (0 and 4): time-major x, the compute-dtype copies of the parameters (transposes for a training plan),
+// b_ih + b_hh, slot 0 of every layer
+static int prep_row_major(const Call& C, const FwdArgs& A) {
+  const WsLayout& w = C.w;
+  char* ws = C.ws;
+  hipStream_t st = C.st;
+  const int H = C.H, dt = C.dt;
+  const int64_t G = C.G;
+  int rc;
+  if ((rc = launch_cast_strided(A.x, A.xsb, A.xst, C.B, C.T, C.d.I, ws + w.x_c, dt, st))) return rc;
+  if ((rc = mask_x(C, st))) return rc;
+  for (int l = 0; l < C.NL; ++l) {
+    const LayerWs& L = w.layer[l];
+    const int64_t I = C.in_width(l);
+    if ((rc = launch_cast(A.w_ih[l], ws + L.wih, G * I, dt, st))) return rc;
+    if ((rc = launch_cast(A.w_hh[l], ws + L.whh, G * H, dt, st))) return rc;
+    if (C.P.training) {
+      if ((rc = launch_transpose_cast(A.w_hh[l], G, H, ws + L.whht, dt, st))) return rc;
+      if ((rc = launch_transpose_cast(A.w_ih[l], G, I, ws + L.wiht, dt, st))) return rc;
+    }
+    if ((rc = launch_add_vec(A.b_ih[l], A.b_hh[l], (float*)(ws + L.bias), G, st))) return rc;
+    if ((rc = install_slot0(C, l, A.h0, A.c0))) return rc;
+  }
+  return CSN_OK;
+}
+
+// chunk c of the sequence: steps [t0, t0 + nsteps).  The backward walks the chunks from the end: its reverse chunk c
+// covers the steps [t_hi - nsteps + 1, t_hi] with t_hi = T - 1 - t0.
+struct Chunk { int t0, nsteps; };
+static Chunk chunk_at(const Call& C, int c) {
+  const int t0 = c * C.Cz;
+  return Chunk{t0, t0 + C.Cz <= C.T ? C.Cz : C.T - t0};
+}
+// is step (or reverse step) t the last one of its chunk?
+static bool ends_chunk(const Call& C, int t) { return (t + 1) % C.Cz == 0 || t == C.T - 1; }
+
+// layer l finished chunk c -> xproj_{l+1}[chunk c] = h_l[chunk c] W_ih^T + b
+static int xproj_chunk_gemm(const Call& C, int l, int c, hipStream_t on) {
+  const LayerWs& Ln = C.w.layer[l + 1];
+  const Chunk k = chunk_at(C, c);
+  return gemm_nt(C.ws + C.w.layer[l].h_all + (size_t)(k.t0 + 1) * C.B * C.H * C.es, C.ws + Ln.wih, (const float*)(C.ws + Ln.bias),
+                 (float*)(C.ws + Ln.xproj) + (size_t)k.t0 * C.B * C.G, (int64_t)k.nsteps * C.B, C.G, C.H, C.dt, CSN_F32, 0, on, C.P.opt);
+}
+
+// layer l >= 1 finished reverse chunk c -> dx_l[chunk] = dgates_l[chunk] W_ih (the dy of the layer below; Bt = W_ih^T [H, 4H]),
+// then the gradient w.r.t. h_n of the layer below joins it at t = T-1 (with lengths: at each row's last step)
+static int dx_chunk_gemm(const Call& C, int l, int c, const float* dh_n, hipStream_t on) {
+  const LayerWs& L = C.w.layer[l];
+  const Chunk k = chunk_at(C, c);
+  const int t_hi = C.T - 1 - k.t0, t_lo = t_hi - k.nsteps + 1;
+  if (int rc = gemm_nt(C.ws + L.dgates + (size_t)t_lo * C.B * C.G * C.es, C.ws + L.wiht, nullptr, (float*)(C.ws + L.dx) + (size_t)t_lo * C.B * C.H,
+                       (int64_t)k.nsteps * C.B, C.H, C.G, C.dt, CSN_F32, 0, on, C.P.opt))
+    return rc;
+  if (dh_n) return add_dh_n_rows(C, dh_n + (size_t)(l - 1) * C.B * C.H, (float*)(C.ws + L.dx), t_lo, t_hi, on);
+  return CSN_OK;
+}
+
+// input gradient of layer 0, whole sequence, out to the caller (batch-first)
+static int dx_out(const Call& C, float* dx, hipStream_t on) {
+  const LayerWs& L = C.w.layer[0];
+  if (int rc = gemm_nt(C.ws + L.dgates, C.ws + L.wiht, nullptr, C.ws + L.dx, C.TB, C.d.I, C.G, C.dt, CSN_F32, 0, on, C.P.opt)) return rc;
+  return emit_dx(C, (const float*)(C.ws + L.dx), dx, C.d.I, on);
+}
+
+// weight / bias gradients of layer l (its recurrence complete), row-major paths.  colsum: db_ih and db_hh as the column
+// sums of dgates (the float32 weight-stationary kernel has summed the bias gradient itself)
+static int weight_grads_rm(const Call& C, const BwdArgs& A, int l, bool colsum) {
+  const WsLayout& w = C.w;
+  const LayerWs& L = w.layer[l];
+  char* ws = C.ws;
+  const int acc = C.P.grad_accumulate;
+  int rc;
+  if ((rc = gemm_tn_full(ws + L.dgates, ws + L.h_all, A.dw_hh[l], C.G, C.H, C.TB, C.dt, ws + w.tn_scratch, acc, C.st, C.P.opt))) return rc;
+  if ((rc = gemm_tn_full(ws + L.dgates, layer_input(C, l), A.dw_ih[l], C.G, C.in_width(l), C.TB, C.dt, ws + w.tn_scratch, acc, C.st, C.P.opt))) return rc;
+  // db_ih and db_hh both come out of the reduction (each adds to its own previous contents under CSN_GRAD_ACCUMULATE)
+  if (colsum) return launch_colsum(ws + L.dgates, C.TB, C.G, C.dt, A.db_ih[l], A.db_hh[l], acc, ws + w.colsum, C.st);
+  return CSN_OK;
+}
+
+// weight / bias gradients of layer l (its recurrence complete), fast paths: two split-K GEMMs, the reductions that
+// un-permute the gate-interleaved 4H axis, the bias gradient -- four or five launches on `on`
+static int weight_grads_blk(const Call& C, const BwdArgs& A, int l, hipStream_t on) {
+  const WsLayout& w = C.w;
+  const LayerWs& L = w.layer[l];
+  char* ws = C.ws;
+  const int H = C.H;
+  const int64_t G = C.G, TB = C.TB, I = C.in_width(l);
+  float* slabs = (float*)(ws + w.tn_scratch);
+  const int acc = C.P.grad_accumulate;
+  int S = 1, r;
+  int cs_done = 0, S_cs = 1;
+  if ((r = launch_gemm_tn_slabs(ws + L.dgates, ws + L.h_all, slabs, G, H, TB, CSN_BF16, on, &S, (float*)(ws + w.colsum), &cs_done, C.P.opt))) return r;
+  S_cs = S;
+  if ((r = launch_reduce_slabs_unperm(slabs, G * H, S, H, H, A.dw_hh[l], nullptr, acc, on))) return r;
+  if ((r = launch_gemm_tn_slabs(ws + L.dgates, layer_input(C, l), slabs, G, I, TB, CSN_BF16, on, &S, nullptr, nullptr, C.P.opt))) return r;
+  if ((r = launch_reduce_slabs_unperm(slabs, G * I, S, H, I, A.dw_ih[l], nullptr, acc, on))) return r;
+  // bias gradient = column sums of dgates: partial sums come out of the dW_hh GEMM when its kernel provides them
+  if (!cs_done) {
+    if ((r = launch_colsum_partial(ws + L.dgates, TB, G, CSN_BF16, ws + w.colsum, on))) return r;
+    S_cs = colsum_chunks();
+  }
+  // db_ih and db_hh both come out of the reduction (each adds to its own previous contents under CSN_GRAD_ACCUMULATE)
+  return launch_reduce_slabs_unperm((const float*)(ws + w.colsum), G, S_cs, H, 1, A.db_ih[l], A.db_hh[l], acc, on);
+}
+
+// end of the recurrence window of a forward (k = 0) / a backward (k = 1): its closing event and what csn_lstm_profile_read reports
+static int prof_end(Call& C, int k, int launches, int cells) {
+  Prof& g_prof = C.P.prof;
+  if (int rc = prof_mark(g_prof, 2 * k + 1, C.st)) return rc;
+  g_prof.launches[k] = launches;
+  g_prof.cells[k] = cells;
+  g_prof.have[k] = g_prof.on;
+  return CSN_OK;
+}
+
+// gradient w.r.t. the initial hidden state of layer l (lstm_dh0_kernel: dgates of step 0 times W_hh), in the form this
+// plan's backward left the two
+static int launch_dh0(const Call& C, int l, float* out) {
+  const LayerWs& L = C.w.layer[l];
+  const int B = C.B, H = C.H;
+  const dim3 grid((unsigned)((H + 63) / 64), (unsigned)((B + 31) / 32));
+  if (C.w.il)
+    lstm_dh0_kernel<bf16_t, true><<<grid, 256, 0, C.st>>>((const bf16_t*)(C.ws + L.dgates), (const bf16_t*)(C.ws + L.whht_blk), B, H, out);
+  else if (C.dt == CSN_BF16)
+    lstm_dh0_kernel<bf16_t, false><<<grid, 256, 0, C.st>>>((const bf16_t*)(C.ws + L.dgates), (const bf16_t*)(C.ws + L.whht), B, H, out);
+  else
+    lstm_dh0_kernel<float, false><<<grid, 256, 0, C.st>>>((const float*)(C.ws + L.dgates), (const float*)(C.ws + L.whht), B, H, out);
+  CSN_LAUNCH_CHECK();
+  return CSN_OK;
+}
+
+// =============================================================================================
+// path 0: generic cells (lstm_cell.hip)
+// =============================================================================================
+// Wavefront over the layers, as in path 1: diagonal d runs layer l at step d - l * lag in ONE launch (blockIdx.z =
 // layer; round 3 ran layer after layer, one launch per layer-step: 2 T L launches per pass, each bound by its launch
 // boundary and its own fill, not by the float32 MFMA rate).  The input projection of layer l + 1 follows layer l chunk by
 // chunk (GEMM over `chunk` steps on the same stream), so lag = chunk.
-static int forward_v1(Plan& P, char* ws, const float* x, int64_t xsb, int64_t xst,
-                      const float* const* w_ih, const float* const* w_hh, const float* const* b_ih,
-                      const float* const* b_hh, const float* h0, const float* c0, int training, csnStream_t stream) {
-  const csnLstmDesc* d = &P.d;
-  const WsLayout& w = P.w;
-  hipStream_t st = as_stream(stream);
-  const int B = d->B, T = d->T, H = d->H, dt = d->dtype, NL = d->L;
-  const int64_t G = 4 * (int64_t)H, TB = (int64_t)T * B;
-  const size_t es = dtype_size(dt);
-  const int Cz = P.opt.chunk, lag = Cz;
+static int forward_v1(Call& C, const FwdArgs& A) {
+  const WsLayout& w = C.w;
+  char* ws = C.ws;
+  hipStream_t st = C.st;
+  const int B = C.B, T = C.T, H = C.H, dt = C.dt, NL = C.NL;
+  const int64_t G = C.G;
+  const size_t es = C.es;
+  const int lag = C.Cz;
+  const int training = C.P.training;
   int rc;
-  if ((rc = launch_cast_strided(x, xsb, xst, B, T, d->I, ws + w.x_c, dt, st))) return rc;
-  if ((rc = mask_x(P, ws, st))) return rc;
-  for (int l = 0; l < NL; ++l) {
-    const LayerWs& L = w.layer[l];
-    const int64_t I = l == 0 ? d->I : H;
-    if ((rc = launch_cast(w_ih[l], ws + L.wih, G * I, dt, st))) return rc;
-    if ((rc = launch_cast(w_hh[l], ws + L.whh, G * H, dt, st))) return rc;
-    if (training) {
-      if ((rc = launch_transpose_cast(w_hh[l], G, H, ws + L.whht, dt, st))) return rc;
-      if ((rc = launch_transpose_cast(w_ih[l], G, I, ws + L.wiht, dt, st))) return rc;
-    }
-    if ((rc = launch_add_vec(b_ih[l], b_hh[l], (float*)(ws + L.bias), G, st))) return rc;
-    // slot 0 = the initial state (the cells read it at t = 0; the dW_hh GEMM reads h_all slot 0 too)
-    if (h0) {
-      if ((rc = launch_cast(h0 + (size_t)l * B * H, ws + L.h_all, (int64_t)B * H, dt, st))) return rc;
-    } else {
-      CSN_HIP_CHECK(hipMemsetAsync(ws + L.h_all, 0, (size_t)B * H * es, st));
-    }
-    if (c0)
-      CSN_HIP_CHECK(hipMemcpyAsync(ws + L.c_all, c0 + (size_t)l * B * H, (size_t)B * H * 4, hipMemcpyDeviceToDevice, st));
-    else
-      CSN_HIP_CHECK(hipMemsetAsync(ws + L.c_all, 0, (size_t)B * H * 4, st));
-  }
+  if ((rc = prep_row_major(C, A))) return rc;
   // layer 0: projection of every step in one GEMM
-  if ((rc = gemm_nt(ws + w.x_c, ws + w.layer[0].wih, (const float*)(ws + w.layer[0].bias), ws + w.layer[0].xproj, TB, G,
-                    d->I, dt, CSN_F32, 0, st, P.opt)))
+  if ((rc = gemm_nt(ws + w.x_c, ws + w.layer[0].wih, (const float*)(ws + w.layer[0].bias), ws + w.layer[0].xproj, C.TB, G,
+                    C.d.I, dt, CSN_F32, 0, st, C.P.opt)))
     return rc;
   const int D = T + lag * (NL - 1);
   for (int dg = 0; dg < D; ++dg) {
@@ -814,42 +998,31 @@ static int forward_v1(Plan& P, char* ws, const float* x, int64_t xsb, int64_t xs
     // a layer that just finished a chunk feeds the next layer's input projection
     for (int l = 0; l + 1 < NL; ++l) {
       const int t = dg - lag * l;
-      if (t < 0 || t >= T || ((t + 1) % Cz != 0 && t != T - 1)) continue;
-      const int t0 = (t / Cz) * Cz, nsteps = t - t0 + 1;
-      const LayerWs& Ln = w.layer[l + 1];
-      if ((rc = gemm_nt(ws + w.layer[l].h_all + (size_t)(t0 + 1) * B * H * es, ws + Ln.wih, (const float*)(ws + Ln.bias),
-                        (float*)(ws + Ln.xproj) + (size_t)t0 * B * G, (int64_t)nsteps * B, G, H, dt, CSN_F32, 0, st, P.opt)))
-        return rc;
+      if (t < 0 || t >= T || !ends_chunk(C, t)) continue;
+      if ((rc = xproj_chunk_gemm(C, l, t / C.Cz, st))) return rc;
     }
   }
   return CSN_OK;
 }
 
-static int backward_v1(Plan& P, char* ws, const float* dy_last, const float* dy_tm, const float* dh_n, const float* dc_n,
-                       float* const* dw_ih, float* const* dw_hh, float* const* db_ih, float* const* db_hh, float* dx,
-                       csnStream_t stream) {
-  const csnLstmDesc* d = &P.d;
-  const WsLayout& w = P.w;
-  hipStream_t st = as_stream(stream);
-  const int B = d->B, T = d->T, H = d->H, dt = d->dtype, NL = d->L;
-  const int64_t G = 4 * (int64_t)H, TB = (int64_t)T * B;
-  const size_t es = dtype_size(dt);
-  const int Cz = P.opt.chunk, lag = Cz;
-  const int acc = P.grad_accumulate;
+static int backward_v1(Call& C, const BwdArgs& A) {
+  const WsLayout& w = C.w;
+  char* ws = C.ws;
+  hipStream_t st = C.st;
+  const int B = C.B, T = C.T, H = C.H, dt = C.dt, NL = C.NL;
+  const int64_t G = C.G;
+  const size_t es = C.es;
+  const int lag = C.Cz;
   int rc;
-  for (int l = 0; l < NL; ++l) {
-    if (dc_n)      // the carried dc starts as the gradient w.r.t. c_n; after step 0 it is the gradient w.r.t. c0
-      CSN_HIP_CHECK(hipMemcpyAsync(ws + w.layer[l].dc_carry, dc_n + (size_t)l * B * H, (size_t)B * H * 4, hipMemcpyDeviceToDevice, st));
-    else
-      CSN_HIP_CHECK(hipMemsetAsync(ws + w.layer[l].dc_carry, 0, (size_t)B * H * 4, st));
-  }
+  for (int l = 0; l < NL; ++l)
+    if ((rc = seed_dc_carry(C, l, A.dc_n, false))) return rc;
   // diagonal d: layer l at reverse step d - lag * (L - 1 - l); the gradient w.r.t. a layer's input (= dy of the layer
   // below) follows chunk by chunk
   const int D = T + lag * (NL - 1);
   for (int dg = 0; dg < D; ++dg) {
     CellBwdBatch b{};
-    CellMask mask{P.dlen, {0, 0, 0, 0}};
-    const CellMask* mk = P.dlen ? &mask : nullptr;
+    CellMask mask{C.dlen, {0, 0, 0, 0}};
+    const CellMask* mk = C.dlen ? &mask : nullptr;
     int np = 0;
     for (int l = NL - 1; l >= 0; --l) {
       const int r = dg - lag * (NL - 1 - l);
@@ -862,7 +1035,7 @@ static int backward_v1(Plan& P, char* ws, const float* dy_last, const float* dy_
         np = 0;
       }
       mask.t[np] = t;
-      const float* dy_t = top ? (dy_tm ? dy_tm + (size_t)t * B * H : (t == T - 1 ? dy_last : nullptr))
+      const float* dy_t = top ? (A.dy_tm ? A.dy_tm + (size_t)t * B * H : (t == T - 1 ? A.dy_last : nullptr))
                               : (const float*)(ws + w.layer[l + 1].dx) + (size_t)t * B * H;
       b.p[np++] = CellBwdOne{(t == T - 1) ? nullptr : (const void*)(ws + L.dgates + (size_t)(t + 1) * B * G * es), ws + L.whht, dy_t, H,
                              ws + L.gates + (size_t)t * B * G * es, (const float*)(ws + L.c_all) + (size_t)(t + 1) * B * H,
@@ -872,75 +1045,44 @@ static int backward_v1(Plan& P, char* ws, const float* dy_last, const float* dy_
     if (np > 0 && (rc = launch_cell_bwd_batch(b, np, B, H, dt, st, mk))) return rc;
     for (int l = NL - 1; l >= 1; --l) {
       const int r = dg - lag * (NL - 1 - l);
-      if (r < 0 || r >= T || ((r + 1) % Cz != 0 && r != T - 1)) continue;
-      const int t_lo = T - 1 - r, t_hi = T - 1 - (r / Cz) * Cz;       // steps of this reverse chunk
-      const LayerWs& L = w.layer[l];
-      if ((rc = gemm_nt(ws + L.dgates + (size_t)t_lo * B * G * es, ws + L.wiht, nullptr, (float*)(ws + L.dx) + (size_t)t_lo * B * H,
-                        (int64_t)(t_hi - t_lo + 1) * B, H, G, dt, CSN_F32, 0, st, P.opt)))
-        return rc;
-      // gradient w.r.t. h_n of the layer below joins its dy at t = T-1 (with lengths: at each row's last step)
-      if (dh_n && (rc = add_dh_n_rows(P, dh_n + (size_t)(l - 1) * B * H, (float*)(ws + L.dx), t_lo, t_hi, st))) return rc;
+      if (r < 0 || r >= T || !ends_chunk(C, r)) continue;
+      if ((rc = dx_chunk_gemm(C, l, r / C.Cz, A.dh_n, st))) return rc;
     }
   }
   for (int l = NL - 1; l >= 0; --l) {
-    const LayerWs& L = w.layer[l];
-    const int64_t I = l == 0 ? d->I : H;
-    const void* inp = l == 0 ? (const void*)(ws + w.x_c)
-                             : (const void*)(ws + w.layer[l - 1].h_all + (size_t)B * H * es);
-    if ((rc = gemm_tn_full(ws + L.dgates, ws + L.h_all, dw_hh[l], G, H, TB, dt, ws + w.tn_scratch, acc, st, P.opt))) return rc;
-    if ((rc = gemm_tn_full(ws + L.dgates, inp, dw_ih[l], G, I, TB, dt, ws + w.tn_scratch, acc, st, P.opt))) return rc;
-    // db_ih and db_hh both come out of the reduction (each adds to its own previous contents under CSN_GRAD_ACCUMULATE)
-    if ((rc = launch_colsum(ws + L.dgates, TB, G, dt, db_ih[l], db_hh[l], acc, ws + w.colsum, st))) return rc;
-    P.grads_ready(l);
+    if ((rc = weight_grads_rm(C, A, l, true))) return rc;
+    C.P.grads_ready(l);
   }
-  if (dx) {
-    const LayerWs& L = w.layer[0];
-    if ((rc = gemm_nt(ws + L.dgates, ws + L.wiht, nullptr, ws + L.dx, TB, d->I, G, dt, CSN_F32, 0, st, P.opt))) return rc;
-    if ((rc = emit_dx(P, (const float*)(ws + L.dx), dx, d->I, st))) return rc;
-  }
+  if (A.dx) return dx_out(C, A.dx, st);
   return CSN_OK;
 }
 
-// Exact-float32 path, weight-stationary (lstm_f32_persist.hip): layer after layer, ONE recurrence launch per layer and
-// block of M-tiles, the non-recurrent contractions as whole-sequence GEMMs between them (the same GEMM kernels, the same
-// K order per output element as the chunked calls of forward_v1: row chunking does not enter a row's sum).
-static int forward_f32p(Plan& P, char* ws, const float* x, int64_t xsb, int64_t xst,
-                        const float* const* w_ih, const float* const* w_hh, const float* const* b_ih,
-                        const float* const* b_hh, int training, csnStream_t stream) {
-  const csnLstmDesc* d = &P.d;
-  const WsLayout& w = P.w;
-  Prof& g_prof = P.prof;
-  hipStream_t st = as_stream(stream);
-  const int B = d->B, T = d->T, H = d->H, NL = d->L;
-  const int64_t G = 4 * (int64_t)H, TB = (int64_t)T * B;
+// =============================================================================================
+// path 4: exact float32, weight-stationary (lstm_f32_persist.hip)
+// =============================================================================================
+// Layer after layer, ONE recurrence launch per layer and block of M-tiles, the non-recurrent contractions as
+// whole-sequence GEMMs between them (the same GEMM kernels, the same K order per output element as the chunked calls of
+// forward_v1: row chunking does not enter a row's sum).
+static int forward_f32p(Call& C, const FwdArgs& A) {
+  const WsLayout& w = C.w;
+  Prof& g_prof = C.P.prof;
+  char* ws = C.ws;
+  hipStream_t st = C.st;
+  const int B = C.B, T = C.T, H = C.H, NL = C.NL;
   const int MTt = (B + 63) / 64, per = f32_persist_tiles_per_launch(H);
   int rc;
-  if ((rc = launch_cast_strided(x, xsb, xst, B, T, d->I, ws + w.x_c, CSN_F32, st))) return rc;
-  for (int l = 0; l < NL; ++l) {
-    const LayerWs& L = w.layer[l];
-    const int64_t I = l == 0 ? d->I : H;
-    if ((rc = launch_cast(w_ih[l], ws + L.wih, G * I, CSN_F32, st))) return rc;
-    if ((rc = launch_cast(w_hh[l], ws + L.whh, G * H, CSN_F32, st))) return rc;
-    if (training) {
-      if ((rc = launch_transpose_cast(w_hh[l], G, H, ws + L.whht, CSN_F32, st))) return rc;
-      if ((rc = launch_transpose_cast(w_ih[l], G, I, ws + L.wiht, CSN_F32, st))) return rc;
-    }
-    if ((rc = launch_add_vec(b_ih[l], b_hh[l], (float*)(ws + L.bias), G, st))) return rc;
-    CSN_HIP_CHECK(hipMemsetAsync(ws + L.h_all, 0, (size_t)B * H * 4, st));
-    CSN_HIP_CHECK(hipMemsetAsync(ws + L.c_all, 0, (size_t)B * H * 4, st));
-  }
+  if ((rc = prep_row_major(C, A))) return rc;
   CSN_HIP_CHECK(hipMemsetAsync(ws + w.zero_fwd, 0, w.zero_fwd_bytes, st));      // the flag lines of every layer
   int n_launch = 0;
   if ((rc = prof_mark(g_prof, 0, st))) return rc;
   for (int l = 0; l < NL; ++l) {
     const LayerWs& L = w.layer[l];
-    const void* inp = l == 0 ? (const void*)(ws + w.x_c) : (const void*)(ws + w.layer[l - 1].h_all + (size_t)B * H * 4);
-    if ((rc = gemm_nt(inp, ws + L.wih, (const float*)(ws + L.bias), ws + L.xproj, TB, G, l == 0 ? d->I : H, CSN_F32, CSN_F32, 0, st, P.opt)))
+    if ((rc = gemm_nt(layer_input(C, l), ws + L.wih, (const float*)(ws + L.bias), ws + L.xproj, C.TB, C.G, C.in_width(l), CSN_F32, CSN_F32, 0, st, C.P.opt)))
       return rc;
     F32PersistFwdArgs a{};
     a.w_hh = (const float*)(ws + L.whh);
     a.xproj = (const float*)(ws + L.xproj);
-    a.gates = training ? (float*)(ws + L.gates) : nullptr;
+    a.gates = C.P.training ? (float*)(ws + L.gates) : nullptr;
     a.c_all = (float*)(ws + L.c_all);
     a.h_all = (float*)(ws + L.h_all);
     a.h_blk = (float*)(ws + L.h_blk_all);
@@ -956,22 +1098,16 @@ static int forward_f32p(Plan& P, char* ws, const float* x, int64_t xsb, int64_t 
       ++n_launch;
     }
   }
-  if ((rc = prof_mark(g_prof, 1, st))) return rc;
-  g_prof.launches[0] = n_launch;
-  g_prof.cells[0] = T * NL;
-  g_prof.have[0] = g_prof.on;
-  return CSN_OK;
+  return prof_end(C, 0, n_launch, T * NL);
 }
 
-static int backward_f32p(Plan& P, char* ws, const float* dy_last, const float* dy_tm,
-                         float* const* dw_ih, float* const* dw_hh, float* const* db_ih, float* const* db_hh, float* dx,
-                         csnStream_t stream) {
-  const csnLstmDesc* d = &P.d;
-  const WsLayout& w = P.w;
-  Prof& g_prof = P.prof;
-  hipStream_t st = as_stream(stream);
-  const int B = d->B, T = d->T, H = d->H, NL = d->L;
-  const int64_t G = 4 * (int64_t)H, TB = (int64_t)T * B;
+static int backward_f32p(Call& C, const BwdArgs& A) {
+  const WsLayout& w = C.w;
+  Prof& g_prof = C.P.prof;
+  char* ws = C.ws;
+  hipStream_t st = C.st;
+  const int B = C.B, T = C.T, H = C.H, NL = C.NL;
+  const int64_t G = C.G;
   const int MTt = (B + 63) / 64, per = f32_persist_tiles_per_launch(H);
   int rc;
   CSN_HIP_CHECK(hipMemsetAsync(ws + w.zero_bwd, 0, w.zero_bwd_bytes, st));
@@ -984,8 +1120,8 @@ static int backward_f32p(Plan& P, char* ws, const float* dy_last, const float* d
     a.w_hh_t = (const float*)(ws + L.whht);
     a.gates = (const float*)(ws + L.gates);
     a.c_all = (const float*)(ws + L.c_all);
-    a.dy = top ? dy_tm : (const float*)(ws + w.layer[l + 1].dx);
-    a.dy_last = (top && dy_tm == nullptr) ? dy_last : nullptr;
+    a.dy = top ? A.dy_tm : (const float*)(ws + w.layer[l + 1].dx);
+    a.dy_last = (top && A.dy_tm == nullptr) ? A.dy_last : nullptr;
     a.zeros = (const float*)(ws + w.zeros_bh);
     a.dgates = (float*)(ws + L.dgates);
     a.dg_blk = (float*)(ws + L.dg_blk_all);
@@ -1002,54 +1138,34 @@ static int backward_f32p(Plan& P, char* ws, const float* dy_last, const float* d
       ++n_launch;
     }
     // bias gradients: the row groups' partial sums in fixed order (db_ih = db_hh)
-    sum_rows_kernel<<<(unsigned)((G + 255) / 256), 256, 0, st>>>((const float*)(ws + w.f32_bias_part), MTt * 4, G, db_ih[l], db_hh[l], P.grad_accumulate);
+    sum_rows_kernel<<<(unsigned)((G + 255) / 256), 256, 0, st>>>((const float*)(ws + w.f32_bias_part), MTt * 4, G, A.db_ih[l], A.db_hh[l], C.P.grad_accumulate);
     CSN_LAUNCH_CHECK();
     // gradient w.r.t. this layer's input = dy of the layer below, whole sequence
-    if (l > 0 && (rc = gemm_nt(ws + L.dgates, ws + L.wiht, nullptr, ws + L.dx, TB, H, G, CSN_F32, CSN_F32, 0, st, P.opt))) return rc;
+    if (l > 0 && (rc = gemm_nt(ws + L.dgates, ws + L.wiht, nullptr, ws + L.dx, C.TB, H, G, CSN_F32, CSN_F32, 0, st, C.P.opt))) return rc;
   }
-  if ((rc = prof_mark(g_prof, 3, st))) return rc;
-  g_prof.launches[1] = n_launch;
-  g_prof.cells[1] = T * NL;
-  g_prof.have[1] = g_prof.on;
+  if ((rc = prof_end(C, 1, n_launch, T * NL))) return rc;
   for (int l = NL - 1; l >= 0; --l) {
-    const LayerWs& L = w.layer[l];
-    const int64_t I = l == 0 ? d->I : H;
-    const void* inp = l == 0 ? (const void*)(ws + w.x_c) : (const void*)(ws + w.layer[l - 1].h_all + (size_t)B * H * 4);
-    if ((rc = gemm_tn_full(ws + L.dgates, ws + L.h_all, dw_hh[l], G, H, TB, CSN_F32, ws + w.tn_scratch, P.grad_accumulate, st, P.opt))) return rc;
-    if ((rc = gemm_tn_full(ws + L.dgates, inp, dw_ih[l], G, I, TB, CSN_F32, ws + w.tn_scratch, P.grad_accumulate, st, P.opt))) return rc;
-    P.grads_ready(l);
+    if ((rc = weight_grads_rm(C, A, l, false))) return rc;
+    C.P.grads_ready(l);
   }
-  if (dx) {
-    const LayerWs& L = w.layer[0];
-    if ((rc = gemm_nt(ws + L.dgates, ws + L.wiht, nullptr, ws + L.dx, TB, d->I, G, CSN_F32, CSN_F32, 0, st, P.opt))) return rc;
-    tb_to_bt_kernel<<<grid_for(TB * d->I), 256, 0, st>>>((const float*)(ws + L.dx), dx, B, T, d->I);
-    CSN_LAUNCH_CHECK();
-  }
+  if (A.dx) return dx_out(C, A.dx, st);
   return CSN_OK;
 }
 
 // =============================================================================================
-// il fast path (wavefront over layers, GEMMs on the side stream)
+// paths 1 - 3: bf16 fast paths, every 4H axis gate-interleaved (lstm_cell_blk.hip and the weight-stationary kernels)
 // =============================================================================================
-static int forward_persist(Plan& P, char* ws, const float* h0, const float* c0, int training, hipStream_t st, SideCtx* sc,
-                           hipStream_t side);
-
-static int forward_il(Plan& P, char* ws, const float* x, int64_t xsb, int64_t xst,
-                      const float* const* w_ih, const float* const* w_hh, const float* const* b_ih,
-                      const float* const* b_hh, const float* h0, const float* c0, int training, csnStream_t stream) {
-  const csnLstmDesc* d = &P.d;
-  const WsLayout& w = P.w;
-  Prof& g_prof = P.prof;
-  hipStream_t st = as_stream(stream);
-  SideCtx* sc = &P.sc;
-  int rc;
-  if ((rc = side_ctx(P.sc))) return rc;
-  hipStream_t side = P.opt.no_side_stream ? st : sc->side;
-  const int B = d->B, T = d->T, H = d->H, NL = d->L;
-  const int64_t G = 4 * (int64_t)H, TB = (int64_t)T * B;
+// Layout preparation of both fast forwards: time-major x, permuted / fragment-major parameters, bias sums, the zeroed
+// hand-off buffers of the per-diagonal path, and layer 0's input projection unless the recurrence kernel multiplies x itself
+static int prep_fast(Call& C, const FwdArgs& A) {
+  const csnLstmDesc& d = C.d;
+  const WsLayout& w = C.w;
+  char* ws = C.ws;
+  hipStream_t st = C.st;
+  const int B = C.B, T = C.T, H = C.H, NL = C.NL;
+  const int64_t G = C.G, TB = C.TB;
   const size_t Bpad = ((size_t)B + 63) / 64 * 64;
-  const int Cz = P.opt.chunk, lag = 2 * Cz;
-
+  int rc;
   // all layout preparation in one launch (prep_multi_kernel); a training plan with more than 6 layers has more jobs
   // than one launch holds (1 + 5 L): a full batch is launched and a new one started -- the jobs are independent
   PrepArgs pa{};
@@ -1064,57 +1180,67 @@ static int forward_il(Plan& P, char* ws, const float* x, int64_t xsb, int64_t xs
     PrepJob& J = pa.job[pa.njobs++];
     J = PrepJob{kind, a_, b_, dst, n0, n1, n2, s0, s1, Hh, pr, pk, work, 0u, 0u};
   };
-  job(kPrepCastX, x, nullptr, ws + w.x_c, B, T, d->I, xsb, xst, 0, 0, 0, TB * d->I);
+  job(kPrepCastX, A.x, nullptr, ws + w.x_c, B, T, d.I, A.xsb, A.xst, 0, 0, 0, TB * d.I);
   for (int l = 0; l < NL; ++l) {
     const LayerWs& L = w.layer[l];
-    const int64_t I = l == 0 ? d->I : H;
-    job(kPrepPermRows, w_ih[l], nullptr, ws + L.wih, 0, I, 0, 0, 0, H, 0, 0, G * I);
-    job(kPrepBlockify, w_hh[l], nullptr, ws + L.whh_blk, G, H, 0, H, 1, H, 1, 0, G * H / 8);
-    job(kPrepBias, b_ih[l], b_hh[l], ws + L.bias, 0, 0, 0, 0, 0, H, 0, 0, G);
-    if (training) {
-      job(kPrepTransPerm, w_ih[l], nullptr, ws + L.wiht, 0, I, 0, 0, 0, H, 0, 0, G * I);
+    const int64_t I = C.in_width(l);
+    job(kPrepPermRows, A.w_ih[l], nullptr, ws + L.wih, 0, I, 0, 0, 0, H, 0, 0, G * I);
+    job(kPrepBlockify, A.w_hh[l], nullptr, ws + L.whh_blk, G, H, 0, H, 1, H, 1, 0, G * H / 8);
+    job(kPrepBias, A.b_ih[l], A.b_hh[l], ws + L.bias, 0, 0, 0, 0, 0, H, 0, 0, G);
+    if (C.P.training) {
+      job(kPrepTransPerm, A.w_ih[l], nullptr, ws + L.wiht, 0, I, 0, 0, 0, H, 0, 0, G * I);
       // W_hh^T [H rows = unit][k' = 4u'+g]: element (u, k') = W_hh[std_row(k')][u]
-      job(kPrepBlockify, w_hh[l], nullptr, ws + L.whht_blk, H, G, 0, 1, H, H, 0, 1, H * G / 8);
+      job(kPrepBlockify, A.w_hh[l], nullptr, ws + L.whht_blk, H, G, 0, 1, H, H, 0, 1, H * G / 8);
     }
     if (!w.persist) {       // ping-pong hand-off buffers of the per-timestep launches
       CSN_HIP_CHECK(hipMemsetAsync(ws + L.hblk[0], 0, Bpad * H * 2, st));
       CSN_HIP_CHECK(hipMemsetAsync(ws + L.hblk[1], 0, Bpad * H * 2, st));
-      // (weight-stationary paths: slot 0 is never written, csn_lstm_workspace_init zeroed it)
-      CSN_HIP_CHECK(hipMemsetAsync(ws + L.h_all, 0, (size_t)B * H * 2, st));
-      CSN_HIP_CHECK(hipMemsetAsync(ws + L.c_all, 0, (size_t)B * H * 4, st));
-      // initial state (CSN_LSTM_STATE plans, never weight-stationary): bf16 h0 fragment-major into the ping-pong buffer
-      // step 0 reads, and row-major into h_all slot 0 for the dW_hh GEMM; c0 into c_all slot 0 (behind the memsets)
-      if (h0) {
-        if ((rc = launch_blockify_x(h0 + (size_t)l * B * H, H, 0, B, 1, H, ws + L.hblk[0], st))) return rc;
-        if ((rc = launch_cast(h0 + (size_t)l * B * H, ws + L.h_all, (int64_t)B * H, CSN_BF16, st))) return rc;
-      }
-      if (c0)
-        CSN_HIP_CHECK(hipMemcpyAsync(ws + L.c_all, c0 + (size_t)l * B * H, (size_t)B * H * 4, hipMemcpyDeviceToDevice, st));
+      // initial state (CSN_LSTM_STATE plans): bf16 h0 fragment-major into the ping-pong buffer step 0 reads, behind its
+      // memset.  (weight-stationary paths: forward_persist installs the state; a stateless plan never writes slot 0,
+      // csn_lstm_workspace_init zeroed it)
+      if (A.h0 && (rc = launch_blockify_x(A.h0 + (size_t)l * B * H, H, 0, B, 1, H, ws + L.hblk[0], st))) return rc;
+      if ((rc = install_slot0(C, l, A.h0, A.c0))) return rc;
     }
   }
   if (w.fuse_x) {
     // layer 0 multiplies x_t itself inside the weight-stationary kernel: fragment-major x and W_ih instead of
     // a [T, B, 4H] float32 projection written to and re-read from HBM
-    job(kPrepBlockifyX, x, nullptr, ws + w.x_blk, B, T, d->I, xsb, xst, (int64_t)Bpad, 0, 0, (int64_t)T * Bpad * d->I / 8);
-    job(kPrepBlockify, w_ih[0], nullptr, ws + w.wih0_blk, G, d->I, 0, d->I, 1, H, 1, 0, G * d->I / 8);
+    job(kPrepBlockifyX, A.x, nullptr, ws + w.x_blk, B, T, d.I, A.xsb, A.xst, (int64_t)Bpad, 0, 0, (int64_t)T * Bpad * d.I / 8);
+    job(kPrepBlockify, A.w_ih[0], nullptr, ws + w.wih0_blk, G, d.I, 0, d.I, 1, H, 1, 0, G * d.I / 8);
   }
   if (prep_rc != CSN_OK) return prep_rc;
   if ((rc = launch_prep_multi(pa, st))) return rc;
-  if ((rc = mask_x(P, ws, st))) return rc;
+  if ((rc = mask_x(C, st))) return rc;
   if (!w.fuse_x) {
     // layer 0 input projection for every step, main stream
     if ((rc = gemm_nt(ws + w.x_c, ws + w.layer[0].wih, (const float*)(ws + w.layer[0].bias), ws + w.layer[0].xproj,
-                          TB, G, d->I, CSN_BF16, CSN_F32, 0, st, P.opt)))
+                      TB, G, d.I, CSN_BF16, CSN_F32, 0, st, C.P.opt)))
       return rc;
   }
-  if (w.persist) return forward_persist(P, ws, h0, c0, training, st, sc, side);
+  return CSN_OK;
+}
+
+// Path 1, per-diagonal cells: the WAVEFRONT of the file header, lag = 2 chunks, input projections on the side stream
+static int forward_il(Call& C, const FwdArgs& A) {
+  const WsLayout& w = C.w;
+  char* ws = C.ws;
+  hipStream_t st = C.st;
+  SideCtx* sc = &C.P.sc;
+  int rc;
+  if ((rc = side_ctx(C.P.sc))) return rc;
+  hipStream_t side = C.P.opt.no_side_stream ? st : sc->side;
+  const int B = C.B, T = C.T, H = C.H, NL = C.NL;
+  const int64_t G = C.G;
+  const int Cz = C.Cz, lag = 2 * Cz;
+  const int training = C.P.training;
+  if ((rc = prep_fast(C, A))) return rc;
   if (NL > 1 && (rc = hand_off(sc, st, side))) return rc;   // side stream sees the prepared weights
 
   const int nch = (T + Cz - 1) / Cz;
   std::vector<hipEvent_t> xproj_ready((size_t)NL * nch, nullptr);
   const int D = T + lag * (NL - 1);
   int n_launch = 0, n_cells = 0;
-  if ((rc = prof_mark(g_prof, 0, st))) return rc;
+  if ((rc = prof_mark(C.P.prof, 0, st))) return rc;
   for (int dg = 0; dg < D; ++dg) {
     CellFwdArgs a{};
     a.B = B;
@@ -1125,52 +1251,43 @@ static int forward_il(Plan& P, char* ws, const float* x, int64_t xsb, int64_t xs
       if (t < 0 || t >= T) continue;
       const LayerWs& L = w.layer[l];
       if (np == 4) {       // (more than 4 layers on one diagonal, L >= 5: a second launch, the problems are independent)
-        if ((rc = launch_cell_fwd_il(a, np, st, P.opt.fwd_nk))) return rc;
+        if ((rc = launch_cell_fwd_il(a, np, st))) return rc;
         ++n_launch;
         n_cells += np;
         np = 0;
       }
       if (l > 0 && t % Cz == 0) CSN_HIP_CHECK(hipStreamWaitEvent(st, xproj_ready[(size_t)l * nch + t / Cz], 0));
-      CellFwdProb& P = a.p[np++];
-      P.h_prev_blk = (t == 0 && !h0) ? nullptr : (const bf16_t*)(ws + L.hblk[t & 1]);
-      P.w_blk = (const bf16_t*)(ws + L.whh_blk);
-      P.xproj = (const float*)(ws + L.xproj) + (size_t)t * B * G;
-      P.c_prev = (t == 0 && !c0) ? nullptr : (const float*)(ws + L.c_all) + (size_t)t * B * H;
-      P.gates_out = training ? (bf16_t*)(ws + L.gates) + (size_t)t * B * G : nullptr;
-      P.c_out = (float*)(ws + L.c_all) + (size_t)(t + 1) * B * H;
-      P.h_out = (bf16_t*)(ws + L.h_all) + (size_t)(t + 1) * B * H;
-      P.h_out_blk = (bf16_t*)(ws + L.hblk[(t + 1) & 1]);
+      CellFwdProb& q = a.p[np++];
+      q.h_prev_blk = (t == 0 && !A.h0) ? nullptr : (const bf16_t*)(ws + L.hblk[t & 1]);
+      q.w_blk = (const bf16_t*)(ws + L.whh_blk);
+      q.xproj = (const float*)(ws + L.xproj) + (size_t)t * B * G;
+      q.c_prev = (t == 0 && !A.c0) ? nullptr : (const float*)(ws + L.c_all) + (size_t)t * B * H;
+      q.gates_out = training ? (bf16_t*)(ws + L.gates) + (size_t)t * B * G : nullptr;
+      q.c_out = (float*)(ws + L.c_all) + (size_t)(t + 1) * B * H;
+      q.h_out = (bf16_t*)(ws + L.h_all) + (size_t)(t + 1) * B * H;
+      q.h_out_blk = (bf16_t*)(ws + L.hblk[(t + 1) & 1]);
     }
     if (np == 0) continue;
-    if ((rc = launch_cell_fwd_il(a, np, st, P.opt.fwd_nk))) return rc;
+    if ((rc = launch_cell_fwd_il(a, np, st))) return rc;
     ++n_launch;
     n_cells += np;
     // a layer that just finished a chunk feeds the next layer's input projection (side stream)
     for (int l = 0; l + 1 < NL; ++l) {
       const int t = dg - lag * l;
-      if (t < 0 || t >= T) continue;
-      if ((t + 1) % Cz != 0 && t != T - 1) continue;
-      const int c = t / Cz, t0 = c * Cz, nsteps = t - t0 + 1;
+      if (t < 0 || t >= T || !ends_chunk(C, t)) continue;
+      const int c = t / Cz;
       if ((rc = hand_off(sc, st, side))) return rc;
-      const LayerWs& Ln = w.layer[l + 1];
-      rc = gemm_nt((const bf16_t*)(ws + w.layer[l].h_all) + (size_t)(t0 + 1) * B * H, ws + Ln.wih,
-                       (const float*)(ws + Ln.bias), (float*)(ws + Ln.xproj) + (size_t)t0 * B * G,
-                       (int64_t)nsteps * B, G, H, CSN_BF16, CSN_F32, 0, side, P.opt);
-      if (rc) return rc;
+      if ((rc = xproj_chunk_gemm(C, l, c, side))) return rc;
       hipEvent_t ev;
       if ((rc = next_event(sc, &ev))) return rc;
       CSN_HIP_CHECK(hipEventRecord(ev, side));
       xproj_ready[(size_t)(l + 1) * nch + c] = ev;
     }
   }
-  if ((rc = prof_mark(g_prof, 1, st))) return rc;
-  g_prof.launches[0] = n_launch;
-  g_prof.cells[0] = n_cells;
-  g_prof.have[0] = g_prof.on;
-  return CSN_OK;
+  return prof_end(C, 0, n_launch, n_cells);
 }
 
-// Weight-stationary forward (lstm_fwd_persist.hip).
+// Paths 2 and 3, weight-stationary forward (lstm_fwd_persist.hip, lstm_fwd_ns.hip).
 //
 // Grouped form (the fast one, taken when slots * M-tiles <= 8): ONE launch per chunk diagonal advances layer
 // l through chunk (dg - l) for every layer in range -- at cfg2 two layers x four 64-row M-tiles = 8 hand-off
@@ -1181,17 +1298,24 @@ static int forward_il(Plan& P, char* ws, const float* x, int64_t xsb, int64_t xs
 //
 // Stream form (any number of layers / M-tiles): layer l runs chunk after chunk on its own stream, the GEMMs
 // on the side stream, ordered by events; placement-independent hand-off.
-static int forward_persist(Plan& P, char* ws, const float* h0, const float* c0, int training, hipStream_t st, SideCtx* sc,
-                           hipStream_t side) {
-  const csnLstmDesc* d = &P.d;
-  const WsLayout& w = P.w;
+static int forward_persist(Call& C, const FwdArgs& A) {
+  Plan& P = C.P;
+  const WsLayout& w = C.w;
   Prof& g_prof = P.prof;
-  const int B = d->B, T = d->T, H = d->H, NL = d->L;
-  const int64_t G = 4 * (int64_t)H;
-  const int Bpad = (B + 63) / 64 * 64, MT = Bpad / 64;
-  const int Cz = P.opt.chunk;
-  const int nch = (T + Cz - 1) / Cz;
+  char* ws = C.ws;
+  hipStream_t st = C.st;
+  SideCtx* sc = &P.sc;
   int rc;
+  if ((rc = side_ctx(P.sc))) return rc;
+  hipStream_t side = P.opt.no_side_stream ? st : sc->side;
+  const float* h0 = A.h0;
+  const float* c0 = A.c0;
+  const int B = C.B, T = C.T, H = C.H, NL = C.NL;
+  const int Bpad = (B + 63) / 64 * 64, MT = Bpad / 64;
+  const int Cz = C.Cz;
+  const int nch = (T + Cz - 1) / Cz;
+  const int training = P.training;
+  if ((rc = prep_fast(C, A))) return rc;
   // one fill: the flag lines of every layer, the XCD agreement words
   CSN_HIP_CHECK(hipMemsetAsync(ws + w.zero_fwd, 0, w.zero_fwd_bytes, st));
   auto fill_slot = [&](PersistFwdSlot& S, int l, int c) {
@@ -1211,18 +1335,11 @@ static int forward_persist(Plan& P, char* ws, const float* h0, const float* c0, 
       S.x_blk = (const bf16_t*)(ws + w.x_blk);
       S.wih_blk = (const bf16_t*)(ws + w.wih0_blk);
       S.bias = (const float*)(ws + L.bias);
-      S.I = d->I;
+      S.I = C.d.I;
     }
-    S.t0 = c * Cz;
-    S.nsteps = (S.t0 + Cz <= T) ? Cz : T - S.t0;
-  };
-  auto xproj_gemm = [&](int l, int c, hipStream_t on) {   // layer l finished chunk c -> xproj_{l+1}[chunk c]
-    const LayerWs& L = w.layer[l];
-    const LayerWs& Ln = w.layer[l + 1];
-    const int t0 = c * Cz, nsteps = (t0 + Cz <= T) ? Cz : T - t0;
-    return gemm_nt((const bf16_t*)(ws + L.h_all) + (size_t)(t0 + 1) * B * H, ws + Ln.wih,
-                       (const float*)(ws + Ln.bias), (float*)(ws + Ln.xproj) + (size_t)t0 * B * G,
-                       (int64_t)nsteps * B, G, H, CSN_BF16, CSN_F32, 0, on, P.opt);
+    const Chunk k = chunk_at(C, c);
+    S.t0 = k.t0;
+    S.nsteps = k.nsteps;
   };
   PersistFwdArgs a{};
   a.error_flag = (unsigned*)(ws + w.status);
@@ -1246,15 +1363,10 @@ static int forward_persist(Plan& P, char* ws, const float* h0, const float* c0, 
     const LayerWs& L = w.layer[l];
     if (h0) {
       if ((rc = launch_blockify_x(h0 + (size_t)l * B * H, H, 0, B, 1, H, ws + L.h_blk_all, st))) return rc;
-      if ((rc = launch_cast(h0 + (size_t)l * B * H, ws + L.h_all, (int64_t)B * H, CSN_BF16, st))) return rc;
-    } else {
-      if (a.state) CSN_HIP_CHECK(hipMemsetAsync(ws + L.h_blk_all, 0, (size_t)Bpad * H * 2, st));
-      CSN_HIP_CHECK(hipMemsetAsync(ws + L.h_all, 0, (size_t)B * H * 2, st));
+    } else if (a.state) {
+      CSN_HIP_CHECK(hipMemsetAsync(ws + L.h_blk_all, 0, (size_t)Bpad * H * 2, st));
     }
-    if (c0)
-      CSN_HIP_CHECK(hipMemcpyAsync(ws + L.c_all, c0 + (size_t)l * B * H, (size_t)B * H * 4, hipMemcpyDeviceToDevice, st));
-    else
-      CSN_HIP_CHECK(hipMemsetAsync(ws + L.c_all, 0, (size_t)B * H * 4, st));
+    if ((rc = install_slot0(C, l, h0, c0))) return rc;
   }
   int n_launch = 0;
   P.half_launches[0] = 0;
@@ -1297,13 +1409,9 @@ static int forward_persist(Plan& P, char* ws, const float* h0, const float* c0, 
       if ((rc = prof_pair(g_prof, 0, true, st))) return rc;
       ++n_launch;
       for (int i = 0; i < ns; ++i)      // layer l finished chunk c -> xproj_{l+1}[chunk c], before the next launch
-        if (lay[i] + 1 < NL && (rc = xproj_gemm(lay[i], chk[i], st))) return rc;
+        if (lay[i] + 1 < NL && (rc = xproj_chunk_gemm(C, lay[i], chk[i], st))) return rc;
     }
-    if ((rc = prof_mark(g_prof, 1, st))) return rc;
-    g_prof.launches[0] = n_launch;
-    g_prof.cells[0] = T * NL;
-    g_prof.have[0] = g_prof.on;
-    return CSN_OK;
+    return prof_end(C, 0, n_launch, T * NL);
   }
 
   // every launch needs ALL its workgroups resident (one per CU): layers on streams of their own may only run side
@@ -1316,7 +1424,6 @@ static int forward_persist(Plan& P, char* ws, const float* h0, const float* c0, 
     if (ls[l] != st && (rc = hand_off(sc, st, ls[l]))) return rc;
   }
   if (side != st && (rc = hand_off(sc, st, side))) return rc;
-  const bool gemm_slot = P.opt.gemm_slot;
   if ((rc = prof_mark(g_prof, 0, st))) return rc;
   a.nslots = 1;
   a.xcd_groups = 0;
@@ -1331,10 +1438,8 @@ static int forward_persist(Plan& P, char* ws, const float* h0, const float* c0, 
       if (l + 1 < NL) {
         // layer l finished chunk c -> GEMM xproj_{l+1}[chunk] on the side stream -> layer l+1 may start it
         if ((rc = hand_off(sc, ls[l], side))) return rc;
-        if ((rc = xproj_gemm(l, c, side))) return rc;
+        if ((rc = xproj_chunk_gemm(C, l, c, side))) return rc;
         if (side != ls[l + 1] && (rc = hand_off(sc, side, ls[l + 1]))) return rc;
-        // optional: the producing layer's next chunk also waits, so the GEMM runs in a slot of its own
-        if (gemm_slot && side != ls[l] && (rc = hand_off(sc, side, ls[l]))) return rc;
       }
     }
   }
@@ -1342,83 +1447,44 @@ static int forward_persist(Plan& P, char* ws, const float* h0, const float* c0, 
   for (int l = 1; l < NL; ++l)
     if (ls[l] != st && (rc = hand_off(sc, ls[l], st))) return rc;
   if (side != st && (rc = hand_off(sc, side, st))) return rc;
-  if ((rc = prof_mark(g_prof, 1, st))) return rc;
-  g_prof.launches[0] = n_launch;
-  g_prof.cells[0] = T * NL;
-  g_prof.have[0] = g_prof.on;
-  return CSN_OK;
+  return prof_end(C, 0, n_launch, T * NL);
 }
 
-static int backward_persist(Plan& P, char* ws, const float* dy_last, const float* dy_tm, const float* dh_n,
-                            const float* dc_n, float* const* dw_ih, float* const* dw_hh, float* const* db_ih,
-                            float* const* db_hh, float* dx, hipStream_t st);
-
-static int backward_il(Plan& P, char* ws, const float* dy_last, const float* dy_tm, const float* dh_n, const float* dc_n,
-                       float* const* dw_ih, float* const* dw_hh, float* const* db_ih, float* const* db_hh, float* dx,
-                       csnStream_t stream) {
-  const csnLstmDesc* d = &P.d;
-  const WsLayout& w = P.w;
-  Prof& g_prof = P.prof;
-  hipStream_t st = as_stream(stream);
-  if (bwd_grouped(&P)) return backward_persist(P, ws, dy_last, dy_tm, dh_n, dc_n, dw_ih, dw_hh, db_ih, db_hh, dx, st);
-  SideCtx* sc = &P.sc;
+// Paths 1 and 2, and path 3 where its grouped form does not apply: per-diagonal backward cells, lag = 2 chunks, the input
+// gradients and the weight gradients on the side stream
+static int backward_il(Call& C, const BwdArgs& A) {
+  const WsLayout& w = C.w;
+  char* ws = C.ws;
+  hipStream_t st = C.st;
+  SideCtx* sc = &C.P.sc;
   int rc;
-  if ((rc = side_ctx(P.sc))) return rc;
-  hipStream_t side = P.opt.no_side_stream ? st : sc->side;
-  const int B = d->B, T = d->T, H = d->H, NL = d->L;
-  const int64_t G = 4 * (int64_t)H, TB = (int64_t)T * B;
+  if ((rc = side_ctx(C.P.sc))) return rc;
+  hipStream_t side = C.P.opt.no_side_stream ? st : sc->side;
+  const int B = C.B, T = C.T, H = C.H, NL = C.NL;
+  const int64_t G = C.G;
   const size_t Bpad = ((size_t)B + 63) / 64 * 64;
-  const int Cz = P.opt.chunk, lag = 2 * Cz;
+  const int Cz = C.Cz, lag = 2 * Cz;
   const int nch = (T + Cz - 1) / Cz;
-  const bool state = P.state != 0;
+  const bool state = C.P.state != 0;
 
   for (int l = 0; l < NL; ++l) {
     const LayerWs& L = w.layer[l];
-    if (dc_n)      // the carried dc starts as the gradient w.r.t. c_n; after step 0 it is the gradient w.r.t. c0
-      CSN_HIP_CHECK(hipMemcpyAsync(ws + L.dc_carry, dc_n + (size_t)l * B * H, (size_t)B * H * 4, hipMemcpyDeviceToDevice, st));
-    else
-      CSN_HIP_CHECK(hipMemsetAsync(ws + L.dc_carry, 0, (size_t)B * H * 4, st));
+    if ((rc = seed_dc_carry(C, l, A.dc_n, false))) return rc;
     CSN_HIP_CHECK(hipMemsetAsync(ws + L.dgblk[0], 0, Bpad * G * 2, st));
     CSN_HIP_CHECK(hipMemsetAsync(ws + L.dgblk[1], 0, Bpad * G * 2, st));
   }
   if ((rc = hand_off(sc, st, side))) return rc;
 
-  // weight / bias gradients of one layer, on the side stream (after its recurrence is complete)
-  auto weight_grads = [&](int l) -> int {
-    const LayerWs& L = w.layer[l];
-    const int64_t I = l == 0 ? d->I : H;
-    const void* inp = l == 0 ? (const void*)(ws + w.x_c)
-                             : (const void*)((const bf16_t*)(ws + w.layer[l - 1].h_all) + (size_t)B * H);
-    float* slabs = (float*)(ws + w.tn_scratch);
-    const int acc = P.grad_accumulate;
-    int S = 1, r;
-    int cs_done = 0, S_cs = 1;
-    if ((r = launch_gemm_tn_slabs(ws + L.dgates, ws + L.h_all, slabs, G, H, TB, CSN_BF16, side, &S, (float*)(ws + w.colsum), &cs_done, P.opt))) return r;
-    S_cs = S;
-    if ((r = launch_reduce_slabs_unperm(slabs, G * H, S, H, H, dw_hh[l], nullptr, acc, side))) return r;
-    if ((r = launch_gemm_tn_slabs(ws + L.dgates, inp, slabs, G, I, TB, CSN_BF16, side, &S, nullptr, nullptr, P.opt))) return r;
-    if ((r = launch_reduce_slabs_unperm(slabs, G * I, S, H, I, dw_ih[l], nullptr, acc, side))) return r;
-    // bias gradient = column sums of dgates: partial sums come out of the dW_hh GEMM when its kernel provides them
-    if (!cs_done) {
-      if ((r = launch_colsum_partial(ws + L.dgates, TB, G, CSN_BF16, ws + w.colsum, side))) return r;
-      S_cs = colsum_chunks();
-    }
-    // db_ih and db_hh both come out of the reduction (each adds to its own previous contents under CSN_GRAD_ACCUMULATE)
-    if ((r = launch_reduce_slabs_unperm((const float*)(ws + w.colsum), G, S_cs, H, 1, db_ih[l], db_hh[l], acc, side)))
-      return r;
-    return CSN_OK;
-  };
-
   std::vector<hipEvent_t> dx_ready((size_t)NL * nch, nullptr);
   const int D = T + lag * (NL - 1);
   int n_launch = 0, n_cells = 0;
-  if ((rc = prof_mark(g_prof, 2, st))) return rc;
+  if ((rc = prof_mark(C.P.prof, 2, st))) return rc;
   for (int dg = 0; dg < D; ++dg) {
     CellBwdArgs a{};
     a.B = B;
     a.H = H;
-    CellMask mask{P.dlen, {0, 0, 0, 0}};
-    const CellMask* mk = P.dlen ? &mask : nullptr;
+    CellMask mask{C.dlen, {0, 0, 0, 0}};
+    const CellMask* mk = C.dlen ? &mask : nullptr;
     int np = 0;
     for (int l = NL - 1; l >= 0; --l) {
       const int r = dg - lag * (NL - 1 - l);      // reverse step index of layer l on this diagonal
@@ -1434,22 +1500,22 @@ static int backward_il(Plan& P, char* ws, const float* dy_last, const float* dy_
       }
       mask.t[np] = t;
       if (!top && r % Cz == 0) CSN_HIP_CHECK(hipStreamWaitEvent(st, dx_ready[(size_t)(l + 1) * nch + r / Cz], 0));
-      CellBwdProb& P = a.p[np++];
-      P.dg_next_blk = (t == T - 1) ? nullptr : (const bf16_t*)(ws + L.dgblk[(t + 1) & 1]);
-      P.wt_blk = (const bf16_t*)(ws + L.whht_blk);
+      CellBwdProb& q = a.p[np++];
+      q.dg_next_blk = (t == T - 1) ? nullptr : (const bf16_t*)(ws + L.dgblk[(t + 1) & 1]);
+      q.wt_blk = (const bf16_t*)(ws + L.whht_blk);
       if (top) {
-        P.dy = dy_tm ? dy_tm + (size_t)t * B * H : (t == T - 1 ? dy_last : nullptr);
+        q.dy = A.dy_tm ? A.dy_tm + (size_t)t * B * H : (t == T - 1 ? A.dy_last : nullptr);
       } else {
-        P.dy = (const float*)(ws + w.layer[l + 1].dx) + (size_t)t * B * H;
+        q.dy = (const float*)(ws + w.layer[l + 1].dx) + (size_t)t * B * H;
       }
-      P.dy_ld = H;
-      P.gates = (const bf16_t*)(ws + L.gates) + (size_t)t * B * G;
-      P.c = (const float*)(ws + L.c_all) + (size_t)(t + 1) * B * H;
+      q.dy_ld = H;
+      q.gates = (const bf16_t*)(ws + L.gates) + (size_t)t * B * G;
+      q.c = (const float*)(ws + L.c_all) + (size_t)(t + 1) * B * H;
       // (a CSN_LSTM_STATE plan reads c_all slot 0 at t = 0: c0, or the zeros its forward wrote there)
-      P.c_prev = (t == 0 && !state) ? nullptr : (const float*)(ws + L.c_all) + (size_t)t * B * H;
-      P.dc_carry = (float*)(ws + L.dc_carry);
-      P.dg_out = (bf16_t*)(ws + L.dgates) + (size_t)t * B * G;
-      P.dg_out_blk = (bf16_t*)(ws + L.dgblk[t & 1]);
+      q.c_prev = (t == 0 && !state) ? nullptr : (const float*)(ws + L.c_all) + (size_t)t * B * H;
+      q.dc_carry = (float*)(ws + L.dc_carry);
+      q.dg_out = (bf16_t*)(ws + L.dgates) + (size_t)t * B * G;
+      q.dg_out_blk = (bf16_t*)(ws + L.dgblk[t & 1]);
     }
     if (np == 0) continue;
     if ((rc = launch_cell_bwd_il(a, np, st, mk))) return rc;
@@ -1457,49 +1523,33 @@ static int backward_il(Plan& P, char* ws, const float* dy_last, const float* dy_
     n_cells += np;
     for (int l = NL - 1; l >= 0; --l) {
       const int r = dg - lag * (NL - 1 - l);
-      if (r < 0 || r >= T) continue;
-      const bool chunk_end = ((r + 1) % Cz == 0) || r == T - 1;
-      if (!chunk_end) continue;
-      const LayerWs& L = w.layer[l];
-      const int64_t I = l == 0 ? d->I : H;
+      if (r < 0 || r >= T || !ends_chunk(C, r)) continue;
       const int cr = r / Cz;
-      const int t_lo = T - 1 - r, t_hi = T - 1 - cr * Cz;       // steps covered by this (reverse) chunk
       const bool last = (r == T - 1);
       if (l > 0 || last) {
         if ((rc = hand_off(sc, st, side))) return rc;
       }
       if (l > 0) {
-        // dx_l[chunk] = dgates_l[chunk] (interleaved K) * W_ih;  Bt = W_ih^T [I, 4H']
-        rc = gemm_nt((const bf16_t*)(ws + L.dgates) + (size_t)t_lo * B * G, ws + L.wiht, nullptr,
-                         (float*)(ws + L.dx) + (size_t)t_lo * B * I, (int64_t)(t_hi - t_lo + 1) * B, I, G, CSN_BF16,
-                         CSN_F32, 0, side, P.opt);
-        if (rc) return rc;
-        // gradient w.r.t. h_n of the layer below joins its dy at t = T-1 (with lengths: at each row's last step)
-        if (dh_n && (rc = add_dh_n_rows(P, dh_n + (size_t)(l - 1) * B * H, (float*)(ws + L.dx), t_lo, t_hi, side))) return rc;
+        if ((rc = dx_chunk_gemm(C, l, cr, A.dh_n, side))) return rc;
         hipEvent_t ev;
         if ((rc = next_event(sc, &ev))) return rc;
         CSN_HIP_CHECK(hipEventRecord(ev, side));
         dx_ready[(size_t)l * nch + cr] = ev;
-      } else if (last && dx != nullptr) {
-        rc = gemm_nt(ws + L.dgates, ws + L.wiht, nullptr, ws + L.dx, TB, I, G, CSN_BF16, CSN_F32, 0,
-                         side, P.opt);
-        if (rc) return rc;
-        if ((rc = emit_dx(P, (const float*)(ws + L.dx), dx, I, side))) return rc;
+      } else if (last && A.dx != nullptr) {
+        if ((rc = dx_out(C, A.dx, side))) return rc;
       }
-      if (last && (rc = weight_grads(l))) return rc;
+      // the weight gradients of a layer follow on the side stream once its recurrence is complete
+      if (last && (rc = weight_grads_blk(C, A, l, side))) return rc;
     }
   }
-  if ((rc = prof_mark(g_prof, 3, st))) return rc;
-  g_prof.launches[1] = n_launch;
-  g_prof.cells[1] = n_cells;
-  g_prof.have[1] = g_prof.on;
+  if ((rc = prof_end(C, 1, n_launch, n_cells))) return rc;
   if ((rc = hand_off(sc, side, st))) return rc;   // the caller's stream resumes after all side-stream work
   // (the weight gradients of this path run on the side stream: only now are they ordered before the caller's stream)
-  for (int l = NL - 1; l >= 0; --l) P.grads_ready(l);
+  for (int l = NL - 1; l >= 0; --l) C.P.grads_ready(l);
   return CSN_OK;
 }
 
-// Weight-stationary backward recurrence (lstm_bwd_persist.hip), grouped form: ONE launch per chunk diagonal
+// Path 3, weight-stationary backward recurrence (lstm_bwd_persist.hip), grouped form: ONE launch per chunk diagonal
 // walks every layer in range backwards through one chunk.  The input gradient of a layer's chunk
 // (dx_l = dgates_l W_ih, the dy of the layer below) is a GEMM, and it runs INSIDE the next launch: the backward
 // kernel's groups occupy 24 of the 32 CUs of their XCD (24 slices of 32 units at H = 768), so the launch is
@@ -1510,16 +1560,17 @@ static int backward_il(Plan& P, char* ws, const float* dy_last, const float* dy_
 // the launch was measured too: the event waits between the streams cost ~30 us per launch, most of the gain.)
 // CSN_NO_BESIDE: lag one chunk, GEMM between two launches.
 // The weight / bias gradients follow once the recurrence is complete.
-static int backward_persist(Plan& P, char* ws, const float* dy_last, const float* dy_tm, const float* dh_n,
-                            const float* dc_n, float* const* dw_ih, float* const* dw_hh, float* const* db_ih,
-                            float* const* db_hh, float* dx, hipStream_t st) {
-  const csnLstmDesc* d = &P.d;
-  const WsLayout& w = P.w;
+static int backward_persist(Call& C, const BwdArgs& A) {
+  Plan& P = C.P;
+  const WsLayout& w = C.w;
   Prof& g_prof = P.prof;
-  const int B = d->B, T = d->T, H = d->H, NL = d->L;
-  const int64_t G = 4 * (int64_t)H, TB = (int64_t)T * B;
+  char* ws = C.ws;
+  hipStream_t st = C.st;
+  const float* dh_n = A.dh_n;
+  const int B = C.B, T = C.T, H = C.H, NL = C.NL;
+  const int64_t G = C.G;
   const int Bpad = (B + 63) / 64 * 64, MT = Bpad / 64;
-  const int Cz = P.opt.chunk;
+  const int Cz = C.Cz;
   const int nch = (T + Cz - 1) / Cz;
   const bool beside = NL > 1 && NL <= 4 && bwd_persist_slices(H) <= 28 && G % 64 == 0 && !P.opt.no_beside;
   const int lag = beside ? 2 : 1;
@@ -1527,45 +1578,19 @@ static int backward_persist(Plan& P, char* ws, const float* dy_last, const float
   int rc;
   // one fill: carried dc and flag lines of every layer, the XCD agreement words (zeros_bh: csn_lstm_workspace_init)
   CSN_HIP_CHECK(hipMemsetAsync(ws + w.zero_bwd, 0, w.zero_bwd_bytes, st));
-  // gradient w.r.t. c_n: the carried dc every layer starts from (the kernel reads it at launch start and writes it back at
-  // launch end, so after the last launch it holds the gradient w.r.t. c0)
-  if (dc_n)
-    for (int l = 0; l < NL; ++l)
-      CSN_HIP_CHECK(hipMemcpyAsync(ws + w.layer[l].dc_carry, dc_n + (size_t)l * B * H, (size_t)B * H * 4,
-                                   hipMemcpyDeviceToDevice, st));
+  // (the kernel reads the carried dc at launch start and writes it back at launch end, so after the last launch it holds
+  // the gradient w.r.t. c0)
+  for (int l = 0; l < NL; ++l)
+    if ((rc = seed_dc_carry(C, l, A.dc_n, true))) return rc;
   // gradient w.r.t. h_n of layer l - 1: added to row T-1 of layer l's input gradient once the GEMM of that chunk has
   // run (inline, or beside the recurrence in the next launch), before the launch that runs layer l - 1's first chunk
   // (with lengths: after the GEMM of EVERY chunk, at the rows whose last step lies in it)
   struct DhAdd { int l, t_lo, t_hi; };       // l = 0: none
   auto add_dh_n = [&](const DhAdd& q) -> int {
-    return add_dh_n_rows(P, dh_n + (size_t)(q.l - 1) * B * H, (float*)(ws + w.layer[q.l].dx), q.t_lo, q.t_hi, st);
+    return add_dh_n_rows(C, dh_n + (size_t)(q.l - 1) * B * H, (float*)(ws + w.layer[q.l].dx), q.t_lo, q.t_hi, st);
   };
   const bool try_local = !P.opt.no_xcd_local;
 
-  // weight / bias gradients of one layer (its recurrence complete): four launches on the caller's stream
-  auto weight_grads = [&](int l) -> int {
-    const LayerWs& L = w.layer[l];
-    const int64_t I = l == 0 ? d->I : H;
-    const void* inp = l == 0 ? (const void*)(ws + w.x_c)
-                             : (const void*)((const bf16_t*)(ws + w.layer[l - 1].h_all) + (size_t)B * H);
-    float* slabs = (float*)(ws + w.tn_scratch);
-    const int acc = P.grad_accumulate;
-    int S = 1, r;
-    int cs_done = 0, S_cs = 1;
-    if ((r = launch_gemm_tn_slabs(ws + L.dgates, ws + L.h_all, slabs, G, H, TB, CSN_BF16, st, &S, (float*)(ws + w.colsum), &cs_done, P.opt))) return r;
-    S_cs = S;
-    if ((r = launch_reduce_slabs_unperm(slabs, G * H, S, H, H, dw_hh[l], nullptr, acc, st))) return r;
-    if ((r = launch_gemm_tn_slabs(ws + L.dgates, inp, slabs, G, I, TB, CSN_BF16, st, &S, nullptr, nullptr, P.opt))) return r;
-    if ((r = launch_reduce_slabs_unperm(slabs, G * I, S, H, I, dw_ih[l], nullptr, acc, st))) return r;
-    // bias gradient = column sums of dgates: partial sums come out of the dW_hh GEMM when its kernel provides them
-    if (!cs_done) {
-      if ((r = launch_colsum_partial(ws + L.dgates, TB, G, CSN_BF16, ws + w.colsum, st))) return r;
-      S_cs = colsum_chunks();
-    }
-    // db_ih and db_hh both come out of the reduction (each adds to its own previous contents under CSN_GRAD_ACCUMULATE)
-    if ((r = launch_reduce_slabs_unperm((const float*)(ws + w.colsum), G, S_cs, H, 1, db_ih[l], db_hh[l], acc, st))) return r;
-    return CSN_OK;
-  };
   PersistBwdArgs a{};
   a.error_flag = (unsigned*)(ws + w.status);
   a.B = B; a.H = H; a.T = T; a.Bpad = Bpad; a.MT = MT;
@@ -1596,8 +1621,8 @@ static int backward_persist(Plan& P, char* ws, const float* dy_last, const float
       S.gates = (const bf16_t*)(ws + L.gates);
       S.c_all = (const float*)(ws + L.c_all);
       if (l == NL - 1) {
-        S.dy = dy_tm;
-        S.dy_last = dy_tm ? nullptr : dy_last;
+        S.dy = A.dy_tm;
+        S.dy_last = A.dy_tm ? nullptr : A.dy_last;
       } else {
         S.dy = (const float*)(ws + w.layer[l + 1].dx);
         S.dy_last = nullptr;
@@ -1607,8 +1632,9 @@ static int backward_persist(Plan& P, char* ws, const float* dy_last, const float
       S.dgates = (bf16_t*)(ws + L.dgates);
       S.dg_blk_all = (bf16_t*)(ws + L.dg_blk_all);
       S.flags = (unsigned*)(ws + L.bflags);
-      S.t_hi = T - 1 - c * Cz;
-      S.nsteps = (c * Cz + Cz <= T) ? Cz : T - c * Cz;
+      const Chunk k = chunk_at(C, c);
+      S.t_hi = T - 1 - k.t0;
+      S.nsteps = k.nsteps;
       lay[ns] = l;
       chk[ns] = c;
       ++ns;
@@ -1628,7 +1654,7 @@ static int backward_persist(Plan& P, char* ws, const float* dy_last, const float
     a.ngemm = npending;
     // few groups: 32-row groups, twice as many (forward_persist).  The grid and the GEMM workers stay what they are --
     // 8 groups of 24 slices leave the same 8 x 8 workgroups for the tiles.  A batch with lengths stays on 64 rows.
-    const bool half = !P.opt.no_half_tiles && P.dlen == nullptr && 2 * ns * MT <= 8;
+    const bool half = !P.opt.no_half_tiles && C.dlen == nullptr && 2 * ns * MT <= 8;
     a.half_tiles = half ? 1 : 0;
     a.MT = half ? 2 * MT : MT;
     if (half) {
@@ -1644,7 +1670,7 @@ static int backward_persist(Plan& P, char* ws, const float* dy_last, const float
     npending = 0;
     a.agree = try_local ? (unsigned long long*)(ws + w.agree_b) + (size_t)dg * 8 : nullptr;
     if ((rc = prof_pair(g_prof, 1, false, st))) return rc;
-    if ((rc = launch_bwd_persist(a, st, P.dlen))) return rc;
+    if ((rc = launch_bwd_persist(a, st, C.dlen))) return rc;
     if ((rc = prof_pair(g_prof, 1, true, st))) return rc;
     ++n_launch;
     for (int i = 0; i < nadds; ++i)
@@ -1652,44 +1678,46 @@ static int backward_persist(Plan& P, char* ws, const float* dy_last, const float
     for (int i = 0; i < ns; ++i) {
       const int l = lay[i];
       if (l == 0) continue;
-      // dx_l[chunk] = dgates_l[chunk] (interleaved K) * W_ih;  Bt = W_ih^T [I, 4H']
-      const LayerWs& L = w.layer[l];
-      const int t_hi = T - 1 - chk[i] * Cz, t_lo = t_hi - a.slot[i].nsteps + 1;
-      const bf16_t* Ag = (const bf16_t*)(ws + L.dgates) + (size_t)t_lo * B * G;
-      float* Cg = (float*)(ws + L.dx) + (size_t)t_lo * B * H;
-      const int64_t Mg = (int64_t)(t_hi - t_lo + 1) * B;
-      const DhAdd add{(dh_n && (chk[i] == 0 || P.dlen)) ? l : 0, t_lo, t_hi};
-      if (beside) {
-        pending_add[npending] = add;
-        pending[npending++] = BesideGemm{Ag, (const bf16_t*)(ws + L.wiht), Cg, (int)Mg, H, (int)G};
-      } else {
-        if ((rc = gemm_nt(Ag, ws + L.wiht, nullptr, Cg, Mg, H, G, CSN_BF16, CSN_F32, 0, st, P.opt))) return rc;
-        if (add.l && (rc = add_dh_n(add))) return rc;
+      if (!beside) {
+        if ((rc = dx_chunk_gemm(C, l, chk[i], dh_n, st))) return rc;
+        continue;
       }
+      // dx_chunk_gemm's GEMM and dh_n term, left for the next launch
+      const LayerWs& L = w.layer[l];
+      const int t_hi = a.slot[i].t_hi, t_lo = t_hi - a.slot[i].nsteps + 1;
+      pending_add[npending] = DhAdd{(dh_n && (chk[i] == 0 || C.dlen)) ? l : 0, t_lo, t_hi};
+      pending[npending++] = BesideGemm{(const bf16_t*)(ws + L.dgates) + (size_t)t_lo * B * G, (const bf16_t*)(ws + L.wiht),
+                                       (float*)(ws + L.dx) + (size_t)t_lo * B * H, (t_hi - t_lo + 1) * B, H, (int)G};
     }
   }
-  if ((rc = prof_mark(g_prof, 3, st))) return rc;
-  g_prof.launches[1] = n_launch;
-  g_prof.cells[1] = T * NL;
-  g_prof.have[1] = g_prof.on;
+  if ((rc = prof_end(C, 1, n_launch, T * NL))) return rc;
 
-  if (dx != nullptr) {
-    const LayerWs& L = w.layer[0];
-    if ((rc = gemm_nt(ws + L.dgates, ws + L.wiht, nullptr, ws + L.dx, TB, d->I, G, CSN_BF16, CSN_F32, 0,
-                          st, P.opt)))
-      return rc;
-    if ((rc = emit_dx(P, (const float*)(ws + L.dx), dx, d->I, st))) return rc;
-  }
+  if (A.dx != nullptr && (rc = dx_out(C, A.dx, st))) return rc;
   // (every recurrence launch has been enqueued by now: what a gradient-ready callback starts -- a collective on another
   // stream -- runs beside the remaining layers' weight-gradient GEMMs, never beside a one-workgroup-per-CU launch)
   for (int l = NL - 1; l >= 0; --l) {
-    if ((rc = weight_grads(l))) return rc;
+    if ((rc = weight_grads_blk(C, A, l, st))) return rc;
     P.grads_ready(l);
   }
   return CSN_OK;
 }
 
 // =============================================================================================
+// the path of a call (csn_lstm_plan_path: the forward of paths 2 and 3 is one, the backward of path 3 falls back to that of
+// paths 1 and 2 where its grouped form does not apply)
+static int run_forward(Call& C, const FwdArgs& A) {
+  if (C.w.persist) return forward_persist(C, A);
+  if (C.w.il) return forward_il(C, A);
+  if (C.w.f32_persist) return forward_f32p(C, A);
+  return forward_v1(C, A);
+}
+static int run_backward(Call& C, const BwdArgs& A) {
+  if (bwd_grouped(&C.P, C.T)) return backward_persist(C, A);
+  if (C.w.il) return backward_il(C, A);
+  if (C.w.f32_persist) return backward_f32p(C, A);
+  return backward_v1(C, A);
+}
+
 // state arguments ([L,B,H] float32): only on a CSN_LSTM_STATE plan, 16-B aligned (read / written as float4)
 static int check_state_args(const Plan& P, const char* fn, const void* const* ptrs, const char* const* names, int n) {
   for (int i = 0; i < n; ++i) {
@@ -1721,69 +1749,54 @@ extern "C" int csn_lstm_forward(csnLstmPlan* Pp, const float* x, int64_t x_strid
   CSN_HIP_CHECK(hipGetDevice(&dev));
   CSN_REQUIRE(dev == P.device, "csn_lstm_forward: plan was created on device %d, current device is %d", P.device, dev);
   hipStream_t st = as_stream(stream);
-  const WsLayout& w = P.w;
-  const int training = P.training;
-  char* ws = (char*)workspace;
-  const int B = d->B, T = d->T, H = d->H, dt = d->dtype;
-  const size_t es = dtype_size(dt);
   int rc;
   // (the status word is NOT cleared here: it stays raised from the first timed-out hand-off until
   // csn_lstm_status_clear, so a check at the end of an epoch / a timed region covers every step in it)
-  if ((rc = upload_lengths(Pp, st))) return rc;
-  if (P.dlen != nullptr) {
+  const int* dlen = nullptr;
+  if ((rc = upload_lengths(Pp, st, &dlen))) return rc;
+  Call C(P, workspace, st, dlen);
+  const FwdArgs A{x, x_stride_b, x_stride_t, w_ih, w_hh, b_ih, b_hh, h0, c0};
+  const WsLayout& w = P.w;
+  char* ws = C.ws;
+  const int B = C.B, H = C.H, dt = C.dt;
+  const size_t es = C.es;
+  if (dlen != nullptr) {
     // Variable-length batch: every path runs its unchanged kernels over steps 0 .. max(lengths)-1 of ALL rows (short rows
     // run on over zeroed padding), then each row's results are selected: slot n of h_all / c_all is its final state
-    if (P.t_eff > 0) {
-      EffectiveT scope(P.d, P.t_eff);
-      rc = w.il ? forward_il(P, ws, x, x_stride_b, x_stride_t, w_ih, w_hh, b_ih, b_hh, h0, c0, training, stream)
-                : forward_v1(P, ws, x, x_stride_b, x_stride_t, w_ih, w_hh, b_ih, b_hh, h0, c0, training, stream);
-      if (rc) return rc;
+    if (C.T > 0) {
+      if ((rc = run_forward(C, A))) return rc;
     } else {
       // every row is empty: no recurrence launch; slot 0 (the initial state) is all the gathers below read
-      for (int l = 0; l < d->L; ++l) {
-        const LayerWs& L = w.layer[l];
-        if (h0) {
-          if ((rc = launch_cast(h0 + (size_t)l * B * H, ws + L.h_all, (int64_t)B * H, dt, st))) return rc;
-        } else {
-          CSN_HIP_CHECK(hipMemsetAsync(ws + L.h_all, 0, (size_t)B * H * es, st));
-        }
-        if (c0)
-          CSN_HIP_CHECK(hipMemcpyAsync(ws + L.c_all, c0 + (size_t)l * B * H, (size_t)B * H * 4, hipMemcpyDeviceToDevice, st));
-        else
-          CSN_HIP_CHECK(hipMemsetAsync(ws + L.c_all, 0, (size_t)B * H * 4, st));
-      }
+      for (int l = 0; l < d->L; ++l)
+        if ((rc = install_slot0(C, l, h0, c0))) return rc;
       if (h0 || c0) P.state_seen = true;      // (slot 0 is no longer the zeros csn_lstm_workspace_init left)
       P.prof.have[0] = false;
     }
     const unsigned gbh = grid_for((int64_t)B * H);
     auto gather_h = [&](const LayerWs& L, float* out) {
-      if (dt == CSN_BF16) gather_state_kernel<bf16_t><<<gbh, 256, 0, st>>>((const bf16_t*)(ws + L.h_all), P.dlen, out, B, H);
-      else gather_state_kernel<float><<<gbh, 256, 0, st>>>((const float*)(ws + L.h_all), P.dlen, out, B, H);
+      if (dt == CSN_BF16) gather_state_kernel<bf16_t><<<gbh, 256, 0, st>>>((const bf16_t*)(ws + L.h_all), dlen, out, B, H);
+      else gather_state_kernel<float><<<gbh, 256, 0, st>>>((const float*)(ws + L.h_all), dlen, out, B, H);
     };
     for (int l = 0; l < d->L; ++l) {
       const LayerWs& L = w.layer[l];
       if (h_n) gather_h(L, h_n + (size_t)l * B * H);
-      if (c_n) gather_state_kernel<float><<<gbh, 256, 0, st>>>((const float*)(ws + L.c_all), P.dlen, c_n + (size_t)l * B * H, B, H);
+      if (c_n) gather_state_kernel<float><<<gbh, 256, 0, st>>>((const float*)(ws + L.c_all), dlen, c_n + (size_t)l * B * H, B, H);
     }
     const LayerWs& top = w.layer[d->L - 1];
     if (y_last) gather_h(top, y_last);
     if (y_all) {
+      const int T = C.T_full;       // the caller's rows: zeros from each row's length on
       const int64_t n = (int64_t)T * B * H;
       if (dt == CSN_BF16)
-        gather_y_all_len_kernel<bf16_t><<<grid_for(n), 256, 0, st>>>((const bf16_t*)(ws + top.h_all), y_all, P.dlen, B, T, H);
+        gather_y_all_len_kernel<bf16_t><<<grid_for(n), 256, 0, st>>>((const bf16_t*)(ws + top.h_all), y_all, dlen, B, T, H);
       else
-        gather_y_all_len_kernel<float><<<grid_for(n), 256, 0, st>>>((const float*)(ws + top.h_all), y_all, P.dlen, B, T, H);
+        gather_y_all_len_kernel<float><<<grid_for(n), 256, 0, st>>>((const float*)(ws + top.h_all), y_all, dlen, B, T, H);
     }
     CSN_LAUNCH_CHECK();
     return CSN_OK;
   }
-  if (w.il)
-    rc = forward_il(P, ws, x, x_stride_b, x_stride_t, w_ih, w_hh, b_ih, b_hh, h0, c0, training, stream);
-  else if (w.f32_persist)
-    rc = forward_f32p(P, ws, x, x_stride_b, x_stride_t, w_ih, w_hh, b_ih, b_hh, training, stream);
-  else
-    rc = forward_v1(P, ws, x, x_stride_b, x_stride_t, w_ih, w_hh, b_ih, b_hh, h0, c0, training, stream);
-  if (rc) return rc;
+  if ((rc = run_forward(C, A))) return rc;
+  const int T = C.T;
   // final state of every layer: slot T of h_all (upcast of the h the next layer consumed) and of c_all
   for (int l = 0; l < d->L && (h_n || c_n); ++l) {
     const LayerWs& L = w.layer[l];
@@ -1832,38 +1845,37 @@ extern "C" int csn_lstm_backward(csnLstmPlan* Pp, const float* dy_last, const fl
   CSN_HIP_CHECK(hipGetDevice(&dev));
   CSN_REQUIRE(dev == P.device, "csn_lstm_backward: plan was created on device %d, current device is %d", P.device, dev);
   hipStream_t st = as_stream(stream);
-  const WsLayout& w = P.w;
-  char* ws = (char*)workspace;
-  const int B = d->B, T = d->T, H = d->H;
-  const int64_t TB = (int64_t)T * B;
-
   int rc;
-  if ((rc = upload_lengths(Pp, st))) return rc;
-  if (P.dlen != nullptr) {
+  const int* dlen = nullptr;
+  if ((rc = upload_lengths(Pp, st, &dlen))) return rc;
+  Call C(P, workspace, st, dlen);
+  BwdArgs A{dy_last, nullptr, dh_n, dc_n, dw_ih, dw_hh, db_ih, db_hh, dx};
+  const WsLayout& w = P.w;
+  char* ws = C.ws;
+  const int B = C.B, H = C.H, NL = C.NL;
+  const size_t BH = (size_t)B * H;
+  float* buf = (float*)(ws + w.dy_tm);       // dense time-major dy of the top layer
+
+  if (dlen != nullptr) {
     // Variable-length batch (the lengths of the matching forward): the backward of the steps the forward ran, with the
     // masked cell kernels; every gradient that enters at a row's end is added at that row's own last step
-    const int L_ = d->L, dt = d->dtype;
-    const int64_t G = 4 * (int64_t)H;
-    if (P.t_eff > 0) {
-      const int Te = P.t_eff;
-      float* buf = (float*)(ws + w.dy_tm);       // dense time-major dy of the top layer, zeros over the padding
-      bt_to_tb_len_kernel<<<grid_for((int64_t)Te * B * H), 256, 0, st>>>(dy_all, buf, P.dlen, B, T, Te, H);
-      if (dy_last) add_at_end_kernel<<<grid_for((int64_t)B * H), 256, 0, st>>>(dy_last, buf, P.dlen, 0, Te - 1, B, H);
-      if (dh_n) add_at_end_kernel<<<grid_for((int64_t)B * H), 256, 0, st>>>(dh_n + (size_t)(L_ - 1) * B * H, buf, P.dlen, 0, Te - 1, B, H);
+    const int64_t G = C.G;
+    const int Te = C.T;
+    if (Te > 0) {
+      // zeros over the padding of dy
+      bt_to_tb_len_kernel<<<grid_for((int64_t)Te * B * H), 256, 0, st>>>(dy_all, buf, dlen, B, C.T_full, Te, H);
+      if (dy_last) add_at_end_kernel<<<grid_for((int64_t)BH), 256, 0, st>>>(dy_last, buf, dlen, 0, Te - 1, B, H);
+      if (dh_n) add_at_end_kernel<<<grid_for((int64_t)BH), 256, 0, st>>>(dh_n + (NL - 1) * BH, buf, dlen, 0, Te - 1, B, H);
       CSN_LAUNCH_CHECK();
-      {
-        EffectiveT scope(P.d, Te);
-        rc = w.il ? backward_il(P, ws, nullptr, buf, dh_n, dc_n, dw_ih, dw_hh, db_ih, db_hh, dx, stream)
-                  : backward_v1(P, ws, nullptr, buf, dh_n, dc_n, dw_ih, dw_hh, db_ih, db_hh, dx, stream);
-      }
-      if (rc) return rc;
+      A.dy_last = nullptr;
+      A.dy_tm = buf;
+      if ((rc = run_backward(C, A))) return rc;
     } else {
       // every row is empty: no recurrence, no parameter contribution
-      if (dx) CSN_HIP_CHECK(hipMemsetAsync(dx, 0, (size_t)T * B * d->I * 4, st));
-      for (int l = L_ - 1; l >= 0; --l) {
+      if (dx) CSN_HIP_CHECK(hipMemsetAsync(dx, 0, (size_t)C.T_full * B * d->I * 4, st));
+      for (int l = NL - 1; l >= 0; --l) {
         if (!P.grad_accumulate) {
-          const int64_t I = l == 0 ? d->I : H;
-          CSN_HIP_CHECK(hipMemsetAsync(dw_ih[l], 0, (size_t)(G * I) * 4, st));
+          CSN_HIP_CHECK(hipMemsetAsync(dw_ih[l], 0, (size_t)(G * C.in_width(l)) * 4, st));
           CSN_HIP_CHECK(hipMemsetAsync(dw_hh[l], 0, (size_t)(G * H) * 4, st));
           CSN_HIP_CHECK(hipMemsetAsync(db_ih[l], 0, (size_t)G * 4, st));
           CSN_HIP_CHECK(hipMemsetAsync(db_hh[l], 0, (size_t)G * 4, st));
@@ -1872,90 +1884,64 @@ extern "C" int csn_lstm_backward(csnLstmPlan* Pp, const float* dy_last, const fl
       }
       P.prof.have[1] = false;
     }
-    for (int l = 0; l < L_ && (dh0 || dc0); ++l) {
-      const LayerWs& L = w.layer[l];
+    for (int l = 0; l < NL && (dh0 || dc0); ++l) {
       if (dh0) {
-        float* out = dh0 + (size_t)l * B * H;
-        if (P.t_eff > 0) {
-          const dim3 grid((unsigned)((H + 63) / 64), (unsigned)((B + 31) / 32));
-          if (w.il)
-            lstm_dh0_kernel<bf16_t, true><<<grid, 256, 0, st>>>((const bf16_t*)(ws + L.dgates), (const bf16_t*)(ws + L.whht_blk), B, H, out);
-          else if (dt == CSN_BF16)
-            lstm_dh0_kernel<bf16_t, false><<<grid, 256, 0, st>>>((const bf16_t*)(ws + L.dgates), (const bf16_t*)(ws + L.whht), B, H, out);
-          else
-            lstm_dh0_kernel<float, false><<<grid, 256, 0, st>>>((const float*)(ws + L.dgates), (const float*)(ws + L.whht), B, H, out);
+        float* out = dh0 + l * BH;
+        if (Te > 0) {
+          if ((rc = launch_dh0(C, l, out))) return rc;
         } else {
-          CSN_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)B * H * 4, st));
+          CSN_HIP_CHECK(hipMemsetAsync(out, 0, BH * 4, st));
         }
         // an empty row's dgates are zero at step 0: its dh0 is the gradient w.r.t. its h_n
-        if (dh_n) add_rows_len0_kernel<<<grid_for((int64_t)B * H), 256, 0, st>>>(dh_n + (size_t)l * B * H, out, P.dlen, B, H);
+        if (dh_n) add_rows_len0_kernel<<<grid_for((int64_t)BH), 256, 0, st>>>(dh_n + l * BH, out, dlen, B, H);
         CSN_LAUNCH_CHECK();
       }
       if (dc0) {
         // the carried dc: an empty row's passed every (masked) step as it was
-        if (P.t_eff > 0)
-          CSN_HIP_CHECK(hipMemcpyAsync(dc0 + (size_t)l * B * H, ws + L.dc_carry, (size_t)B * H * 4, hipMemcpyDeviceToDevice, st));
+        if (Te > 0)
+          CSN_HIP_CHECK(hipMemcpyAsync(dc0 + l * BH, ws + w.layer[l].dc_carry, BH * 4, hipMemcpyDeviceToDevice, st));
         else if (dc_n)
-          CSN_HIP_CHECK(hipMemcpyAsync(dc0 + (size_t)l * B * H, dc_n + (size_t)l * B * H, (size_t)B * H * 4, hipMemcpyDeviceToDevice, st));
+          CSN_HIP_CHECK(hipMemcpyAsync(dc0 + l * BH, dc_n + l * BH, BH * 4, hipMemcpyDeviceToDevice, st));
         else
-          CSN_HIP_CHECK(hipMemsetAsync(dc0 + (size_t)l * B * H, 0, (size_t)B * H * 4, st));
+          CSN_HIP_CHECK(hipMemsetAsync(dc0 + l * BH, 0, BH * 4, st));
       }
     }
     return CSN_OK;
   }
 
   // gradient w.r.t. the top layer's outputs, time-major.  With only dy_last, no buffer is needed.
-  const float* dy_tm = nullptr;
+  const int T = C.T;
   if (dy_all) {
-    float* buf = (float*)(ws + w.dy_tm);
-    bt_to_tb_kernel<<<grid_for(TB * H), 256, 0, st>>>(dy_all, buf, B, T, H);
+    bt_to_tb_kernel<<<grid_for(C.TB * H), 256, 0, st>>>(dy_all, buf, B, T, H);
     CSN_LAUNCH_CHECK();
     if (dy_last) {
-      add_rows_kernel<<<grid_for((int64_t)B * H), 256, 0, st>>>(dy_last, buf + (size_t)(T - 1) * B * H, (int64_t)B * H);
+      add_rows_kernel<<<grid_for((int64_t)BH), 256, 0, st>>>(dy_last, buf + (size_t)(T - 1) * BH, (int64_t)BH);
       CSN_LAUNCH_CHECK();
     }
-    dy_tm = buf;
+    A.dy_tm = buf;
   }
   // gradient w.r.t. the top layer's h_n: one more term of its dy at t = T-1 (dy_last is caller memory: added into a
   // workspace copy of it, in the dy_tm region that is unused when dy_all is NULL)
   if (dh_n) {
-    const float* dh_top = dh_n + (size_t)(d->L - 1) * B * H;
-    if (dy_tm) {
-      add_rows_kernel<<<grid_for((int64_t)B * H), 256, 0, st>>>(dh_top, (float*)dy_tm + (size_t)(T - 1) * B * H, (int64_t)B * H);
+    const float* dh_top = dh_n + (NL - 1) * BH;
+    if (A.dy_tm) {
+      add_rows_kernel<<<grid_for((int64_t)BH), 256, 0, st>>>(dh_top, buf + (size_t)(T - 1) * BH, (int64_t)BH);
       CSN_LAUNCH_CHECK();
     } else if (dy_last) {
-      float* buf = (float*)(ws + w.dy_tm);
-      CSN_HIP_CHECK(hipMemcpyAsync(buf, dy_last, (size_t)B * H * 4, hipMemcpyDeviceToDevice, st));
-      add_rows_kernel<<<grid_for((int64_t)B * H), 256, 0, st>>>(dh_top, buf, (int64_t)B * H);
+      CSN_HIP_CHECK(hipMemcpyAsync(buf, dy_last, BH * 4, hipMemcpyDeviceToDevice, st));
+      add_rows_kernel<<<grid_for((int64_t)BH), 256, 0, st>>>(dh_top, buf, (int64_t)BH);
       CSN_LAUNCH_CHECK();
-      dy_last = buf;
+      A.dy_last = buf;
     } else {
-      dy_last = dh_top;
+      A.dy_last = dh_top;
     }
   }
-  if (w.il)
-    rc = backward_il(P, ws, dy_last, dy_tm, dh_n, dc_n, dw_ih, dw_hh, db_ih, db_hh, dx, stream);
-  else if (w.f32_persist)
-    rc = backward_f32p(P, ws, dy_last, dy_tm, dw_ih, dw_hh, db_ih, db_hh, dx, stream);
-  else
-    rc = backward_v1(P, ws, dy_last, dy_tm, dh_n, dc_n, dw_ih, dw_hh, db_ih, db_hh, dx, stream);
-  if (rc) return rc;
+  if ((rc = run_backward(C, A))) return rc;
   // gradients w.r.t. the initial state (CSN_LSTM_STATE plans only: paths 0 and 1, everything on `stream` by now)
-  for (int l = 0; l < d->L && (dh0 || dc0); ++l) {
-    const LayerWs& L = w.layer[l];
-    if (dh0) {
-      const dim3 grid((unsigned)((H + 63) / 64), (unsigned)((B + 31) / 32));
-      float* out = dh0 + (size_t)l * B * H;
-      if (w.il)
-        lstm_dh0_kernel<bf16_t, true><<<grid, 256, 0, st>>>((const bf16_t*)(ws + L.dgates), (const bf16_t*)(ws + L.whht_blk), B, H, out);
-      else if (d->dtype == CSN_BF16)
-        lstm_dh0_kernel<bf16_t, false><<<grid, 256, 0, st>>>((const bf16_t*)(ws + L.dgates), (const bf16_t*)(ws + L.whht), B, H, out);
-      else
-        lstm_dh0_kernel<float, false><<<grid, 256, 0, st>>>((const float*)(ws + L.dgates), (const float*)(ws + L.whht), B, H, out);
-      CSN_LAUNCH_CHECK();
-    }
+  for (int l = 0; l < NL && (dh0 || dc0); ++l) {
+    if (dh0 && (rc = launch_dh0(C, l, dh0 + l * BH))) return rc;
     if (dc0)
-      CSN_HIP_CHECK(hipMemcpyAsync(dc0 + (size_t)l * B * H, ws + L.dc_carry, (size_t)B * H * 4, hipMemcpyDeviceToDevice, st));
+      CSN_HIP_CHECK(hipMemcpyAsync(dc0 + l * BH, ws + w.layer[l].dc_carry, BH * 4, hipMemcpyDeviceToDevice, st));
   }
   return CSN_OK;
 }

@@ -156,7 +156,7 @@ struct PrepArgs {
 int launch_prep_multi(PrepArgs& A, hipStream_t st);
 
 bool cell_blk_supported(int H, int dtype, const Options& opt);
-int launch_cell_fwd_il(const CellFwdArgs& a, int nprob, hipStream_t st, int max_nk);
+int launch_cell_fwd_il(const CellFwdArgs& a, int nprob, hipStream_t st);
 int launch_cell_bwd_il(const CellBwdArgs& a, int nprob, hipStream_t st, const CellMask* mask = nullptr);
 int launch_blockify_x(const float* x, int64_t xsb, int64_t xst, int B, int T, int I, void* dst, hipStream_t st);
 int launch_blockify(const float* src, int64_t ld_r, int64_t ld_k, int64_t R, int64_t K, int perm_r, int perm_k,

@@ -652,17 +652,13 @@ static int launch_fwd_t(const CellFwdArgs& a, int nprob, hipStream_t st) {
   return CSN_OK;
 }
 
-int launch_cell_fwd_il(const CellFwdArgs& a, int nprob, hipStream_t st, int max_nk) {
+int launch_cell_fwd_il(const CellFwdArgs& a, int nprob, hipStream_t st) {
   const int H = a.H;
-  const int steps = H / 128;                       // k-steps per wave
-  const int nk = pick_nk(steps, max_nk);
   const int nq = (H % 24 == 0) ? 6 : ((H % 32 == 0) ? 8 : 4);
 #define CSN_CASE(NQ, NK) if (nq == NQ) return launch_fwd_t<NQ, NK>(a, nprob, st)
-  // (k-blocks per pass: only 1 is built -- the deeper passes CSN_FWD_NK used to select spilled 32 - 147 registers)
-  (void)nk;
+  // (k-blocks per pass: only 1 is built -- deeper passes spilled 32 - 147 registers)
   CSN_CASE(6, 1); CSN_CASE(8, 1); CSN_CASE(4, 1);
 #undef CSN_CASE
-  if (nq == 8) return launch_fwd_t<8, 1>(a, nprob, st);
   return fail(CSN_ERR_UNSUPPORTED, "launch_cell_fwd_il: no kernel for H=%d", H);
 }
 
