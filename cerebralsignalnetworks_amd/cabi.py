@@ -40,6 +40,9 @@ SIGNATURES = {
     "csn_eeg_filtfilt_scratch_bytes": (_c_size_t, [_c_int, _c_int, _c_int, _c_int]),
     "csn_eeg_filtfilt": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, ctypes.POINTER(ctypes.c_double), _c_int,
                                   _c_void_p, _c_void_p, _c_void_p]),
+    "csn_eeg_bandpass_stream": (_c_int, [_c_void_p, _c_i64, _c_int, _c_int, _c_int, ctypes.POINTER(ctypes.c_double), _c_int,
+                                         _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_void_p]),
+    "csn_eeg_bandpass_stream_path": (_c_int, [_c_void_p, _c_i64, _c_int, _c_int, _c_int]),
     "csn_lstm_plan_create": (_c_int, [ctypes.POINTER(LstmDesc), _c_int, ctypes.POINTER(_c_void_p)]),
     "csn_lstm_plan_destroy": (None, [_c_void_p]),
     "csn_lstm_plan_workspace_bytes": (_c_size_t, [_c_void_p]),
@@ -173,6 +176,64 @@ def eeg_bandpass_znorm(x_bct, sos, ddof=0, out_dtype=torch.float32, time_major=F
         _check(load().csn_eeg_bandpass_znorm(_ptr(x), B, C, T, sos.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
                                              sos.shape[0], int(ddof), _ptr(y), _dt(out_dtype), int(time_major), _stream()))
     return y
+
+
+def _stream_rows(x_bct):
+    """x[B,C,T] as the stream entry point takes it: the tensor itself where its rows are equally spaced runs of
+    consecutive samples (a time slice of a longer [B,C,Ttotal] buffer is), a contiguous copy otherwise."""
+    B, C, T = x_bct.shape
+    if not (x_bct.stride(2) == 1 and x_bct.stride(0) == C * x_bct.stride(1) and x_bct.stride(1) >= T):
+        x_bct = x_bct.contiguous()
+    return x_bct, x_bct.stride(1)
+
+
+def _stream_state(t, name, shape, dtype):
+    if t is None:
+        return
+    _need_cuda(t)
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise CsnError(f"eeg_bandpass_stream: {name} must be a contiguous {dtype} tensor of shape {tuple(shape)}, "
+                       f"got {t.dtype} {tuple(t.shape)}")
+
+
+def eeg_bandpass_stream(x_bct, sos, state_in=None, state_out=None, mean=None, inv_std=None, out_dtype=torch.float32,
+                        time_major=False):
+    """One piece of a recording through the causal band-pass: x[B,C,T] float32 (device; may be a time slice of a longer
+    tensor, no copy) -> (y[B,T,C] or [T,B,C], state_out).  ``state_in`` / ``state_out``: [B,C,nsec,2] float64 on the
+    device (``scipy.signal.sosfilt``'s zi with the section axis moved inward); ``state_in=None`` starts a recording,
+    ``state_out=None`` allocates the result, and the two may be the same tensor.  ``mean`` / ``inv_std``: optional [C]
+    float32, ``y = (filtered - mean) * inv_std``."""
+    import numpy as np
+    _need_cuda(x_bct)
+    if x_bct.dtype != torch.float32:
+        raise CsnError("eeg_bandpass_stream expects float32 input")
+    if x_bct.dim() != 3:
+        raise CsnError(f"eeg_bandpass_stream expects x[B,C,T], got shape {tuple(x_bct.shape)}")
+    x, row_stride = _stream_rows(x_bct)
+    B, C, T = x.shape
+    sos = np.ascontiguousarray(np.asarray(sos, dtype=np.float64).reshape(-1, 6)) if sos is not None else np.zeros((0, 6))
+    nsec = sos.shape[0]
+    if (mean is None) != (inv_std is None):
+        raise CsnError("eeg_bandpass_stream: mean and inv_std are given together or not at all")
+    _stream_state(state_in, "state_in", (B, C, nsec, 2), torch.float64)
+    _stream_state(mean, "mean", (C,), torch.float32)
+    _stream_state(inv_std, "inv_std", (C,), torch.float32)
+    if state_out is None:
+        state_out = torch.empty((B, C, nsec, 2), dtype=torch.float64, device=x.device)
+    _stream_state(state_out, "state_out", (B, C, nsec, 2), torch.float64)
+    y = torch.empty((T, B, C) if time_major else (B, T, C), dtype=out_dtype, device=x.device)
+    with torch.cuda.device(x.device):
+        _check(load().csn_eeg_bandpass_stream(_ptr(x), row_stride, B, C, T, sos.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                              nsec, _ptr(state_in), _ptr(state_out), _ptr(mean), _ptr(inv_std), _ptr(y),
+                                              _dt(out_dtype), int(time_major), _stream()))
+    return y, state_out
+
+
+def eeg_bandpass_stream_path(x_bct, nsec):
+    """Which kernel ``eeg_bandpass_stream`` runs for this piece: 1 = tile-walking scan, 0 = stateful row-walking."""
+    x, row_stride = _stream_rows(x_bct)
+    B, C, T = x.shape
+    return load().csn_eeg_bandpass_stream_path(_ptr(x), row_stride, C, T, int(nsec))
 
 
 def eeg_filtfilt(x_stc, sos):

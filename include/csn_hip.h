@@ -37,7 +37,7 @@ enum csnDtype { CSN_F32 = 0, CSN_BF16 = 1 };
 
 /* ABI version of this header; bumped on any signature change.  A symbol added beside the existing ones
  * (csn_lstm_plan_set_grad_mode, csn_lstm_plan_set_lengths, csn_lstm_plan_half_tile_launches, the csn_flat_* family,
- * csn_adam_step, csn_lars_step) breaks no caller and does not bump it. */
+ * csn_adam_step, csn_lars_step, csn_eeg_bandpass_stream and its _path) breaks no caller and does not bump it. */
 #define CSN_ABI_VERSION 6
 int csn_abi_version(void);
 /* Thread-local message for the last non-zero status returned on this thread. */
@@ -72,6 +72,30 @@ int csn_eeg_bandpass_znorm(const float* x, int B, int C, int T,
 size_t csn_eeg_filtfilt_scratch_bytes(int S, int T, int C, int nsec);
 int csn_eeg_filtfilt(const float* x, int S, int T, int C, const double* sos, int nsec,
                      float* y, void* scratch, csnStream_t stream);
+
+/* Causal band-pass of a recording delivered in pieces: scipy.signal.sosfilt(sos, x, zi) per (segment, channel) row.
+ *   x          piece [B,C,T] float32, T >= 1; row (b,c) starts at x + (b*C + c) * x_row_stride, x_row_stride >= T
+ *              (a piece may be a time slice of a longer [B,C,Ttotal] buffer: no copy)
+ *   sos, nsec  as csn_eeg_bandpass_znorm (nsec 0..8; 0 = no filter)
+ *   state_in   [B,C,nsec,2] float64, the direct-form-II-transposed (s1, s2) of every section = scipy's zi[nsec,B,C,2]
+ *              with the section axis moved inward; NULL = zeros (start of a recording)
+ *   state_out  same layout, the state after the last sample of the piece; may be NULL; may alias state_in
+ *   mean, inv_std  optional [C] float32 (both or neither): y = (filtered - mean[c]) * inv_std[c], formed in float64,
+ *              rounded once
+ *   y          out_dtype, [B,T,C] (time_major = 0) or [T,B,C]
+ * With nsec == 0 there is no state: state_in and state_out are ignored and only the affine applies.
+ * Stateless like every other entry point: the state lives in the caller's buffers, the library keeps nothing between
+ * calls, and what depends on the coefficients alone travels with the kernel arguments.  Two kernels: a tile-walking
+ * chunk scan (nsec <= 5, C, T and x_row_stride multiples of 4, x 16-byte aligned) whose tiles of 512 samples are
+ * left-aligned in the piece -- pieces that are whole tiles give the bits of the one-shot call -- and a stateful
+ * row-walking kernel for everything else (any T, C, stride, alignment; nsec <= 8).  Neither computes statistics: the
+ * z-score of csn_eeg_bandpass_znorm is per call, this normalisation is the caller's fixed per-channel affine. */
+int csn_eeg_bandpass_stream(const float* x, int64_t x_row_stride, int B, int C, int T,
+                            const double* sos, int nsec, const double* state_in, double* state_out,
+                            const float* mean, const float* inv_std,
+                            void* y, int out_dtype, int time_major, csnStream_t stream);
+/* Which kernel a call with these arguments runs: 1 = tile-walking scan, 0 = stateful row-walking kernel.  Host only. */
+int csn_eeg_bandpass_stream_path(const float* x, int64_t x_row_stride, int C, int T, int nsec);
 
 /* ------------------------------------------------------------------------------------
  * K3  stacked LSTM, gate order i,f,g,o, nn.LSTM parameter layout; zero initial state, or (h0, c0) on a plan
