@@ -159,7 +159,13 @@ size_t csn_lstm_workspace_bytes(const csnLstmDesc* d, int training);
  * re-zeroes per call only what it dirties (flag lines, carried dc). */
 int csn_lstm_workspace_init(const csnLstmPlan* plan, void* workspace, csnStream_t stream);
 
-/* x: element (b,t,i) at x[b*x_stride_b + t*x_stride_t + i] (float32).
+/* x: element (b,t,i) at x[b*x_stride_b + t*x_stride_t + i] (float32).  The strides are in ELEMENTS and may be any
+ *   non-negative values, 0 included (a broadcast row), in either order (x_stride_b < x_stride_t is a time-major
+ *   buffer); the innermost stride is 1.  x needs the 4-byte alignment of a float only: a base on 16 bytes with
+ *   both strides multiples of 4 (and, for the row-major copy, I % 8 == 0) merely selects 16-byte loads.  x is never
+ *   written, and it is not read after csn_lstm_forward has returned its work to `stream`: the forward re-lays it out
+ *   into the workspace and everything else, csn_lstm_backward included (which takes no x), reads those copies, so work
+ *   enqueued on `stream` behind the call may overwrite x.  (tests/test_gpu_lstm_input_views.py)
  * w_ih/w_hh/b_ih/b_hh: [host] arrays of L device pointers to float32 parameters
  *   weight_ih_l{k}[4H,I_k], weight_hh_l{k}[4H,H], bias_ih_l{k}[4H], bias_hh_l{k}[4H].
  * h0, c0: optional [L,B,H] float32 initial state (NULL = zeros), dense, 16-B aligned.
