@@ -99,6 +99,9 @@ SIGNATURES = {
     "csn_l2_topk_scratch_bytes": (_c_size_t, [_c_i64, _c_i64]),
     "csn_l2_topk": (_c_int, [_c_void_p, _c_void_p, _c_i64, _c_i64, _c_int, _c_int, _c_void_p, _c_void_p,
                              _c_void_p, _c_void_p]),
+    "csn_l2_topk_tiled_scratch_bytes": (_c_size_t, [_c_i64, _c_i64, _c_int]),
+    "csn_l2_topk_tiled": (_c_int, [_c_void_p, _c_void_p, _c_i64, _c_i64, _c_int, _c_int, _c_int, _c_void_p, _c_void_p,
+                                   _c_void_p, _c_void_p, _c_void_p]),
 }
 
 
@@ -596,3 +599,23 @@ def l2_topk(gallery, query, k):
     dist = torch.empty((Nq, k), dtype=torch.float32, device=g.device)
     _check(lib.csn_l2_topk(_ptr(g), _ptr(q), Ng, Nq, D, k, _ptr(idx), _ptr(dist), _ptr(scratch), _stream()))
     return dist, idx
+
+
+def l2_topk_tiled(gallery, query, k, splits=0, dist64=False):
+    """csn_l2_topk_tiled: k up to 1024, no [Nq,Ng] scratch.  -> (dist, idx), or (dist, idx, dist64) with dist64=True."""
+    _need_cuda(gallery, query)
+    g, q = gallery.float().contiguous(), query.float().contiguous()
+    Ng, D = g.shape
+    Nq = q.shape[0]
+    lib = load()
+    nbytes = lib.csn_l2_topk_tiled_scratch_bytes(Ng, Nq, k)
+    if nbytes == 0:
+        raise CsnError(f"libcsn_hip: {lib.csn_last_error().decode()}")
+    with torch.cuda.device(g.device):
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=g.device)
+        idx = torch.empty((Nq, k), dtype=torch.int64, device=g.device)
+        dist = torch.empty((Nq, k), dtype=torch.float32, device=g.device)
+        d64 = torch.empty((Nq, k), dtype=torch.float64, device=g.device) if dist64 else None
+        _check(lib.csn_l2_topk_tiled(_ptr(g), _ptr(q), Ng, Nq, D, k, splits, _ptr(idx), _ptr(dist), _ptr(d64), _ptr(scratch),
+                                     _stream()))
+    return (dist, idx, d64) if dist64 else (dist, idx)

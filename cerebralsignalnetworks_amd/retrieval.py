@@ -3,7 +3,7 @@
 ``evaluate`` keeps the signature of /root/reference/utils/Utilities.py:28
 (``evaluate(FLAGS, gallery_features, query_features, gallery_labels, query_labels, dataset)``
 -> ``(Recall_Total, Precision_Total)``); the ``faiss.IndexFlatL2`` add/search of :45-55 is the
-HIP kernel ``csn_l2_topk``.  ``evaluate_full`` additionally returns top-1 accuracy and (D, I).
+HIP kernel ``csn_l2_topk`` or, for k > 64 and large problems, ``csn_l2_topk_tiled`` (same bits).  ``evaluate_full`` additionally returns top-1 accuracy and (D, I).
 """
 import numpy as np
 import torch
@@ -11,13 +11,51 @@ import torch
 from . import cabi
 
 
-def l2_search(gallery_features, query_features, k, device=None):
-    """-> (D[nq,k] float32 squared distances, I[nq,k] int64) as numpy arrays."""
+MATRIX_SCRATCH_BUDGET = 1 << 30      # bytes of [Nq,Ng] float64 from which on the matrix form (csn_l2_topk) is not used
+MATRIX_MAX_K = 64                    # csn_l2_topk's k limit
+
+
+def _takes_tiled(Ng, Nq, k):
+    """csn_l2_topk_tiled where csn_l2_topk cannot serve (k > 64, or a distance matrix of the budget or more), which is
+    also where it was measured to be the faster one (32768 x 4096 x 768: 1.7 x at k = 5, 2.3 x at k = 64); csn_l2_topk
+    below, where it was the faster one at the one shape measured (2048 x 512 x 768, k = 5: 0.17 against 0.25 ms) --
+    DESIGN.md section 13, profiles/l2_topk_tiled_bench.json.  Both return the same bits, so no caller can tell."""
+    return k > MATRIX_MAX_K or Ng * Nq * 8 >= MATRIX_SCRATCH_BUDGET
+
+
+def l2_search(gallery_features, query_features, k, device=None, dist64=False):
+    """-> (D[nq,k] squared distances, I[nq,k] int64) as numpy arrays; D is float32, or with ``dist64=True`` the float64
+    values the selection ran on (always the tiled kernel).  1 <= k <= min(1024, Ng)."""
     device = device or torch.device("cuda", torch.cuda.current_device())
     g = torch.as_tensor(np.asarray(gallery_features, dtype=np.float32)).reshape(len(gallery_features), -1).to(device)
     q = torch.as_tensor(np.asarray(query_features, dtype=np.float32)).reshape(len(query_features), -1).to(device)
-    D, I = cabi.l2_topk(g, q, k)
+    if dist64:
+        _, I, D = cabi.l2_topk_tiled(g, q, k, dist64=True)
+    elif _takes_tiled(g.shape[0], q.shape[0], k):
+        D, I = cabi.l2_topk_tiled(g, q, k)
+    else:
+        D, I = cabi.l2_topk(g, q, k)
     return D.cpu().numpy(), I.cpu().numpy()
+
+
+def merge_topk(D_parts, I_parts, k):
+    """Exact merge of candidate lists: D_parts / I_parts are sequences of [nq, k_p] arrays (float64 distances, int64
+    indices into one common numbering); -> (D[nq,k] float64, I[nq,k] int64), the k smallest under (distance, index),
+    ascending.  Padding entries (+inf, -1) are dropped; every query must have at least k real candidates."""
+    D = np.concatenate([np.asarray(d, dtype=np.float64).reshape(len(d), -1) for d in D_parts], axis=1)
+    I = np.concatenate([np.asarray(i, dtype=np.int64).reshape(len(i), -1) for i in I_parts], axis=1)
+    if D.shape != I.shape:
+        raise ValueError(f"merge_topk: distances {D.shape} and indices {I.shape} differ in shape")
+    pad = I < 0
+    if D.shape[1] < k or ((~pad).sum(axis=1) < k).any():
+        raise ValueError(f"merge_topk: fewer than k={k} candidates for a query")
+    Dk = np.where(pad, np.inf, D)
+    Ik = np.where(pad, np.iinfo(np.int64).max, I)          # padding sorts behind every real entry, whatever its distance
+    Dout, Iout = np.empty((len(D), k), np.float64), np.empty((len(D), k), np.int64)
+    for r in range(len(D)):
+        o = np.lexsort((Ik[r], Dk[r]))[:k]
+        Dout[r], Iout[r] = D[r, o], I[r, o]
+    return Dout, Iout
 
 
 def _bookkeeping(I, gallery_labels, query_labels, class_id_to_str, class_str_to_id, topK):
@@ -84,25 +122,53 @@ def _all_gather_rows(local, group=None):
 
 
 def evaluate_distributed(FLAGS, gallery_features, query_features, gallery_labels, query_labels, dataset,
-                         search_fn=None, group=None):
+                         search_fn=None, group=None, shard_gallery=False):
     """Multi-rank evaluation: every rank holds the embeddings of ITS shard of the gallery
     and of the queries (the pattern of PerilsEEGDataset.py:191-215, where shards are gathered to rank 0).  The
     gallery is all-gathered and kept replicated, every rank searches its own queries against it (csn_l2_topk),
     and the per-query neighbour lists are gathered so that every rank reports the same Recall / Precision / top-1
     as a single-process ``evaluate_full`` over the concatenated data.  Labels are the reference's label dicts.
-    ``search_fn(gallery, query, k) -> (D, I)`` defaults to the HIP search."""
+    ``search_fn(gallery, query, k) -> (D, I)`` defaults to the HIP search.
+
+    ``shard_gallery=True`` keeps the gallery where it is: the queries (the small side) are all-gathered, every rank
+    searches all of them against its own shard with k_r = min(topK, shard size), adds its base offset (the row's index in
+    the rank-ordered concatenation that the replicated form builds), the candidate lists travel as float64 distances +
+    int64 indices padded with (+inf, -1), and every rank merges them exactly (``merge_topk``).  The returned dict is the
+    replicated form's.  ``search_fn`` must return float64 distances here (default ``l2_search(..., dist64=True)``): two
+    distinct float64 distances can collide in float32, and a float32 merge would order them by index."""
     import torch.distributed as dist
     if not (dist.is_available() and dist.is_initialized()):
         return evaluate_full(FLAGS, gallery_features, query_features, gallery_labels, query_labels, dataset)
     topK = FLAGS.topK
-    search = search_fn or l2_search
     by_id = {v["ClassId"]: v for v in list(gallery_labels) + list(query_labels)}
-    gal, _ = _all_gather_rows(np.asarray(gallery_features, dtype=np.float32).reshape(len(gallery_features), -1), group)
-    gal_ids, _ = _all_gather_rows(np.array([l["ClassId"] for l in gallery_labels], dtype=np.int64), group)
     qry = np.asarray(query_features, dtype=np.float32).reshape(len(query_features), -1)
-    D_loc, I_loc = search(gal, qry, topK) if len(qry) else (np.zeros((0, topK), np.float32), np.zeros((0, topK), np.int64))
-    I_all, _ = _all_gather_rows(np.asarray(I_loc, dtype=np.int64), group)
-    D_all, _ = _all_gather_rows(np.asarray(D_loc, dtype=np.float32), group)
+    if shard_gallery:
+        gal_ids, shard_sizes = _all_gather_rows(np.array([l["ClassId"] for l in gallery_labels], dtype=np.int64), group)
+        search = search_fn or (lambda g, q, k: l2_search(g, q, k, dist64=True))
+        gal = np.asarray(gallery_features, dtype=np.float32).reshape(len(gallery_features), qry.shape[1])
+        qry_all, _ = _all_gather_rows(qry, group)
+        base = sum(shard_sizes[:dist.get_rank(group)])
+        k_r = min(topK, len(gal))
+        D_loc = np.full((len(qry_all), topK), np.inf, dtype=np.float64)
+        I_loc = np.full((len(qry_all), topK), -1, dtype=np.int64)
+        if k_r > 0 and len(qry_all):
+            D_r, I_r = search(gal, qry_all, k_r)
+            if np.asarray(D_r).dtype != np.float64:
+                raise TypeError("evaluate_distributed(shard_gallery=True): search_fn must return float64 distances")
+            D_loc[:, :k_r], I_loc[:, :k_r] = D_r, np.asarray(I_r, dtype=np.int64) + base
+        world = dist.get_world_size(group)
+        D_parts, _ = _all_gather_rows(D_loc, group)
+        I_parts, _ = _all_gather_rows(I_loc, group)
+        D64, I_all = merge_topk(D_parts.reshape(world, len(qry_all), topK), I_parts.reshape(world, len(qry_all), topK), topK)
+        with np.errstate(over="ignore"):
+            D_all = D64.astype(np.float32)          # inf where the float64 distance overflows float32, like out_dist
+    else:
+        search = search_fn or l2_search
+        gal, _ = _all_gather_rows(np.asarray(gallery_features, dtype=np.float32).reshape(len(gallery_features), -1), group)
+        gal_ids, _ = _all_gather_rows(np.array([l["ClassId"] for l in gallery_labels], dtype=np.int64), group)
+        D_loc, I_loc = search(gal, qry, topK) if len(qry) else (np.zeros((0, topK), np.float32), np.zeros((0, topK), np.int64))
+        I_all, _ = _all_gather_rows(np.asarray(I_loc, dtype=np.int64), group)
+        D_all, _ = _all_gather_rows(np.asarray(D_loc, dtype=np.float32), group)
     q_ids, _ = _all_gather_rows(np.array([l["ClassId"] for l in query_labels], dtype=np.int64), group)
     # label dicts by class id: every rank needs the dict of every class that occurs anywhere
     ids_known = sorted(by_id)
@@ -113,4 +179,3 @@ def evaluate_distributed(FLAGS, gallery_features, query_features, gallery_labels
     recall, precision, scores, top1 = _bookkeeping(I_all, [by_id[int(k)] for k in gal_ids], [by_id[int(k)] for k in q_ids],
                                                    dataset.class_id_to_str, dataset.class_str_to_id, topK)
     return dict(Recall_Total=recall, Precision_Total=precision, class_scores=scores, top1=top1, D=D_all, I=I_all)
-

@@ -392,6 +392,22 @@ size_t csn_l2_topk_scratch_bytes(int64_t Ng, int64_t Nq);
 int csn_l2_topk(const float* gallery, const float* query, int64_t Ng, int64_t Nq, int D, int k,
                 int64_t* out_idx, float* out_dist, void* scratch, csnStream_t stream);
 
+/* K8, tiled form: the same search (utils/Utilities.py:45-55) without the [Nq,Ng] distance matrix, for k up to 1024.
+ * A workgroup owns 64 queries and one of `splits` contiguous ranges of gallery rows; it computes 64 x 64 distance tiles
+ * in registers, keeps a sorted list of the k best per query, and a second kernel merges the ranges' lists.
+ *   1 <= k <= min(1024, Ng); inputs finite float32; splits = 0: the library chooses (at most 64), > 0: forced (tests,
+ *   tuning; more than the gallery allows is clamped).  Null pointers (other than out_dist64), splits < 0 and sizes <= 0
+ *   are refused on the host before any launch; the scratch function returns 0 for arguments the call refuses.
+ *   Distances: acc = 0.0; for d = 0 .. D-1 ascending: df = (double)q[d] - (double)g[d]; acc = fma(df, df, acc) -- one chain
+ *   per pair, the bits of csn_l2_topk.  Selection: the k smallest under (float64 distance, gallery index), ascending.
+ *   out_dist64 (may be NULL) holds those float64 distances, out_dist their float32 rounding (inf where that overflows).
+ *   For k <= 64 out_idx and out_dist equal csn_l2_topk's exactly, for every value of splits.
+ *   scratch: csn_l2_topk_tiled_scratch_bytes(Ng, Nq, k) bytes = 2 buffers x S x Nq x k x 16 + S x Nq x 8 (rounded up to
+ *   256), S = min(ceil(Ng / 64), max(8, the library's choice of splits)) -- independent of Ng beyond 64 tiles. */
+size_t csn_l2_topk_tiled_scratch_bytes(int64_t Ng, int64_t Nq, int k);
+int csn_l2_topk_tiled(const float* gallery, const float* query, int64_t Ng, int64_t Nq, int D, int k, int splits,
+                      int64_t* out_idx, float* out_dist, double* out_dist64, void* scratch, csnStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
