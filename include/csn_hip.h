@@ -8,9 +8,10 @@
  * those call sites and cites it.  Signatures carry only plain pointers and sizes:
  * every `const T*` / `T*` is a DEVICE pointer unless marked [host]; `stream` is a
  * hipStream_t passed as void* (NULL = the default stream).  All work is enqueued on
- * `stream`; nothing synchronises the device.  Return value: 0 on success, non-zero
- * csnStatus otherwise, with a message in csn_last_error().  Shape / alignment
- * violations are rejected on the host before any launch.
+ * `stream` or ordered by it, and only the calls listed there wait for the device
+ * ("Stream contract" below).  Return value: 0 on success, non-zero csnStatus otherwise,
+ * with a message in csn_last_error().  Shape / alignment violations are rejected on the
+ * host before any launch.
  *
  * Tensors are dense row-major unless strides are given.  dtype codes: CSN_F32, CSN_BF16.
  */
@@ -25,6 +26,55 @@ extern "C" {
 #endif
 
 typedef void* csnStream_t;
+
+/* ------------------------------------------------------------------------------------
+ * Stream contract of every entry point that takes a csnStream_t (tests/test_gpu_stream_order.py runs each of them with
+ * inputs produced late on `stream`, outputs read and inputs overwritten on it directly behind the call and no other
+ * synchronisation -- evidence where it fails, not proof where it passes: DESIGN.md section 14).
+ *
+ * ORDER.  Everything the call enqueues -- kernels, memsets, copies, and the work the LSTM puts on streams of its own
+ * (a plan owns a side stream and seven per-layer streams) -- runs after everything the caller enqueued on `stream`
+ * before the call and before everything the caller enqueues on `stream` after it.  Work on the plan's own streams is
+ * forked from `stream` by an event and joined back to it by an event before the call returns.  The caller synchronises
+ * no other stream, and no entry point that takes a `stream` uses the default (NULL) stream unless it is `stream`.  (The one
+ * call that does use the NULL stream takes no `stream`: csn_lstm_status_read, under BLOCKING.)
+ *
+ * HOST.  The calls return once their work is enqueued; none waits for the device, except as listed under BLOCKING.
+ * [host] arguments (sos, the arrays of layer pointers, seg_end, flags, lengths) are read before the call returns and may
+ * be freed then.
+ *
+ * OVERWRITE.  When a call has returned, work enqueued on `stream` may overwrite or free EVERY device argument of it:
+ * inputs, scratch and -- once read -- outputs.  For the LSTM in particular:
+ *   csn_lstm_forward   copies x, every weight and bias, h0 and c0 into the workspace (re-laid out, in the compute dtype).
+ *                      Nothing later reads the caller's copies: csn_lstm_backward takes the weights, the transposes, the
+ *                      initial state and the input from the workspace, so an optimiser step enqueued on `stream` right
+ *                      behind the forward may already rewrite the parameters the matching backward is still to use.
+ *   csn_lstm_backward  reads from caller memory only its own arguments dy_last, dy_all, dh_n, dc_n (and, accumulating,
+ *                      the previous dw / db); all four may be overwritten behind it.  dw, db, dx, dh0, dc0 are complete
+ *                      in stream order behind it (the gradient-ready callback marks an earlier point per layer).
+ *   The workspace belongs to the plan's calls from a forward to its backward; the lengths are host memory (above).
+ *
+ * ANOTHER STREAM.  A plan (and its workspace) may be called on another stream than its previous call used, provided the
+ * new stream is ordered behind the old one (an event wait, or a synchronisation): every call leaves all of its work
+ * joined to the stream it was given.  Calls of one plan on streams NOT so ordered race on the workspace and on the
+ * plan's event pool.
+ *
+ * BLOCKING (the only entry points that wait for the device on the host):
+ *   csn_lstm_status_read   hipMemcpy to the host on the NULL stream: returns when the word has arrived.  The NULL stream
+ *                          does not wait for streams created with hipStreamNonBlocking (PyTorch's side streams are):
+ *                          the caller synchronises such a stream first if the word is to cover the work on it.
+ *   csn_lstm_profile_read  waits for the closing profile event of the last forward / backward.
+ *   csn_lstm_forward / csn_lstm_backward ON A PLAN WITH LENGTHS wait for the lengths upload of the plan's PREVIOUS call
+ *                          with lengths (a copy of 4 * B bytes; they reuse its pinned staging array) -- hence until `stream`
+ *                          has reached that copy; the first such call allocates the staging and device arrays.
+ *                          csn_lstm_plan_set_lengths itself only stores the lengths on the host.
+ *   csn_lstm_plan_destroy  frees the plan's streams and events (and, after lengths, device memory, which waits for the
+ *                          device): call it when the plan's work has completed.
+ * Not blocking, but host work beyond the launches: csn_lstm_plan_create computes the workspace layout and reads the
+ * environment (no device work); the first forward / backward of a plan creates its streams, and a call grows the event
+ * pool when it needs more events than any call before it; the first launch of a kernel with a large dynamic LDS
+ * allocation sets that function attribute once per process.
+ * ---------------------------------------------------------------------------------- */
 
 enum csnStatus {
   CSN_OK = 0,
