@@ -54,6 +54,9 @@ def build_parser():
     p.add_argument('--synthetic', type=int, default=0)
     p.add_argument('--embed_dim', type=int, default=128)
     p.add_argument('--lstm_layers', type=int, default=4)
+    p.add_argument('--lstm_dropout', type=float, default=0.0,
+                   help='nn.LSTM(dropout=p) between the LSTM layers of the STUDENT (0 = off); the teacher, which is never '
+                        'trained, runs without it, like the stochastic depth of the reference\'s ViT teacher')
     p.add_argument('--dtype', type=str, default="bf16", choices=["bf16", "f32"])
     p.add_argument('--time_low', type=int, default=0)
     p.add_argument('--time_high', type=int, default=495)
@@ -87,11 +90,11 @@ def main(argv=None):
     train_idx = split_indices(N, (0.8, 0.2), seed=43)[0].to(device)      # random_split([0.8, 0.2], seed 43)
 
     dtype = torch.bfloat16 if FLAGS.dtype == "bf16" else torch.float32
-    def make():
+    def make(dropout=0.0):
         backbone = Model(input_size=C, lstm_size=FLAGS.embed_dim, lstm_layers=FLAGS.lstm_layers,
-                         output_size=FLAGS.embed_dim, include_top=False, compute_dtype=dtype)
+                         output_size=FLAGS.embed_dim, include_top=False, compute_dtype=dtype, dropout=dropout)
         return backbone
-    student = MultiCropWrapper(make(), DINOHead(FLAGS.embed_dim, FLAGS.out_dim, FLAGS.use_bn_in_head,
+    student = MultiCropWrapper(make(FLAGS.lstm_dropout), DINOHead(FLAGS.embed_dim, FLAGS.out_dim, FLAGS.use_bn_in_head,
                                                 FLAGS.norm_last_layer)).to(device)
     teacher = MultiCropWrapper(make(), DINOHead(FLAGS.embed_dim, FLAGS.out_dim, FLAGS.use_bn_in_head)).to(device)
     teacher.load_state_dict(student.state_dict())

@@ -17,6 +17,7 @@ CSN_F32, CSN_BF16 = 0, 1
 STATUS_TIMEOUT, STATUS_NONFINITE, STATUS_STALE_SLOT = 1, 2, 4      # bits of csn_lstm_status_read (include/csn_hip.h)
 ABI_VERSION = 6
 LSTM_STATE = 0x100      # csn_lstm_plan_create flag CSN_LSTM_STATE (include/csn_hip.h)
+LSTM_DROPOUT = 0x200    # csn_lstm_plan_create flag CSN_LSTM_DROPOUT (include/csn_hip.h)
 GRAD_OVERWRITE, GRAD_ACCUMULATE = 0, 1      # csn_lstm_plan_set_grad_mode (include/csn_hip.h)
 SEG_DECAYED, SEG_SCALED = 1, 2              # per-segment flags of csn_flat_segments_prepare (include/csn_hip.h)
 
@@ -53,6 +54,8 @@ SIGNATURES = {
     "csn_lstm_plan_set_grad_callback": (_c_int, [_c_void_p, _c_void_p, _c_void_p]),
     "csn_lstm_plan_set_grad_mode": (_c_int, [_c_void_p, _c_int]),
     "csn_lstm_plan_set_lengths": (_c_int, [_c_void_p, ctypes.POINTER(ctypes.c_int32)]),
+    "csn_lstm_plan_set_dropout": (_c_int, [_c_void_p, _c_float, ctypes.c_uint64, ctypes.c_uint32]),
+    "csn_lstm_dropout_keep": (_c_int, [ctypes.c_uint64, ctypes.c_uint32, _c_float, _c_i64, _c_i64, _c_void_p]),
     "csn_lstm_workspace_bytes": (_c_size_t, [ctypes.POINTER(LstmDesc), _c_int]),
     "csn_lstm_forward": (_c_int, [_c_void_p, _c_void_p, _c_i64, _c_i64,
                                   ctypes.POINTER(_c_void_p), ctypes.POINTER(_c_void_p),
@@ -316,17 +319,20 @@ class LstmPlan:
     -- all per plan, the library has no global state) + one workspace; forward()/backward() enqueue on the
     current stream."""
 
-    def __init__(self, B, T, I, H, L, dtype, device, training=True, state=False):
+    def __init__(self, B, T, I, H, L, dtype, device, training=True, state=False, dropout=False):
         """state=True: a CSN_LSTM_STATE plan, which takes the state keywords of forward() / backward() (and runs the
-        per-step cell kernels, path 0 or 1)."""
+        per-step cell kernels, path 0 or 1).  dropout=True: a CSN_LSTM_DROPOUT plan, whose workspace holds the dropped
+        layer outputs and which takes set_dropout(p > 0)."""
         self.desc = LstmDesc(B, T, I, H, L, _dt(dtype))
         self.training = bool(training)
         self.state = bool(state)
+        self.dropout = bool(dropout)
         self.device = torch.device(device)
         lib = load()
         handle = _c_void_p()
         with torch.cuda.device(self.device):
-            _check(lib.csn_lstm_plan_create(ctypes.byref(self.desc), int(self.training) | (LSTM_STATE if self.state else 0),
+            _check(lib.csn_lstm_plan_create(ctypes.byref(self.desc), int(self.training) | (LSTM_STATE if self.state else 0) |
+                                            (LSTM_DROPOUT if self.dropout else 0),
                                             ctypes.byref(handle)))
         self._plan = handle
         nbytes = lib.csn_lstm_plan_workspace_bytes(self._plan)
@@ -344,7 +350,8 @@ class LstmPlan:
 
     def key(self):
         d = self.desc
-        return (d.B, d.T, d.I, d.H, d.L, d.dtype, self.training) + ((True,) if self.state else ())
+        return ((d.B, d.T, d.I, d.H, d.L, d.dtype, self.training) + ((True,) if self.state else ()) +
+                (("dropout plan",) if self.dropout else ()))
 
     def path(self):
         """0 generic cells, 1 per-diagonal bf16 launches, 2 weight-stationary forward, 3 + weight-stationary backward, 4 the
@@ -383,6 +390,13 @@ class LstmPlan:
         if len(vals) != self.desc.B:
             raise CsnError(f"LSTM lengths: {len(vals)} entries for a batch of {self.desc.B}")
         _check(load().csn_lstm_plan_set_lengths(self._plan, (ctypes.c_int32 * len(vals))(*vals)))
+
+    def set_dropout(self, p, seed=0, subsequence=0):
+        """Inter-layer dropout of the following forward() / backward() calls (csn_lstm_plan_set_dropout): probability p
+        in [0, 1] (0 = off), a 64-bit seed and a 32-bit subsequence (e.g. the data-parallel rank).  Sticky until set
+        again; a backward must run with the setting of its forward.  p > 0 needs a plan created with dropout=True."""
+        _check(load().csn_lstm_plan_set_dropout(self._plan, float(p), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                int(subsequence) & 0xFFFFFFFF))
 
     def dgates_copies(self):
         """Copies of the gate gradients the last backward wrote per step (csn_hip.h): 2, or 0 before any backward."""
@@ -479,6 +493,16 @@ class LstmPlan:
                                             ctypes.byref(bm), ctypes.byref(bl), ctypes.byref(bc)))
         return dict(fwd_ms=fm.value, fwd_launches=fl.value, fwd_cells=fc.value,
                     bwd_ms=bm.value, bwd_launches=bl.value, bwd_cells=bc.value)
+
+
+def lstm_dropout_keep(seed, subsequence, p, first, n):
+    """The dropout mask of csn_lstm_plan_set_dropout(p, seed, subsequence) for the elements first .. first + n - 1
+    (e = ((l T + t) B + b) H + u) as a numpy uint8 array, 1 = kept.  Host code: needs no GPU."""
+    import numpy as np
+    keep = np.empty(int(n), dtype=np.uint8)
+    _check(load().csn_lstm_dropout_keep(int(seed) & 0xFFFFFFFFFFFFFFFF, int(subsequence) & 0xFFFFFFFF, float(p), int(first),
+                                        int(n), keep.ctypes.data_as(_c_void_p)))
+    return keep
 
 
 def cosine_loss(student, teacher, want_grad=True, grad_scale=1.0):

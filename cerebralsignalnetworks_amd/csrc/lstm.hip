@@ -38,6 +38,7 @@
 #include "csn_common.h"
 #include "lstm_cell_blk.h"
 #include "lstm_cell_common.h"
+#include "lstm_dropout.h"
 #include "lstm_f32_persist.h"
 
 namespace csn {
@@ -45,6 +46,7 @@ namespace csn {
 struct LayerWs {
   size_t wih, whh, whht, wiht, whh_blk, whht_blk, bias, xproj, gates, c_all, h_all, dgates, dx, dc_carry, hblk[2],
       dgblk[2], h_blk_all, counters, dg_blk_all, bflags;
+  size_t h_drop;           // CSN_LSTM_DROPOUT plans, layers below the top: [T,B,H] compute dtype, what layer l + 1 reads in place of h_all
 };
 struct WsLayout {
   LayerWs layer[8];
@@ -63,7 +65,7 @@ static bool whole_chip() {       // (asked when a layout is made -- plan creatio
   return hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus >= 256;
 }
 
-static WsLayout make_layout(const csnLstmDesc& d, int training, const Options& opt) {
+static WsLayout make_layout(const csnLstmDesc& d, int training, bool dropout, const Options& opt) {
   WsLayout w{};
   w.il = cell_blk_supported(d.H, d.dtype, opt);
   // (the K-split weight-stationary kernels address their per-step hand-off slabs with 32-bit byte offsets from step 0: a
@@ -169,6 +171,8 @@ static WsLayout make_layout(const csnLstmDesc& d, int training, const Options& o
     w.tn_scratch = take(tn_bytes);
     w.colsum = take(colsum_scratch_bytes(G));
   }
+  // (behind everything else: a plan without the bit is laid out as it always was)
+  for (int l = 0; dropout && l + 1 < d.L; ++l) w.layer[l].h_drop = take(TB * H * es);
   w.total = off;
   return w;
 }
@@ -433,6 +437,10 @@ static int prof_pair(Prof& g_prof, int k, bool end, hipStream_t st) {   // k: 0 
 struct csnLstmPlan {
   csnLstmDesc d;
   int training;
+  int dropout = 0;            // created with CSN_LSTM_DROPOUT: the workspace holds h_drop, csn_lstm_plan_set_dropout takes p > 0
+  float drop_p = 0.f;         // csn_lstm_plan_set_dropout (sticky): 0 = off
+  uint64_t drop_seed = 0;
+  uint32_t drop_subsequence = 0;
   int state;                  // created with CSN_LSTM_STATE: accepts (h0, c0) / (h_n, c_n) and their gradients
   bool state_seen = false;    // a forward with a state has run: stateless forwards re-zero slot 0 (weight-stationary paths)
   int device;
@@ -467,7 +475,8 @@ extern "C" int csn_lstm_plan_create(const csnLstmDesc* d, int training, csnLstmP
   Plan* P = new Plan();
   P->d = *d;
   P->state = (training & CSN_LSTM_STATE) != 0;
-  P->training = (training & ~CSN_LSTM_STATE) != 0;
+  P->dropout = (training & CSN_LSTM_DROPOUT) != 0;
+  P->training = (training & ~(CSN_LSTM_STATE | CSN_LSTM_DROPOUT)) != 0;
   if (hipGetDevice(&P->device) != hipSuccess) {
     delete P;
     return fail(CSN_ERR_HIP, "csn_lstm_plan_create: hipGetDevice failed");
@@ -483,7 +492,7 @@ extern "C" int csn_lstm_plan_create(const csnLstmDesc* d, int training, csnLstmP
     const unsigned long long cmax = ((1ull << 32) - 1ull) / per_step;
     if (cmax >= 3 && (unsigned long long)P->opt.chunk > cmax - 2) P->opt.chunk = (int)(cmax - 2);
   }
-  P->w = make_layout(*d, P->training, P->opt);
+  P->w = make_layout(*d, P->training, P->dropout != 0, P->opt);
   *out = P;
   return CSN_OK;
 }
@@ -577,6 +586,16 @@ extern "C" int csn_lstm_plan_set_lengths(csnLstmPlan* P, const int32_t* lengths)
   }
   P->lengths.assign(lengths, lengths + P->d.B);
   P->t_eff = longest;
+  return CSN_OK;
+}
+
+extern "C" int csn_lstm_plan_set_dropout(csnLstmPlan* P, float p, uint64_t seed, uint32_t subsequence) {
+  CSN_REQUIRE(P != nullptr, "csn_lstm_plan_set_dropout: null plan");
+  CSN_REQUIRE(p >= 0.f && p <= 1.f, "csn_lstm_plan_set_dropout: p = %g outside [0, 1]", (double)p);      // (NaN fails both)
+  CSN_REQUIRE(p == 0.f || P->dropout, "csn_lstm_plan_set_dropout: p = %g, but the plan was created without CSN_LSTM_DROPOUT", (double)p);
+  P->drop_p = p;
+  P->drop_seed = seed;
+  P->drop_subsequence = subsequence;
   return CSN_OK;
 }
 
@@ -759,7 +778,7 @@ extern "C" size_t csn_lstm_workspace_bytes(const csnLstmDesc* d, int training) {
   if (check_desc("csn_lstm_workspace_bytes", d) != CSN_OK) return 0;
   Options opt = options_from_env();
   if ((training & CSN_LSTM_STATE) && d->dtype == CSN_F32) opt.no_persist = true;
-  return make_layout(*d, (training & ~CSN_LSTM_STATE) != 0, opt).total;
+  return make_layout(*d, (training & ~(CSN_LSTM_STATE | CSN_LSTM_DROPOUT)) != 0, (training & CSN_LSTM_DROPOUT) != 0, opt).total;
 }
 
 // C[M,N] = A[K,M]^T B[K,N] through the split-K slabs + their fixed-order reduction (the body of csn_gemm_tn)
@@ -792,8 +811,30 @@ static int mask_x(const Call& C, hipStream_t st) {
 // jobs every path shares
 // =============================================================================================
 // what layer l multiplies by W_ih, time-major from step 0: the re-laid-out x, or the outputs of the layer below (h_all from slot 1)
+// (with dropout on: the masked and scaled copy of those outputs, h_drop, which has no slot 0)
+static bool drop_on(const Call& C) { return C.P.dropout && C.P.drop_p > 0.f && C.NL > 1; }
 static const void* layer_input(const Call& C, int l) {
+  if (l > 0 && drop_on(C)) return C.ws + C.w.layer[l - 1].h_drop;
   return l == 0 ? (const void*)(C.ws + C.w.x_c) : (const void*)(C.ws + C.w.layer[l - 1].h_all + (size_t)C.B * C.H * C.es);
+}
+
+// Inter-layer dropout (csn_lstm_plan_set_dropout; lstm_dropout.hip), interface l = between layers l and l + 1, steps
+// [t_lo, t_hi]; both are no-ops unless the plan has the bit and p > 0.  The element index runs over the PLAN's T, so a
+// call with lengths draws the mask of the same call without them.
+//   forward : h_drop[l] <- mask * h_all[l] / (1 - p), in front of the GEMM that reads it
+//   backward: dx of layer l + 1 *= mask / (1 - p) in place, between its GEMM and the dh_n term of layer l
+static int drop_fwd(const Call& C, int l, int t_lo, int t_hi, hipStream_t on) {
+  if (!drop_on(C)) return CSN_OK;
+  const size_t BH = (size_t)C.B * C.H;
+  return launch_lstm_dropout_fwd(C.ws + C.w.layer[l].h_all + (size_t)(t_lo + 1) * BH * C.es, C.ws + C.w.layer[l].h_drop + (size_t)t_lo * BH * C.es,
+                                 (int64_t)(t_hi - t_lo + 1) * (int64_t)BH, ((uint64_t)l * C.T_full + t_lo) * BH, C.dt,
+                                 dropout_cfg(C.P.drop_p, C.P.drop_seed, C.P.drop_subsequence), on);
+}
+static int drop_bwd(const Call& C, int l, int t_lo, int t_hi, hipStream_t on) {
+  if (!drop_on(C)) return CSN_OK;
+  const size_t BH = (size_t)C.B * C.H;
+  return launch_lstm_dropout_bwd((float*)(C.ws + C.w.layer[l + 1].dx) + (size_t)t_lo * BH, (int64_t)(t_hi - t_lo + 1) * (int64_t)BH,
+                                 ((uint64_t)l * C.T_full + t_lo) * BH, dropout_cfg(C.P.drop_p, C.P.drop_seed, C.P.drop_subsequence), on);
 }
 
 // slot 0 of h_all / c_all of layer l = the initial state (the cells read it at t = 0; the dW_hh GEMM reads h_all slot 0
@@ -864,7 +905,8 @@ static bool ends_chunk(const Call& C, int t) { return (t + 1) % C.Cz == 0 || t =
 static int xproj_chunk_gemm(const Call& C, int l, int c, hipStream_t on) {
   const LayerWs& Ln = C.w.layer[l + 1];
   const Chunk k = chunk_at(C, c);
-  return gemm_nt(C.ws + C.w.layer[l].h_all + (size_t)(k.t0 + 1) * C.B * C.H * C.es, C.ws + Ln.wih, (const float*)(C.ws + Ln.bias),
+  if (int rc = drop_fwd(C, l, k.t0, k.t0 + k.nsteps - 1, on)) return rc;
+  return gemm_nt((const char*)layer_input(C, l + 1) + (size_t)k.t0 * C.B * C.H * C.es, C.ws + Ln.wih, (const float*)(C.ws + Ln.bias),
                  (float*)(C.ws + Ln.xproj) + (size_t)k.t0 * C.B * C.G, (int64_t)k.nsteps * C.B, C.G, C.H, C.dt, CSN_F32, 0, on, C.P.opt);
 }
 
@@ -877,6 +919,7 @@ static int dx_chunk_gemm(const Call& C, int l, int c, const float* dh_n, hipStre
   if (int rc = gemm_nt(C.ws + L.dgates + (size_t)t_lo * C.B * C.G * C.es, C.ws + L.wiht, nullptr, (float*)(C.ws + L.dx) + (size_t)t_lo * C.B * C.H,
                        (int64_t)k.nsteps * C.B, C.H, C.G, C.dt, CSN_F32, 0, on, C.P.opt))
     return rc;
+  if (int rc = drop_bwd(C, l - 1, t_lo, t_hi, on)) return rc;
   if (dh_n) return add_dh_n_rows(C, dh_n + (size_t)(l - 1) * C.B * C.H, (float*)(C.ws + L.dx), t_lo, t_hi, on);
   return CSN_OK;
 }
@@ -1077,6 +1120,7 @@ static int forward_f32p(Call& C, const FwdArgs& A) {
   if ((rc = prof_mark(g_prof, 0, st))) return rc;
   for (int l = 0; l < NL; ++l) {
     const LayerWs& L = w.layer[l];
+    if (l > 0 && (rc = drop_fwd(C, l - 1, 0, T - 1, st))) return rc;
     if ((rc = gemm_nt(layer_input(C, l), ws + L.wih, (const float*)(ws + L.bias), ws + L.xproj, C.TB, C.G, C.in_width(l), CSN_F32, CSN_F32, 0, st, C.P.opt)))
       return rc;
     F32PersistFwdArgs a{};
@@ -1142,6 +1186,7 @@ static int backward_f32p(Call& C, const BwdArgs& A) {
     CSN_LAUNCH_CHECK();
     // gradient w.r.t. this layer's input = dy of the layer below, whole sequence
     if (l > 0 && (rc = gemm_nt(ws + L.dgates, ws + L.wiht, nullptr, ws + L.dx, C.TB, H, G, CSN_F32, CSN_F32, 0, st, C.P.opt))) return rc;
+    if (l > 0 && (rc = drop_bwd(C, l - 1, 0, T - 1, st))) return rc;
   }
   if ((rc = prof_end(C, 1, n_launch, T * NL))) return rc;
   for (int l = NL - 1; l >= 0; --l) {
@@ -1585,6 +1630,7 @@ static int backward_persist(Call& C, const BwdArgs& A) {
   // gradient w.r.t. h_n of layer l - 1: added to row T-1 of layer l's input gradient once the GEMM of that chunk has
   // run (inline, or beside the recurrence in the next launch), before the launch that runs layer l - 1's first chunk
   // (with lengths: after the GEMM of EVERY chunk, at the rows whose last step lies in it)
+  // (dropout: the mask of that chunk goes between the two -- behind the launch that ran the GEMM, in front of the term)
   struct DhAdd { int l, t_lo, t_hi; };       // l = 0: none
   auto add_dh_n = [&](const DhAdd& q) -> int {
     return add_dh_n_rows(C, dh_n + (size_t)(q.l - 1) * B * H, (float*)(ws + w.layer[q.l].dx), q.t_lo, q.t_hi, st);
@@ -1608,6 +1654,7 @@ static int backward_persist(Call& C, const BwdArgs& A) {
   P.half_launches[1] = 0;
   BesideGemm pending[3];           // GEMMs of the chunks finished by the previous launch
   DhAdd pending_add[3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};  // dh_n term that follows pending[i] (layer 0: none)
+  DhAdd pending_drop[3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}; // layer and steps of pending[i]: what its dropout mask covers
   int npending = 0;
   if ((rc = prof_mark(g_prof, 2, st))) return rc;
   for (int dg = 0; dg < ndiag; ++dg) {
@@ -1645,6 +1692,7 @@ static int backward_persist(Call& C, const BwdArgs& A) {
       for (int i = 0; i < npending; ++i) {
         const BesideGemm& g = pending[i];
         if ((rc = gemm_nt(g.A, g.Bt, nullptr, g.C, g.M, g.N, g.K, CSN_BF16, CSN_F32, 0, st, P.opt))) return rc;
+        if ((rc = drop_bwd(C, pending_drop[i].l - 1, pending_drop[i].t_lo, pending_drop[i].t_hi, st))) return rc;
         if (pending_add[i].l && (rc = add_dh_n(pending_add[i]))) return rc;
       }
       npending = 0;
@@ -1661,10 +1709,12 @@ static int backward_persist(Call& C, const BwdArgs& A) {
       for (int i = 0; i < ns; ++i) a.slot[i].flags += (size_t)T * MT * kPersistFlagLine;
       ++P.half_launches[1];
     }
-    DhAdd launch_adds[3];
+    DhAdd launch_adds[3], launch_drops[3];
     int nadds = 0;
+    const int ndrops = npending;
     for (int i = 0; i < npending; ++i) {
       a.gemm[i] = pending[i];
+      launch_drops[i] = pending_drop[i];
       if (pending_add[i].l) launch_adds[nadds++] = pending_add[i];
     }
     npending = 0;
@@ -1673,6 +1723,8 @@ static int backward_persist(Call& C, const BwdArgs& A) {
     if ((rc = launch_bwd_persist(a, st, C.dlen))) return rc;
     if ((rc = prof_pair(g_prof, 1, true, st))) return rc;
     ++n_launch;
+    for (int i = 0; i < ndrops; ++i)
+      if ((rc = drop_bwd(C, launch_drops[i].l - 1, launch_drops[i].t_lo, launch_drops[i].t_hi, st))) return rc;
     for (int i = 0; i < nadds; ++i)
       if ((rc = add_dh_n(launch_adds[i]))) return rc;
     for (int i = 0; i < ns; ++i) {
@@ -1686,6 +1738,7 @@ static int backward_persist(Call& C, const BwdArgs& A) {
       const LayerWs& L = w.layer[l];
       const int t_hi = a.slot[i].t_hi, t_lo = t_hi - a.slot[i].nsteps + 1;
       pending_add[npending] = DhAdd{(dh_n && (chk[i] == 0 || C.dlen)) ? l : 0, t_lo, t_hi};
+      pending_drop[npending] = DhAdd{l, t_lo, t_hi};
       pending[npending++] = BesideGemm{(const bf16_t*)(ws + L.dgates) + (size_t)t_lo * B * G, (const bf16_t*)(ws + L.wiht),
                                        (float*)(ws + L.dx) + (size_t)t_lo * B * H, (t_hi - t_lo + 1) * B, H, (int)G};
     }

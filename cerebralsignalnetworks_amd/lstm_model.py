@@ -9,6 +9,8 @@ include_top)``; ``forward(x[B,T,C]) -> [B,output_size]`` or ``([B,output_size],
 (/root/reference/LSTMDistill.py:118-120): ``lstm.{weight_ih,weight_hh,bias_ih,bias_hh}_l{k}``,
 ``fc.*``, ``class_pred.*`` -- checkpoints round-trip with a stock ``nn.LSTM``.
 """
+import warnings
+
 import torch
 import torch.nn as nn
 
@@ -42,15 +44,51 @@ def _direct_grads(owner, params):
     return True, mode == "accumulate"
 
 
+def _dropout_p(owner):
+    """``owner.dropout`` as it is now (the attribute may have been assigned since construction): a float in [0, 1]."""
+    p = owner.dropout
+    if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0 <= p <= 1:
+        raise ValueError(f"dropout should be a number in range [0, 1] representing the probability of an element being "
+                         f"zeroed, got {p!r}")
+    return float(p)
+
+
+def _draw_dropout(owner):
+    """-> None when inter-layer dropout is off for this call, else (p, seed, subsequence) for plan.set_dropout.  On, as in
+    nn.LSTM.forward: the module is in train() mode, ``owner.dropout`` (read now) > 0 and there is a layer to drop into --
+    grad mode does not enter.  The 64-bit seed comes from the default CPU generator (no device sync, reproducible under
+    torch.manual_seed); the subsequence is ``owner.dropout_subsequence``, or the torch.distributed rank, so that ranks
+    seeded alike still draw different masks."""
+    p = _dropout_p(owner)
+    if not owner.training or p == 0.0 or owner.num_layers < 2:
+        return None
+    lo, hi = torch.randint(0, 2 ** 32, (2,), dtype=torch.int64).tolist()
+    sub = owner.dropout_subsequence
+    if sub is None:
+        dist = torch.distributed
+        sub = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+    return p, (hi << 32) | lo, int(sub)
+
+
+def _set_dropout(plan, drop):
+    """On every forward and backward: plans are shared between calls (a plan without the bit takes p = 0 only)."""
+    if drop is None:
+        plan.set_dropout(0.0)
+    else:
+        plan.set_dropout(*drop)
+
+
 class _LstmFunction(torch.autograd.Function):
     """Stacked LSTM over libcsn_hip.  A training forward keeps its state in a workspace that stays
     checked out until the matching backward has run, so several forwards (e.g. the multi-crop views of
     the DINO trainer) can be outstanding at once."""
 
     @staticmethod
-    def forward(ctx, x, owner, want_all, training, L, *params):
+    def forward(ctx, x, owner, want_all, training, drop, L, *params):
         w_ih, w_hh, b_ih, b_hh = params[0:L], params[L:2 * L], params[2 * L:3 * L], params[3 * L:4 * L]
-        plan = owner._checkout(x.shape[0], x.shape[1], x.device, training)
+        plan = owner._checkout(x.shape[0], x.shape[1], x.device, training, dropout=drop is not None)
+        _set_dropout(plan, drop)
+        ctx.drop = drop                     # kept with the node: the backward runs with the mask of its forward
         y_last, y_all = plan.forward(x, w_ih, w_hh, b_ih, b_hh, want_all=want_all)
         ctx.lease, ctx.L, ctx.want_all = _Lease(plan), L, want_all
         ctx.owner = owner
@@ -82,12 +120,13 @@ class _LstmFunction(torch.autograd.Function):
         dx = torch.empty(ctx.x_shape, dtype=torch.float32, device=dy_last.device) if ctx.need_dx else None
         plan.set_grad_callback(owner.grad_ready_hook if direct else None)
         plan.set_grad_mode(accumulate)      # on every backward: plans are shared between calls
+        _set_dropout(plan, ctx.drop)
         plan.backward(dy_last, dy_all if ctx.want_all else None, grads, dx=dx)
         ctx.lease.release()
         if direct:
-            return (dx, None, None, None, None, *([None] * (4 * L)))
+            return (dx, None, None, None, None, None, *([None] * (4 * L)))
         flat = [g for group in grads for g in group]
-        return (dx, None, None, None, None, *flat)
+        return (dx, None, None, None, None, None, *flat)
 
 
 class HipLSTM(nn.Module):
@@ -95,15 +134,27 @@ class HipLSTM(nn.Module):
 
     ``compute_dtype``: torch.bfloat16 (bf16 MFMA operands, f32 accumulate and cell state -- the
     fast path) or torch.float32 (exact-f32 MFMA -- the parity path).
+
+    ``dropout``: nn.LSTM's inter-layer dropout -- in train() mode the output sequence of every layer but the top one is
+    masked with probability ``dropout`` and scaled by 1/(1 - dropout) before the next layer reads it, inside the fused
+    multi-layer launches.  The attribute is read on every call, as nn.LSTM.forward reads it.
+    ``dropout_subsequence``: None = the torch.distributed rank.
     """
 
     MAX_IDLE_PLANS = 4      # workspaces are large (10 GB at cfg2): keep only a few idle ones
     _STATE_PLANS = False    # LSTM: plans created with CSN_LSTM_STATE
 
-    def __init__(self, input_size, hidden_size, num_layers=1, compute_dtype=torch.bfloat16):
+    def __init__(self, input_size, hidden_size, num_layers=1, compute_dtype=torch.bfloat16, dropout=0.0):
         super().__init__()
         self.input_size, self.hidden_size, self.num_layers = input_size, hidden_size, num_layers
         self.compute_dtype = compute_dtype
+        self.dropout = dropout
+        _dropout_p(self)
+        if dropout > 0 and num_layers == 1:
+            warnings.warn("dropout option adds dropout after all but last recurrent layer, so non-zero dropout expects "
+                          f"num_layers greater than 1, but got dropout={dropout} and num_layers={num_layers}")
+        self.dropout = float(dropout)
+        self.dropout_subsequence = None
         ref = nn.LSTM(input_size, hidden_size, num_layers=num_layers, batch_first=True)   # same init + key names
         for name, p in ref.named_parameters():
             self.register_parameter(name, nn.Parameter(p.detach().clone()))
@@ -115,8 +166,8 @@ class HipLSTM(nn.Module):
         self.direct_grads = False
         self.grad_ready_hook = None
 
-    def _checkout(self, B, T, device, training):
-        key = (B, T, str(device), bool(training), self.compute_dtype)
+    def _checkout(self, B, T, device, training, dropout=False):
+        key = (B, T, str(device), bool(training), self.compute_dtype) + (("dropout plan",) if dropout else ())
         pool = self._plans.setdefault(key, [])
         for plan in pool:
             if not plan.busy:
@@ -126,7 +177,7 @@ class HipLSTM(nn.Module):
             k, pl = idle.pop(0)
             self._plans[k].remove(pl)
         plan = cabi.LstmPlan(B, T, self.input_size, self.hidden_size, self.num_layers, self.compute_dtype, device,
-                             training=training, state=self._STATE_PLANS)
+                             training=training, state=self._STATE_PLANS, dropout=dropout)
         pool.append(plan)
         return plan
 
@@ -134,13 +185,14 @@ class HipLSTM(nn.Module):
         return [pl for lst in self._plans.values() for pl in lst]
 
     def forward(self, x, want_all=False):
+        _dropout_p(self)
         if not x.is_cuda:
             raise cabi.CsnError("HipLSTM runs on the GPU only (no CPU fallback); move the module and input to cuda")
         L = self.num_layers
         params = [getattr(self, f"{n}_l{k}") for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh") for k in range(L)]
         # (grad mode is off inside Function.forward, so "is a backward coming" is decided here)
         training = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))
-        y_last, y_all = _LstmFunction.apply(x, self, want_all, training, L, *params)
+        y_last, y_all = _LstmFunction.apply(x, self, want_all, training, _draw_dropout(self), L, *params)
         return (y_all, y_last) if want_all else y_last
 
 
@@ -151,10 +203,12 @@ class _LstmStateFunction(torch.autograd.Function):
     chunks of one recording are chained through their state)."""
 
     @staticmethod
-    def forward(ctx, x, h0, c0, owner, training, lengths, L, *params):
+    def forward(ctx, x, h0, c0, owner, training, lengths, drop, L, *params):
         w_ih, w_hh, b_ih, b_hh = params[0:L], params[L:2 * L], params[2 * L:3 * L], params[3 * L:4 * L]
-        plan = owner._checkout(x.shape[0], x.shape[1], x.device, training)
+        plan = owner._checkout(x.shape[0], x.shape[1], x.device, training, dropout=drop is not None)
         plan.set_lengths(lengths)           # on every forward: plans are shared between calls (None = every row is T)
+        _set_dropout(plan, drop)
+        ctx.drop = drop
         _, y_all, h_n, c_n = plan.forward(x, w_ih, w_hh, b_ih, b_hh, want_all=True, h0=h0, c0=c0, want_state=True)
         ctx.lease, ctx.L, ctx.owner = _Lease(plan), L, owner
         ctx.lengths = lengths               # kept with the node: the backward runs with the lengths of its forward
@@ -186,12 +240,13 @@ class _LstmStateFunction(torch.autograd.Function):
         plan.set_grad_callback(ctx.owner.grad_ready_hook if direct else None)
         plan.set_grad_mode(direct)
         plan.set_lengths(ctx.lengths)
+        _set_dropout(plan, ctx.drop)
         plan.backward(None, dy_all, grads, dx=dx, dh_n=dh_n, dc_n=dc_n, dh0=dh0, dc0=dc0)
         ctx.lease.release()
         if direct:
-            return (dx, dh0, dc0, None, None, None, None, *([None] * (4 * L)))
+            return (dx, dh0, dc0, None, None, None, None, None, *([None] * (4 * L)))
         flat = [g for group in grads for g in group]
-        return (dx, dh0, dc0, None, None, None, None, *flat)
+        return (dx, dh0, dc0, None, None, None, None, None, *flat)
 
 
 class LSTM(HipLSTM):
@@ -207,6 +262,9 @@ class LSTM(HipLSTM):
     ``PackedSequence``; the output is then a PackedSequence with the same batch_sizes and indices and (h_n, c_n) come
     back in the original batch order, as from nn.LSTM.  The plan is still keyed by (B, T): lengths are per call, and the
     work follows the longest row.
+
+    Inter-layer dropout: the constructor still refuses ``dropout != 0``; set the attribute (``lstm.dropout = p``), which is
+    read on every call as nn.LSTM.forward reads it, and is active in train() mode (HipLSTM).
 
     Runs on CSN_LSTM_STATE plans (include/csn_hip.h): with bf16 compute the path HipLSTM takes for the shape (the
     weight-stationary kernels where they apply), with float32 the per-step cells (path 0).  With bf16 compute, h0 is rounded to bf16 as
@@ -264,12 +322,13 @@ class LSTM(HipLSTM):
             bad = [n for n in lengths if n < 0 or n > x.shape[1]]
             if bad:
                 raise ValueError(f"LSTM: length {bad[0]} outside [0, T = {x.shape[1]}]")
+        _dropout_p(self)
         if not x.is_cuda:
             raise cabi.CsnError("LSTM runs on the GPU only (no CPU fallback); move the module and input to cuda")
         params = [getattr(self, f"{n}_l{k}") for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh") for k in range(L)]
         training = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params) or
                                                 any(t is not None and t.requires_grad for t in (h0, c0)))
-        y_all, h_n, c_n = _LstmStateFunction.apply(x, h0, c0, self, training, lengths, L, *params)
+        y_all, h_n, c_n = _LstmStateFunction.apply(x, h0, c0, self, training, lengths, _draw_dropout(self), L, *params)
         return y_all, (h_n, c_n)
 
 
@@ -278,11 +337,11 @@ class Model(nn.Module):
     ``MultiCropWrapper`` (utils/utils.py:607-612) without breaking forward."""
 
     def __init__(self, input_size=128, lstm_size=128, lstm_layers=1, output_size=128, include_top=True,
-                 n_classes=40, compute_dtype=torch.bfloat16):
+                 n_classes=40, compute_dtype=torch.bfloat16, dropout=0.0):
         super().__init__()
         self.input_size, self.lstm_size, self.lstm_layers = input_size, lstm_size, lstm_layers
         self.output_size, self.include_top = output_size, include_top
-        self.lstm = HipLSTM(input_size, lstm_size, lstm_layers, compute_dtype=compute_dtype)
+        self.lstm = HipLSTM(input_size, lstm_size, lstm_layers, compute_dtype=compute_dtype, dropout=dropout)
         self.fc = nn.Linear(lstm_size, output_size)
         if include_top:
             self.class_pred = nn.Linear(output_size, n_classes)
@@ -304,10 +363,10 @@ class LSTMModel(nn.Module):
     """
 
     def __init__(self, input_size, hidden_size, n_layers=2, out_features=384, number_of_classes=None,
-                 all_steps=False, compute_dtype=torch.bfloat16):
+                 all_steps=False, compute_dtype=torch.bfloat16, dropout=0.0):
         super().__init__()
         self.hidden_size, self.n_layer, self.input_size, self.all_steps = hidden_size, n_layers, input_size, all_steps
-        self.lstm = HipLSTM(input_size, hidden_size, n_layers, compute_dtype=compute_dtype)
+        self.lstm = HipLSTM(input_size, hidden_size, n_layers, compute_dtype=compute_dtype, dropout=dropout)
         self.fc = nn.Linear(hidden_size, out_features)
         if number_of_classes:
             self.class_pred = nn.Linear(out_features, number_of_classes)

@@ -177,6 +177,11 @@ typedef struct csnLstmPlan csnLstmPlan;
  * state.  A plan without the bit rejects every state argument and runs exactly as before.  The remaining bits:
  * != 0 = training. */
 #define CSN_LSTM_STATE 0x100
+/* `training` may also carry CSN_LSTM_DROPOUT: the plan can apply nn.LSTM's inter-layer dropout (csn_lstm_plan_set_dropout
+ * below).  Its workspace gains h_drop[l], [T,B,H] in the compute dtype, for every layer l < L-1 (197 MB at B 256, T 500,
+ * H 768, L 2, bf16, on 10 GB), laid out behind everything else.  Valid on training and inference plans, with or
+ * without CSN_LSTM_STATE.  Until a p > 0 is set the plan runs the launches and writes the bits of a plan without it. */
+#define CSN_LSTM_DROPOUT 0x200
 int csn_lstm_plan_create(const csnLstmDesc* d, int training, csnLstmPlan** out);
 void csn_lstm_plan_destroy(csnLstmPlan* plan);
 /* Bytes of device scratch ("workspace") a forward (+ backward) of this plan needs; 256-B aligned base.  The
@@ -302,6 +307,34 @@ int csn_lstm_plan_set_grad_mode(csnLstmPlan* plan, int mode);
  * ordered on one stream, or by the caller.
  * Null plan, a plan without CSN_LSTM_STATE, an entry outside [0, T]: CSN_ERR_INVALID_ARGUMENT (the setting is kept). */
 int csn_lstm_plan_set_lengths(csnLstmPlan* plan, const int32_t* lengths);
+
+/* Inter-layer dropout, with torch.nn.LSTM(dropout=p)'s meaning: for every layer l < L-1 the output sequence of layer l is
+ * multiplied element-wise by an independent Bernoulli(1-p) mask and by 1/(1-p) before layer l+1's input projection.
+ * NOT dropped: y_all, y_last, h_n, c_n, the recurrent h, the top layer's output.  With L = 1 it does nothing.  p = 0 is
+ * off (always accepted); p = 1 drops everything.  Sticky until set again, like the lengths, and it takes no stream: the
+ * setting a forward / backward finds when it is CALLED is the one it uses, and the matching backward must run with the
+ * setting of its forward (a wrapper that shares plans keeps (p, seed, subsequence) with the forward's autograd node and
+ * sets them again before the backward).  The caller decides when it is on (training mode); the library does not know.
+ * The mask is fully specified, the same on every path, and reproducible on a CPU (csn_lstm_dropout_keep):
+ *   element (l, t, b, u) of interface l (between layers l and l+1) has the 64-bit index e = ((l T + t) B + b) H + u with
+ *   the PLAN's T, B, H (a call with lengths draws the mask of the same call without them);
+ *   words = Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85) of
+ *   counter (lo32(e >> 2), hi32(e >> 2), subsequence, 0) under key (lo32(seed), hi32(seed)); the word used is e & 3;
+ *   keep iff word >= thr, thr = floor(float32(p) 2^32); at p = 1 nothing is kept, whatever the word.
+ * Forward, float32 arithmetic with s = 1.0f / (1.0f - p):  h_drop = keep ? (compute dtype)(float(h) * s) : 0 -- on a
+ * CSN_BF16 plan one more bf16 rounding.  Backward: the gradient that reaches layer l from layer l+1 (dgates W_ih,
+ * float32) becomes keep ? dx * s : 0 BEFORE dh_n[l] is added (h_n is not dropped); dW_ih of layer l+1 is taken against
+ * h_drop.  A dropped element is a selected zero, not a product: NaN / Inf there do not get through.  The gradient
+ * w.r.t. x (layer 0) is never masked.  With lengths the mask covers the steps the GEMMs cover.
+ * Cost: one element-wise launch in front of every next-layer input-projection GEMM and one behind every input-gradient
+ * GEMM of a layer >= 1 (lstm_dropout.hip); no recurrence or GEMM kernel differs.
+ * `subsequence` separates streams that share a seed (data-parallel ranks).
+ * Null plan, p outside [0, 1] or NaN, p > 0 on a plan without CSN_LSTM_DROPOUT: CSN_ERR_INVALID_ARGUMENT (the setting is
+ * kept). */
+int csn_lstm_plan_set_dropout(csnLstmPlan* plan, float p, uint64_t seed, uint32_t subsequence);
+/* The published definition of that mask, on the host: keep_host[i] = 1 if element e = first + i is kept, else 0, for
+ * i in [0, n).  Host code filling a host array: no device, no stream, usable on a machine without a GPU. */
+int csn_lstm_dropout_keep(uint64_t seed, uint32_t subsequence, float p, int64_t first, int64_t n, uint8_t* keep_host);
 
 /* The workspace's status word: 0 = ok.  Bit CSN_STATUS_TIMEOUT: a bounded in-kernel wait of a weight-stationary
  * kernel gave up at some point since the word was last cleared (the results of that forward / backward and of every
