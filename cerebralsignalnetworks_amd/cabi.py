@@ -18,6 +18,7 @@ STATUS_TIMEOUT, STATUS_NONFINITE, STATUS_STALE_SLOT = 1, 2, 4      # bits of csn
 ABI_VERSION = 6
 LSTM_STATE = 0x100      # csn_lstm_plan_create flag CSN_LSTM_STATE (include/csn_hip.h)
 LSTM_DROPOUT = 0x200    # csn_lstm_plan_create flag CSN_LSTM_DROPOUT (include/csn_hip.h)
+LSTM_REVERSE = 0x400    # csn_lstm_plan_create flag CSN_LSTM_REVERSE (include/csn_hip.h)
 GRAD_OVERWRITE, GRAD_ACCUMULATE = 0, 1      # csn_lstm_plan_set_grad_mode (include/csn_hip.h)
 SEG_DECAYED, SEG_SCALED = 1, 2              # per-segment flags of csn_flat_segments_prepare (include/csn_hip.h)
 
@@ -54,6 +55,7 @@ SIGNATURES = {
     "csn_lstm_plan_set_grad_callback": (_c_int, [_c_void_p, _c_void_p, _c_void_p]),
     "csn_lstm_plan_set_grad_mode": (_c_int, [_c_void_p, _c_int]),
     "csn_lstm_plan_set_lengths": (_c_int, [_c_void_p, ctypes.POINTER(ctypes.c_int32)]),
+    "csn_lstm_plan_set_io": (_c_int, [_c_void_p, _c_i64, _c_i64, _c_int]),
     "csn_lstm_plan_set_dropout": (_c_int, [_c_void_p, _c_float, ctypes.c_uint64, ctypes.c_uint32]),
     "csn_lstm_dropout_keep": (_c_int, [ctypes.c_uint64, ctypes.c_uint32, _c_float, _c_i64, _c_i64, _c_void_p]),
     "csn_lstm_workspace_bytes": (_c_size_t, [ctypes.POINTER(LstmDesc), _c_int]),
@@ -319,20 +321,23 @@ class LstmPlan:
     -- all per plan, the library has no global state) + one workspace; forward()/backward() enqueue on the
     current stream."""
 
-    def __init__(self, B, T, I, H, L, dtype, device, training=True, state=False, dropout=False):
+    def __init__(self, B, T, I, H, L, dtype, device, training=True, state=False, dropout=False, reverse=False):
         """state=True: a CSN_LSTM_STATE plan, which takes the state keywords of forward() / backward() (and runs the
         per-step cell kernels, path 0 or 1).  dropout=True: a CSN_LSTM_DROPOUT plan, whose workspace holds the dropped
-        layer outputs and which takes set_dropout(p > 0)."""
+        layer outputs and which takes set_dropout(p > 0).  reverse=True: a CSN_LSTM_REVERSE plan, which walks every
+        row backwards in time from its own last valid step (the reverse direction of a bidirectional layer)."""
         self.desc = LstmDesc(B, T, I, H, L, _dt(dtype))
         self.training = bool(training)
         self.state = bool(state)
         self.dropout = bool(dropout)
+        self.reverse = bool(reverse)
+        self._io = (0, 0, False)
         self.device = torch.device(device)
         lib = load()
         handle = _c_void_p()
         with torch.cuda.device(self.device):
             _check(lib.csn_lstm_plan_create(ctypes.byref(self.desc), int(self.training) | (LSTM_STATE if self.state else 0) |
-                                            (LSTM_DROPOUT if self.dropout else 0),
+                                            (LSTM_DROPOUT if self.dropout else 0) | (LSTM_REVERSE if self.reverse else 0),
                                             ctypes.byref(handle)))
         self._plan = handle
         nbytes = lib.csn_lstm_plan_workspace_bytes(self._plan)
@@ -351,7 +356,7 @@ class LstmPlan:
     def key(self):
         d = self.desc
         return ((d.B, d.T, d.I, d.H, d.L, d.dtype, self.training) + ((True,) if self.state else ()) +
-                (("dropout plan",) if self.dropout else ()))
+                (("dropout plan",) if self.dropout else ()) + (("reverse plan",) if self.reverse else ()))
 
     def path(self):
         """0 generic cells, 1 per-diagonal bf16 launches, 2 weight-stationary forward, 3 + weight-stationary backward, 4 the
@@ -391,6 +396,25 @@ class LstmPlan:
             raise CsnError(f"LSTM lengths: {len(vals)} entries for a batch of {self.desc.B}")
         _check(load().csn_lstm_plan_set_lengths(self._plan, (ctypes.c_int32 * len(vals))(*vals)))
 
+    def set_io(self, y_all_pitch=0, dy_all_pitch=0, dx_add=False):
+        """Where the following calls find y_all / dy_all and how they store dx (csn_lstm_plan_set_io).  A pitch is the
+        number of elements per (b, t) row, 0 = dense (H): forward(y_all=view) then writes, and backward(dy_all=view) reads,
+        a [B,T,H] view of a wider tensor in place -- one half of a [B,T,2H] buffer.  dx_add=True: backward ADDS the input
+        gradient to dx over the valid steps.  Sticky until set again."""
+        _check(load().csn_lstm_plan_set_io(self._plan, int(y_all_pitch), int(dy_all_pitch), int(bool(dx_add))))
+        self._io = (int(y_all_pitch), int(dy_all_pitch), bool(dx_add))
+
+    def _pitched(self, t, pitch, name):
+        """t must be a float32 [B,T,H] device view with strides (T * pitch, pitch, 1), 16-byte aligned."""
+        d = self.desc
+        _need_cuda(t)
+        pitch = pitch or d.H
+        if (t.dtype != torch.float32 or tuple(t.shape) != (d.B, d.T, d.H) or t.stride() != (d.T * pitch, pitch, 1)
+                or t.data_ptr() % 16):
+            raise CsnError(f"LSTM {name}: a float32 [B,T,H] view with pitch {pitch} is needed, got {t.dtype} "
+                           f"{tuple(t.shape)} strides {t.stride()}")
+        return t
+
     def set_dropout(self, p, seed=0, subsequence=0):
         """Inter-layer dropout of the following forward() / backward() calls (csn_lstm_plan_set_dropout): probability p
         in [0, 1] (0 = off), a 64-bit seed and a 32-bit subsequence (e.g. the data-parallel rank).  Sticky until set
@@ -407,23 +431,36 @@ class LstmPlan:
         (csn_hip.h); 0 under CSN_NO_HALF_TILES=1."""
         return load().csn_lstm_plan_half_tile_launches(self._plan, which)
 
-    def forward(self, x_bti, w_ih, w_hh, b_ih, b_hh, want_all=False, h0=None, c0=None, want_state=False):
+    def forward(self, x_bti, w_ih, w_hh, b_ih, b_hh, want_all=False, h0=None, c0=None, want_state=False, y_all=None,
+                state_out=None):
         """-> (y_last, y_all); with want_state=True -> (y_last, y_all, h_n, c_n).  h0 / c0: [L,B,H] initial state or
-        None (zeros); the state keywords need a plan created with state=True."""
+        None (zeros); the state keywords need a plan created with state=True.  y_all: a [B,T,H] view to write every step
+        into (its pitch set with set_io) instead of a new tensor.  state_out: (h_n, c_n), dense float32 [L,B,H] tensors (or
+        slices of larger ones) to write the final state into, with want_state=True."""
         d = self.desc
         _need_cuda(x_bti)
         if x_bti.dtype != torch.float32 or x_bti.stride(2) != 1:
             x_bti = x_bti.float().contiguous()
         assert x_bti.shape == (d.B, d.T, d.I), (tuple(x_bti.shape), (d.B, d.T, d.I))
         y_last = torch.empty((d.B, d.H), dtype=torch.float32, device=x_bti.device)
-        y_all = torch.empty((d.B, d.T, d.H), dtype=torch.float32, device=x_bti.device) if want_all else None
+        if y_all is not None:
+            y_all = self._pitched(y_all, self._io[0], "y_all")
+        elif want_all:
+            if self._io[0]:
+                raise CsnError("LSTM y_all: the plan has a y_all pitch set (set_io): pass the view to write into")
+            y_all = torch.empty((d.B, d.T, d.H), dtype=torch.float32, device=x_bti.device)
         ws = [[p.detach() for p in group] for group in (w_ih, w_hh, b_ih, b_hh)]
         for group in ws:
             for p in group:
                 assert p.dtype == torch.float32 and p.is_contiguous() and p.is_cuda
         h0, c0 = self._state_in(h0), self._state_in(c0)
-        h_n = torch.empty((d.L, d.B, d.H), dtype=torch.float32, device=x_bti.device) if want_state else None
-        c_n = torch.empty((d.L, d.B, d.H), dtype=torch.float32, device=x_bti.device) if want_state else None
+        if want_state and state_out is not None:
+            h_n, c_n = state_out
+            for out in state_out:
+                assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == (d.L, d.B, d.H) and out.is_cuda
+        else:
+            h_n = torch.empty((d.L, d.B, d.H), dtype=torch.float32, device=x_bti.device) if want_state else None
+            c_n = torch.empty((d.L, d.B, d.H), dtype=torch.float32, device=x_bti.device) if want_state else None
         with torch.cuda.device(self.device):
             _check(load().csn_lstm_forward(self._plan, _ptr(x_bti), x_bti.stride(0), x_bti.stride(1),
                                            _ptr_array(ws[0]), _ptr_array(ws[1]), _ptr_array(ws[2]), _ptr_array(ws[3]),
@@ -450,7 +487,7 @@ class LstmPlan:
         if dy_last is not None:
             dy_last = dy_last.float().contiguous()
         if dy_all is not None:
-            dy_all = dy_all.float().contiguous()
+            dy_all = self._pitched(dy_all, self._io[1], "dy_all") if self._io[1] else dy_all.float().contiguous()
         dh_n, dc_n = self._state_in(dh_n), self._state_in(dc_n)
         for out in (dh0, dc0):
             if out is not None:

@@ -299,6 +299,50 @@ __global__ void tb_to_bt_len_kernel(const float* __restrict__ src, float* __rest
   }
 }
 
+// ---- CSN_LSTM_REVERSE plans and csn_lstm_plan_set_io: the three batch-first <-> time-major passes
+// with a row walked backwards, a pitch on the caller's side, and an adding store.  n = len[b] (Tn without lengths) valid
+// steps of row b; step s of the recurrence is the caller's t = rev ? n - 1 - s : s, so slot n - t of h_all holds the output
+// at t of a reverse plan.  Calls with none of the three run the kernels above, unchanged.
+// y[(b Tn + t) pitch + h] = t < n ? h_all[slot][b][h] : 0
+template <typename T>
+__global__ void gather_y_all_io_kernel(const T* __restrict__ h_all, float* __restrict__ y, const int* __restrict__ len, int B, int Tn,
+                                       int H, int64_t pitch, int rev) {
+  const int64_t total = (int64_t)B * Tn * H;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+    const int64_t h = i % H, r = i / H, t = r % Tn, b = r / Tn;
+    const int64_t n = len != nullptr ? len[b] : Tn;
+    y[r * pitch + h] = t < n ? to_f32(h_all[((rev ? n - t : t + 1) * B + b) * (int64_t)H + h]) : 0.f;
+  }
+}
+// dst[s][b][h], s < Te  =  s < n && src ? src[(b Tn + t) pitch + h] : 0
+__global__ void bt_to_tb_io_kernel(const float* __restrict__ src, float* __restrict__ dst, const int* __restrict__ len, int B, int Tn,
+                                   int Te, int H, int64_t pitch, int rev) {
+  const int64_t total = (int64_t)B * Te * H;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+    const int64_t h = i % H, r = i / H, b = r % B, s = r / B;
+    const int64_t n = len != nullptr ? len[b] : Tn;
+    dst[i] = (src != nullptr && s < n) ? src[(b * Tn + (rev ? n - 1 - s : s)) * pitch + h] : 0.f;
+  }
+}
+// dst[b][t][i] (Tn steps per row) = or += src[s][b][i] for t < n; the padding is zeroed, or with add left as it is
+__global__ void tb_to_bt_io_kernel(const float* __restrict__ src, float* __restrict__ dst, const int* __restrict__ len, int B, int Tn,
+                                   int H, int rev, int add) {
+  const int64_t total = (int64_t)B * Tn * H;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+    const int64_t h = i % H, r = i / H, t = r % Tn, b = r / Tn;
+    const int64_t n = len != nullptr ? len[b] : Tn;
+    if (t < n) {
+      const float v = src[((rev ? n - 1 - t : t) * B + b) * (int64_t)H + h];
+      dst[i] = add ? dst[i] + v : v;
+    } else if (!add) {
+      dst[i] = 0.f;
+    }
+  }
+}
+
 // Gradient w.r.t. the initial hidden state of one layer (CSN_LSTM_STATE plans):
 //   out[b][j] = sum_k dg[b][k] Wt(j, k),  k in [0, 4H), dg = dgates at t = 0 [B, 4H] row-major,
 //   Wt = W_hh^T [H, 4H]: row-major (BLK = false, generic path) or fragment-major (BLK = true, per-diagonal path, 4H axis
@@ -453,6 +497,9 @@ struct csnLstmPlan {
   csnGradReadyFn grad_cb = nullptr;      // csn_lstm_plan_set_grad_callback
   void* grad_cb_user = nullptr;
   int grad_accumulate = 0;               // csn_lstm_plan_set_grad_mode: dw / db are added to, not overwritten
+  int reverse = 0;                       // created with CSN_LSTM_REVERSE: the layout passes walk every row backwards in time
+  int64_t y_pitch = 0, dy_pitch = 0;     // csn_lstm_plan_set_io: elements per (b, t) row of y_all / dy_all, 0 = dense (H)
+  int dx_add = 0;                        // csn_lstm_plan_set_io: dx is added to over the valid steps, not overwritten
   // csn_lstm_plan_set_lengths (empty = every row is T): the lengths of the next calls and the longest of them.  What a
   // call in progress derives from them lives in its Call, not here.  (len_dev: [B] int32 owned by the plan -- a state
   // plan's workspace is laid out exactly as a plain plan's)
@@ -476,7 +523,8 @@ extern "C" int csn_lstm_plan_create(const csnLstmDesc* d, int training, csnLstmP
   P->d = *d;
   P->state = (training & CSN_LSTM_STATE) != 0;
   P->dropout = (training & CSN_LSTM_DROPOUT) != 0;
-  P->training = (training & ~(CSN_LSTM_STATE | CSN_LSTM_DROPOUT)) != 0;
+  P->reverse = (training & CSN_LSTM_REVERSE) != 0;
+  P->training = (training & ~(CSN_LSTM_STATE | CSN_LSTM_DROPOUT | CSN_LSTM_REVERSE)) != 0;
   if (hipGetDevice(&P->device) != hipSuccess) {
     delete P;
     return fail(CSN_ERR_HIP, "csn_lstm_plan_create: hipGetDevice failed");
@@ -599,6 +647,20 @@ extern "C" int csn_lstm_plan_set_dropout(csnLstmPlan* P, float p, uint64_t seed,
   return CSN_OK;
 }
 
+extern "C" int csn_lstm_plan_set_io(csnLstmPlan* P, int64_t y_all_pitch, int64_t dy_all_pitch, int dx_add) {
+  CSN_REQUIRE(P != nullptr, "csn_lstm_plan_set_io: null plan");
+  const int64_t pitch[2] = {y_all_pitch, dy_all_pitch};
+  const char* const names[2] = {"y_all_pitch", "dy_all_pitch"};
+  for (int i = 0; i < 2; ++i)
+    CSN_REQUIRE(pitch[i] == 0 || (pitch[i] >= P->d.H && pitch[i] % 4 == 0),
+                "csn_lstm_plan_set_io: %s = %lld is neither 0 (dense) nor a multiple of 4 that is >= H = %d", names[i],
+                (long long)pitch[i], P->d.H);
+  P->y_pitch = y_all_pitch == P->d.H ? 0 : y_all_pitch;
+  P->dy_pitch = dy_all_pitch == P->d.H ? 0 : dy_all_pitch;
+  P->dx_add = dx_add != 0;
+  return CSN_OK;
+}
+
 // lengths of the call in progress -> the plan's device array, in stream order (every forward and backward that runs with
 // lengths uploads what the plan holds, so the kernels of a call read the lengths of that call); *dlen: that array, or null
 // for a plan without lengths
@@ -670,7 +732,9 @@ struct BwdArgs {
 // input gradient out of its time-major workspace form; with lengths the caller's rows have T_full steps, zeros behind the longest
 static int emit_dx(const Call& C, const float* dx_tm, float* dx, int64_t I, hipStream_t st) {
   const int B = C.B, T = C.T;
-  if (C.dlen != nullptr) tb_to_bt_len_kernel<<<csn::grid_for((int64_t)C.T_full * B * I), 256, 0, st>>>(dx_tm, dx, B, C.T_full, T, (int)I);
+  if (C.P.reverse || C.P.dx_add)
+    tb_to_bt_io_kernel<<<csn::grid_for((int64_t)C.T_full * B * I), 256, 0, st>>>(dx_tm, dx, C.dlen, B, C.T_full, (int)I, C.P.reverse, C.P.dx_add);
+  else if (C.dlen != nullptr) tb_to_bt_len_kernel<<<csn::grid_for((int64_t)C.T_full * B * I), 256, 0, st>>>(dx_tm, dx, B, C.T_full, T, (int)I);
   else csn::tb_to_bt_kernel<<<csn::grid_for((int64_t)T * B * I), 256, 0, st>>>(dx_tm, dx, B, T, (int)I);
   CSN_LAUNCH_CHECK();
   return CSN_OK;
@@ -778,7 +842,7 @@ extern "C" size_t csn_lstm_workspace_bytes(const csnLstmDesc* d, int training) {
   if (check_desc("csn_lstm_workspace_bytes", d) != CSN_OK) return 0;
   Options opt = options_from_env();
   if ((training & CSN_LSTM_STATE) && d->dtype == CSN_F32) opt.no_persist = true;
-  return make_layout(*d, (training & ~(CSN_LSTM_STATE | CSN_LSTM_DROPOUT)) != 0, (training & CSN_LSTM_DROPOUT) != 0, opt).total;
+  return make_layout(*d, (training & ~(CSN_LSTM_STATE | CSN_LSTM_DROPOUT | CSN_LSTM_REVERSE)) != 0, (training & CSN_LSTM_DROPOUT) != 0, opt).total;
 }
 
 // C[M,N] = A[K,M]^T B[K,N] through the split-K slabs + their fixed-order reduction (the body of csn_gemm_tn)
@@ -874,7 +938,7 @@ static int prep_row_major(const Call& C, const FwdArgs& A) {
   const int H = C.H, dt = C.dt;
   const int64_t G = C.G;
   int rc;
-  if ((rc = launch_cast_strided(A.x, A.xsb, A.xst, C.B, C.T, C.d.I, ws + w.x_c, dt, st))) return rc;
+  if ((rc = launch_cast_strided(A.x, A.xsb, A.xst, C.B, C.T, C.d.I, ws + w.x_c, dt, st, C.dlen, C.P.reverse))) return rc;
   if ((rc = mask_x(C, st))) return rc;
   for (int l = 0; l < C.NL; ++l) {
     const LayerWs& L = w.layer[l];
@@ -1223,9 +1287,11 @@ static int prep_fast(Call& C, const FwdArgs& A) {
       pa.njobs = 0;
     }
     PrepJob& J = pa.job[pa.njobs++];
-    J = PrepJob{kind, a_, b_, dst, n0, n1, n2, s0, s1, Hh, pr, pk, work, 0u, 0u};
+    J = PrepJob{kind, a_, b_, dst, n0, n1, n2, s0, s1, Hh, pr, pk, work, 0u, 0u, nullptr};
   };
-  job(kPrepCastX, A.x, nullptr, ws + w.x_c, B, T, d.I, A.xsb, A.xst, 0, 0, 0, TB * d.I);
+  // (the two x jobs of a reverse plan: perm_r = 1 and the lengths -- each row is read backwards from its own last step)
+  job(kPrepCastX, A.x, nullptr, ws + w.x_c, B, T, d.I, A.xsb, A.xst, 0, C.P.reverse, 0, TB * d.I);
+  pa.job[pa.njobs - 1].len = C.dlen;
   for (int l = 0; l < NL; ++l) {
     const LayerWs& L = w.layer[l];
     const int64_t I = C.in_width(l);
@@ -1250,7 +1316,8 @@ static int prep_fast(Call& C, const FwdArgs& A) {
   if (w.fuse_x) {
     // layer 0 multiplies x_t itself inside the weight-stationary kernel: fragment-major x and W_ih instead of
     // a [T, B, 4H] float32 projection written to and re-read from HBM
-    job(kPrepBlockifyX, A.x, nullptr, ws + w.x_blk, B, T, d.I, A.xsb, A.xst, (int64_t)Bpad, 0, 0, (int64_t)T * Bpad * d.I / 8);
+    job(kPrepBlockifyX, A.x, nullptr, ws + w.x_blk, B, T, d.I, A.xsb, A.xst, (int64_t)Bpad, C.P.reverse, 0, (int64_t)T * Bpad * d.I / 8);
+    pa.job[pa.njobs - 1].len = C.dlen;
     job(kPrepBlockify, A.w_ih[0], nullptr, ws + w.wih0_blk, G, d.I, 0, d.I, 1, H, 1, 0, G * d.I / 8);
   }
   if (prep_rc != CSN_OK) return prep_rc;
@@ -1781,6 +1848,18 @@ static int check_state_args(const Plan& P, const char* fn, const void* const* pt
   return CSN_OK;
 }
 
+// y_all of a reverse plan and / or with a pitch (csn_lstm_plan_set_io), with or without lengths
+static int gather_y_all_io(const Call& C, float* y_all) {
+  const LayerWs& top = C.w.layer[C.NL - 1];
+  const int64_t n = (int64_t)C.T_full * C.B * C.H, pitch = C.P.y_pitch ? C.P.y_pitch : C.H;
+  if (C.dt == CSN_BF16)
+    gather_y_all_io_kernel<bf16_t><<<grid_for(n), 256, 0, C.st>>>((const bf16_t*)(C.ws + top.h_all), y_all, C.dlen, C.B, C.T_full, C.H, pitch, C.P.reverse);
+  else
+    gather_y_all_io_kernel<float><<<grid_for(n), 256, 0, C.st>>>((const float*)(C.ws + top.h_all), y_all, C.dlen, C.B, C.T_full, C.H, pitch, C.P.reverse);
+  CSN_LAUNCH_CHECK();
+  return CSN_OK;
+}
+
 extern "C" int csn_lstm_forward(csnLstmPlan* Pp, const float* x, int64_t x_stride_b, int64_t x_stride_t,
                                 const float* const* w_ih, const float* const* w_hh, const float* const* b_ih,
                                 const float* const* b_hh, const float* h0, const float* c0, void* workspace,
@@ -1840,7 +1919,9 @@ extern "C" int csn_lstm_forward(csnLstmPlan* Pp, const float* x, int64_t x_strid
     if (y_all) {
       const int T = C.T_full;       // the caller's rows: zeros from each row's length on
       const int64_t n = (int64_t)T * B * H;
-      if (dt == CSN_BF16)
+      if (P.reverse || P.y_pitch) {
+        if ((rc = gather_y_all_io(C, y_all))) return rc;
+      } else if (dt == CSN_BF16)
         gather_y_all_len_kernel<bf16_t><<<grid_for(n), 256, 0, st>>>((const bf16_t*)(ws + top.h_all), y_all, dlen, B, T, H);
       else
         gather_y_all_len_kernel<float><<<grid_for(n), 256, 0, st>>>((const float*)(ws + top.h_all), y_all, dlen, B, T, H);
@@ -1864,7 +1945,9 @@ extern "C" int csn_lstm_forward(csnLstmPlan* Pp, const float* x, int64_t x_strid
     if ((rc = launch_upcast(ws + top.h_all + (size_t)T * B * H * es, dt, y_last, (int64_t)B * H, st))) return rc;
   if (y_all) {
     const int64_t n = (int64_t)T * B * H;
-    if (dt == CSN_BF16)
+    if (P.reverse || P.y_pitch) {
+      if ((rc = gather_y_all_io(C, y_all))) return rc;
+    } else if (dt == CSN_BF16)
       gather_y_all_kernel<bf16_t><<<grid_for(n), 256, 0, st>>>((const bf16_t*)(ws + top.h_all), y_all, B, T, H);
     else
       gather_y_all_kernel<float><<<grid_for(n), 256, 0, st>>>((const float*)(ws + top.h_all), y_all, B, T, H);
@@ -1916,7 +1999,10 @@ extern "C" int csn_lstm_backward(csnLstmPlan* Pp, const float* dy_last, const fl
     const int Te = C.T;
     if (Te > 0) {
       // zeros over the padding of dy
-      bt_to_tb_len_kernel<<<grid_for((int64_t)Te * B * H), 256, 0, st>>>(dy_all, buf, dlen, B, C.T_full, Te, H);
+      if (P.reverse || P.dy_pitch)
+        bt_to_tb_io_kernel<<<grid_for((int64_t)Te * B * H), 256, 0, st>>>(dy_all, buf, dlen, B, C.T_full, Te, H, P.dy_pitch ? P.dy_pitch : H, P.reverse);
+      else
+        bt_to_tb_len_kernel<<<grid_for((int64_t)Te * B * H), 256, 0, st>>>(dy_all, buf, dlen, B, C.T_full, Te, H);
       if (dy_last) add_at_end_kernel<<<grid_for((int64_t)BH), 256, 0, st>>>(dy_last, buf, dlen, 0, Te - 1, B, H);
       if (dh_n) add_at_end_kernel<<<grid_for((int64_t)BH), 256, 0, st>>>(dh_n + (NL - 1) * BH, buf, dlen, 0, Te - 1, B, H);
       CSN_LAUNCH_CHECK();
@@ -1925,7 +2011,7 @@ extern "C" int csn_lstm_backward(csnLstmPlan* Pp, const float* dy_last, const fl
       if ((rc = run_backward(C, A))) return rc;
     } else {
       // every row is empty: no recurrence, no parameter contribution
-      if (dx) CSN_HIP_CHECK(hipMemsetAsync(dx, 0, (size_t)C.T_full * B * d->I * 4, st));
+      if (dx && !P.dx_add) CSN_HIP_CHECK(hipMemsetAsync(dx, 0, (size_t)C.T_full * B * d->I * 4, st));
       for (int l = NL - 1; l >= 0; --l) {
         if (!P.grad_accumulate) {
           CSN_HIP_CHECK(hipMemsetAsync(dw_ih[l], 0, (size_t)(G * C.in_width(l)) * 4, st));
@@ -1965,7 +2051,10 @@ extern "C" int csn_lstm_backward(csnLstmPlan* Pp, const float* dy_last, const fl
   // gradient w.r.t. the top layer's outputs, time-major.  With only dy_last, no buffer is needed.
   const int T = C.T;
   if (dy_all) {
-    bt_to_tb_kernel<<<grid_for(C.TB * H), 256, 0, st>>>(dy_all, buf, B, T, H);
+    if (P.reverse || P.dy_pitch)
+      bt_to_tb_io_kernel<<<grid_for(C.TB * H), 256, 0, st>>>(dy_all, buf, nullptr, B, T, T, H, P.dy_pitch ? P.dy_pitch : H, P.reverse);
+    else
+      bt_to_tb_kernel<<<grid_for(C.TB * H), 256, 0, st>>>(dy_all, buf, B, T, H);
     CSN_LAUNCH_CHECK();
     if (dy_last) {
       add_rows_kernel<<<grid_for((int64_t)BH), 256, 0, st>>>(dy_last, buf + (size_t)(T - 1) * BH, (int64_t)BH);

@@ -148,6 +148,7 @@ struct PrepJob {
   int perm_r, perm_k;
   int64_t work;                      // work items (threads) of the job
   unsigned blk_begin, blk_count;     // filled by the launcher
+  const int* len;                    // x jobs with perm_r != 0 (reverse plans): [B] valid steps per row, null = n1 for all
 };
 struct PrepArgs {
   PrepJob job[kPrepMaxJobs];

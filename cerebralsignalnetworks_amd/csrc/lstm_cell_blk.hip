@@ -230,7 +230,15 @@ __global__ void __launch_bounds__(256) prep_multi_kernel(PrepArgs A) {
       bf16_t* dst = (bf16_t*)J.dst;
       if ((I & 7) == 0 && (J.s0 & 3) == 0 && (J.s1 & 3) == 0 && (reinterpret_cast<uintptr_t>(J.a) & 15) == 0) {
         for (int64_t c = gid; c < Bn * Tn * I / 8; c += stride) {     // 8 elements per thread and trip
-          const int64_t i = c * 8, i2 = i % I, r = i / I, b = r % Bn, t = r / Bn;
+          const int64_t i = c * 8, i2 = i % I, r = i / I, b = r % Bn;
+          int64_t t = r / Bn;
+          if (J.perm_r) {       // reverse plan: step t of row b is its n - 1 - t; from n on zeros, the padding is not read
+            t = (J.len != nullptr ? J.len[b] : Tn) - 1 - t;
+            if (t < 0) {
+              *reinterpret_cast<uint4*>(dst + i) = make_uint4(0u, 0u, 0u, 0u);
+              continue;
+            }
+          }
           const float4* sp = reinterpret_cast<const float4*>(J.a + b * J.s0 + t * J.s1 + i2);
           const float4 u = sp[0], v = sp[1];
           *reinterpret_cast<bf16x8*>(dst + i) = (bf16x8){(bf16_t)u.x, (bf16_t)u.y, (bf16_t)u.z, (bf16_t)u.w,
@@ -238,8 +246,10 @@ __global__ void __launch_bounds__(256) prep_multi_kernel(PrepArgs A) {
         }
       } else {
         for (int64_t i = gid; i < Bn * Tn * I; i += stride) {
-          const int64_t i2 = i % I, r = i / I, b = r % Bn, t = r / Bn;
-          dst[i] = (bf16_t)J.a[b * J.s0 + t * J.s1 + i2];
+          const int64_t i2 = i % I, r = i / I, b = r % Bn;
+          int64_t t = r / Bn;
+          if (J.perm_r) t = (J.len != nullptr ? J.len[b] : Tn) - 1 - t;
+          dst[i] = (bf16_t)(t >= 0 ? J.a[b * J.s0 + t * J.s1 + i2] : 0.f);
         }
       }
       break;
@@ -248,8 +258,16 @@ __global__ void __launch_bounds__(256) prep_multi_kernel(PrepArgs A) {
       const int64_t Bn = J.n0, Tn = J.n1, I = J.n2, Bpad = J.H, per_t = Bpad * I / 8, kblocks = I >> 5;
       bf16_t* dst = (bf16_t*)J.dst;
       for (int64_t ci = gid; ci < per_t * Tn; ci += stride) {
-        const int64_t t = ci / per_t, c = ci % per_t, blk = c >> 6, lane = c & 63;
+        const int64_t c = ci % per_t, blk = c >> 6, lane = c & 63;
         const int64_t r = (blk / kblocks) * 16 + (lane & 15), k = (blk % kblocks) * 32 + 8 * (lane >> 4);
+        int64_t t = ci / per_t;
+        if (J.perm_r && r < Bn) {      // reverse plan, as in kPrepCastX
+          t = (J.len != nullptr ? J.len[r] : Tn) - 1 - t;
+          if (t < 0) {
+            *reinterpret_cast<uint4*>(dst + ci * 8) = make_uint4(0u, 0u, 0u, 0u);
+            continue;
+          }
+        }
         bf16x8 v;
         if (r < Bn && ((J.s0 | J.s1) & 3) == 0 && (reinterpret_cast<uintptr_t>(J.a) & 15) == 0) {
           const float4* sp = reinterpret_cast<const float4*>(J.a + r * J.s0 + t * J.s1 + k);

@@ -72,26 +72,28 @@ int launch_upcast(const void* src, int dtype, float* dst, int64_t n, hipStream_t
 // Used for x[b][t][i] (strides s0=b, s1=t) -> time-major [T][B][I] in the compute dtype.
 template <typename T>
 __global__ void cast_strided_kernel(const float* __restrict__ src, int64_t s0, int64_t s1, int64_t n0, int64_t n1,
-                                    int64_t n2, T* __restrict__ dst) {
+                                    int64_t n2, T* __restrict__ dst, const int* __restrict__ len, int rev) {
   const int64_t total = n0 * n1 * n2;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
     const int64_t i2 = i % n2;
     const int64_t r = i / n2;       // r = i1*n0 + i0
-    const int64_t i0 = r % n0, i1 = r / n0;
-    dst[i] = from_f32<T>(src[i0 * s0 + i1 * s1 + i2]);
+    const int64_t i0 = r % n0;
+    int64_t i1 = r / n0;
+    if (rev) i1 = (len != nullptr ? len[i0] : n1) - 1 - i1;      // a reverse plan's row, backwards from its own last step
+    dst[i] = from_f32<T>(i1 >= 0 ? src[i0 * s0 + i1 * s1 + i2] : 0.f);
   }
 }
 
 int launch_cast_strided(const float* src, int64_t s0, int64_t s1, int64_t n0, int64_t n1, int64_t n2, void* dst,
-                        int dtype, hipStream_t st) {
+                        int dtype, hipStream_t st, const int* len, int rev) {
   const int64_t total = n0 * n1 * n2;
   if (total <= 0) return CSN_OK;
   const unsigned grid = capped_grid(total, 256);
   if (dtype == CSN_BF16)
-    cast_strided_kernel<bf16_t><<<grid, 256, 0, st>>>(src, s0, s1, n0, n1, n2, (bf16_t*)dst);
+    cast_strided_kernel<bf16_t><<<grid, 256, 0, st>>>(src, s0, s1, n0, n1, n2, (bf16_t*)dst, len, rev);
   else
-    cast_strided_kernel<float><<<grid, 256, 0, st>>>(src, s0, s1, n0, n1, n2, (float*)dst);
+    cast_strided_kernel<float><<<grid, 256, 0, st>>>(src, s0, s1, n0, n1, n2, (float*)dst, len, rev);
   CSN_LAUNCH_CHECK();
   return CSN_OK;
 }

@@ -249,6 +249,41 @@ class _LstmStateFunction(torch.autograd.Function):
         return (dx, dh0, dc0, None, None, None, None, None, *flat)
 
 
+def _forward_packed(module, name, x, hx, lengths):
+    """LSTM / BiLSTM on a PackedSequence: the padded batch with the lengths it carries, and the output packed again with
+    the input's batch_sizes and indices; (h_n, c_n) come back in the original batch order, as from nn.LSTM."""
+    if lengths is not None:
+        raise ValueError(f"{name}: lengths given together with a PackedSequence (it carries its own)")
+    padded, lens = nn.utils.rnn.pad_packed_sequence(x, batch_first=True)
+    output, state = module.forward(padded, hx, lengths=lens)
+    # pad_packed_sequence gave the rows in the original batch order: back into the input's own (sorted) order, so
+    # that the data lines up with its batch_sizes whatever order it gave to rows of equal length
+    if x.sorted_indices is not None:
+        output, lens = output.index_select(0, x.sorted_indices), lens[x.sorted_indices.cpu()]
+    packed = nn.utils.rnn.pack_padded_sequence(output, lens, batch_first=True, enforce_sorted=True)
+    return nn.utils.rnn.PackedSequence(packed.data, x.batch_sizes, x.sorted_indices, x.unsorted_indices), state
+
+
+def _check_lengths(name, lengths, B, T):
+    """The ``lengths`` argument of LSTM / BiLSTM -> None or a tuple of B ints in [0, T]."""
+    if lengths is None:
+        return None
+    if isinstance(lengths, torch.Tensor):
+        if lengths.is_cuda:
+            raise ValueError(f"{name}: lengths must be a CPU int tensor or a sequence of ints (pass CPU lengths, as "
+                             "pack_padded_sequence takes them)")
+        if lengths.dim() != 1 or lengths.dtype.is_floating_point or lengths.dtype in (torch.bool,):
+            raise ValueError(f"{name}: lengths must be a 1-d int tensor, got {lengths.dtype} of shape {list(lengths.shape)}")
+        lengths = lengths.tolist()
+    lengths = tuple(int(n) for n in lengths)
+    if len(lengths) != B:
+        raise ValueError(f"{name}: {len(lengths)} lengths for a batch of {B}")
+    bad = [n for n in lengths if n < 0 or n > T]
+    if bad:
+        raise ValueError(f"{name}: length {bad[0]} outside [0, T = {T}]")
+    return lengths
+
+
 class LSTM(HipLSTM):
     """Drop-in for ``torch.nn.LSTM(input_size, hidden_size, num_layers, batch_first=True)`` on the HIP path, with the
     whole of its call contract: ``forward(x[B,T,I], hx=None) -> (output[B,T,H], (h_n[L,B,H], c_n[L,B,H]))``, hx =
@@ -280,22 +315,13 @@ class LSTM(HipLSTM):
                                               ("proj_size != 0", proj_size != 0)) if bad]
         if unsupported:
             raise ValueError(f"LSTM: {', '.join(unsupported)} is not supported (batch-first, biased, unidirectional "
-                             f"stacks without projection or inter-layer dropout only)")
+                             f"stacks without projection or inter-layer dropout only; for bidirectional=True use BiLSTM)")
         super().__init__(input_size, hidden_size, num_layers, compute_dtype=compute_dtype)
         self.bias, self.batch_first, self.dropout, self.bidirectional, self.proj_size = True, True, 0.0, False, 0
 
     def forward(self, x, hx=None, lengths=None):
         if isinstance(x, nn.utils.rnn.PackedSequence):
-            if lengths is not None:
-                raise ValueError("LSTM: lengths given together with a PackedSequence (it carries its own)")
-            padded, lens = nn.utils.rnn.pad_packed_sequence(x, batch_first=True)
-            output, state = self.forward(padded, hx, lengths=lens)
-            # pad_packed_sequence gave the rows in the original batch order: back into the input's own (sorted) order, so
-            # that the data lines up with its batch_sizes whatever order it gave to rows of equal length
-            if x.sorted_indices is not None:
-                output, lens = output.index_select(0, x.sorted_indices), lens[x.sorted_indices.cpu()]
-            packed = nn.utils.rnn.pack_padded_sequence(output, lens, batch_first=True, enforce_sorted=True)
-            return nn.utils.rnn.PackedSequence(packed.data, x.batch_sizes, x.sorted_indices, x.unsorted_indices), state
+            return _forward_packed(self, "LSTM", x, hx, lengths)
         if x.dim() != 3:
             raise ValueError(f"LSTM: input must be batched [B, T, {self.input_size}] (batch_first); got shape "
                              f"{list(x.shape)} (unbatched input is not supported)")
@@ -308,20 +334,7 @@ class LSTM(HipLSTM):
             for name, t in (("h0", h0), ("c0", c0)):
                 if tuple(t.shape) != (L, B, H):
                     raise ValueError(f"LSTM: {name} must be [num_layers, B, hidden_size] = {[L, B, H]}, got {list(t.shape)}")
-        if lengths is not None:
-            if isinstance(lengths, torch.Tensor):
-                if lengths.is_cuda:
-                    raise ValueError("LSTM: lengths must be a CPU int tensor or a sequence of ints (pass CPU lengths, as "
-                                     "pack_padded_sequence takes them)")
-                if lengths.dim() != 1 or lengths.dtype.is_floating_point or lengths.dtype in (torch.bool,):
-                    raise ValueError(f"LSTM: lengths must be a 1-d int tensor, got {lengths.dtype} of shape {list(lengths.shape)}")
-                lengths = lengths.tolist()
-            lengths = tuple(int(n) for n in lengths)
-            if len(lengths) != B:
-                raise ValueError(f"LSTM: {len(lengths)} lengths for a batch of {B}")
-            bad = [n for n in lengths if n < 0 or n > x.shape[1]]
-            if bad:
-                raise ValueError(f"LSTM: length {bad[0]} outside [0, T = {x.shape[1]}]")
+        lengths = _check_lengths("LSTM", lengths, B, x.shape[1])
         _dropout_p(self)
         if not x.is_cuda:
             raise cabi.CsnError("LSTM runs on the GPU only (no CPU fallback); move the module and input to cuda")
@@ -332,22 +345,182 @@ class LSTM(HipLSTM):
         return y_all, (h_n, c_n)
 
 
+class _BiLstmFunction(torch.autograd.Function):
+    """Bidirectional stacked LSTM: (x, h0, c0, params) -> (output[B,T,2H], h_n[2L,B,H], c_n[2L,B,H]) as 2L single-layer
+    plans, a plain and a CSN_LSTM_REVERSE one per layer, one after the other on the current stream.  The two directions
+    of a layer write their halves of one [B,T,2H] tensor in place (csn_lstm_plan_set_io), which is the next layer's x;
+    the backward reads the halves of its gradient in place and the second direction adds its input gradient to the
+    first's.  No torch op touches a [B,T,.] tensor here apart from allocating it."""
+
+    @staticmethod
+    def forward(ctx, x, h0, c0, owner, training, lengths, L, *params):
+        B, T, H = x.shape[0], x.shape[1], owner.hidden_size
+        h_n = torch.empty((2 * L, B, H), dtype=torch.float32, device=x.device)
+        c_n = torch.empty((2 * L, B, H), dtype=torch.float32, device=x.device)
+        leases, inp = [], x
+        for l in range(L):
+            out = torch.empty((B, T, 2 * H), dtype=torch.float32, device=x.device)
+            for d in range(2):
+                k = 2 * l + d
+                w = [[params[4 * k + g]] for g in range(4)]
+                plan = owner._checkout(B, T, inp.shape[2], x.device, training, reverse=d == 1)
+                lease = _Lease(plan)        # (at once: the next direction / layer of the same shape must take another plan)
+                plan.set_lengths(lengths)
+                plan.set_io(2 * H, 2 * H, False)
+                plan.forward(inp, *w, h0=None if h0 is None else h0[k:k + 1], c0=None if c0 is None else c0[k:k + 1],
+                             want_state=True, y_all=out[:, :, d * H:(d + 1) * H], state_out=(h_n[k:k + 1], c_n[k:k + 1]))
+                if training:
+                    leases.append(lease)
+                else:
+                    lease.release()
+            inp = out
+        ctx.leases, ctx.L, ctx.owner, ctx.lengths = leases, L, owner, lengths
+        ctx.need = (x.requires_grad, h0 is not None and h0.requires_grad, c0 is not None and c0.requires_grad)
+        ctx.x_shape = x.shape
+        ctx.param_like = params
+        return inp, h_n, c_n
+
+    @staticmethod
+    def backward(ctx, dy, dh_n, dc_n):
+        L, leases = ctx.L, ctx.leases
+        if not leases or leases[0].plan is None:
+            raise RuntimeError("BiLSTM: second backward through one forward -- its workspaces were handed back after the "
+                               "first (retain_graph / double backward are not supported)")
+        B, T, _ = ctx.x_shape
+        H = ctx.owner.hidden_size
+        dev = ctx.param_like[0].device
+        need_dx, need_dh0, need_dc0 = ctx.need
+        grads = [torch.empty_like(p) for p in ctx.param_like]
+        dh0 = torch.empty((2 * L, B, H), dtype=torch.float32, device=dev) if need_dh0 else None
+        dc0 = torch.empty((2 * L, B, H), dtype=torch.float32, device=dev) if need_dc0 else None
+        if dy.dtype != torch.float32 or not dy.is_contiguous():
+            dy = dy.float().contiguous()    # (autograd hands a dense gradient as a rule: an expanded or sliced one is copied once)
+        for l in range(L - 1, -1, -1):
+            width = ctx.x_shape[2] if l == 0 else 2 * H
+            dinp = torch.empty((B, T, width), dtype=torch.float32, device=dev) if (l > 0 or need_dx) else None
+            for d in range(2):
+                k = 2 * l + d
+                plan = leases[k].plan
+                plan.set_grad_callback(None)
+                plan.set_grad_mode(False)
+                plan.set_lengths(ctx.lengths)
+                plan.set_io(2 * H, 2 * H, d == 1)       # the reverse direction adds its dx to the forward one's
+                plan.backward(None, dy[:, :, d * H:(d + 1) * H], [[grads[4 * k + g]] for g in range(4)], dx=dinp,
+                              dh_n=dh_n[k:k + 1], dc_n=dc_n[k:k + 1], dh0=None if dh0 is None else dh0[k:k + 1],
+                              dc0=None if dc0 is None else dc0[k:k + 1])
+                leases[k].release()
+            dy = dinp
+        return (dy, dh0, dc0, None, None, None, None, *grads)
+
+
+class BiLSTM(nn.Module):
+    """``torch.nn.LSTM(input_size, hidden_size, num_layers, batch_first=True, bidirectional=True)`` on the HIP path:
+    ``forward(x[B,T,I] | PackedSequence, hx=None, lengths=None) -> (output[B,T,2H], (h_n[2L,B,H], c_n[2L,B,H]))``, hx
+    and h_n indexed ``2 * layer + direction`` as in torch; gradients reach x, h0, c0 and every parameter.  Parameter
+    names, order, shapes and init are nn.LSTM's (``weight_ih_l{k}``, ..., ``bias_hh_l{k}``, then the same with
+    ``_reverse``, layer by layer; ``weight_ih_l{k>=1}`` is [4H, 2H]), so state_dicts load both ways.  Lengths, a
+    PackedSequence and a length of 0 mean what they mean for ``LSTM``: the reverse direction of a row starts at that
+    row's own last valid step.  ``output[:, 0, H:]`` is therefore the reverse direction's final output and
+    ``output[:, -1, H:]`` its first: the summary of a sequence is ``cat(h_n[-2], h_n[-1])``.
+
+    Runs as 2L single-layer CSN_LSTM_STATE plans, a plain and a CSN_LSTM_REVERSE one per layer, sequentially on the
+    current stream (the weight-stationary launches need the whole chip, so the directions do not overlap); no recurrence
+    kernel differs from ``LSTM``'s, only the layout passes around it index time backwards.  The
+    upper layers read an input of width 2H, which the fused input projection (I <= 128) does not take: they project
+    through the GEMM.  All 2L workspaces stay leased from a training forward to its backward: at B 256, T 500, I 128,
+    H 768, L 2 in bf16 that is 2 x 4.32 GB (layer 0) + 2 x 5.42 GB (layer 1, input width 2H) = 19.48 GB, against 8.47 GB
+    for the unidirectional two-layer plan (csn_lstm_workspace_bytes; 22.77 GB at B 256, T 440, H 1024).
+
+    Not in this class: inter-layer dropout (it lives between the layers of one plan: ``dropout != 0`` is refused), and
+    the direct / accumulating gradient writes of ``HipLSTM`` (gradients go to autograd temporaries).
+    """
+
+    MAX_IDLE_PLANS = 4
+
+    def __init__(self, input_size, hidden_size, num_layers=1, compute_dtype=torch.bfloat16, dropout=0.0):
+        super().__init__()
+        if dropout != 0:
+            raise ValueError("BiLSTM: dropout != 0 is not supported (the inter-layer dropout of this library lives "
+                             "between the layers of one plan; a bidirectional stack runs one plan per layer and direction)")
+        self.input_size, self.hidden_size, self.num_layers = input_size, hidden_size, num_layers
+        self.compute_dtype = compute_dtype
+        self.bias, self.batch_first, self.dropout, self.bidirectional, self.proj_size = True, True, 0.0, True, 0
+        ref = nn.LSTM(input_size, hidden_size, num_layers=num_layers, batch_first=True, bidirectional=True)
+        for name, p in ref.named_parameters():      # same init, key names and order
+            self.register_parameter(name, nn.Parameter(p.detach().clone()))
+        self._plans = {}        # key -> list of plans; plan.busy marks a forward awaiting its backward
+
+    def _checkout(self, B, T, I, device, training, reverse):
+        key = (B, T, I, str(device), bool(training), self.compute_dtype, bool(reverse))
+        pool = self._plans.setdefault(key, [])
+        for plan in pool:
+            if not plan.busy:
+                return plan
+        idle = [(k, pl) for k, lst in self._plans.items() for pl in lst if not pl.busy and k != key]
+        while len(idle) >= self.MAX_IDLE_PLANS:
+            k, pl = idle.pop(0)
+            self._plans[k].remove(pl)
+        plan = cabi.LstmPlan(B, T, I, self.hidden_size, 1, self.compute_dtype, device, training=training, state=True,
+                             reverse=reverse)
+        pool.append(plan)
+        return plan
+
+    def all_plans(self):
+        return [pl for lst in self._plans.values() for pl in lst]
+
+    def forward(self, x, hx=None, lengths=None):
+        if isinstance(x, nn.utils.rnn.PackedSequence):
+            return _forward_packed(self, "BiLSTM", x, hx, lengths)
+        if x.dim() != 3:
+            raise ValueError(f"BiLSTM: input must be batched [B, T, {self.input_size}] (batch_first); got shape "
+                             f"{list(x.shape)} (unbatched input is not supported)")
+        if x.shape[2] != self.input_size:
+            raise ValueError(f"BiLSTM: input has {x.shape[2]} features, expected {self.input_size}")
+        B, L, H = x.shape[0], self.num_layers, self.hidden_size
+        h0 = c0 = None
+        if hx is not None:
+            h0, c0 = hx
+            for name, t in (("h0", h0), ("c0", c0)):
+                if tuple(t.shape) != (2 * L, B, H):
+                    raise ValueError(f"BiLSTM: {name} must be [2 * num_layers, B, hidden_size] = {[2 * L, B, H]}, got "
+                                     f"{list(t.shape)}")
+        lengths = _check_lengths("BiLSTM", lengths, B, x.shape[1])
+        if not x.is_cuda:
+            raise cabi.CsnError("BiLSTM runs on the GPU only (no CPU fallback); move the module and input to cuda")
+        params = [getattr(self, f"{n}_l{k}{sfx}") for k in range(L) for sfx in ("", "_reverse")
+                  for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
+        training = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params) or
+                                                any(t is not None and t.requires_grad for t in (h0, c0)))
+        output, h_n, c_n = _BiLstmFunction.apply(x, h0, c0, self, training, lengths, L, *params)
+        return output, (h_n, c_n)
+
+
 class Model(nn.Module):
     """``models.lstm.Model``.  ``head``/``fc`` may be reassigned by
     ``MultiCropWrapper`` (utils/utils.py:607-612) without breaking forward."""
 
     def __init__(self, input_size=128, lstm_size=128, lstm_layers=1, output_size=128, include_top=True,
-                 n_classes=40, compute_dtype=torch.bfloat16, dropout=0.0):
+                 n_classes=40, compute_dtype=torch.bfloat16, dropout=0.0, bidirectional=False):
+        """``bidirectional=True``: the encoder is a ``BiLSTM`` and ``fc`` has 2 * lstm_size inputs.  The feature fed to
+        ``fc`` is then ``cat(h_n[-2], h_n[-1])``, the top layer's FINAL state in each direction -- not ``output[:, -1]``,
+        whose reverse half has seen one step only."""
         super().__init__()
         self.input_size, self.lstm_size, self.lstm_layers = input_size, lstm_size, lstm_layers
-        self.output_size, self.include_top = output_size, include_top
-        self.lstm = HipLSTM(input_size, lstm_size, lstm_layers, compute_dtype=compute_dtype, dropout=dropout)
-        self.fc = nn.Linear(lstm_size, output_size)
+        self.output_size, self.include_top, self.bidirectional = output_size, include_top, bool(bidirectional)
+        if self.bidirectional:
+            self.lstm = BiLSTM(input_size, lstm_size, lstm_layers, compute_dtype=compute_dtype, dropout=dropout)
+        else:
+            self.lstm = HipLSTM(input_size, lstm_size, lstm_layers, compute_dtype=compute_dtype, dropout=dropout)
+        self.fc = nn.Linear((2 if self.bidirectional else 1) * lstm_size, output_size)
         if include_top:
             self.class_pred = nn.Linear(output_size, n_classes)
 
     def forward(self, x):
-        last = self.lstm(x)                    # [B, H] = top layer at the last timestep
+        if self.bidirectional:
+            _, (h_n, _) = self.lstm(x)
+            last = torch.cat((h_n[-2], h_n[-1]), dim=1)    # [B, 2H]
+        else:
+            last = self.lstm(x)                # [B, H] = top layer at the last timestep
         feat = self.fc(last)
         if self.include_top and hasattr(self, "class_pred"):
             return feat, self.class_pred(feat)

@@ -199,12 +199,12 @@ def check_device_status(model, collective=True):
     rank must reach it.  ``collective=False``: this rank's verdict only (work that one rank does alone, e.g. rank 0's
     fixture check before a benchmark's timed region)."""
     from . import cabi
-    from .lstm_model import HipLSTM
+    from .lstm_model import BiLSTM, HipLSTM
     torch.cuda.synchronize()
     bad = 0
     dev = None
     for mod in model.modules():
-        if isinstance(mod, HipLSTM):
+        if isinstance(mod, (HipLSTM, BiLSTM)):
             for plan in mod.all_plans():
                 bad |= plan.status(clear=True)
                 dev = plan.device

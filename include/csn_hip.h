@@ -86,8 +86,9 @@ enum csnStatus {
 enum csnDtype { CSN_F32 = 0, CSN_BF16 = 1 };
 
 /* ABI version of this header; bumped on any signature change.  A symbol added beside the existing ones
- * (csn_lstm_plan_set_grad_mode, csn_lstm_plan_set_lengths, csn_lstm_plan_half_tile_launches, the csn_flat_* family,
- * csn_adam_step, csn_lars_step, csn_eeg_bandpass_stream and its _path) breaks no caller and does not bump it. */
+ * (csn_lstm_plan_set_grad_mode, csn_lstm_plan_set_lengths, csn_lstm_plan_set_io, csn_lstm_plan_half_tile_launches, the
+ * csn_flat_* family, csn_adam_step, csn_lars_step, csn_eeg_bandpass_stream and its _path) breaks no caller and does not
+ * bump it; neither does a new bit of csn_lstm_plan_create's `training` word. */
 #define CSN_ABI_VERSION 6
 int csn_abi_version(void);
 /* Thread-local message for the last non-zero status returned on this thread. */
@@ -182,6 +183,18 @@ typedef struct csnLstmPlan csnLstmPlan;
  * H 768, L 2, bf16, on 10 GB), laid out behind everything else.  Valid on training and inference plans, with or
  * without CSN_LSTM_STATE.  Until a p > 0 is set the plan runs the launches and writes the bits of a plan without it. */
 #define CSN_LSTM_DROPOUT 0x200
+/* `training` may also carry CSN_LSTM_REVERSE: the plan walks every row BACKWARDS in time -- the reverse direction of a
+ * bidirectional LSTM.  Valid with or without the other two bits, for any L, on every path: a reverse
+ * plan takes the path, runs the recurrence kernels and has the workspace of a plan without the bit.  Only the layout
+ * passes around the recurrence differ: with n = lengths[b] (T when no lengths are set), recurrence step s of row b
+ * consumes x[b, n-1-s] and its top-layer output lands at y_all[b, n-1-s]; (h0, c0) is the state in front of time n-1;
+ * y_last, h_n, c_n are taken after step n-1, that is at time 0; dy_all[b, t] is read and dx[b, t] written under the same
+ * map, dy_last / dh_n / dc_n enter at the last step as on any plan.  x[b, t >= n] and dy_all[b, t >= n] are never read,
+ * y_all and dx are zero there, n = 0 passes through.  With R = "reverse each row's first n steps, leave the rest":
+ * y_all = R(y_all of a plan without the bit on R(x)) and dx = R(its dx for R(dy_all)); every other result -- y_last, h_n,
+ * c_n, dh0, dc0, all weight gradients -- is that plan's, and all of it holds bit for bit (the workspace behind the
+ * layout passes has the same contents).  (tests/test_gpu_bilstm.py) */
+#define CSN_LSTM_REVERSE 0x400
 int csn_lstm_plan_create(const csnLstmDesc* d, int training, csnLstmPlan** out);
 void csn_lstm_plan_destroy(csnLstmPlan* plan);
 /* Bytes of device scratch ("workspace") a forward (+ backward) of this plan needs; 256-B aligned base.  The
@@ -307,6 +320,19 @@ int csn_lstm_plan_set_grad_mode(csnLstmPlan* plan, int mode);
  * ordered on one stream, or by the caller.
  * Null plan, a plan without CSN_LSTM_STATE, an entry outside [0, T]: CSN_ERR_INVALID_ARGUMENT (the setting is kept). */
 int csn_lstm_plan_set_lengths(csnLstmPlan* plan, const int32_t* lengths);
+
+/* Where the plan's later calls find y_all and dy_all, and how they store dx; host only, sticky until set again like the
+ * gradient mode, and a call uses the setting it finds when it is CALLED.
+ *   y_all_pitch, dy_all_pitch   elements per (b, t) row: element (b, t, h) is at base[(b T + t) pitch + h].  0 = dense (H);
+ *                               otherwise pitch >= H and pitch % 4 == 0.  Only the H elements of a row are written / read.
+ *   dx_add != 0                 dx[b, t, :] += ... over the valid steps (t < lengths[b]) instead of =; the padding of dx is
+ *                               left as it is and nothing is zeroed.  fl32(prev + g), g the value the storing form writes.
+ * For the two directions of a bidirectional layer: each plan writes its half of one [B, T, 2H] tensor (y_all = base + H
+ * for the second, pitch 2H) and reads its half of that tensor's gradient in place, and the second direction adds its
+ * input gradient to the first's -- no concatenation, split or sum pass.  Every path, every plan.  With (0, 0, 0), the
+ * default, a plan without CSN_LSTM_REVERSE enqueues the launches and writes the bits it did before this symbol existed.
+ * Null plan or a pitch that is neither 0 nor a multiple of 4 >= H: CSN_ERR_INVALID_ARGUMENT (the setting is kept). */
+int csn_lstm_plan_set_io(csnLstmPlan* plan, int64_t y_all_pitch, int64_t dy_all_pitch, int dx_add);
 
 /* Inter-layer dropout, with torch.nn.LSTM(dropout=p)'s meaning: for every layer l < L-1 the output sequence of layer l is
  * multiplied element-wise by an independent Bernoulli(1-p) mask and by 1/(1-p) before layer l+1's input projection.
