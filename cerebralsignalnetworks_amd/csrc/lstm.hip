@@ -2033,6 +2033,8 @@ extern "C" int csn_lstm_backward(csnLstmPlan* Pp, const float* dy_last, const fl
         }
         // an empty row's dgates are zero at step 0: its dh0 is the gradient w.r.t. its h_n
         if (dh_n) add_rows_len0_kernel<<<grid_for((int64_t)BH), 256, 0, st>>>(dh_n + l * BH, out, dlen, B, H);
+        // ... and y_last of an empty row is h_n of the top layer, that is its h0: dy_last reaches dh0 there
+        if (dy_last && l == NL - 1) add_rows_len0_kernel<<<grid_for((int64_t)BH), 256, 0, st>>>(dy_last, out, dlen, B, H);
         CSN_LAUNCH_CHECK();
       }
       if (dc0) {

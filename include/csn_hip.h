@@ -309,7 +309,8 @@ int csn_lstm_plan_set_grad_mode(csnLstmPlan* plan, int mode);
  * n = lengths[b]:  y_all[b, t >= n] = 0;  h_n[l, b], c_n[l, b] = the state after step n-1 (CSN_BF16: the bf16 h every
  * consumer saw);  y_last[b] = h_n[L-1, b];  nothing at t >= n enters any gradient: dx[b, t >= n] = 0, dy_all[b, t >= n]
  * is ignored, dh_n[l, b] / dc_n[l, b] / dy_last[b] enter at step n-1.  n = 0 (beyond torch): the row passes through --
- * h_n = h0 (bf16-rounded on CSN_BF16), c_n = c0, zero output, dh0 = dh_n, dc0 = dc_n, no parameter contribution; with
+ * h_n = h0 (bf16-rounded on CSN_BF16), c_n = c0, zero output, dh0 = dh_n (+ dy_last in the top layer, whose h_n is y_last),
+ * dc0 = dc_n, no parameter contribution; with
  * every row 0 no recurrence kernel is launched.  x[b, t >= n] and dy_all[b, t >= n] are never read as data: whatever
  * they hold (NaN, Inf), every result has the bits of the same call with zeros there.
  * The recurrence and every GEMM behind it cover max(lengths) steps, not T.
@@ -344,6 +345,8 @@ int csn_lstm_plan_set_io(csnLstmPlan* plan, int64_t y_all_pitch, int64_t dy_all_
  * The mask is fully specified, the same on every path, and reproducible on a CPU (csn_lstm_dropout_keep):
  *   element (l, t, b, u) of interface l (between layers l and l+1) has the 64-bit index e = ((l T + t) B + b) H + u with
  *   the PLAN's T, B, H (a call with lengths draws the mask of the same call without them);
+ *   on a CSN_LSTM_REVERSE plan t is the recurrence step s (the caller's time n-1-s), as the mask is applied in the workspace:
+ *   this is what makes a reverse dropout plan equal the plain dropout plan on reversed data, bit for bit;
  *   words = Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85) of
  *   counter (lo32(e >> 2), hi32(e >> 2), subsequence, 0) under key (lo32(seed), hi32(seed)); the word used is e & 3;
  *   keep iff word >= thr, thr = floor(float32(p) 2^32); at p = 1 nothing is kept, whatever the word.
