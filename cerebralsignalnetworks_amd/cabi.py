@@ -107,6 +107,11 @@ SIGNATURES = {
     "csn_l2_topk_tiled_scratch_bytes": (_c_size_t, [_c_i64, _c_i64, _c_int]),
     "csn_l2_topk_tiled": (_c_int, [_c_void_p, _c_void_p, _c_i64, _c_i64, _c_int, _c_int, _c_int, _c_void_p, _c_void_p,
                                    _c_void_p, _c_void_p, _c_void_p]),
+    "csn_chan_l2_dist": (_c_int, [_c_void_p, _c_i64, _c_i64, _c_void_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int,
+                                  _c_int, _c_int, ctypes.POINTER(ctypes.c_int32), _c_int, _c_void_p, _c_void_p]),
+    "csn_chan_l2_select": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_i64, _c_i64, _c_void_p, _c_void_p, _c_int,
+                                    _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+    "csn_chan_l2_accumulate": (_c_int, [_c_void_p, _c_void_p, _c_i64, _c_int, _c_void_p]),
 }
 
 
@@ -680,3 +685,85 @@ def l2_topk_tiled(gallery, query, k, splits=0, dist64=False):
         _check(lib.csn_l2_topk_tiled(_ptr(g), _ptr(q), Ng, Nq, D, k, splits, _ptr(idx), _ptr(dist), _ptr(d64), _ptr(scratch),
                                      _stream()))
     return (dist, idx, d64) if dist64 else (dist, idx)
+
+
+def _nct_view(x, name):
+    """A float32 [N,C,T] device tensor whose time stride is 1 and whose strides csn_chan_l2_dist can address in place
+    (a slice of a larger tensor is); anything else is made contiguous."""
+    if x.dim() != 3:
+        raise CsnError(f"chan_l2_dist: {name} must be [N,C,T], got shape {tuple(x.shape)}")
+    x = x.float()
+    N, C, T = x.shape
+    if N and C and T and (x.stride(2) != 1 or x.stride(1) < T or x.stride(0) < (C - 1) * x.stride(1) + T):
+        x = x.contiguous()
+    return x
+
+
+def chan_l2_dist(gallery_nct, query_nct, t0, t1, channels=None, out=None):
+    """csn_chan_l2_dist: per-channel squared-L2 matrices Dc[nch,Nq,Ng] float64 of the window [t0, t1) of channel-first
+    recordings, read in place.  channels: a host sequence (None = all, ascending).  out: a dense float64 buffer to fill."""
+    _need_cuda(gallery_nct, query_nct)
+    g, q = _nct_view(gallery_nct, "gallery"), _nct_view(query_nct, "query")
+    Ng, C, T = g.shape
+    Nq = q.shape[0]
+    if tuple(q.shape[1:]) != (C, T):
+        raise CsnError(f"chan_l2_dist: gallery is [*, {C}, {T}], query [*, {q.shape[1]}, {q.shape[2]}]")
+    if channels is None:
+        nch, arr = C, None
+    else:
+        nch = len(channels)
+        arr = (ctypes.c_int32 * max(nch, 1))(*[int(c) for c in channels])
+    with torch.cuda.device(g.device):
+        if out is None:
+            out = torch.empty((max(nch, 0), Nq, Ng), dtype=torch.float64, device=g.device)
+        elif (not out.is_cuda or out.device != g.device or out.dtype != torch.float64 or not out.is_contiguous()
+              or out.numel() != nch * Nq * Ng):
+            raise CsnError("chan_l2_dist: out must be a dense float64 buffer of nch*Nq*Ng elements on the gallery's device")
+        _check(load().csn_chan_l2_dist(_ptr(g), g.stride(0), g.stride(1), _ptr(q), q.stride(0), q.stride(1), Ng, Nq, C, T,
+                                       int(t0), int(t1), arr, nch, _ptr(out), _stream()))
+    return out.view(nch, Nq, Ng)
+
+
+def chan_l2_select(base, Dc, gallery_class, query_class, k, want=("idx", "dist", "hits", "top1")):
+    """csn_chan_l2_select: for every (candidate, query) the k smallest of base + Dc[j] under (value, index).  base may be
+    None.  -> dict with the outputs named in ``want``: idx [nc,Nq,k] int64, dist [nc,Nq,k] float64, hits / top1 [nc,Nq]
+    int32."""
+    _need_cuda(base, Dc, gallery_class, query_class)
+    if Dc.dim() != 3 or Dc.dtype != torch.float64 or not Dc.is_contiguous():
+        raise CsnError("chan_l2_select: Dc must be a dense float64 [nc,Nq,Ng] tensor")
+    nc, Nq, Ng = Dc.shape
+    if base is not None and (base.dtype != torch.float64 or not base.is_contiguous() or tuple(base.shape) != (Nq, Ng)):
+        raise CsnError("chan_l2_select: base must be a dense float64 [Nq,Ng] tensor")
+    for t, n, name in ((gallery_class, Ng, "gallery_class"), (query_class, Nq, "query_class")):
+        if t is not None and (t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != n):
+            raise CsnError(f"chan_l2_select: {name} must be a dense int32 tensor of {n} elements")
+    unknown = set(want) - {"idx", "dist", "hits", "top1"}
+    if unknown:
+        raise CsnError(f"chan_l2_select: unknown outputs {sorted(unknown)}")
+    k = int(k)
+    kk = max(k, 0)
+    with torch.cuda.device(Dc.device):
+        out = {}
+        if "idx" in want:
+            out["idx"] = torch.empty((nc, Nq, kk), dtype=torch.int64, device=Dc.device)
+        if "dist" in want:
+            out["dist"] = torch.empty((nc, Nq, kk), dtype=torch.float64, device=Dc.device)
+        if "hits" in want:
+            out["hits"] = torch.empty((nc, Nq), dtype=torch.int32, device=Dc.device)
+        if "top1" in want:
+            out["top1"] = torch.empty((nc, Nq), dtype=torch.int32, device=Dc.device)
+        _check(load().csn_chan_l2_select(_ptr(base), _ptr(Dc), nc, Nq, Ng, _ptr(gallery_class), _ptr(query_class), k,
+                                         _ptr(out.get("idx")), _ptr(out.get("dist")), _ptr(out.get("hits")),
+                                         _ptr(out.get("top1")), _stream()))
+    return out
+
+
+def chan_l2_accumulate(base, D_one, first):
+    """csn_chan_l2_accumulate, in place: base = D_one if first else base + D_one (float64, element-wise)."""
+    _need_cuda(base, D_one)
+    if (base.dtype != torch.float64 or D_one.dtype != torch.float64 or not base.is_contiguous() or not D_one.is_contiguous()
+            or base.numel() != D_one.numel()):
+        raise CsnError("chan_l2_accumulate: base and D_one must be dense float64 tensors of one size")
+    with torch.cuda.device(base.device):
+        _check(load().csn_chan_l2_accumulate(_ptr(base), _ptr(D_one), base.numel(), int(bool(first)), _stream()))
+    return base

@@ -15,13 +15,12 @@
 // Kernel 2 (l2_topk_merge_splits_kernel), one workgroup per query: merges the splits' sorted lists pairwise (log2 S
 // rounds of rank computation, the list of the lower index range first on equal distance) and writes the outputs.
 // No workgroup waits on another; every loop is bounded by the shapes.
-#include "csn_common.h"
+#include "l2_tile.h"
 
 namespace csn {
 
 namespace tk {
-constexpr int TQ = 64, TG = 64, DS = 32;
-constexpr int LDP = 68;       // words per d-row of a staged operand slice: 16-byte aligned, bank = (4c + r) mod 32 on the writes
+// (TQ, TG, DS, LDP and the distance-tile body: l2_tile.h, shared with channel_l2.hip)
 constexpr int DTP = 66;       // float64 per row of the distance tile
 constexpr int MAX_K = 1024, MAX_SPLITS = 64, TARGET_WGS = 512 /* 256 CUs about twice over */;
 
@@ -31,7 +30,6 @@ struct Lists {
   int* meta;           // [splits][Nq][2]: entries in the list, which buffer holds it
 };
 
-static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 // the most splits a call may use (the scratch is sized for it): what the library would choose, or 8, within the gallery
 static inline int splits_auto(int64_t Ng, int64_t Nq) {
   const int64_t qt = cdiv(Nq, TQ), gt = cdiv(Ng, TG);
@@ -126,57 +124,13 @@ l2_topk_tiled_kernel(const float* __restrict__ gallery, const float* __restrict_
     cnt[tid] = 0;
     cur[tid] = 0;
   }
-  // staging map: 8 elements per thread and operand; a 32-lane half writes 8 consecutive d of 4 consecutive rows
-  const int sc = tid & 7, sr = tid >> 3;
-
   for (int64_t t = t_begin; t < t_end; ++t) {
     const int64_t g0 = t * TG;
     double acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[i][j] = 0.0;
-
-    float qr[8], gr[8];
-    auto fetch = [&](int d0) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int c = d0 + sc + 8 * (j & 3);
-        const int64_t rq = q0 + sr + 32 * (j >> 2), rg = g0 + sr + 32 * (j >> 2);
-        qr[j] = (rq < Nq && c < D) ? query[rq * D + c] : 0.0f;
-        gr[j] = (rg < g_end && c < D) ? gallery[rg * D + c] : 0.0f;
-      }
-    };
-    fetch(0);
-    for (int d0 = 0; d0 < D; d0 += DS) {
-      __syncthreads();          // the previous slice's reads, or the selection's reads of the distance tile, are done
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int o = (sc + 8 * (j & 3)) * LDP + sr + 32 * (j >> 2);
-        qs[o] = qr[j];
-        gs[o] = gr[j];
-      }
-      __syncthreads();
-      if (d0 + DS < D) fetch(d0 + DS);
-#pragma unroll 4
-      for (int c = 0; c < DS; ++c) {
-        const f32x4 qf = *reinterpret_cast<const f32x4*>(qs + c * LDP + tq * 4);
-        const f32x4 gf = *reinterpret_cast<const f32x4*>(gs + c * LDP + tg * 4);
-        double qd[4], gd[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          qd[i] = (double)qf[i];
-          gd[i] = (double)gf[i];
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const double df = qd[i] - gd[j];
-            acc[i][j] = fma(df, df, acc[i][j]);
-          }
-      }
-    }
+    l2_tile_distances(
+        acc, qs, gs, tid, D,
+        [&](int r, int c) { return (q0 + r < Nq && c < D) ? query[(q0 + r) * D + c] : 0.0f; },
+        [&](int r, int c) { return (g0 + r < g_end && c < D) ? gallery[(g0 + r) * D + c] : 0.0f; });
     __syncthreads();            // every wave is done with the operand slices: the distance tile takes their place
 #pragma unroll
     for (int i = 0; i < 4; ++i)

@@ -520,6 +520,38 @@ size_t csn_l2_topk_tiled_scratch_bytes(int64_t Ng, int64_t Nq, int k);
 int csn_l2_topk_tiled(const float* gallery, const float* query, int64_t Ng, int64_t Nq, int D, int k, int splits,
                       int64_t* out_idx, float* out_dist, double* out_dist64, void* scratch, csnStream_t stream);
 
+/* K8, channel discovery: the greedy forward selection of EEG channels of
+ * TestRetrieval_Perils_DiscoverChannels.py:125-351 without one index build and search per candidate.  The squared L2
+ * distance over a channel subset is the sum of the per-channel distances: csn_chan_l2_dist computes those once,
+ * csn_chan_l2_select runs one round's selection for every candidate at once, csn_chan_l2_accumulate adds the accepted
+ * channel to the running sum.  All three refuse on the host, before any launch: null pointers (other than the ones
+ * marked nullable), sizes <= 0, and what each lists below.
+ *
+ * csn_chan_l2_dist: gallery / query are float32 recordings, channel-first: element (n, c, t) at base[n*ld_n + c*ld_c + t]
+ *   (strides in elements, time stride 1), n < Ng / Nq, c < C, t < T.  ld_c >= T and ld_n >= (C-1)*ld_c + T (a slice of a
+ *   larger tensor is fine); only float alignment is needed.  Window [t0, t1): 0 <= t0 < t1 <= T.  channels: HOST array of
+ *   nch channel numbers in [0, C), in any order, repeats allowed; NULL = all C channels ascending (nch ignored).
+ *   Dc[nch, Nq, Ng] float64, dense:
+ *     Dc[j,q,g] = acc, acc = 0.0; for t = t0 .. t1-1: df = (double)Q[q,c_j,t] - (double)G[g,c_j,t]; acc = fma(df, df, acc)
+ *   -- one chain per (channel, pair), never split: the bits csn_l2_topk_tiled's out_dist64 holds for the feature matrix
+ *   X[:, c_j, t0:t1].  Inputs finite.  Ng <= 64 * 65535.
+ * csn_chan_l2_select: base[Nq,Ng] float64 (NULL: no fixed channel yet), Dc[nc,Nq,Ng] float64, gallery_class[Ng] /
+ *   query_class[Nq] int32 (device; needed only by out_hits / out_top1).  For every candidate j and query q: the k
+ *   smallest of v[g] = base[q,g] + Dc[j,q,g] (one float64 add; Dc[j,q,g] itself without base) under (value, gallery index)
+ *   ascending, ties -> lower index.  1 <= k <= min(64, Ng); nc <= 65535.  Outputs, each nullable, at least one given:
+ *   out_idx[nc,Nq,k] int64, out_dist[nc,Nq,k] float64 (the v of the chosen rows),
+ *   out_hits[nc,Nq] int32 = how many of the k have gallery_class == query_class[q],
+ *   out_top1[nc,Nq] int32 = gallery_class of the first.
+ * csn_chan_l2_accumulate: base[i] = first ? D_one[i] : base[i] + D_one[i], i < n, float64.  A subset's matrix is therefore
+ *   ((D_s1 + D_s2) + ...) + D_cand in selection order. */
+int csn_chan_l2_dist(const float* gallery, int64_t g_ld_n, int64_t g_ld_c, const float* query, int64_t q_ld_n,
+                     int64_t q_ld_c, int64_t Ng, int64_t Nq, int C, int T, int t0, int t1, const int32_t* channels, int nch,
+                     double* Dc, csnStream_t stream);
+int csn_chan_l2_select(const double* base, const double* Dc, int nc, int64_t Nq, int64_t Ng, const int32_t* gallery_class,
+                       const int32_t* query_class, int k, int64_t* out_idx, double* out_dist, int32_t* out_hits,
+                       int32_t* out_top1, csnStream_t stream);
+int csn_chan_l2_accumulate(double* base, const double* D_one, int64_t n, int first, csnStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
