@@ -108,6 +108,9 @@ def build_parser(flavour=PERILS):
                         'to one)')
     p.add_argument('--fused_optimizer', action='store_true',
                    help='adamw / adam / lars as fused HIP steps over the flat parameter buffer (rmsprop always is)')
+    p.add_argument('--fused_loss', action='store_true',
+                   help='featdist / kd: loss value and gradient from one fused HIP call in float64 (csn_distill_loss) '
+                        'instead of a chain of torch ops; does nothing with --loss cosine (always fused) or --loss barlow')
     p.add_argument('--compat_label_bug', action='store_true',
                    help='reproduce the batch-local label lookup of transformEEGDataLSTMByList')
     return p
@@ -211,7 +214,8 @@ def main(argv=None, flavour=PERILS):
     sos = EEGFilters(FLAGS.fs, order=FLAGS.filter_order).sos if FLAGS.filter_order else None
     trainer = DistillTrainer(model, sos, loss=FLAGS.loss, lr=FLAGS.learning_rate, optimizer=FLAGS.optimizer,
                              nepochs=max(FLAGS.num_epochs, HyperParams.warmup_teacher_temp_epochs + 1), kd_params=kd,
-                             accum_steps=FLAGS.accum_steps, fused_optimizer=FLAGS.fused_optimizer)
+                             accum_steps=FLAGS.accum_steps, fused_optimizer=FLAGS.fused_optimizer,
+                             fused_loss=FLAGS.fused_loss)
 
     def batches(idx, epoch, shuffle, multiple_of=1):
         shard = idx[shard_indices(len(idx), epoch, FLAGS.seed, rank, world, shuffle=shuffle).to(device)]

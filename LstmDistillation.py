@@ -62,6 +62,9 @@ def build_parser():
     p.add_argument('--time_high', type=int, default=495)
     p.add_argument('--fused_optimizer', action='store_true',
                    help='per-tensor clip + AdamW as one fused HIP step over the flat parameter buffer')
+    p.add_argument('--fused_loss', action='store_true',
+                   help='DINO loss value and student gradient from one fused HIP call in float64 (csn_dino_loss) instead of '
+                        'a chain of torch ops; the centre update is unchanged')
     return p
 
 
@@ -111,7 +114,7 @@ def main(argv=None):
             mod.direct_grads = "accumulate"
 
     dino_loss = DINOLoss(FLAGS.out_dim, FLAGS.local_crops_number + 2, FLAGS.warmup_teacher_temp, FLAGS.teacher_temp,
-                         FLAGS.warmup_teacher_temp_epochs, FLAGS.epochs).to(device)
+                         FLAGS.warmup_teacher_temp_epochs, FLAGS.epochs, fused=FLAGS.fused_loss).to(device)
     regularized = [p for n, p in student.named_parameters() if p.requires_grad and not (n.endswith(".bias") or p.ndim == 1)]
     not_reg = [p for n, p in student.named_parameters() if p.requires_grad and (n.endswith(".bias") or p.ndim == 1)]
     if FLAGS.fused_optimizer:       # the clip loop and the two-group AdamW below as three launches (flat_optim.FlatAdamW)

@@ -89,6 +89,12 @@ SIGNATURES = {
                                         _c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p]),
     "csn_cosine_loss_scratch_bytes": (_c_size_t, [_c_int]),
     "csn_cosine_loss": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_void_p, _c_void_p, _c_float, _c_void_p, _c_void_p]),
+    "csn_distill_loss_scratch_bytes": (_c_size_t, [_c_int]),
+    "csn_distill_loss": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_double,
+                                  _c_double, _c_double, _c_void_p, _c_void_p, _c_void_p, _c_float, _c_void_p, _c_void_p]),
+    "csn_dino_loss_scratch_bytes": (_c_size_t, [_c_int, _c_int]),
+    "csn_dino_loss": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_i64, _c_double,
+                               _c_double, _c_int, _c_void_p, _c_void_p, _c_float, _c_void_p, _c_void_p]),
     "csn_rmsprop_step": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_i64, _c_float, _c_float, _c_float, _c_void_p]),
     "csn_flat_segments_scratch_bytes": (_c_size_t, [_c_int, _c_i64]),
     "csn_flat_segments_prepare": (_c_int, [ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32), _c_int, _c_i64,
@@ -557,6 +563,70 @@ def cosine_loss(student, teacher, want_grad=True, grad_scale=1.0):
     scratch = torch.empty(lib.csn_cosine_loss_scratch_bytes(B) // 8, dtype=torch.float64, device=s.device)   # caller-owned
     with torch.cuda.device(s.device):
         _check(lib.csn_cosine_loss(_ptr(s), _ptr(t), B, D, _ptr(loss), _ptr(ds), float(grad_scale), _ptr(scratch), _stream()))
+    return loss, ds
+
+
+SOFT_KL, SOFT_CE_OF_PROBS = 0, 1            # csn_distill_loss soft_mode (include/csn_hip.h)
+DINO_SKIP_FIRST, DINO_SKIP_SAME = 0, 1      # csn_dino_loss pairing (include/csn_hip.h)
+
+
+def _f32_rows(t, name, ndim):
+    if t.dtype != torch.float32 or t.dim() != ndim:
+        raise CsnError(f"{name}: expected a float32 tensor of {ndim} dimensions, got {t.dtype} {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def distill_loss(student, teacher, soft_mode, T, w_soft, logits=None, labels=None, w_ce=0.0, want_grad=True,
+                 grad_scale=1.0):
+    """csn_distill_loss on student / teacher [B,D] float32 -> (loss[1], dstudent | None, dlogits | None).
+    ``logits`` may be ``student`` itself (the alias: K == D; the CE gradient is then part of dstudent and dlogits is None).
+    ``want_grad``: a bool for both gradients or a pair (dstudent, dlogits)."""
+    _need_cuda(student, teacher, logits, labels)
+    alias = logits is student
+    s, t = _f32_rows(student, "student", 2), _f32_rows(teacher, "teacher", 2)
+    B, D = s.shape
+    if t.shape != s.shape:
+        raise CsnError(f"distill_loss: teacher {tuple(t.shape)} against student {tuple(s.shape)}")
+    if (logits is None) != (labels is None):
+        raise CsnError("distill_loss: logits and labels go together")
+    lg, lab, K = None, None, 0
+    if logits is not None:
+        lg = s if alias else _f32_rows(logits, "logits", 2)
+        K = lg.shape[1]
+        lab = labels.to(torch.int64).contiguous()
+        if lg.shape[0] != B or lab.shape != (B,):
+            raise CsnError(f"distill_loss: logits {tuple(lg.shape)} / labels {tuple(lab.shape)} against B = {B}")
+    want_ds, want_dl = want_grad if isinstance(want_grad, (tuple, list)) else (want_grad, want_grad)
+    loss = torch.empty(1, dtype=torch.float32, device=s.device)
+    ds = torch.empty_like(s) if want_ds else None
+    dl = torch.empty_like(lg) if (want_dl and lg is not None and not alias) else None
+    lib = load()
+    scratch = torch.empty(lib.csn_distill_loss_scratch_bytes(B) // 8, dtype=torch.float64, device=s.device)   # caller-owned
+    with torch.cuda.device(s.device):
+        _check(lib.csn_distill_loss(_ptr(s), _ptr(t), B, D, _ptr(lg), K, _ptr(lab), int(soft_mode), float(T), float(w_soft),
+                                    float(w_ce), _ptr(loss), _ptr(ds), _ptr(dl), float(grad_scale), _ptr(scratch), _stream()))
+    return loss, ds, dl
+
+
+def dino_loss(student, teacher, center, teacher_temp, student_temp, pairing, want_grad=True, grad_scale=1.0):
+    """csn_dino_loss on student [V,B,D], teacher [G,B,D], center [D] or [B,D] (float32) -> (loss[1], dstudent | None)."""
+    _need_cuda(student, teacher, center)
+    s, t = _f32_rows(student, "student", 3), _f32_rows(teacher, "teacher", 3)
+    V, B, D = s.shape
+    G = t.shape[0]
+    if t.shape[1:] != s.shape[1:]:
+        raise CsnError(f"dino_loss: teacher {tuple(t.shape)} against student {tuple(s.shape)}")
+    if center.dtype != torch.float32 or center.numel() not in (D, B * D) or center.shape[-1] != D:
+        raise CsnError(f"dino_loss: center {center.dtype} {tuple(center.shape)} is neither [D] nor [B,D] float32")
+    c = center.contiguous()
+    stride = D if (c.numel() == B * D and c.dim() > 1 and c.shape[-2] == B) else 0
+    loss = torch.empty(1, dtype=torch.float32, device=s.device)
+    ds = torch.empty_like(s) if want_grad else None
+    lib = load()
+    scratch = torch.empty(lib.csn_dino_loss_scratch_bytes(B, D) // 8, dtype=torch.float64, device=s.device)   # caller-owned
+    with torch.cuda.device(s.device):
+        _check(lib.csn_dino_loss(_ptr(s), _ptr(t), V, G, B, D, _ptr(c), stride, float(teacher_temp), float(student_temp),
+                                 int(pairing), _ptr(loss), _ptr(ds), float(grad_scale), _ptr(scratch), _stream()))
     return loss, ds
 
 

@@ -29,6 +29,8 @@ import torch.distributed as dist
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import cabi
+
 
 def cosine_scheduler(base_value, final_value, epochs, niter_per_ep, warmup_epochs=0, start_warmup_value=0):
     """Per-iteration schedule: ``warmup_epochs`` of linear ramp start_warmup_value -> base_value (end point
@@ -84,10 +86,34 @@ class MultiCropWrapper(nn.Module):
         return self.head(torch.cat(rows))
 
 
+class _DinoLossFn(torch.autograd.Function):
+    """csn_dino_loss: the student gradient is computed in the forward, saved, and multiplied by the incoming scalar."""
+
+    @staticmethod
+    def forward(ctx, student_vbd, teacher_gbd, center, teacher_temp, student_temp, pairing):
+        loss, ds = cabi.dino_loss(student_vbd, teacher_gbd, center, teacher_temp, student_temp, pairing,
+                                  want_grad=ctx.needs_input_grad[0])
+        ctx.has_grad = ds is not None
+        ctx.save_for_backward(ds) if ds is not None else None
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.has_grad:
+            return None, None, None, None, None, None
+        (ds,) = ctx.saved_tensors
+        return ds * g, None, None, None, None, None
+
+
 class DINOLoss(nn.Module):
+    """``fused=True``: loss and student gradient from one csn_dino_loss call (float64 arithmetic, two launches) when
+    student, teacher and centre are float32 device tensors; anything else takes the torch form below.  The centre
+    update stays in torch either way."""
+
     def __init__(self, out_dim, ncrops, warmup_teacher_temp, teacher_temp, warmup_teacher_temp_epochs, nepochs,
-                 student_temp=0.1, center_momentum=0.9, compat=True):
+                 student_temp=0.1, center_momentum=0.9, compat=True, fused=False):
         super().__init__()
+        self.fused = bool(fused)
         self.student_temp, self.center_momentum, self.ncrops, self.compat = student_temp, center_momentum, ncrops, compat
         self.register_buffer("center", torch.zeros(1, out_dim))
         ramp = np.linspace(warmup_teacher_temp, teacher_temp, warmup_teacher_temp_epochs)
@@ -95,6 +121,10 @@ class DINOLoss(nn.Module):
 
     def forward(self, student_output, teacher_output, epoch):
         temp = self.teacher_temp_schedule[epoch]
+        if self.fused and all(t.is_cuda and t.dtype == torch.float32 for t in (student_output, teacher_output, self.center)):
+            loss = self._fused_forward(student_output, teacher_output.detach(), float(temp))
+            self.update_center(teacher_output)
+            return loss
         q = F.softmax((teacher_output - self.center) / temp, dim=-1).detach()
         log_p = F.log_softmax(student_output / self.student_temp, dim=-1)
         if self.compat:
@@ -109,6 +139,15 @@ class DINOLoss(nn.Module):
             loss = sum(-(g_views[g] * (total - s_views[g])).sum(dim=-1).mean() for g in range(2)) / (2 * (self.ncrops - 1))
         self.update_center(teacher_output)
         return loss
+
+    def _fused_forward(self, student_output, teacher_output, temp):
+        if self.compat:         # stacked views [V, B, out] / [G, B, out]; the centre is [1, out] or, once updated, [1, B, out]
+            return _DinoLossFn.apply(student_output, teacher_output, self.center, temp, self.student_temp,
+                                     cabi.DINO_SKIP_FIRST)
+        # row-concatenated views [V * B, out] / [2 * B, out] seen as [V, B, out] / [2, B, out]
+        d = student_output.shape[-1]
+        return _DinoLossFn.apply(student_output.reshape(self.ncrops, -1, d), teacher_output.reshape(2, -1, d), self.center,
+                                 temp, self.student_temp, cabi.DINO_SKIP_SAME)
 
     @torch.no_grad()
     def update_center(self, teacher_output):

@@ -1,7 +1,7 @@
 """Losses of the distillation path, same names / argument meaning as the reference classes.
 
   CosineSimilarityLoss       LstmDistillFromDinoV2Train.py:36-43   (fused HIP forward+gradient)
-  FeatureDistributionLoss    LstmDistillFromDinoV2Train.py:107-140 (torch ops; not hot)
+  FeatureDistributionLoss    LstmDistillFromDinoV2Train.py:107-140 (torch ops; fused=True: csn_distill_loss)
   loss_fn_kd                 LstmDistillFromDinoV2TrainSpampinato.py:107-121
   FeatureDistributionLossKD  LstmDistillFromDinoV2TrainSpampinato.py:125-184 (soft-target KL + CE)
   FeatureDistributionLossSoft LstmDistillFromDinoV2Eval.py:106-146 (soft-target KL alone)
@@ -11,6 +11,10 @@
 Every class is checked against values and gradients obtained by executing the reference's own definition
 (tests/golden/ref_losses.npz, tests/test_ref_pinned.py).
 Reference quirks are kept on purpose.
+
+``fused=True`` on FeatureDistributionLoss, its KD and Soft variants and loss_fn_kd: value and gradient come from ONE
+csn_distill_loss call (float64 arithmetic, two launches) when every tensor input is a float32
+device tensor; anything else (CPU tensors, float64) takes the torch form.  Opt-in: the default keeps the torch form.
 """
 import numpy as np
 import torch
@@ -56,16 +60,46 @@ class CosineSimilarityLoss(nn.Module):
         return _CosineLossFn.apply(student_outputs, teacher_outputs)
 
 
+def _fusable(*tensors):
+    """Every given tensor is on a GPU, and float32 unless it holds integers (labels)."""
+    return all(t is not None and t.is_cuda and (t.dtype == torch.float32 or not t.is_floating_point()) for t in tensors)
+
+
+class _DistillLossFn(torch.autograd.Function):
+    """csn_distill_loss: the gradients are computed in the forward, saved, and multiplied by the incoming scalar.
+    ``logits is None`` with ``alias``: the student tensor is also the logits of the CE term."""
+
+    @staticmethod
+    def forward(ctx, student, teacher, logits, labels, soft_mode, T, w_soft, w_ce, alias):
+        want = (ctx.needs_input_grad[0], ctx.needs_input_grad[2])
+        loss, ds, dl = cabi.distill_loss(student, teacher, soft_mode, T, w_soft, logits=student if alias else logits,
+                                         labels=labels, w_ce=w_ce, want_grad=want)
+        ctx.have = (ds is not None, dl is not None)
+        ctx.save_for_backward(*[g for g in (ds, dl) if g is not None])
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        saved = list(ctx.saved_tensors)
+        ds = saved.pop(0) * g if ctx.have[0] else None
+        dl = saved.pop(0) * g if ctx.have[1] else None
+        return ds, None, dl, None, None, None, None, None, None
+
+
 class FeatureDistributionLoss(nn.Module):
-    def __init__(self, nepochs, warmup_teacher_temp, teacher_temp, warmup_teacher_temp_epochs):
+    def __init__(self, nepochs, warmup_teacher_temp, teacher_temp, warmup_teacher_temp_epochs, fused=False):
         super().__init__()
         self.mse = nn.MSELoss()
+        self.fused = bool(fused)
         self.teacher_temp_schedule = np.concatenate((
             np.linspace(warmup_teacher_temp, teacher_temp, warmup_teacher_temp_epochs),
             np.ones(max(0, nepochs - warmup_teacher_temp_epochs)) * teacher_temp))
 
     def forward(self, student_outputs, teacher_outputs, epoch, label, pred_label=None):
         HyperParams.T = self.teacher_temp_schedule[epoch]
+        if self.fused and _fusable(student_outputs, teacher_outputs, label, pred_label):
+            return _DistillLossFn.apply(student_outputs, teacher_outputs, pred_label, label, cabi.SOFT_CE_OF_PROBS,
+                                        float(HyperParams.T), HyperParams.beta, HyperParams.alpha, False)
         teacher_logits_with_T = F.softmax(teacher_outputs / HyperParams.T, dim=-1)
         student_logits_with_T = F.softmax(student_outputs / HyperParams.T, dim=-1)
         term1 = HyperParams.alpha * F.cross_entropy(pred_label, label)
@@ -88,6 +122,10 @@ class FeatureDistributionLossKD(FeatureDistributionLoss):
 
     def forward(self, student_outputs, teacher_outputs, epoch, label):
         HyperParams.T = self.teacher_temp_schedule[epoch]
+        if self.fused and _fusable(student_outputs, teacher_outputs, label):
+            T = float(HyperParams.T)
+            return _DistillLossFn.apply(student_outputs, teacher_outputs, None, label, cabi.SOFT_KL, T,
+                                        HyperParams.soft_target_loss_weight * T * T, HyperParams.ce_loss_weight, True)
         return HyperParams.soft_target_loss_weight * _soft_target_kl(student_outputs, teacher_outputs, HyperParams.T) \
             + HyperParams.ce_loss_weight * F.cross_entropy(student_outputs, label)
 
@@ -99,6 +137,9 @@ class FeatureDistributionLossSoft(FeatureDistributionLoss):
 
     def forward(self, student_outputs, teacher_outputs, epoch):
         HyperParams.T = self.teacher_temp_schedule[epoch]
+        if self.fused and _fusable(student_outputs, teacher_outputs):
+            T = float(HyperParams.T)
+            return _DistillLossFn.apply(student_outputs, teacher_outputs, None, None, cabi.SOFT_KL, T, T * T, 0.0, False)
         return _soft_target_kl(student_outputs, teacher_outputs, HyperParams.T)
 
 
@@ -111,8 +152,12 @@ class FeatureDistributionLossMSE(nn.Module):
         return 0.4 * d_std * d_std + 0.4 * d_mean * d_mean + 0.2 * F.mse_loss(student_outputs, teacher_outputs)
 
 
-def loss_fn_kd(outputs, labels, teacher_outputs, params):
+def loss_fn_kd(outputs, labels, teacher_outputs, params, fused=False):
     alpha, T = params.alpha, params.temperature
+    if fused and outputs.dim() == 2 and _fusable(outputs, teacher_outputs, labels):
+        # nn.KLDivLoss() keeps reduction='mean': the mean over all B * D elements
+        return _DistillLossFn.apply(outputs, teacher_outputs, None, labels, cabi.SOFT_KL, float(T),
+                                    alpha * T * T / outputs.shape[1], 1. - alpha, True)
     return nn.KLDivLoss()(F.log_softmax(outputs / T, dim=1), F.softmax(teacher_outputs / T, dim=1)) * (alpha * T * T) \
         + F.cross_entropy(outputs, labels) * (1. - alpha)
 

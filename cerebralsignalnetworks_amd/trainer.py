@@ -227,9 +227,12 @@ def check_device_status(model, collective=True):
 
 class DistillTrainer:
     def __init__(self, model, sos, ddof=0, loss="cosine", lr=1e-3, optimizer="rmsprop", nepochs=100,
-                 kd_params=None, preprocess=True, accum_steps=1, fused_optimizer=False):
+                 kd_params=None, preprocess=True, accum_steps=1, fused_optimizer=False, fused_loss=False):
         """``fused_optimizer=True`` (on a GPU): adamw / adam / lars step the flat buffers in one to three HIP launches
         (flat_optim.FlatAdamW / FlatLARS) instead of the torch optimisers; rmsprop is fused either way.
+
+        ``fused_loss=True``: the featdist and kd losses compute value and gradient in one csn_distill_loss call (float64
+        arithmetic, two launches) instead of a chain of torch ops; cosine is fused either way, barlow is not affected.
 
         ``accum_steps = k > 1``: train_step splits its batch into k equal micro-batches and sums their gradients (each
         loss scaled by 1 / k) in the flat buffer before the one all-reduce and optimiser step -- the step of the whole
@@ -270,7 +273,8 @@ class DistillTrainer:
             raise ValueError(optimizer)
         self.cosine = CosineSimilarityLoss()
         self.featdist = FeatureDistributionLoss(nepochs, HyperParams.warmup_teacher_temp, HyperParams.teacher_temp,
-                                                HyperParams.warmup_teacher_temp_epochs)
+                                                HyperParams.warmup_teacher_temp_epochs, fused=fused_loss)
+        self.fused_loss = bool(fused_loss)
         self.kd_params = kd_params
         self.barlow = None
         rank, world = dist_info()
@@ -341,7 +345,7 @@ class DistillTrainer:
             return self.featdist(feat, targets, epoch, labels, pred_label=cls)
         if self.loss_name == "kd":
             feat = out[0] if isinstance(out, tuple) else out
-            return loss_fn_kd(feat, labels, targets, self.kd_params)
+            return loss_fn_kd(feat, labels, targets, self.kd_params, fused=self.fused_loss)
         if self.loss_name == "barlow":
             # BASELINE.json config 5: Barlow-Twins cross-correlation between the LSTM embedding of the EEG view
             # and the (frozen) image embedding; net.py:33-42 with the global batch size and an all-reduced c

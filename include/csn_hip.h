@@ -87,8 +87,8 @@ enum csnDtype { CSN_F32 = 0, CSN_BF16 = 1 };
 
 /* ABI version of this header; bumped on any signature change.  A symbol added beside the existing ones
  * (csn_lstm_plan_set_grad_mode, csn_lstm_plan_set_lengths, csn_lstm_plan_set_io, csn_lstm_plan_half_tile_launches, the
- * csn_flat_* family, csn_adam_step, csn_lars_step, csn_eeg_bandpass_stream and its _path) breaks no caller and does not
- * bump it; neither does a new bit of csn_lstm_plan_create's `training` word. */
+ * csn_flat_* family, csn_adam_step, csn_lars_step, csn_eeg_bandpass_stream and its _path, csn_distill_loss,
+ * csn_dino_loss) breaks no caller and does not bump it; neither does a new bit of csn_lstm_plan_create's `training` word. */
 #define CSN_ABI_VERSION 6
 int csn_abi_version(void);
 /* Thread-local message for the last non-zero status returned on this thread. */
@@ -432,6 +432,63 @@ int csn_lstm_cell_backward(const void* dgates_next, const void* w_hh_t,
 size_t csn_cosine_loss_scratch_bytes(int B);
 int csn_cosine_loss(const float* student, const float* teacher, int B, int D,
                     float* loss, float* dstudent, float grad_scale, void* scratch, csnStream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * K5b  the distillation losses of the training scripts, value and gradient in two launches.
+ * Both entry points follow csn_cosine_loss: float32 inputs, float64 arithmetic, each float32 output rounded once;
+ * caller-owned scratch of *_scratch_bytes (8-byte aligned), no library state; everything enqueued on `stream`.  Every
+ * softmax and log-softmax subtracts the row maximum first.  One wave per row; a row of D <= 1024 stays in registers, a
+ * longer one is re-read in every pass.  Per-row float64 partial sums are added by a finishing launch in an order that
+ * depends on the row count only: two calls on the same input give the same bits.
+ *
+ * csn_distill_loss: student[B,D], teacher[B,D]; logits[B,K] and labels int64[B], both or neither (NULL).
+ *     loss = fl32( w_soft/B * sum_b soft_b + w_ce/B * sum_b ce_b )        (without logits: the first term alone)
+ *   soft_mode CSN_SOFT_KL:          soft_b = sum_o p_t (log p_t - log_softmax(student_b / T)_o), p_t = softmax(teacher_b / T).
+ *     A term with p_t == 0 is 0: nn.KLDivLoss's convention.  The explicit torch formula
+ *     sum(p_t * (p_t.log() - log_q)) gives NaN there (0 * -inf) and the same value everywhere else.
+ *   soft_mode CSN_SOFT_CE_OF_PROBS: soft_b = - sum_o softmax(student_b / T)_o * log_softmax(p_t)_o -- the reference's
+ *     F.cross_entropy(teacher_probabilities, student_probabilities): probabilities used as logits.
+ *   ce_b = - log_softmax(logits_b)[labels_b].  A label outside [0, K) makes that row's ce_b -- hence the loss -- and the
+ *     row's CE gradient NaN; the label is checked before it is used, nothing outside the row is read.
+ *   `logits` may be `student` itself (the KD case: one tensor distilled and classified); then K == D is required, the CE
+ *     gradient is added to the soft gradient in float64 before the one rounding into dstudent, and dlogits must be NULL.
+ *   Gradients (both optional), multiplied by grad_scale:
+ *     KL:          dstudent = w_soft/(B T) (softmax(s/T) - p_t)
+ *     CE_OF_PROBS: dstudent = - w_soft/(B T) q o (a - sum_o q a),  a = log_softmax(p_t), q = softmax(s/T)
+ *     CE:          dlogits (or, aliased, added into dstudent) = w_ce/B (softmax(logits) - onehot(labels))
+ *   An output passed as NULL is not written.
+ *   Refused on the host before any launch: a null student / teacher / loss / scratch, B <= 0 or D <= 0, T not finite or
+ *   not positive, an unknown soft_mode, logits without labels or with K <= 0, the alias with K != D, dlogits without
+ *   logits or together with the alias, misaligned scratch.
+ *   The library's losses:  FeatureDistributionLoss   CE_OF_PROBS, logits = pred_label, w_soft = beta, w_ce = alpha
+ *                          loss_fn_kd                KL, alias, w_soft = alpha T^2 / D, w_ce = 1 - alpha
+ *                          FeatureDistributionLossKD KL, alias, w_soft = 0.25 T^2, w_ce = 0.75
+ *                          FeatureDistributionLossSoft KL, no logits, w_soft = T^2
+ *   Replaces: LstmDistillFromDinoV2Train.py:107-140, LstmDistillFromDinoV2TrainSpampinato.py:107-184,
+ *   LstmDistillFromDinoV2Eval.py:106-146.
+ *
+ * csn_dino_loss: student[V,B,D], teacher[G,B,D]; center + b * center_stride_b is the centre of batch row b:
+ *   center_stride_b 0 = one shared [D] centre, D = the per-sample [B,D] centre the reference's update_center makes of it.
+ *     q[g,b] = softmax((teacher[g,b] - center_b) / teacher_temp),  logp[v,b] = log_softmax(student[v,b] / student_temp)
+ *     loss = fl32( - c * sum_{g,b} sum_{v in S_g} q[g,b] . logp[v,b] ),  c = 1 / (G B (V - 1))
+ *   pairing CSN_DINO_SKIP_FIRST: S_g = {1 .. V-1} (the reference's chunk(1), LstmDistillation.py:128);
+ *   pairing CSN_DINO_SKIP_SAME:  S_g = {v != g} (the pairing of the DINO paper).
+ *   dstudent[V,B,D] (optional) = grad_scale * (-c / student_temp) (sum_{g: v in S_g} q[g,b] - n_v softmax(student[v,b] / student_temp)),
+ *   n_v = |{g : v in S_g}|; a view that no pair uses gets an explicit zero row.
+ *   Refused on the host: null pointers (other than dstudent), B <= 0 or D <= 0, V < 2, G outside [1, V], a
+ *   center_stride_b other than 0 or D, temperatures not finite or not positive, an unknown pairing, misaligned scratch.
+ *   The centre update (and its all-reduce) is not part of the call.  Replaces: DINOLoss.forward, LstmDistillation.py:118-148.
+ * ---------------------------------------------------------------------------------- */
+enum csnSoftMode { CSN_SOFT_KL = 0, CSN_SOFT_CE_OF_PROBS = 1 };
+enum csnDinoPairing { CSN_DINO_SKIP_FIRST = 0, CSN_DINO_SKIP_SAME = 1 };
+size_t csn_distill_loss_scratch_bytes(int B);
+int csn_distill_loss(const float* student, const float* teacher, int B, int D, const float* logits, int K,
+                     const int64_t* labels, int soft_mode, double T, double w_soft, double w_ce, float* loss,
+                     float* dstudent, float* dlogits, float grad_scale, void* scratch, csnStream_t stream);
+size_t csn_dino_loss_scratch_bytes(int B, int D);
+int csn_dino_loss(const float* student, const float* teacher, int V, int G, int B, int D, const float* center,
+                  int64_t center_stride_b, double teacher_temp, double student_temp, int pairing, float* loss,
+                  float* dstudent, float grad_scale, void* scratch, csnStream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * Optimiser step of the hot loop over ONE flat float32 parameter / gradient / state buffer (16-byte aligned).
