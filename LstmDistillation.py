@@ -65,6 +65,13 @@ def build_parser():
     p.add_argument('--fused_loss', action='store_true',
                    help='DINO loss value and student gradient from one fused HIP call in float64 (csn_dino_loss) instead of '
                         'a chain of torch ops; the centre update is unchanged')
+    p.add_argument('--fused_views', action='store_true',
+                   help='all 2 + local_crops_number views of a step in ONE student pass and both global views in ONE '
+                        'teacher pass, cut out of the batch in place by the LSTM\'s input windows (one backward). With '
+                        '--lstm_dropout the fused pass draws other dropout masks than the per-view passes (a mask depends '
+                        'on the plan\'s batch and steps): masks of the same law, not the same bits')
+    p.add_argument('--per_sample_crops', action='store_true',
+                   help='one crop start per (view, sample) instead of one per view; needs --fused_views')
     return p
 
 
@@ -77,7 +84,10 @@ def main(argv=None):
     from cerebralsignalnetworks_amd.lstm_model import HipLSTM
     from cerebralsignalnetworks_amd.trainer import FlatGrads, check_device_status, shard_indices, split_indices
 
-    FLAGS, _ = build_parser().parse_known_args(argv)
+    parser = build_parser()
+    FLAGS, _ = parser.parse_known_args(argv)
+    if FLAGS.per_sample_crops and not FLAGS.fused_views:
+        parser.error("--per_sample_crops needs --fused_views")
     rank, world, local = init_distributed()
     device = torch.device("cuda", local)
     torch.manual_seed(FLAGS.seed)
@@ -142,10 +152,17 @@ def main(argv=None):
                     group["weight_decay"] = wd_schedule[it]
             b = shard[it_local * FLAGS.batch_size_per_gpu:(it_local + 1) * FLAGS.batch_size_per_gpu]
             eeg = dataset.eeg_all[b].transpose(1, 2).contiguous()                       # [B,T,C]
-            gviews, lviews = temporal_crops(eeg, 2, FLAGS.local_crops_number)
-            with torch.no_grad():
-                teacher_outputs = torch.stack([teacher(v.contiguous()) for v in gviews], dim=0)
-            student_outputs = torch.stack([student(v.contiguous()) for v in gviews + lviews], dim=0)
+            if FLAGS.fused_views:
+                starts, lengths = temporal_crops(eeg, 2, FLAGS.local_crops_number, as_views=True,
+                                                 per_sample=FLAGS.per_sample_crops)
+                with torch.no_grad():
+                    teacher_outputs = teacher.forward_views(eeg, starts[:2], lengths[:2])
+                student_outputs = student.forward_views(eeg, starts, lengths)
+            else:
+                gviews, lviews = temporal_crops(eeg, 2, FLAGS.local_crops_number)
+                with torch.no_grad():
+                    teacher_outputs = torch.stack([teacher(v.contiguous()) for v in gviews], dim=0)
+                student_outputs = torch.stack([student(v.contiguous()) for v in gviews + lviews], dim=0)
             loss = dino_loss(student_outputs, teacher_outputs, EPOCH)
             grads.zero()
             loss.backward()

@@ -55,6 +55,8 @@ SIGNATURES = {
     "csn_lstm_plan_set_grad_callback": (_c_int, [_c_void_p, _c_void_p, _c_void_p]),
     "csn_lstm_plan_set_grad_mode": (_c_int, [_c_void_p, _c_int]),
     "csn_lstm_plan_set_lengths": (_c_int, [_c_void_p, ctypes.POINTER(ctypes.c_int32)]),
+    "csn_lstm_plan_set_views": (_c_int, [_c_void_p, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                                         ctypes.c_int32, ctypes.c_int32]),
     "csn_lstm_plan_set_io": (_c_int, [_c_void_p, _c_i64, _c_i64, _c_int]),
     "csn_lstm_plan_set_dropout": (_c_int, [_c_void_p, _c_float, ctypes.c_uint64, ctypes.c_uint32]),
     "csn_lstm_dropout_keep": (_c_int, [ctypes.c_uint64, ctypes.c_uint32, _c_float, _c_i64, _c_i64, _c_void_p]),
@@ -343,6 +345,7 @@ class LstmPlan:
         self.dropout = bool(dropout)
         self.reverse = bool(reverse)
         self._io = (0, 0, False)
+        self._views = None          # (src_rows, src_T) while input windows are set (set_views)
         self.device = torch.device(device)
         lib = load()
         handle = _c_void_p()
@@ -407,6 +410,24 @@ class LstmPlan:
             raise CsnError(f"LSTM lengths: {len(vals)} entries for a batch of {self.desc.B}")
         _check(load().csn_lstm_plan_set_lengths(self._plan, (ctypes.c_int32 * len(vals))(*vals)))
 
+    def set_views(self, rows, starts=None, src_rows=None, src_T=None):
+        """Input windows of the following forward() calls (csn_lstm_plan_set_views): row b of the LSTM batch is row
+        ``rows[b]`` of a source tensor [src_rows, src_T, I] from step ``starts[b]`` on, for lengths[b] steps (T without
+        lengths); forward() then takes that source tensor, whatever its strides, instead of a [B, T, I] input, and reads
+        nothing past a row's window.  Two sequences of B ints (or CPU int tensors); ``set_views(None)`` turns windows
+        off.  Sticky until set again.  Every result has the bits of the call on the gathered dense rows."""
+        if rows is None:
+            _check(load().csn_lstm_plan_set_views(self._plan, None, None, 0, 0))
+            self._views = None
+            return
+        r = [int(v) for v in (rows.tolist() if isinstance(rows, torch.Tensor) else rows)]
+        t = [int(v) for v in (starts.tolist() if isinstance(starts, torch.Tensor) else starts)]
+        if len(r) != self.desc.B or len(t) != self.desc.B:
+            raise CsnError(f"LSTM views: {len(r)} rows and {len(t)} starts for a batch of {self.desc.B}")
+        _check(load().csn_lstm_plan_set_views(self._plan, (ctypes.c_int32 * len(r))(*r), (ctypes.c_int32 * len(t))(*t),
+                                              int(src_rows), int(src_T)))
+        self._views = (int(src_rows), int(src_T))
+
     def set_io(self, y_all_pitch=0, dy_all_pitch=0, dx_add=False):
         """Where the following calls find y_all / dy_all and how they store dx (csn_lstm_plan_set_io).  A pitch is the
         number of elements per (b, t) row, 0 = dense (H): forward(y_all=view) then writes, and backward(dy_all=view) reads,
@@ -444,7 +465,8 @@ class LstmPlan:
 
     def forward(self, x_bti, w_ih, w_hh, b_ih, b_hh, want_all=False, h0=None, c0=None, want_state=False, y_all=None,
                 state_out=None):
-        """-> (y_last, y_all); with want_state=True -> (y_last, y_all, h_n, c_n).  h0 / c0: [L,B,H] initial state or
+        """-> (y_last, y_all); with want_state=True -> (y_last, y_all, h_n, c_n).  With input windows set (set_views)
+        x_bti is the SOURCE [src_rows, src_T, I], passed with its own strides.  h0 / c0: [L,B,H] initial state or
         None (zeros); the state keywords need a plan created with state=True.  y_all: a [B,T,H] view to write every step
         into (its pitch set with set_io) instead of a new tensor.  state_out: (h_n, c_n), dense float32 [L,B,H] tensors (or
         slices of larger ones) to write the final state into, with want_state=True."""
@@ -452,7 +474,8 @@ class LstmPlan:
         _need_cuda(x_bti)
         if x_bti.dtype != torch.float32 or x_bti.stride(2) != 1:
             x_bti = x_bti.float().contiguous()
-        assert x_bti.shape == (d.B, d.T, d.I), (tuple(x_bti.shape), (d.B, d.T, d.I))
+        want = (d.B, d.T, d.I) if self._views is None else self._views + (d.I,)
+        assert x_bti.shape == want, (tuple(x_bti.shape), want)
         y_last = torch.empty((d.B, d.H), dtype=torch.float32, device=x_bti.device)
         if y_all is not None:
             y_all = self._pitched(y_all, self._io[0], "y_all")

@@ -153,8 +153,10 @@ int launch_cell_bwd_batch(const CellBwdBatch& b, int np, int B, int H, int dtype
 // ---- internal launchers shared across translation units --------------------------------
 // out[r*ldo + c] = (T)in[strided]; generic strided cast used for the time-major input copy.
 // rev != 0 (reverse LSTM plans): index i1 of row i0 is read at n - 1 - i1, n = len[i0] (n1 without len); zeros from n on
+// vrow / vt0 != NULL (input windows): row i0 is source row vrow[i0] from index vt0[i0] on, never read from n on
 int launch_cast_strided(const float* src, int64_t s0, int64_t s1, int64_t n0, int64_t n1, int64_t n2,
-                        void* dst, int dtype, hipStream_t st, const int* len = nullptr, int rev = 0);
+                        void* dst, int dtype, hipStream_t st, const int* len = nullptr, int rev = 0,
+                        const int* vrow = nullptr, const int* vt0 = nullptr);
 // dst[c*R + r] = (T)src[r*C + c]
 int launch_transpose_cast(const float* src, int64_t R, int64_t C, void* dst, int dtype, hipStream_t st);
 // dst = (T)src, n elements

@@ -508,6 +508,13 @@ struct csnLstmPlan {
   int32_t* len_dev = nullptr;
   int32_t* len_pin = nullptr;            // pinned staging of the upload, and the event behind its last copy
   hipEvent_t len_ev = nullptr;
+  // csn_lstm_plan_set_views (empty = off): per row the source row and the first source step of its input window, and
+  // the source's extents.  view_dev / view_pin: [2 B] int32 (rows, then starts), uploaded by every forward like the lengths
+  std::vector<int32_t> view_row, view_t0;
+  int view_src_rows = 0, view_src_T = 0;
+  int32_t* view_dev = nullptr;
+  int32_t* view_pin = nullptr;
+  hipEvent_t view_ev = nullptr;
   void grads_ready(int layer) const {
     if (grad_cb != nullptr) grad_cb(grad_cb_user, layer);
   }
@@ -560,6 +567,9 @@ extern "C" void csn_lstm_plan_destroy(csnLstmPlan* P) {
   if (P->len_ev) (void)hipEventDestroy(P->len_ev);
   if (P->len_pin) (void)hipHostFree(P->len_pin);
   if (P->len_dev) (void)hipFree(P->len_dev);
+  if (P->view_ev) (void)hipEventDestroy(P->view_ev);
+  if (P->view_pin) (void)hipHostFree(P->view_pin);
+  if (P->view_dev) (void)hipFree(P->view_dev);
   if (switched) (void)hipSetDevice(cur);
   delete P;
 }
@@ -637,6 +647,30 @@ extern "C" int csn_lstm_plan_set_lengths(csnLstmPlan* P, const int32_t* lengths)
   return CSN_OK;
 }
 
+extern "C" int csn_lstm_plan_set_views(csnLstmPlan* P, const int32_t* src_row, const int32_t* t0, int32_t src_rows,
+                                       int32_t src_T) {
+  CSN_REQUIRE(P != nullptr, "csn_lstm_plan_set_views: null plan");
+  CSN_REQUIRE((src_row == nullptr) == (t0 == nullptr), "csn_lstm_plan_set_views: exactly one of src_row and t0 is null");
+  if (src_row == nullptr) {
+    P->view_row.clear();
+    P->view_t0.clear();
+    P->view_src_rows = P->view_src_T = 0;
+    return CSN_OK;
+  }
+  CSN_REQUIRE(src_rows >= 1, "csn_lstm_plan_set_views: src_rows = %d", (int)src_rows);
+  CSN_REQUIRE(src_T >= 1, "csn_lstm_plan_set_views: src_T = %d", (int)src_T);
+  for (int b = 0; b < P->d.B; ++b) {
+    CSN_REQUIRE(src_row[b] >= 0 && src_row[b] < src_rows, "csn_lstm_plan_set_views: src_row[%d] = %d outside [0, %d)", b,
+                (int)src_row[b], (int)src_rows);
+    CSN_REQUIRE(t0[b] >= 0, "csn_lstm_plan_set_views: t0[%d] = %d is negative", b, (int)t0[b]);
+  }
+  P->view_row.assign(src_row, src_row + P->d.B);
+  P->view_t0.assign(t0, t0 + P->d.B);
+  P->view_src_rows = src_rows;
+  P->view_src_T = src_T;
+  return CSN_OK;
+}
+
 extern "C" int csn_lstm_plan_set_dropout(csnLstmPlan* P, float p, uint64_t seed, uint32_t subsequence) {
   CSN_REQUIRE(P != nullptr, "csn_lstm_plan_set_dropout: null plan");
   CSN_REQUIRE(p >= 0.f && p <= 1.f, "csn_lstm_plan_set_dropout: p = %g outside [0, 1]", (double)p);      // (NaN fails both)
@@ -684,6 +718,28 @@ static int upload_lengths(csnLstmPlan* P, hipStream_t st, const int** dlen) {
   return CSN_OK;
 }
 
+// input windows of the forward in progress -> the plan's device arrays, in stream order, exactly as upload_lengths does
+// (the backward reads no x and uploads nothing); *vrow / *vt0: the [B] arrays, or null for a plan without windows
+static int upload_views(csnLstmPlan* P, hipStream_t st, const int** vrow, const int** vt0) {
+  *vrow = *vt0 = nullptr;
+  if (P->view_row.empty()) return CSN_OK;
+  const size_t B = (size_t)P->d.B, bytes = 2 * B * 4;
+  if (P->view_pin == nullptr) {
+    CSN_HIP_CHECK(hipMalloc((void**)&P->view_dev, bytes));
+    CSN_HIP_CHECK(hipHostMalloc((void**)&P->view_pin, bytes, hipHostMallocDefault));
+    CSN_HIP_CHECK(hipEventCreateWithFlags(&P->view_ev, hipEventDisableTiming));
+  } else {
+    CSN_HIP_CHECK(hipEventSynchronize(P->view_ev));
+  }
+  memcpy(P->view_pin, P->view_row.data(), B * 4);
+  memcpy(P->view_pin + B, P->view_t0.data(), B * 4);
+  CSN_HIP_CHECK(hipMemcpyAsync(P->view_dev, P->view_pin, bytes, hipMemcpyHostToDevice, st));
+  CSN_HIP_CHECK(hipEventRecord(P->view_ev, st));
+  *vrow = P->view_dev;
+  *vt0 = P->view_dev + B;
+  return CSN_OK;
+}
+
 // One forward or backward call: lives on the stack of csn_lstm_forward / csn_lstm_backward and is handed to every path and
 // helper below.  What holds for the duration of a call only is here, not in the plan: P.d is never written after
 // csn_lstm_plan_create.  A call with lengths runs every path over the steps of the longest row (all saved tensors are
@@ -695,6 +751,8 @@ struct Call {
   char* ws;
   hipStream_t st;       // the caller's stream
   const int* dlen;      // device copy of the lengths ([B] int32, owned by the plan), null without lengths
+  const int* vrow = nullptr;      // device copies of the input windows of a forward ([B] int32 each, owned by the plan),
+  const int* vt0 = nullptr;       // null without windows
   int T;                // the steps this call runs: the longest row with lengths, else d.T
   int T_full;           // d.T: the steps per row of the caller's batch-first tensors
   int B, H, NL, dt, Cz; // Cz: steps per chunk
@@ -938,7 +996,7 @@ static int prep_row_major(const Call& C, const FwdArgs& A) {
   const int H = C.H, dt = C.dt;
   const int64_t G = C.G;
   int rc;
-  if ((rc = launch_cast_strided(A.x, A.xsb, A.xst, C.B, C.T, C.d.I, ws + w.x_c, dt, st, C.dlen, C.P.reverse))) return rc;
+  if ((rc = launch_cast_strided(A.x, A.xsb, A.xst, C.B, C.T, C.d.I, ws + w.x_c, dt, st, C.dlen, C.P.reverse, C.vrow, C.vt0))) return rc;
   if ((rc = mask_x(C, st))) return rc;
   for (int l = 0; l < C.NL; ++l) {
     const LayerWs& L = w.layer[l];
@@ -1278,6 +1336,8 @@ static int prep_fast(Call& C, const FwdArgs& A) {
   // all layout preparation in one launch (prep_multi_kernel); a training plan with more than 6 layers has more jobs
   // than one launch holds (1 + 5 L): a full batch is launched and a new one started -- the jobs are independent
   PrepArgs pa{};
+  pa.vrow = C.vrow;
+  pa.vt0 = C.vt0;
   int prep_rc = CSN_OK;
   auto job = [&](int kind, const float* a_, const float* b_, void* dst, int64_t n0, int64_t n1, int64_t n2, int64_t s0,
                  int64_t s1, int64_t Hh, int pr, int pk, int64_t work) {
@@ -1880,6 +1940,13 @@ extern "C" int csn_lstm_forward(csnLstmPlan* Pp, const float* x, int64_t x_strid
   int dev = -1;
   CSN_HIP_CHECK(hipGetDevice(&dev));
   CSN_REQUIRE(dev == P.device, "csn_lstm_forward: plan was created on device %d, current device is %d", P.device, dev);
+  // input windows: every row's window lies inside the source (checked per call -- the lengths may be newer than the views)
+  for (int b = 0; b < d->B && !P.view_row.empty(); ++b) {
+    const int n = P.lengths.empty() ? d->T : P.lengths[b];
+    CSN_REQUIRE((int64_t)P.view_t0[b] + n <= P.view_src_T,
+                "csn_lstm_forward: the window of row %d, steps [%d, %d), ends past the source's %d steps", b,
+                (int)P.view_t0[b], (int)P.view_t0[b] + n, P.view_src_T);
+  }
   hipStream_t st = as_stream(stream);
   int rc;
   // (the status word is NOT cleared here: it stays raised from the first timed-out hand-off until
@@ -1887,6 +1954,7 @@ extern "C" int csn_lstm_forward(csnLstmPlan* Pp, const float* x, int64_t x_strid
   const int* dlen = nullptr;
   if ((rc = upload_lengths(Pp, st, &dlen))) return rc;
   Call C(P, workspace, st, dlen);
+  if ((rc = upload_views(Pp, st, &C.vrow, &C.vt0))) return rc;
   const FwdArgs A{x, x_stride_b, x_stride_t, w_ih, w_hh, b_ih, b_hh, h0, c0};
   const WsLayout& w = P.w;
   char* ws = C.ws;

@@ -148,12 +148,18 @@ struct PrepJob {
   int perm_r, perm_k;
   int64_t work;                      // work items (threads) of the job
   unsigned blk_begin, blk_count;     // filled by the launcher
-  const int* len;                    // x jobs with perm_r != 0 (reverse plans): [B] valid steps per row, null = n1 for all
+  const int* len;                    // x jobs of reverse plans (perm_r != 0) and of calls with input windows: [B] valid steps per row, null = n1 for all
 };
+// vrow / vt0: the input windows of the call (csn_lstm_plan_set_views), [B] device arrays or null; they belong to the x
+// jobs and sit here ONCE (a call has one x): a pointer pair per job would put the struct past the 4096 bytes a kernel's
+// by-value arguments may take
 struct PrepArgs {
   PrepJob job[kPrepMaxJobs];
   int njobs;
+  const int* vrow;
+  const int* vt0;
 };
+static_assert(sizeof(PrepArgs) <= 4096, "PrepArgs is passed by value: the kernel-argument segment holds 4096 bytes");
 int launch_prep_multi(PrepArgs& A, hipStream_t st);
 
 bool cell_blk_supported(int H, int dtype, const Options& opt);

@@ -226,20 +226,29 @@ __global__ void __launch_bounds__(256) prep_multi_kernel(PrepArgs A) {
       break;
     }
     case kPrepCastX: {                    // x[b][t][i] (strides s0, s1) -> time-major [T][B][I] bf16
+      // input windows (A.vrow != null): row b is source row vrow[b] from time vt0[b] on.  The load sits under t < n
+      // (n = len[b], or Tn): from n on a zero is stored and x is NOT read -- vt0[b] + t may lie past the source's end
       const int64_t Bn = J.n0, Tn = J.n1, I = J.n2;
+      const bool win = A.vrow != nullptr;
       bf16_t* dst = (bf16_t*)J.dst;
       if ((I & 7) == 0 && (J.s0 & 3) == 0 && (J.s1 & 3) == 0 && (reinterpret_cast<uintptr_t>(J.a) & 15) == 0) {
         for (int64_t c = gid; c < Bn * Tn * I / 8; c += stride) {     // 8 elements per thread and trip
           const int64_t i = c * 8, i2 = i % I, r = i / I, b = r % Bn;
-          int64_t t = r / Bn;
-          if (J.perm_r) {       // reverse plan: step t of row b is its n - 1 - t; from n on zeros, the padding is not read
-            t = (J.len != nullptr ? J.len[b] : Tn) - 1 - t;
-            if (t < 0) {
+          int64_t t = r / Bn, sb = b;
+          if (J.perm_r || win) {
+            // reverse plan: step t of row b is its n - 1 - t; from n on zeros, the padding is not read
+            const int64_t n = J.len != nullptr ? J.len[b] : Tn;
+            if (J.perm_r) t = n - 1 - t;
+            if (t < 0 || (win && t >= n)) {
               *reinterpret_cast<uint4*>(dst + i) = make_uint4(0u, 0u, 0u, 0u);
               continue;
             }
+            if (win) {
+              sb = A.vrow[b];
+              t += A.vt0[b];
+            }
           }
-          const float4* sp = reinterpret_cast<const float4*>(J.a + b * J.s0 + t * J.s1 + i2);
+          const float4* sp = reinterpret_cast<const float4*>(J.a + sb * J.s0 + t * J.s1 + i2);
           const float4 u = sp[0], v = sp[1];
           *reinterpret_cast<bf16x8*>(dst + i) = (bf16x8){(bf16_t)u.x, (bf16_t)u.y, (bf16_t)u.z, (bf16_t)u.w,
                                                          (bf16_t)v.x, (bf16_t)v.y, (bf16_t)v.z, (bf16_t)v.w};
@@ -248,6 +257,12 @@ __global__ void __launch_bounds__(256) prep_multi_kernel(PrepArgs A) {
         for (int64_t i = gid; i < Bn * Tn * I; i += stride) {
           const int64_t i2 = i % I, r = i / I, b = r % Bn;
           int64_t t = r / Bn;
+          if (win) {
+            const int64_t n = J.len != nullptr ? J.len[b] : Tn;
+            if (J.perm_r) t = n - 1 - t;
+            dst[i] = (bf16_t)(t >= 0 && t < n ? J.a[(int64_t)A.vrow[b] * J.s0 + (A.vt0[b] + t) * J.s1 + i2] : 0.f);
+            continue;
+          }
           if (J.perm_r) t = (J.len != nullptr ? J.len[b] : Tn) - 1 - t;
           dst[i] = (bf16_t)(t >= 0 ? J.a[b * J.s0 + t * J.s1 + i2] : 0.f);
         }
@@ -256,26 +271,32 @@ __global__ void __launch_bounds__(256) prep_multi_kernel(PrepArgs A) {
     }
     case kPrepBlockifyX: {                // x -> [T][Bpad * I] fragment-major bf16 slabs (rows >= B zero)
       const int64_t Bn = J.n0, Tn = J.n1, I = J.n2, Bpad = J.H, per_t = Bpad * I / 8, kblocks = I >> 5;
+      const bool win = A.vrow != nullptr;
       bf16_t* dst = (bf16_t*)J.dst;
       for (int64_t ci = gid; ci < per_t * Tn; ci += stride) {
         const int64_t c = ci % per_t, blk = c >> 6, lane = c & 63;
         const int64_t r = (blk / kblocks) * 16 + (lane & 15), k = (blk % kblocks) * 32 + 8 * (lane >> 4);
-        int64_t t = ci / per_t;
-        if (J.perm_r && r < Bn) {      // reverse plan, as in kPrepCastX
-          t = (J.len != nullptr ? J.len[r] : Tn) - 1 - t;
-          if (t < 0) {
+        int64_t t = ci / per_t, sr = r;
+        if ((J.perm_r || win) && r < Bn) {      // reverse plan / input windows, as in kPrepCastX: no read from n on
+          const int64_t n = J.len != nullptr ? J.len[r] : Tn;
+          if (J.perm_r) t = n - 1 - t;
+          if (t < 0 || (win && t >= n)) {
             *reinterpret_cast<uint4*>(dst + ci * 8) = make_uint4(0u, 0u, 0u, 0u);
             continue;
+          }
+          if (win) {
+            sr = A.vrow[r];
+            t += A.vt0[r];
           }
         }
         bf16x8 v;
         if (r < Bn && ((J.s0 | J.s1) & 3) == 0 && (reinterpret_cast<uintptr_t>(J.a) & 15) == 0) {
-          const float4* sp = reinterpret_cast<const float4*>(J.a + r * J.s0 + t * J.s1 + k);
+          const float4* sp = reinterpret_cast<const float4*>(J.a + sr * J.s0 + t * J.s1 + k);
           const float4 u = sp[0], w = sp[1];
           v = (bf16x8){(bf16_t)u.x, (bf16_t)u.y, (bf16_t)u.z, (bf16_t)u.w, (bf16_t)w.x, (bf16_t)w.y, (bf16_t)w.z, (bf16_t)w.w};
         } else {
 #pragma unroll
-          for (int e = 0; e < 8; ++e) v[e] = (bf16_t)(r < Bn ? J.a[r * J.s0 + t * J.s1 + k + e] : 0.f);
+          for (int e = 0; e < 8; ++e) v[e] = (bf16_t)(r < Bn ? J.a[sr * J.s0 + t * J.s1 + k + e] : 0.f);
         }
         *reinterpret_cast<bf16x8*>(dst + ci * 8) = v;
       }

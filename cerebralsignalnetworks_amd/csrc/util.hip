@@ -70,9 +70,13 @@ int launch_upcast(const void* src, int dtype, float* dst, int64_t n, hipStream_t
 
 // ---- strided cast: dst[(i1*n0 + i0)*n2 + i2] = src[i0*s0 + i1*s1 + i2] ----------------------
 // Used for x[b][t][i] (strides s0=b, s1=t) -> time-major [T][B][I] in the compute dtype.
+// Input windows (vrow / vt0 != NULL, csn_lstm_plan_set_views): row i0 is source row vrow[i0] from time vt0[i0] on, and the
+// load sits under i1 < n (n = len[i0], or n1 without lengths): from a row's length on a zero is stored and the source is
+// NOT read -- vt0 + i1 may lie past the end of the source there.
 template <typename T>
 __global__ void cast_strided_kernel(const float* __restrict__ src, int64_t s0, int64_t s1, int64_t n0, int64_t n1,
-                                    int64_t n2, T* __restrict__ dst, const int* __restrict__ len, int rev) {
+                                    int64_t n2, T* __restrict__ dst, const int* __restrict__ len, int rev,
+                                    const int* __restrict__ vrow, const int* __restrict__ vt0) {
   const int64_t total = n0 * n1 * n2;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
@@ -80,20 +84,27 @@ __global__ void cast_strided_kernel(const float* __restrict__ src, int64_t s0, i
     const int64_t r = i / n2;       // r = i1*n0 + i0
     const int64_t i0 = r % n0;
     int64_t i1 = r / n0;
+    if (vrow != nullptr) {
+      const int64_t n = len != nullptr ? len[i0] : n1;
+      if (rev) i1 = n - 1 - i1;
+      const bool in = i1 >= 0 && i1 < n;
+      dst[i] = from_f32<T>(in ? src[(int64_t)vrow[i0] * s0 + (vt0[i0] + i1) * s1 + i2] : 0.f);
+      continue;
+    }
     if (rev) i1 = (len != nullptr ? len[i0] : n1) - 1 - i1;      // a reverse plan's row, backwards from its own last step
     dst[i] = from_f32<T>(i1 >= 0 ? src[i0 * s0 + i1 * s1 + i2] : 0.f);
   }
 }
 
 int launch_cast_strided(const float* src, int64_t s0, int64_t s1, int64_t n0, int64_t n1, int64_t n2, void* dst,
-                        int dtype, hipStream_t st, const int* len, int rev) {
+                        int dtype, hipStream_t st, const int* len, int rev, const int* vrow, const int* vt0) {
   const int64_t total = n0 * n1 * n2;
   if (total <= 0) return CSN_OK;
   const unsigned grid = capped_grid(total, 256);
   if (dtype == CSN_BF16)
-    cast_strided_kernel<bf16_t><<<grid, 256, 0, st>>>(src, s0, s1, n0, n1, n2, (bf16_t*)dst, len, rev);
+    cast_strided_kernel<bf16_t><<<grid, 256, 0, st>>>(src, s0, s1, n0, n1, n2, (bf16_t*)dst, len, rev, vrow, vt0);
   else
-    cast_strided_kernel<float><<<grid, 256, 0, st>>>(src, s0, s1, n0, n1, n2, (float*)dst, len, rev);
+    cast_strided_kernel<float><<<grid, 256, 0, st>>>(src, s0, s1, n0, n1, n2, (float*)dst, len, rev, vrow, vt0);
   CSN_LAUNCH_CHECK();
   return CSN_OK;
 }

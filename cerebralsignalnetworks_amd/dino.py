@@ -85,6 +85,34 @@ class MultiCropWrapper(nn.Module):
             rows.append(out[0] if isinstance(out, tuple) else out)
         return self.head(torch.cat(rows))
 
+    def forward_views(self, eeg_btc, starts, lengths):
+        """All V views of the batch in ONE backbone pass over V * B rows, cut out of ``eeg_btc`` [B, T, C] in place by the
+        LSTM's input windows (no slice, no copy): ``starts`` / ``lengths`` as ``temporal_crops(as_views=True)`` gives
+        them.  -> [V, B, out], standing where ``torch.stack([self(v) for v in views])`` stands.  The head runs once on
+        all rows -- once per view chunk when it holds a BatchNorm1d in training mode, whose batch statistics are then
+        those of the per-view form."""
+        B = eeg_btc.shape[0]
+        rows, row_starts, row_lengths = view_rows(starts, lengths, B)
+        out = self.backbone(eeg_btc, views=(rows, row_starts), lengths=row_lengths)
+        feat = out[0] if isinstance(out, tuple) else out
+        if self.training and any(isinstance(m, nn.BatchNorm1d) for m in self.head.modules()):
+            z = torch.cat([self.head(chunk) for chunk in feat.split(B)])
+        else:
+            z = self.head(feat)
+        return z.reshape(len(lengths), B, -1)
+
+
+def view_rows(starts, lengths, B):
+    """View-major rows of a fused multi-view pass: row ``v * B + b`` is sample b of view v.  ``starts``: V ints (one start
+    per view) or [V][B] (one per view and sample); ``lengths``: V ints.  -> (src_row, t0, n), three lists of V * B ints."""
+    V = len(lengths)
+    starts = np.asarray(starts, dtype=np.int64)
+    if starts.shape not in ((V,), (V, B)):
+        raise ValueError(f"view starts of shape {starts.shape} for {V} views of a batch of {B}")
+    starts = np.broadcast_to(starts.reshape(V, -1), (V, B))
+    rows = [b for _ in range(V) for b in range(B)]
+    return rows, [int(t) for t in starts.reshape(-1)], [int(lengths[v]) for v in range(V) for _ in range(B)]
+
 
 class _DinoLossFn(torch.autograd.Function):
     """csn_dino_loss: the student gradient is computed in the forward, saved, and multiplied by the incoming scalar."""
@@ -160,12 +188,27 @@ class DINOLoss(nn.Module):
         self.center = self.center * self.center_momentum + batch_center * (1 - self.center_momentum)
 
 
-def temporal_crops(eeg_btc, n_global=2, n_local=4, global_len=300, local_len=200, rng=None):
+def temporal_crops(eeg_btc, n_global=2, n_local=4, global_len=300, local_len=200, rng=None, as_views=False,
+                   per_sample=False):
     """Multi-crop in time: per view one random start shared by the batch (drawn from [0, T)), moved left so the
-    window ends inside the segment."""
+    window ends inside the segment.  -> (global views, local views), slices of ``eeg_btc``.
+
+    ``as_views=True``: nothing is sliced -- -> (starts, lengths), V starts and V lengths (global views first) for
+    ``MultiCropWrapper.forward_views``.  ``rng`` is drawn from exactly as in the slicing form, call for call: a seed gives
+    the same crops in both.  ``per_sample=True`` (with as_views): one start per (view, sample), ``starts`` an int array
+    [V, B] -- the augmentation DINO describes, free with input windows; it draws B values per view."""
     rng = rng or np.random
     T = eeg_btc.size(1)
     lengths = [global_len] * n_global + [local_len] * n_local
+    if per_sample and not as_views:
+        raise ValueError("temporal_crops: per_sample=True needs as_views=True (a sliced view has one start)")
+    if as_views:
+        if per_sample:
+            B = eeg_btc.size(0)
+            starts = np.stack([np.minimum(np.asarray(rng.randint(0, T, size=B), dtype=np.int64), T - n) for n in lengths])
+        else:
+            starts = [min(int(rng.randint(0, T)), T - n) for n in lengths]
+        return starts, lengths
     views = []
     for length in lengths:
         start = min(int(rng.randint(0, T)), T - length)

@@ -166,8 +166,11 @@ class HipLSTM(nn.Module):
         self.direct_grads = False
         self.grad_ready_hook = None
 
-    def _checkout(self, B, T, device, training, dropout=False):
-        key = (B, T, str(device), bool(training), self.compute_dtype) + (("dropout plan",) if dropout else ())
+    def _checkout(self, B, T, device, training, dropout=False, state=None):
+        """state: None = the class's kind of plan; True = a CSN_LSTM_STATE plan (the views form of HipLSTM: lengths)."""
+        state = self._STATE_PLANS if state is None else bool(state)
+        key = ((B, T, str(device), bool(training), self.compute_dtype) + (("dropout plan",) if dropout else ()) +
+               (("state plan",) if state != self._STATE_PLANS else ()))
         pool = self._plans.setdefault(key, [])
         for plan in pool:
             if not plan.busy:
@@ -177,12 +180,25 @@ class HipLSTM(nn.Module):
             k, pl = idle.pop(0)
             self._plans[k].remove(pl)
         plan = cabi.LstmPlan(B, T, self.input_size, self.hidden_size, self.num_layers, self.compute_dtype, device,
-                             training=training, state=self._STATE_PLANS, dropout=dropout)
+                             training=training, state=state, dropout=dropout)
         pool.append(plan)
         return plan
 
     def all_plans(self):
         return [pl for lst in self._plans.values() for pl in lst]
+
+    def forward_views(self, x, views, lengths):
+        """Input windows: ``x`` is a SOURCE [S, Tsrc, I]; row b of the LSTM batch is ``x[rows[b], starts[b]:starts[b] +
+        lengths[b]]`` with ``views = (rows, starts)``, read in place (csn_lstm_plan_set_views: no slice, no copy, no read
+        past a window).  -> y_last [B', H], each row's top-layer output at its own last step: the bits of ``forward`` on
+        the gathered rows.  The batch is B' = len(rows) and the plan runs T' = max(lengths) steps, so all the multi-crop
+        views of a batch are ONE recurrence pass.  No gradient reaches x (``x.requires_grad`` raises)."""
+        _dropout_p(self)
+        rows, starts, lengths = _check_views("HipLSTM", x, views, lengths, self.input_size)
+        L = self.num_layers
+        params = [getattr(self, f"{n}_l{k}") for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh") for k in range(L)]
+        training = torch.is_grad_enabled() and any(p.requires_grad for p in params)
+        return _LstmViewsFunction.apply(x, self, training, (rows, starts), lengths, _draw_dropout(self), L, *params)
 
     def forward(self, x, want_all=False):
         _dropout_p(self)
@@ -196,6 +212,74 @@ class HipLSTM(nn.Module):
         return (y_all, y_last) if want_all else y_last
 
 
+def _check_views(name, x, views, lengths, input_size):
+    """The ``views`` / ``lengths`` arguments of the window forms -> (rows, starts, lengths), tuples of B' ints.  What the
+    library checks itself (rows and windows inside the source) is left to it."""
+    if isinstance(x, nn.utils.rnn.PackedSequence) or x.dim() != 3 or x.shape[2] != input_size:
+        raise ValueError(f"{name}: with views the input is the source tensor [S, Tsrc, {input_size}]")
+    if x.requires_grad:
+        raise ValueError(f"{name}: views on an input that requires grad (the gradient of shared source rows would need a "
+                         "scatter-add: not supported)")
+    if lengths is None:
+        raise ValueError(f"{name}: views need lengths (the steps of every row's window)")
+    if not x.is_cuda:
+        raise cabi.CsnError(f"{name} runs on the GPU only (no CPU fallback); move the module and input to cuda")
+    rows, starts = ([int(v) for v in (t.tolist() if isinstance(t, torch.Tensor) else t)] for t in views)
+    if len(rows) != len(starts) or not rows:
+        raise ValueError(f"{name}: views = (rows, starts) with {len(rows)} rows and {len(starts)} starts")
+    return tuple(rows), tuple(starts), _check_lengths(name, lengths, len(rows), x.shape[1])
+
+
+def _run_views(plan, x, views, lengths, call):
+    """call() between setting the windows and lengths of a pooled plan and clearing the windows again."""
+    plan.set_lengths(lengths)
+    plan.set_views(views[0], views[1], x.shape[0], x.shape[1])
+    try:
+        return call()
+    finally:
+        plan.set_views(None)
+
+
+class _LstmViewsFunction(torch.autograd.Function):
+    """HipLSTM.forward_views: (source x, params) -> y_last of the windowed rows, on a CSN_LSTM_STATE plan keyed by
+    (B', T' = max(lengths)).  x gets no gradient; the parameter gradients go where _LstmFunction's go."""
+
+    @staticmethod
+    def forward(ctx, x, owner, training, views, lengths, drop, L, *params):
+        w_ih, w_hh, b_ih, b_hh = params[0:L], params[L:2 * L], params[2 * L:3 * L], params[3 * L:4 * L]
+        plan = owner._checkout(len(lengths), max(1, max(lengths)), x.device, training, dropout=drop is not None, state=True)
+        _set_dropout(plan, drop)
+        ctx.drop, ctx.lengths = drop, lengths
+        y_last, _ = _run_views(plan, x, views, lengths, lambda: plan.forward(x, w_ih, w_hh, b_ih, b_hh))
+        ctx.lease, ctx.L, ctx.owner = _Lease(plan), L, owner
+        ctx.param_like = params
+        if not training:
+            ctx.lease.release()
+        return y_last
+
+    @staticmethod
+    def backward(ctx, dy_last):
+        L, plan = ctx.L, ctx.lease.plan
+        if plan is None:
+            raise RuntimeError("HipLSTM: second backward through one forward -- its workspace was handed back after the "
+                               "first (retain_graph / double backward are not supported)")
+        owner = ctx.owner
+        direct, accumulate = _direct_grads(owner, ctx.param_like)
+        if direct:
+            grads = [[p.grad for p in ctx.param_like[g * L:(g + 1) * L]] for g in range(4)]
+        else:
+            grads = [[torch.empty_like(p) for p in ctx.param_like[g * L:(g + 1) * L]] for g in range(4)]
+        plan.set_grad_callback(owner.grad_ready_hook if direct else None)
+        plan.set_grad_mode(accumulate)
+        plan.set_lengths(ctx.lengths)       # the backward runs with the lengths of its forward; it reads no x, so no views
+        _set_dropout(plan, ctx.drop)
+        plan.backward(dy_last, None, grads)
+        ctx.lease.release()
+        if direct:
+            return (None, None, None, None, None, None, None, *([None] * (4 * L)))
+        return (None, None, None, None, None, None, None, *[g for group in grads for g in group])
+
+
 class _LstmStateFunction(torch.autograd.Function):
     """Stacked LSTM with an initial state in and the final state out: (x, h0, c0, params) -> (y_all, h_n, c_n).
     The gradients go to temporaries, or with ``direct_grads = "accumulate"`` are added straight to the parameters' .grad
@@ -203,13 +287,19 @@ class _LstmStateFunction(torch.autograd.Function):
     chunks of one recording are chained through their state)."""
 
     @staticmethod
-    def forward(ctx, x, h0, c0, owner, training, lengths, drop, L, *params):
+    def forward(ctx, x, h0, c0, owner, training, lengths, views, drop, L, *params):
         w_ih, w_hh, b_ih, b_hh = params[0:L], params[L:2 * L], params[2 * L:3 * L], params[3 * L:4 * L]
-        plan = owner._checkout(x.shape[0], x.shape[1], x.device, training, dropout=drop is not None)
-        plan.set_lengths(lengths)           # on every forward: plans are shared between calls (None = every row is T)
-        _set_dropout(plan, drop)
+        run = lambda: plan.forward(x, w_ih, w_hh, b_ih, b_hh, want_all=True, h0=h0, c0=c0, want_state=True)
+        if views is not None:               # input windows: x is the source, the batch is (len(rows), max(lengths))
+            plan = owner._checkout(len(lengths), max(1, max(lengths)), x.device, training, dropout=drop is not None)
+            _set_dropout(plan, drop)
+            _, y_all, h_n, c_n = _run_views(plan, x, views, lengths, run)
+        else:
+            plan = owner._checkout(x.shape[0], x.shape[1], x.device, training, dropout=drop is not None)
+            plan.set_lengths(lengths)       # on every forward: plans are shared between calls (None = every row is T)
+            _set_dropout(plan, drop)
+            _, y_all, h_n, c_n = run()
         ctx.drop = drop
-        _, y_all, h_n, c_n = plan.forward(x, w_ih, w_hh, b_ih, b_hh, want_all=True, h0=h0, c0=c0, want_state=True)
         ctx.lease, ctx.L, ctx.owner = _Lease(plan), L, owner
         ctx.lengths = lengths               # kept with the node: the backward runs with the lengths of its forward
         ctx.need = (x.requires_grad, h0 is not None and h0.requires_grad, c0 is not None and c0.requires_grad)
@@ -244,9 +334,9 @@ class _LstmStateFunction(torch.autograd.Function):
         plan.backward(None, dy_all, grads, dx=dx, dh_n=dh_n, dc_n=dc_n, dh0=dh0, dc0=dc0)
         ctx.lease.release()
         if direct:
-            return (dx, dh0, dc0, None, None, None, None, None, *([None] * (4 * L)))
+            return (dx, dh0, dc0, None, None, None, None, None, None, *([None] * (4 * L)))
         flat = [g for group in grads for g in group]
-        return (dx, dh0, dc0, None, None, None, None, None, *flat)
+        return (dx, dh0, dc0, None, None, None, None, None, None, *flat)
 
 
 def _forward_packed(module, name, x, hx, lengths):
@@ -319,7 +409,14 @@ class LSTM(HipLSTM):
         super().__init__(input_size, hidden_size, num_layers, compute_dtype=compute_dtype)
         self.bias, self.batch_first, self.dropout, self.bidirectional, self.proj_size = True, True, 0.0, False, 0
 
-    def forward(self, x, hx=None, lengths=None):
+    def forward(self, x, hx=None, lengths=None, views=None):
+        """``views = (rows, starts)``, each B' ints, with ``lengths`` (B' ints, required): x is a SOURCE [S, Tsrc, I] and
+        row b of the LSTM batch is ``x[rows[b], starts[b]:starts[b] + lengths[b]]``, read in place.  The batch is then
+        B' = len(rows), T' = max(lengths): output [B', T', H], hx and (h_n, c_n) [L, B', H], all with the bits of the call
+        on the gathered rows.  No gradient reaches x through views (``x.requires_grad`` raises ValueError)."""
+        if views is not None:
+            rows, starts, lengths = _check_views("LSTM", x, views, lengths, self.input_size)
+            views = (rows, starts)
         if isinstance(x, nn.utils.rnn.PackedSequence):
             return _forward_packed(self, "LSTM", x, hx, lengths)
         if x.dim() != 3:
@@ -327,21 +424,23 @@ class LSTM(HipLSTM):
                              f"{list(x.shape)} (unbatched input is not supported)")
         if x.shape[2] != self.input_size:
             raise ValueError(f"LSTM: input has {x.shape[2]} features, expected {self.input_size}")
-        B, L, H = x.shape[0], self.num_layers, self.hidden_size
+        B, L, H = (x.shape[0] if views is None else len(views[0])), self.num_layers, self.hidden_size
         h0 = c0 = None
         if hx is not None:
             h0, c0 = hx
             for name, t in (("h0", h0), ("c0", c0)):
                 if tuple(t.shape) != (L, B, H):
                     raise ValueError(f"LSTM: {name} must be [num_layers, B, hidden_size] = {[L, B, H]}, got {list(t.shape)}")
-        lengths = _check_lengths("LSTM", lengths, B, x.shape[1])
+        if views is None:
+            lengths = _check_lengths("LSTM", lengths, B, x.shape[1])
         _dropout_p(self)
         if not x.is_cuda:
             raise cabi.CsnError("LSTM runs on the GPU only (no CPU fallback); move the module and input to cuda")
         params = [getattr(self, f"{n}_l{k}") for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh") for k in range(L)]
         training = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params) or
                                                 any(t is not None and t.requires_grad for t in (h0, c0)))
-        y_all, h_n, c_n = _LstmStateFunction.apply(x, h0, c0, self, training, lengths, _draw_dropout(self), L, *params)
+        y_all, h_n, c_n = _LstmStateFunction.apply(x, h0, c0, self, training, lengths, views, _draw_dropout(self), L,
+                                                   *params)
         return y_all, (h_n, c_n)
 
 
@@ -515,10 +614,18 @@ class Model(nn.Module):
         if include_top:
             self.class_pred = nn.Linear(output_size, n_classes)
 
-    def forward(self, x):
+    def forward(self, x, views=None, lengths=None):
+        """``views = (rows, starts)`` with ``lengths``: x is a source [S, Tsrc, C] and the result has one row per window
+        (HipLSTM.forward_views) -- feature rows [B', output_size], and the class logits with include_top."""
+        if views is not None and self.bidirectional:
+            raise ValueError("Model: views are not supported with bidirectional=True")
+        if views is None and lengths is not None:
+            raise ValueError("Model: lengths are taken with views only")
         if self.bidirectional:
             _, (h_n, _) = self.lstm(x)
             last = torch.cat((h_n[-2], h_n[-1]), dim=1)    # [B, 2H]
+        elif views is not None:
+            last = self.lstm.forward_views(x, views, lengths)      # [B', H] = top layer at each window's last step
         else:
             last = self.lstm(x)                # [B, H] = top layer at the last timestep
         feat = self.fc(last)

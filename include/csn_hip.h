@@ -68,6 +68,8 @@ typedef void* csnStream_t;
  *                          with lengths (a copy of 4 * B bytes; they reuse its pinned staging array) -- hence until `stream`
  *                          has reached that copy; the first such call allocates the staging and device arrays.
  *                          csn_lstm_plan_set_lengths itself only stores the lengths on the host.
+ *   csn_lstm_forward ON A PLAN WITH INPUT WINDOWS waits in the same way for the windows upload (8 * B bytes) of the
+ *                          plan's previous forward with windows; csn_lstm_plan_set_views only stores them on the host.
  *   csn_lstm_plan_destroy  frees the plan's streams and events (and, after lengths, device memory, which waits for the
  *                          device): call it when the plan's work has completed.
  * Not blocking, but host work beyond the launches: csn_lstm_plan_create computes the workspace layout and reads the
@@ -86,7 +88,7 @@ enum csnStatus {
 enum csnDtype { CSN_F32 = 0, CSN_BF16 = 1 };
 
 /* ABI version of this header; bumped on any signature change.  A symbol added beside the existing ones
- * (csn_lstm_plan_set_grad_mode, csn_lstm_plan_set_lengths, csn_lstm_plan_set_io, csn_lstm_plan_half_tile_launches, the
+ * (csn_lstm_plan_set_grad_mode, csn_lstm_plan_set_lengths, csn_lstm_plan_set_views, csn_lstm_plan_set_io, csn_lstm_plan_half_tile_launches, the
  * csn_flat_* family, csn_adam_step, csn_lars_step, csn_eeg_bandpass_stream and its _path, csn_distill_loss,
  * csn_dino_loss) breaks no caller and does not bump it; neither does a new bit of csn_lstm_plan_create's `training` word. */
 #define CSN_ABI_VERSION 6
@@ -321,6 +323,27 @@ int csn_lstm_plan_set_grad_mode(csnLstmPlan* plan, int mode);
  * ordered on one stream, or by the caller.
  * Null plan, a plan without CSN_LSTM_STATE, an entry outside [0, T]: CSN_ERR_INVALID_ARGUMENT (the setting is kept). */
 int csn_lstm_plan_set_lengths(csnLstmPlan* plan, const int32_t* lengths);
+
+/* Input windows: every row of the LSTM batch names the row of a SOURCE tensor it is cut from and the source step it
+ * starts at.  `src_row` and `t0` are HOST arrays of B entries; the `x` of csn_lstm_forward is then
+ * the source, [src_rows, src_T, I] under the call's own x_stride_b / x_stride_t.  With n = lengths[b] (T on a plan
+ * without lengths), step t < n of row b reads  x[src_row[b] * x_stride_b + (t0[b] + t) * x_stride_t + i];  on a
+ * CSN_LSTM_REVERSE plan recurrence step s reads time t0[b] + n - 1 - s.  Many rows may share a source row: all the
+ * multi-crop views of a batch run as ONE call on the uncopied batch.
+ * src_row = t0 = NULL: windows off (the default; such a plan enqueues the launches and writes the bits it did before
+ * this symbol existed).  Host only and sticky until set again, like the lengths; every forward uploads the arrays in
+ * stream order into device arrays the plan owns (the backward reads no x and uploads nothing).
+ * IDENTITY.  A call with windows has, bit for bit, every output and every gradient of the same plan called with the same
+ * lengths on the dense input  xm[b, t] = x[src_row[b], t0[b] + t]  for t < n, anything at all (NaN) for t >= n.  Only the
+ * layout pass in front of the recurrence differs; dx stays the dense [B, T, I] gradient of the gathered rows.
+ * NO READ PAST A WINDOW.  Nothing at t >= n is loaded (t0[b] + t may lie past the end of the source there): the layout
+ * kernels store a zero instead.
+ * Every plan, every path, training and inference; the lengths still need a CSN_LSTM_STATE plan.
+ * Null plan, exactly one array NULL, src_row[b] outside [0, src_rows), t0[b] < 0, src_rows < 1 or src_T < 1:
+ * CSN_ERR_INVALID_ARGUMENT (the setting is kept).  csn_lstm_forward returns CSN_ERR_INVALID_ARGUMENT, before it
+ * enqueues anything, when t0[b] + n > src_T for some row (the lengths may be newer than the views). */
+int csn_lstm_plan_set_views(csnLstmPlan* plan, const int32_t* src_row, const int32_t* t0, int32_t src_rows,
+                            int32_t src_T);
 
 /* Where the plan's later calls find y_all and dy_all, and how they store dx; host only, sticky until set again like the
  * gradient mode, and a call uses the setting it finds when it is CALLED.
