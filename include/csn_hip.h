@@ -50,8 +50,14 @@ typedef void* csnStream_t;
  *                      initial state and the input from the workspace, so an optimiser step enqueued on `stream` right
  *                      behind the forward may already rewrite the parameters the matching backward is still to use.
  *   csn_lstm_backward  reads from caller memory only its own arguments dy_last, dy_all, dh_n, dc_n (and, accumulating,
- *                      the previous dw / db); all four may be overwritten behind it.  dw, db, dx, dh0, dc0 are complete
+ *                      the previous dw / db; under dx_add of csn_lstm_plan_set_io the previous dx, which is then an input
+ *                      as well as an output: what it holds must be there in stream order in front of the call); all four
+ *                      may be overwritten behind it.  dw, db, dx, dh0, dc0 are complete
  *                      in stream order behind it (the gradient-ready callback marks an earlier point per layer).
+ *   A pitched y_all / dy_all (csn_lstm_plan_set_io) follows the same rule as the dense one: the forward writes, and the
+ *                      backward reads, only the H elements of every (b, t) row of the half it was given, in stream order;
+ *                      the rest of the wider buffer is neither read nor written and belongs to the caller (or to the
+ *                      other direction's plan) throughout, and the whole buffer may be overwritten behind the backward.
  *   The workspace belongs to the plan's calls from a forward to its backward; the lengths are host memory (above).
  *
  * ANOTHER STREAM.  A plan (and its workspace) may be called on another stream than its previous call used, provided the

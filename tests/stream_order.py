@@ -21,7 +21,11 @@ _Lstm.backward's "overwrite_tail" mode exists because the closing join of the pe
 only seen by a reader directly behind the call's last launch.)
 
 CASE_TABLE names every entry point of include/csn_hip.h that takes a csnStream_t (tests/test_stream_order_cpu.py holds
-the two against each other) with its stream-order cases: single calls here, or the tests that run it through a plan."""
+the two against each other) with its stream-order cases: single calls here, or the tests that run it through a plan.
+PLAN_SETTERS does the same for the csn_lstm_plan_set_* functions, which take no stream themselves: what they set --
+gradient mode and callback, lengths, input windows, the y_all / dy_all pitch and the adding dx, dropout -- adds launches,
+copies and host staging to the forward and backward that follow, and the table names the tests that run those in stream
+order (FEATURE_SETS and the draws below them are their host side)."""
 import math
 import time
 
@@ -513,7 +517,99 @@ def _l2_topk_tiled(splits):
 
 BF16, F32 = torch.bfloat16, torch.float32
 _LSTM_TESTS = ("test_lstm_forward_with_late_inputs", "test_lstm_backward_with_late_inputs", "test_lstm_two_steps_back_to_back",
-               "test_lstm_lengths_with_late_inputs")
+               "test_lstm_lengths_with_late_inputs", "test_lstm_feature_forward_with_late_inputs",
+               "test_lstm_feature_backward_with_late_inputs", "test_lstm_settings_change_between_unsynchronised_calls",
+               "test_bilstm_module_on_a_side_stream_with_late_inputs", "test_lstm_grad_ready_callback_marks_complete_gradients")
+_LSTM_FORWARD_TESTS = tuple(t for t in _LSTM_TESTS if t != "test_lstm_grad_ready_callback_marks_complete_gradients")
+
+# every csn_lstm_plan_set_* function of include/csn_hip.h (host only: none takes a stream; what it sets is read by the
+# following csn_lstm_forward / csn_lstm_backward) -> the tests of tests/test_gpu_stream_order.py that run a call under that
+# setting in stream order (tests/test_stream_order_cpu.py holds this table against the header too)
+PLAN_SETTERS = {
+    "csn_lstm_plan_set_grad_callback": ("test_lstm_grad_ready_callback_marks_complete_gradients",),
+    "csn_lstm_plan_set_grad_mode": ("test_lstm_backward_with_late_inputs", "test_lstm_lengths_with_late_inputs",
+                                    "test_lstm_feature_backward_with_late_inputs",
+                                    "test_lstm_grad_ready_callback_marks_complete_gradients"),
+    "csn_lstm_plan_set_lengths": ("test_lstm_lengths_with_late_inputs", "test_lstm_feature_forward_with_late_inputs",
+                                  "test_lstm_feature_backward_with_late_inputs",
+                                  "test_lstm_settings_change_between_unsynchronised_calls",
+                                  "test_bilstm_module_on_a_side_stream_with_late_inputs"),
+    "csn_lstm_plan_set_views": ("test_lstm_feature_forward_with_late_inputs", "test_lstm_feature_backward_with_late_inputs",
+                                "test_lstm_settings_change_between_unsynchronised_calls"),
+    "csn_lstm_plan_set_io": ("test_lstm_feature_forward_with_late_inputs", "test_lstm_feature_backward_with_late_inputs",
+                             "test_bilstm_module_on_a_side_stream_with_late_inputs"),
+    "csn_lstm_plan_set_dropout": ("test_lstm_feature_forward_with_late_inputs", "test_lstm_feature_backward_with_late_inputs",
+                                  "test_lstm_settings_change_between_unsynchronised_calls"),
+}
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# LSTM plans with features: the host-side draws (no GPU needed: tests/test_stream_order_cpu.py checks them)
+# ---------------------------------------------------------------------------------------------------------------------------
+# feature set -> what the plan carries.  "lengths" only ever on a CSN_LSTM_STATE plan (the stateless path 4 case runs
+# its windows over T steps)
+FEATURE_SETS = {"dropout": ("dropout",), "reverse_io": ("reverse_io",), "windows": ("windows", "lengths"),
+                "all": ("dropout", "reverse_io", "windows", "lengths")}
+# name -> ((B, T, I, H, L), CSN_LSTM_STATE plan?) of the cases the feature tests run (tests/test_gpu_stream_order.py holds
+# each against the case of that name)
+FEATURE_CASES = {
+    "v1_h96": ((8, 40, 24, 96, 2), True),
+    "p1_l5": ((8, 30, 16, 128, 5), True),
+    "p2_nopersist_bwd": ((64, 40, 128, 768, 2), True),
+    "ks_fused_h768_t32": ((256, 32, 128, 768, 2), True),
+    "f32_h128": ((70, 37, 24, 128, 2), True),
+    "ns_fused_h1024_t33": ((65, 33, 128, 1024, 2), True),
+    "streams_b320_h256": ((320, 40, 32, 256, 2), True),
+    "p4_f32_h128": ((70, 37, 24, 128, 2), False),
+}
+DROPOUT = (0.5, 1234, 1)            # (p, seed, subsequence) of every feature plan with dropout
+SETTINGS_CASES = ("v1_h96", "ks_fused_h768_t32", "f32_h128")
+
+
+def two_mixed_lengths(B, T):
+    """The "two_mixed" pattern of tests/test_gpu_lstm_views.py: the first third of the rows T, the rest 2T/3."""
+    return [T if b < max(1, B // 3) else (2 * T) // 3 for b in range(B)]
+
+
+def random_windows(B, Tsrc, lengths, seed=0):
+    """-> (S, src_row[B], t0[B]): the draw of tests/test_gpu_lstm_views.py::_windows("random", ...)."""
+    rng = np.random.default_rng(500 + seed)
+    S = max(1, B // 3)
+    rows = rng.integers(0, S, B).tolist()
+    return S, rows, rng.integers(0, Tsrc - np.asarray(lengths) + 1).tolist()
+
+
+def feature_settings(name, feature_set):
+    """The sticky host settings of the plan of (name, feature set): dict(dropout = (p, seed, subsequence) or None,
+    reverse_io, lengths = [B] or None, views = (rows, starts, S, Tsrc) or None)."""
+    (B, T, I, H, L), state = FEATURE_CASES[name]
+    f = FEATURE_SETS[feature_set]
+    out = {"dropout": DROPOUT if "dropout" in f else None, "reverse_io": "reverse_io" in f, "lengths": None, "views": None}
+    if "lengths" in f and state:
+        out["lengths"] = two_mixed_lengths(B, T)
+    if "windows" in f:
+        Tsrc = T + 7
+        S, rows, starts = random_windows(B, Tsrc, out["lengths"] or [T] * B)
+        out["views"] = (rows, starts, S, Tsrc)
+    return out
+
+
+def settings_a_and_b(name):
+    """The two settings of test_lstm_settings_change_between_unsynchronised_calls: lengths, windows (rows, starts, S,
+    Tsrc) and dropout triple.  B's differ from A's in every row -- length, source row and start --, in seed, subsequence
+    and p, and in Tsrc."""
+    (B, T, I, H, L), _ = FEATURE_CASES[name]
+    a = {"lengths": two_mixed_lengths(B, T), "dropout": DROPOUT}
+    S, rows, starts = random_windows(B, T + 7, a["lengths"])
+    a["views"] = (rows, starts, S, T + 7)
+    assert S >= 2
+    rng = np.random.default_rng(77)
+    lb = [int(v) if int(v) != n else (int(v) + 1) % (T + 1) for v, n in zip(rng.integers(0, T + 1, B), a["lengths"])]
+    Tsrc = T + 11
+    sb = [int(v) if int(v) != t else (t + 1 if t + 1 + n <= Tsrc else t - 1)
+          for v, t, n in zip(rng.integers(0, Tsrc - np.asarray(lb) + 1), starts, lb)]
+    b = {"lengths": lb, "dropout": (0.25, 99, 3), "views": ([(r + 1) % S for r in rows], sb, S, Tsrc)}
+    return a, b
 
 # every extern "C" function of include/csn_hip.h with a csnStream_t parameter
 CASE_TABLE = {
@@ -523,8 +619,8 @@ CASE_TABLE = {
     "csn_eeg_bandpass_stream": [Stateless("csn_eeg_bandpass_stream", "rows", _bandpass_stream((3, 5, 37), 3, scan=False)),
                                 Stateless("csn_eeg_bandpass_stream", "scan", _bandpass_stream((2, 8, 64), 3, scan=True))],
     "csn_lstm_workspace_init": InTest("test_workspace_init_and_status_word_in_stream_order"),
-    "csn_lstm_forward": InTest(*_LSTM_TESTS),
-    "csn_lstm_backward": InTest(*_LSTM_TESTS[1:]),
+    "csn_lstm_forward": InTest(*_LSTM_FORWARD_TESTS),
+    "csn_lstm_backward": InTest(*(t for t in _LSTM_TESTS if "_forward_with_late_inputs" not in t)),
     "csn_lstm_status_clear": InTest("test_workspace_init_and_status_word_in_stream_order"),
     "csn_lstm_status_raise": InTest("test_workspace_init_and_status_word_in_stream_order"),
     # the five routes of gemm_nt() in csrc/gemm.hip in the order it tries them (the wide one in both tile widths: 16 x 16

@@ -7,21 +7,33 @@ import pytest
 import torch
 
 import stream_order as so
+import channel_discovery_stream_cases  # noqa: F401  (these two join the stream-order case table on import: without them
+import distill_loss_stream_cases  # noqa: F401   this module, run on its own, misses their entry points in the table)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _entry_points_with_a_stream(header_text):
-    """Names of the functions include/csn_hip.h declares with a csnStream_t parameter."""
+def _declarations(header_text):
+    """(name, parameter text) of every csn_* function include/csn_hip.h declares."""
     text = re.sub(r"/\*.*?\*/", " ", header_text, flags=re.S)
     text = re.sub(r"//[^\n]*", " ", text)
     text = re.sub(r"^\s*#[^\n]*", " ", text, flags=re.M)
-    names = []
+    found = []
     for decl in text.split(";"):
         m = re.search(r"\b(csn_\w+)\s*\(([^()]*)\)\s*$", decl, flags=re.S)
-        if m and re.search(r"\bcsnStream_t\b", m.group(2)):
-            names.append(m.group(1))
-    return names
+        if m:
+            found.append((m.group(1), m.group(2)))
+    return found
+
+
+def _entry_points_with_a_stream(header_text):
+    """Names of the functions include/csn_hip.h declares with a csnStream_t parameter."""
+    return [name for name, params in _declarations(header_text) if re.search(r"\bcsnStream_t\b", params)]
+
+
+def _plan_setters(header_text):
+    """Names of the csn_lstm_plan_set_* functions include/csn_hip.h declares."""
+    return [name for name, _ in _declarations(header_text) if name.startswith("csn_lstm_plan_set_")]
 
 
 def _header():
@@ -39,6 +51,9 @@ def test_parser_finds_declarations_and_only_those():
     typedef void (*csnFn)(void* user, int layer);
     int csn_d(csnFn fn, void* user);"""
     assert _entry_points_with_a_stream(text) == ["csn_a", "csn_b"]
+    assert [n for n, _ in _declarations(text)] == ["csn_a", "csn_a_scratch_bytes", "csn_b", "csn_d"]
+    assert _plan_setters("int csn_lstm_plan_set_x(csnLstmPlan* plan, csnFn fn, void* user); /* csn_lstm_plan_set_y(int a); */\n"
+                         "int csn_lstm_plan_path(const csnLstmPlan* plan);") == ["csn_lstm_plan_set_x"]
 
 
 def test_case_table_names_exactly_the_entry_points_that_take_a_stream():
@@ -59,8 +74,7 @@ def test_a_removed_table_entry_is_noticed(monkeypatch):
 
 
 def test_every_table_entry_is_a_case_or_a_reason():
-    with open(os.path.join(ROOT, "tests", "test_gpu_stream_order.py")) as f:
-        gpu_tests = set(re.findall(r"^def (test_\w+)\(", f.read(), flags=re.M))
+    gpu_tests = _gpu_tests()
     for name, entry in so.CASE_TABLE.items():
         if isinstance(entry, so.InTest):
             assert entry.tests and set(entry.tests) <= gpu_tests, (name, entry.tests)
@@ -69,6 +83,85 @@ def test_every_table_entry_is_a_case_or_a_reason():
     ids = [c.id for c in so.STATELESS_CASES]
     assert len(ids) == len(set(ids))
     assert "test_stateless_entry_point_with_late_inputs" in gpu_tests
+
+
+def _gpu_tests():
+    with open(os.path.join(ROOT, "tests", "test_gpu_stream_order.py")) as f:
+        return set(re.findall(r"^def (test_\w+)\(", f.read(), flags=re.M))
+
+
+def test_plan_setters_table_names_exactly_the_setters_of_the_header():
+    declared = _plan_setters(_header())
+    assert len(declared) == len(set(declared)) and len(declared) >= 6, declared
+    missing = sorted(set(declared) - set(so.PLAN_SETTERS))
+    stale = sorted(set(so.PLAN_SETTERS) - set(declared))
+    assert not missing, f"csn_lstm_plan_set_* functions with no stream-order test: {missing}"
+    assert not stale, f"PLAN_SETTERS names functions the header does not declare: {stale}"
+    gpu_tests = _gpu_tests()
+    for name, tests in so.PLAN_SETTERS.items():
+        assert tests and set(tests) <= gpu_tests, (name, sorted(set(tests) - gpu_tests))
+        # a setter only matters through the calls that follow it: its tests are tests of the forward or the backward
+        assert set(tests) <= set(so.CASE_TABLE["csn_lstm_forward"].tests) | set(so.CASE_TABLE["csn_lstm_backward"].tests), name
+
+
+def test_a_removed_setter_or_a_test_that_does_not_exist_is_noticed(monkeypatch):
+    full = dict(so.PLAN_SETTERS)
+    table = dict(full)
+    del table["csn_lstm_plan_set_views"]
+    monkeypatch.setattr(so, "PLAN_SETTERS", table)
+    with pytest.raises(AssertionError, match="csn_lstm_plan_set_views"):
+        test_plan_setters_table_names_exactly_the_setters_of_the_header()
+    table = dict(full, csn_lstm_plan_set_io=("test_that_was_renamed",))
+    monkeypatch.setattr(so, "PLAN_SETTERS", table)
+    with pytest.raises(AssertionError, match="test_that_was_renamed"):
+        test_plan_setters_table_names_exactly_the_setters_of_the_header()
+    monkeypatch.setattr(so, "PLAN_SETTERS", dict(full, csn_lstm_plan_set_nothing=("test_lstm_forward_with_late_inputs",)))
+    with pytest.raises(AssertionError, match="csn_lstm_plan_set_nothing"):
+        test_plan_setters_table_names_exactly_the_setters_of_the_header()
+
+
+def _check_settings(shape, state, f, S_Tsrc=None):
+    B, T, I, H, L = shape
+    n = f["lengths"]
+    if n is not None:
+        assert state and len(n) == B and all(0 <= v <= T for v in n)
+    if f["dropout"] is not None:
+        assert L >= 2 and 0.0 < f["dropout"][0] < 1.0          # with one layer there is no interface to drop
+    if f["views"] is not None:
+        rows, starts, S, Tsrc = f["views"]
+        assert S == max(1, B // 3) and len(rows) == len(starts) == B
+        assert all(0 <= r < S for r in rows)
+        assert all(t0 >= 0 and t0 + k <= Tsrc for t0, k in zip(starts, n or [T] * B))
+
+
+def test_feature_settings_are_legal_for_every_case_and_feature_set():
+    for name, (shape, state) in so.FEATURE_CASES.items():
+        B, T, I, H, L = shape
+        assert L >= 2 and H % 4 == 0                            # (the [B,T,2H] halves start on 16 bytes)
+        for fs, parts in so.FEATURE_SETS.items():
+            f = so.feature_settings(name, fs)
+            _check_settings(shape, state, f)
+            assert (f["dropout"] is not None) == ("dropout" in parts) and f["reverse_io"] == ("reverse_io" in parts)
+            assert (f["views"] is not None) == ("windows" in parts) and (f["lengths"] is not None) == ("lengths" in parts and state)
+            if f["views"] is not None:
+                assert f["views"][3] == T + 7
+            if f["lengths"] is not None:                        # two_mixed: some rows T (the plan's own T is reached), the rest shorter
+                assert max(f["lengths"]) == T and 0 < min(f["lengths"]) < T
+    assert so.two_mixed_lengths(8, 40) == [40, 40] + [26] * 6
+    assert so.feature_settings("v1_h96", "all") == so.feature_settings("v1_h96", "all")          # fixed seeds
+
+
+def test_settings_a_and_b_differ_in_every_row():
+    for name in so.SETTINGS_CASES:
+        shape, state = so.FEATURE_CASES[name]
+        a, b = so.settings_a_and_b(name)
+        for f in (a, b):
+            _check_settings(shape, state, {**f, "reverse_io": False})
+        assert all(x != y for x, y in zip(a["lengths"], b["lengths"]))
+        (ra, ta, Sa, Tsa), (rb, tb, Sb, Tsb) = a["views"], b["views"]
+        assert all(x != y for x, y in zip(ra, rb)) and all(x != y for x, y in zip(ta, tb))
+        assert Sa == Sb and Tsa != Tsb
+        assert all(x != y for x, y in zip(a["dropout"], b["dropout"]))
 
 
 def test_late_holds_poison_until_the_copy():
