@@ -286,6 +286,21 @@ def gemm_nt(a, bt, bias=None, out_dtype=torch.float32, out=None, accumulate=Fals
     return c
 
 
+def gemm_nt_w4_offsets_fit(M, N, K):
+    """True where csn_gemm_nt's four-wave 256 x 192 kernel can address A[M, K] and Bt[N, K] with its 32-bit offsets (host
+    only).  Bound on use, not in SIGNATURES: an older library given through CSN_LIB_PATH for an A/B run still loads."""
+    fn = load().csn_gemm_nt_w4_offsets_fit
+    fn.restype, fn.argtypes = _c_int, [_c_i64, _c_i64, _c_i64]
+    return bool(fn(M, N, K))
+
+
+def gemm_nt_w4_lds_bytes():
+    """Dynamic LDS bytes of a launch of the four-wave 256 x 192 kernel (host only; bound on use as above)."""
+    fn = load().csn_gemm_nt_w4_lds_bytes
+    fn.restype, fn.argtypes = _c_int, []
+    return int(fn())
+
+
 def gemm_tn(a_km, b_kn):
     _need_cuda(a_km, b_kn)
     a, b = a_km.contiguous(), b_kn.contiguous()

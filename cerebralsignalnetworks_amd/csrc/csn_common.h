@@ -48,7 +48,7 @@ int fail(int status, const char* fmt, ...);
 // library keeps no mutable global state, so plans on different streams / threads / devices never share any.
 struct Options {
   bool cell_v1, no_persist, no_persist_bwd, persist_streams, no_xcd_local, no_rotate, no_fuse_x, no_beside,
-      no_side_stream, fwd_ksplit, fwd_nsplit, fwd_flags, bwd_flags, dpoll_no_hint, fwd_hint, gemm_no_dma, gemm_no_256, gemm_generic, tn_no_tr, tn_no_stagger, filter_v1, tags_no_rearm, gemm_no_192, no_half_tiles;
+      no_side_stream, fwd_ksplit, fwd_nsplit, fwd_flags, bwd_flags, dpoll_no_hint, fwd_hint, gemm_no_dma, gemm_no_256, gemm_generic, tn_no_tr, tn_no_stagger, filter_v1, tags_no_rearm, gemm_no_192, no_half_tiles, nt_no_w4;
   int chunk;       // timesteps per weight-stationary launch
   int tn_stages;   // LDS-DMA ring depth of the 256 x 256 weight-gradient kernel
 };
@@ -79,6 +79,7 @@ static inline Options options_from_env() {
   o.gemm_no_dma = on("CSN_GEMM_NO_DMA");
   o.gemm_no_256 = on("CSN_GEMM_NO_256");
   o.gemm_no_192 = on("CSN_GEMM_NO_192");
+  o.nt_no_w4 = on("CSN_NT_NO_W4");
   o.gemm_generic = on("CSN_GEMM_GENERIC");
   o.tn_no_tr = on("CSN_TN_NO_TR");
   o.filter_v1 = on("CSN_FILTER_V1");

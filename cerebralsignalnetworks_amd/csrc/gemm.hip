@@ -781,7 +781,9 @@ gemm_nt_256_kernel(const bf16_t* __restrict__ A, const bf16_t* __restrict__ Bt, 
   }   // tile loop
 }
 
-// NT, 256 x BN output tile, BN = 192 or 256 (N % BN == 0): the same kernel with a wider tile -- at the LSTM's chunk shapes
+// NT, 256 x BN output tile, BN = 192 or 256 (N % BN == 0), 8 waves, one workgroup per CU.  The default at BN = 256 (cfg4's
+// projection); at BN = 192 the four-wave gemm_nt_w4_kernel below is the default and this instantiation the reference form
+// (CSN_NT_NO_W4, and operands outside that kernel's 32-bit offsets).  The 256 x 128 kernel with a wider tile -- at the LSTM's chunk shapes
 // (8192 x 3072 x 768 with BN = 192, 8192 x 4096 x 1024 with BN = 256) 512 tiles = exactly two per CU instead of three /
 // four, 21 % / 33 % fewer bytes through the L2 -> CU fabric, which is what the 256 x 128 form is bound by (DESIGN.md
 // section 6: the vendor library's 192 x 256 kernel is faster by exactly that ratio).  8 waves (4 along M x 2 along N,
@@ -916,6 +918,146 @@ gemm_nt_wide_kernel(const bf16_t* __restrict__ A, const bf16_t* __restrict__ Bt,
     }
   }
   }   // tile loop
+}
+
+// The 256 x 192 tile on FOUR waves (2 along M x 2 along N, 128 x 96 outputs per wave = 8 x 6 accumulator fragments), TWO
+// workgroups to a CU, the default for BN = 192: the 192 store instructions of a tile's epilogue cost the CU about a quarter
+// of the launch when nothing else runs on it, and with two independent workgroups resident one
+// stores while the other multiplies.  Residency is a speed property only: no workgroup waits for another.
+// Stage: 32 contraction columns, A 256 rows x 64 B = 16 KB, B 192 rows x 64 B = 12 KB.  LDS image: 64-byte rows, four
+// 16-byte chunks per row, chunk ch of row r at position ch ^ nt64_sw(r): the 16 lanes of every ds_read_b128 lane group
+// ({0-3,12-15,20-27}, ...) then hit the 16 distinct 16-byte slots of the 256-byte bank row when lane l reads row
+// (l & 15), chunk (l >> 4).  A 1 KB LDS-DMA instruction fills 16 rows x 4 chunks, the swizzle on the source side.
+// Rings as in gemm_nt_wide_kernel: A (the streaming operand) NA stages, two k-steps ahead at NA = 3; B (L2-resident)
+// two stages, one k-step ahead; NA x 16 + 24 KB = 72 KB at NA = 3, two workgroups in a CU's 160 KB.  Counted vmcnt +
+// raw barrier; the 3 B + 4 A pieces of a step go one to an MFMA group; the six B fragments of a stage are held, the A
+// fragments streamed one ahead of the MFMA group that uses them.
+// Same 16 x 16 x 32 k-blocks per output element in ascending k, same operand order, same epilogue arithmetic as
+// gemm_nt_wide_kernel / gemm_nt_256_kernel: float32 results are bit-identical, bf16 the same rounding of them.
+// Source offsets are 32-bit byte offsets per lane against the scalar operand base (7 registers instead of 14 at 243 of
+// 256): the launcher takes this kernel only where nt_w4_offsets_fit().
+#ifndef CSN_NT_W4_NA          // A ring depth (timing experiments override it: tools/abl_build.sh)
+#define CSN_NT_W4_NA 3
+#endif
+__device__ __forceinline__ int nt64_sw(int row) {
+  const int g = (row >> 2) & 3;
+  return (((g ^ (g >> 1)) & 1) << 1) | (g >> 1);
+}
+template <typename OutT, int NA>
+__global__ void __launch_bounds__(256, 2)
+gemm_nt_w4_kernel(const bf16_t* __restrict__ A, const bf16_t* __restrict__ Bt, const float* __restrict__ bias,
+                  OutT* __restrict__ C, int64_t M, int64_t N, int64_t K, int accumulate) {
+  static_assert(NA == 2 || NA == 3, "A ring depth");
+  constexpr unsigned kAStage = 16384u, kBStage = 12288u, kBBase = NA * kAStage;
+  static_assert(kBBase + 2 * kBStage <= 81920u, "two workgroups per CU");
+  extern __shared__ __attribute__((aligned(1024))) char smem[];  // A: NA x 16 KB, then B: 2 x 12 KB
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);       // scalar: the LDS address of a DMA piece goes to M0
+  const int wm = wave >> 1, wn = wave & 1;
+  const unsigned ntn = (unsigned)(N / 192);
+  const unsigned lid = xcd_remap(blockIdx.x, gridDim.x);
+  const int64_t m0 = (int64_t)(lid / ntn) * 256, n0 = (int64_t)(lid % ntn) * 192;
+  const int nk = __builtin_amdgcn_readfirstlane((int)(K / 32));
+
+  // staging: instruction i of wave w fills rows [(4 i + w) 16, + 16) of a stage; lane -> row lane >> 2, LDS chunk
+  // position c = lane & 3 <- global chunk c ^ nt64_sw(row); A has 16 instructions per stage (4 per wave), B 12 (3)
+  unsigned a_off[4], b_off[3];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int row = (4 * i + wave) * 16 + (lane >> 2);
+    const int ch = (lane & 3) ^ nt64_sw(row);
+    int64_t am = m0 + row;
+    am = am < M ? am : M - 1;
+    a_off[i] = (unsigned)((am * K + ch * 8) * 2);
+  }
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const int row = (4 * i + wave) * 16 + (lane >> 2);
+    const int ch = (lane & 3) ^ nt64_sw(row);
+    b_off[i] = (unsigned)(((n0 + row) * K + ch * 8) * 2);
+  }
+  auto issue_a = [&](int kt, int i) {
+    glds16(reinterpret_cast<const char*>(A + (int64_t)kt * 32) + a_off[i], smem + (unsigned)(kt % NA) * kAStage + (4 * i + wave) * 1024);
+  };
+  auto issue_b = [&](int kt, int i) {
+    glds16(reinterpret_cast<const char*>(Bt + (int64_t)kt * 32) + b_off[i], smem + kBBase + (unsigned)(kt & 1) * kBStage + (4 * i + wave) * 1024);
+  };
+
+  // fragment addresses inside a stage: fragment i is 16 rows = 1024 bytes further (the swizzle repeats every 16 rows)
+  const unsigned frag = (unsigned)((lane & 15) * 64) + ((((unsigned)lane >> 4) ^ (unsigned)nt64_sw(lane & 15)) << 4);
+  const unsigned a_base = (unsigned)(wm * 128 * 64) + frag;
+  const unsigned b_base = kBBase + (unsigned)(wn * 96 * 64) + frag;
+#define W4_READ(addr, off) ({ bf16x8 v_; asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v_) : "v"(addr), "n"(off) : "memory"); v_; })
+
+  f32x4 acc[8][6];
+#pragma unroll
+  for (int i = 0; i < 8; ++i)
+#pragma unroll
+    for (int j = 0; j < 6; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+  // issue order: A(0) B(0) [A(1)] | step kt: B(kt+1), then A(kt+NA-1).  Behind B(kt) the wave has issued only A(kt+1)
+  // at NA = 3 (4 pieces): vmcnt(4) = "my pieces of A(kt) and B(kt) have landed" (vector-memory operations retire in
+  // order); at NA = 2 nothing: vmcnt(0).
+  //   read-after-DMA : the wait sits in front of step kt's barrier, the first read of stage kt behind it.
+  //   DMA-after-read : the slots of B(kt+1) and A(kt+NA-1) were last read in step kt - 1; a wave's reads of a step are
+  //                    retired by that step's MFMAs' counted lgkmcnt, all of them in front of step kt's barrier.
+#pragma unroll
+  for (int i = 0; i < 4; ++i) issue_a(0, i);
+#pragma unroll
+  for (int i = 0; i < 3; ++i) issue_b(0, i);
+  if (NA == 3 && nk > 1) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) issue_a(1, i);
+  }
+  for (int kt = 0; kt < nk; ++kt) {
+    if (NA == 3 && kt + 1 < nk) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    const bool more_b = kt + 1 < nk, more_a = kt + NA - 1 < nk;
+    const unsigned aa = a_base + (unsigned)(kt % NA) * kAStage, ba = b_base + (unsigned)(kt & 1) * kBStage;
+    bf16x8 af[2], bfr[6];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) bfr[j] = W4_READ(ba, j * 1024);
+    af[0] = W4_READ(aa, 0);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      if (i < 7) af[(i + 1) & 1] = W4_READ(aa, (i + 1) * 1024);
+      if (i < 7) asm volatile("s_waitcnt lgkmcnt(1)" ::: "memory");      // everything but A i+1
+      else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int j = 0; j < 6; ++j) {
+        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j], af[i & 1], acc[i][j], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        if (j == 1) {        // one DMA piece per MFMA group, behind MFMAs that wait for nothing new
+          if (i < 3) { if (more_b) issue_b(kt + 1, i); }
+          else if (i < 7) { if (more_a) issue_a(kt + NA - 1, i - 3); }
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+    }
+  }
+#undef W4_READ
+
+  // epilogue from the accumulators, as gemm_nt_wide_kernel
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const int64_t m = m0 + wm * 128 + i * 16 + (lane & 15);
+    if (m >= M) continue;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+      const int64_t n = n0 + wn * 96 + j * 16 + (lane >> 4) * 4;
+      f32x4 v = acc[i][j];
+      if (bias) v += *reinterpret_cast<const f32x4*>(bias + n);
+      if constexpr (sizeof(OutT) == 4) {
+        f32x4* dst = reinterpret_cast<f32x4*>((float*)C + m * N + n);
+        if (accumulate) v += *dst;
+        *dst = v;
+      } else {
+        *reinterpret_cast<bf16x4*>((bf16_t*)C + m * N + n) = (bf16x4){(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]};
+      }
+    }
+  }
 }
 
 // TN, 256 x 256 output tile, 8 waves (2 along M x 4 along N, 128 x 64 outputs per wave), LDS-DMA stages of
@@ -1408,6 +1550,14 @@ static int tn_splits_256(int64_t M, int64_t N, int64_t K) {
   return (int)s;
 }
 
+// gemm_nt_w4_kernel addresses its operands with 32-bit byte offsets per lane: both must be smaller than 4 GiB
+static bool nt_w4_offsets_fit(int64_t M, int64_t N, int64_t K) {
+  const int64_t lim = (int64_t)1 << 31;      // elements of 2 bytes
+  return M <= lim / K && N <= lim / K && M * K < lim && N * K < lim;
+}
+static constexpr int kNtW4LdsBytes = CSN_NT_W4_NA * 16384 + 2 * 12288;
+static_assert(kNtW4LdsBytes <= 81920, "two workgroups of gemm_nt_w4_kernel per CU");
+
 int gemm_nt(const void* A, const void* Bt, const float* bias, void* C, int64_t M, int64_t N, int64_t K, int dtype,
             int out_dtype, int accumulate, hipStream_t st, const Options& opt) {
   CSN_REQUIRE(A && Bt && C, "csn_gemm_nt: null pointer");
@@ -1444,6 +1594,14 @@ int gemm_nt(const void* A, const void* Bt, const float* bias, void* C, int64_t M
           gemm_nt_wide_kernel<bf16_t, 256><<<gridw, 512, lds, st>>>((const bf16_t*)A, (const bf16_t*)Bt, bias, (bf16_t*)C, M, N, K, 0);
         else
           gemm_nt_wide_kernel<float, 256><<<gridw, 512, lds, st>>>((const bf16_t*)A, (const bf16_t*)Bt, bias, (float*)C, M, N, K, accumulate);
+      } else if (!opt.nt_no_w4 && nt_w4_offsets_fit(M, N, K)) {
+        // four waves, two workgroups per CU (CSN_NT_NO_W4: the 8-wave kernel below, the reference form)
+        if (int rc = ensure_dyn_lds<&gemm_nt_w4_kernel<bf16_t, CSN_NT_W4_NA>>(kNtW4LdsBytes)) return rc;
+        if (int rc = ensure_dyn_lds<&gemm_nt_w4_kernel<float, CSN_NT_W4_NA>>(kNtW4LdsBytes)) return rc;
+        if (out_dtype == CSN_BF16)
+          gemm_nt_w4_kernel<bf16_t, CSN_NT_W4_NA><<<gridw, 256, kNtW4LdsBytes, st>>>((const bf16_t*)A, (const bf16_t*)Bt, bias, (bf16_t*)C, M, N, K, 0);
+        else
+          gemm_nt_w4_kernel<float, CSN_NT_W4_NA><<<gridw, 256, kNtW4LdsBytes, st>>>((const bf16_t*)A, (const bf16_t*)Bt, bias, (float*)C, M, N, K, accumulate);
       } else {
         if (int rc = ensure_dyn_lds<&gemm_nt_wide_kernel<bf16_t, 192>>(lds)) return rc;
         if (int rc = ensure_dyn_lds<&gemm_nt_wide_kernel<float, 192>>(lds)) return rc;
@@ -1502,6 +1660,14 @@ size_t gemm_tn_scratch_bytes(int64_t M, int64_t N, int64_t K, const Options& opt
   return (size_t)(a > b ? a : b) * (size_t)M * (size_t)N * sizeof(float);
 }
 }  // namespace csn
+
+// Host-only diagnostics of the dispatch above for the tests (bound on use by cabi.py; not part of the public header, so
+// a library from before them still loads for an A/B run): 1 where gemm_nt_w4_kernel's 32-bit offsets cover A[M, K] and
+// Bt[N, K], and the dynamic LDS bytes of its launches.
+extern "C" int csn_gemm_nt_w4_offsets_fit(int64_t M, int64_t N, int64_t K) {
+  return M > 0 && N > 0 && K > 0 && nt_w4_offsets_fit(M, N, K) ? 1 : 0;
+}
+extern "C" int csn_gemm_nt_w4_lds_bytes(void) { return kNtW4LdsBytes; }
 
 extern "C" size_t csn_gemm_tn_scratch_bytes(int64_t M, int64_t N, int64_t K) {
   return gemm_tn_scratch_bytes(M, N, K, options_from_env());

@@ -30,3 +30,6 @@ a2, b2 = rnd(8192, 768), rnd(3072, 768)
 bias = torch.randn(3072, device=dev)
 out = torch.empty(8192, 3072, device=dev)
 bench("nt 8192x3072x768 f32", lambda: cabi.gemm_nt(a2, b2, bias, out=out), 2.0 * 8192 * 3072 * 768)
+os.environ["CSN_NT_NO_W4"] = "1"      # the 8-wave kernel of the same 256 x 192 tile (the switches are read per call)
+bench("nt 8192x3072x768 f32 CSN_NT_NO_W4=1", lambda: cabi.gemm_nt(a2, b2, bias, out=out), 2.0 * 8192 * 3072 * 768)
+del os.environ["CSN_NT_NO_W4"]
