@@ -109,8 +109,9 @@ def build_parser(flavour=PERILS):
     p.add_argument('--fused_optimizer', action='store_true',
                    help='adamw / adam / lars as fused HIP steps over the flat parameter buffer (rmsprop always is)')
     p.add_argument('--fused_loss', action='store_true',
-                   help='featdist / kd: loss value and gradient from one fused HIP call in float64 (csn_distill_loss) '
-                        'instead of a chain of torch ops; does nothing with --loss cosine (always fused) or --loss barlow')
+                   help='featdist / kd / barlow: loss value and gradient from fused HIP calls in float64 (csn_distill_loss, '
+                        'csn_barlow_corr + csn_barlow_grad) instead of a chain of torch ops; does nothing with --loss cosine '
+                        '(always fused)')
     p.add_argument('--compat_label_bug', action='store_true',
                    help='reproduce the batch-local label lookup of transformEEGDataLSTMByList')
     return p

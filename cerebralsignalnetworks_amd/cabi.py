@@ -109,6 +109,12 @@ SIGNATURES = {
     "csn_lars_step": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_i64, _c_int, _c_void_p, _c_double, _c_double,
                                _c_double, _c_double, _c_void_p]),
     "csn_barlow_offdiag_sqsum": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_void_p]),
+    "csn_barlow_saved_bytes": (_c_size_t, [_c_int]),
+    "csn_barlow_scratch_bytes": (_c_size_t, [_c_int, _c_int]),
+    "csn_barlow_corr": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_double, _c_double, _c_void_p, _c_void_p, _c_void_p,
+                                 _c_void_p, _c_double, _c_void_p]),
+    "csn_barlow_grad": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_double, _c_double,
+                                 _c_float, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
     "csn_l2_topk_scratch_bytes": (_c_size_t, [_c_i64, _c_i64]),
     "csn_l2_topk": (_c_int, [_c_void_p, _c_void_p, _c_i64, _c_i64, _c_int, _c_int, _c_void_p, _c_void_p,
                              _c_void_p, _c_void_p]),
@@ -760,6 +766,56 @@ def barlow_offdiag_sqsum(c):
     with torch.cuda.device(c.device):
         _check(load().csn_barlow_offdiag_sqsum(_ptr(c), c.shape[0], _ptr(out), _stream()))
     return out
+
+
+def _barlow_pair(z1, z2, who):
+    _need_cuda(z1, z2)
+    a, b = _f32_rows(z1, "z1", 2), _f32_rows(z2, "z2", 2)
+    if a.shape != b.shape or a.device != b.device:
+        raise CsnError(f"{who}: z2 {tuple(b.shape)} on {b.device} against z1 {tuple(a.shape)} on {a.device}")
+    return a, b
+
+
+def barlow_corr(z1, z2, batch_size, eps=1e-5, running_mean=None, running_var=None, momentum=0.1):
+    """csn_barlow_corr on z1 / z2 [B,D] float32 -> (c [D,D] float64: THIS rank's term, saved [4,D] float64).
+    ``batch_size`` is the GLOBAL batch.  ``running_mean`` / ``running_var`` (float32 [D], contiguous, both or neither) are
+    updated in place, for z1 and then for z2."""
+    a, b = _barlow_pair(z1, z2, "barlow_corr")
+    B, D = a.shape
+    if (running_mean is None) != (running_var is None):
+        raise CsnError("barlow_corr: running_mean and running_var go together")
+    for name, r in (("running_mean", running_mean), ("running_var", running_var)):
+        if r is not None and (r.dtype != torch.float32 or r.shape != (D,) or not r.is_contiguous() or r.device != a.device):
+            raise CsnError(f"barlow_corr: {name} must be a contiguous float32 [{D}] tensor on {a.device}, "
+                           f"got {r.dtype} {tuple(r.shape)} on {r.device}")
+    lib = load()
+    c = torch.empty((D, D), dtype=torch.float64, device=a.device)
+    saved = torch.empty((4, D), dtype=torch.float64, device=a.device)       # csn_barlow_saved_bytes(D) bytes, caller-owned
+    with torch.cuda.device(a.device):
+        _check(lib.csn_barlow_corr(_ptr(a), _ptr(b), B, D, float(eps), 1.0 / float(batch_size), _ptr(c), _ptr(saved),
+                                   _ptr(running_mean), _ptr(running_var), float(momentum), _stream()))
+    return c, saved
+
+
+def barlow_grad(z1, z2, c, c_local, saved, batch_size, lambd, grad_scale=1.0, want=(True, True)):
+    """csn_barlow_grad -> (loss[1], dz1 | None, dz2 | None).  ``c``: the sum of every rank's term, ``c_local``: this rank's,
+    as barlow_corr returned it (the same tensor on one rank); ``want``: which of (dz1, dz2) to compute."""
+    a, b = _barlow_pair(z1, z2, "barlow_grad")
+    B, D = a.shape
+    _need_cuda(c, c_local, saved)
+    for name, t, shape in (("c", c, (D, D)), ("c_local", c_local, (D, D)), ("saved", saved, (4, D))):
+        if t.dtype != torch.float64 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != a.device:
+            raise CsnError(f"barlow_grad: {name} must be a contiguous float64 {list(shape)} tensor on {a.device}, "
+                           f"got {t.dtype} {tuple(t.shape)} on {t.device}")
+    lib = load()
+    loss = torch.empty(1, dtype=torch.float32, device=a.device)
+    dz1 = torch.empty_like(a) if want[0] else None
+    dz2 = torch.empty_like(b) if want[1] else None
+    scratch = torch.empty(lib.csn_barlow_scratch_bytes(B, D) // 8, dtype=torch.float64, device=a.device)     # caller-owned
+    with torch.cuda.device(a.device):
+        _check(lib.csn_barlow_grad(_ptr(a), _ptr(b), B, D, _ptr(c), _ptr(c_local), _ptr(saved), 1.0 / float(batch_size),
+                                   float(lambd), float(grad_scale), _ptr(loss), _ptr(dz1), _ptr(dz2), _ptr(scratch), _stream()))
+    return loss, dz1, dz2
 
 
 def l2_topk(gallery, query, k):

@@ -6,7 +6,7 @@
   FeatureDistributionLossKD  LstmDistillFromDinoV2TrainSpampinato.py:125-184 (soft-target KL + CE)
   FeatureDistributionLossSoft LstmDistillFromDinoV2Eval.py:106-146 (soft-target KL alone)
   FeatureDistributionLossMSE LstmDistillation.py:161-172 (global mean / std / MSE match)
-  BarlowTwinsLoss            EEG-BarlowNetworks/net.py:33-42 (HIP off-diagonal reduction)
+  BarlowTwinsLoss            EEG-BarlowNetworks/net.py:33-42 (HIP off-diagonal reduction; fused=True: csn_barlow_corr + _grad)
   LARS, barlow_learning_rate EEG-BarlowNetworks/optim.py:5-44, barlow_utils.py:8-21
 Every class is checked against values and gradients obtained by executing the reference's own definition
 (tests/golden/ref_losses.npz, tests/test_ref_pinned.py).
@@ -15,6 +15,8 @@ Reference quirks are kept on purpose.
 ``fused=True`` on FeatureDistributionLoss, its KD and Soft variants and loss_fn_kd: value and gradient come from ONE
 csn_distill_loss call (float64 arithmetic, two launches) when every tensor input is a float32
 device tensor; anything else (CPU tensors, float64) takes the torch form.  Opt-in: the default keeps the torch form.
+``fused=True`` on BarlowTwinsLoss: batch norm, correlation, loss and both gradients from csn_barlow_corr + csn_barlow_grad
+(float64 arithmetic, five launches) under the same rule, in training mode.
 """
 import numpy as np
 import torch
@@ -202,16 +204,64 @@ class _AllReduceSum(torch.autograd.Function):
         return g
 
 
+def _dist_world():
+    if torch.distributed.is_available() and torch.distributed.is_initialized():
+        return torch.distributed.get_world_size()
+    return 1
+
+
+class _BarlowFusedFn(torch.autograd.Function):
+    """csn_barlow_corr, the all-reduce of the float64 c, csn_barlow_grad: like _DistillLossFn the gradients are computed in
+    the forward, saved, and multiplied by the incoming scalar.  Each rank's gradient goes through its own term of c only
+    (the _AllReduceSum contract).  The kernel updates the running statistics of ``bn`` (for z1, then for z2)."""
+
+    @staticmethod
+    def forward(ctx, z1, z2, bn, batch_size, lambd):
+        want = (ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        z1, z2 = z1.contiguous(), z2.contiguous()
+        track = bn.track_running_stats and bn.running_mean is not None
+        c_local, saved = cabi.barlow_corr(z1, z2, batch_size, eps=bn.eps, running_mean=bn.running_mean if track else None,
+                                          running_var=bn.running_var if track else None, momentum=float(bn.momentum))
+        if track and bn.num_batches_tracked is not None:
+            bn.num_batches_tracked.add_(2)
+        c = c_local
+        if _dist_world() > 1:
+            c = c_local.clone()
+            torch.distributed.all_reduce(c)
+        loss, dz1, dz2 = cabi.barlow_grad(z1, z2, c, c_local, saved, batch_size, lambd, want=want)
+        ctx.have = (dz1 is not None, dz2 is not None)
+        ctx.save_for_backward(*[g for g in (dz1, dz2) if g is not None])
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        grads = list(ctx.saved_tensors)
+        dz1 = grads.pop(0) * g if ctx.have[0] else None
+        dz2 = grads.pop(0) * g if ctx.have[1] else None
+        return dz1, dz2, None, None, None
+
+
 class BarlowTwinsLoss(nn.Module):
     """net.py:33-42 on two embedding batches: bn(z1).T @ bn(z2) / batch_size, all_reduce, on + lambd*off.
-    ``batch_size`` is the GLOBAL batch (args.batch_size there); BatchNorm statistics stay per rank, as there."""
+    ``batch_size`` is the GLOBAL batch (args.batch_size there); BatchNorm statistics stay per rank, as there.
 
-    def __init__(self, dim, batch_size, lambd=0.0051):
+    ``fused=True``: value and both gradients in float64 from csn_barlow_corr + csn_barlow_grad when
+    both inputs are float32 device tensors, the module and its ``bn`` are in training mode and ``bn.momentum`` is a number;
+    anything else takes the torch form below, bit for bit."""
+
+    def __init__(self, dim, batch_size, lambd=0.0051, fused=False):
         super().__init__()
         self.bn = nn.BatchNorm1d(dim, affine=False)
         self.batch_size, self.lambd = batch_size, lambd
+        self.fused = bool(fused)
+
+    def _fused_applies(self, z1, z2):
+        return self.fused and self.training and self.bn.training and isinstance(self.bn.momentum, (int, float)) \
+            and z1.dim() == 2 and z1.shape == z2.shape and _fusable(z1, z2)
 
     def forward(self, z1, z2):
+        if self._fused_applies(z1, z2):
+            return _BarlowFusedFn.apply(z1, z2, self.bn, self.batch_size, self.lambd)
         c = self.bn(z1).T @ self.bn(z2)
         c = c / self.batch_size
         if torch.distributed.is_available() and torch.distributed.is_initialized() \

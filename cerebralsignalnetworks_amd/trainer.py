@@ -232,7 +232,8 @@ class DistillTrainer:
         (flat_optim.FlatAdamW / FlatLARS) instead of the torch optimisers; rmsprop is fused either way.
 
         ``fused_loss=True``: the featdist and kd losses compute value and gradient in one csn_distill_loss call (float64
-        arithmetic, two launches) instead of a chain of torch ops; cosine is fused either way, barlow is not affected.
+        arithmetic, two launches) instead of a chain of torch ops, and barlow in csn_barlow_corr + csn_barlow_grad (float64,
+        five launches; BarlowTwinsLoss(fused=True)); cosine is fused either way.
 
         ``accum_steps = k > 1``: train_step splits its batch into k equal micro-batches and sums their gradients (each
         loss scaled by 1 / k) in the flat buffer before the one all-reduce and optimiser step -- the step of the whole
@@ -352,7 +353,7 @@ class DistillTrainer:
             feat = out[0] if isinstance(out, tuple) else out
             if self.barlow is None:
                 _, world = dist_info()
-                self.barlow = BarlowTwinsLoss(feat.shape[1], feat.shape[0] * world).to(feat.device)
+                self.barlow = BarlowTwinsLoss(feat.shape[1], feat.shape[0] * world, fused=self.fused_loss).to(feat.device)
             return self.barlow(feat, targets)
         raise ValueError(self.loss_name)
 

@@ -96,7 +96,7 @@ enum csnDtype { CSN_F32 = 0, CSN_BF16 = 1 };
 /* ABI version of this header; bumped on any signature change.  A symbol added beside the existing ones
  * (csn_lstm_plan_set_grad_mode, csn_lstm_plan_set_lengths, csn_lstm_plan_set_views, csn_lstm_plan_set_io, csn_lstm_plan_half_tile_launches, the
  * csn_flat_* family, csn_adam_step, csn_lars_step, csn_eeg_bandpass_stream and its _path, csn_distill_loss,
- * csn_dino_loss) breaks no caller and does not bump it; neither does a new bit of csn_lstm_plan_create's `training` word. */
+ * csn_dino_loss, csn_barlow_corr, csn_barlow_grad) breaks no caller and does not bump it; neither does a new bit of csn_lstm_plan_create's `training` word. */
 #define CSN_ABI_VERSION 6
 int csn_abi_version(void);
 /* Thread-local message for the last non-zero status returned on this thread. */
@@ -578,6 +578,46 @@ int csn_lars_step(float* params, const float* grads, float* mu, int64_t n, int n
  * Replaces: EEG-BarlowNetworks/net.py:6-9,39-40.
  * ---------------------------------------------------------------------------------- */
 int csn_barlow_offdiag_sqsum(const float* c, int D, float* out, csnStream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * K7b  the Barlow-Twins loss itself, value and both gradients: BatchNorm1d(affine=False) in training
+ * mode on z1[B,D] and z2[B,D] (float32), the cross-correlation, on + lambd * off, and the closed-form backward through the
+ * batch norm.  Float64 arithmetic on the float32 inputs, every float32 output rounded once; caller-owned `saved`
+ * (csn_barlow_saved_bytes) and `scratch` (csn_barlow_scratch_bytes), both 8-byte aligned; no library state; everything is
+ * enqueued on `stream`.  Two calls, because the reference all-reduces c between them (net.py:38) outside autograd: each rank
+ * back-propagates d loss(c summed) / d c through its own term c_local only.
+ *
+ * csn_barlow_corr, for z = z1 and z = z2 and every column i:
+ *     mean_i = sum_b z[b,i] / B,   var_i = sum_b (z[b,i] - mean_i)^2 / B   (two passes, biased),   rstd_i = 1 / sqrt(var_i + eps)
+ *     zn[b,i] = (z[b,i] - mean_i) rstd_i
+ *     c[i,j] = inv_batch * sum_b z1n[b,i] z2n[b,j]          float64 [D,D] row-major, THIS rank's term;
+ *   inv_batch = 1 / the GLOBAL batch (all ranks).  saved = mean1[D], rstd1[D], mean2[D], rstd2[D] (float64).
+ *   running_mean / running_var (float32 [D], both NULL or both set): the ONE buffer pair is updated twice, for z1 and then
+ *   for z2, as one nn.BatchNorm1d called twice:   rm <- fl32((1 - momentum) rm + momentum mean)
+ *                                                 rv <- fl32((1 - momentum) rv + momentum var B / (B - 1))
+ * csn_barlow_grad, c = the sum of every rank's term, c_local = this rank's (the same pointer on one rank):
+ *     G[i,j] = 2 (c[i,i] - 1) on the diagonal, 2 lambd c[i,j] off it
+ *     loss = fl32( sum_i (c_ii - 1)^2 + lambd sum_{i != j} c_ij^2 )                       (not scaled by grad_scale)
+ *     k1[i] = sum_j G[i,j] c_local[i,j] / B,      k2[j] = sum_i G[i,j] c_local[i,j] / B
+ *     dz1[b,i] = fl32( grad_scale rstd1[i] (inv_batch sum_j G[i,j] z2n[b,j] - z1n[b,i] k1[i]) )
+ *     dz2[b,j] = fl32( grad_scale rstd2[j] (inv_batch sum_i G[i,j] z1n[b,i] - z2n[b,j] k2[j]) )
+ *   -- the batch-norm backward (dzn - mean_b dzn - zn mean_b(dzn zn)) rstd in closed form: mean_b(dzn zn) is k, and
+ *   mean_b dzn is identically zero because zn is column-centred.  dz1 / dz2 passed as NULL are not written.
+ *   Every contraction is one fma chain per result in ascending order; the sums over c are added in an order that depends on
+ *   D only: two calls on the same input give the same bits.  NaN / Inf in the inputs propagate.
+ * Launches: corr 2, grad 3 (2 without a gradient).
+ * Refused on the host before any launch: a null z1 / z2 / c / c_local / saved / loss / scratch; B < 2 (BatchNorm1d refuses
+ * one row in training) or D < 1; eps, inv_batch or lambd not finite, eps or inv_batch <= 0; momentum outside [0, 1];
+ * exactly one running pointer; c, c_local, saved or scratch not 8-byte aligned.
+ * Replaces: BarlowTwins.forward and its autograd backward, EEG-BarlowNetworks/net.py:33-42.
+ * ---------------------------------------------------------------------------------- */
+size_t csn_barlow_saved_bytes(int D);
+size_t csn_barlow_scratch_bytes(int B, int D);
+int csn_barlow_corr(const float* z1, const float* z2, int B, int D, double eps, double inv_batch, double* c, void* saved,
+                    float* running_mean, float* running_var, double momentum, csnStream_t stream);
+int csn_barlow_grad(const float* z1, const float* z2, int B, int D, const double* c, const double* c_local,
+                    const void* saved, double inv_batch, double lambd, float grad_scale, float* loss, float* dz1,
+                    float* dz2, void* scratch, csnStream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * K8  exact squared-L2 top-k.  Replaces: faiss.IndexFlatL2(d).add / .search(k),

@@ -124,6 +124,25 @@ for i in range(n_cases):
         return float((np.abs(out - ref) / np.maximum(1.0, np.abs(ref))).max()), 1e-5
     case(f"barlow_offdiag D{Dm}", h)
 
+    Bb, Db = int(rng.integers(2, 300)), int(rng.integers(1, 500))
+
+    def bl(Bb=Bb, Db=Db):
+        # csn_barlow_corr + csn_barlow_grad against float64 autograd of batch norm -> correlation -> on + lambd off
+        z1, z2 = (rng.standard_normal((Bb, Db)).astype(np.float32) for _ in range(2))
+        a, b = (torch.tensor(z, dtype=torch.float64, requires_grad=True) for z in (z1, z2))
+        n1, n2 = (torch.nn.functional.batch_norm(z, None, None, training=True, eps=1e-5) for z in (a, b))
+        cm = n1.T @ n2 / Bb
+        dg = torch.diagonal(cm)
+        ref = (dg - 1).pow(2).sum() + 0.0051 * (cm.pow(2).sum() - dg.pow(2).sum())
+        ref.backward()
+        cd, saved = cabi.barlow_corr(t(z1), t(z2), Bb)
+        loss, d1, d2 = cabi.barlow_grad(t(z1), t(z2), cd, cd, saved, Bb, 0.0051)
+        e0 = abs(float(loss) - float(ref)) / max(1.0, abs(float(ref)))
+        e1 = float((d1.double().cpu() - a.grad).abs().max() / a.grad.abs().max())
+        e2 = float((d2.double().cpu() - b.grad).abs().max() / b.grad.abs().max())
+        return max(e0, e1, e2), 2e-7
+    case(f"barlow_loss B{Bb} D{Db}", bl)
+
 # ---- retrieval ---------------------------------------------------------------------------------
 for i in range(n_cases):
     Ng, Nq, D = int(rng.integers(1, 3000)), int(rng.integers(1, 300)), int(rng.integers(1, 500))
