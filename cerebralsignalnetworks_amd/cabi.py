@@ -307,6 +307,28 @@ def gemm_nt_w4_lds_bytes():
     return int(fn())
 
 
+# the values of NtRoute (csrc/gemm_nt.hip) and TnRoute (csrc/gemm_tn.hip): TN as (route, kernel behind it)
+GEMM_NT_ROUTES = ("generic", "bf16", "dma", "tile256x128", "wide192", "wide256", "wide192w4")
+GEMM_TN_ROUTES = (("generic", "generic"), ("tile128", "tn128"), ("tile128", "tn128-notr"), ("tile256", "ring3"),
+                  ("tile256", "ring4"), ("tile256", "ring5"), ("tile256", "w4-128"), ("tile256", "w4-256"))
+
+
+def gemm_nt_route(M, N, K, dtype=torch.bfloat16, aligned16=True):
+    """The kernel csn_gemm_nt takes for this shape under the current environment's switches, one of GEMM_NT_ROUTES (host
+    only; bound on use as gemm_nt_w4_offsets_fit).  aligned16: A, Bt, C and bias are all 16-byte aligned."""
+    fn = load().csn_gemm_nt_route
+    fn.restype, fn.argtypes = _c_int, [_c_i64, _c_i64, _c_i64, _c_int, _c_int]
+    return GEMM_NT_ROUTES[fn(M, N, K, _dt(dtype), int(aligned16))]
+
+
+def gemm_tn_route(M, N, K, dtype=torch.bfloat16, aligned16=True, colsum=False):
+    """(route, kernel) the weight-gradient GEMM takes, one of GEMM_TN_ROUTES (host only; bound on use).  colsum: the caller
+    asks for the column sums of A as well (the LSTM's bias gradient)."""
+    fn = load().csn_gemm_tn_route
+    fn.restype, fn.argtypes = _c_int, [_c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_int]
+    return GEMM_TN_ROUTES[fn(M, N, K, _dt(dtype), int(aligned16), int(colsum))]
+
+
 def gemm_tn(a_km, b_kn):
     _need_cuda(a_km, b_kn)
     a, b = a_km.contiguous(), b_kn.contiguous()

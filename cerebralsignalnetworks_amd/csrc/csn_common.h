@@ -174,6 +174,11 @@ int launch_colsum(const void* X, int64_t R, int64_t N, int dtype, float* out, fl
                   hipStream_t st);
 int colsum_chunks();
 int launch_colsum_partial(const void* X, int64_t R, int64_t N, int dtype, void* scratch, hipStream_t st);
+// C(m,n) = sum_k A[m*sam + k*sak] B[k*sbk + n*sbn] (+ bias[n]) on the exact-f32 MFMA, any strides; `splits` K splits
+// write float32 slabs slab_stride elements apart (gemm_f32.hip: the fallback of the bf16 kernels below)
+int launch_generic(const void* A, int64_t sam, int64_t sak, const void* Bm, int64_t sbk, int64_t sbn,
+                   const float* bias, void* C, int64_t ldc, int64_t M, int64_t N, int64_t K, int dtype,
+                   int out_dtype, int accumulate, int splits, int64_t slab_stride, hipStream_t st);
 // split-K slabs of C[M,N] = A[K,M]^T B[K,N] into `slabs` ([S][M*N] f32); returns S through S_out
 int launch_gemm_tn_slabs(const void* A, const void* B, float* slabs, int64_t M, int64_t N, int64_t K, int dtype,
                          hipStream_t st, int* S_out, float* colsum, int* colsum_done, const Options& opt);

@@ -4,11 +4,12 @@
 // leave idle -- the input gradient dx of the chunk the layer above finished one launch ago -- so it needs no stream,
 // event or flag: both of its dependencies are kernel boundaries.
 //
-// Structure = gemm_nt_256_kernel (gemm.hip): ring of 3 LDS-DMA stages of 64 contraction columns (A 32 KB + B 16 KB,
-// 128-byte rows, XOR swizzle applied on the source side), counted vmcnt + raw barrier, fragment reads in inline
-// asm with counted lgkmcnt; here 4 waves (2 x 2) of 128 x 64 outputs each.  K % 64 == 0, N % 4 == 0.
+// Structure = gemm_nt_256_kernel (gemm_nt.hip), primitives and store epilogue from gemm_tile.h: ring of 3 LDS-DMA
+// stages of 64 contraction columns (A 32 KB + B 16 KB, 128-byte rows, XOR swizzle applied on the source side), counted
+// vmcnt + raw barrier, fragment reads in inline asm with counted lgkmcnt; here 4 waves (2 x 2) of 128 x 64 outputs
+// each.  K % 64 == 0, N % 4 == 0.
 #pragma once
-#include "csn_common.h"
+#include "gemm_tile.h"
 #include "lstm_cell_blk.h"
 
 namespace csn {
@@ -16,16 +17,6 @@ namespace csn {
 static constexpr int kBesideStages = 3;
 static constexpr unsigned kBesideStageBytes = 49152;
 static constexpr unsigned kBesideLdsBytes = kBesideStages * kBesideStageBytes;
-
-__device__ __forceinline__ bf16x8 beside_lds_read_b128(unsigned addr) {
-  bf16x8 v;
-  asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr) : "memory");
-  return v;
-}
-__device__ __forceinline__ void beside_glds16(const void* g, void* l) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-}
 
 // `smem`: the workgroup's dynamic LDS (at LDS offset 0, >= kBesideLdsBytes); worker = this workgroup's index
 // among the nworkers workgroups that share the GEMM (workgroups of one XCD should have consecutive indices).
@@ -46,6 +37,7 @@ __device__ __forceinline__ void beside_gemm_tiles(const BesideGemm& g, char* sme
     const int64_t m0 = (int64_t)(lid / ntn) * 256, n0 = (int64_t)(lid % ntn) * 128;
     // staging: a 1 KB instruction fills 8 rows x 8 chunks; A has 32 per stage (8 per wave), B 16 (4 per wave);
     // lane -> row r = lane >> 3, LDS chunk position c = lane & 7 <- global chunk c ^ ((row >> 1) & 7)
+    // (nt_dma_src of gemm_tile.h written out: the addresses are formed per stage here, not held in registers)
     const int srow = lane >> 3;
     auto issue = [&](int kt) {
       char* a_s = smem + (kt % NSTAGE) * kBesideStageBytes;
@@ -56,7 +48,7 @@ __device__ __forceinline__ void beside_gemm_tiles(const BesideGemm& g, char* sme
         const int ch = (lane & 7) ^ ((row >> 1) & 7);
         int64_t am = m0 + row;
         am = am < M ? am : M - 1;
-        beside_glds16(g.A + am * K + (int64_t)kt * 64 + ch * 8, a_s + (4 * i + wave) * 1024);
+        glds16(g.A + am * K + (int64_t)kt * 64 + ch * 8, a_s + (4 * i + wave) * 1024);
       }
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -64,7 +56,7 @@ __device__ __forceinline__ void beside_gemm_tiles(const BesideGemm& g, char* sme
         const int ch = (lane & 7) ^ ((row >> 1) & 7);
         int64_t bn = n0 + row;
         bn = bn < N ? bn : N - 1;
-        beside_glds16(g.Bt + bn * K + (int64_t)kt * 64 + ch * 8, b_s + (4 * i + wave) * 1024);
+        glds16(g.Bt + bn * K + (int64_t)kt * 64 + ch * 8, b_s + (4 * i + wave) * 1024);
       }
     };
 
@@ -89,9 +81,9 @@ __device__ __forceinline__ void beside_gemm_tiles(const BesideGemm& g, char* sme
         const unsigned xo = kk ? 64u : 0u;
         bf16x8 af[8], bfr[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) bfr[j] = beside_lds_read_b128(((b_base ^ xo) + sb) + j * 2048u);
+        for (int j = 0; j < 4; ++j) bfr[j] = lds_read_b128(((b_base ^ xo) + sb) + j * 2048u);
 #pragma unroll
-        for (int i = 0; i < 8; ++i) af[i] = beside_lds_read_b128(((a_base ^ xo) + sb) + i * 2048u);
+        for (int i = 0; i < 8; ++i) af[i] = lds_read_b128(((a_base ^ xo) + sb) + i * 2048u);
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
           switch (7 - i) {   // LDS reads complete in order: A tile i is ready once at most 7 - i younger reads are out
@@ -119,6 +111,8 @@ __device__ __forceinline__ void beside_gemm_tiles(const BesideGemm& g, char* sme
       if (m >= M) continue;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
+        // (nt_store_frag of gemm_tile.h without bias and accumulation, written out: through the function the
+        // compiler addresses g.C differently in all 36 instantiations of the backward kernel)
         const int64_t n = n0 + wn * 64 + j * 16 + (lane >> 4) * 4;
         if (n + 3 < N) {
           *reinterpret_cast<float4*>(g.C + m * N + n) = make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);

@@ -1,5 +1,5 @@
 """Shared by tests/test_gemm_tn_splits_cpu.py and tests/test_gpu_gemm_tn_splits.py (not a test module): a plain-Python
-statement of how the weight-gradient GEMM (csn_gemm_tn, launch_gemm_tn_slabs in csrc/gemm.hip) cuts its contraction
+statement of how the weight-gradient GEMM (csn_gemm_tn, launch_gemm_tn_slabs in csrc/gemm_tn.hip) cuts its contraction
 K = T * B into S splits of `kper` rows, the cases the two files run, and their exact small-integer operands.
 
 The formulas are WRITTEN OUT here, not imported from the library: the CPU file holds them against

@@ -292,13 +292,15 @@ def _filtfilt(device):
     return {"x": x}, lambda a: {"y": cabi.eeg_filtfilt(a["x"], sos)}
 
 
-def gemm_nt_route(M, N, K, dtype):
-    """Mirror of the dispatch of gemm_nt() in csrc/gemm.hip for 16-byte aligned operands and no CSN_GEMM_* switch: the
-    kernel family a shape takes.  The cases below assert the route their label names, so a change of the thresholds
-    there shows up here instead of quietly moving a case."""
-    if not (dtype == torch.bfloat16 and K % 8 == 0 and N % 4 == 0):
+def gemm_nt_route(M, N, K, dtype, aligned16=True, generic=False, no_dma=False, no_256=False, no_192=False, no_w4=False):
+    """Mirror of nt_route() in csrc/gemm_nt.hip: the kernel family a shape takes.  The keywords are the operands'
+    16-byte alignment and the switches CSN_GEMM_GENERIC, CSN_GEMM_NO_DMA, CSN_GEMM_NO_256, CSN_GEMM_NO_192 and
+    CSN_NT_NO_W4 (which picks between the two forms of the 192 tile: both are "wide192" here).  The cases below assert
+    the route their label names, so a change of the thresholds there shows up here instead of quietly moving a case;
+    tests/test_stream_order_cpu.py holds this mirror against the library's own answer (cabi.gemm_nt_route)."""
+    if not (dtype == torch.bfloat16 and K % 8 == 0 and N % 4 == 0 and aligned16 and not generic):
         return "generic"
-    if K % 64 == 0 and K >= 128 and M >= 256:
+    if K % 64 == 0 and K >= 128 and M >= 256 and not (no_dma or no_256 or no_192):
         def fills(bn):          # whole tiles for every CU: at least 256 tiles, at most 10 % of the last round empty
             t = (N // bn) * -(-M // 256)
             return N % bn == 0 and t >= 256 and t * 10 >= -(-t // 256) * 256 * 9
@@ -306,15 +308,16 @@ def gemm_nt_route(M, N, K, dtype):
             return "wide256"
         if fills(192):
             return "wide192"
-    if K % 64 == 0 and K >= 256 and M >= 256 and N >= 1024:
+    if K % 64 == 0 and K >= 256 and M >= 256 and N >= 1024 and not (no_dma or no_256):
         return "tile256x128"
-    return "dma" if K % 64 == 0 else "bf16"
+    return "dma" if K % 64 == 0 and not no_dma else "bf16"
 
 
-def gemm_tn_route(M, N, K):
-    """Mirror of launch_gemm_tn_slabs() in csrc/gemm.hip for aligned bf16 operands with M and N multiples of 8."""
+def gemm_tn_route(M, N, K, no_256=False, no_dma=False):
+    """Mirror of tn_route() in csrc/gemm_tn.hip for aligned bf16 operands with M and N multiples of 8; the keywords are
+    the switches CSN_GEMM_NO_256 and CSN_GEMM_NO_DMA."""
     assert M % 8 == 0 and N % 8 == 0
-    return "tile256" if M >= 256 and N >= 128 and K % 64 == 0 and K >= 8192 else "tile128"
+    return "tile256" if M >= 256 and N >= 128 and K % 64 == 0 and K >= 8192 and not (no_256 or no_dma) else "tile128"
 
 
 def _gemm_nt(route, M, N, K, dtype, out_dtype, accumulate=False):
@@ -623,7 +626,7 @@ CASE_TABLE = {
     "csn_lstm_backward": InTest(*(t for t in _LSTM_TESTS if "_forward_with_late_inputs" not in t)),
     "csn_lstm_status_clear": InTest("test_workspace_init_and_status_word_in_stream_order"),
     "csn_lstm_status_raise": InTest("test_workspace_init_and_status_word_in_stream_order"),
-    # the five routes of gemm_nt() in csrc/gemm.hip in the order it tries them (the wide one in both tile widths: 16 x 16
+    # the five routes of gemm_nt() in csrc/gemm_nt.hip in the order it tries them (the wide one in both tile widths: 16 x 16
     # tiles of 256 x 256, 64 x 4 tiles of 256 x 192 where 64 x 3 tiles of 256 do not fill the chip), and one accumulating call
     "csn_gemm_nt": [Stateless("csn_gemm_nt", "wide256", _gemm_nt("wide256", 4096, 4096, 128, BF16, BF16)),
                     Stateless("csn_gemm_nt", "wide192", _gemm_nt("wide192", 16384, 768, 128, BF16, BF16)),

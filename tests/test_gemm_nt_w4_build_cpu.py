@@ -1,4 +1,4 @@
-"""CPU: what the build says about the four-wave 256 x 192 kernel (gemm_nt_w4_kernel, csrc/gemm.hip) -- the compiler's
+"""CPU: what the build says about the four-wave 256 x 192 kernel (gemm_nt_w4_kernel, csrc/gemm_nt.hip) -- the compiler's
 resource remarks kept next to the object, the LDS the launcher asks for -- and the launcher's rule for operands outside
 the kernel's 32-bit offset window.  Two workgroups per CU need at most 256 registers per lane at two waves per SIMD,
 no scratch, and at most half of the CU's 160 KB of LDS each."""
@@ -10,7 +10,7 @@ import pytest
 from cerebralsignalnetworks_amd import cabi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-RES = os.path.join(ROOT, "build", "csrc", "gemm.res")
+RES = os.path.join(ROOT, "build", "csrc", "gemm_nt.res")
 
 
 def _kernels(text, name):
@@ -36,7 +36,7 @@ def test_parser_reads_a_resource_block():
     assert _kernels(text, "nothing") == {}
 
 
-@pytest.mark.skipif(not os.path.exists(RES), reason="no in-tree build: build/csrc/gemm.res is absent")
+@pytest.mark.skipif(not os.path.exists(RES), reason="no in-tree build: build/csrc/gemm_nt.res is absent")
 def test_both_instantiations_fit_two_workgroups_per_cu():
     with open(RES) as f:
         kernels = _kernels(f.read(), "gemm_nt_w4_kernel")

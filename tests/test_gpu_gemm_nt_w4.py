@@ -1,4 +1,4 @@
-"""The four-wave 256 x 192 input-projection kernel (gemm_nt_w4_kernel in csrc/gemm.hip, the default wherever the 8-wave
+"""The four-wave 256 x 192 input-projection kernel (gemm_nt_w4_kernel in csrc/gemm_nt.hip, the default wherever the 8-wave
 gemm_nt_wide_kernel<.., 192> ran): a ring that wraps, clamped and skipped rows in both wave rows, a last row tile of one
 row, an odd number of 64-column blocks, two workgroups on every CU, the LSTM's aspect.
 

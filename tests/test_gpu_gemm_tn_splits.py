@@ -1,4 +1,4 @@
-"""The weight-gradient GEMM (csn_gemm_tn and the LSTM plans, launch_gemm_tn_slabs in csrc/gemm.hip) where rounding the
+"""The weight-gradient GEMM (csn_gemm_tn and the LSTM plans, launch_gemm_tn_slabs in csrc/gemm_tn.hip) where rounding the
 rows per K split up leaves the last splits SHORT -- 64 / 128 / 192 rows, i.e. 2 / 4 / 6 ring stages against a prefetch
 distance of 3, one row, 48 rows -- or EMPTY, in every kernel that has code for it.
 

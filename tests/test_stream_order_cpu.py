@@ -219,7 +219,88 @@ def test_gemm_route_mirrors_name_the_routes_of_the_cases():
                                              (256, 1024, 256, torch.bfloat16), (130, 132, 64, torch.bfloat16),
                                              (70, 132, 40, torch.bfloat16), (33, 20, 7, torch.float32))]
     assert routes == ["wide256", "wide192", "tile256x128", "dma", "bf16", "generic"]
-    # the two shapes csrc/gemm.hip quotes: 16 x 32 tiles of 192 fill two rounds, 128 tiles of 192 do not fill one
+    # the two shapes csrc/gemm_nt.hip quotes: 16 x 32 tiles of 192 fill two rounds, 128 tiles of 192 do not fill one
     assert so.gemm_nt_route(8192, 3072, 768, torch.bfloat16) == "wide192"
     assert so.gemm_nt_route(8192, 768, 3072, torch.bfloat16) == "dma"
     assert [so.gemm_tn_route(136, 72, 600), so.gemm_tn_route(256, 256, 8192), so.gemm_tn_route(256, 120, 8192)] == ["tile128", "tile256", "tile128"]
+
+
+_ROUTE_SWITCHES = ("CSN_GEMM_GENERIC", "CSN_GEMM_NO_DMA", "CSN_GEMM_NO_256", "CSN_GEMM_NO_192", "CSN_NT_NO_W4",
+                   "CSN_TN_NO_STAGGER", "CSN_TN_STAGES", "CSN_TN_NO_TR")
+_SWEEP = [(M, N, K) for M in (8, 136, 255, 256, 264, 4088, 4096, 8192, 16384)
+          for N in (4, 72, 76, 128, 192, 768, 1024, 1028, 3072, 4096) for K in (7, 40, 64, 72, 128, 256, 768, 8192)]
+
+
+def _only(monkeypatch, env):
+    for name in _ROUTE_SWITCHES:
+        monkeypatch.delenv(name, raising=False)
+    for name, value in env.items():
+        monkeypatch.setenv(name, value)
+
+
+def test_gemm_nt_route_mirror_agrees_with_the_library(monkeypatch):
+    """The hand-written mirror so.gemm_nt_route against what the library says it launches (cabi.gemm_nt_route), over a
+    sweep of shapes, both operand types, every single switch, and misaligned operands.  The mirror calls both forms of the
+    192 tile "wide192"; which form it is follows from CSN_NT_NO_W4 alone here (every swept operand is far below the
+    4 GiB window of the four-wave kernel)."""
+    from cerebralsignalnetworks_amd import cabi
+    envs = [({}, {}), ({"CSN_GEMM_GENERIC": "1"}, {"generic": True}), ({"CSN_GEMM_NO_DMA": "1"}, {"no_dma": True}),
+            ({"CSN_GEMM_NO_256": "1"}, {"no_256": True}), ({"CSN_GEMM_NO_192": "1"}, {"no_192": True}),
+            ({"CSN_NT_NO_W4": "1"}, {"no_w4": True})]
+    for env, kw in envs:
+        _only(monkeypatch, env)
+        for aligned in ((True, False) if not env else (True,)):
+            for dtype in (torch.bfloat16, torch.float32):
+                for (M, N, K) in _SWEEP:
+                    want = so.gemm_nt_route(M, N, K, dtype, aligned16=aligned, **kw)
+                    if want == "wide192" and not kw.get("no_w4"):
+                        want = "wide192w4"
+                    assert cabi.gemm_nt_route(M, N, K, dtype, aligned) == want, (M, N, K, dtype, aligned, env)
+    # the routes the parent's ladder gives, read line by line
+    _only(monkeypatch, {})
+    table = [((8192, 3072, 768), "wide192w4"), ((8192, 4096, 1024), "wide256"), ((8192, 768, 3072), "dma"),
+             ((8192, 1024, 768), "tile256x128"), ((4088, 3072, 128), "wide192w4"), ((4088, 4096, 128), "wide256"),
+             ((264, 1028, 256), "tile256x128"), ((136, 76, 64), "dma"), ((136, 76, 72), "bf16"), ((136, 76, 70), "generic")]
+    for shape, want in table:
+        assert cabi.gemm_nt_route(*shape) == want, shape
+    _only(monkeypatch, {"CSN_NT_NO_W4": "1"})
+    assert cabi.gemm_nt_route(8192, 3072, 768) == "wide192"
+
+
+def _tn_kernel_behind(route, N, colsum, no_stagger=False, stages=4, no_tr=False):
+    """The kernel behind a TN route, as the ladder of launch_gemm_tn_slabs chose it before there was a route function."""
+    if route == "tile256":
+        if not no_stagger and stages == 4:
+            return "w4-128" if N <= 128 else "w4-256"
+        if colsum:
+            return "ring4"
+        return {3: "ring3", 5: "ring5"}.get(stages, "ring4")
+    return {"tile128": "tn128-notr" if no_tr else "tn128", "generic": "generic"}[route]
+
+
+def test_gemm_tn_route_mirrors_agree_with_the_library(monkeypatch):
+    """so.gemm_tn_route and gemm_tn_splits.regime against cabi.gemm_tn_route over the same sweep, with and without
+    column sums, under every single switch of the 256-tile kernels, and for misaligned operands."""
+    import gemm_tn_splits as sp
+    from cerebralsignalnetworks_amd import cabi
+    envs = [({}, {}, {}), ({"CSN_GEMM_NO_256": "1"}, {"no_256": True}, {}),
+            ({"CSN_TN_NO_STAGGER": "1"}, {}, {"no_stagger": True}), ({"CSN_TN_STAGES": "3"}, {}, {"stages": 3}),
+            ({"CSN_TN_STAGES": "5"}, {}, {"stages": 5}), ({"CSN_TN_NO_TR": "1"}, {}, {"no_tr": True})]
+    family = {"tn256": "tile256", "tn128": "tile128", "f32_128": "generic", "generic": "generic"}
+    for env, route_kw, kernel_kw in envs:
+        _only(monkeypatch, env)
+        for aligned in ((True, False) if not env else (True,)):
+            for bf16 in (True, False):
+                for (M, N, K) in _SWEEP:
+                    if bf16 and aligned and M % 8 == 0 and N % 8 == 0:
+                        route = so.gemm_tn_route(M, N, K, **route_kw)
+                        assert family[sp.regime(M, N, K, True, **route_kw).kernel] == route, (M, N, K, env)
+                    elif aligned:
+                        route = family[sp.regime(M, N, K, bf16, **route_kw).kernel]
+                        assert route == "generic", (M, N, K, bf16)
+                    else:
+                        route = "generic"                   # misaligned operands: neither bf16 kernel family
+                    for colsum in (False, True):
+                        want = (route, _tn_kernel_behind(route, N, colsum, **kernel_kw))
+                        got = cabi.gemm_tn_route(M, N, K, torch.bfloat16 if bf16 else torch.float32, aligned, colsum)
+                        assert got == want, (M, N, K, bf16, aligned, colsum, env)
