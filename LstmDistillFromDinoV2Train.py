@@ -93,6 +93,9 @@ def build_parser(flavour=PERILS):
     p.add_argument('--bidirectional', action='store_true',
                    help='nn.LSTM(bidirectional=True): the encoder runs in both directions (BiLSTM) and fc takes the final '
                         'state of each, 2 * hidden_size features (not with --lstm_dropout)')
+    p.add_argument('--resident_lstm', action='store_true',
+                   help='hidden_size <= 128: the LSTM runs the steps of a chunk inside one launch per layer, W_hh in '
+                        'registers (CSN_LSTM_RESIDENT plans), with the bits of the per-step cell kernels')
     p.add_argument('--output_size', type=int, default=384)
     p.add_argument('--loss', type=str, default=flavour.loss, choices=["featdist", "cosine", "kd", "barlow"])
     p.add_argument('--optimizer', type=str, default=flavour.optimizer, choices=["rmsprop", "adamw", "adam", "lars"])
@@ -203,7 +206,7 @@ def main(argv=None, flavour=PERILS):
     include_top = FLAGS.loss == "featdist"
     model = Model(input_size=C, lstm_size=FLAGS.hidden_size, lstm_layers=FLAGS.lstm_layers,
                   output_size=features_length, include_top=include_top, compute_dtype=dtype,
-                  dropout=FLAGS.lstm_dropout, bidirectional=FLAGS.bidirectional).to(device)
+                  dropout=FLAGS.lstm_dropout, bidirectional=FLAGS.bidirectional, resident=FLAGS.resident_lstm).to(device)
     if flavour.name == "spampinato":
         if os.path.exists(FLAGS.custom_model_weights):           # :369-371: resume only if the file is there, strict keys
             model.load_state_dict(torch.load(FLAGS.custom_model_weights, map_location="cpu", weights_only=True))

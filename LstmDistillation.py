@@ -57,6 +57,9 @@ def build_parser():
     p.add_argument('--lstm_dropout', type=float, default=0.0,
                    help='nn.LSTM(dropout=p) between the LSTM layers of the STUDENT (0 = off); the teacher, which is never '
                         'trained, runs without it, like the stochastic depth of the reference\'s ViT teacher')
+    p.add_argument('--resident_lstm', action='store_true',
+                   help='embed_dim <= 128: student and teacher LSTMs run the steps of a chunk inside one launch per layer, '
+                        'W_hh in registers (CSN_LSTM_RESIDENT plans), with the bits of the per-step cell kernels')
     p.add_argument('--dtype', type=str, default="bf16", choices=["bf16", "f32"])
     p.add_argument('--time_low', type=int, default=0)
     p.add_argument('--time_high', type=int, default=495)
@@ -105,7 +108,8 @@ def main(argv=None):
     dtype = torch.bfloat16 if FLAGS.dtype == "bf16" else torch.float32
     def make(dropout=0.0):
         backbone = Model(input_size=C, lstm_size=FLAGS.embed_dim, lstm_layers=FLAGS.lstm_layers,
-                         output_size=FLAGS.embed_dim, include_top=False, compute_dtype=dtype, dropout=dropout)
+                         output_size=FLAGS.embed_dim, include_top=False, compute_dtype=dtype, dropout=dropout,
+                         resident=FLAGS.resident_lstm)
         return backbone
     student = MultiCropWrapper(make(FLAGS.lstm_dropout), DINOHead(FLAGS.embed_dim, FLAGS.out_dim, FLAGS.use_bn_in_head,
                                                 FLAGS.norm_last_layer)).to(device)

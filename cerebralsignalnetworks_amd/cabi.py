@@ -19,6 +19,8 @@ ABI_VERSION = 6
 LSTM_STATE = 0x100      # csn_lstm_plan_create flag CSN_LSTM_STATE (include/csn_hip.h)
 LSTM_DROPOUT = 0x200    # csn_lstm_plan_create flag CSN_LSTM_DROPOUT (include/csn_hip.h)
 LSTM_REVERSE = 0x400    # csn_lstm_plan_create flag CSN_LSTM_REVERSE (include/csn_hip.h)
+LSTM_RESIDENT = 0x800   # csn_lstm_plan_create flag CSN_LSTM_RESIDENT: the CU-resident recurrence, H <= 128 (path 5)
+RESIDENT_MAX_H = 128
 GRAD_OVERWRITE, GRAD_ACCUMULATE = 0, 1      # csn_lstm_plan_set_grad_mode (include/csn_hip.h)
 SEG_DECAYED, SEG_SCALED = 1, 2              # per-segment flags of csn_flat_segments_prepare (include/csn_hip.h)
 
@@ -377,16 +379,20 @@ class LstmPlan:
     -- all per plan, the library has no global state) + one workspace; forward()/backward() enqueue on the
     current stream."""
 
-    def __init__(self, B, T, I, H, L, dtype, device, training=True, state=False, dropout=False, reverse=False):
+    def __init__(self, B, T, I, H, L, dtype, device, training=True, state=False, dropout=False, reverse=False,
+                 resident=False):
         """state=True: a CSN_LSTM_STATE plan, which takes the state keywords of forward() / backward() (and runs the
         per-step cell kernels, path 0 or 1).  dropout=True: a CSN_LSTM_DROPOUT plan, whose workspace holds the dropped
         layer outputs and which takes set_dropout(p > 0).  reverse=True: a CSN_LSTM_REVERSE plan, which walks every
-        row backwards in time from its own last valid step (the reverse direction of a bidirectional layer)."""
+        row backwards in time from its own last valid step (the reverse direction of a bidirectional layer).
+        resident=True: a CSN_LSTM_RESIDENT plan (H <= 128), which runs the steps of a chunk inside one launch per layer
+        (path 5) with the workspace and, bit for bit, the results of the per-step cells (path 0)."""
         self.desc = LstmDesc(B, T, I, H, L, _dt(dtype))
         self.training = bool(training)
         self.state = bool(state)
         self.dropout = bool(dropout)
         self.reverse = bool(reverse)
+        self.resident = bool(resident)
         self._io = (0, 0, False)
         self._views = None          # (src_rows, src_T) while input windows are set (set_views)
         self.device = torch.device(device)
@@ -394,7 +400,8 @@ class LstmPlan:
         handle = _c_void_p()
         with torch.cuda.device(self.device):
             _check(lib.csn_lstm_plan_create(ctypes.byref(self.desc), int(self.training) | (LSTM_STATE if self.state else 0) |
-                                            (LSTM_DROPOUT if self.dropout else 0) | (LSTM_REVERSE if self.reverse else 0),
+                                            (LSTM_DROPOUT if self.dropout else 0) | (LSTM_REVERSE if self.reverse else 0) |
+                                            (LSTM_RESIDENT if self.resident else 0),
                                             ctypes.byref(handle)))
         self._plan = handle
         nbytes = lib.csn_lstm_plan_workspace_bytes(self._plan)
@@ -413,11 +420,12 @@ class LstmPlan:
     def key(self):
         d = self.desc
         return ((d.B, d.T, d.I, d.H, d.L, d.dtype, self.training) + ((True,) if self.state else ()) +
-                (("dropout plan",) if self.dropout else ()) + (("reverse plan",) if self.reverse else ()))
+                (("dropout plan",) if self.dropout else ()) + (("reverse plan",) if self.reverse else ()) +
+                (("resident plan",) if getattr(self, "resident", False) else ()))
 
     def path(self):
         """0 generic cells, 1 per-diagonal bf16 launches, 2 weight-stationary forward, 3 + weight-stationary backward, 4 the
-        exact-float32 path's weight-stationary recurrence."""
+        exact-float32 path's weight-stationary recurrence, 5 the CU-resident recurrence of a resident=True plan."""
         return load().csn_lstm_plan_path(self._plan)
 
     def kernel_names(self):

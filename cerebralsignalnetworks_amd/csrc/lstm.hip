@@ -2,7 +2,7 @@
 // Replaces nn.LSTM(batch_first=True).forward / autograd backward as called at
 // /root/reference/LSTMDistill.py:118,132 and /root/reference/LSTMDistillRetreival.py:91,103.
 //
-// Five paths share the C entry points (csn_lstm_plan_path; make_layout decides at plan creation):
+// Six paths share the C entry points (csn_lstm_plan_path; make_layout decides at plan creation):
 //
 //  0  generic (forward_v1 / backward_v1): float32, or bf16 shapes the fast paths do not cover; cell kernels of
 //     lstm_cell.hip, the layers as a wavefront of one launch per diagonal, lag = 1 chunk, everything on the caller's stream.
@@ -21,6 +21,9 @@
 //  3  path 2 with the weight-stationary backward (backward_persist: lstm_bwd_persist.hip, one launch per chunk diagonal,
 //     the input-gradient GEMM inside the next launch) where its grouped form applies (bwd_grouped), else backward_il.
 //  4  exact float32, weight-stationary (forward_f32p / backward_f32p: lstm_f32_persist.hip), layer after layer.
+//  5  CU-resident recurrence (forward_resident / backward_resident: lstm_resident.hip), opt-in with CSN_LSTM_RESIDENT,
+//     H <= 128, both dtypes: path 0's workspace and host flow with the step loop of a chunk inside the kernel -- one
+//     launch per CHUNK diagonal, everything on the caller's stream, every result bit for bit that of path 0.
 //
 // Each path is one function over the per-call context (struct Call) and the caller's pointers (FwdArgs / BwdArgs); what
 // more than one of them does -- slot 0, weight gradients, chunk GEMMs, dx out, the profile epilogue -- is one helper each.
@@ -40,6 +43,7 @@
 #include "lstm_cell_common.h"
 #include "lstm_dropout.h"
 #include "lstm_f32_persist.h"
+#include "lstm_resident.h"
 
 namespace csn {
 
@@ -175,6 +179,21 @@ static WsLayout make_layout(const csnLstmDesc& d, int training, bool dropout, co
   for (int l = 0; dropout && l + 1 < d.L; ++l) w.layer[l].h_drop = take(TB * H * es);
   w.total = off;
   return w;
+}
+
+// the bits of `training` that are not "training"
+static const int kPlanBits = CSN_LSTM_STATE | CSN_LSTM_DROPOUT | CSN_LSTM_REVERSE | CSN_LSTM_RESIDENT;
+
+// CSN_LSTM_RESIDENT: a whole layer's W_hh has to fit the registers of one workgroup
+static int check_resident(const char* fn, const csnLstmDesc* d, int training) {
+  if ((training & CSN_LSTM_RESIDENT) && !resident_supported(d->H))
+    return fail(CSN_ERR_UNSUPPORTED, "%s: CSN_LSTM_RESIDENT takes H <= %d, not H=%d", fn, kResidentMaxH, d->H);
+  return CSN_OK;
+}
+// ... and the plan is laid out as path 0 lays it out (il = persist = f32_persist = false)
+static void resident_options(Options& opt) {
+  opt.cell_v1 = true;
+  opt.no_persist = true;
 }
 
 static int check_desc(const char* fn, const csnLstmDesc* d) {
@@ -498,6 +517,7 @@ struct csnLstmPlan {
   void* grad_cb_user = nullptr;
   int grad_accumulate = 0;               // csn_lstm_plan_set_grad_mode: dw / db are added to, not overwritten
   int reverse = 0;                       // created with CSN_LSTM_REVERSE: the layout passes walk every row backwards in time
+  int resident = 0;                      // created with CSN_LSTM_RESIDENT: path 0's layout, the recurrence of lstm_resident.hip
   int64_t y_pitch = 0, dy_pitch = 0;     // csn_lstm_plan_set_io: elements per (b, t) row of y_all / dy_all, 0 = dense (H)
   int dx_add = 0;                        // csn_lstm_plan_set_io: dx is added to over the valid steps, not overwritten
   // csn_lstm_plan_set_lengths (empty = every row is T): the lengths of the next calls and the longest of them.  What a
@@ -526,12 +546,14 @@ typedef csnLstmPlan Plan;
 extern "C" int csn_lstm_plan_create(const csnLstmDesc* d, int training, csnLstmPlan** out) {
   if (int rc = check_desc("csn_lstm_plan_create", d)) return rc;
   CSN_REQUIRE(out != nullptr, "csn_lstm_plan_create: null output pointer");
+  if (int rc = check_resident("csn_lstm_plan_create", d, training)) return rc;
   Plan* P = new Plan();
   P->d = *d;
   P->state = (training & CSN_LSTM_STATE) != 0;
   P->dropout = (training & CSN_LSTM_DROPOUT) != 0;
   P->reverse = (training & CSN_LSTM_REVERSE) != 0;
-  P->training = (training & ~(CSN_LSTM_STATE | CSN_LSTM_DROPOUT | CSN_LSTM_REVERSE)) != 0;
+  P->resident = (training & CSN_LSTM_RESIDENT) != 0;
+  P->training = (training & ~kPlanBits) != 0;
   if (hipGetDevice(&P->device) != hipSuccess) {
     delete P;
     return fail(CSN_ERR_HIP, "csn_lstm_plan_create: hipGetDevice failed");
@@ -539,6 +561,7 @@ extern "C" int csn_lstm_plan_create(const csnLstmDesc* d, int training, csnLstmP
   P->opt = options_from_env();
   // (the exact-float32 weight-stationary path (4) takes no state: a float32 state plan runs the per-step cells)
   if (P->state && d->dtype == CSN_F32) P->opt.no_persist = true;
+  if (P->resident) resident_options(P->opt);
   {
     // the weight-stationary kernels address the steps of ONE launch with 32-bit byte offsets from the launch's base
     // (lstm_fwd_ns.hip; launch_fwd_ns refuses more): a CSN_LSTM_CHUNK that large is clamped here, not left to wrap
@@ -578,6 +601,7 @@ extern "C" size_t csn_lstm_plan_workspace_bytes(const csnLstmPlan* P) { return P
 
 extern "C" int csn_lstm_plan_path(const csnLstmPlan* P) {
   if (P == nullptr) return -1;
+  if (P->resident) return 5;
   return P->w.f32_persist ? 4 : (P->w.persist_bwd ? 3 : (P->w.persist ? 2 : (P->w.il ? 1 : 0)));
 }
 
@@ -599,6 +623,7 @@ static bool bwd_grouped(const csnLstmPlan* P, int T) {
 extern "C" const char* csn_lstm_plan_kernel_name(const csnLstmPlan* P, int which) {
   if (P == nullptr) return nullptr;
   const bool ks = (P->d.dtype == CSN_F32 ? P->d.H % 128 == 0 : P->d.H % 256 == 0);      // K-split cell kernels (lstm_cell.hip)
+  if (P->resident) return which == 0 ? "lstm_resident_fwd_kernel" : (which == 1 ? "lstm_resident_bwd_kernel" : nullptr);
   if (P->w.f32_persist) return which == 0 ? "lstm_fwd_f32_persist_kernel" : (which == 1 ? "lstm_bwd_f32_persist_kernel" : nullptr);
   if (which == 0) {
     if (P->w.fwd_ns) return "lstm_fwd_ns_kernel";
@@ -898,9 +923,11 @@ extern "C" int csn_lstm_status_read(const csnLstmPlan* P, const void* workspace,
 
 extern "C" size_t csn_lstm_workspace_bytes(const csnLstmDesc* d, int training) {
   if (check_desc("csn_lstm_workspace_bytes", d) != CSN_OK) return 0;
+  if (check_resident("csn_lstm_workspace_bytes", d, training) != CSN_OK) return 0;
   Options opt = options_from_env();
   if ((training & CSN_LSTM_STATE) && d->dtype == CSN_F32) opt.no_persist = true;
-  return make_layout(*d, (training & ~(CSN_LSTM_STATE | CSN_LSTM_DROPOUT | CSN_LSTM_REVERSE)) != 0, (training & CSN_LSTM_DROPOUT) != 0, opt).total;
+  if (training & CSN_LSTM_RESIDENT) resident_options(opt);
+  return make_layout(*d, (training & ~kPlanBits) != 0, (training & CSN_LSTM_DROPOUT) != 0, opt).total;
 }
 
 // C[M,N] = A[K,M]^T B[K,N] through the split-K slabs + their fixed-order reduction (the body of csn_gemm_tn)
@@ -1214,6 +1241,107 @@ static int backward_v1(Call& C, const BwdArgs& A) {
       if ((rc = dx_chunk_gemm(C, l, r / C.Cz, A.dh_n, st))) return rc;
     }
   }
+  for (int l = NL - 1; l >= 0; --l) {
+    if ((rc = weight_grads_rm(C, A, l, true))) return rc;
+    C.P.grads_ready(l);
+  }
+  if (A.dx) return dx_out(C, A.dx, st);
+  return CSN_OK;
+}
+
+// =============================================================================================
+// path 5: CU-resident recurrence, H <= 128 (lstm_resident.hip; CSN_LSTM_RESIDENT plans)
+// =============================================================================================
+// forward_v1 / backward_v1 with the step loop of a chunk moved into the kernel: the wavefront runs over CHUNKS, diagonal
+// d runs layer l at chunk d - l in one launch (up to four (layer, chunk) problems, a second launch beyond), and the same
+// chunk GEMMs follow it.  ceil(T / Cz) + L - 1 recurrence launches per pass for L <= 4, against T + Cz (L - 1).
+static int forward_resident(Call& C, const FwdArgs& A) {
+  const WsLayout& w = C.w;
+  char* ws = C.ws;
+  hipStream_t st = C.st;
+  const int B = C.B, T = C.T, H = C.H, dt = C.dt, NL = C.NL;
+  int rc;
+  C.P.half_launches[0] = 0;
+  if ((rc = prep_row_major(C, A))) return rc;
+  if ((rc = gemm_nt(ws + w.x_c, ws + w.layer[0].wih, (const float*)(ws + w.layer[0].bias), ws + w.layer[0].xproj, C.TB, C.G,
+                    C.d.I, dt, CSN_F32, 0, st, C.P.opt)))
+    return rc;
+  if ((rc = prof_mark(C.P.prof, 0, st))) return rc;
+  const int nch = (T + C.Cz - 1) / C.Cz, D = nch + NL - 1;
+  int n_launch = 0;
+  for (int dg = 0; dg < D; ++dg) {
+    ResFwdBatch b{};
+    int np = 0;
+    for (int l = 0; l < NL; ++l) {
+      const int c = dg - l;
+      if (c < 0 || c >= nch) continue;
+      const LayerWs& L = w.layer[l];
+      const Chunk k = chunk_at(C, c);
+      if (np == 4) {       // (more than 4 layers on one diagonal: a second launch, the problems are independent)
+        if ((rc = launch_resident_fwd(b, np, B, H, dt, st))) return rc;
+        ++n_launch;
+        np = 0;
+      }
+      b.p[np++] = ResFwdOne{ws + L.whh, (const float*)(ws + L.xproj), (float*)(ws + L.c_all), ws + L.h_all,
+                            C.P.training ? ws + L.gates : nullptr, k.t0, k.nsteps};
+    }
+    if (np > 0) {
+      if ((rc = launch_resident_fwd(b, np, B, H, dt, st))) return rc;
+      ++n_launch;
+    }
+    // a layer that just finished a chunk feeds the next layer's input projection
+    for (int l = 0; l + 1 < NL; ++l) {
+      const int c = dg - l;
+      if (c < 0 || c >= nch) continue;
+      if ((rc = xproj_chunk_gemm(C, l, c, st))) return rc;
+    }
+  }
+  return prof_end(C, 0, n_launch, T * NL);
+}
+
+static int backward_resident(Call& C, const BwdArgs& A) {
+  const WsLayout& w = C.w;
+  char* ws = C.ws;
+  hipStream_t st = C.st;
+  const int B = C.B, T = C.T, H = C.H, dt = C.dt, NL = C.NL;
+  int rc;
+  C.P.dgates_copies = 0;
+  C.P.half_launches[1] = 0;
+  for (int l = 0; l < NL; ++l)
+    if ((rc = seed_dc_carry(C, l, A.dc_n, false))) return rc;
+  if ((rc = prof_mark(C.P.prof, 2, st))) return rc;
+  // diagonal d: layer l at reverse chunk d - (L - 1 - l) (reverse chunk c: the steps [t_hi - nsteps + 1, t_hi], t_hi = T - 1 - t0)
+  const int nch = (T + C.Cz - 1) / C.Cz, D = nch + NL - 1;
+  int n_launch = 0;
+  for (int dg = 0; dg < D; ++dg) {
+    ResBwdBatch b{};
+    int np = 0;
+    for (int l = NL - 1; l >= 0; --l) {
+      const int c = dg - (NL - 1 - l);
+      if (c < 0 || c >= nch) continue;
+      const LayerWs& L = w.layer[l];
+      const Chunk k = chunk_at(C, c);
+      const bool top = (l == NL - 1);
+      if (np == 4) {
+        if ((rc = launch_resident_bwd(b, np, B, T, H, dt, C.dlen, st))) return rc;
+        ++n_launch;
+        np = 0;
+      }
+      b.p[np++] = ResBwdOne{ws + L.whht, top ? A.dy_tm : (const float*)(ws + w.layer[l + 1].dx), top ? A.dy_last : nullptr,
+                            ws + L.gates, (const float*)(ws + L.c_all), (float*)(ws + L.dc_carry), ws + L.dgates,
+                            T - 1 - k.t0, k.nsteps};
+    }
+    if (np > 0) {
+      if ((rc = launch_resident_bwd(b, np, B, T, H, dt, C.dlen, st))) return rc;
+      ++n_launch;
+    }
+    for (int l = NL - 1; l >= 1; --l) {
+      const int c = dg - (NL - 1 - l);
+      if (c < 0 || c >= nch) continue;
+      if ((rc = dx_chunk_gemm(C, l, c, A.dh_n, st))) return rc;
+    }
+  }
+  if ((rc = prof_end(C, 1, n_launch, T * NL))) return rc;
   for (int l = NL - 1; l >= 0; --l) {
     if ((rc = weight_grads_rm(C, A, l, true))) return rc;
     C.P.grads_ready(l);
@@ -1886,12 +2014,14 @@ static int backward_persist(Call& C, const BwdArgs& A) {
 // the path of a call (csn_lstm_plan_path: the forward of paths 2 and 3 is one, the backward of path 3 falls back to that of
 // paths 1 and 2 where its grouped form does not apply)
 static int run_forward(Call& C, const FwdArgs& A) {
+  if (C.P.resident) return forward_resident(C, A);
   if (C.w.persist) return forward_persist(C, A);
   if (C.w.il) return forward_il(C, A);
   if (C.w.f32_persist) return forward_f32p(C, A);
   return forward_v1(C, A);
 }
 static int run_backward(Call& C, const BwdArgs& A) {
+  if (C.P.resident) return backward_resident(C, A);
   if (bwd_grouped(&C.P, C.T)) return backward_persist(C, A);
   if (C.w.il) return backward_il(C, A);
   if (C.w.f32_persist) return backward_f32p(C, A);

@@ -23,32 +23,8 @@
 
 namespace csn {
 
-template <typename T> struct Frag;
-template <> struct Frag<bf16_t> {
-  typedef bf16x8 type;
-  static constexpr int kStep = 32;  // k covered by one fragment load (8 per lane x 4 lane groups)
-  static __device__ __forceinline__ type load(const bf16_t* row_ptr, int k0, int lane) {
-    return *reinterpret_cast<const bf16x8*>(row_ptr + k0 + 8 * (lane >> 4));
-  }
-  static __device__ __forceinline__ type zero() { return (bf16x8){0, 0, 0, 0, 0, 0, 0, 0}; }
-  static __device__ __forceinline__ f32x4 mma(const type& a, const type& b, f32x4 acc) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
-  }
-};
-template <> struct Frag<float> {
-  typedef f32x4 type;
-  static constexpr int kStep = 16;  // 4 per lane x 4 lane groups
-  static __device__ __forceinline__ type load(const float* row_ptr, int k0, int lane) {
-    return *reinterpret_cast<const f32x4*>(row_ptr + k0 + 4 * (lane >> 4));
-  }
-  static __device__ __forceinline__ type zero() { return (f32x4){0.f, 0.f, 0.f, 0.f}; }
-  static __device__ __forceinline__ f32x4 mma(const type& a, const type& b, f32x4 acc) {
-    // MFMA jj contracts k = k0 + 4*(lane>>4) + jj over the 4 lane groups; A and B use the same map.
-#pragma unroll
-    for (int jj = 0; jj < 4; ++jj) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[jj], b[jj], acc, 0, 0, 0);
-    return acc;
-  }
-};
+// (Frag<T>, the MFMA operand fragments, and the per-element cell math cell_fwd_point / cell_bwd_point live in
+// lstm_cell_common.h: the CU-resident recurrence of lstm_resident.hip uses the same ones)
 
 #define CSN_CELL_FWD_BIND                                                                                    \
   const CellFwdOne& q_ = batch.p[blockIdx.z];                                                                \
@@ -110,15 +86,7 @@ lstm_cell_fwd_kernel(CellFwdBatch batch, int B, int H) {
   float cp[4] = {0.f, 0.f, 0.f, 0.f};
   if (c_prev != nullptr) Vec4<float>::load(c_prev + (int64_t)mrow * H + ub, cp);
   float gi[4], gf[4], gg[4], go[4], cn[4], hn[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    gi[r] = sigmoid_f32(pre[0][r]);
-    gf[r] = sigmoid_f32(pre[1][r]);
-    gg[r] = tanh_f32(pre[2][r]);
-    go[r] = sigmoid_f32(pre[3][r]);
-    cn[r] = gf[r] * cp[r] + gi[r] * gg[r];
-    hn[r] = go[r] * tanh_f32(cn[r]);
-  }
+  cell_fwd_point(pre, cp, gi, gf, gg, go, cn, hn);
   if (gates_out != nullptr) {
     T* gp = gates_out + (int64_t)mrow * 4 * H + ub;
     Vec4<T>::store(gp, gi);
@@ -176,25 +144,9 @@ lstm_cell_bwd_kernel(CellBwdBatch batch, int B, int H, typename CellMaskArg<MASK
   if (c_prev != nullptr) Vec4<float>::load(c_prev + (int64_t)mrow * H + ub, cp);
   Vec4<float>::load(dc_carry + (int64_t)mrow * H + ub, dcn);
   float dai[4], daf[4], dag[4], dao[4], dcarry[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const float tc = tanh_f32(cc[r]);
-    const float d_o = dh[r] * tc;
-    const float dc = dh[r] * go[r] * (1.0f - tc * tc) + dcn[r];
-    dai[r] = dc * gg[r] * gi[r] * (1.0f - gi[r]);
-    daf[r] = dc * cp[r] * gf[r] * (1.0f - gf[r]);
-    dag[r] = dc * gi[r] * (1.0f - gg[r] * gg[r]);
-    dao[r] = d_o * go[r] * (1.0f - go[r]);
-    dcarry[r] = dc * gf[r];
-  }
+  cell_bwd_point(dh, gi, gf, gg, go, cc, cp, dcn, dai, daf, dag, dao, dcarry);
   if constexpr (MASK) {
-    if (mask.t[blockIdx.z] >= mask.lengths[mrow]) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        dai[r] = daf[r] = dag[r] = dao[r] = 0.f;
-        dcarry[r] = dcn[r];
-      }
-    }
+    if (mask.t[blockIdx.z] >= mask.lengths[mrow]) cell_bwd_dead(dcn, dai, daf, dag, dao, dcarry);
   }
   T* op = dg_out + (int64_t)mrow * K + ub;
   Vec4<T>::store(op, dai);
@@ -230,15 +182,7 @@ __device__ __forceinline__ void cell_fwd_epilogue(f32x4 (&acc)[4], int mrow, int
   float cp[4] = {0.f, 0.f, 0.f, 0.f};
   if (c_prev != nullptr) Vec4<float>::load(c_prev + (int64_t)mrow * H + ub, cp);
   float gi[4], gf[4], gg[4], go[4], cn[4], hn[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    gi[r] = sigmoid_f32(pre[0][r]);
-    gf[r] = sigmoid_f32(pre[1][r]);
-    gg[r] = tanh_f32(pre[2][r]);
-    go[r] = sigmoid_f32(pre[3][r]);
-    cn[r] = gf[r] * cp[r] + gi[r] * gg[r];
-    hn[r] = go[r] * tanh_f32(cn[r]);
-  }
+  cell_fwd_point(pre, cp, gi, gf, gg, go, cn, hn);
   if (gates_out != nullptr) {
     T* gp = gates_out + (int64_t)mrow * 4 * H + ub;
     Vec4<T>::store(gp, gi);
@@ -446,25 +390,9 @@ lstm_cell_bwd_ks_kernel(CellBwdBatch batch, int B, int H, typename CellMaskArg<M
   if (c_prev != nullptr) Vec4<float>::load(c_prev + (int64_t)mrow * H + ub, cp);
   Vec4<float>::load(dc_carry + (int64_t)mrow * H + ub, dcn);
   float dai[4], daf[4], dag[4], dao[4], dcarry[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const float tc = tanh_f32(cc[r]);
-    const float d_o = dh[r] * tc;
-    const float dc = dh[r] * go[r] * (1.0f - tc * tc) + dcn[r];
-    dai[r] = dc * gg[r] * gi[r] * (1.0f - gi[r]);
-    daf[r] = dc * cp[r] * gf[r] * (1.0f - gf[r]);
-    dag[r] = dc * gi[r] * (1.0f - gg[r] * gg[r]);
-    dao[r] = d_o * go[r] * (1.0f - go[r]);
-    dcarry[r] = dc * gf[r];
-  }
+  cell_bwd_point(dh, gi, gf, gg, go, cc, cp, dcn, dai, daf, dag, dao, dcarry);
   if constexpr (MASK) {
-    if (mask.t[blockIdx.z] >= mask.lengths[mrow]) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        dai[r] = daf[r] = dag[r] = dao[r] = 0.f;
-        dcarry[r] = dcn[r];
-      }
-    }
+    if (mask.t[blockIdx.z] >= mask.lengths[mrow]) cell_bwd_dead(dcn, dai, daf, dag, dao, dcarry);
   }
   T* op = dg_out + (int64_t)mrow * K + ub;
   Vec4<T>::store(op, dai);

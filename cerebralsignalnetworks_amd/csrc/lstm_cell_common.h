@@ -55,6 +55,78 @@ template <> struct Vec4<bf16_t> {
 };
 
 
+// MFMA operand fragments of the generic cell kernels (lstm_cell.hip) and of the CU-resident recurrence
+// (lstm_resident.hip), k-contiguous per lane: W as the A operand, h / dgates as the B operand.
+template <typename T> struct Frag;
+template <> struct Frag<bf16_t> {
+  typedef bf16x8 type;
+  static constexpr int kStep = 32;  // k covered by one fragment load (8 per lane x 4 lane groups)
+  static constexpr int kLane = 8;   // k per lane
+  static __device__ __forceinline__ type load(const bf16_t* row_ptr, int k0, int lane) {
+    return *reinterpret_cast<const bf16x8*>(row_ptr + k0 + 8 * (lane >> 4));
+  }
+  static __device__ __forceinline__ type zero() { return (bf16x8){0, 0, 0, 0, 0, 0, 0, 0}; }
+  static __device__ __forceinline__ f32x4 mma(const type& a, const type& b, f32x4 acc) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
+  }
+};
+template <> struct Frag<float> {
+  typedef f32x4 type;
+  static constexpr int kStep = 16;  // 4 per lane x 4 lane groups
+  static constexpr int kLane = 4;
+  static __device__ __forceinline__ type load(const float* row_ptr, int k0, int lane) {
+    return *reinterpret_cast<const f32x4*>(row_ptr + k0 + 4 * (lane >> 4));
+  }
+  static __device__ __forceinline__ type zero() { return (f32x4){0.f, 0.f, 0.f, 0.f}; }
+  static __device__ __forceinline__ f32x4 mma(const type& a, const type& b, f32x4 acc) {
+    // MFMA jj contracts k = k0 + 4*(lane>>4) + jj over the 4 lane groups; A and B use the same map.
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[jj], b[jj], acc, 0, 0, 0);
+    return acc;
+  }
+};
+
+// The per-element cell math of those kernels, four consecutive units of one batch row per lane.  ONE definition for the
+// per-step cells and the resident recurrence: the two give the same bits because they evaluate the same expressions.
+// forward: pre[gate][r] = pre-activations (i, f, g, o), cp = c_{t-1}
+__device__ __forceinline__ void cell_fwd_point(const float (&pre)[4][4], const float (&cp)[4], float (&gi)[4], float (&gf)[4],
+                                               float (&gg)[4], float (&go)[4], float (&cn)[4], float (&hn)[4]) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    gi[r] = sigmoid_f32(pre[0][r]);
+    gf[r] = sigmoid_f32(pre[1][r]);
+    gg[r] = tanh_f32(pre[2][r]);
+    go[r] = sigmoid_f32(pre[3][r]);
+    cn[r] = gf[r] * cp[r] + gi[r] * gg[r];
+    hn[r] = go[r] * tanh_f32(cn[r]);
+  }
+}
+// backward: dh = gradient w.r.t. h_t, cc = c_t, cp = c_{t-1}, dcn = the carried dc; the pre-activation gradients and the new carry
+__device__ __forceinline__ void cell_bwd_point(const float (&dh)[4], const float (&gi)[4], const float (&gf)[4], const float (&gg)[4],
+                                               const float (&go)[4], const float (&cc)[4], const float (&cp)[4], const float (&dcn)[4],
+                                               float (&dai)[4], float (&daf)[4], float (&dag)[4], float (&dao)[4], float (&dcarry)[4]) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const float tc = tanh_f32(cc[r]);
+    const float d_o = dh[r] * tc;
+    const float dc = dh[r] * go[r] * (1.0f - tc * tc) + dcn[r];
+    dai[r] = dc * gg[r] * gi[r] * (1.0f - gi[r]);
+    daf[r] = dc * cp[r] * gf[r] * (1.0f - gf[r]);
+    dag[r] = dc * gi[r] * (1.0f - gg[r] * gg[r]);
+    dao[r] = d_o * go[r] * (1.0f - go[r]);
+    dcarry[r] = dc * gf[r];
+  }
+}
+// a cell at t >= lengths[row]: zero gate gradients, the carried dc passes as it came
+__device__ __forceinline__ void cell_bwd_dead(const float (&dcn)[4], float (&dai)[4], float (&daf)[4], float (&dag)[4],
+                                              float (&dao)[4], float (&dcarry)[4]) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    dai[r] = daf[r] = dag[r] = dao[r] = 0.f;
+    dcarry[r] = dcn[r];
+  }
+}
+
 // Fast activations for the bf16 path: v_exp_f32 + v_rcp_f32 (about 1 ulp each), far inside the
 // 8 significant bits the bf16 operands keep.  The f32 parity path uses expf / tanhf instead.
 __device__ __forceinline__ float fast_sigmoid(float x) {

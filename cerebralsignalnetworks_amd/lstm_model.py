@@ -53,6 +53,13 @@ def _dropout_p(owner):
     return float(p)
 
 
+def _check_resident(name, resident, hidden_size):
+    """``resident=True`` (CSN_LSTM_RESIDENT plans: the CU-resident recurrence, path 5) takes hidden sizes up to 128."""
+    if resident and hidden_size > cabi.RESIDENT_MAX_H:
+        raise ValueError(f"{name}: resident=True takes hidden_size <= {cabi.RESIDENT_MAX_H}, got {hidden_size}")
+    return bool(resident)
+
+
 def _draw_dropout(owner):
     """-> None when inter-layer dropout is off for this call, else (p, seed, subsequence) for plan.set_dropout.  On, as in
     nn.LSTM.forward: the module is in train() mode, ``owner.dropout`` (read now) > 0 and there is a layer to drop into --
@@ -139,15 +146,20 @@ class HipLSTM(nn.Module):
     masked with probability ``dropout`` and scaled by 1/(1 - dropout) before the next layer reads it, inside the fused
     multi-layer launches.  The attribute is read on every call, as nn.LSTM.forward reads it.
     ``dropout_subsequence``: None = the torch.distributed rank.
+
+    ``resident=True`` (hidden_size <= 128): every plan of the module is a CSN_LSTM_RESIDENT one -- the steps of a chunk
+    run inside one launch per layer, W_hh in registers, with the results of the per-step cells bit for bit (DESIGN.md
+    section 21).  A property of the plans, not of the parameters: state_dicts are unchanged.
     """
 
     MAX_IDLE_PLANS = 4      # workspaces are large (10 GB at cfg2): keep only a few idle ones
     _STATE_PLANS = False    # LSTM: plans created with CSN_LSTM_STATE
 
-    def __init__(self, input_size, hidden_size, num_layers=1, compute_dtype=torch.bfloat16, dropout=0.0):
+    def __init__(self, input_size, hidden_size, num_layers=1, compute_dtype=torch.bfloat16, dropout=0.0, resident=False):
         super().__init__()
         self.input_size, self.hidden_size, self.num_layers = input_size, hidden_size, num_layers
         self.compute_dtype = compute_dtype
+        self.resident = _check_resident(type(self).__name__, resident, hidden_size)
         self.dropout = dropout
         _dropout_p(self)
         if dropout > 0 and num_layers == 1:
@@ -170,7 +182,7 @@ class HipLSTM(nn.Module):
         """state: None = the class's kind of plan; True = a CSN_LSTM_STATE plan (the views form of HipLSTM: lengths)."""
         state = self._STATE_PLANS if state is None else bool(state)
         key = ((B, T, str(device), bool(training), self.compute_dtype) + (("dropout plan",) if dropout else ()) +
-               (("state plan",) if state != self._STATE_PLANS else ()))
+               (("state plan",) if state != self._STATE_PLANS else ()) + (("resident plan",) if self.resident else ()))
         pool = self._plans.setdefault(key, [])
         for plan in pool:
             if not plan.busy:
@@ -180,7 +192,7 @@ class HipLSTM(nn.Module):
             k, pl = idle.pop(0)
             self._plans[k].remove(pl)
         plan = cabi.LstmPlan(B, T, self.input_size, self.hidden_size, self.num_layers, self.compute_dtype, device,
-                             training=training, state=state, dropout=dropout)
+                             training=training, state=state, dropout=dropout, resident=self.resident)
         pool.append(plan)
         return plan
 
@@ -399,14 +411,14 @@ class LSTM(HipLSTM):
     _STATE_PLANS = True
 
     def __init__(self, input_size, hidden_size, num_layers=1, bias=True, batch_first=True, dropout=0.0,
-                 bidirectional=False, proj_size=0, compute_dtype=torch.bfloat16):
+                 bidirectional=False, proj_size=0, compute_dtype=torch.bfloat16, resident=False):
         unsupported = [name for name, bad in (("bias=False", not bias), ("batch_first=False", not batch_first),
                                               ("dropout != 0", dropout != 0), ("bidirectional=True", bidirectional),
                                               ("proj_size != 0", proj_size != 0)) if bad]
         if unsupported:
             raise ValueError(f"LSTM: {', '.join(unsupported)} is not supported (batch-first, biased, unidirectional "
                              f"stacks without projection or inter-layer dropout only; for bidirectional=True use BiLSTM)")
-        super().__init__(input_size, hidden_size, num_layers, compute_dtype=compute_dtype)
+        super().__init__(input_size, hidden_size, num_layers, compute_dtype=compute_dtype, resident=resident)
         self.bias, self.batch_first, self.dropout, self.bidirectional, self.proj_size = True, True, 0.0, False, 0
 
     def forward(self, x, hx=None, lengths=None, views=None):
@@ -536,8 +548,9 @@ class BiLSTM(nn.Module):
 
     MAX_IDLE_PLANS = 4
 
-    def __init__(self, input_size, hidden_size, num_layers=1, compute_dtype=torch.bfloat16, dropout=0.0):
+    def __init__(self, input_size, hidden_size, num_layers=1, compute_dtype=torch.bfloat16, dropout=0.0, resident=False):
         super().__init__()
+        self.resident = _check_resident("BiLSTM", resident, hidden_size)     # passed to all 2L single-layer plans
         if dropout != 0:
             raise ValueError("BiLSTM: dropout != 0 is not supported (the inter-layer dropout of this library lives "
                              "between the layers of one plan; a bidirectional stack runs one plan per layer and direction)")
@@ -550,7 +563,7 @@ class BiLSTM(nn.Module):
         self._plans = {}        # key -> list of plans; plan.busy marks a forward awaiting its backward
 
     def _checkout(self, B, T, I, device, training, reverse):
-        key = (B, T, I, str(device), bool(training), self.compute_dtype, bool(reverse))
+        key = (B, T, I, str(device), bool(training), self.compute_dtype, bool(reverse)) + (("resident plan",) if self.resident else ())
         pool = self._plans.setdefault(key, [])
         for plan in pool:
             if not plan.busy:
@@ -560,7 +573,7 @@ class BiLSTM(nn.Module):
             k, pl = idle.pop(0)
             self._plans[k].remove(pl)
         plan = cabi.LstmPlan(B, T, I, self.hidden_size, 1, self.compute_dtype, device, training=training, state=True,
-                             reverse=reverse)
+                             reverse=reverse, resident=self.resident)
         pool.append(plan)
         return plan
 
@@ -599,17 +612,18 @@ class Model(nn.Module):
     ``MultiCropWrapper`` (utils/utils.py:607-612) without breaking forward."""
 
     def __init__(self, input_size=128, lstm_size=128, lstm_layers=1, output_size=128, include_top=True,
-                 n_classes=40, compute_dtype=torch.bfloat16, dropout=0.0, bidirectional=False):
+                 n_classes=40, compute_dtype=torch.bfloat16, dropout=0.0, bidirectional=False, resident=False):
         """``bidirectional=True``: the encoder is a ``BiLSTM`` and ``fc`` has 2 * lstm_size inputs.  The feature fed to
         ``fc`` is then ``cat(h_n[-2], h_n[-1])``, the top layer's FINAL state in each direction -- not ``output[:, -1]``,
-        whose reverse half has seen one step only."""
+        whose reverse half has seen one step only.  ``resident=True`` (lstm_size <= 128): the encoder's plans run the
+        CU-resident recurrence (HipLSTM)."""
         super().__init__()
         self.input_size, self.lstm_size, self.lstm_layers = input_size, lstm_size, lstm_layers
         self.output_size, self.include_top, self.bidirectional = output_size, include_top, bool(bidirectional)
         if self.bidirectional:
-            self.lstm = BiLSTM(input_size, lstm_size, lstm_layers, compute_dtype=compute_dtype, dropout=dropout)
+            self.lstm = BiLSTM(input_size, lstm_size, lstm_layers, compute_dtype=compute_dtype, dropout=dropout, resident=resident)
         else:
-            self.lstm = HipLSTM(input_size, lstm_size, lstm_layers, compute_dtype=compute_dtype, dropout=dropout)
+            self.lstm = HipLSTM(input_size, lstm_size, lstm_layers, compute_dtype=compute_dtype, dropout=dropout, resident=resident)
         self.fc = nn.Linear((2 if self.bidirectional else 1) * lstm_size, output_size)
         if include_top:
             self.class_pred = nn.Linear(output_size, n_classes)
@@ -643,10 +657,10 @@ class LSTMModel(nn.Module):
     """
 
     def __init__(self, input_size, hidden_size, n_layers=2, out_features=384, number_of_classes=None,
-                 all_steps=False, compute_dtype=torch.bfloat16, dropout=0.0):
+                 all_steps=False, compute_dtype=torch.bfloat16, dropout=0.0, resident=False):
         super().__init__()
         self.hidden_size, self.n_layer, self.input_size, self.all_steps = hidden_size, n_layers, input_size, all_steps
-        self.lstm = HipLSTM(input_size, hidden_size, n_layers, compute_dtype=compute_dtype, dropout=dropout)
+        self.lstm = HipLSTM(input_size, hidden_size, n_layers, compute_dtype=compute_dtype, dropout=dropout, resident=resident)
         self.fc = nn.Linear(hidden_size, out_features)
         if number_of_classes:
             self.class_pred = nn.Linear(out_features, number_of_classes)

@@ -203,6 +203,18 @@ typedef struct csnLstmPlan csnLstmPlan;
  * c_n, dh0, dc0, all weight gradients -- is that plan's, and all of it holds bit for bit (the workspace behind the
  * layout passes has the same contents).  (tests/test_gpu_bilstm.py) */
 #define CSN_LSTM_REVERSE 0x400
+/* `training` may also carry CSN_LSTM_RESIDENT: the plan runs the CU-resident recurrence (path 5)
+ * instead of the path it would take.  H in {32, 64, 96, 128}, CSN_BF16 and CSN_F32, any B, T, I, L 1..8, training and
+ * inference plans, with every other bit; with H > 128 csn_lstm_plan_create returns CSN_ERR_UNSUPPORTED and
+ * csn_lstm_workspace_bytes 0.  The workspace is that of the same descriptor on path 0 (the generic per-step cells; what
+ * CSN_CELL_V1=1 selects), nothing added, and so are the host flow and every plan feature: state, lengths, dropout,
+ * reverse, windows, io, gradient accumulation, the gradient-ready callback.  What changes is the recurrence: the steps
+ * of a chunk (CSN_LSTM_CHUNK, default 32) of a layer run inside ONE launch, W_hh in the registers of a workgroup that
+ * owns 16 batch rows, h in LDS -- ceil(T / chunk) + L - 1 recurrence launches per pass (L <= 4) against
+ * T + chunk (L - 1).  Every output and gradient equals, BIT FOR BIT, that of the same plan on path 0: same MFMA, same
+ * k order per element, same gate expressions.  Opt-in: a plan without the bit is what it was.
+ * (tests/test_gpu_lstm_resident.py) */
+#define CSN_LSTM_RESIDENT 0x800
 int csn_lstm_plan_create(const csnLstmDesc* d, int training, csnLstmPlan** out);
 void csn_lstm_plan_destroy(csnLstmPlan* plan);
 /* Bytes of device scratch ("workspace") a forward (+ backward) of this plan needs; 256-B aligned base.  The
@@ -211,7 +223,8 @@ size_t csn_lstm_plan_workspace_bytes(const csnLstmPlan* plan);
 /* Which kernels the plan runs: 0 generic per-step cells (exact f32 / odd shapes), 1 per-diagonal bf16 launches,
  * 2 weight-stationary forward, 3 weight-stationary forward and backward (bf16), 4 weight-stationary forward and
  * backward of the exact-float32 path (CSN_F32, H in {128, 256, 384, 512, 768, 1024}, a whole MI355X: one launch per layer and
- * block of batch rows; its workspace also holds fragment-major copies of h and of the gate gradients). */
+ * block of batch rows; its workspace also holds fragment-major copies of h and of the gate gradients), 5 the CU-resident
+ * recurrence of a CSN_LSTM_RESIDENT plan (H <= 128, both dtypes: path 0's workspace, one launch per chunk diagonal). */
 int csn_lstm_plan_path(const csnLstmPlan* plan);
 /* Copies of the gate gradients the plan's LAST csn_lstm_backward wrote per step: 2 = the fragment-major hand-off slab
  * and a row-major copy for the GEMMs behind the recurrence, which every weight-stationary bf16 backward writes; 0 = no
@@ -302,7 +315,7 @@ int csn_lstm_plan_set_grad_callback(csnLstmPlan* plan, csnGradReadyFn fn, void* 
  * stores for the same inputs and prev is what the buffer held: one rounding, prev joins last -- bit for bit what
  * `p.grad += g` gives, so a backward that writes straight into a gradient buffer cannot be told from one that goes through
  * a temporary.  db_ih and db_hh each add to their OWN previous contents (in this mode one buffer for both is refused on the host).
- * Every path (csn_lstm_plan_path 0-4), with and without CSN_LSTM_STATE and the gradient-ready callback, whose meaning
+ * Every path (csn_lstm_plan_path 0-5), with and without CSN_LSTM_STATE and the gradient-ready callback, whose meaning
  * is unchanged: the accumulating kernels of a layer are enqueued before it fires for that layer.  Uses: several forwards
  * through one set of parameters in a step (multi-crop views), micro-batches summed into one optimiser step, the chunks
  * of a recording chained through their state.  Null plan / unknown mode: CSN_ERR_INVALID_ARGUMENT. */
