@@ -1645,6 +1645,7 @@ static int forward_persist(Call& C, const FwdArgs& A) {
   a.error_flag = (unsigned*)(ws + w.status);
   a.B = B; a.H = H; a.T = T; a.Bpad = Bpad; a.MT = MT;
   a.rotate = !P.opt.no_rotate;
+  a.park = !P.opt.no_fwd_park;
   // (forward: no hint words by default -- the first k-block's own pieces are what the wave spins on; measured 205 -> 200 us
   // per launch; CSN_FWD_HINT restores them)
   a.data_polls = (!w.fwd_ns && !P.opt.fwd_flags) ? (P.opt.fwd_hint && !P.opt.dpoll_no_hint ? 1 : 2) : 0;

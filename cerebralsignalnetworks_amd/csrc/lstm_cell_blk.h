@@ -93,7 +93,21 @@ struct PersistFwdArgs {
   // writes and re-arms exactly the (row, unit) pieces it owns at either height, so launches of both heights follow each
   // other on the same ring of slabs; the flag lines of the two heights are separate (slot.flags is the height's own)
   int half_tiles;
+  // != 0 (K-split kernel, H = 768 with data polls; elsewhere ignored): two k-block groups of h in flight and the waiting
+  // register set parked in LDS; 0 (CSN_NO_FWD_PARK): a ring of 4, everything in registers.  Bit-identical results
+  int park;
 };
+// float4 slots per accumulator tile in the forward's reduction buffer: 64 + padding.  The epilogue's lanes walk (row, unit
+// quad j) with j fastest and read slot (tile j, row): with 65 a lane's 16-byte bank group is (j + row) mod 16 -- three lanes
+// of a 16-lane group on one group; with 71 it is (7 j + row) mod 16, distinct except for one rare pair.
+static constexpr int kRedTile = 71;
+static constexpr int kParkSlots = 6;     // float4 slots per thread of the parked form's region
+// dynamic LDS request of lstm_fwd_persist_kernel<NQ, ...> in bytes, at either tile height: [4 waves][4 NQ tiles][kRedTile]
+// partial sums, [NQ][4] bias, and in the parked form [kParkSlots][256 threads].  More than half of a CU's 160 KB on
+// purpose: a workgroup stays alone on its CU
+constexpr size_t fwd_persist_lds_bytes(int nq, bool park) {
+  return (size_t)(4 * 4 * nq * kRedTile + 4 * nq + (park ? kParkSlots * 256 : 0)) * 16;
+}
 bool fwd_persist_supported(int B, int H, int dtype, const Options& opt);
 // N-split weight-stationary forward (lstm_fwd_ns.hip): the default where it applies
 bool fwd_ns_supported(int B, int H, int dtype, const Options& opt);

@@ -92,10 +92,6 @@ __device__ __forceinline__ void span_exit(unsigned long long t_entry) {
 
 namespace csn {
 
-// float4 slots per accumulator tile in the reduction buffer: 64 + padding.  The epilogue's lanes walk (row, unit quad j)
-// with j fastest and read slot (tile j, row): with 65 a lane's 16-byte bank group is (j + row) mod 16 -- three lanes of a
-// 16-lane group on one group; with 71 it is (7 j + row) mod 16, distinct except for one rare pair.
-static constexpr int kRedTile = 71;
 static constexpr unsigned long long kSpinTimeoutTicks = 20000000ull;   // 0.2 s of the 100 MHz wall clock
 
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
@@ -151,9 +147,27 @@ __device__ __forceinline__ T bounded_poll(const T* p, unsigned* error_flag, Pred
 #ifndef CSN_FWD_RING
 #define CSN_FWD_RING 4
 #endif
-template <int NQ, int KS, bool DPOLL, int RG = 4>
+// float4 slots per thread of the parking region (PARK): a thread's 16-byte pieces of the step's input projection (plain
+// form) or the wave's W_ih fragments (fused form), kParkSlots of them (lstm_cell_blk.h), slot i of thread t at float4 index 256 i + t -- lane-linear, so every
+// ds_write_b128 / ds_read_b128 is conflict-free, and private to the thread, so no barrier orders them
+static constexpr int kParkRing = 2;      // k-block groups of h in flight in the PARK form
+// PARK (<6,6> with data polls, the default there; off: CSN_NO_FWD_PARK, which keeps ring 4 and registers): what the
+// A/B of DESIGN.md section 3.4 (i) left standing.
+//   * kParkRing = 2 k-block groups of h in flight instead of CSN_FWD_RING = 4.  Without hint words a wave requests its
+//     tile as soon as it reaches the step, usually before the producers have stored: every group requested that early
+//     comes back as sentinel and is read again in its turn, one round trip apiece.  Measured per training step at cfg2,
+//     ring 1 / 2 / 3 / 4 / 5 / 6: +0.07 / -0.12 / -0.10 / -0.04 / +0.05 / +0.08 ms against the ring of 4 in registers.
+//   * the register set that only WAITS while the MFMAs run lives in LDS the kernel requests anyway (one workgroup per
+//     CU) -- worth 0.03 - 0.05 ms of the above:
+//       plain: the step's input projection (`cur`, requested a step early, added in the epilogue) is written to the
+//         thread's slots at the top of the step and read back in the epilogue, beside the partial-sum reads;
+//       fused: the stationary W_ih fragments are written once per launch and read back in front of the x MFMAs (in
+//         front of the last k-block's MFMAs the allocator spilled 112 registers); the x fragments stay where they were.
+// Same MFMAs in the same order on the same operands, same epilogue arithmetic: the two forms agree bit for bit.
+template <int NQ, int KS, bool DPOLL, int RG = 4, bool PARK = false>
 __global__ void __launch_bounds__(256) lstm_fwd_persist_kernel(PersistFwdArgs a) {
   static_assert(RG == 4 || RG == 2, "tiles of 64 or 32 rows");
+  static_assert(!PARK || (NQ == 6 && KS == 6 && DPOLL), "the parked form exists for <6,6> with data polls only");
   constexpr int NT = RG * NQ;
   constexpr int NPAIR = 16 * RG * NQ;
   constexpr int NPASS = (NPAIR + 255) / 256;
@@ -253,11 +267,15 @@ __global__ void __launch_bounds__(256) lstm_fwd_persist_kernel(PersistFwdArgs a)
 #pragma unroll
   for (int i = 0; i < 8; ++i) cur[i] = nxt[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
   float* const bias_lds = reinterpret_cast<float*>(red + 4 * NT * kRedTile);      // [NQ][4] float4, behind the reduction buffer
+  f32x4* const park = reinterpret_cast<f32x4*>(red + 4 * NT * kRedTile + 4 * NQ) + tid;      // PARK: this thread's slots, 256 float4 apart
+  static_assert(!PARK || (NQ <= kParkSlots && (HALFQ ? NFULL * 4 + 2 : NPASS * 4) <= kParkSlots), "parking region too small");
   if (fused) {
     if (xwave) {
 #pragma unroll
-      for (int j = 0; j < NQ; ++j)
+      for (int j = 0; j < NQ; ++j) {
         cur[j] = *reinterpret_cast<const f32x4*>(S.wih_blk + ((int64_t)((u0 >> 2) + j) * xkb + wave) * 512 + lane * 8);
+        if constexpr (PARK) park[j * 256] = cur[j];
+      }
     }
     // the bias of this workgroup's gate rows in accumulator order: entry (j, lane >> 4) = rows 16 j + 4 (lane >> 4) ..+3
     if (tid < NQ * 4)
@@ -334,6 +352,16 @@ __global__ void __launch_bounds__(256) lstm_fwd_persist_kernel(PersistFwdArgs a)
     if (fused) {
 #pragma unroll
       for (int rg = 0; rg < RG; ++rg) xf[rg] = __builtin_bit_cast(bf16x8, nxt[rg]);
+    } else if constexpr (PARK) {
+      // park the step's input projection until the epilogue (the same slots were read in the last epilogue, earlier
+      // in this thread's program order)
+#pragma unroll
+      for (int ps = 0; ps < NPASS; ++ps)
+        if (pok[ps]) {
+#pragma unroll
+          for (int q = 0; q < (HALFQ && ps == NFULL ? 2 : 4); ++q) park[(ps * 4 + q) * 256] = nxt[ps * 4 + q];
+        }
+      __builtin_amdgcn_sched_barrier(0);
     } else {
 #pragma unroll
       for (int i = 0; i < 8; ++i) cur[i] = nxt[i];
@@ -357,6 +385,16 @@ __global__ void __launch_bounds__(256) lstm_fwd_persist_kernel(PersistFwdArgs a)
       }
     }
 
+    // PARK, fused: the W_ih fragments come back from their slots in front of the x MFMAs
+    bf16x8 wih[NQ];
+    auto fetch_wih = [&]() {
+      if constexpr (PARK) {
+        if (xwave) {
+#pragma unroll
+          for (int j = 0; j < NQ; ++j) wih[j] = __builtin_bit_cast(bf16x8, park[j * 256]);
+        }
+      }
+    };
     if (t > 0 || a.state) {
       // Wait for h_{t-1} (slot t).  A wave only multiplies its K quarter of h, i.e. the units of the
       // nslices/4 producer slices [wave * nslices/4, ...): it polls exactly those flags of the group's flag
@@ -405,7 +443,7 @@ __global__ void __launch_bounds__(256) lstm_fwd_persist_kernel(PersistFwdArgs a)
       // the H = 512 instantiation (NQ 8, KS 4), whose W_hh fragments came back with a foreign 4th dword (0.8 % errors in
       // h, build-dependent).  Ring depth per instantiation so that every one fits its 512 registers; `make` fails on
       // scratch use in these kernels (tools/check_spills.py).
-      constexpr int RING_MAX = (NQ == 8 && KS == 4) ? 2 : ((NQ == 6 && KS == 6 && !DPOLL) ? 3 : CSN_FWD_RING);
+      constexpr int RING_MAX = PARK ? kParkRing : (NQ == 8 && KS == 4) ? 2 : ((NQ == 6 && KS == 6 && !DPOLL) ? 3 : CSN_FWD_RING);
       constexpr int RING = KS > RING_MAX ? RING_MAX : KS;
       bf16x8 hf[RING][RG];
       // (the rotated k-block walk as ONE running scalar offset: k-block (i + rot) % KS of the i-th group issued; as
@@ -474,12 +512,13 @@ __global__ void __launch_bounds__(256) lstm_fwd_persist_kernel(PersistFwdArgs a)
         }
       }
     }
+    fetch_wih();
     if (xwave) {                               // x_t W_ih^T, requested a step ago
 #pragma unroll
       for (int rg = 0; rg < RG; ++rg)
 #pragma unroll
         for (int j = 0; j < NQ; ++j)
-          acc[rg][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, cur[j]), xf[rg], acc[rg][j], 0, 0, 0);
+          acc[rg][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(PARK ? wih[j] : __builtin_bit_cast(bf16x8, cur[j]), xf[rg], acc[rg][j], 0, 0, 0);
     }
     __builtin_amdgcn_sched_barrier(0);
     // next step's input projection (or input): in flight during this step's reduction and epilogue, landed
@@ -554,7 +593,7 @@ __global__ void __launch_bounds__(256) lstm_fwd_persist_kernel(PersistFwdArgs a)
           const float4 v = red[w2 * NT * kRedTile + idx];
           sum.x += v.x; sum.y += v.y; sum.z += v.z; sum.w += v.w;
         }
-        const f32x4 xq = fused ? (f32x4){0.f, 0.f, 0.f, 0.f} : cur[ps * 4 + q];
+        const f32x4 xq = fused ? (f32x4){0.f, 0.f, 0.f, 0.f} : PARK ? park[(ps * 4 + q) * 256] : cur[ps * 4 + q];
         gi[q] = fast_sigmoid(sum.x + xq[0]);
         gf[q] = fast_sigmoid(sum.y + xq[1]);
         gg[q] = fast_tanh(sum.z + xq[2]);
@@ -664,12 +703,28 @@ template <int NQ, int KS>
 static int launch_persist_t(const PersistFwdArgs& a, hipStream_t st) {
   // (the 32-row instantiations ask for the 64-row tile's LDS, more than half a CU's, although they use half of it: their
   // register counts would let two workgroups share a CU, and a launch of 8 groups needs every CU for a workgroup of its own)
-  const size_t lds = (size_t)(4 * 4 * NQ * kRedTile + 4 * NQ) * sizeof(float4);
-  static_assert((4 * 4 * NQ * kRedTile + 4 * NQ) * sizeof(float4) > 80 * 1024, "the LDS request no longer keeps a workgroup alone on its CU");
+  const size_t lds = fwd_persist_lds_bytes(NQ, false);
+  static_assert(fwd_persist_lds_bytes(NQ, false) > 80 * 1024, "the LDS request no longer keeps a workgroup alone on its CU");
   if (int rc = ensure_dyn_lds<&lstm_fwd_persist_kernel<NQ, KS, false>>((int)lds)) return rc;
   if (int rc = ensure_dyn_lds<&lstm_fwd_persist_kernel<NQ, KS, true>>((int)lds)) return rc;
   const unsigned nslices = (unsigned)(a.H / (4 * NQ));
   const unsigned grid = a.xcd_groups ? 8u * nslices : nslices * (unsigned)(a.MT * a.nslots);
+  if constexpr (NQ == 6 && KS == 6) {
+    // the parked form (the default with data polls): the same request plus the parking region
+    constexpr size_t lds_park = fwd_persist_lds_bytes(NQ, true);
+    static_assert(lds_park > 80 * 1024 && lds_park <= 160 * 1024, "the parked form's LDS request: above half a CU's LDS, within all of it");
+    if (a.data_polls && a.park) {
+      if (a.half_tiles) {
+        if (int rc = ensure_dyn_lds<&lstm_fwd_persist_kernel<NQ, KS, true, 2, true>>((int)lds_park)) return rc;
+        lstm_fwd_persist_kernel<NQ, KS, true, 2, true><<<dim3(grid), 256, lds_park, st>>>(a);
+      } else {
+        if (int rc = ensure_dyn_lds<&lstm_fwd_persist_kernel<NQ, KS, true, 4, true>>((int)lds_park)) return rc;
+        lstm_fwd_persist_kernel<NQ, KS, true, 4, true><<<dim3(grid), 256, lds_park, st>>>(a);
+      }
+      CSN_LAUNCH_CHECK();
+      return CSN_OK;
+    }
+  }
   if (a.half_tiles) {
     if (int rc = ensure_dyn_lds<&lstm_fwd_persist_kernel<NQ, KS, false, 2>>((int)lds)) return rc;
     if (int rc = ensure_dyn_lds<&lstm_fwd_persist_kernel<NQ, KS, true, 2>>((int)lds)) return rc;
