@@ -32,7 +32,7 @@ def load_checkpoint_into(model, path):
 def main(argv=None):
     from cerebralsignalnetworks_amd import Model, EEGFilters
     from cerebralsignalnetworks_amd.dataset import EEGDataset
-    from cerebralsignalnetworks_amd.retrieval import evaluate_distributed, evaluate_full
+    from cerebralsignalnetworks_amd.retrieval import evaluate_device, evaluate_distributed, evaluate_full
     from cerebralsignalnetworks_amd.trainer import DistillTrainer, split_indices
 
     p = build_parser()
@@ -78,12 +78,17 @@ def main(argv=None):
         r = evaluate_full(FLAGS, gallery, query, glab, qlab, dataset)
     else:
         tr, te = (ix[rank::world].to(device) for ix in split_indices(N, (0.8, 0.2), seed=43))      # random_split, Eval.py:324-325
-        gallery = trainer.embed_all(dataset.eeg_all[tr], FLAGS.batch_size).cpu().numpy()
-        query = trainer.embed_all(dataset.eeg_all[te], FLAGS.batch_size).cpu().numpy()
+        gallery = trainer.embed_all(dataset.eeg_all[tr], FLAGS.batch_size)
+        query = trainer.embed_all(dataset.eeg_all[te], FLAGS.batch_size)
         trainer.check_device_status()      # every embedding batch above: a timed-out in-kernel hand-off invalidates the run
         glab = [dataset.getLabelbyIndex(int(i)) for i in tr.cpu()]
         qlab = [dataset.getLabelbyIndex(int(i)) for i in te.cpu()]
-        r = evaluate_distributed(FLAGS, list(gallery), list(query), glab, qlab, dataset)
+        if FLAGS.device_eval and world == 1:
+            # the embeddings stay where embed_all left them: search and class hits on the device, the same floats
+            r = evaluate_device(FLAGS, gallery, query, glab, qlab, dataset)
+        else:
+            r = evaluate_distributed(FLAGS, list(gallery.cpu().numpy()), list(query.cpu().numpy()), glab, qlab, dataset,
+                                     on_device=FLAGS.device_eval)
     dt = time.perf_counter() - t0
     if rank != 0:
         return r

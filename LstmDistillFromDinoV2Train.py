@@ -117,6 +117,10 @@ def build_parser(flavour=PERILS):
                         '(always fused)')
     p.add_argument('--compat_label_bug', action='store_true',
                    help='reproduce the batch-local label lookup of transformEEGDataLSTMByList')
+    p.add_argument('--device_eval', action='store_true',
+                   help='retrieval leg: the embeddings stay on the device, class hits are counted there (csn_topk_merge, '
+                        'csn_topk_class_metrics) and the host folds per-class integers into the same Recall / Precision / '
+                        'top1 (not with --compat_label_bug, which keeps the host form)')
     return p
 
 
@@ -162,7 +166,7 @@ def init_distributed():
 def main(argv=None, flavour=PERILS):
     from cerebralsignalnetworks_amd import Model, EEGFilters
     from cerebralsignalnetworks_amd.dataset import EEGDataset
-    from cerebralsignalnetworks_amd.retrieval import evaluate_distributed, evaluate_full
+    from cerebralsignalnetworks_amd.retrieval import evaluate_device, evaluate_distributed, evaluate_full
     from torch.utils.data import DataLoader, Subset
     from cerebralsignalnetworks_amd.trainer import DistillTrainer, shard_indices, split_indices
     from cerebralsignalnetworks_amd.losses import HyperParams
@@ -261,8 +265,11 @@ def main(argv=None, flavour=PERILS):
                     q_ix = q_ix[: len(range(rank, len(val_idx), world))]
                 gallery = trainer.embed_all(dataset.eeg_all[g_ix], FLAGS.batch_size)
                 query = trainer.embed_all(dataset.eeg_all[q_ix], FLAGS.batch_size)
-                r = evaluate_distributed(FLAGS, list(gallery.cpu().numpy()), list(query.cpu().numpy()), labels_of(g_ix),
-                                         labels_of(q_ix), dataset)
+                if FLAGS.device_eval and world == 1:
+                    r = evaluate_device(FLAGS, gallery, query, labels_of(g_ix), labels_of(q_ix), dataset)
+                else:
+                    r = evaluate_distributed(FLAGS, list(gallery.cpu().numpy()), list(query.cpu().numpy()), labels_of(g_ix),
+                                             labels_of(q_ix), dataset, on_device=FLAGS.device_eval)
             # validation loss over ALL ranks' shards: sum of the batch losses and their count, one all-reduce, so that
             # the best-checkpoint decision below is the same on every rank and covers the whole validation split
             vsum = torch.zeros(2, device=device, dtype=torch.float64)

@@ -21,6 +21,7 @@ LSTM_DROPOUT = 0x200    # csn_lstm_plan_create flag CSN_LSTM_DROPOUT (include/cs
 LSTM_REVERSE = 0x400    # csn_lstm_plan_create flag CSN_LSTM_REVERSE (include/csn_hip.h)
 LSTM_RESIDENT = 0x800   # csn_lstm_plan_create flag CSN_LSTM_RESIDENT: the CU-resident recurrence, H <= 128 (path 5)
 RESIDENT_MAX_H = 128
+TOPK_MERGE_STAGED_MAX = 2048      # csn_topk_merge keeps up to this many candidates of a query (P * k_in) in LDS
 GRAD_OVERWRITE, GRAD_ACCUMULATE = 0, 1      # csn_lstm_plan_set_grad_mode (include/csn_hip.h)
 SEG_DECAYED, SEG_SCALED = 1, 2              # per-segment flags of csn_flat_segments_prepare (include/csn_hip.h)
 
@@ -128,6 +129,11 @@ SIGNATURES = {
     "csn_chan_l2_select": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_i64, _c_i64, _c_void_p, _c_void_p, _c_int,
                                     _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
     "csn_chan_l2_accumulate": (_c_int, [_c_void_p, _c_void_p, _c_i64, _c_int, _c_void_p]),
+    "csn_topk_merge_staged_max": (_c_int, []),
+    "csn_topk_merge": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_i64, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p,
+                                _c_void_p]),
+    "csn_topk_class_metrics": (_c_int, [_c_void_p, _c_i64, _c_int, _c_void_p, _c_i64, _c_void_p, _c_int, _c_void_p,
+                                        _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
 }
 
 
@@ -961,3 +967,67 @@ def chan_l2_accumulate(base, D_one, first):
     with torch.cuda.device(base.device):
         _check(load().csn_chan_l2_accumulate(_ptr(base), _ptr(D_one), base.numel(), int(bool(first)), _stream()))
     return base
+
+
+def topk_merge(D_parts, I_parts, k, want=("idx", "dist64", "dist")):
+    """csn_topk_merge: the exact merge of P candidate lists.  D_parts [P,Nq,k_in] float64, I_parts [P,Nq,k_in] int64,
+    dense device tensors, padding (+inf, -1).  -> dict with the outputs named in ``want``: idx [Nq,k] int64 (always),
+    dist64 [Nq,k] float64, dist [Nq,k] float32.  A query with fewer than k real candidates has index -1 in its last
+    places; the caller checks."""
+    _need_cuda(D_parts, I_parts)
+    if D_parts.dim() != 3 or D_parts.dtype != torch.float64 or not D_parts.is_contiguous():
+        raise CsnError("topk_merge: D_parts must be a dense float64 [P,Nq,k_in] tensor")
+    if I_parts.dtype != torch.int64 or not I_parts.is_contiguous() or I_parts.shape != D_parts.shape:
+        raise CsnError(f"topk_merge: I_parts must be a dense int64 tensor of D_parts' shape {tuple(D_parts.shape)}")
+    if I_parts.device != D_parts.device:
+        raise CsnError("topk_merge: D_parts and I_parts are on different devices")
+    unknown = set(want) - {"idx", "dist64", "dist"}
+    if unknown:
+        raise CsnError(f"topk_merge: unknown outputs {sorted(unknown)}")
+    P, Nq, k_in = D_parts.shape
+    k = int(k)
+    kk = max(k, 0)
+    dev = D_parts.device
+    with torch.cuda.device(dev):
+        out = {"idx": torch.empty((Nq, kk), dtype=torch.int64, device=dev)}
+        if "dist64" in want:
+            out["dist64"] = torch.empty((Nq, kk), dtype=torch.float64, device=dev)
+        if "dist" in want:
+            out["dist"] = torch.empty((Nq, kk), dtype=torch.float32, device=dev)
+        _check(load().csn_topk_merge(_ptr(D_parts), _ptr(I_parts), P, Nq, k_in, k, _ptr(out["idx"]),
+                                     _ptr(out.get("dist64")), _ptr(out.get("dist")), _stream()))
+    return out
+
+
+def topk_class_metrics(idx, gallery_class, query_class, n_classes,
+                       want=("hits", "top1", "pred", "class", "top1_correct")):
+    """csn_topk_class_metrics: per-query hit counts of neighbour lists idx [Nq,k] int64 and their per-class integer sums.
+    gallery_class [Ng] / query_class [Nq]: dense int32 device tensors of class ids in [0, n_classes).  -> dict with the
+    outputs named in ``want``: hits / top1 / pred [Nq] int32, class [n_classes,4] int64 (queries, queries with a hit, sum
+    of hits, first query index or -1), top1_correct [1] int64."""
+    _need_cuda(idx, gallery_class, query_class)
+    if idx.dim() != 2 or idx.dtype != torch.int64 or not idx.is_contiguous():
+        raise CsnError("topk_class_metrics: idx must be a dense int64 [Nq,k] tensor")
+    Nq, k = idx.shape
+    Ng = gallery_class.numel()
+    for t, n, name in ((gallery_class, Ng, "gallery_class"), (query_class, Nq, "query_class")):
+        if t.dtype != torch.int32 or not t.is_contiguous() or t.dim() != 1 or t.numel() != n or t.device != idx.device:
+            raise CsnError(f"topk_class_metrics: {name} must be a dense int32 tensor of {n} elements on idx's device")
+    unknown = set(want) - {"hits", "top1", "pred", "class", "top1_correct"}
+    if unknown:
+        raise CsnError(f"topk_class_metrics: unknown outputs {sorted(unknown)}")
+    n_classes = int(n_classes)
+    dev = idx.device
+    with torch.cuda.device(dev):
+        out = {}
+        for name in ("hits", "top1", "pred"):
+            if name in want:
+                out[name] = torch.empty(Nq, dtype=torch.int32, device=dev)
+        if "class" in want:
+            out["class"] = torch.empty((max(n_classes, 0), 4), dtype=torch.int64, device=dev)
+        if "top1_correct" in want:
+            out["top1_correct"] = torch.empty(1, dtype=torch.int64, device=dev)
+        _check(load().csn_topk_class_metrics(_ptr(idx), Nq, k, _ptr(gallery_class), Ng, _ptr(query_class), n_classes,
+                                             _ptr(out.get("hits")), _ptr(out.get("top1")), _ptr(out.get("pred")),
+                                             _ptr(out.get("class")), _ptr(out.get("top1_correct")), _stream()))
+    return out

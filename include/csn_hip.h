@@ -96,7 +96,7 @@ enum csnDtype { CSN_F32 = 0, CSN_BF16 = 1 };
 /* ABI version of this header; bumped on any signature change.  A symbol added beside the existing ones
  * (csn_lstm_plan_set_grad_mode, csn_lstm_plan_set_lengths, csn_lstm_plan_set_views, csn_lstm_plan_set_io, csn_lstm_plan_half_tile_launches, the
  * csn_flat_* family, csn_adam_step, csn_lars_step, csn_eeg_bandpass_stream and its _path, csn_distill_loss,
- * csn_dino_loss, csn_barlow_corr, csn_barlow_grad) breaks no caller and does not bump it; neither does a new bit of csn_lstm_plan_create's `training` word. */
+ * csn_dino_loss, csn_barlow_corr, csn_barlow_grad, csn_topk_merge and its _staged_max, csn_topk_class_metrics) breaks no caller and does not bump it; neither does a new bit of csn_lstm_plan_create's `training` word. */
 #define CSN_ABI_VERSION 6
 int csn_abi_version(void);
 /* Thread-local message for the last non-zero status returned on this thread. */
@@ -690,6 +690,32 @@ int csn_chan_l2_select(const double* base, const double* Dc, int nc, int64_t Nq,
                        const int32_t* query_class, int k, int64_t* out_idx, double* out_dist, int32_t* out_hits,
                        int32_t* out_top1, csnStream_t stream);
 int csn_chan_l2_accumulate(double* base, const double* D_one, int64_t n, int first, csnStream_t stream);
+
+/* K8, retrieval evaluation behind the search: the exact merge of sharded candidate lists and the
+ * per-class hit counts of utils/Utilities.py:57-99 on the device.  Both are stateless, run on `stream`, and refuse on the
+ * host, before any launch: null pointers (other than the ones marked nullable), sizes <= 0, and the limits listed.
+ *
+ * csn_topk_merge: D_parts[P,Nq,k_in] float64 and I_parts[P,Nq,k_in] int64, dense; a padding entry is (+inf, -1) -- any
+ *   entry with a negative index is padding, whatever its distance.  For every query the k smallest real entries of its
+ *   P * k_in candidates under (float64 distance, index), ascending, ties -> lower index (equal pairs: the lower part, then
+ *   the lower place); a real distance may be +inf.  1 <= k <= 1024, 1 <= k_in <= 1024, 1 <= P <= 64, P * k_in >= k.
+ *   out_idx[Nq,k] int64; out_dist64[Nq,k] float64 and out_dist[Nq,k] float32 (its float32 rounding, inf where that
+ *   overflows) may each be NULL.  A query with fewer than k real candidates gets (+inf, -1) in the remaining places.
+ *   csn_topk_merge_staged_max: up to this many candidates per query (P * k_in) are kept in LDS, more are re-read from L2.
+ * csn_topk_class_metrics: idx[Nq,k] int64 neighbour lists (1 <= k <= 1024; an index outside [0, Ng) counts as a miss and
+ *   is never dereferenced), gallery_class[Ng] / query_class[Nq] int32 class ids in [0, n_classes), n_classes <= 65536 (a
+ *   query whose class is outside adds to no class row).  Outputs, each nullable, at least one given:
+ *   out_hits[Nq] int32 = how many of the k have the query's class; out_top1[Nq] int32 = class of the first (-1: none);
+ *   out_pred[Nq] int32 = the query's class where hits > 0, else out_top1;
+ *   out_class[n_classes,4] int64 = per class {queries, queries with hits > 0, sum of hits, lowest query index or -1};
+ *   out_top1_correct[1] int64 = queries whose first neighbour has their class.
+ *   Integer sums and a minimum only: the result does not depend on the grid, the order of execution or the stream. */
+int csn_topk_merge_staged_max(void);
+int csn_topk_merge(const double* D_parts, const int64_t* I_parts, int P, int64_t Nq, int k_in, int k, int64_t* out_idx,
+                   double* out_dist64, float* out_dist, csnStream_t stream);
+int csn_topk_class_metrics(const int64_t* idx, int64_t Nq, int k, const int32_t* gallery_class, int64_t Ng,
+                           const int32_t* query_class, int n_classes, int32_t* out_hits, int32_t* out_top1,
+                           int32_t* out_pred, int64_t* out_class, int64_t* out_top1_correct, csnStream_t stream);
 
 #ifdef __cplusplus
 }
