@@ -47,7 +47,7 @@ int fail(int status, const char* fmt, ...);
 // (csn_lstm_plan_create) or once per call of a stateless entry point -- and passed down by reference: the
 // library keeps no mutable global state, so plans on different streams / threads / devices never share any.
 struct Options {
-  bool cell_v1, no_persist, no_persist_bwd, persist_streams, no_xcd_local, no_rotate, no_fuse_x, no_beside,
+  bool cell_v1, no_persist, no_persist_bwd, persist_streams, no_xcd_local, no_rotate, no_fuse_x, no_beside, beside_128,
       no_side_stream, fwd_ksplit, fwd_nsplit, fwd_flags, bwd_flags, dpoll_no_hint, fwd_hint, gemm_no_dma, gemm_no_256, gemm_generic, tn_no_tr, tn_no_stagger, filter_v1, tags_no_rearm, gemm_no_192, no_half_tiles, nt_no_w4, no_fwd_park;
   int chunk;       // timesteps per weight-stationary launch
   int tn_stages;   // LDS-DMA ring depth of the 256 x 256 weight-gradient kernel
@@ -67,6 +67,7 @@ static inline Options options_from_env() {
   o.no_rotate = on("CSN_NO_ROTATE");
   o.no_fuse_x = on("CSN_NO_FUSE_X");
   o.no_beside = on("CSN_NO_BESIDE");
+  o.beside_128 = on("CSN_BESIDE_128");
   o.no_half_tiles = on("CSN_NO_HALF_TILES");
   o.no_fwd_park = on("CSN_NO_FWD_PARK");
   o.no_side_stream = on("CSN_NO_SIDE_STREAM");

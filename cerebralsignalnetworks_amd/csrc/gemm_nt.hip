@@ -467,10 +467,6 @@ gemm_nt_wide_kernel(const bf16_t* __restrict__ A, const bf16_t* __restrict__ Bt,
 #ifndef CSN_NT_W4_NA          // A ring depth (timing experiments override it: tools/abl_build.sh)
 #define CSN_NT_W4_NA 3
 #endif
-__device__ __forceinline__ int nt64_sw(int row) {
-  const int g = (row >> 2) & 3;
-  return (((g ^ (g >> 1)) & 1) << 1) | (g >> 1);
-}
 template <typename OutT, int NA>
 __global__ void __launch_bounds__(256, 2)
 gemm_nt_w4_kernel(const bf16_t* __restrict__ A, const bf16_t* __restrict__ Bt, const float* __restrict__ bias,

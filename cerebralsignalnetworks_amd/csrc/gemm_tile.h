@@ -23,6 +23,13 @@ __device__ __forceinline__ int nt_lds_off(int row, int chunk) {  // byte offset 
   return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4);
 }
 
+// NT, LDS image of the stages of 32 contraction columns (gemm_nt_w4_kernel, the wide body of gemm_beside.h): 64-byte
+// rows, four 16-byte chunks per row, chunk ch of row r at position ch ^ nt64_sw(r)
+__device__ __forceinline__ int nt64_sw(int row) {
+  const int g = (row >> 2) & 3;
+  return (((g ^ (g >> 1)) & 1) << 1) | (g >> 1);
+}
+
 // TN, LDS image of one operand tile: 32 k-rows x 128 columns (bf16) = 256-byte rows, eight
 // 16-column blocks per row.  Block cb of k-row r is stored at block (cb ^ s(r)),
 // s(r) = (r & 3) | (((r >> 3) & 1) << 2), so the 8 k-rows that the lower (or upper) 32 lanes of

@@ -1898,6 +1898,7 @@ static int backward_persist(Call& C, const BwdArgs& A) {
   a.B = B; a.H = H; a.T = T; a.Bpad = Bpad; a.MT = MT;
   a.xcd_groups = 1;
   a.grid_slices = 32;
+  a.beside_narrow = P.opt.beside_128 ? 1 : 0;
   a.rotate = !P.opt.no_rotate;
   a.data_polls = P.opt.bwd_flags ? 0 : (P.opt.dpoll_no_hint ? 2 : 1);
 #ifdef CSN_SLAB_TAGS

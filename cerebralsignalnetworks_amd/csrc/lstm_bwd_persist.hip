@@ -108,14 +108,16 @@ __global__ void __launch_bounds__(256) lstm_bwd_persist_kernel(PersistBwdArgs a,
     const int ngroups = a.nslots * MT, gs = a.grid_slices;
     if (grp >= ngroups || slice >= nslices) {
       // no recurrence work for this workgroup: it walks the tiles of the launch's input-gradient GEMMs.  Workers of
-      // one XCD (equal blockIdx.x % 8) get consecutive indices, so they work on neighbouring tiles.
+      // one XCD (equal blockIdx.x % 8) get consecutive indices [base, base + here), so they work on neighbouring tiles.
       if (a.ngemm > 0) {
         const int idle_here = gs - nslices;
         const unsigned base = grp <= ngroups ? (unsigned)(grp * idle_here)
                                              : (unsigned)(ngroups * idle_here + (grp - ngroups) * gs);
-        const unsigned worker = base + (unsigned)(grp < ngroups ? slice - nslices : slice);
+        const unsigned here = (unsigned)(grp < ngroups ? idle_here : gs);
+        const unsigned local = (unsigned)(grp < ngroups ? slice - nslices : slice);
         const unsigned nworkers = (unsigned)(ngroups * idle_here + (8 - ngroups) * gs);
-        for (int i = 0; i < a.ngemm; ++i) beside_gemm_tiles(a.gemm[i], reinterpret_cast<char*>(red), worker, nworkers);
+        for (int i = 0; i < a.ngemm; ++i)
+          beside_gemm_tiles(a.gemm[i], reinterpret_cast<char*>(red), base, here, local, nworkers, ((a.gemm_wide >> i) & 1) != 0);
       }
       return;
     }
@@ -593,6 +595,10 @@ static int launch_bwd_persist_t(const PersistBwdArgs& a, hipStream_t st, const i
     if (b.ngemm > 0) {
       lds = kBesideLdsBytes;                 // the GEMM workers' staging ring; also keeps every workgroup alone on its CU
       if (b.grid_slices < (int)nslices) b.grid_slices = (int)nslices;
+      b.gemm_wide = 0;                       // bit i: GEMM i on 256 x 192 tiles (gemm_beside.h)
+      for (int i = 0; i < b.ngemm; ++i)
+        if (!b.beside_narrow && beside_takes_wide(b.gemm[i].M, b.gemm[i].N, b.nslots * b.MT, (int)nslices, b.grid_slices))
+          b.gemm_wide |= 1 << i;
     } else {
       b.grid_slices = (int)nslices;
     }
@@ -621,7 +627,7 @@ int launch_bwd_persist(const PersistBwdArgs& a, hipStream_t st, const int* lengt
   CSN_REQUIRE(!a.half_tiles || (a.xcd_groups && lengths == nullptr), "launch_bwd_persist: 32-row groups need the grouped form and no lengths");
   CSN_REQUIRE(a.ngemm >= 0 && a.ngemm <= 3 && (a.ngemm == 0 || a.xcd_groups), "launch_bwd_persist: bad GEMM list");
   for (int i = 0; i < a.ngemm; ++i)
-    CSN_REQUIRE(a.gemm[i].K % 64 == 0 && a.gemm[i].N % 4 == 0 && a.gemm[i].M > 0, "launch_bwd_persist: GEMM %d shape", i);
+    CSN_REQUIRE(a.gemm[i].K % 64 == 0 && a.gemm[i].K <= (1 << 22) && a.gemm[i].N % 4 == 0 && a.gemm[i].M > 0, "launch_bwd_persist: GEMM %d shape", i);
   switch (a.H) {
     case 1024: return launch_bwd_persist_t<2, 32>(a, st, lengths);
     case 768: return launch_bwd_persist_t<2, 24>(a, st, lengths);

@@ -136,6 +136,8 @@ struct PersistBwdArgs {
   int nslots;
   BesideGemm gemm[3];      // input-gradient GEMMs of the chunks the layers above finished one launch ago
   int ngemm;
+  int beside_narrow;       // != 0 (CSN_BESIDE_128): the GEMMs take 256 x 128 tiles at every width (gemm_beside.h); same bits
+  int gemm_wide;           // bit i: gemm[i] takes 256 x 192 tiles; set by launch_bwd_persist from the launch's geometry
   int grid_slices;         // xcd_groups: the grid is 8 * grid_slices workgroups (>= slices per group)
   int xcd_groups;
   int rotate;              // != 0: each workgroup walks the k-blocks from its own offset (changes the summation order)
