@@ -520,6 +520,14 @@ class LstmPlan:
         (csn_hip.h); 0 under CSN_NO_HALF_TILES=1."""
         return load().csn_lstm_plan_half_tile_launches(self._plan, which)
 
+    def bwd_launches(self, which):
+        """Recurrence launches of the last weight-stationary backward (which = 0) and the chunk diagonals its merged
+        launch covered (which = 1; 0: none merged, e.g. under CSN_BWD_NO_MERGE=1) (csrc/lstm.hip).  Bound on use, not in
+        SIGNATURES: an older library given through CSN_LIB_PATH for an A/B run still loads."""
+        fn = load().csn_lstm_plan_bwd_launches
+        fn.restype, fn.argtypes = _c_int, [_c_void_p, _c_int]
+        return int(fn(self._plan, which))
+
     def forward(self, x_bti, w_ih, w_hh, b_ih, b_hh, want_all=False, h0=None, c0=None, want_state=False, y_all=None,
                 state_out=None):
         """-> (y_last, y_all); with want_state=True -> (y_last, y_all, h_n, c_n).  With input windows set (set_views)

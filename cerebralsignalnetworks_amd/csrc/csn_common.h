@@ -48,7 +48,7 @@ int fail(int status, const char* fmt, ...);
 // library keeps no mutable global state, so plans on different streams / threads / devices never share any.
 struct Options {
   bool cell_v1, no_persist, no_persist_bwd, persist_streams, no_xcd_local, no_rotate, no_fuse_x, no_beside, beside_128,
-      no_side_stream, fwd_ksplit, fwd_nsplit, fwd_flags, bwd_flags, dpoll_no_hint, fwd_hint, gemm_no_dma, gemm_no_256, gemm_generic, tn_no_tr, tn_no_stagger, filter_v1, tags_no_rearm, gemm_no_192, no_half_tiles, nt_no_w4, no_fwd_park;
+      no_side_stream, fwd_ksplit, fwd_nsplit, fwd_flags, bwd_flags, dpoll_no_hint, fwd_hint, gemm_no_dma, gemm_no_256, gemm_generic, tn_no_tr, tn_no_stagger, filter_v1, tags_no_rearm, gemm_no_192, no_half_tiles, nt_no_w4, no_fwd_park, bwd_no_merge;
   int chunk;       // timesteps per weight-stationary launch
   int tn_stages;   // LDS-DMA ring depth of the 256 x 256 weight-gradient kernel
 };
@@ -75,6 +75,7 @@ static inline Options options_from_env() {
   o.fwd_nsplit = on("CSN_FWD_NSPLIT");
   o.fwd_flags = on("CSN_FWD_FLAGS");
   o.bwd_flags = on("CSN_BWD_FLAGS");
+  o.bwd_no_merge = on("CSN_BWD_NO_MERGE");
   o.dpoll_no_hint = on("CSN_DPOLL_NO_HINT");
   o.fwd_hint = on("CSN_FWD_HINT");
   o.tn_no_stagger = on("CSN_TN_NO_STAGGER");

@@ -19,7 +19,8 @@
 //  2  weight-stationary forward (forward_persist: lstm_fwd_persist.hip or lstm_fwd_ns.hip, one launch per chunk
 //     diagonal, or per layer and chunk on streams of their own), backward of path 1.
 //  3  path 2 with the weight-stationary backward (backward_persist: lstm_bwd_persist.hip, one launch per chunk diagonal,
-//     the input-gradient GEMM inside the next launch) where its grouped form applies (bwd_grouped), else backward_il.
+//     the input-gradient GEMM inside the next launch; the diagonals with every layer in range merged into one launch)
+//     where its grouped form applies (bwd_grouped), else backward_il.
 //  4  exact float32, weight-stationary (forward_f32p / backward_f32p: lstm_f32_persist.hip), layer after layer.
 //  5  CU-resident recurrence (forward_resident / backward_resident: lstm_resident.hip), opt-in with CSN_LSTM_RESIDENT,
 //     H <= 128, both dtypes: path 0's workspace and host flow with the step loop of a chunk inside the kernel -- one
@@ -54,7 +55,7 @@ struct LayerWs {
 };
 struct WsLayout {
   LayerWs layer[8];
-  size_t x_c, x_blk, wih0_blk, dy_tm, tn_scratch, colsum, status, agree, agree_b, zeros_bh, f32_bias_part, total;
+  size_t x_c, x_blk, wih0_blk, dy_tm, tn_scratch, colsum, status, agree, agree_b, merge_cnt, zeros_bh, f32_bias_part, total;
   // weight-stationary paths: everything that must be zero at the start of a forward / a backward sits in ONE block each
   size_t zero_fwd, zero_fwd_bytes, zero_bwd, zero_bwd_bytes;
   bool fuse_x;
@@ -168,6 +169,8 @@ static WsLayout make_layout(const csnLstmDesc& d, int training, bool dropout, co
       w.layer[l].bflags = take((size_t)d.T * (Bpad / 64) * 3 * kPersistFlagLine * 4);
     }
     w.agree_b = take(((size_t)d.T + 8) * 8 * sizeof(unsigned long long));
+    // merged backward launches: rec_done[L][chunks] and gemm_done[L][chunks] (lstm_cell_blk.h), at most T chunks
+    w.merge_cnt = take((2 * (size_t)d.L * d.T * sizeof(unsigned) + 15) / 16 * 16);
     w.zero_bwd_bytes = off - w.zero_bwd;
   }
   if (training) {
@@ -512,6 +515,7 @@ struct csnLstmPlan {
   csn::SideCtx sc;
   csn::Prof prof;
   int dgates_copies = 0;      // what the last backward wrote per step (csn_lstm_plan_dgates_copies)
+  int bwd_launches[2] = {0, 0};    // last backward: recurrence launches, diagonals the merged one covered (csn_lstm_plan_bwd_launches)
   int half_launches[2] = {0, 0};   // recurrence launches of the last forward / backward on 32-row groups (csn_lstm_plan_half_tile_launches)
   csnGradReadyFn grad_cb = nullptr;      // csn_lstm_plan_set_grad_callback
   void* grad_cb_user = nullptr;
@@ -607,6 +611,14 @@ extern "C" int csn_lstm_plan_path(const csnLstmPlan* P) {
 
 extern "C" int csn_lstm_plan_dgates_copies(const csnLstmPlan* P) { return P == nullptr ? -1 : P->dgates_copies; }
 
+// Host-only diagnostic for the tests, exported beside the public header like csn_gemm_nt_w4_offsets_fit (cabi.py binds it
+// on use): the weight-stationary recurrence launches of the plan's LAST backward (which = 0), and how many chunk
+// diagonals the merged one of them covered (which = 1; 0 = none was merged: CSN_BWD_NO_MERGE=1, dropout, lengths, dh_n,
+// flags in place of data polls, H = 1024, one layer, fewer than two diagonals with every layer in range).  0 / 0 before
+// any backward and on the other paths; -1 for a null plan / other `which`.
+extern "C" int csn_lstm_plan_bwd_launches(const csnLstmPlan* P, int which) {
+  return (P == nullptr || which < 0 || which > 1) ? -1 : P->bwd_launches[which];
+}
 extern "C" int csn_lstm_plan_half_tile_launches(const csnLstmPlan* P, int which) {
   return (P == nullptr || which < 0 || which > 1) ? -1 : P->half_launches[which];
 }
@@ -1914,8 +1926,20 @@ static int backward_persist(Call& C, const BwdArgs& A) {
   DhAdd pending_drop[3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}; // layer and steps of pending[i]: what its dropout mask covers
   int npending = 0;
   if ((rc = prof_mark(g_prof, 2, st))) return rc;
+  // Merged launch: the diagonals on which EVERY layer is in range, [lag (NL - 1), nch - 1], hold the same workgroups
+  // with the same W_hh^T slices, carried dc and ring position (the tile height depends only on the layer count), and
+  // where nothing is enqueued between their launches (no dropout mask, no dh_n term, no lengths) they run as ONE launch
+  // of as many rounds: the two kernel boundaries around each input-gradient GEMM become chunk-level counters
+  // (lstm_cell_blk.h: PersistBwdArgs::nrounds).  Their GEMMs all have chunk * B rows -- the short chunk is the top
+  // layer's on the last of them, multiplied one launch later.  CSN_BWD_NO_MERGE=1: one launch per diagonal.
+  const int m_first = lag * (NL - 1), m_count = nch - m_first;
+  const bool merge = beside && !P.opt.bwd_no_merge && a.data_polls && C.dlen == nullptr && !drop_on(C) && dh_n == nullptr && m_count >= 2;
+  unsigned* const cnt = (unsigned*)(ws + w.merge_cnt);     // rec_done[NL][nch], then gemm_done[NL][nch]
+  P.bwd_launches[0] = P.bwd_launches[1] = 0;
   for (int dg = 0; dg < ndiag; ++dg) {
     int lay[4], chk[4], ns = 0;
+    const bool merged = merge && dg == m_first;
+    if (merged) dg = m_first + m_count - 1;       // what follows the launch is what follows its last diagonal
     for (int l = NL - 1; l >= 0; --l) {
       const int c = dg - lag * (NL - 1 - l);      // reverse chunk index of layer l on this diagonal
       if (c < 0 || c >= nch) continue;
@@ -1939,9 +1963,35 @@ static int backward_persist(Call& C, const BwdArgs& A) {
       const Chunk k = chunk_at(C, c);
       S.t_hi = T - 1 - k.t0;
       S.nsteps = k.nsteps;
+      S.cnt_pub = S.cnt_wait = -1;
       lay[ns] = l;
       chk[ns] = c;
       ++ns;
+    }
+    a.nrounds = 1;
+    a.chunk = Cz;
+    a.cnt = cnt;
+    if (merged) {
+      // the slots hold the run's LAST diagonal (the GEMMs left for the next launch are formed from it below): the launch
+      // starts m_count - 1 full chunks above it
+      CSN_REQUIRE(ns == NL && npending == NL - 1, "backward_persist: merged launch without every layer");
+      a.nrounds = m_count;
+      for (int i = 0; i < ns; ++i) {
+        PersistBwdSlot& S = a.slot[i];
+        const int c0 = chk[i] - (m_count - 1);
+        S.t_hi += (m_count - 1) * Cz;
+        S.nsteps = Cz;
+        if (lay[i] > 0) S.cnt_pub = lay[i] * nch + c0;
+        if (lay[i] < NL - 1) S.cnt_wait = (NL + lay[i] + 1) * nch + c0;
+      }
+      for (int i = 0; i < npending; ++i) CSN_REQUIRE(pending[i].M == Cz * B, "backward_persist: merged launch with a short GEMM");
+      a.wk_wait = a.slot[0].cnt_pub - 1;
+      a.wk_pub = a.slot[1].cnt_wait + 1;
+      a.wk_stride = nch + lag;
+      for (int i = 1; i + 1 < ns; ++i)
+        CSN_REQUIRE(a.slot[i].cnt_pub == a.slot[0].cnt_pub - i * a.wk_stride && a.slot[i + 1].cnt_wait == a.slot[1].cnt_wait - i * a.wk_stride,
+                    "backward_persist: merged launch whose counters are not evenly spaced");
+      P.bwd_launches[1] = m_count;
     }
     if (ns == 0) {
       // a diagonal without a layer in range (one chunk per layer, T <= chunk, and the layers two launches apart): nothing
@@ -1964,7 +2014,7 @@ static int backward_persist(Call& C, const BwdArgs& A) {
     a.MT = half ? 2 * MT : MT;
     if (half) {
       for (int i = 0; i < ns; ++i) a.slot[i].flags += (size_t)T * MT * kPersistFlagLine;
-      ++P.half_launches[1];
+      P.half_launches[1] += merged ? m_count : 1;     // (a merged launch: once per diagonal it covers)
     }
     DhAdd launch_adds[3], launch_drops[3];
     int nadds = 0;
@@ -1980,6 +2030,12 @@ static int backward_persist(Call& C, const BwdArgs& A) {
     if ((rc = launch_bwd_persist(a, st, C.dlen))) return rc;
     if ((rc = prof_pair(g_prof, 1, true, st))) return rc;
     ++n_launch;
+    if (merged)       // back to the last diagonal's own chunk: the GEMMs formed below are those it leaves behind
+      for (int i = 0; i < ns; ++i) {
+        const Chunk k = chunk_at(C, chk[i]);
+        a.slot[i].t_hi = T - 1 - k.t0;
+        a.slot[i].nsteps = k.nsteps;
+      }
     for (int i = 0; i < ndrops; ++i)
       if ((rc = drop_bwd(C, launch_drops[i].l - 1, launch_drops[i].t_lo, launch_drops[i].t_hi, st))) return rc;
     for (int i = 0; i < nadds; ++i)
@@ -2000,6 +2056,7 @@ static int backward_persist(Call& C, const BwdArgs& A) {
                                        (float*)(ws + L.dx) + (size_t)t_lo * B * H, (t_hi - t_lo + 1) * B, H, (int)G};
     }
   }
+  P.bwd_launches[0] = n_launch;
   if ((rc = prof_end(C, 1, n_launch, T * NL))) return rc;
 
   if (A.dx != nullptr && (rc = dx_out(C, A.dx, st))) return rc;
@@ -2023,6 +2080,7 @@ static int run_forward(Call& C, const FwdArgs& A) {
   return forward_v1(C, A);
 }
 static int run_backward(Call& C, const BwdArgs& A) {
+  C.P.bwd_launches[0] = C.P.bwd_launches[1] = 0;     // (only the weight-stationary backward counts them)
   if (C.P.resident) return backward_resident(C, A);
   if (bwd_grouped(&C.P, C.T)) return backward_persist(C, A);
   if (C.w.il) return backward_il(C, A);

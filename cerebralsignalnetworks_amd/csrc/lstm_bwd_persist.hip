@@ -21,6 +21,12 @@
 // 32-row groups instead, 2 MT tiles per layer -- MFMA issue, the reduction and the epilogue's store issue of a step
 // all halve.  A row's arithmetic does not depend on the rows beside it, a workgroup writes and re-arms exactly the
 // (row, unit) pieces it owns at either height, and the height changes only between launches: same bits, same ring.
+//
+// Rounds (PersistBwdArgs::nrounds): the chunk diagonals on which every layer is in range hold the same workgroups, slices,
+// carried dc and ring position, so the host issues them as ONE launch and the kernel loops over them around its step
+// loop.  What a kernel boundary did for the input-gradient GEMM between two diagonals -- make a chunk's row-major dgates
+// visible to the workers, and their dx to the layer below -- two chunk-level counters do: round_publish / round_wait
+// below.  Nothing inside a chunk changes; a launch of one round is the launch it always was.
 #include "csn_common.h"
 #include "lstm_cell_common.h"
 #include "lstm_cell_blk.h"
@@ -82,6 +88,46 @@ struct PersistNoLens {};
 template <bool MASK> struct PersistLensArg { typedef PersistNoLens type; };
 template <> struct PersistLensArg<true> { typedef PersistLens type; };
 
+// Chunk-level hand-off between the rounds of a merged launch (PersistBwdArgs::nrounds): row-major dgates and dx cross
+// XCDs through plain / nt stores, so visibility is an agent-scope release by the producers and an agent-scope acquire by
+// every consuming workgroup.  Both are called by ALL threads of a workgroup, under a uniform condition.
+// Publish: every wave's stores have left it, then ONE lane writes the XCD's L2 back and counts the workgroup in.
+// (the one lane: compared afresh at every use -- as a loop invariant the lane mask was a pair of SGPRs kept, and spilled,
+// across the step loop)
+__device__ __forceinline__ bool round_leader() {
+  unsigned t = threadIdx.x;
+  asm volatile("" : "+v"(t));
+  return t == 0u;
+}
+__device__ __forceinline__ void round_publish(unsigned* word) {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (round_leader()) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // (the fence's own wait can be dropped by the compiler)
+    __hip_atomic_fetch_add(word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+// Wait: ONE lane polls the counter (the kernel's bounded spin: same time-out, same sticky status word, gives up when it
+// is set), then the acquire; the barrier holds the other waves until the invalidate has completed.  No load of the
+// handed-off bytes may be issued in front of this.
+__device__ __forceinline__ void round_wait(const unsigned* word, unsigned want, unsigned* error_flag) {
+  if (round_leader()) {
+    const unsigned long long t_begin = wall_clock64();
+    while (__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < want) {
+      __builtin_amdgcn_s_sleep(1);
+      if (__hip_atomic_load(error_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) break;
+      if (wall_clock64() - t_begin > kBwdSpinTimeoutTicks) {
+        __hip_atomic_store(error_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        break;
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  }
+  __syncthreads();
+}
+
 template <int NUT, int KS, bool DPOLL, bool MASK = false, int RG = 4>
 __global__ void __launch_bounds__(256) lstm_bwd_persist_kernel(PersistBwdArgs a, typename PersistLensArg<MASK>::type lens) {
 #ifndef CSN_BWD_RING
@@ -101,29 +147,63 @@ __global__ void __launch_bounds__(256) lstm_bwd_persist_kernel(PersistBwdArgs a,
   const unsigned long long t_entry_ = wall_clock64();
 #endif
   const int nslices = H / (16 * NUT);
-  int grp, slice;
+  // (the tile bodies below run at the kernel's SGPR limit: nothing of the recurrence workgroups' set-up may stay alive
+  // across them, so the block coordinates are formed again behind them from an opaque copy of the block index, and the
+  // round loop reads its arguments from the kernel-argument segment through a pointer that is opaque in every iteration
+  // -- a loop invariant kept in an SGPR across the tile bodies was a spilled SGPR in every instantiation)
+  unsigned bid = blockIdx.x;
   if (a.xcd_groups) {
-    grp = blockIdx.x & 7;
-    slice = blockIdx.x >> 3;
+    const int wgrp = (int)(bid & 7u), wslice = (int)(bid >> 3);
     const int ngroups = a.nslots * MT, gs = a.grid_slices;
-    if (grp >= ngroups || slice >= nslices) {
+    if (wgrp >= ngroups || wslice >= nslices) {
       // no recurrence work for this workgroup: it walks the tiles of the launch's input-gradient GEMMs.  Workers of
       // one XCD (equal blockIdx.x % 8) get consecutive indices [base, base + here), so they work on neighbouring tiles.
       if (a.ngemm > 0) {
         const int idle_here = gs - nslices;
-        const unsigned base = grp <= ngroups ? (unsigned)(grp * idle_here)
-                                             : (unsigned)(ngroups * idle_here + (grp - ngroups) * gs);
-        const unsigned here = (unsigned)(grp < ngroups ? idle_here : gs);
-        const unsigned local = (unsigned)(grp < ngroups ? slice - nslices : slice);
+        const unsigned base = wgrp <= ngroups ? (unsigned)(wgrp * idle_here)
+                                              : (unsigned)(ngroups * idle_here + (wgrp - ngroups) * gs);
+        const unsigned here = (unsigned)(wgrp < ngroups ? idle_here : gs);
+        const unsigned local = (unsigned)(wgrp < ngroups ? wslice - nslices : wslice);
         const unsigned nworkers = (unsigned)(ngroups * idle_here + (8 - ngroups) * gs);
-        for (int i = 0; i < a.ngemm; ++i)
-          beside_gemm_tiles(a.gemm[i], reinterpret_cast<char*>(red), base, here, local, nworkers, ((a.gemm_wide >> i) & 1) != 0);
+        // round r of a merged launch: the GEMMs the host would have listed for diagonal first + r -- those of round 0
+        // moved down r chunks, same shape, so the same gemm_wide decision and the same walk.  From round 1 on the
+        // operand comes from this launch: GEMM i waits until every workgroup of slot i's layer has left the chunk
+        // (word wk_wait + r - i wk_stride = slot i's cnt_pub + r - 1).  A round's output is the dy of slot i + 1 in the
+        // next round: published (word wk_pub + r - i wk_stride = slot i + 1's cnt_wait + r + 1) unless the next launch reads it.
+        typedef const PersistBwdArgs __attribute__((address_space(4)))* KArgs;
+        KArgs ap = (KArgs)__builtin_amdgcn_kernarg_segment_ptr();
+        for (int r = 0;; ++r) {
+          asm volatile("" : "+s"(ap));
+          if (r >= ap->nrounds) break;
+          for (int i = 0;; ++i) {
+            asm volatile("" : "+s"(ap));
+            if (i >= ap->ngemm) break;
+            BesideGemm g;
+            g.A = ap->gemm[i].A; g.Bt = ap->gemm[i].Bt; g.C = ap->gemm[i].C;
+            g.M = ap->gemm[i].M; g.N = ap->gemm[i].N; g.K = ap->gemm[i].K;
+            if (r > 0) {
+              round_wait(ap->cnt + (ap->wk_wait + r - i * ap->wk_stride), (unsigned)(ap->MT * nslices), ap->error_flag);
+              const unsigned down = (unsigned)(r * ap->chunk) * (unsigned)ap->B;      // rows below round 0's, < T * B
+              g.A -= (size_t)down * (unsigned)g.K;
+              g.C -= (size_t)down * (unsigned)g.N;
+            }
+            beside_gemm_tiles(g, reinterpret_cast<char*>(red), base, here, local, nworkers, ((ap->gemm_wide >> i) & 1) != 0);
+            asm volatile("" : "+s"(ap));
+            if (r + 1 < ap->nrounds) round_publish(ap->cnt + (ap->wk_pub + r - i * ap->wk_stride));
+          }
+        }
       }
       return;
     }
+  }
+  asm volatile("" : "+s"(bid));
+  int grp, slice;
+  if (a.xcd_groups) {
+    grp = (int)(bid & 7u);
+    slice = (int)(bid >> 3);
   } else {
-    grp = blockIdx.x / nslices;
-    slice = blockIdx.x % nslices;
+    grp = (int)bid / nslices;
+    slice = (int)bid % nslices;
   }
   const PersistBwdSlot& S = a.slot[grp / MT];
   const int mt = grp % MT;
@@ -140,7 +220,7 @@ __global__ void __launch_bounds__(256) lstm_bwd_persist_kernel(PersistBwdArgs a,
   bf16_t* const dg_blk_all = S.dg_blk_all;
   unsigned* const flags = S.flags + (size_t)mt * kPersistFlagLine;
   const size_t flag_step = (size_t)MT * kPersistFlagLine;
-  const int t_hi = S.t_hi, nsteps = S.nsteps;
+  int t_hi = S.t_hi, nsteps = S.nsteps;       // of the round: a merged launch walks nrounds chunks
   // hand-off by DATA (see lstm_fwd_persist.hip): ring of 4 slabs, dgates_s in slot s & 3, unwritten regions hold the
   // all-ones sentinel; no store drain and no flag on the producer side
   constexpr bool dpoll = DPOLL;
@@ -212,7 +292,7 @@ __global__ void __launch_bounds__(256) lstm_bwd_persist_kernel(PersistBwdArgs a,
   // saved tensors of one step, requested a full step early (behind the MFMAs of the step before)
   bf16x8 gt_n[NPASS][2];
   float4 cpv_n[NPASS], dy_n[NPASS];
-  auto request_saved = [&](int t) {
+  auto request_saved = [&](int t, const float* dy) {
 #pragma unroll
     for (int ps = 0; ps < NPASS; ++ps) {
       cpv_n[ps] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -230,7 +310,6 @@ __global__ void __launch_bounds__(256) lstm_bwd_persist_kernel(PersistBwdArgs a,
       }
     }
   };
-  request_saved(t_hi);
   // data polls: ONE buffer resource over the ring of 4 slabs, the slab of a step is a scalar offset -- a resource per
   // slab and use (read, write, re-arm) ran the kernel out of SGPRs; flags: a resource per slab (T slabs can exceed 2 GiB)
   const __amdgpu_buffer_rsrc_t ring_rsrc = __builtin_amdgcn_make_buffer_rsrc(
@@ -257,6 +336,28 @@ __global__ void __launch_bounds__(256) lstm_bwd_persist_kernel(PersistBwdArgs a,
       }
     }
   };
+  // Rounds of a merged launch (one round otherwise): wreg, dcn, cc, the ring and `local` carry over -- what a kernel
+  // boundary would have reloaded.  The first step's saved tensors are requested BEHIND the round's wait and acquire: its
+  // dy is the dx a GEMM of this launch wrote on other XCDs, and a load in front of the acquire could leave a stale line.
+  // (H = 1024 -- 32 slices, no workers, never merged -- has no SGPR left even for r: one round at compile time)
+  // (the round state that lives across the step loop is r alone: everything else a round boundary needs is read from the
+  // kernel-argument segment there, through a pointer that is opaque to the compiler, see the workers' loop)
+  typedef const PersistBwdArgs __attribute__((address_space(4)))* KArgs;
+  KArgs ap = (KArgs)__builtin_amdgcn_kernarg_segment_ptr();
+  for (int r = 0;; ++r) {
+  if (KS < 32 && r > 0) {
+    asm volatile("" : "+s"(ap));
+    const int cnt_wait = ap->slot[grp / ap->MT].cnt_wait;
+    if (cnt_wait >= 0) {
+      const int gs = ap->grid_slices, ngroups = ap->nslots * ap->MT;
+      round_wait(ap->cnt + (cnt_wait + r), (unsigned)(ngroups * (gs - nslices) + (8 - ngroups) * gs), ap->error_flag);
+    }
+  }
+  {
+    const float* dy_r = dy;        // (opaque: the null test is made here, not kept as a lane mask across the step loop)
+    asm volatile("" : "+s"(dy_r));
+    request_saved(t_hi, dy_r);
+  }
   for (int s = 0; s < nsteps; ++s) {
     const int t = t_hi - s;
     bf16x8 gt[NPASS][2];
@@ -441,7 +542,7 @@ __global__ void __launch_bounds__(256) lstm_bwd_persist_kernel(PersistBwdArgs a,
       } while (again);
     }
     // the next step's saved tensors: in flight during this step's reduction and epilogue
-    if (s + 1 < nsteps) request_saved(t - 1);
+    if (s + 1 < nsteps) request_saved(t - 1, dy);
     __builtin_amdgcn_sched_barrier(0);
     CSN_BSTAMP(1);     // dgates loads + MFMA
 
@@ -561,6 +662,14 @@ __global__ void __launch_bounds__(256) lstm_bwd_persist_kernel(PersistBwdArgs a,
     }
     CSN_BSTAMP(5);     // signal
   }
+  if (KS >= 32) break;
+  asm volatile("" : "+s"(ap));
+  if (r + 1 >= ap->nrounds) break;
+  const int cnt_pub = ap->slot[grp / ap->MT].cnt_pub;
+  if (cnt_pub >= 0) round_publish(ap->cnt + (cnt_pub + r));
+  t_hi -= nsteps;
+  nsteps = t_hi + 1 < ap->chunk ? t_hi + 1 : ap->chunk;
+  }
 
 #pragma unroll
   for (int ps = 0; ps < NPASS; ++ps)
@@ -626,6 +735,9 @@ int launch_bwd_persist(const PersistBwdArgs& a, hipStream_t st, const int* lengt
               a.half_tiles ? 32 : 64, a.Bpad);
   CSN_REQUIRE(!a.half_tiles || (a.xcd_groups && lengths == nullptr), "launch_bwd_persist: 32-row groups need the grouped form and no lengths");
   CSN_REQUIRE(a.ngemm >= 0 && a.ngemm <= 3 && (a.ngemm == 0 || a.xcd_groups), "launch_bwd_persist: bad GEMM list");
+  CSN_REQUIRE(a.nrounds == 1 || (a.nrounds > 1 && a.xcd_groups && a.data_polls && lengths == nullptr && a.ngemm == a.nslots - 1 &&
+                                 a.ngemm >= 1 && a.H < 1024 && a.chunk >= 1 && a.cnt != nullptr),
+              "launch_bwd_persist: a merged launch needs the grouped form with data polls, no lengths and a GEMM per layer boundary");
   for (int i = 0; i < a.ngemm; ++i)
     CSN_REQUIRE(a.gemm[i].K % 64 == 0 && a.gemm[i].K <= (1 << 22) && a.gemm[i].N % 4 == 0 && a.gemm[i].M > 0, "launch_bwd_persist: GEMM %d shape", i);
   switch (a.H) {

@@ -129,7 +129,12 @@ struct PersistBwdSlot {
   bf16_t* dgates;          // [T, B, 4H] interleaved, row-major (GEMM operand)
   bf16_t* dg_blk_all;      // [T][Bpad * 4H] fragment-major slabs (slot t = dgates_t); never reused in a backward
   unsigned* flags;         // [T][MT][kPersistFlagLine], zeroed per backward (MT = tiles of the launch's height; the two heights use lines of their own)
-  int t_hi, nsteps;        // steps t_hi, t_hi - 1, ..., t_hi - nsteps + 1
+  int t_hi, nsteps;        // steps t_hi, t_hi - 1, ..., t_hi - nsteps + 1 (of a merged launch: those of its first round)
+  // merged launches (PersistBwdArgs::nrounds > 1), indices into PersistBwdArgs::cnt or -1: in round r the layer's
+  // workgroups add to word cnt_pub + r when they leave the round's chunk (rec_done of that chunk; -1: layer 0, nobody
+  // multiplies its dgates inside the launch) and, from round 1 on, enter the chunk only once word cnt_wait + r has
+  // counted every worker (gemm_done of the layer above at that chunk; -1: the top layer, its dy is the caller's)
+  int cnt_pub, cnt_wait;
 };
 struct PersistBwdArgs {
   PersistBwdSlot slot[4];
@@ -146,7 +151,19 @@ struct PersistBwdArgs {
   unsigned* error_flag;
   int B, H, T, Bpad, MT;   // MT: M-tiles per layer at the launch's tile height
   int half_tiles;          // != 0: hand-off groups of 32 rows (MT = Bpad / 32), else 64 (MT = Bpad / 64); grouped form only
+  // Merged launch: nrounds consecutive chunk diagonals in one launch (1: a launch of one diagonal, as ever; > 1 only in
+  // the grouped form with data polls, every layer in range in every round and ngemm = nslots - 1 GEMMs of M = chunk * B
+  // rows).  Round r is diagonal first + r: a slot's chunk lies `chunk` steps below that of round r - 1 (only the last
+  // round's may be short), gemm[i] is the host's gemm[i] moved down r chunks (slot i's chunk of round r - 1, its output
+  // the dy of slot i + 1 in round r + 1), and the two kernel boundaries that a GEMM stands between are the counters
+  // cnt[] (zeroed per backward): see PersistBwdSlot::cnt_pub / cnt_wait.
+  int nrounds, chunk;
+  unsigned* cnt;
+  // the same words as the GEMM workers index them (slot i is layer nslots - 1 - i, two chunks behind slot i - 1): GEMM i
+  // of round r waits on word wk_wait + r - i * wk_stride and adds to word wk_pub + r - i * wk_stride
+  int wk_wait, wk_pub, wk_stride;
 };
+static_assert(sizeof(PersistBwdArgs) <= 4096, "PersistBwdArgs is passed by value: the kernel-argument segment holds 4096 bytes");
 bool bwd_persist_supported(int B, int H, int dtype, const Options& opt);
 int bwd_persist_slices(int H);
 // lengths != NULL (variable-length batches): [B] device array; the masked instantiation of the kernel

@@ -233,7 +233,8 @@ int csn_lstm_plan_path(const csnLstmPlan* plan);
 int csn_lstm_plan_dgates_copies(const csnLstmPlan* plan);
 /* How many weight-stationary recurrence launches of the plan's LAST forward (which = 0) / backward (which = 1) ran on
  * hand-off groups of 32 rows instead of 64 (launches whose 64-row groups would cover at most half of the XCDs;
- * CSN_NO_HALF_TILES=1 keeps 64 rows everywhere: 0).  Diagnostic; -1 for a null plan / other `which`. */
+ * CSN_NO_HALF_TILES=1 keeps 64 rows everywhere: 0; a merged backward launch counts once per chunk diagonal it covers, so
+ * the figure does not depend on CSN_BWD_NO_MERGE).  Diagnostic; -1 for a null plan / other `which`. */
 int csn_lstm_plan_half_tile_launches(const csnLstmPlan* plan, int which);
 /* Name of the device function that advances the recurrence on this plan's path: which = 0 forward, 1 backward
  * ("lstm_fwd_persist_kernel", "lstm_fwd_ns_kernel", "lstm_bwd_persist_kernel", "lstm_cell_fwd_il_kernel", ... -- the
