@@ -45,6 +45,7 @@
 #include "lstm_dropout.h"
 #include "lstm_f32_persist.h"
 #include "lstm_resident.h"
+#include "lstm_schedule.h"
 
 namespace csn {
 
@@ -626,10 +627,7 @@ extern "C" int csn_lstm_plan_half_tile_launches(const csnLstmPlan* P, int which)
 // does a backward of this plan over T steps take the grouped weight-stationary form?  (a call passes the steps it runs --
 // with lengths the longest row --, csn_lstm_plan_kernel_name the plan's T)
 static bool bwd_grouped(const csnLstmPlan* P, int T) {
-  if (!P->w.persist_bwd) return false;
-  const int MTg = (P->d.B + 63) / 64, nchg = (T + P->opt.chunk - 1) / P->opt.chunk;
-  const int slots = P->d.L < nchg ? P->d.L : nchg;
-  return slots <= 4 && slots * MTg <= 8 && !P->opt.persist_streams;
+  return csn::bwd_grouped(P->w.persist_bwd, P->d.B, P->d.L, T, P->opt.chunk, P->opt.persist_streams);
 }
 
 extern "C" const char* csn_lstm_plan_kernel_name(const csnLstmPlan* P, int which) {
@@ -1052,15 +1050,9 @@ static int prep_row_major(const Call& C, const FwdArgs& A) {
   return CSN_OK;
 }
 
-// chunk c of the sequence: steps [t0, t0 + nsteps).  The backward walks the chunks from the end: its reverse chunk c
-// covers the steps [t_hi - nsteps + 1, t_hi] with t_hi = T - 1 - t0.
-struct Chunk { int t0, nsteps; };
-static Chunk chunk_at(const Call& C, int c) {
-  const int t0 = c * C.Cz;
-  return Chunk{t0, t0 + C.Cz <= C.T ? C.Cz : C.T - t0};
-}
-// is step (or reverse step) t the last one of its chunk?
-static bool ends_chunk(const Call& C, int t) { return (t + 1) % C.Cz == 0 || t == C.T - 1; }
+// chunk c of this call's steps, and whether step (or reverse step) t ends its chunk (lstm_schedule.h)
+static Chunk chunk_at(const Call& C, int c) { return chunk_at(C.T, C.Cz, c); }
+static bool ends_chunk(const Call& C, int t) { return ends_chunk(C.T, C.Cz, t); }
 
 // layer l finished chunk c -> xproj_{l+1}[chunk c] = h_l[chunk c] W_ih^T + b
 static int xproj_chunk_gemm(const Call& C, int l, int c, hipStream_t on) {
@@ -1610,6 +1602,9 @@ static int forward_il(Call& C, const FwdArgs& A) {
 //
 // Stream form (any number of layers / M-tiles): layer l runs chunk after chunk on its own stream, the GEMMs
 // on the side stream, ordered by events; placement-independent hand-off.
+//
+// Which form a call takes and what each launch holds is fwd_persist_form / fwd_persist_schedule (lstm_schedule.h); this
+// function sets up the call, then enqueues that schedule entry by entry.
 static int forward_persist(Call& C, const FwdArgs& A) {
   Plan& P = C.P;
   const WsLayout& w = C.w;
@@ -1624,13 +1619,12 @@ static int forward_persist(Call& C, const FwdArgs& A) {
   const float* c0 = A.c0;
   const int B = C.B, T = C.T, H = C.H, NL = C.NL;
   const int Bpad = (B + 63) / 64 * 64, MT = Bpad / 64;
-  const int Cz = C.Cz;
-  const int nch = (T + Cz - 1) / Cz;
   const int training = P.training;
   if ((rc = prep_fast(C, A))) return rc;
   // one fill: the flag lines of every layer, the XCD agreement words
   CSN_HIP_CHECK(hipMemsetAsync(ws + w.zero_fwd, 0, w.zero_fwd_bytes, st));
-  auto fill_slot = [&](PersistFwdSlot& S, int l, int c) {
+  auto fill_slot = [&](PersistFwdSlot& S, const FwdSlot& s) {
+    const int l = s.layer;
     const LayerWs& L = w.layer[l];
     S.w_blk = (const bf16_t*)(ws + L.whh_blk);
     S.xproj = (const float*)(ws + L.xproj);
@@ -1649,9 +1643,8 @@ static int forward_persist(Call& C, const FwdArgs& A) {
       S.bias = (const float*)(ws + L.bias);
       S.I = C.d.I;
     }
-    const Chunk k = chunk_at(C, c);
-    S.t0 = k.t0;
-    S.nsteps = k.nsteps;
+    S.t0 = s.t0;
+    S.nsteps = s.nsteps;
   };
   PersistFwdArgs a{};
   a.error_flag = (unsigned*)(ws + w.status);
@@ -1684,52 +1677,37 @@ static int forward_persist(Call& C, const FwdArgs& A) {
   int n_launch = 0;
   P.half_launches[0] = 0;
 
-  const int max_slots = NL < nch ? NL : nch;
-  const int fwd_slices = w.fwd_ns ? fwd_ns_slices(H) : fwd_persist_slices(H);
   auto launch_fwd = [&](const PersistFwdArgs& args, hipStream_t on) {
     return w.fwd_ns ? launch_fwd_ns(args, on) : launch_fwd_persist(args, on);
   };
-  const bool grouped = max_slots <= 4 && max_slots * MT <= 8 && fwd_slices <= 32 &&
-                       !P.opt.persist_streams;
-  if (grouped) {
-    const int ndiag = nch + NL - 1;
+  const FwdSchedIn in{T, B, H, NL, C.Cz, w.fwd_ns, P.opt.persist_streams, P.opt.no_half_tiles};
+  const FwdForm form = fwd_persist_form(in);
+  const std::vector<FwdLaunch> sched = fwd_persist_schedule(in);
+  if (form == FwdForm::grouped) {
     const bool try_local = !P.opt.no_xcd_local;
     if ((rc = prof_mark(g_prof, 0, st))) return rc;
-    for (int dg = 0; dg < ndiag; ++dg) {
-      int lay[4], chk[4], ns = 0;
-      for (int l = 0; l < NL; ++l) {
-        const int c = dg - l;
-        if (c < 0 || c >= nch) continue;
-        lay[ns] = l;
-        chk[ns] = c;
-        fill_slot(a.slot[ns], l, c);
-        ++ns;
+    a.xcd_groups = 1;
+    for (const FwdLaunch& q : sched) {
+      for (int i = 0; i < q.nslots; ++i) {
+        fill_slot(a.slot[i], q.slot[i]);
+        if (q.half) a.slot[i].flags += ((size_t)T + 1) * MT * kPersistFlagLine;      // the 32-row tiles' own lines
       }
-      a.nslots = ns;
-      a.xcd_groups = 1;
-      // few groups (the wavefront's fill and drain, small batches): 32-row groups, twice as many, so that the launch
-      // spreads over all eight XCDs and every step of its chain handles half the rows (K-split kernel only)
-      const bool half = !w.fwd_ns && !P.opt.no_half_tiles && 2 * ns * MT <= 8;
-      a.half_tiles = half ? 1 : 0;
-      a.MT = half ? 2 * MT : MT;
-      if (half) {
-        for (int i = 0; i < ns; ++i) a.slot[i].flags += ((size_t)T + 1) * MT * kPersistFlagLine;
-        ++P.half_launches[0];
-      }
-      a.agree = try_local ? (unsigned long long*)(ws + w.agree) + (size_t)dg * 8 : nullptr;
+      a.nslots = q.nslots;
+      a.half_tiles = q.half ? 1 : 0;
+      a.MT = q.MT;
+      if (q.half) ++P.half_launches[0];
+      a.agree = try_local ? (unsigned long long*)(ws + w.agree) + (size_t)q.agree * 8 : nullptr;
       if ((rc = prof_pair(g_prof, 0, false, st))) return rc;
       if ((rc = launch_fwd(a, st))) return rc;
       if ((rc = prof_pair(g_prof, 0, true, st))) return rc;
       ++n_launch;
-      for (int i = 0; i < ns; ++i)      // layer l finished chunk c -> xproj_{l+1}[chunk c], before the next launch
-        if (lay[i] + 1 < NL && (rc = xproj_chunk_gemm(C, lay[i], chk[i], st))) return rc;
+      for (int i = 0; i < q.nslots; ++i)      // layer l finished chunk c -> xproj_{l+1}[chunk c], before the next launch
+        if (q.slot[i].feeds_next && (rc = xproj_chunk_gemm(C, q.slot[i].layer, q.slot[i].chunk, st))) return rc;
     }
     return prof_end(C, 0, n_launch, T * NL);
   }
 
-  // every launch needs ALL its workgroups resident (one per CU): layers on streams of their own may only run side
-  // by side while together they fit the chip; otherwise everything goes down the caller's stream, layer after layer
-  if (NL * fwd_slices * MT > 256) side = st;
+  if (form == FwdForm::caller_stream) side = st;
   hipStream_t ls[8];
   ls[0] = st;
   for (int l = 1; l < NL; ++l) {
@@ -1743,17 +1721,17 @@ static int forward_persist(Call& C, const FwdArgs& A) {
   a.agree = nullptr;
   a.half_tiles = 0;
   a.MT = MT;
-  for (int c = 0; c < nch; ++c) {
-    for (int l = 0; l < NL; ++l) {
-      fill_slot(a.slot[0], l, c);
-      if ((rc = launch_fwd(a, ls[l]))) return rc;
-      ++n_launch;
-      if (l + 1 < NL) {
-        // layer l finished chunk c -> GEMM xproj_{l+1}[chunk] on the side stream -> layer l+1 may start it
-        if ((rc = hand_off(sc, ls[l], side))) return rc;
-        if ((rc = xproj_chunk_gemm(C, l, c, side))) return rc;
-        if (side != ls[l + 1] && (rc = hand_off(sc, side, ls[l + 1]))) return rc;
-      }
+  for (const FwdLaunch& q : sched) {
+    const FwdSlot& s = q.slot[0];
+    const int l = s.layer;
+    fill_slot(a.slot[0], s);
+    if ((rc = launch_fwd(a, ls[l]))) return rc;
+    ++n_launch;
+    if (s.feeds_next) {
+      // layer l finished chunk c -> GEMM xproj_{l+1}[chunk] on the side stream -> layer l+1 may start it
+      if ((rc = hand_off(sc, ls[l], side))) return rc;
+      if ((rc = xproj_chunk_gemm(C, l, s.chunk, side))) return rc;
+      if (side != ls[l + 1] && (rc = hand_off(sc, side, ls[l + 1]))) return rc;
     }
   }
   // the caller's stream resumes after every layer stream (and the side stream) has drained
@@ -1873,6 +1851,9 @@ static int backward_il(Call& C, const BwdArgs& A) {
 // the launch was measured too: the event waits between the streams cost ~30 us per launch, most of the gain.)
 // CSN_NO_BESIDE: lag one chunk, GEMM between two launches.
 // The weight / bias gradients follow once the recurrence is complete.
+//
+// What each launch holds, which diagonals merge and what follows a launch on the stream is bwd_persist_schedule
+// (lstm_schedule.h); this function sets up the call, then enqueues that schedule entry by entry.
 static int backward_persist(Call& C, const BwdArgs& A) {
   Plan& P = C.P;
   const WsLayout& w = C.w;
@@ -1884,10 +1865,6 @@ static int backward_persist(Call& C, const BwdArgs& A) {
   const int64_t G = C.G;
   const int Bpad = (B + 63) / 64 * 64, MT = Bpad / 64;
   const int Cz = C.Cz;
-  const int nch = (T + Cz - 1) / Cz;
-  const bool beside = NL > 1 && NL <= 4 && bwd_persist_slices(H) <= 28 && G % 64 == 0 && !P.opt.no_beside;
-  const int lag = beside ? 2 : 1;
-  const int ndiag = nch + lag * (NL - 1);
   int rc;
   // one fill: carried dc and flag lines of every layer, the XCD agreement words (zeros_bh: csn_lstm_workspace_init)
   CSN_HIP_CHECK(hipMemsetAsync(ws + w.zero_bwd, 0, w.zero_bwd_bytes, st));
@@ -1895,14 +1872,6 @@ static int backward_persist(Call& C, const BwdArgs& A) {
   // the gradient w.r.t. c0)
   for (int l = 0; l < NL; ++l)
     if ((rc = seed_dc_carry(C, l, A.dc_n, true))) return rc;
-  // gradient w.r.t. h_n of layer l - 1: added to row T-1 of layer l's input gradient once the GEMM of that chunk has
-  // run (inline, or beside the recurrence in the next launch), before the launch that runs layer l - 1's first chunk
-  // (with lengths: after the GEMM of EVERY chunk, at the rows whose last step lies in it)
-  // (dropout: the mask of that chunk goes between the two -- behind the launch that ran the GEMM, in front of the term)
-  struct DhAdd { int l, t_lo, t_hi; };       // l = 0: none
-  auto add_dh_n = [&](const DhAdd& q) -> int {
-    return add_dh_n_rows(C, dh_n + (size_t)(q.l - 1) * B * H, (float*)(ws + w.layer[q.l].dx), q.t_lo, q.t_hi, st);
-  };
   const bool try_local = !P.opt.no_xcd_local;
 
   PersistBwdArgs a{};
@@ -1916,43 +1885,52 @@ static int backward_persist(Call& C, const BwdArgs& A) {
 #ifdef CSN_SLAB_TAGS
   if (a.data_polls && P.opt.tags_no_rearm) a.data_polls |= 4;
 #endif
+  a.chunk = Cz;
+  a.cnt = (unsigned*)(ws + w.merge_cnt);     // merged launches: rec_done[NL][nch], then gemm_done[NL][nch]
   P.dgates_copies = 2;     // hand-off slabs + the row-major copy the GEMMs read (csn_lstm_plan_dgates_copies)
   if (a.data_polls)        // the ring of 4 hand-off slabs of every layer starts as sentinel
     for (int l = 0; l < NL; ++l) CSN_HIP_CHECK(hipMemsetAsync(ws + w.layer[l].dg_blk_all, 0xff, (size_t)4 * Bpad * G * 2, st));
   int n_launch = 0;
   P.half_launches[1] = 0;
-  BesideGemm pending[3];           // GEMMs of the chunks finished by the previous launch
-  DhAdd pending_add[3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};  // dh_n term that follows pending[i] (layer 0: none)
-  DhAdd pending_drop[3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}; // layer and steps of pending[i]: what its dropout mask covers
-  int npending = 0;
-  if ((rc = prof_mark(g_prof, 2, st))) return rc;
-  // Merged launch: the diagonals on which EVERY layer is in range, [lag (NL - 1), nch - 1], hold the same workgroups
-  // with the same W_hh^T slices, carried dc and ring position (the tile height depends only on the layer count), and
-  // where nothing is enqueued between their launches (no dropout mask, no dh_n term, no lengths) they run as ONE launch
-  // of as many rounds: the two kernel boundaries around each input-gradient GEMM become chunk-level counters
-  // (lstm_cell_blk.h: PersistBwdArgs::nrounds).  Their GEMMs all have chunk * B rows -- the short chunk is the top
-  // layer's on the last of them, multiplied one launch later.  CSN_BWD_NO_MERGE=1: one launch per diagonal.
-  const int m_first = lag * (NL - 1), m_count = nch - m_first;
-  const bool merge = beside && !P.opt.bwd_no_merge && a.data_polls && C.dlen == nullptr && !drop_on(C) && dh_n == nullptr && m_count >= 2;
-  unsigned* const cnt = (unsigned*)(ws + w.merge_cnt);     // rec_done[NL][nch], then gemm_done[NL][nch]
   P.bwd_launches[0] = P.bwd_launches[1] = 0;
-  for (int dg = 0; dg < ndiag; ++dg) {
-    int lay[4], chk[4], ns = 0;
-    const bool merged = merge && dg == m_first;
-    if (merged) dg = m_first + m_count - 1;       // what follows the launch is what follows its last diagonal
-    for (int l = NL - 1; l >= 0; --l) {
-      const int c = dg - lag * (NL - 1 - l);      // reverse chunk index of layer l on this diagonal
-      if (c < 0 || c >= nch) continue;
-      const LayerWs& L = w.layer[l];
-      PersistBwdSlot& S = a.slot[ns];
+
+  const std::vector<BwdLaunch> sched =
+      bwd_persist_schedule(BwdSchedIn{T, B, H, NL, Cz, C.dlen != nullptr, drop_on(C), dh_n != nullptr, a.data_polls != 0,
+                                      P.opt.no_beside, P.opt.bwd_no_merge, P.opt.no_half_tiles});
+  auto beside_gemm = [&](const BwdGemm& g) {
+    const LayerWs& L = w.layer[g.layer];
+    return BesideGemm{(const bf16_t*)(ws + L.dgates) + (size_t)g.t_lo * B * G, (const bf16_t*)(ws + L.wiht),
+                      (float*)(ws + L.dx) + (size_t)g.t_lo * B * H, (g.t_hi - g.t_lo + 1) * B, H, (int)G};
+  };
+  // what follows GEMM g on the stream: the dropout mask of its steps, then the gradient w.r.t. h_n of the layer below
+  auto mask = [&](const BwdGemm& g) -> int { return g.mask ? drop_bwd(C, g.layer - 1, g.t_lo, g.t_hi, st) : CSN_OK; };
+  auto add_dh_n = [&](const BwdGemm& g) -> int {
+    if (!g.add) return CSN_OK;
+    return add_dh_n_rows(C, dh_n + (size_t)(g.layer - 1) * B * H, (float*)(ws + w.layer[g.layer].dx), g.t_lo, g.t_hi, st);
+  };
+  if ((rc = prof_mark(g_prof, 2, st))) return rc;
+  for (const BwdLaunch& q : sched) {
+    if (q.nslots == 0) {      // no layer in range: the GEMMs the previous launch left behind, stand-alone
+      for (int i = 0; i < q.ngemm; ++i) {
+        const BesideGemm g = beside_gemm(q.gemm[i]);
+        if ((rc = gemm_nt(g.A, g.Bt, nullptr, g.C, g.M, g.N, g.K, CSN_BF16, CSN_F32, 0, st, P.opt))) return rc;
+        if ((rc = mask(q.gemm[i]))) return rc;
+        if ((rc = add_dh_n(q.gemm[i]))) return rc;
+      }
+      continue;
+    }
+    for (int i = 0; i < q.nslots; ++i) {
+      const BwdSlot& s = q.slot[i];
+      const LayerWs& L = w.layer[s.layer];
+      PersistBwdSlot& S = a.slot[i];
       S.wt_blk = (const bf16_t*)(ws + L.whht_blk);
       S.gates = (const bf16_t*)(ws + L.gates);
       S.c_all = (const float*)(ws + L.c_all);
-      if (l == NL - 1) {
+      if (s.layer == NL - 1) {
         S.dy = A.dy_tm;
         S.dy_last = A.dy_tm ? nullptr : A.dy_last;
       } else {
-        S.dy = (const float*)(ws + w.layer[l + 1].dx);
+        S.dy = (const float*)(ws + w.layer[s.layer + 1].dx);
         S.dy_last = nullptr;
       }
       S.zeros = (const float*)(ws + w.zeros_bh);
@@ -1960,101 +1938,41 @@ static int backward_persist(Call& C, const BwdArgs& A) {
       S.dgates = (bf16_t*)(ws + L.dgates);
       S.dg_blk_all = (bf16_t*)(ws + L.dg_blk_all);
       S.flags = (unsigned*)(ws + L.bflags);
-      const Chunk k = chunk_at(C, c);
-      S.t_hi = T - 1 - k.t0;
-      S.nsteps = k.nsteps;
-      S.cnt_pub = S.cnt_wait = -1;
-      lay[ns] = l;
-      chk[ns] = c;
-      ++ns;
+      if (q.half) S.flags += (size_t)T * MT * kPersistFlagLine;      // the 32-row tiles' own lines
+      S.t_hi = s.t_hi;
+      S.nsteps = s.nsteps;
+      S.cnt_pub = s.cnt_pub;
+      S.cnt_wait = s.cnt_wait;
     }
-    a.nrounds = 1;
-    a.chunk = Cz;
-    a.cnt = cnt;
-    if (merged) {
-      // the slots hold the run's LAST diagonal (the GEMMs left for the next launch are formed from it below): the launch
-      // starts m_count - 1 full chunks above it
-      CSN_REQUIRE(ns == NL && npending == NL - 1, "backward_persist: merged launch without every layer");
-      a.nrounds = m_count;
-      for (int i = 0; i < ns; ++i) {
-        PersistBwdSlot& S = a.slot[i];
-        const int c0 = chk[i] - (m_count - 1);
-        S.t_hi += (m_count - 1) * Cz;
-        S.nsteps = Cz;
-        if (lay[i] > 0) S.cnt_pub = lay[i] * nch + c0;
-        if (lay[i] < NL - 1) S.cnt_wait = (NL + lay[i] + 1) * nch + c0;
-      }
-      for (int i = 0; i < npending; ++i) CSN_REQUIRE(pending[i].M == Cz * B, "backward_persist: merged launch with a short GEMM");
-      a.wk_wait = a.slot[0].cnt_pub - 1;
-      a.wk_pub = a.slot[1].cnt_wait + 1;
-      a.wk_stride = nch + lag;
-      for (int i = 1; i + 1 < ns; ++i)
-        CSN_REQUIRE(a.slot[i].cnt_pub == a.slot[0].cnt_pub - i * a.wk_stride && a.slot[i + 1].cnt_wait == a.slot[1].cnt_wait - i * a.wk_stride,
+    a.nslots = q.nslots;
+    a.ngemm = q.ngemm;
+    for (int i = 0; i < q.ngemm; ++i) a.gemm[i] = beside_gemm(q.gemm[i]);
+    a.nrounds = q.nrounds;
+    if (q.nrounds > 1) {
+      CSN_REQUIRE(q.nslots == NL && q.ngemm == NL - 1, "backward_persist: merged launch without every layer");
+      for (int i = 0; i < q.ngemm; ++i) CSN_REQUIRE(a.gemm[i].M == Cz * B, "backward_persist: merged launch with a short GEMM");
+      a.wk_wait = q.wk_wait;
+      a.wk_pub = q.wk_pub;
+      a.wk_stride = q.wk_stride;
+      for (int i = 1; i + 1 < q.nslots; ++i)
+        CSN_REQUIRE(q.slot[i].cnt_pub == q.slot[0].cnt_pub - i * q.wk_stride && q.slot[i + 1].cnt_wait == q.slot[1].cnt_wait - i * q.wk_stride,
                     "backward_persist: merged launch whose counters are not evenly spaced");
-      P.bwd_launches[1] = m_count;
+      P.bwd_launches[1] = q.nrounds;
     }
-    if (ns == 0) {
-      // a diagonal without a layer in range (one chunk per layer, T <= chunk, and the layers two launches apart): nothing
-      // to recur over, but the input-gradient GEMMs the previous launch left for "the next launch" still have to run
-      for (int i = 0; i < npending; ++i) {
-        const BesideGemm& g = pending[i];
-        if ((rc = gemm_nt(g.A, g.Bt, nullptr, g.C, g.M, g.N, g.K, CSN_BF16, CSN_F32, 0, st, P.opt))) return rc;
-        if ((rc = drop_bwd(C, pending_drop[i].l - 1, pending_drop[i].t_lo, pending_drop[i].t_hi, st))) return rc;
-        if (pending_add[i].l && (rc = add_dh_n(pending_add[i]))) return rc;
-      }
-      npending = 0;
-      continue;
-    }
-    a.nslots = ns;
-    a.ngemm = npending;
-    // few groups: 32-row groups, twice as many (forward_persist).  The grid and the GEMM workers stay what they are --
-    // 8 groups of 24 slices leave the same 8 x 8 workgroups for the tiles.  A batch with lengths stays on 64 rows.
-    const bool half = !P.opt.no_half_tiles && C.dlen == nullptr && 2 * ns * MT <= 8;
-    a.half_tiles = half ? 1 : 0;
-    a.MT = half ? 2 * MT : MT;
-    if (half) {
-      for (int i = 0; i < ns; ++i) a.slot[i].flags += (size_t)T * MT * kPersistFlagLine;
-      P.half_launches[1] += merged ? m_count : 1;     // (a merged launch: once per diagonal it covers)
-    }
-    DhAdd launch_adds[3], launch_drops[3];
-    int nadds = 0;
-    const int ndrops = npending;
-    for (int i = 0; i < npending; ++i) {
-      a.gemm[i] = pending[i];
-      launch_drops[i] = pending_drop[i];
-      if (pending_add[i].l) launch_adds[nadds++] = pending_add[i];
-    }
-    npending = 0;
-    a.agree = try_local ? (unsigned long long*)(ws + w.agree_b) + (size_t)dg * 8 : nullptr;
+    a.half_tiles = q.half ? 1 : 0;
+    a.MT = q.MT;
+    if (q.half) P.half_launches[1] += q.nrounds;      // (a merged launch: once per diagonal it covers)
+    a.agree = try_local ? (unsigned long long*)(ws + w.agree_b) + (size_t)q.agree * 8 : nullptr;
     if ((rc = prof_pair(g_prof, 1, false, st))) return rc;
     if ((rc = launch_bwd_persist(a, st, C.dlen))) return rc;
     if ((rc = prof_pair(g_prof, 1, true, st))) return rc;
     ++n_launch;
-    if (merged)       // back to the last diagonal's own chunk: the GEMMs formed below are those it leaves behind
-      for (int i = 0; i < ns; ++i) {
-        const Chunk k = chunk_at(C, chk[i]);
-        a.slot[i].t_hi = T - 1 - k.t0;
-        a.slot[i].nsteps = k.nsteps;
-      }
-    for (int i = 0; i < ndrops; ++i)
-      if ((rc = drop_bwd(C, launch_drops[i].l - 1, launch_drops[i].t_lo, launch_drops[i].t_hi, st))) return rc;
-    for (int i = 0; i < nadds; ++i)
-      if ((rc = add_dh_n(launch_adds[i]))) return rc;
-    for (int i = 0; i < ns; ++i) {
-      const int l = lay[i];
-      if (l == 0) continue;
-      if (!beside) {
-        if ((rc = dx_chunk_gemm(C, l, chk[i], dh_n, st))) return rc;
-        continue;
-      }
-      // dx_chunk_gemm's GEMM and dh_n term, left for the next launch
-      const LayerWs& L = w.layer[l];
-      const int t_hi = a.slot[i].t_hi, t_lo = t_hi - a.slot[i].nsteps + 1;
-      pending_add[npending] = DhAdd{(dh_n && (chk[i] == 0 || C.dlen)) ? l : 0, t_lo, t_hi};
-      pending_drop[npending] = DhAdd{l, t_lo, t_hi};
-      pending[npending++] = BesideGemm{(const bf16_t*)(ws + L.dgates) + (size_t)t_lo * B * G, (const bf16_t*)(ws + L.wiht),
-                                       (float*)(ws + L.dx) + (size_t)t_lo * B * H, (t_hi - t_lo + 1) * B, H, (int)G};
-    }
+    for (int i = 0; i < q.ngemm; ++i)
+      if ((rc = mask(q.gemm[i]))) return rc;
+    for (int i = 0; i < q.ngemm; ++i)
+      if ((rc = add_dh_n(q.gemm[i]))) return rc;
+    for (int i = 0; q.inline_gemms && i < q.nslots; ++i)
+      if (q.slot[i].layer > 0 && (rc = dx_chunk_gemm(C, q.slot[i].layer, q.slot[i].chunk, dh_n, st))) return rc;
   }
   P.bwd_launches[0] = n_launch;
   if ((rc = prof_end(C, 1, n_launch, T * NL))) return rc;

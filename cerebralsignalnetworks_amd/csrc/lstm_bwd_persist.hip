@@ -680,7 +680,6 @@ bool bwd_persist_supported(int B, int H, int dtype, const Options& opt) {
   if (dtype != CSN_BF16 || opt.no_persist || opt.no_persist_bwd) return false;
   return H == 128 || H == 256 || H == 384 || H == 512 || H == 768 || H == 1024;
 }
-int bwd_persist_slices(int H) { return H / 32; }
 
 // 32-row groups (a.half_tiles): every instantiation holds W_hh^T in more than 256 registers (KS * NUT fragments plus the
 // ring), so a SIMD takes one wave and a CU one workgroup whatever the LDS request.  The masked kernel has no 32-row

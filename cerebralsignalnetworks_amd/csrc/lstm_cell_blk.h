@@ -1,6 +1,7 @@
 // Argument blocks of the multi-problem cell kernels (lstm_cell_blk.hip) and their launchers.
 #pragma once
 #include "csn_common.h"
+#include "lstm_schedule.h"      // fwd_persist_slices, fwd_ns_slices, bwd_persist_slices
 
 // Debug library (-DCSN_SLAB_TAGS, `make tags`): bit 2 of data_polls = fault injection "do not re-arm the ring slots", so
 // that consumers ARE served stale occupants and the tag check can be seen to fire.  The product build has neither.
@@ -111,9 +112,7 @@ constexpr size_t fwd_persist_lds_bytes(int nq, bool park) {
 bool fwd_persist_supported(int B, int H, int dtype, const Options& opt);
 // N-split weight-stationary forward (lstm_fwd_ns.hip): the default where it applies
 bool fwd_ns_supported(int B, int H, int dtype, const Options& opt);
-int fwd_ns_slices(int H);
 int launch_fwd_ns(const PersistFwdArgs& a, hipStream_t st);
-int fwd_persist_slices(int H);   // workgroups per hand-off group
 int launch_fwd_persist(const PersistFwdArgs& a, hipStream_t st);
 
 // weight-stationary backward recurrence (lstm_bwd_persist.hip): ONE launch walks up to 4 layers, each backwards
@@ -165,7 +164,6 @@ struct PersistBwdArgs {
 };
 static_assert(sizeof(PersistBwdArgs) <= 4096, "PersistBwdArgs is passed by value: the kernel-argument segment holds 4096 bytes");
 bool bwd_persist_supported(int B, int H, int dtype, const Options& opt);
-int bwd_persist_slices(int H);
 // lengths != NULL (variable-length batches): [B] device array; the masked instantiation of the kernel
 int launch_bwd_persist(const PersistBwdArgs& a, hipStream_t st, const int* lengths = nullptr);
 

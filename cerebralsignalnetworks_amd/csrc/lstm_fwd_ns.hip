@@ -553,7 +553,6 @@ static int launch_ns_t(const PersistFwdArgs& a, hipStream_t st) {
   return CSN_OK;
 }
 
-int fwd_ns_slices(int H) { return H / 32; }
 
 int launch_fwd_ns(const PersistFwdArgs& a, hipStream_t st) {
   CSN_REQUIRE(a.nslots >= 1 && a.nslots <= 4 && a.MT >= 1, "launch_fwd_ns: bad slot count");

@@ -697,7 +697,6 @@ bool fwd_persist_supported(int B, int H, int dtype, const Options& opt) {
   return shape && wgs <= 128;
 }
 
-int fwd_persist_slices(int H) { return H / (4 * ((H % 24 == 0) ? 6 : 8)); }
 
 template <int NQ, int KS>
 static int launch_persist_t(const PersistFwdArgs& a, hipStream_t st) {

@@ -7,9 +7,11 @@ import re
 
 import lstm_feature_fuzz as fz
 import lstm_input_views as views
+import lstm_schedule_probe as sp
 import lstm_width_matrix as wm
 import test_gpu_half_tiles as ht
 import test_gpu_lstm_state as st
+import test_gpu_stream_order as gso
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "cerebralsignalnetworks_amd", "csrc")
 WIDTHS = {128, 256, 384, 512, 768, 1024}
@@ -90,6 +92,53 @@ def test_the_mirror_counts_the_32_row_launches_as_the_half_tile_test_does():
         want = ht._expected_half_launches(c["B"], c["T"], c["H"], c["L"], int(c["env"]["CSN_LSTM_CHUNK"]), c["env"], c["lengths"])
         assert wm.half_tile_launches(c) == want, (c["id"], c["env"], wm.half_tile_launches(c), want)
         assert wm.dgates_copies(c) == 2
+
+
+def test_the_mirror_counts_the_launches_of_the_schedules_the_library_builds(tmp_path):
+    """The weight-stationary records of the ledger against fwd_persist_schedule / bwd_persist_schedule (csrc/lstm_schedule.h,
+    through the host-only program of tests/lstm_schedule_probe.py): the launches on 32-row groups, the recurrence launches
+    (the occupied diagonals of the mirror; a merged launch covers one per round), and the form of the forward."""
+    ask = sp.build(tmp_path)
+    recs, queries = [], []
+    for c in wm.ledger_records():
+        _, fwd, bwd = fz.expected_plan(c)
+        steps = c["T"] if c["lengths"] is None else max(c["lengths"])
+        if steps == 0 or not {fwd, bwd} & {st._PF, st._NSF, "lstm_bwd_persist_kernel"}:
+            continue
+        env = c["env"]
+        shape = (steps, c["B"], c["H"], c["L"], max(1, int(env.get("CSN_LSTM_CHUNK", 32))))
+        no_half = wm._on(env, "CSN_NO_HALF_TILES")
+        recs.append((c, fwd, bwd))
+        queries.append(sp.fwd_query(*shape, fwd_ns=fwd == st._NSF, persist_streams=wm._on(env, "CSN_PERSIST_STREAMS"), no_half=no_half))
+        queries.append(sp.bwd_query(*shape, lengths=c["lengths"] is not None, dropout=c["dropout"] is not None,
+                                    dh_n="dh_n" in c["grads_in"], flags=wm._on(env, "CSN_BWD_FLAGS"),
+                                    no_beside=wm._on(env, "CSN_NO_BESIDE"), no_merge=wm._on(env, "CSN_BWD_NO_MERGE"), no_half=no_half))
+    answers = ask(queries)
+    assert len(recs) > 100
+    seen = set()
+    for i, (c, fwd, bwd) in enumerate(recs):
+        real_f, real_b = answers[2 * i], answers[2 * i + 1]
+        f, b = wm.launches(c)
+        half = wm.half_tile_launches(c)
+        if fwd in (st._PF, st._NSF):
+            assert len(real_f["launches"]) == len(f), (c["id"], c["env"])
+            assert sum(q["half"] for q in real_f["launches"]) == half[0], (c["id"], c["env"])
+            seen.add(fwd)
+        if bwd == "lstm_bwd_persist_kernel":
+            assert sum(q["nrounds"] for q in real_b if q["slots"]) == len(b), (c["id"], c["env"])
+            assert sum(q["half"] * q["nrounds"] for q in real_b) == half[1], (c["id"], c["env"])
+            seen.add(bwd)
+    assert seen == {st._PF, st._NSF, "lstm_bwd_persist_kernel"}
+    # the form of the forward: the cases of tests/test_gpu_stream_order.py that name theirs
+    for name, streams in gso.STREAM_FORM.items():
+        shape, dtype, _, env = gso._case(name)[:4]
+        B, T, I, H, L = shape
+        path, fwd, _ = fz.expected_plan(wm.record(B, T, I, H, L, "bf16", env))
+        assert dtype == st.BF16 and path in (2, 3) and fwd in (st._PF, st._NSF), name
+        [real] = ask([sp.fwd_query(T, B, H, L, int(env.get("CSN_LSTM_CHUNK", 32)), fwd_ns=fwd == st._NSF,
+                                   persist_streams=env.get("CSN_PERSIST_STREAMS") == "1")])
+        assert (real["form"] == "layer_streams") == gso._forward_takes_layer_streams(shape, env, fwd) == streams, (name, real["form"])
+        assert real["form"] != "caller_stream", name
 
 
 def test_the_ledger():
