@@ -28,6 +28,7 @@
 //
 // Each path is one function over the per-call context (struct Call) and the caller's pointers (FwdArgs / BwdArgs); what
 // more than one of them does -- slot 0, weight gradients, chunk GEMMs, dx out, the profile epilogue -- is one helper each.
+// The layer wavefronts of paths 0, 1 and 5 are ONE schedule (wavefront_schedule, lstm_schedule.h: unit, lag, direction).
 //
 // Layout in HBM (inside the caller's workspace; [T,B,*] time-major so one timestep is one slab):
 //   per layer: compute-dtype weight copies (+ transposes / fragment-major forms), bias,
@@ -1050,9 +1051,8 @@ static int prep_row_major(const Call& C, const FwdArgs& A) {
   return CSN_OK;
 }
 
-// chunk c of this call's steps, and whether step (or reverse step) t ends its chunk (lstm_schedule.h)
+// chunk c of this call's steps (lstm_schedule.h)
 static Chunk chunk_at(const Call& C, int c) { return chunk_at(C.T, C.Cz, c); }
-static bool ends_chunk(const Call& C, int t) { return ends_chunk(C.T, C.Cz, t); }
 
 // layer l finished chunk c -> xproj_{l+1}[chunk c] = h_l[chunk c] W_ih^T + b
 static int xproj_chunk_gemm(const Call& C, int l, int c, hipStream_t on) {
@@ -1157,7 +1157,9 @@ static int launch_dh0(const Call& C, int l, float* out) {
 // Wavefront over the layers, as in path 1: diagonal d runs layer l at step d - l * lag in ONE launch (blockIdx.z =
 // layer; round 3 ran layer after layer, one launch per layer-step: 2 T L launches per pass, each bound by its launch
 // boundary and its own fill, not by the float32 MFMA rate).  The input projection of layer l + 1 follows layer l chunk by
-// chunk (GEMM over `chunk` steps on the same stream), so lag = chunk.
+// chunk (GEMM over `chunk` steps on the same stream), so lag = chunk.  Which cells a launch holds and which chunks a
+// diagonal finished is wavefront_schedule (lstm_schedule.h), here and in paths 1 and 5: each of the six functions fills one
+// problem of its kernel's batch from a cell and enqueues the launches, the chunk GEMMs behind one that closes a diagonal.
 static int forward_v1(Call& C, const FwdArgs& A) {
   const WsLayout& w = C.w;
   char* ws = C.ws;
@@ -1165,7 +1167,6 @@ static int forward_v1(Call& C, const FwdArgs& A) {
   const int B = C.B, T = C.T, H = C.H, dt = C.dt, NL = C.NL;
   const int64_t G = C.G;
   const size_t es = C.es;
-  const int lag = C.Cz;
   const int training = C.P.training;
   int rc;
   if ((rc = prep_row_major(C, A))) return rc;
@@ -1173,32 +1174,24 @@ static int forward_v1(Call& C, const FwdArgs& A) {
   if ((rc = gemm_nt(ws + w.x_c, ws + w.layer[0].wih, (const float*)(ws + w.layer[0].bias), ws + w.layer[0].xproj, C.TB, G,
                     C.d.I, dt, CSN_F32, 0, st, C.P.opt)))
     return rc;
-  const int D = T + lag * (NL - 1);
-  for (int dg = 0; dg < D; ++dg) {
+  auto cell = [&](const WaveCell& s) {
+    const LayerWs& L = w.layer[s.layer];
+    const int t = s.t;
+    return CellFwdOne{ws + L.h_all + (size_t)t * B * H * es, ws + L.whh, (const float*)(ws + L.xproj) + (size_t)t * B * G, G,
+                      (const float*)(ws + L.c_all) + (size_t)t * B * H,
+                      training ? ws + L.gates + (size_t)t * B * G * es : nullptr,
+                      (float*)(ws + L.c_all) + (size_t)(t + 1) * B * H, ws + L.h_all + (size_t)(t + 1) * B * H * es};
+  };
+  return wavefront_schedule(WaveIn{T, NL, C.Cz, WaveUnit::step, 1, false}, [&](const WaveLaunch& q) -> int {
     CellFwdBatch b{};
-    int np = 0;
-    for (int l = 0; l < NL; ++l) {
-      const int t = dg - lag * l;
-      if (t < 0 || t >= T) continue;
-      const LayerWs& L = w.layer[l];
-      if (np == 4) {       // (more than 4 layers on one diagonal: a second launch, the problems are independent)
-        if ((rc = launch_cell_fwd_batch(b, np, B, H, dt, st))) return rc;
-        np = 0;
-      }
-      b.p[np++] = CellFwdOne{ws + L.h_all + (size_t)t * B * H * es, ws + L.whh, (const float*)(ws + L.xproj) + (size_t)t * B * G, G,
-                             (const float*)(ws + L.c_all) + (size_t)t * B * H,
-                             training ? ws + L.gates + (size_t)t * B * G * es : nullptr,
-                             (float*)(ws + L.c_all) + (size_t)(t + 1) * B * H, ws + L.h_all + (size_t)(t + 1) * B * H * es};
-    }
-    if (np > 0 && (rc = launch_cell_fwd_batch(b, np, B, H, dt, st))) return rc;
+    for (int i = 0; i < q.ncells; ++i) b.p[i] = cell(q.cell[i]);
+    if (int rc = launch_cell_fwd_batch(b, q.ncells, B, H, dt, st)) return rc;
     // a layer that just finished a chunk feeds the next layer's input projection
-    for (int l = 0; l + 1 < NL; ++l) {
-      const int t = dg - lag * l;
-      if (t < 0 || t >= T || !ends_chunk(C, t)) continue;
-      if ((rc = xproj_chunk_gemm(C, l, t / C.Cz, st))) return rc;
-    }
-  }
-  return CSN_OK;
+    for (int i = 0; i < q.ndone; ++i)
+      if (q.done[i].layer + 1 < NL)
+        if (int rc = xproj_chunk_gemm(C, q.done[i].layer, q.done[i].chunk, st)) return rc;
+    return CSN_OK;
+  });
 }
 
 static int backward_v1(Call& C, const BwdArgs& A) {
@@ -1208,43 +1201,34 @@ static int backward_v1(Call& C, const BwdArgs& A) {
   const int B = C.B, T = C.T, H = C.H, dt = C.dt, NL = C.NL;
   const int64_t G = C.G;
   const size_t es = C.es;
-  const int lag = C.Cz;
   int rc;
   for (int l = 0; l < NL; ++l)
     if ((rc = seed_dc_carry(C, l, A.dc_n, false))) return rc;
-  // diagonal d: layer l at reverse step d - lag * (L - 1 - l); the gradient w.r.t. a layer's input (= dy of the layer
-  // below) follows chunk by chunk
-  const int D = T + lag * (NL - 1);
-  for (int dg = 0; dg < D; ++dg) {
+  auto cell = [&](const WaveCell& s) {
+    const int l = s.layer, t = s.t;
+    const LayerWs& L = w.layer[l];
+    const float* dy_t = l == NL - 1 ? (A.dy_tm ? A.dy_tm + (size_t)t * B * H : (t == T - 1 ? A.dy_last : nullptr))
+                                    : (const float*)(ws + w.layer[l + 1].dx) + (size_t)t * B * H;
+    return CellBwdOne{(t == T - 1) ? nullptr : (const void*)(ws + L.dgates + (size_t)(t + 1) * B * G * es), ws + L.whht, dy_t, H,
+                      ws + L.gates + (size_t)t * B * G * es, (const float*)(ws + L.c_all) + (size_t)(t + 1) * B * H,
+                      (const float*)(ws + L.c_all) + (size_t)t * B * H, (float*)(ws + L.dc_carry),
+                      ws + L.dgates + (size_t)t * B * G * es};
+  };
+  // the gradient w.r.t. a layer's input (= dy of the layer below) follows chunk by chunk
+  rc = wavefront_schedule(WaveIn{T, NL, C.Cz, WaveUnit::step, 1, true}, [&](const WaveLaunch& q) -> int {
     CellBwdBatch b{};
     CellMask mask{C.dlen, {0, 0, 0, 0}};
-    const CellMask* mk = C.dlen ? &mask : nullptr;
-    int np = 0;
-    for (int l = NL - 1; l >= 0; --l) {
-      const int r = dg - lag * (NL - 1 - l);
-      if (r < 0 || r >= T) continue;
-      const int t = T - 1 - r;
-      const LayerWs& L = w.layer[l];
-      const bool top = (l == NL - 1);
-      if (np == 4) {
-        if ((rc = launch_cell_bwd_batch(b, np, B, H, dt, st, mk))) return rc;
-        np = 0;
-      }
-      mask.t[np] = t;
-      const float* dy_t = top ? (A.dy_tm ? A.dy_tm + (size_t)t * B * H : (t == T - 1 ? A.dy_last : nullptr))
-                              : (const float*)(ws + w.layer[l + 1].dx) + (size_t)t * B * H;
-      b.p[np++] = CellBwdOne{(t == T - 1) ? nullptr : (const void*)(ws + L.dgates + (size_t)(t + 1) * B * G * es), ws + L.whht, dy_t, H,
-                             ws + L.gates + (size_t)t * B * G * es, (const float*)(ws + L.c_all) + (size_t)(t + 1) * B * H,
-                             (const float*)(ws + L.c_all) + (size_t)t * B * H, (float*)(ws + L.dc_carry),
-                             ws + L.dgates + (size_t)t * B * G * es};
+    for (int i = 0; i < q.ncells; ++i) {
+      mask.t[i] = q.cell[i].t;
+      b.p[i] = cell(q.cell[i]);
     }
-    if (np > 0 && (rc = launch_cell_bwd_batch(b, np, B, H, dt, st, mk))) return rc;
-    for (int l = NL - 1; l >= 1; --l) {
-      const int r = dg - lag * (NL - 1 - l);
-      if (r < 0 || r >= T || !ends_chunk(C, r)) continue;
-      if ((rc = dx_chunk_gemm(C, l, r / C.Cz, A.dh_n, st))) return rc;
-    }
-  }
+    if (int rc = launch_cell_bwd_batch(b, q.ncells, B, H, dt, st, C.dlen ? &mask : nullptr)) return rc;
+    for (int i = 0; i < q.ndone; ++i)
+      if (q.done[i].layer > 0)
+        if (int rc = dx_chunk_gemm(C, q.done[i].layer, q.done[i].chunk, A.dh_n, st)) return rc;
+    return CSN_OK;
+  });
+  if (rc) return rc;
   for (int l = NL - 1; l >= 0; --l) {
     if ((rc = weight_grads_rm(C, A, l, true))) return rc;
     C.P.grads_ready(l);
@@ -1271,35 +1255,24 @@ static int forward_resident(Call& C, const FwdArgs& A) {
                     C.d.I, dt, CSN_F32, 0, st, C.P.opt)))
     return rc;
   if ((rc = prof_mark(C.P.prof, 0, st))) return rc;
-  const int nch = (T + C.Cz - 1) / C.Cz, D = nch + NL - 1;
+  auto cell = [&](const WaveCell& s) {
+    const LayerWs& L = w.layer[s.layer];
+    return ResFwdOne{ws + L.whh, (const float*)(ws + L.xproj), (float*)(ws + L.c_all), ws + L.h_all,
+                     C.P.training ? ws + L.gates : nullptr, s.t, s.nsteps};
+  };
   int n_launch = 0;
-  for (int dg = 0; dg < D; ++dg) {
+  rc = wavefront_schedule(WaveIn{T, NL, C.Cz, WaveUnit::chunk, 1, false}, [&](const WaveLaunch& q) -> int {
     ResFwdBatch b{};
-    int np = 0;
-    for (int l = 0; l < NL; ++l) {
-      const int c = dg - l;
-      if (c < 0 || c >= nch) continue;
-      const LayerWs& L = w.layer[l];
-      const Chunk k = chunk_at(C, c);
-      if (np == 4) {       // (more than 4 layers on one diagonal: a second launch, the problems are independent)
-        if ((rc = launch_resident_fwd(b, np, B, H, dt, st))) return rc;
-        ++n_launch;
-        np = 0;
-      }
-      b.p[np++] = ResFwdOne{ws + L.whh, (const float*)(ws + L.xproj), (float*)(ws + L.c_all), ws + L.h_all,
-                            C.P.training ? ws + L.gates : nullptr, k.t0, k.nsteps};
-    }
-    if (np > 0) {
-      if ((rc = launch_resident_fwd(b, np, B, H, dt, st))) return rc;
-      ++n_launch;
-    }
+    for (int i = 0; i < q.ncells; ++i) b.p[i] = cell(q.cell[i]);
+    if (int rc = launch_resident_fwd(b, q.ncells, B, H, dt, st)) return rc;
+    ++n_launch;
     // a layer that just finished a chunk feeds the next layer's input projection
-    for (int l = 0; l + 1 < NL; ++l) {
-      const int c = dg - l;
-      if (c < 0 || c >= nch) continue;
-      if ((rc = xproj_chunk_gemm(C, l, c, st))) return rc;
-    }
-  }
+    for (int i = 0; i < q.ndone; ++i)
+      if (q.done[i].layer + 1 < NL)
+        if (int rc = xproj_chunk_gemm(C, q.done[i].layer, q.done[i].chunk, st)) return rc;
+    return CSN_OK;
+  });
+  if (rc) return rc;
   return prof_end(C, 0, n_launch, T * NL);
 }
 
@@ -1314,37 +1287,26 @@ static int backward_resident(Call& C, const BwdArgs& A) {
   for (int l = 0; l < NL; ++l)
     if ((rc = seed_dc_carry(C, l, A.dc_n, false))) return rc;
   if ((rc = prof_mark(C.P.prof, 2, st))) return rc;
-  // diagonal d: layer l at reverse chunk d - (L - 1 - l) (reverse chunk c: the steps [t_hi - nsteps + 1, t_hi], t_hi = T - 1 - t0)
-  const int nch = (T + C.Cz - 1) / C.Cz, D = nch + NL - 1;
+  auto cell = [&](const WaveCell& s) {      // (reverse chunk: the steps [t_hi - nsteps + 1, t_hi])
+    const int l = s.layer;
+    const LayerWs& L = w.layer[l];
+    const bool top = (l == NL - 1);
+    return ResBwdOne{ws + L.whht, top ? A.dy_tm : (const float*)(ws + w.layer[l + 1].dx), top ? A.dy_last : nullptr,
+                     ws + L.gates, (const float*)(ws + L.c_all), (float*)(ws + L.dc_carry), ws + L.dgates,
+                     s.t, s.nsteps};
+  };
   int n_launch = 0;
-  for (int dg = 0; dg < D; ++dg) {
+  rc = wavefront_schedule(WaveIn{T, NL, C.Cz, WaveUnit::chunk, 1, true}, [&](const WaveLaunch& q) -> int {
     ResBwdBatch b{};
-    int np = 0;
-    for (int l = NL - 1; l >= 0; --l) {
-      const int c = dg - (NL - 1 - l);
-      if (c < 0 || c >= nch) continue;
-      const LayerWs& L = w.layer[l];
-      const Chunk k = chunk_at(C, c);
-      const bool top = (l == NL - 1);
-      if (np == 4) {
-        if ((rc = launch_resident_bwd(b, np, B, T, H, dt, C.dlen, st))) return rc;
-        ++n_launch;
-        np = 0;
-      }
-      b.p[np++] = ResBwdOne{ws + L.whht, top ? A.dy_tm : (const float*)(ws + w.layer[l + 1].dx), top ? A.dy_last : nullptr,
-                            ws + L.gates, (const float*)(ws + L.c_all), (float*)(ws + L.dc_carry), ws + L.dgates,
-                            T - 1 - k.t0, k.nsteps};
-    }
-    if (np > 0) {
-      if ((rc = launch_resident_bwd(b, np, B, T, H, dt, C.dlen, st))) return rc;
-      ++n_launch;
-    }
-    for (int l = NL - 1; l >= 1; --l) {
-      const int c = dg - (NL - 1 - l);
-      if (c < 0 || c >= nch) continue;
-      if ((rc = dx_chunk_gemm(C, l, c, A.dh_n, st))) return rc;
-    }
-  }
+    for (int i = 0; i < q.ncells; ++i) b.p[i] = cell(q.cell[i]);
+    if (int rc = launch_resident_bwd(b, q.ncells, B, T, H, dt, C.dlen, st)) return rc;
+    ++n_launch;
+    for (int i = 0; i < q.ndone; ++i)
+      if (q.done[i].layer > 0)
+        if (int rc = dx_chunk_gemm(C, q.done[i].layer, q.done[i].chunk, A.dh_n, st)) return rc;
+    return CSN_OK;
+  });
+  if (rc) return rc;
   if ((rc = prof_end(C, 1, n_launch, T * NL))) return rc;
   for (int l = NL - 1; l >= 0; --l) {
     if ((rc = weight_grads_rm(C, A, l, true))) return rc;
@@ -1535,59 +1497,51 @@ static int forward_il(Call& C, const FwdArgs& A) {
   hipStream_t side = C.P.opt.no_side_stream ? st : sc->side;
   const int B = C.B, T = C.T, H = C.H, NL = C.NL;
   const int64_t G = C.G;
-  const int Cz = C.Cz, lag = 2 * Cz;
+  const int Cz = C.Cz;
   const int training = C.P.training;
   if ((rc = prep_fast(C, A))) return rc;
   if (NL > 1 && (rc = hand_off(sc, st, side))) return rc;   // side stream sees the prepared weights
 
   const int nch = (T + Cz - 1) / Cz;
   std::vector<hipEvent_t> xproj_ready((size_t)NL * nch, nullptr);
-  const int D = T + lag * (NL - 1);
   int n_launch = 0, n_cells = 0;
   if ((rc = prof_mark(C.P.prof, 0, st))) return rc;
-  for (int dg = 0; dg < D; ++dg) {
-    CellFwdArgs a{};
-    a.B = B;
-    a.H = H;
-    int np = 0;
-    for (int l = 0; l < NL; ++l) {
-      const int t = dg - lag * l;
-      if (t < 0 || t >= T) continue;
-      const LayerWs& L = w.layer[l];
-      if (np == 4) {       // (more than 4 layers on one diagonal, L >= 5: a second launch, the problems are independent)
-        if ((rc = launch_cell_fwd_il(a, np, st))) return rc;
-        ++n_launch;
-        n_cells += np;
-        np = 0;
-      }
-      if (l > 0 && t % Cz == 0) CSN_HIP_CHECK(hipStreamWaitEvent(st, xproj_ready[(size_t)l * nch + t / Cz], 0));
-      CellFwdProb& q = a.p[np++];
-      q.h_prev_blk = (t == 0 && !A.h0) ? nullptr : (const bf16_t*)(ws + L.hblk[t & 1]);
-      q.w_blk = (const bf16_t*)(ws + L.whh_blk);
-      q.xproj = (const float*)(ws + L.xproj) + (size_t)t * B * G;
-      q.c_prev = (t == 0 && !A.c0) ? nullptr : (const float*)(ws + L.c_all) + (size_t)t * B * H;
-      q.gates_out = training ? (bf16_t*)(ws + L.gates) + (size_t)t * B * G : nullptr;
-      q.c_out = (float*)(ws + L.c_all) + (size_t)(t + 1) * B * H;
-      q.h_out = (bf16_t*)(ws + L.h_all) + (size_t)(t + 1) * B * H;
-      q.h_out_blk = (bf16_t*)(ws + L.hblk[(t + 1) & 1]);
+  auto cell = [&](CellFwdProb& q, const WaveCell& s) {
+    const LayerWs& L = w.layer[s.layer];
+    const int t = s.t;
+    q.h_prev_blk = (t == 0 && !A.h0) ? nullptr : (const bf16_t*)(ws + L.hblk[t & 1]);
+    q.w_blk = (const bf16_t*)(ws + L.whh_blk);
+    q.xproj = (const float*)(ws + L.xproj) + (size_t)t * B * G;
+    q.c_prev = (t == 0 && !A.c0) ? nullptr : (const float*)(ws + L.c_all) + (size_t)t * B * H;
+    q.gates_out = training ? (bf16_t*)(ws + L.gates) + (size_t)t * B * G : nullptr;
+    q.c_out = (float*)(ws + L.c_all) + (size_t)(t + 1) * B * H;
+    q.h_out = (bf16_t*)(ws + L.h_all) + (size_t)(t + 1) * B * H;
+    q.h_out_blk = (bf16_t*)(ws + L.hblk[(t + 1) & 1]);
+  };
+  rc = wavefront_schedule(WaveIn{T, NL, Cz, WaveUnit::step, 2, false}, [&](const WaveLaunch& q) -> int {
+    CellFwdArgs a{};  a.B = B; a.H = H;
+    for (int i = 0; i < q.ncells; ++i) {
+      const WaveCell& s = q.cell[i];      // entering a chunk: its projection has to be there
+      if (s.layer > 0 && s.enters) CSN_HIP_CHECK(hipStreamWaitEvent(st, xproj_ready[(size_t)s.layer * nch + s.chunk], 0));
+      cell(a.p[i], s);
     }
-    if (np == 0) continue;
-    if ((rc = launch_cell_fwd_il(a, np, st))) return rc;
+    if (int rc = launch_cell_fwd_il(a, q.ncells, st)) return rc;
     ++n_launch;
-    n_cells += np;
+    n_cells += q.ncells;
     // a layer that just finished a chunk feeds the next layer's input projection (side stream)
-    for (int l = 0; l + 1 < NL; ++l) {
-      const int t = dg - lag * l;
-      if (t < 0 || t >= T || !ends_chunk(C, t)) continue;
-      const int c = t / Cz;
-      if ((rc = hand_off(sc, st, side))) return rc;
-      if ((rc = xproj_chunk_gemm(C, l, c, side))) return rc;
+    for (int i = 0; i < q.ndone; ++i) {
+      const int l = q.done[i].layer, c = q.done[i].chunk;
+      if (l + 1 == NL) continue;
+      if (int rc = hand_off(sc, st, side)) return rc;
+      if (int rc = xproj_chunk_gemm(C, l, c, side)) return rc;
       hipEvent_t ev;
-      if ((rc = next_event(sc, &ev))) return rc;
+      if (int rc = next_event(sc, &ev)) return rc;
       CSN_HIP_CHECK(hipEventRecord(ev, side));
       xproj_ready[(size_t)(l + 1) * nch + c] = ev;
     }
-  }
+    return CSN_OK;
+  });
+  if (rc) return rc;
   return prof_end(C, 0, n_launch, n_cells);
 }
 
@@ -1754,7 +1708,7 @@ static int backward_il(Call& C, const BwdArgs& A) {
   const int B = C.B, T = C.T, H = C.H, NL = C.NL;
   const int64_t G = C.G;
   const size_t Bpad = ((size_t)B + 63) / 64 * 64;
-  const int Cz = C.Cz, lag = 2 * Cz;
+  const int Cz = C.Cz;
   const int nch = (T + Cz - 1) / Cz;
   const bool state = C.P.state != 0;
 
@@ -1767,72 +1721,60 @@ static int backward_il(Call& C, const BwdArgs& A) {
   if ((rc = hand_off(sc, st, side))) return rc;
 
   std::vector<hipEvent_t> dx_ready((size_t)NL * nch, nullptr);
-  const int D = T + lag * (NL - 1);
   int n_launch = 0, n_cells = 0;
   if ((rc = prof_mark(C.P.prof, 2, st))) return rc;
-  for (int dg = 0; dg < D; ++dg) {
-    CellBwdArgs a{};
-    a.B = B;
-    a.H = H;
-    CellMask mask{C.dlen, {0, 0, 0, 0}};
-    const CellMask* mk = C.dlen ? &mask : nullptr;
-    int np = 0;
-    for (int l = NL - 1; l >= 0; --l) {
-      const int r = dg - lag * (NL - 1 - l);      // reverse step index of layer l on this diagonal
-      if (r < 0 || r >= T) continue;
-      const int t = T - 1 - r;
-      const LayerWs& L = w.layer[l];
-      const bool top = (l == NL - 1);
-      if (np == 4) {       // (more than 4 layers on one diagonal, L >= 5: a second launch, the problems are independent)
-        if ((rc = launch_cell_bwd_il(a, np, st, mk))) return rc;
-        ++n_launch;
-        n_cells += np;
-        np = 0;
-      }
-      mask.t[np] = t;
-      if (!top && r % Cz == 0) CSN_HIP_CHECK(hipStreamWaitEvent(st, dx_ready[(size_t)(l + 1) * nch + r / Cz], 0));
-      CellBwdProb& q = a.p[np++];
-      q.dg_next_blk = (t == T - 1) ? nullptr : (const bf16_t*)(ws + L.dgblk[(t + 1) & 1]);
-      q.wt_blk = (const bf16_t*)(ws + L.whht_blk);
-      if (top) {
-        q.dy = A.dy_tm ? A.dy_tm + (size_t)t * B * H : (t == T - 1 ? A.dy_last : nullptr);
-      } else {
-        q.dy = (const float*)(ws + w.layer[l + 1].dx) + (size_t)t * B * H;
-      }
-      q.dy_ld = H;
-      q.gates = (const bf16_t*)(ws + L.gates) + (size_t)t * B * G;
-      q.c = (const float*)(ws + L.c_all) + (size_t)(t + 1) * B * H;
-      // (a CSN_LSTM_STATE plan reads c_all slot 0 at t = 0: c0, or the zeros its forward wrote there)
-      q.c_prev = (t == 0 && !state) ? nullptr : (const float*)(ws + L.c_all) + (size_t)t * B * H;
-      q.dc_carry = (float*)(ws + L.dc_carry);
-      q.dg_out = (bf16_t*)(ws + L.dgates) + (size_t)t * B * G;
-      q.dg_out_blk = (bf16_t*)(ws + L.dgblk[t & 1]);
+  auto cell = [&](CellBwdProb& q, const WaveCell& s) {
+    const int l = s.layer, t = s.t;
+    const LayerWs& L = w.layer[l];
+    q.dg_next_blk = (t == T - 1) ? nullptr : (const bf16_t*)(ws + L.dgblk[(t + 1) & 1]);
+    q.wt_blk = (const bf16_t*)(ws + L.whht_blk);
+    if (l == NL - 1) {
+      q.dy = A.dy_tm ? A.dy_tm + (size_t)t * B * H : (t == T - 1 ? A.dy_last : nullptr);
+    } else {
+      q.dy = (const float*)(ws + w.layer[l + 1].dx) + (size_t)t * B * H;
     }
-    if (np == 0) continue;
-    if ((rc = launch_cell_bwd_il(a, np, st, mk))) return rc;
+    q.dy_ld = H;
+    q.gates = (const bf16_t*)(ws + L.gates) + (size_t)t * B * G;
+    q.c = (const float*)(ws + L.c_all) + (size_t)(t + 1) * B * H;
+    // (a CSN_LSTM_STATE plan reads c_all slot 0 at t = 0: c0, or the zeros its forward wrote there)
+    q.c_prev = (t == 0 && !state) ? nullptr : (const float*)(ws + L.c_all) + (size_t)t * B * H;
+    q.dc_carry = (float*)(ws + L.dc_carry);
+    q.dg_out = (bf16_t*)(ws + L.dgates) + (size_t)t * B * G;
+    q.dg_out_blk = (bf16_t*)(ws + L.dgblk[t & 1]);
+  };
+  rc = wavefront_schedule(WaveIn{T, NL, Cz, WaveUnit::step, 2, true}, [&](const WaveLaunch& q) -> int {
+    CellBwdArgs a{};  a.B = B; a.H = H;
+    CellMask mask{C.dlen, {0, 0, 0, 0}};
+    for (int i = 0; i < q.ncells; ++i) {
+      const WaveCell& s = q.cell[i];      // entering a chunk: its dy (the dx of the layer above) has to be there
+      mask.t[i] = s.t;
+      if (s.layer < NL - 1 && s.enters) CSN_HIP_CHECK(hipStreamWaitEvent(st, dx_ready[(size_t)(s.layer + 1) * nch + s.chunk], 0));
+      cell(a.p[i], s);
+    }
+    if (int rc = launch_cell_bwd_il(a, q.ncells, st, C.dlen ? &mask : nullptr)) return rc;
     ++n_launch;
-    n_cells += np;
-    for (int l = NL - 1; l >= 0; --l) {
-      const int r = dg - lag * (NL - 1 - l);
-      if (r < 0 || r >= T || !ends_chunk(C, r)) continue;
-      const int cr = r / Cz;
-      const bool last = (r == T - 1);
-      if (l > 0 || last) {
-        if ((rc = hand_off(sc, st, side))) return rc;
-      }
+    n_cells += q.ncells;
+    for (int i = 0; i < q.ndone; ++i) {
+      const int l = q.done[i].layer, cr = q.done[i].chunk;
+      const bool last = q.done[i].last;
+      if (l > 0 || last)
+        if (int rc = hand_off(sc, st, side)) return rc;
       if (l > 0) {
-        if ((rc = dx_chunk_gemm(C, l, cr, A.dh_n, side))) return rc;
+        if (int rc = dx_chunk_gemm(C, l, cr, A.dh_n, side)) return rc;
         hipEvent_t ev;
-        if ((rc = next_event(sc, &ev))) return rc;
+        if (int rc = next_event(sc, &ev)) return rc;
         CSN_HIP_CHECK(hipEventRecord(ev, side));
         dx_ready[(size_t)l * nch + cr] = ev;
       } else if (last && A.dx != nullptr) {
-        if ((rc = dx_out(C, A.dx, side))) return rc;
+        if (int rc = dx_out(C, A.dx, side)) return rc;
       }
       // the weight gradients of a layer follow on the side stream once its recurrence is complete
-      if (last && (rc = weight_grads_blk(C, A, l, side))) return rc;
+      if (last)
+        if (int rc = weight_grads_blk(C, A, l, side)) return rc;
     }
-  }
+    return CSN_OK;
+  });
+  if (rc) return rc;
   if ((rc = prof_end(C, 1, n_launch, n_cells))) return rc;
   if ((rc = hand_off(sc, side, st))) return rc;   // the caller's stream resumes after all side-stream work
   // (the weight gradients of this path run on the side stream: only now are they ordered before the caller's stream)

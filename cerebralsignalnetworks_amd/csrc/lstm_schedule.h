@@ -1,8 +1,10 @@
-// Launch schedules of the weight-stationary LSTM paths (forward_persist / backward_persist, lstm.hip) as pure functions of
-// (T, B, H, L, chunk) and a few booleans: which (layer, chunk) cells a launch holds, which input-gradient GEMMs ride in
-// it, its tile height, which diagonals merge into one launch and which counter words that launch uses.  The host
-// functions build a schedule and enqueue it entry by entry.  Standard headers only, no HIP, no workspace pointers: a
-// host-only program includes this file and prints what the library runs (tests/lstm_schedule_probe.py).
+// Launch schedules of the LSTM host paths (lstm.hip) as pure functions of (T, B, H, L, chunk) and a few booleans.
+// Weight-stationary paths (forward_persist / backward_persist): which (layer, chunk) cells a launch holds, which
+// input-gradient GEMMs ride in it, its tile height, which diagonals merge into one launch and which counter words that
+// launch uses.  Per-diagonal and CU-resident paths (the _v1, _il and _resident pairs): the layer wavefront -- which cells a
+// launch holds, which launch closes its diagonal and which chunks the diagonal finished.  The host functions build a
+// schedule and enqueue it entry by entry.  Standard headers only, no HIP, no workspace pointers: a host-only program
+// includes this file and prints what the library runs (tests/lstm_schedule_probe.py).
 #pragma once
 #include <vector>
 
@@ -30,6 +32,61 @@ inline bool bwd_grouped(bool persist_bwd, int B, int L, int steps, int chunk, bo
   const int MTg = (B + 63) / 64, nchg = (steps + chunk - 1) / chunk;
   const int slots = L < nchg ? L : nchg;
   return slots <= 4 && slots * MTg <= 8 && !persist_streams;
+}
+
+// ---- layer wavefront of the per-diagonal and CU-resident paths (0, 1, 5 and the backward_il fall-back of 2 / 3) ------------
+// One machine, six drivers.  The layers advance as a wavefront: diagonal dg holds the i-th layer (forward: counted from
+// the bottom, backward: from the top) at unit dg - lag * i, a unit being a step (the _v1 and _il pairs) or a whole chunk
+// (the _resident pair), and a layer that finished a chunk is followed by a chunk job (forward: the input projection of
+// the layer above, backward: the input gradient = dy of the layer below) that the next layer's entry into that chunk
+// needs -- hence the lag, in chunks: 1 where the job runs on the caller's stream in front of the next diagonal (_v1,
+// _resident), 2 where it runs on the side stream beside the next chunk (_il).
+enum class WaveUnit { step, chunk };
+constexpr int kWaveMaxLayers = 8;       // (csn_lstm_plan_create takes L <= 8)
+struct WaveIn { int T, L, chunk; WaveUnit unit; int lag; bool backward; };      // T: the steps this call runs; lag in chunks
+struct WaveCell {
+  int layer, chunk;           // backward: the reverse chunk
+  int t, nsteps;              // forward: the steps [t, t + nsteps); backward: t, t - 1, ..., t - nsteps + 1 (t = BwdSlot's t_hi)
+  bool enters, ends;          // the first / the last unit of its chunk (ends_chunk); both always for whole-chunk units
+  bool last;                  // ... and the last of its layer: the layer's recurrence is complete
+};
+struct WaveLaunch {
+  WaveCell cell[4]; int ncells;       // 1 to 4, never two cells of one layer
+  bool closes;                // the last launch of its diagonal: the chunk jobs go behind it, never between the two launches of
+  WaveCell done[kWaveMaxLayers];      // a diagonal with more than four layers in range.  done: the cells of the WHOLE
+  int ndone;                  // diagonal that ended a chunk, in the diagonal's layer order (only on a closing launch)
+};
+
+// The recurrence launches in enqueue order, one call of visit(const WaveLaunch&) each; a non-zero return stops the walk
+// and is returned.  A diagonal without a layer in range (T < lag: the layers further apart than the sequence is long)
+// is not a launch.  A visitor, not a vector: the host functions consume each launch once, in order; nothing is allocated.
+template <class Visit>
+inline int wavefront_schedule(const WaveIn& in, Visit&& visit) {
+  const int T = in.T, L = in.L, nch = (T + in.chunk - 1) / in.chunk;
+  const bool by_step = in.unit == WaveUnit::step;
+  const int units = by_step ? T : nch, lag = by_step ? in.lag * in.chunk : in.lag;
+  const int ndiag = units + lag * (L - 1);
+  for (int dg = 0; dg < ndiag; ++dg) {
+    WaveCell on[kWaveMaxLayers];      // the cells of this diagonal
+    int n = 0;
+    for (int i = 0; i < L; ++i) {
+      const int u = dg - lag * i, layer = in.backward ? L - 1 - i : i;
+      if (u < 0 || u >= units) continue;
+      const Chunk k = by_step ? Chunk{u, 1} : chunk_at(T, in.chunk, u);
+      on[n++] = WaveCell{layer, by_step ? u / in.chunk : u, in.backward ? T - 1 - k.t0 : k.t0, k.nsteps,
+                         !by_step || u % in.chunk == 0, !by_step || ends_chunk(T, in.chunk, u), u == units - 1};
+    }
+    for (int first = 0; first < n; first += 4) {      // (more than 4 layers on one diagonal: a second launch, the problems are independent)
+      WaveLaunch q{};
+      q.ncells = n - first < 4 ? n - first : 4;
+      for (int i = 0; i < q.ncells; ++i) q.cell[i] = on[first + i];
+      q.closes = first + 4 >= n;
+      for (int i = 0; q.closes && i < n; ++i)
+        if (on[i].ends) q.done[q.ndone++] = on[i];
+      if (int rc = visit(q)) return rc;
+    }
+  }
+  return 0;
 }
 
 // ---- forward ------------------------------------------------------------------------------------------------------------

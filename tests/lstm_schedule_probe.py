@@ -6,6 +6,10 @@ csrc/lstm_schedule.h and csrc/gemm_beside.h, reads one query per line on stdin a
     grouped persist_bwd B L steps chunk persist_streams                            -> bwd_grouped: 0 / 1
     wide M N ngroups nslices grid_slices                                           -> beside_takes_wide: 0 / 1
     tiles npanels ntn xbase xcount local nworkers                                  -> beside_xcd_tiles: [first, end, step]
+    wave T L chunk by_chunk lag backward                                           -> wavefront_schedule: [launch]
+
+A wave launch is {"cells": [[layer, chunk, t, nsteps, enters, ends, last]], "closes": 0 / 1, "done": [[layer, chunk, last]]}:
+the cells of the launch, whether it closes its diagonal, and (closing launches only) the chunks the diagonal finished.
 
 build(dir) compiles it once (a module-scoped fixture per test module); the function it returns takes a list of query
 lines and returns the parsed answers, one process per list."""
@@ -61,6 +65,23 @@ static void print_fwd(const FwdSchedIn& in) {
   printf("]}\n");
 }
 
+static void print_wave(const WaveIn& in) {
+  int n = 0;
+  printf("[");
+  wavefront_schedule(in, [&](const WaveLaunch& q) {
+    printf("%s{\"cells\": [", n++ ? ", " : "");
+    for (int i = 0; i < q.ncells; ++i) {
+      const WaveCell& c = q.cell[i];
+      printf("%s[%d, %d, %d, %d, %d, %d, %d]", i ? ", " : "", c.layer, c.chunk, c.t, c.nsteps, (int)c.enters, (int)c.ends, (int)c.last);
+    }
+    printf("], \"closes\": %d, \"done\": [", (int)q.closes);
+    for (int i = 0; i < q.ndone; ++i) printf("%s[%d, %d, %d]", i ? ", " : "", q.done[i].layer, q.done[i].chunk, (int)q.done[i].last);
+    printf("]}");
+    return 0;
+  });
+  printf("]\n");
+}
+
 int main() {
   char line[256], what[16];
   int v[12];
@@ -78,6 +99,8 @@ int main() {
     else if (!strcmp(what, "tiles") && n == 6) {
       const BesideWalk w = beside_xcd_tiles(v[0], v[1], v[2], v[3], v[4], v[5]);
       printf("[%u, %u, %u]\n", w.first, w.end, w.step);
+    } else if (!strcmp(what, "wave") && n == 6 && v[0] >= 1 && v[1] >= 1 && v[1] <= kWaveMaxLayers && v[2] >= 1 && v[4] >= 1) {
+      print_wave(WaveIn{v[0], v[1], v[2], v[3] ? WaveUnit::chunk : WaveUnit::step, v[4], v[5] != 0});
     } else {
       fprintf(stderr, "bad query: %s", line);
       return 1;
@@ -111,6 +134,17 @@ def bwd_query(T, B, H, L, chunk, lengths=False, dropout=False, dh_n=False, flags
 
 def fwd_query(T, B, H, L, chunk, fwd_ns=False, persist_streams=False, no_half=False):
     return "fwd " + " ".join(str(int(v)) for v in (T, B, H, L, chunk, fwd_ns, persist_streams, no_half))
+
+
+# the six wavefronts of lstm.hip: (unit is a whole chunk, lag in chunks, backward)
+WAVE_VARIANTS = {"forward_v1": (False, 1, False), "backward_v1": (False, 1, True),
+                 "forward_resident": (True, 1, False), "backward_resident": (True, 1, True),
+                 "forward_il": (False, 2, False), "backward_il": (False, 2, True)}
+
+
+def wave_query(variant, T, L, chunk):
+    by_chunk, lag, backward = WAVE_VARIANTS[variant]
+    return "wave " + " ".join(str(int(v)) for v in (T, L, chunk, by_chunk, lag, backward))
 
 
 def bwd_rounds(launch, T, chunk):
