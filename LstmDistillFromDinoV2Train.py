@@ -92,7 +92,8 @@ def build_parser(flavour=PERILS):
                         'retrieval run in eval mode, without it)')
     p.add_argument('--bidirectional', action='store_true',
                    help='nn.LSTM(bidirectional=True): the encoder runs in both directions (BiLSTM) and fc takes the final '
-                        'state of each, 2 * hidden_size features (not with --lstm_dropout)')
+                        'state of each, 2 * hidden_size features; with --lstm_dropout the concatenated output of every '
+                        'layer but the top one is dropped once, as torch drops it')
     p.add_argument('--resident_lstm', action='store_true',
                    help='hidden_size <= 128: the LSTM runs the steps of a chunk inside one launch per layer, W_hh in '
                         'registers (CSN_LSTM_RESIDENT plans), with the bits of the per-step cell kernels')

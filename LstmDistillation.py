@@ -57,6 +57,10 @@ def build_parser():
     p.add_argument('--lstm_dropout', type=float, default=0.0,
                    help='nn.LSTM(dropout=p) between the LSTM layers of the STUDENT (0 = off); the teacher, which is never '
                         'trained, runs without it, like the stochastic depth of the reference\'s ViT teacher')
+    p.add_argument('--bidirectional', action='store_true',
+                   help='nn.LSTM(bidirectional=True): student and teacher encoders run in both directions (BiLSTM) and the '
+                        'heads take the final state of each, 2 * embed_dim features; works with --fused_views and '
+                        '--lstm_dropout')
     p.add_argument('--resident_lstm', action='store_true',
                    help='embed_dim <= 128: student and teacher LSTMs run the steps of a chunk inside one launch per layer, '
                         'W_hh in registers (CSN_LSTM_RESIDENT plans), with the bits of the per-step cell kernels')
@@ -109,11 +113,13 @@ def main(argv=None):
     def make(dropout=0.0):
         backbone = Model(input_size=C, lstm_size=FLAGS.embed_dim, lstm_layers=FLAGS.lstm_layers,
                          output_size=FLAGS.embed_dim, include_top=False, compute_dtype=dtype, dropout=dropout,
-                         resident=FLAGS.resident_lstm)
+                         bidirectional=FLAGS.bidirectional, resident=FLAGS.resident_lstm)
         return backbone
-    student = MultiCropWrapper(make(FLAGS.lstm_dropout), DINOHead(FLAGS.embed_dim, FLAGS.out_dim, FLAGS.use_bn_in_head,
+    # (MultiCropWrapper replaces the backbone's fc by the identity: the head reads the encoder's feature itself)
+    feat_dim = (2 if FLAGS.bidirectional else 1) * FLAGS.embed_dim
+    student = MultiCropWrapper(make(FLAGS.lstm_dropout), DINOHead(feat_dim, FLAGS.out_dim, FLAGS.use_bn_in_head,
                                                 FLAGS.norm_last_layer)).to(device)
-    teacher = MultiCropWrapper(make(), DINOHead(FLAGS.embed_dim, FLAGS.out_dim, FLAGS.use_bn_in_head)).to(device)
+    teacher = MultiCropWrapper(make(), DINOHead(feat_dim, FLAGS.out_dim, FLAGS.use_bn_in_head)).to(device)
     teacher.load_state_dict(student.state_dict())
     for p in teacher.parameters():
         p.requires_grad = False

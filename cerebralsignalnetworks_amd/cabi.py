@@ -62,6 +62,8 @@ SIGNATURES = {
                                          ctypes.c_int32, ctypes.c_int32]),
     "csn_lstm_plan_set_io": (_c_int, [_c_void_p, _c_i64, _c_i64, _c_int]),
     "csn_lstm_plan_set_dropout": (_c_int, [_c_void_p, _c_float, ctypes.c_uint64, ctypes.c_uint32]),
+    "csn_lstm_plan_set_output_dropout": (_c_int, [_c_void_p, _c_float, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint64,
+                                                  _c_i64]),
     "csn_lstm_dropout_keep": (_c_int, [ctypes.c_uint64, ctypes.c_uint32, _c_float, _c_i64, _c_i64, _c_void_p]),
     "csn_lstm_workspace_bytes": (_c_size_t, [ctypes.POINTER(LstmDesc), _c_int]),
     "csn_lstm_forward": (_c_int, [_c_void_p, _c_void_p, _c_i64, _c_i64,
@@ -510,6 +512,15 @@ class LstmPlan:
         again; a backward must run with the setting of its forward.  p > 0 needs a plan created with dropout=True."""
         _check(load().csn_lstm_plan_set_dropout(self._plan, float(p), int(seed) & 0xFFFFFFFFFFFFFFFF,
                                                 int(subsequence) & 0xFFFFFFFF))
+
+    def set_output_dropout(self, p, seed=0, subsequence=0, first=0, index_pitch=0):
+        """Dropout on y_all as the following forward() calls store it and on dy_all as the following backward() calls read
+        it (csn_lstm_plan_set_output_dropout): element (b, t, h) is kept iff ``lstm_dropout_keep(seed, subsequence, p,
+        first + (b * T + t) * index_pitch + h, 1)``, t the caller's time also on a reverse plan, and a kept element is
+        scaled by 1 / (1 - p).  p = 0 = off.  Sticky until set again; a backward must run with the setting of its forward.
+        With p > 0: first and index_pitch multiples of 4, index_pitch >= H."""
+        _check(load().csn_lstm_plan_set_output_dropout(self._plan, float(p), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                       int(subsequence) & 0xFFFFFFFF, int(first), int(index_pitch)))
 
     def dgates_copies(self):
         """Copies of the gate gradients the last backward wrote per step (csn_hip.h): 2, or 0 before any backward."""

@@ -526,6 +526,15 @@ struct csnLstmPlan {
   int resident = 0;                      // created with CSN_LSTM_RESIDENT: path 0's layout, the recurrence of lstm_resident.hip
   int64_t y_pitch = 0, dy_pitch = 0;     // csn_lstm_plan_set_io: elements per (b, t) row of y_all / dy_all, 0 = dense (H)
   int dx_add = 0;                        // csn_lstm_plan_set_io: dx is added to over the valid steps, not overwritten
+  // csn_lstm_plan_set_output_dropout (sticky; p = 0 = off): the mask the layout passes apply to y_all as they store it and
+  // to dy_all as they load it, indexed on the caller's tensor
+  float out_drop_p = 0.f;
+  uint64_t out_drop_seed = 0, out_drop_first = 0;
+  uint32_t out_drop_subsequence = 0;
+  int64_t out_drop_pitch = 0;
+  csn::OutDropCfg out_drop() const {
+    return csn::OutDropCfg{csn::dropout_cfg(out_drop_p, out_drop_seed, out_drop_subsequence), out_drop_first, out_drop_pitch};
+  }
   // csn_lstm_plan_set_lengths (empty = every row is T): the lengths of the next calls and the longest of them.  What a
   // call in progress derives from them lives in its Call, not here.  (len_dev: [B] int32 owned by the plan -- a state
   // plan's workspace is laid out exactly as a plain plan's)
@@ -714,6 +723,21 @@ extern "C" int csn_lstm_plan_set_dropout(csnLstmPlan* P, float p, uint64_t seed,
   P->drop_p = p;
   P->drop_seed = seed;
   P->drop_subsequence = subsequence;
+  return CSN_OK;
+}
+
+extern "C" int csn_lstm_plan_set_output_dropout(csnLstmPlan* P, float p, uint64_t seed, uint32_t subsequence, uint64_t first,
+                                                int64_t index_pitch) {
+  CSN_REQUIRE(P != nullptr, "csn_lstm_plan_set_output_dropout: null plan");
+  CSN_REQUIRE(p >= 0.f && p <= 1.f, "csn_lstm_plan_set_output_dropout: p = %g outside [0, 1]", (double)p);      // (NaN fails both)
+  CSN_REQUIRE(p == 0.f || (first % 4 == 0 && index_pitch % 4 == 0 && index_pitch >= P->d.H),
+              "csn_lstm_plan_set_output_dropout: first = %llu and index_pitch = %lld must be multiples of 4, index_pitch >= H = %d",
+              (unsigned long long)first, (long long)index_pitch, P->d.H);
+  P->out_drop_p = p;
+  P->out_drop_seed = seed;
+  P->out_drop_subsequence = subsequence;
+  P->out_drop_first = first;
+  P->out_drop_pitch = index_pitch;
   return CSN_OK;
 }
 
@@ -1958,10 +1982,12 @@ static int check_state_args(const Plan& P, const char* fn, const void* const* pt
   return CSN_OK;
 }
 
-// y_all of a reverse plan and / or with a pitch (csn_lstm_plan_set_io), with or without lengths
+// y_all of a reverse plan and / or with a pitch (csn_lstm_plan_set_io) and / or under output dropout, with or without lengths
 static int gather_y_all_io(const Call& C, float* y_all) {
   const LayerWs& top = C.w.layer[C.NL - 1];
   const int64_t n = (int64_t)C.T_full * C.B * C.H, pitch = C.P.y_pitch ? C.P.y_pitch : C.H;
+  if (C.P.out_drop_p > 0.f)       // csn_lstm_plan_set_output_dropout: the masked pass, whatever the pitch or direction
+    return launch_gather_y_all_drop(C.ws + top.h_all, C.dt, y_all, C.dlen, C.B, C.T_full, C.H, pitch, C.P.reverse, C.P.out_drop(), C.st);
   if (C.dt == CSN_BF16)
     gather_y_all_io_kernel<bf16_t><<<grid_for(n), 256, 0, C.st>>>((const bf16_t*)(C.ws + top.h_all), y_all, C.dlen, C.B, C.T_full, C.H, pitch, C.P.reverse);
   else
@@ -1980,6 +2006,8 @@ extern "C" int csn_lstm_forward(csnLstmPlan* Pp, const float* x, int64_t x_strid
   CSN_REQUIRE(x && w_ih && w_hh && b_ih && b_hh && workspace, "csn_lstm_forward: null pointer");
   CSN_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "csn_lstm_forward: workspace must be 256-B aligned");
   CSN_REQUIRE(y_last || y_all || h_n || c_n, "csn_lstm_forward: no output requested");
+  CSN_REQUIRE(P.out_drop_p == 0.f || (reinterpret_cast<uintptr_t>(y_all) & 15) == 0,
+              "csn_lstm_forward: y_all must be 16-B aligned under csn_lstm_plan_set_output_dropout");
   {
     const void* ptrs[4] = {h0, c0, h_n, c_n};
     const char* names[4] = {"h0", "c0", "h_n", "c_n"};
@@ -2037,7 +2065,7 @@ extern "C" int csn_lstm_forward(csnLstmPlan* Pp, const float* x, int64_t x_strid
     if (y_all) {
       const int T = C.T_full;       // the caller's rows: zeros from each row's length on
       const int64_t n = (int64_t)T * B * H;
-      if (P.reverse || P.y_pitch) {
+      if (P.reverse || P.y_pitch || P.out_drop_p > 0.f) {
         if ((rc = gather_y_all_io(C, y_all))) return rc;
       } else if (dt == CSN_BF16)
         gather_y_all_len_kernel<bf16_t><<<grid_for(n), 256, 0, st>>>((const bf16_t*)(ws + top.h_all), y_all, dlen, B, T, H);
@@ -2063,7 +2091,7 @@ extern "C" int csn_lstm_forward(csnLstmPlan* Pp, const float* x, int64_t x_strid
     if ((rc = launch_upcast(ws + top.h_all + (size_t)T * B * H * es, dt, y_last, (int64_t)B * H, st))) return rc;
   if (y_all) {
     const int64_t n = (int64_t)T * B * H;
-    if (P.reverse || P.y_pitch) {
+    if (P.reverse || P.y_pitch || P.out_drop_p > 0.f) {
       if ((rc = gather_y_all_io(C, y_all))) return rc;
     } else if (dt == CSN_BF16)
       gather_y_all_kernel<bf16_t><<<grid_for(n), 256, 0, st>>>((const bf16_t*)(ws + top.h_all), y_all, B, T, H);
@@ -2084,6 +2112,8 @@ extern "C" int csn_lstm_backward(csnLstmPlan* Pp, const float* dy_last, const fl
   CSN_REQUIRE(P.training, "csn_lstm_backward: the plan was created with training = 0");
   CSN_REQUIRE(workspace && dw_ih && dw_hh && db_ih && db_hh, "csn_lstm_backward: null pointer");
   CSN_REQUIRE(dy_last || dy_all || dh_n || dc_n, "csn_lstm_backward: no incoming gradient");
+  CSN_REQUIRE(P.out_drop_p == 0.f || (reinterpret_cast<uintptr_t>(dy_all) & 15) == 0,
+              "csn_lstm_backward: dy_all must be 16-B aligned under csn_lstm_plan_set_output_dropout");
   {
     const void* ptrs[4] = {dh_n, dc_n, dh0, dc0};
     const char* names[4] = {"dh_n", "dc_n", "dh0", "dc0"};
@@ -2117,7 +2147,9 @@ extern "C" int csn_lstm_backward(csnLstmPlan* Pp, const float* dy_last, const fl
     const int Te = C.T;
     if (Te > 0) {
       // zeros over the padding of dy
-      if (P.reverse || P.dy_pitch)
+      if (P.out_drop_p > 0.f) {
+        if ((rc = launch_bt_to_tb_drop(dy_all, buf, dlen, B, C.T_full, Te, H, P.dy_pitch ? P.dy_pitch : H, P.reverse, P.out_drop(), st))) return rc;
+      } else if (P.reverse || P.dy_pitch)
         bt_to_tb_io_kernel<<<grid_for((int64_t)Te * B * H), 256, 0, st>>>(dy_all, buf, dlen, B, C.T_full, Te, H, P.dy_pitch ? P.dy_pitch : H, P.reverse);
       else
         bt_to_tb_len_kernel<<<grid_for((int64_t)Te * B * H), 256, 0, st>>>(dy_all, buf, dlen, B, C.T_full, Te, H);
@@ -2171,7 +2203,9 @@ extern "C" int csn_lstm_backward(csnLstmPlan* Pp, const float* dy_last, const fl
   // gradient w.r.t. the top layer's outputs, time-major.  With only dy_last, no buffer is needed.
   const int T = C.T;
   if (dy_all) {
-    if (P.reverse || P.dy_pitch)
+    if (P.out_drop_p > 0.f) {
+      if ((rc = launch_bt_to_tb_drop(dy_all, buf, nullptr, B, T, T, H, P.dy_pitch ? P.dy_pitch : H, P.reverse, P.out_drop(), st))) return rc;
+    } else if (P.reverse || P.dy_pitch)
       bt_to_tb_io_kernel<<<grid_for(C.TB * H), 256, 0, st>>>(dy_all, buf, nullptr, B, T, T, H, P.dy_pitch ? P.dy_pitch : H, P.reverse);
     else
       bt_to_tb_kernel<<<grid_for(C.TB * H), 256, 0, st>>>(dy_all, buf, B, T, H);

@@ -46,7 +46,10 @@ def _direct_grads(owner, params):
 
 def _dropout_p(owner):
     """``owner.dropout`` as it is now (the attribute may have been assigned since construction): a float in [0, 1]."""
-    p = owner.dropout
+    return _check_dropout_p(owner.dropout)
+
+
+def _check_dropout_p(p):
     if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0 <= p <= 1:
         raise ValueError(f"dropout should be a number in range [0, 1] representing the probability of an element being "
                          f"zeroed, got {p!r}")
@@ -461,11 +464,26 @@ class _BiLstmFunction(torch.autograd.Function):
     plans, a plain and a CSN_LSTM_REVERSE one per layer, one after the other on the current stream.  The two directions
     of a layer write their halves of one [B,T,2H] tensor in place (csn_lstm_plan_set_io), which is the next layer's x;
     the backward reads the halves of its gradient in place and the second direction adds its input gradient to the
-    first's.  No torch op touches a [B,T,.] tensor here apart from allocating it."""
+    first's.  No torch op touches a [B,T,.] tensor here apart from allocating it.
+
+    ``drop`` = (p, seed, subsequence) or None: inter-layer dropout.  The plans of every layer below the top one store their
+    half of the interface tensor masked and scaled, and read their half of its gradient masked and scaled, inside the
+    layout passes they run anyway (csn_lstm_plan_set_output_dropout): one Philox stream per call covers the concatenated
+    [B,T,2H] interfaces, as torch drops each once.  ``views`` = (rows, starts) or None: x is a source tensor and layer 0's
+    two plans read their rows' windows of it in place (csn_lstm_plan_set_views); the batch is (len(rows), max(lengths))."""
 
     @staticmethod
-    def forward(ctx, x, h0, c0, owner, training, lengths, L, *params):
-        B, T, H = x.shape[0], x.shape[1], owner.hidden_size
+    def _set_output_dropout(plan, drop, l, d, L, B, T, H):
+        """On every forward and backward: plans are pooled, and the top layer's are never dropped."""
+        if drop is None or l >= L - 1:
+            plan.set_output_dropout(0.0)
+        else:
+            plan.set_output_dropout(*drop, first=l * B * T * 2 * H + d * H, index_pitch=2 * H)
+
+    @staticmethod
+    def forward(ctx, x, h0, c0, owner, training, lengths, views, drop, L, *params):
+        H = owner.hidden_size
+        B, T = (x.shape[0], x.shape[1]) if views is None else (len(lengths), max(1, max(lengths)))
         h_n = torch.empty((2 * L, B, H), dtype=torch.float32, device=x.device)
         c_n = torch.empty((2 * L, B, H), dtype=torch.float32, device=x.device)
         leases, inp = [], x
@@ -476,18 +494,29 @@ class _BiLstmFunction(torch.autograd.Function):
                 w = [[params[4 * k + g]] for g in range(4)]
                 plan = owner._checkout(B, T, inp.shape[2], x.device, training, reverse=d == 1)
                 lease = _Lease(plan)        # (at once: the next direction / layer of the same shape must take another plan)
-                plan.set_lengths(lengths)
-                plan.set_io(2 * H, 2 * H, False)
-                plan.forward(inp, *w, h0=None if h0 is None else h0[k:k + 1], c0=None if c0 is None else c0[k:k + 1],
-                             want_state=True, y_all=out[:, :, d * H:(d + 1) * H], state_out=(h_n[k:k + 1], c_n[k:k + 1]))
+                run = lambda: plan.forward(inp, *w, h0=None if h0 is None else h0[k:k + 1],              # noqa: E731
+                                           c0=None if c0 is None else c0[k:k + 1], want_state=True,
+                                           y_all=out[:, :, d * H:(d + 1) * H], state_out=(h_n[k:k + 1], c_n[k:k + 1]))
+                try:
+                    plan.set_io(2 * H, 2 * H, False)
+                    _BiLstmFunction._set_output_dropout(plan, drop, l, d, L, B, T, H)
+                    if views is not None and l == 0:
+                        _run_views(plan, x, views, lengths, run)
+                    else:
+                        plan.set_lengths(lengths)
+                        run()
+                except BaseException:
+                    for held in leases + [lease]:       # (a refused call, e.g. a window past the source: nothing stays leased)
+                        held.release()
+                    raise
                 if training:
                     leases.append(lease)
                 else:
                     lease.release()
             inp = out
-        ctx.leases, ctx.L, ctx.owner, ctx.lengths = leases, L, owner, lengths
+        ctx.leases, ctx.L, ctx.owner, ctx.lengths, ctx.drop = leases, L, owner, lengths, drop
         ctx.need = (x.requires_grad, h0 is not None and h0.requires_grad, c0 is not None and c0.requires_grad)
-        ctx.x_shape = x.shape
+        ctx.x_shape = (B, T, x.shape[2])
         ctx.param_like = params
         return inp, h_n, c_n
 
@@ -506,6 +535,9 @@ class _BiLstmFunction(torch.autograd.Function):
         dc0 = torch.empty((2 * L, B, H), dtype=torch.float32, device=dev) if need_dc0 else None
         if dy.dtype != torch.float32 or not dy.is_contiguous():
             dy = dy.float().contiguous()    # (autograd hands a dense gradient as a rule: an expanded or sliced one is copied once)
+        if dy.data_ptr() % 16:
+            dy = dy.clone()                 # (a pitched dy_all is taken on 16 bytes, and the masked load moves 16: a dense gradient
+                                            # at an odd storage offset is copied once)
         for l in range(L - 1, -1, -1):
             width = ctx.x_shape[2] if l == 0 else 2 * H
             dinp = torch.empty((B, T, width), dtype=torch.float32, device=dev) if (l > 0 or need_dx) else None
@@ -516,12 +548,13 @@ class _BiLstmFunction(torch.autograd.Function):
                 plan.set_grad_mode(False)
                 plan.set_lengths(ctx.lengths)
                 plan.set_io(2 * H, 2 * H, d == 1)       # the reverse direction adds its dx to the forward one's
+                _BiLstmFunction._set_output_dropout(plan, ctx.drop, l, d, L, B, T, H)     # the mask of its forward
                 plan.backward(None, dy[:, :, d * H:(d + 1) * H], [[grads[4 * k + g]] for g in range(4)], dx=dinp,
                               dh_n=dh_n[k:k + 1], dc_n=dc_n[k:k + 1], dh0=None if dh0 is None else dh0[k:k + 1],
                               dc0=None if dc0 is None else dc0[k:k + 1])
                 leases[k].release()
             dy = dinp
-        return (dy, dh0, dc0, None, None, None, None, *grads)
+        return (dy, dh0, dc0, None, None, None, None, None, None, *grads)
 
 
 class BiLSTM(nn.Module):
@@ -542,8 +575,15 @@ class BiLSTM(nn.Module):
     H 768, L 2 in bf16 that is 2 x 4.32 GB (layer 0) + 2 x 5.42 GB (layer 1, input width 2H) = 19.48 GB, against 8.47 GB
     for the unidirectional two-layer plan (csn_lstm_workspace_bytes; 22.77 GB at B 256, T 440, H 1024).
 
-    Not in this class: inter-layer dropout (it lives between the layers of one plan: ``dropout != 0`` is refused), and
-    the direct / accumulating gradient writes of ``HipLSTM`` (gradients go to autograd temporaries).
+    Inter-layer dropout, as on ``LSTM``: the constructor still refuses ``dropout != 0``; set the attribute
+    (``bilstm.dropout = p``), which is read on every call as nn.LSTM.forward reads it and is active in train() mode with
+    ``num_layers >= 2``, also under no_grad.  The concatenated [B,T,2H] output of every layer but the top one is masked
+    once and scaled by 1/(1 - p), inside the layout passes the plans run anyway (csn_lstm_plan_set_output_dropout,
+    DESIGN.md section 23).  ``dropout_subsequence``: None = the torch.distributed rank.
+
+    Input windows: ``forward(x, hx, lengths, views=(rows, starts))`` has ``LSTM.forward``'s contract.
+
+    Not in this class: the direct / accumulating gradient writes of ``HipLSTM`` (gradients go to autograd temporaries).
     """
 
     MAX_IDLE_PLANS = 4
@@ -557,6 +597,7 @@ class BiLSTM(nn.Module):
         self.input_size, self.hidden_size, self.num_layers = input_size, hidden_size, num_layers
         self.compute_dtype = compute_dtype
         self.bias, self.batch_first, self.dropout, self.bidirectional, self.proj_size = True, True, 0.0, True, 0
+        self.dropout_subsequence = None
         ref = nn.LSTM(input_size, hidden_size, num_layers=num_layers, batch_first=True, bidirectional=True)
         for name, p in ref.named_parameters():      # same init, key names and order
             self.register_parameter(name, nn.Parameter(p.detach().clone()))
@@ -580,7 +621,14 @@ class BiLSTM(nn.Module):
     def all_plans(self):
         return [pl for lst in self._plans.values() for pl in lst]
 
-    def forward(self, x, hx=None, lengths=None):
+    def forward(self, x, hx=None, lengths=None, views=None):
+        """``views = (rows, starts)``, each B' ints, with ``lengths`` (B' ints, required): x is a SOURCE [S, Tsrc, I] and
+        row b of the batch is ``x[rows[b], starts[b]:starts[b] + lengths[b]]``, read in place by layer 0's two plans.  The
+        batch is then B' = len(rows), T' = max(lengths): output [B', T', 2H], hx and (h_n, c_n) [2L, B', H], all with the
+        bits of the call on the gathered rows.  No gradient reaches x through views (``x.requires_grad`` raises)."""
+        if views is not None:
+            rows, starts, lengths = _check_views("BiLSTM", x, views, lengths, self.input_size)
+            views = (rows, starts)
         if isinstance(x, nn.utils.rnn.PackedSequence):
             return _forward_packed(self, "BiLSTM", x, hx, lengths)
         if x.dim() != 3:
@@ -588,7 +636,7 @@ class BiLSTM(nn.Module):
                              f"{list(x.shape)} (unbatched input is not supported)")
         if x.shape[2] != self.input_size:
             raise ValueError(f"BiLSTM: input has {x.shape[2]} features, expected {self.input_size}")
-        B, L, H = x.shape[0], self.num_layers, self.hidden_size
+        B, L, H = (x.shape[0] if views is None else len(views[0])), self.num_layers, self.hidden_size
         h0 = c0 = None
         if hx is not None:
             h0, c0 = hx
@@ -596,14 +644,16 @@ class BiLSTM(nn.Module):
                 if tuple(t.shape) != (2 * L, B, H):
                     raise ValueError(f"BiLSTM: {name} must be [2 * num_layers, B, hidden_size] = {[2 * L, B, H]}, got "
                                      f"{list(t.shape)}")
-        lengths = _check_lengths("BiLSTM", lengths, B, x.shape[1])
+        if views is None:
+            lengths = _check_lengths("BiLSTM", lengths, B, x.shape[1])
+        _dropout_p(self)
         if not x.is_cuda:
             raise cabi.CsnError("BiLSTM runs on the GPU only (no CPU fallback); move the module and input to cuda")
         params = [getattr(self, f"{n}_l{k}{sfx}") for k in range(L) for sfx in ("", "_reverse")
                   for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
         training = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params) or
                                                 any(t is not None and t.requires_grad for t in (h0, c0)))
-        output, h_n, c_n = _BiLstmFunction.apply(x, h0, c0, self, training, lengths, L, *params)
+        output, h_n, c_n = _BiLstmFunction.apply(x, h0, c0, self, training, lengths, views, _draw_dropout(self), L, *params)
         return output, (h_n, c_n)
 
 
@@ -621,7 +671,9 @@ class Model(nn.Module):
         self.input_size, self.lstm_size, self.lstm_layers = input_size, lstm_size, lstm_layers
         self.output_size, self.include_top, self.bidirectional = output_size, include_top, bool(bidirectional)
         if self.bidirectional:
-            self.lstm = BiLSTM(input_size, lstm_size, lstm_layers, compute_dtype=compute_dtype, dropout=dropout, resident=resident)
+            self.lstm = BiLSTM(input_size, lstm_size, lstm_layers, compute_dtype=compute_dtype, resident=resident)
+            # (the attribute, as on the LSTM drop-in: its constructor takes 0 only)
+            self.lstm.dropout = _check_dropout_p(dropout)
         else:
             self.lstm = HipLSTM(input_size, lstm_size, lstm_layers, compute_dtype=compute_dtype, dropout=dropout, resident=resident)
         self.fc = nn.Linear((2 if self.bidirectional else 1) * lstm_size, output_size)
@@ -630,13 +682,12 @@ class Model(nn.Module):
 
     def forward(self, x, views=None, lengths=None):
         """``views = (rows, starts)`` with ``lengths``: x is a source [S, Tsrc, C] and the result has one row per window
-        (HipLSTM.forward_views) -- feature rows [B', output_size], and the class logits with include_top."""
-        if views is not None and self.bidirectional:
-            raise ValueError("Model: views are not supported with bidirectional=True")
+        (HipLSTM.forward_views, or BiLSTM.forward with views) -- feature rows [B', output_size], and the class logits with
+        include_top."""
         if views is None and lengths is not None:
             raise ValueError("Model: lengths are taken with views only")
         if self.bidirectional:
-            _, (h_n, _) = self.lstm(x)
+            _, (h_n, _) = self.lstm(x, None, lengths, views)
             last = torch.cat((h_n[-2], h_n[-1]), dim=1)    # [B, 2H]
         elif views is not None:
             last = self.lstm.forward_views(x, views, lengths)      # [B', H] = top layer at each window's last step

@@ -408,6 +408,32 @@ int csn_lstm_plan_set_dropout(csnLstmPlan* plan, float p, uint64_t seed, uint32_
  * i in [0, n).  Host code filling a host array: no device, no stream, usable on a machine without a GPU. */
 int csn_lstm_dropout_keep(uint64_t seed, uint32_t subsequence, float p, int64_t first, int64_t n, uint8_t* keep_host);
 
+/* Output dropout: a dropout mask on y_all as the plan STORES it and on dy_all as the plan READS it, for a caller that
+ * stacks single-layer plans itself (the 2L plans of a bidirectional stack, which share one [B, T, 2H] tensor per layer
+ * through csn_lstm_plan_set_io).  Host only, no stream, sticky until set again like
+ * csn_lstm_plan_set_io; it needs no plan bit and changes no workspace, and it is independent of
+ * csn_lstm_plan_set_dropout (a plan may carry both).
+ *   INDEX.  Element (b, t, h) of y_all has the 64-bit index  e = first + (b T + t) index_pitch + h,  T the plan's T and t
+ *   the CALLER's time -- also on a CSN_LSTM_REVERSE plan, because this mask lives on the caller's tensor.  (NOT as in
+ *   csn_lstm_plan_set_dropout, whose mask lives in the workspace and whose t is the recurrence step.)  With
+ *   first = l B T 2H + d H and index_pitch = 2H the two directions d of layer l draw the halves of ONE stream over the
+ *   concatenated [B, T, 2H] interface.
+ *   KEEP.  csn_lstm_dropout_keep(seed, subsequence, p, e, 1): the same Philox4x32-10 words, threshold and p = 1 rule.
+ *   FORWARD.  y_all[b, t, h] = t < n ? (keep ? float(h_top) * s : 0.f) : 0.f  with s = 1.0f / (1.0f - p) in float32
+ *   arithmetic and n the row's length (T without lengths): a selected zero.  y_last, h_n, c_n, the recurrent h and
+ *   everything inside the plan are untouched.
+ *   BACKWARD.  dy_all is READ as keep ? dy * s : 0.f with the same index; NaN / Inf at a dropped or padded element do not
+ *   get through.  dy_last, dh_n, dc_n are untouched.  The matching backward must run with its forward's setting, as for
+ *   the lengths.
+ * With p = 0 (the default) the plan enqueues the launches and writes the bits it did before this symbol existed.  With
+ * p > 0 the two layout passes are the kernels of lstm_dropout.hip, whatever the plan's pitch or direction: no extra pass
+ * and no extra launch.  They move 16 bytes per access, so with p > 0 csn_lstm_forward / csn_lstm_backward return
+ * CSN_ERR_INVALID_ARGUMENT, before enqueueing anything, for a y_all / dy_all that is not 16-byte aligned.
+ * Null plan, p outside [0, 1] or NaN, or with p > 0: first % 4 != 0, index_pitch % 4 != 0, index_pitch < H:
+ * CSN_ERR_INVALID_ARGUMENT (the setting is kept). */
+int csn_lstm_plan_set_output_dropout(csnLstmPlan* plan, float p, uint64_t seed, uint32_t subsequence, uint64_t first,
+                                     int64_t index_pitch);
+
 /* The workspace's status word: 0 = ok.  Bit CSN_STATUS_TIMEOUT: a bounded in-kernel wait of a weight-stationary
  * kernel gave up at some point since the word was last cleared (the results of that forward / backward and of every
  * later one are invalid).  Bit CSN_STATUS_NONFINITE: a NaN / Inf gradient reached the backward recurrence (the
