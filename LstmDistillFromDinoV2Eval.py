@@ -74,12 +74,16 @@ def main(argv=None):
         loaders = [DataLoader(Subset(dataset, ix.tolist()), batch_size=FLAGS.batch_size, shuffle=False) for ix in (tr, te)]
         gallery, glab = dataset.transformEEGDataLSTMByList(model=embedder, data_loader=loaders[0])
         query, qlab = dataset.transformEEGDataLSTMByList(model=embedder, data_loader=loaders[1])
+        if FLAGS.normalize_embeddings:
+            gallery, query = train_cli.normalize_rows(gallery), train_cli.normalize_rows(query)
         trainer.check_device_status()
         r = evaluate_full(FLAGS, gallery, query, glab, qlab, dataset)
     else:
         tr, te = (ix[rank::world].to(device) for ix in split_indices(N, (0.8, 0.2), seed=43))      # random_split, Eval.py:324-325
         gallery = trainer.embed_all(dataset.eeg_all[tr], FLAGS.batch_size)
         query = trainer.embed_all(dataset.eeg_all[te], FLAGS.batch_size)
+        if FLAGS.normalize_embeddings:
+            gallery, query = train_cli.normalize_rows(gallery), train_cli.normalize_rows(query)
         trainer.check_device_status()      # every embedding batch above: a timed-out in-kernel hand-off invalidates the run
         glab = [dataset.getLabelbyIndex(int(i)) for i in tr.cpu()]
         qlab = [dataset.getLabelbyIndex(int(i)) for i in te.cpu()]

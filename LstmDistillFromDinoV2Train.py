@@ -98,7 +98,12 @@ def build_parser(flavour=PERILS):
                    help='hidden_size <= 128: the LSTM runs the steps of a chunk inside one launch per layer, W_hh in '
                         'registers (CSN_LSTM_RESIDENT plans), with the bits of the per-step cell kernels')
     p.add_argument('--output_size', type=int, default=384)
-    p.add_argument('--loss', type=str, default=flavour.loss, choices=["featdist", "cosine", "kd", "barlow"])
+    p.add_argument('--loss', type=str, default=flavour.loss, choices=["featdist", "cosine", "kd", "barlow", "contrastive"])
+    p.add_argument('--contrastive_temperature', type=float, default=0.07,
+                   help='--loss contrastive: the fixed temperature of the symmetric InfoNCE loss (logit scale = 1 / temperature)')
+    p.add_argument('--contrastive_mask', type=str, default="image", choices=["image", "class", "none"],
+                   help='--loss contrastive: rows that are not each other\'s negatives -- the same image (shown to several '
+                        'subjects), the same class, or none')
     p.add_argument('--optimizer', type=str, default=flavour.optimizer, choices=["rmsprop", "adamw", "adam", "lars"])
     p.add_argument('--dtype', type=str, default="bf16", choices=["bf16", "f32"])
     p.add_argument('--fs', type=float, default=1000.0, help='sampling rate for the band-pass design')
@@ -113,16 +118,26 @@ def build_parser(flavour=PERILS):
     p.add_argument('--fused_optimizer', action='store_true',
                    help='adamw / adam / lars as fused HIP steps over the flat parameter buffer (rmsprop always is)')
     p.add_argument('--fused_loss', action='store_true',
-                   help='featdist / kd / barlow: loss value and gradient from fused HIP calls in float64 (csn_distill_loss, '
-                        'csn_barlow_corr + csn_barlow_grad) instead of a chain of torch ops; does nothing with --loss cosine '
-                        '(always fused)')
+                   help='featdist / kd / barlow / contrastive: loss value and gradient from fused HIP calls in float64 '
+                        '(csn_distill_loss, csn_barlow_corr + csn_barlow_grad, csn_contrastive_lse + csn_contrastive_grad) '
+                        'instead of a chain of torch ops; does nothing with --loss cosine (always fused)')
     p.add_argument('--compat_label_bug', action='store_true',
                    help='reproduce the batch-local label lookup of transformEEGDataLSTMByList')
+    p.add_argument('--normalize_embeddings', action='store_true',
+                   help='retrieval leg: L2-normalise gallery and query embeddings first, so that the L2 ranking is the '
+                        'cosine ranking (what --loss contrastive trains)')
     p.add_argument('--device_eval', action='store_true',
                    help='retrieval leg: the embeddings stay on the device, class hits are counted there (csn_topk_merge, '
                         'csn_topk_class_metrics) and the host folds per-class integers into the same Recall / Precision / '
                         'top1 (not with --compat_label_bug, which keeps the host form)')
     return p
+
+
+def normalize_rows(rows):
+    """--normalize_embeddings: rows / max(|row|, 1e-12) of a [N,D] tensor or of a list of numpy rows."""
+    if torch.is_tensor(rows):
+        return torch.nn.functional.normalize(rows, dim=1, eps=1e-12)
+    return [r / max(float(np.linalg.norm(r)), 1e-12) for r in rows]
 
 
 class _KdParams:
@@ -224,7 +239,7 @@ def main(argv=None, flavour=PERILS):
     trainer = DistillTrainer(model, sos, loss=FLAGS.loss, lr=FLAGS.learning_rate, optimizer=FLAGS.optimizer,
                              nepochs=max(FLAGS.num_epochs, HyperParams.warmup_teacher_temp_epochs + 1), kd_params=kd,
                              accum_steps=FLAGS.accum_steps, fused_optimizer=FLAGS.fused_optimizer,
-                             fused_loss=FLAGS.fused_loss)
+                             fused_loss=FLAGS.fused_loss, contrastive_temperature=FLAGS.contrastive_temperature)
 
     def batches(idx, epoch, shuffle, multiple_of=1):
         shard = idx[shard_indices(len(idx), epoch, FLAGS.seed, rank, world, shuffle=shuffle).to(device)]
@@ -234,6 +249,12 @@ def main(argv=None, flavour=PERILS):
             if len(b):
                 yield b
 
+    def loss_kw(b):
+        """--loss contrastive: the group ids of the batch, by --contrastive_mask."""
+        if FLAGS.loss != "contrastive" or FLAGS.contrastive_mask == "none":
+            return {}
+        return {"groups": (dataset.image_ids_dev if FLAGS.contrastive_mask == "image" else dataset.labels_dev)[b]}
+
     def labels_of(ix):
         return [dataset.getLabelbyIndex(int(i)) for i in ix.cpu()]
 
@@ -241,7 +262,8 @@ def main(argv=None, flavour=PERILS):
     for EPOCH in range(FLAGS.num_epochs):
         losses = []
         for b in batches(train_idx, EPOCH, True, FLAGS.accum_steps):
-            losses.append(trainer.train_step(dataset.eeg_all[b], dataset.features_all[b], dataset.labels_dev[b], EPOCH))
+            losses.append(trainer.train_step(dataset.eeg_all[b], dataset.features_all[b], dataset.labels_dev[b], EPOCH,
+                                             **loss_kw(b)))
         trainer.check_device_status()      # per epoch: a timed-out in-kernel hand-off must not pass silently
         epoch_loss = float(torch.stack(losses).mean().item())                    # one sync per epoch, not per step
         if EPOCH % FLAGS.validation_frequency == 0 and EPOCH > 0:
@@ -256,6 +278,8 @@ def main(argv=None, flavour=PERILS):
                            for ix in (train_idx, val_idx)]
                 gallery_features, gallery_labels = dataset.transformEEGDataLSTMByList(model=embedder, data_loader=loaders[0])
                 query_features, query_labels = dataset.transformEEGDataLSTMByList(model=embedder, data_loader=loaders[1])
+                if FLAGS.normalize_embeddings:
+                    gallery_features, query_features = normalize_rows(gallery_features), normalize_rows(query_features)
                 r = evaluate_full(FLAGS, gallery_features, query_features, gallery_labels, query_labels, dataset)
             else:
                 # each rank embeds ITS shard of the gallery and of the queries; the neighbour lists are gathered
@@ -266,6 +290,8 @@ def main(argv=None, flavour=PERILS):
                     q_ix = q_ix[: len(range(rank, len(val_idx), world))]
                 gallery = trainer.embed_all(dataset.eeg_all[g_ix], FLAGS.batch_size)
                 query = trainer.embed_all(dataset.eeg_all[q_ix], FLAGS.batch_size)
+                if FLAGS.normalize_embeddings:
+                    gallery, query = normalize_rows(gallery), normalize_rows(query)
                 if FLAGS.device_eval and world == 1:
                     r = evaluate_device(FLAGS, gallery, query, labels_of(g_ix), labels_of(q_ix), dataset)
                 else:
@@ -277,7 +303,8 @@ def main(argv=None, flavour=PERILS):
             with torch.no_grad():
                 for b in batches(val_idx, 0, False):
                     out = model(trainer.embed(dataset.eeg_all[b]))
-                    vsum[0] += trainer.compute_loss(out, dataset.features_all[b], dataset.labels_dev[b], EPOCH).double()
+                    vsum[0] += trainer.compute_loss(out, dataset.features_all[b], dataset.labels_dev[b], EPOCH,
+                                                       **loss_kw(b)).double()
                     vsum[1] += 1
             if world > 1:
                 if dist.get_backend() == "nccl":

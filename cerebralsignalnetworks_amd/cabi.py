@@ -120,6 +120,11 @@ SIGNATURES = {
                                  _c_void_p, _c_double, _c_void_p]),
     "csn_barlow_grad": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_double, _c_double,
                                  _c_float, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+    "csn_contrastive_scratch_bytes": (_c_size_t, [_c_int, _c_int, _c_int]),
+    "csn_contrastive_lse": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_double, _c_double,
+                                     _c_double, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+    "csn_contrastive_grad": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_double, _c_void_p,
+                                      _c_void_p, _c_double, _c_double, _c_double, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
     "csn_l2_topk_scratch_bytes": (_c_size_t, [_c_i64, _c_i64]),
     "csn_l2_topk": (_c_int, [_c_void_p, _c_void_p, _c_i64, _c_i64, _c_int, _c_int, _c_void_p, _c_void_p,
                              _c_void_p, _c_void_p]),
@@ -871,6 +876,62 @@ def barlow_grad(z1, z2, c, c_local, saved, batch_size, lambd, grad_scale=1.0, wa
         _check(lib.csn_barlow_grad(_ptr(a), _ptr(b), B, D, _ptr(c), _ptr(c_local), _ptr(saved), 1.0 / float(batch_size),
                                    float(lambd), float(grad_scale), _ptr(loss), _ptr(dz1), _ptr(dz2), _ptr(scratch), _stream()))
     return loss, dz1, dz2
+
+
+def _contrastive_inputs(s_all, t_all, group_all, row0, B, who):
+    _need_cuda(s_all, t_all, group_all)
+    s, t = _f32_rows(s_all, "s_all", 2), _f32_rows(t_all, "t_all", 2)
+    if s.shape != t.shape or s.device != t.device:
+        raise CsnError(f"{who}: t_all {tuple(t.shape)} on {t.device} against s_all {tuple(s.shape)} on {s.device}")
+    N, D = s.shape
+    if group_all is not None:
+        if group_all.dtype != torch.int32 or tuple(group_all.shape) != (N,) or group_all.device != s.device:
+            raise CsnError(f"{who}: group_all must be an int32 [{N}] tensor on {s.device}, got {group_all.dtype} "
+                           f"{tuple(group_all.shape)} on {group_all.device}")
+        group_all = group_all.contiguous()
+    B = N - row0 if B is None else B
+    return s, t, group_all, N, D, int(B)
+
+
+def _contrastive_scratch(lib, B, N, D, device):
+    return torch.empty(lib.csn_contrastive_scratch_bytes(B, N, D) // 8, dtype=torch.float64, device=device)       # caller-owned
+
+
+def contrastive_lse(s_all, t_all, logit_scale, group_all=None, row0=0, B=None, w_a=0.5, w_b=0.5):
+    """csn_contrastive_lse on the gathered rows s_all / t_all [N,D] float32 (group_all: int32 [N] or None) for the local rows
+    row0 .. row0+B-1 (default: all from row0 on) -> (rows_out [3,B] float64: lA, lB, p; loss_part [1] float64: the local
+    rows' part of the global loss)."""
+    s, t, g, N, D, B = _contrastive_inputs(s_all, t_all, group_all, row0, B, "contrastive_lse")
+    lib = load()
+    rows_out = torch.empty((3, max(B, 0)), dtype=torch.float64, device=s.device)
+    loss_part = torch.empty(1, dtype=torch.float64, device=s.device)
+    scratch = _contrastive_scratch(lib, B, N, D, s.device)
+    with torch.cuda.device(s.device):
+        _check(lib.csn_contrastive_lse(_ptr(s), _ptr(t), _ptr(g), N, D, int(row0), B, float(logit_scale), float(w_a),
+                                       float(w_b), _ptr(rows_out), _ptr(loss_part), _ptr(scratch), _stream()))
+    return rows_out, loss_part
+
+
+def contrastive_grad(s_all, t_all, logit_scale, lse_a_local, lse_b_all, group_all=None, row0=0, B=None, w_a=0.5, w_b=0.5,
+                     grad_scale=1.0, want_dscale=False):
+    """csn_contrastive_grad -> (ds [B,D] float32, holding grad_scale; dscale_part [1] float64 | None: the local rows' part
+    of dL/d logit_scale).  ``lse_a_local`` [B] and ``lse_b_all`` [N] float64: rows 0 and 1 of contrastive_lse's rows_out on
+    one rank, lB all-gathered in rank order on several."""
+    s, t, g, N, D, B = _contrastive_inputs(s_all, t_all, group_all, row0, B, "contrastive_grad")
+    _need_cuda(lse_a_local, lse_b_all)
+    for name, v, n in (("lse_a_local", lse_a_local, B), ("lse_b_all", lse_b_all, N)):
+        if v.dtype != torch.float64 or tuple(v.shape) != (n,) or not v.is_contiguous() or v.device != s.device:
+            raise CsnError(f"contrastive_grad: {name} must be a contiguous float64 [{n}] tensor on {s.device}, "
+                           f"got {v.dtype} {tuple(v.shape)} on {v.device}")
+    lib = load()
+    ds = torch.empty((max(B, 0), D), dtype=torch.float32, device=s.device)
+    dscale = torch.empty(1, dtype=torch.float64, device=s.device) if want_dscale else None
+    scratch = _contrastive_scratch(lib, B, N, D, s.device)
+    with torch.cuda.device(s.device):
+        _check(lib.csn_contrastive_grad(_ptr(s), _ptr(t), _ptr(g), N, D, int(row0), B, float(logit_scale), _ptr(lse_a_local),
+                                        _ptr(lse_b_all), float(w_a), float(w_b), float(grad_scale), _ptr(ds), _ptr(dscale),
+                                        _ptr(scratch), _stream()))
+    return ds, dscale
 
 
 def l2_topk(gallery, query, k):

@@ -67,6 +67,7 @@ class EEGDataset(Dataset):
             raw = synthetic_eeg(synthetic, synthetic_channels, synthetic_samples, seed=seed)      # [N,C,T_raw]
             self.labels = torch.randint(0, n_classes, (synthetic,), generator=torch.Generator().manual_seed(seed + 2))
             self.images = [f"n{int(c):08d}_{i}" for i, c in enumerate(self.labels)]
+            image_ids = torch.arange(synthetic)
             for c in range(n_classes):
                 wnid = f"n{c:08d}"
                 self.class_labels_names[wnid] = {"ClassId": c, "ClassName": f"class_{c}", "imagenetClassId": str(c)}
@@ -97,6 +98,7 @@ class EEGDataset(Dataset):
             self.class_labels = loaded["labels"]
             image_names = loaded["images"]
             self.images = [image_names[int(it["image"])] for it in items]
+            image_ids = torch.tensor([int(it["image"]) for it in items])
             self._read_label_file(set(n.split("_")[0] for n in image_names))
             if flavour == "spampinato":
                 if apply_norm_with_stds_and_means:                          # EEGDataset.py:104-105 (at load)
@@ -118,6 +120,8 @@ class EEGDataset(Dataset):
             raw = raw[:, self.filter_channels, :]
         self.eeg_all = raw[:, :, time_low:time_high].contiguous().to(self.device)      # [N,C,T]
         self.labels_dev = self.labels.to(self.device)
+        # the item's index into the file's image list (several subjects see one image): the group ids of ContrastiveLoss
+        self.image_ids_dev = image_ids.to(self.device)
         self.size = self.eeg_all.shape[0]
         if apply_channel_wise_norm and flavour == "perils" and not synthetic:
             self.transformEEGDataToChannelWiseNorm(compat_stale_index=compat_stale_index,      # :132-134

@@ -8,6 +8,8 @@
   FeatureDistributionLossMSE LstmDistillation.py:161-172 (global mean / std / MSE match)
   BarlowTwinsLoss            EEG-BarlowNetworks/net.py:33-42 (HIP off-diagonal reduction; fused=True: csn_barlow_corr + _grad)
   LARS, barlow_learning_rate EEG-BarlowNetworks/optim.py:5-44, barlow_utils.py:8-21
+  ContrastiveLoss            not in the reference: the symmetric InfoNCE loss against frozen teacher rows, global negatives
+                             (torch ops; fused=True: csn_contrastive_lse + csn_contrastive_grad)
 Every class is checked against values and gradients obtained by executing the reference's own definition
 (tests/golden/ref_losses.npz, tests/test_ref_pinned.py).
 Reference quirks are kept on purpose.
@@ -17,6 +19,8 @@ csn_distill_loss call (float64 arithmetic, two launches) w
 device tensor; anything else (CPU tensors, float64) takes the torch form.  Opt-in: the default keeps the torch form.
 ``fused=True`` on BarlowTwinsLoss: batch norm, correlation, loss and both gradients from csn_barlow_corr + csn_barlow_grad
 (float64 arithmetic, five launches) under the same rule, in training mode.
+``fused=True`` on ContrastiveLoss: value and gradient from csn_contrastive_lse + csn_contrastive_grad (float64 arithmetic,
+seven launches) under the same rule.
 """
 import numpy as np
 import torch
@@ -269,6 +273,167 @@ class BarlowTwinsLoss(nn.Module):
             c = _AllReduceSum.apply(c)
         on_diag, off_diag = _BarlowReduce.apply(c.float()) if c.is_cuda else _barlow_reduce_torch(c)
         return on_diag + self.lambd * off_diag
+
+
+def _gather_rows(x, world):
+    """Every rank's ``x`` (equal shapes) concatenated along dimension 0 in rank order."""
+    parts = [torch.empty_like(x) for _ in range(world)]
+    torch.distributed.all_gather(parts, x.contiguous())
+    return torch.cat(parts, dim=0)
+
+
+def _contrastive_left_out(groups_all, row0, B):
+    """[B,N] bool: key j is left out of local query i (the same group id, another row); None without group ids."""
+    if groups_all is None:
+        return None
+    N = groups_all.shape[0]
+    rows = torch.arange(row0, row0 + B, device=groups_all.device)
+    same = groups_all[row0:row0 + B, None] == groups_all[None, :]
+    return same & (rows[:, None] != torch.arange(N, device=groups_all.device)[None, :])
+
+
+def _contrastive_lse_torch(s_all, t_all, groups_all, row0, B, scale, w_a, w_b):
+    """Call 1 in torch ops, in the dtype of the inputs -> (rows [3,B] = lA, lB, p, loss_part: the local rows' part of L)."""
+    sh, th = F.normalize(s_all, dim=1, eps=1e-12), F.normalize(t_all, dim=1, eps=1e-12)
+    N = sh.shape[0]
+    za, zb = scale * (sh[row0:row0 + B] @ th.T), scale * (th[row0:row0 + B] @ sh.T)
+    p = scale * (sh[row0:row0 + B] * th[row0:row0 + B]).sum(1)
+    out = _contrastive_left_out(groups_all, row0, B)
+    if out is not None:
+        za, zb = za.masked_fill(out, float("-inf")), zb.masked_fill(out, float("-inf"))
+    lA, lB = torch.logsumexp(za, dim=1), torch.logsumexp(zb, dim=1)
+    return torch.stack([lA, lB, p]), (w_a * (lA - p) + w_b * (lB - p)).sum() / N
+
+
+def _contrastive_grad_torch(s_all, t_all, groups_all, row0, B, scale, lse_a, lse_b_all, w_a, w_b, grad_scale, want_dscale):
+    """Call 2 in torch ops -> (ds [B,D] holding grad_scale, dscale_part | None)."""
+    sh, th = F.normalize(s_all, dim=1, eps=1e-12), F.normalize(t_all, dim=1, eps=1e-12)
+    N = sh.shape[0]
+    shl, thl = sh[row0:row0 + B], th[row0:row0 + B]
+    out = _contrastive_left_out(groups_all, row0, B)
+    keep = (lambda x: x) if out is None else (lambda x: x.masked_fill(out, 0.0))
+    da = shl @ th.T
+    PA, PBt = keep(torch.exp(scale * da - lse_a[:, None])), keep(torch.exp(scale * da - lse_b_all[None, :]))
+    g = (scale / N) * ((w_a * PA + w_b * PBt) @ th - (w_a + w_b) * thl)
+    nrm = s_all[row0:row0 + B].norm(dim=1, keepdim=True)
+    ds = grad_scale * (g - shl * (shl * g).sum(1, keepdim=True) * (nrm > 1e-12)) / nrm.clamp_min(1e-12)
+    if not want_dscale:
+        return ds, None
+    db = thl @ sh.T
+    PBq = keep(torch.exp(scale * db - lse_b_all[row0:row0 + B, None]))
+    dii = (shl * thl).sum(1)
+    return ds, (w_a * ((PA * da).sum(1) - dii) + w_b * ((PBq * db).sum(1) - dii)).sum() / N
+
+
+class _ContrastiveFn(torch.autograd.Function):
+    """The two calls (csn_contrastive_lse / _grad, or the same in torch ops) with the all-gather of lB and the all-reduce of the
+    float64 loss partial between them: like _BarlowFusedFn the gradient is computed in the forward, saved, and multiplied by
+    the incoming scalar.  ``log_scale`` is the learnable parameter or None; ``scale`` is the logit scale in effect and
+    ``scale_grad`` whether the clamp lets a gradient through to ``log_scale``."""
+
+    @staticmethod
+    def forward(ctx, student, teacher, groups, log_scale, scale, scale_grad, w_a, w_b, fused):
+        dist, world = torch.distributed, _dist_world()
+        s, t = student.detach().contiguous(), teacher.detach().contiguous()
+        B, row0 = s.shape[0], 0
+        if groups is not None:
+            groups = groups.to(device=s.device, dtype=torch.int32).contiguous()
+        if world > 1:
+            sizes = [torch.zeros(1, dtype=torch.int64, device=s.device) for _ in range(world)]
+            dist.all_gather(sizes, torch.tensor([B], dtype=torch.int64, device=s.device))
+            sizes = [int(v) for v in sizes]
+            if any(v != B for v in sizes):
+                raise ValueError(f"ContrastiveLoss needs the same number of rows on every rank, got {sizes}")
+            row0 = dist.get_rank() * B
+            s, t = _gather_rows(s, world), _gather_rows(t, world)
+            groups = None if groups is None else _gather_rows(groups, world)
+        want_dscale = log_scale is not None and ctx.needs_input_grad[3]
+        if fused:
+            rows, loss = cabi.contrastive_lse(s, t, scale, groups, row0, B, w_a, w_b)
+        else:
+            rows, loss = _contrastive_lse_torch(s, t, groups, row0, B, scale, w_a, w_b)
+        loss = loss.double().reshape(1)
+        if world > 1:
+            dist.all_reduce(loss)
+        ctx.want_dscale = want_dscale
+        if not (ctx.needs_input_grad[0] or want_dscale):        # evaluation: the value alone, no second call
+            return loss[0].to(student.dtype)
+        lse_b_all = _gather_rows(rows[1], world) if world > 1 else rows[1]
+        if fused:
+            ds, dscale = cabi.contrastive_grad(s, t, scale, rows[0], lse_b_all, groups, row0, B, w_a, w_b, grad_scale=world,
+                                               want_dscale=want_dscale)
+        else:
+            ds, dscale = _contrastive_grad_torch(s, t, groups, row0, B, scale, rows[0], lse_b_all, w_a, w_b, float(world),
+                                                 want_dscale)
+        saved = [ds]
+        if want_dscale:
+            dscale = dscale.double().reshape(1)
+            if world > 1:
+                dist.all_reduce(dscale)
+            # d L / d log_scale = scale dL/dscale where the clamp at log(max_scale) is not in effect
+            saved.append((dscale[0] * (scale if scale_grad else 0.0)).to(log_scale.dtype).reshape(log_scale.shape))
+        ctx.save_for_backward(*saved)
+        return loss[0].to(student.dtype)
+
+    @staticmethod
+    def backward(ctx, g):
+        saved = ctx.saved_tensors
+        ds = saved[0] * g if ctx.needs_input_grad[0] else None
+        dlog = saved[1] * g.to(saved[1].dtype) if ctx.want_dscale else None
+        return ds, None, None, dlog, None, None, None, None, None
+
+
+class ContrastiveLoss(nn.Module):
+    """The symmetric in-batch contrastive loss (InfoNCE, the CLIP loss) of student rows against FROZEN teacher rows, both
+    L2-normalised, at logit scale 1 / temperature:
+        L = (1/N) sum_i [ w_s2t (lse_j(a s^_i . t^_j) - a s^_i . t^_i) + w_t2s (lse_j(a t^_i . s^_j) - a s^_i . t^_i) ].
+    ``forward(student[B,D], teacher[B,D], groups=None)`` returns a scalar; the teacher gets no gradient.  ``groups`` ([B]
+    integers, e.g. the image index): key j is left out of query i's softmax when groups[i] == groups[j] and j != i, so a
+    duplicate of the positive in the batch is not pushed away as a false negative.
+
+    With torch.distributed initialised the negatives are the GLOBAL batch: the module all-gathers ``student.detach()``,
+    ``teacher`` and ``groups`` (every rank must bring the same B), computes the log-sum-exps of its own rows, all-gathers
+    lB (N float64 values), all-reduces the float64 loss partial and returns the global loss on every rank.  The gradient
+    it hands to autograd is ``world`` times this rank's rows of the gradient of the global loss (grad_scale = world): the
+    MEAN all-reduce of the parameter gradients that FlatGrads / DDP perform then gives exactly the gradient of the global
+    loss -- the other ranks' rows of it come from those ranks.
+
+    ``learnable_temperature=True`` keeps ``log_scale`` = log(1 / temperature) as an nn.Parameter; the scale in effect is
+    exp(min(log_scale, log(max_scale))) and its gradient is scale * dL/dscale from float64 partials all-reduced over the
+    ranks (already global: the parameter is not averaged again).  Reading the scale synchronises with the device.
+
+    Default, and always for CPU or non-float32 tensors: the two-phase algorithm in torch ops in the dtype of the inputs.
+    ``fused=True`` on float32 device tensors: value and gradient in float64 from csn_contrastive_lse + csn_contrastive_grad
+    (seven launches), each float32 output rounded once."""
+
+    def __init__(self, temperature=0.07, learnable_temperature=False, max_scale=100.0, w_s2t=0.5, w_t2s=0.5, fused=False):
+        super().__init__()
+        if not (temperature > 0 and np.isfinite(temperature)) or not (max_scale > 0 and np.isfinite(max_scale)):
+            raise ValueError(f"ContrastiveLoss: temperature {temperature} and max_scale {max_scale} must be finite and positive")
+        self.max_scale, self.w_s2t, self.w_t2s = float(max_scale), float(w_s2t), float(w_t2s)
+        self.fused = bool(fused)
+        log_scale = torch.tensor(float(np.log(1.0 / temperature)))
+        if learnable_temperature:
+            self.log_scale = nn.Parameter(log_scale)
+        else:
+            self.log_scale = None
+            self._scale = min(1.0 / float(temperature), self.max_scale)
+
+    def scale(self):
+        """(the logit scale in effect, whether log_scale is below the clamp)."""
+        if self.log_scale is None:
+            return self._scale, False
+        v, top = float(self.log_scale.detach()), float(np.log(self.max_scale))
+        return (float(np.exp(v)), True) if v <= top else (self.max_scale, False)
+
+    def forward(self, student, teacher, groups=None):
+        if student.dim() != 2 or student.shape != teacher.shape:
+            raise ValueError(f"ContrastiveLoss: student {tuple(student.shape)} and teacher {tuple(teacher.shape)} must be equal [B,D]")
+        if groups is not None and tuple(groups.shape) != (student.shape[0],):
+            raise ValueError(f"ContrastiveLoss: groups {tuple(groups.shape)} must be [{student.shape[0]}]")
+        scale, below = self.scale()
+        fused = self.fused and _fusable(student, teacher) and (groups is None or groups.is_cuda)
+        return _ContrastiveFn.apply(student, teacher, groups, self.log_scale, scale, below, self.w_s2t, self.w_t2s, fused)
 
 
 class LARS(torch.optim.Optimizer):

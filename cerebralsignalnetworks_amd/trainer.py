@@ -19,7 +19,7 @@ import torch.distributed as dist
 import torch.nn as nn
 
 from . import filters
-from .losses import (CosineSimilarityLoss, FeatureDistributionLoss, HyperParams, loss_fn_kd, BarlowTwinsLoss,
+from .losses import (CosineSimilarityLoss, FeatureDistributionLoss, HyperParams, loss_fn_kd, BarlowTwinsLoss, ContrastiveLoss,
                      LARS)
 
 
@@ -227,23 +227,32 @@ def check_device_status(model, collective=True):
 
 class DistillTrainer:
     def __init__(self, model, sos, ddof=0, loss="cosine", lr=1e-3, optimizer="rmsprop", nepochs=100,
-                 kd_params=None, preprocess=True, accum_steps=1, fused_optimizer=False, fused_loss=False):
+                 kd_params=None, preprocess=True, accum_steps=1, fused_optimizer=False, fused_loss=False,
+                 contrastive_temperature=0.07):
         """``fused_optimizer=True`` (on a GPU): adamw / adam / lars step the flat buffers in one to three HIP launches
         (flat_optim.FlatAdamW / FlatLARS) instead of the torch optimisers; rmsprop is fused either way.
 
         ``fused_loss=True``: the featdist and kd losses compute value and gradient in one csn_distill_loss call (float64
         arithmetic, two launches) instead of a chain of torch ops, and barlow in csn_barlow_corr + csn_barlow_grad (float64,
-        five launches; BarlowTwinsLoss(fused=True)); cosine is fused either way.
+        five launches; BarlowTwinsLoss(fused=True)); cosine is fused either way.  ``loss="contrastive"``: ContrastiveLoss at
+        the FIXED ``contrastive_temperature`` (the loss module's parameters are not in the model's flat buffer, so a learnable
+        temperature would never be stepped), over the global batch of all ranks; ``fused_loss=True`` selects
+        csn_contrastive_lse + csn_contrastive_grad (float64, seven launches).  train_step's ``groups`` are its group ids.
 
         ``accum_steps = k > 1``: train_step splits its batch into k equal micro-batches and sums their gradients (each
         loss scaled by 1 / k) in the flat buffer before the one all-reduce and optimiser step -- the step of the whole
         batch in 1 / k of the workspace.  That equals the full batch only for a loss that is a mean over rows (cosine,
-        featdist, kd); barlow normalises with batch statistics and is refused."""
+        featdist, kd); barlow normalises with batch statistics and contrastive takes its negatives from the batch: both
+        are refused."""
         if not isinstance(accum_steps, int) or isinstance(accum_steps, bool) or accum_steps < 1:
             raise ValueError(f"accum_steps must be an integer >= 1, got {accum_steps!r}")
         if accum_steps > 1 and loss == "barlow":
             raise ValueError("accum_steps > 1 needs a loss that is a mean over the batch rows (cosine, featdist, kd): barlow "
                              "normalises with the statistics of the batch, so micro-batches do not sum to the full batch")
+        if accum_steps > 1 and loss == "contrastive":
+            raise ValueError("accum_steps > 1 needs a loss that is a mean over the batch rows (cosine, featdist, kd): "
+                             "contrastive is a batch-level loss whose negatives are the other rows of the batch, so "
+                             "micro-batches do not sum to the full batch")
         self.accum_steps = accum_steps
         self.model = model
         self.sos, self.ddof, self.preprocess = sos, ddof, preprocess
@@ -278,6 +287,7 @@ class DistillTrainer:
         self.fused_loss = bool(fused_loss)
         self.kd_params = kd_params
         self.barlow = None
+        self.contrastive = ContrastiveLoss(temperature=contrastive_temperature, fused=fused_loss) if loss == "contrastive" else None
         rank, world = dist_info()
         if world > 1:   # identical initial weights on every rank
             for p in model.parameters():
@@ -337,7 +347,7 @@ class DistillTrainer:
             return filters.eeg_bandpass_znorm(eeg_bct, self.sos, ddof=self.ddof, time_major=True).transpose(0, 1)
         return eeg_bct.transpose(1, 2).contiguous()
 
-    def compute_loss(self, out, targets, labels, epoch):
+    def compute_loss(self, out, targets, labels, epoch, groups=None):
         if self.loss_name == "cosine":
             feat = out[0] if isinstance(out, tuple) else out
             return self.cosine(feat, targets)
@@ -355,10 +365,14 @@ class DistillTrainer:
                 _, world = dist_info()
                 self.barlow = BarlowTwinsLoss(feat.shape[1], feat.shape[0] * world, fused=self.fused_loss).to(feat.device)
             return self.barlow(feat, targets)
+        if self.loss_name == "contrastive":
+            feat = out[0] if isinstance(out, tuple) else out
+            return self.contrastive(feat, targets, groups)
         raise ValueError(self.loss_name)
 
-    def train_step(self, eeg_bct, targets, labels=None, epoch=0):
-        """One optimisation step on this rank's shard of the global batch; returns the (device) loss.  With
+    def train_step(self, eeg_bct, targets, labels=None, epoch=0, groups=None):
+        """One optimisation step on this rank's shard of the global batch; returns the (device) loss.  ``groups`` ([B]
+        integers): the group ids of loss="contrastive" (rows of one group are not each other's negatives).  With
         ``accum_steps = k > 1`` the shard runs as k equal micro-batches whose gradients are summed in the flat buffer (the
         returned loss is the sum of their losses / k); all-reduce and optimiser step follow the last one."""
         k = self.accum_steps
@@ -372,7 +386,8 @@ class DistillTrainer:
                 self._others_left = self._n_others
             x = self.embed(eeg_bct)
             out = self.model(x)
-            loss = self.compute_loss(out, targets, labels, epoch)
+            loss = self.compute_loss(out, targets, labels, epoch) if groups is None else \
+                self.compute_loss(out, targets, labels, epoch, groups=groups)
             loss.backward()
         else:
             loss = self._micro_batches(eeg_bct, targets, labels, epoch, k)

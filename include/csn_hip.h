@@ -96,7 +96,7 @@ enum csnDtype { CSN_F32 = 0, CSN_BF16 = 1 };
 /* ABI version of this header; bumped on any signature change.  A symbol added beside the existing ones
  * (csn_lstm_plan_set_grad_mode, csn_lstm_plan_set_lengths, csn_lstm_plan_set_views, csn_lstm_plan_set_io, csn_lstm_plan_half_tile_launches, the
  * csn_flat_* family, csn_adam_step, csn_lars_step, csn_eeg_bandpass_stream and its _path, csn_distill_loss,
- * csn_dino_loss, csn_barlow_corr, csn_barlow_grad, csn_topk_merge and its _staged_max, csn_topk_class_metrics) breaks no caller and does not bump it; neither does a new bit of csn_lstm_plan_create's `training` word. */
+ * csn_dino_loss, csn_barlow_corr, csn_barlow_grad, csn_contrastive_lse, csn_contrastive_grad, csn_topk_merge and its _staged_max, csn_topk_class_metrics) breaks no caller and does not bump it; neither does a new bit of csn_lstm_plan_create's `training` word. */
 #define CSN_ABI_VERSION 6
 int csn_abi_version(void);
 /* Thread-local message for the last non-zero status returned on this thread. */
@@ -658,6 +658,50 @@ int csn_barlow_corr(const float* z1, const float* z2, int B, int D, double eps, 
 int csn_barlow_grad(const float* z1, const float* z2, int B, int D, const double* c, const double* c_local,
                     const void* saved, double inv_batch, double lambd, float grad_scale, float* loss, float* dz1,
                     float* dz2, void* scratch, csnStream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * K7c  the symmetric in-batch contrastive (InfoNCE / CLIP) loss of a student against a frozen teacher, exact over the
+ * GLOBAL batch of all ranks.  s_all / t_all [N,D] float32: every rank's rows in rank order (the
+ * all-gathered batch); this rank owns rows row0 .. row0+B-1.  group_all [N] int32 or NULL: key j is left out of query i's
+ * softmax when group[i] == group[j] and j != i (duplicates of the positive); NULL leaves nothing out.  a = logit_scale.
+ *     s^_i = s_i / max(|s_i|, 1e-12),  t^ likewise                         (F.normalize)
+ *     lA_i = log sum_{j allowed} exp(a s^_i . t^_j)      lB_i = log sum_{j allowed} exp(a t^_i . s^_j)      p_i = a s^_i . t^_i
+ *     L    = (1/N) sum_i [ w_a (lA_i - p_i) + w_b (lB_i - p_i) ]
+ *     dL/ds^_i = (a/N) [ w_a (sum_j PA_ij t^_j - t^_i) + w_b (sum_k PB_ki t^_k - t^_i) ]
+ *         PA_ij = exp(a s^_i . t^_j - lA_i),   PB_ki = exp(a t^_k . s^_i - lB_k),   both 0 where the key is left out
+ *     ds_i = grad_scale (dL/ds^_i - s^_i (s^_i . dL/ds^_i)) / max(|s_i|, 1e-12)      the projection only where |s_i| > 1e-12
+ *     dL/da, the local rows' part = (1/N) sum_{i local} [ w_a (sum_j PA_ij s^_i . t^_j - s^_i . t^_i)
+ *                                                        + w_b (sum_j PB_ij t^_i . s^_j - s^_i . t^_i) ]
+ * Two calls, because PB_ki needs lB_k of rows other ranks own and nothing else from them: between the calls the host
+ * all-gathers lB (N float64) and all-reduces the loss partial.  On one rank lse_a_local and lse_b_all are rows 0 and 1 of
+ * rows_out on the device.  The teacher gets no gradient.
+ *   csn_contrastive_lse   rows_out float64 [3][B]: lA, lB, p of the local rows; loss_part float64 [1]: the local rows' part of
+ *                         L, added in an order that depends on B only.  3 launches.
+ *   csn_contrastive_grad  ds float32 [B,D], holding grad_scale; dscale_part float64 [1] or NULL: the local rows' part of
+ *                         dL/da, not scaled by grad_scale.  4 launches, 5 with dscale_part.
+ * Float64 arithmetic on the float32 inputs, every float32 output rounded once; every log-sum-exp subtracts its maximum.  A
+ * row's lA, lB, p and ds depend on (N, D) and the data alone, not on B or row0; partial sums over key tiles (64 keys) and the
+ * splits of the ds contraction (256 keys) are merged in ascending order; two calls give the same bits.  NaN / Inf propagate
+ * as in the torch expression (a key that is left out propagates nothing).  Any int32 is a group id; a query whose every
+ * other key is left out has loss term 0 and a zero gradient.
+ * scratch: caller-owned, 8-byte aligned, csn_contrastive_scratch_bytes(B, N, D) =
+ *     8 * (3 N + 4 ceil(N/64) B + B + B N + ceil(N/256) B D)  bytes
+ *   (norms | per-tile (max, sum exp) pairs or row sums | the diagonal | the B x N weight block | the ds splits); the same
+ *   buffer serves both calls, neither reads what the other wrote.  0 for arguments the calls refuse.  No library state;
+ *   everything is enqueued on `stream`.
+ * Refused on the host before any launch: a null pointer other than group_all / dscale_part; N, D or B <= 0, row0 < 0,
+ * row0 + B > N; logit_scale not finite or <= 0; w_a or w_b not finite; rows_out, loss_part, lse_a_local, lse_b_all,
+ * dscale_part or scratch not 8-byte aligned.
+ * Replaces: nothing in the reference (its scripts have no contrastive objective); the torch expression is
+ * F.normalize x 2, one matmul, two cross_entropy and autograd.
+ * ---------------------------------------------------------------------------------- */
+size_t csn_contrastive_scratch_bytes(int B, int N, int D);
+int csn_contrastive_lse(const float* s_all, const float* t_all, const int* group_all, int N, int D, int row0, int B,
+                        double logit_scale, double w_a, double w_b, double* rows_out, double* loss_part, void* scratch,
+                        csnStream_t stream);
+int csn_contrastive_grad(const float* s_all, const float* t_all, const int* group_all, int N, int D, int row0, int B,
+                         double logit_scale, const double* lse_a_local, const double* lse_b_all, double w_a, double w_b,
+                         double grad_scale, float* ds, double* dscale_part, void* scratch, csnStream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * K8  exact squared-L2 top-k.  Replaces: faiss.IndexFlatL2(d).add / .search(k),

@@ -143,6 +143,28 @@ for i in range(n_cases):
         return max(e0, e1, e2), 2e-7
     case(f"barlow_loss B{Bb} D{Db}", bl)
 
+    Nc, Dc = int(rng.integers(2, 300)), int(rng.integers(2, 500))
+    Bc = int(rng.integers(1, Nc + 1))
+    r0 = int(rng.integers(0, Nc - Bc + 1))
+
+    def cl(Nc=Nc, Dc=Dc, Bc=Bc, r0=r0):
+        # csn_contrastive_lse + csn_contrastive_grad on rows r0 .. r0+Bc-1 against float64 autograd of the one-process formula
+        s, tt = (rng.standard_normal((Nc, Dc)).astype(np.float32) for _ in range(2))
+        grp = rng.integers(0, Nc, size=Nc).astype(np.int32)
+        a = torch.tensor(s, dtype=torch.float64, requires_grad=True)
+        z = (torch.nn.functional.normalize(a, dim=1) @ torch.nn.functional.normalize(torch.tensor(tt, dtype=torch.float64), dim=1).T) / 0.07
+        g64 = torch.from_numpy(grp)
+        z = z.masked_fill((g64[:, None] == g64[None, :]) & ~torch.eye(Nc, dtype=torch.bool), float("-inf"))
+        ref = (0.5 * (torch.logsumexp(z, 1) + torch.logsumexp(z, 0)) - torch.diagonal(z)).sum() / Nc
+        ref.backward()
+        whole, loss = cabi.contrastive_lse(t(s), t(tt), 1 / 0.07, t(grp))
+        rows, _ = cabi.contrastive_lse(t(s), t(tt), 1 / 0.07, t(grp), r0, Bc)
+        ds, _ = cabi.contrastive_grad(t(s), t(tt), 1 / 0.07, rows[0], whole[1], t(grp), r0, Bc)
+        e0 = abs(float(loss) - float(ref)) / max(1.0, abs(float(ref)))
+        e1 = float((ds.double().cpu() - a.grad[r0:r0 + Bc]).abs().max() / a.grad.abs().max())
+        return max(e0, e1), 2e-7
+    case(f"contrastive_loss N{Nc} D{Dc} B{Bc} row0 {r0}", cl)
+
 # ---- retrieval ---------------------------------------------------------------------------------
 for i in range(n_cases):
     Ng, Nq, D = int(rng.integers(1, 3000)), int(rng.integers(1, 300)), int(rng.integers(1, 500))
