@@ -29,6 +29,9 @@
 // Each path is one function over the per-call context (struct Call) and the caller's pointers (FwdArgs / BwdArgs); what
 // more than one of them does -- slot 0, weight gradients, chunk GEMMs, dx out, the profile epilogue -- is one helper each.
 // The layer wavefronts of paths 0, 1 and 5 are ONE schedule (wavefront_schedule, lstm_schedule.h: unit, lag, direction).
+// The API boundary -- the caller's batch-first float32 tensors into the time-major workspace and back, whatever the plan's
+// lengths, direction, pitches or output dropout -- is a file of its own (lstm_boundary.hip: one kernel per layout pass); this
+// file launches none of it, and csn_lstm_forward / csn_lstm_backward are one flow each around run_forward / run_backward.
 //
 // Layout in HBM (inside the caller's workspace; [T,B,*] time-major so one timestep is one slab):
 //   per layer: compute-dtype weight copies (+ transposes / fragment-major forms), bias,
@@ -42,6 +45,7 @@
 
 #include "csn_common.h"
 #include "lstm_cell_blk.h"
+#include "lstm_boundary.h"
 #include "lstm_cell_common.h"
 #include "lstm_dropout.h"
 #include "lstm_f32_persist.h"
@@ -211,162 +215,6 @@ static int check_desc(const char* fn, const csnLstmDesc* d) {
   return CSN_OK;
 }
 
-// y_all[b][t][h] (f32, batch-first) <- h_all[t+1][b][h] (dtype, time-major)
-template <typename T>
-__global__ void gather_y_all_kernel(const T* __restrict__ h_all, float* __restrict__ y, int B, int Tn, int H) {
-  const int64_t total = (int64_t)B * Tn * H;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    const int64_t h = i % H, r = i / H, t = r % Tn, b = r / Tn;
-    y[i] = to_f32(h_all[((t + 1) * B + b) * (int64_t)H + h]);
-  }
-}
-
-// dst[t][b][h] = src[b][t][h]  (f32)
-__global__ void bt_to_tb_kernel(const float* __restrict__ src, float* __restrict__ dst, int B, int Tn, int H) {
-  const int64_t total = (int64_t)B * Tn * H;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    const int64_t h = i % H, r = i / H, b = r % B, t = r / B;
-    dst[i] = src[(b * Tn + t) * (int64_t)H + h];
-  }
-}
-
-// dst[b][t][i] = src[t][b][i]  (f32)
-__global__ void tb_to_bt_kernel(const float* __restrict__ src, float* __restrict__ dst, int B, int Tn, int H) {
-  const int64_t total = (int64_t)B * Tn * H;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    const int64_t h = i % H, r = i / H, t = r % Tn, b = r / Tn;
-    dst[i] = src[(t * B + b) * (int64_t)H + h];
-  }
-}
-
-__global__ void add_rows_kernel(const float* __restrict__ src, float* __restrict__ dst, int64_t n) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) dst[i] += src[i];
-}
-
-// ---- variable-length batches (csn_lstm_plan_set_lengths): len[b] in [0, T] valid steps of row b ----
-// buf[t][b][:] = 0 where t >= len[b]  (time-major input copy: padding is never multiplied)
-template <typename T>
-__global__ void mask_tm_kernel(T* __restrict__ buf, const int* __restrict__ len, int B, int Tn, int W) {
-  const int64_t total = (int64_t)B * Tn * W;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    const int64_t r = i / W, b = r % B, t = r / B;
-    if (t >= len[b]) buf[i] = from_f32<T>(0.f);
-  }
-}
-// the same on the fragment-major slabs [Tn][Bpad * I] of the fused input projection, one 16-byte piece per thread and trip
-__global__ void mask_x_blk_kernel(bf16_t* __restrict__ x_blk, const int* __restrict__ len, int B, int64_t Bpad, int Tn, int I) {
-  const int64_t per_t = Bpad * I / 8, kblocks = I >> 5;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t ci = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; ci < per_t * Tn; ci += stride) {
-    const int64_t t = ci / per_t, c = ci % per_t, blk = c >> 6, lane = c & 63;
-    const int64_t r = (blk / kblocks) * 16 + (lane & 15);
-    if (r < B && t >= len[r]) *reinterpret_cast<uint4*>(x_blk + ci * 8) = make_uint4(0u, 0u, 0u, 0u);
-  }
-}
-// out[b][h] (f32) = all[len[b]][b][h]: slot n of h_all / c_all is the state after step n-1, slot 0 the initial state
-template <typename T>
-__global__ void gather_state_kernel(const T* __restrict__ all, const int* __restrict__ len, float* __restrict__ out, int B, int H) {
-  const int64_t total = (int64_t)B * H;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    const int64_t b = i / H;
-    out[i] = to_f32(all[(int64_t)len[b] * B * H + i]);
-  }
-}
-// gather_y_all_kernel with zeros at t >= len[b] (steps at or beyond the longest row were never run: not read)
-template <typename T>
-__global__ void gather_y_all_len_kernel(const T* __restrict__ h_all, float* __restrict__ y, const int* __restrict__ len, int B, int Tn, int H) {
-  const int64_t total = (int64_t)B * Tn * H;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    const int64_t h = i % H, r = i / H, t = r % Tn, b = r / Tn;
-    y[i] = t < len[b] ? to_f32(h_all[((t + 1) * B + b) * (int64_t)H + h]) : 0.f;
-  }
-}
-// dst[t][b][h], t < Te  =  t < len[b] && src ? src[b][t][h] : 0   (src batch-first with Tn steps per row, or null)
-__global__ void bt_to_tb_len_kernel(const float* __restrict__ src, float* __restrict__ dst, const int* __restrict__ len, int B, int Tn, int Te, int H) {
-  const int64_t total = (int64_t)B * Te * H;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    const int64_t h = i % H, r = i / H, b = r % B, t = r / B;
-    dst[i] = (src != nullptr && t < len[b]) ? src[(b * Tn + t) * (int64_t)H + h] : 0.f;
-  }
-}
-// dst[len[b]-1][b][:] += src[b][:] for the rows whose last step lies in [t_lo, t_hi]: a gradient that enters at the row's end
-__global__ void add_at_end_kernel(const float* __restrict__ src, float* __restrict__ dst_tm, const int* __restrict__ len, int t_lo, int t_hi, int B, int H) {
-  const int64_t total = (int64_t)B * H;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    const int t = len[i / H] - 1;
-    if (t >= t_lo && t <= t_hi) dst_tm[(int64_t)t * B * H + i] += src[i];
-  }
-}
-// dst[b][:] += src[b][:] for the rows of length 0 (their dh0 is dh_n)
-__global__ void add_rows_len0_kernel(const float* __restrict__ src, float* __restrict__ dst, const int* __restrict__ len, int B, int H) {
-  const int64_t total = (int64_t)B * H;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride)
-    if (len[i / H] == 0) dst[i] += src[i];
-}
-// dst[b][t][i] (Tn steps per row) = t < Te ? src[t][b][i] : 0
-__global__ void tb_to_bt_len_kernel(const float* __restrict__ src, float* __restrict__ dst, int B, int Tn, int Te, int H) {
-  const int64_t total = (int64_t)B * Tn * H;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    const int64_t h = i % H, r = i / H, t = r % Tn, b = r / Tn;
-    dst[i] = t < Te ? src[(t * B + b) * (int64_t)H + h] : 0.f;
-  }
-}
-
-// ---- CSN_LSTM_REVERSE plans and csn_lstm_plan_set_io: the three batch-first <-> time-major passes
-// with a row walked backwards, a pitch on the caller's side, and an adding store.  n = len[b] (Tn without lengths) valid
-// steps of row b; step s of the recurrence is the caller's t = rev ? n - 1 - s : s, so slot n - t of h_all holds the output
-// at t of a reverse plan.  Calls with none of the three run the kernels above, unchanged.
-// y[(b Tn + t) pitch + h] = t < n ? h_all[slot][b][h] : 0
-template <typename T>
-__global__ void gather_y_all_io_kernel(const T* __restrict__ h_all, float* __restrict__ y, const int* __restrict__ len, int B, int Tn,
-                                       int H, int64_t pitch, int rev) {
-  const int64_t total = (int64_t)B * Tn * H;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    const int64_t h = i % H, r = i / H, t = r % Tn, b = r / Tn;
-    const int64_t n = len != nullptr ? len[b] : Tn;
-    y[r * pitch + h] = t < n ? to_f32(h_all[((rev ? n - t : t + 1) * B + b) * (int64_t)H + h]) : 0.f;
-  }
-}
-// dst[s][b][h], s < Te  =  s < n && src ? src[(b Tn + t) pitch + h] : 0
-__global__ void bt_to_tb_io_kernel(const float* __restrict__ src, float* __restrict__ dst, const int* __restrict__ len, int B, int Tn,
-                                   int Te, int H, int64_t pitch, int rev) {
-  const int64_t total = (int64_t)B * Te * H;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    const int64_t h = i % H, r = i / H, b = r % B, s = r / B;
-    const int64_t n = len != nullptr ? len[b] : Tn;
-    dst[i] = (src != nullptr && s < n) ? src[(b * Tn + (rev ? n - 1 - s : s)) * pitch + h] : 0.f;
-  }
-}
-// dst[b][t][i] (Tn steps per row) = or += src[s][b][i] for t < n; the padding is zeroed, or with add left as it is
-__global__ void tb_to_bt_io_kernel(const float* __restrict__ src, float* __restrict__ dst, const int* __restrict__ len, int B, int Tn,
-                                   int H, int rev, int add) {
-  const int64_t total = (int64_t)B * Tn * H;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    const int64_t h = i % H, r = i / H, t = r % Tn, b = r / Tn;
-    const int64_t n = len != nullptr ? len[b] : Tn;
-    if (t < n) {
-      const float v = src[((rev ? n - 1 - t : t) * B + b) * (int64_t)H + h];
-      dst[i] = add ? dst[i] + v : v;
-    } else if (!add) {
-      dst[i] = 0.f;
-    }
-  }
-}
-
 // Gradient w.r.t. the initial hidden state of one layer (CSN_LSTM_STATE plans):
 //   out[b][j] = sum_k dg[b][k] Wt(j, k),  k in [0, 4H), dg = dgates at t = 0 [B, 4H] row-major,
 //   Wt = W_hh^T [H, 4H]: row-major (BLK = false, generic path) or fragment-major (BLK = true, per-diagonal path, 4H axis
@@ -423,11 +271,6 @@ __global__ void sum_rows_kernel(const float* __restrict__ part, int P, int64_t n
   for (int p = 0; p < P; ++p) s += part[(int64_t)p * n + i];
   out[i] = accumulate ? out[i] + s : s;
   out2[i] = accumulate ? out2[i] + s : s;
-}
-
-static inline unsigned grid_for(int64_t n) {
-  int64_t g = (n + 255) / 256;
-  return (unsigned)(g < 1 ? 1 : (g > 2048 ? 2048 : g));
 }
 
 // ---- second stream + event pool: owned by the PLAN (created on first use, destroyed with it) -------
@@ -847,28 +690,18 @@ struct BwdArgs {
   float* dx;
 };
 
-// input gradient out of its time-major workspace form; with lengths the caller's rows have T_full steps, zeros behind the longest
+// this call's rows for a layout pass of lstm_boundary.hip over a caller's tensor `width` wide, `pitch` elements from row to row (0: dense)
+static RowMap row_map(const Call& C, int64_t width, int64_t pitch) {
+  return RowMap{C.dlen, C.B, C.T_full, C.T, (int)width, pitch ? pitch : width, C.P.reverse, C.P.dx_add};
+}
+// input gradient out of its time-major workspace form (the caller's rows have T_full steps)
 static int emit_dx(const Call& C, const float* dx_tm, float* dx, int64_t I, hipStream_t st) {
-  const int B = C.B, T = C.T;
-  if (C.P.reverse || C.P.dx_add)
-    tb_to_bt_io_kernel<<<csn::grid_for((int64_t)C.T_full * B * I), 256, 0, st>>>(dx_tm, dx, C.dlen, B, C.T_full, (int)I, C.P.reverse, C.P.dx_add);
-  else if (C.dlen != nullptr) tb_to_bt_len_kernel<<<csn::grid_for((int64_t)C.T_full * B * I), 256, 0, st>>>(dx_tm, dx, B, C.T_full, T, (int)I);
-  else csn::tb_to_bt_kernel<<<csn::grid_for((int64_t)T * B * I), 256, 0, st>>>(dx_tm, dx, B, T, (int)I);
-  CSN_LAUNCH_CHECK();
-  return CSN_OK;
+  return launch_dx_out(dx_tm, dx, row_map(C, I, 0), st);
 }
 // gradient w.r.t. h_n of the layer below, into this layer's time-major input gradient `dx_tm` whose steps [t_lo, t_hi] were
-// just written: at T-1 without lengths, at each row's own last step with them
+// just written: at each row's own last step
 static int add_dh_n_rows(const Call& C, const float* dh_below, float* dx_tm, int t_lo, int t_hi, hipStream_t st) {
-  const int B = C.B, H = C.H, T = C.T;
-  if (C.dlen != nullptr) {
-    add_at_end_kernel<<<csn::grid_for((int64_t)B * H), 256, 0, st>>>(dh_below, dx_tm, C.dlen, t_lo, t_hi, B, H);
-  } else {
-    if (t_hi != T - 1) return CSN_OK;
-    csn::add_rows_kernel<<<csn::grid_for((int64_t)B * H), 256, 0, st>>>(dh_below, dx_tm + (size_t)(T - 1) * B * H, (int64_t)B * H);
-  }
-  CSN_LAUNCH_CHECK();
-  return CSN_OK;
+  return launch_add_at_end(dh_below, dx_tm, C.dlen, C.T, t_lo, t_hi, C.B, C.H, st);
 }
 
 extern "C" int csn_lstm_profile_enable(csnLstmPlan* P, int on) {
@@ -978,16 +811,8 @@ static int gemm_tn_full(const void* A, const void* B, float* C, int64_t M, int64
 static int mask_x(const Call& C, hipStream_t st) {
   if (C.dlen == nullptr) return CSN_OK;
   const csnLstmDesc& d = C.d;
-  char* ws = C.ws;
-  const int64_t n = (int64_t)C.T * d.B * d.I;
-  if (d.dtype == CSN_BF16) mask_tm_kernel<bf16_t><<<grid_for(n), 256, 0, st>>>((bf16_t*)(ws + C.w.x_c), C.dlen, d.B, C.T, d.I);
-  else mask_tm_kernel<float><<<grid_for(n), 256, 0, st>>>((float*)(ws + C.w.x_c), C.dlen, d.B, C.T, d.I);
-  CSN_LAUNCH_CHECK();
-  if (C.w.fuse_x) {
-    const int64_t Bpad = ((int64_t)d.B + 63) / 64 * 64;
-    mask_x_blk_kernel<<<grid_for((int64_t)C.T * Bpad * d.I / 8), 256, 0, st>>>((bf16_t*)(ws + C.w.x_blk), C.dlen, d.B, Bpad, C.T, d.I);
-    CSN_LAUNCH_CHECK();
-  }
+  if (int rc = launch_mask_tm(C.ws + C.w.x_c, d.dtype, C.dlen, d.B, C.T, d.I, st)) return rc;
+  if (C.w.fuse_x) return launch_mask_x_blk((bf16_t*)(C.ws + C.w.x_blk), C.dlen, d.B, ((int64_t)d.B + 63) / 64 * 64, C.T, d.I, st);
   return CSN_OK;
 }
 
@@ -1982,18 +1807,26 @@ static int check_state_args(const Plan& P, const char* fn, const void* const* pt
   return CSN_OK;
 }
 
-// y_all of a reverse plan and / or with a pitch (csn_lstm_plan_set_io) and / or under output dropout, with or without lengths
-static int gather_y_all_io(const Call& C, float* y_all) {
-  const LayerWs& top = C.w.layer[C.NL - 1];
-  const int64_t n = (int64_t)C.T_full * C.B * C.H, pitch = C.P.y_pitch ? C.P.y_pitch : C.H;
-  if (C.P.out_drop_p > 0.f)       // csn_lstm_plan_set_output_dropout: the masked pass, whatever the pitch or direction
-    return launch_gather_y_all_drop(C.ws + top.h_all, C.dt, y_all, C.dlen, C.B, C.T_full, C.H, pitch, C.P.reverse, C.P.out_drop(), C.st);
-  if (C.dt == CSN_BF16)
-    gather_y_all_io_kernel<bf16_t><<<grid_for(n), 256, 0, C.st>>>((const bf16_t*)(C.ws + top.h_all), y_all, C.dlen, C.B, C.T_full, C.H, pitch, C.P.reverse);
-  else
-    gather_y_all_io_kernel<float><<<grid_for(n), 256, 0, C.st>>>((const float*)(C.ws + top.h_all), y_all, C.dlen, C.B, C.T_full, C.H, pitch, C.P.reverse);
-  CSN_LAUNCH_CHECK();
+// ---- what a forward hands back, out of the saved states (slot n of h_all / c_all is a row's state after its n steps: its
+// final state, and slot 0 the initial one, which is all a call whose rows are all empty reads)
+static const OutDropCfg* out_drop_of(const Call& C, OutDropCfg& od) {      // csn_lstm_plan_set_output_dropout, or null
+  od = C.P.out_drop();
+  return C.P.out_drop_p > 0.f ? &od : nullptr;
+}
+static int emit_state(const Call& C, int l, float* h_n, float* c_n) {
+  const LayerWs& L = C.w.layer[l];
+  const size_t at = (size_t)l * C.B * C.H;
+  if (h_n)
+    if (int rc = launch_gather_state(C.ws + L.h_all, C.dt, C.dlen, C.T, h_n + at, C.B, C.H, C.st)) return rc;
+  if (c_n) return launch_gather_state(C.ws + L.c_all, CSN_F32, C.dlen, C.T, c_n + at, C.B, C.H, C.st);
   return CSN_OK;
+}
+static int emit_y_last(const Call& C, float* y_last) {
+  return launch_gather_state(C.ws + C.w.layer[C.NL - 1].h_all, C.dt, C.dlen, C.T, y_last, C.B, C.H, C.st);
+}
+static int emit_y_all(const Call& C, float* y_all) {
+  OutDropCfg od;
+  return launch_y_out(C.ws + C.w.layer[C.NL - 1].h_all, C.dt, y_all, row_map(C, C.H, C.P.y_pitch), out_drop_of(C, od), C.st);
 }
 
 extern "C" int csn_lstm_forward(csnLstmPlan* Pp, const float* x, int64_t x_stride_b, int64_t x_stride_t,
@@ -2034,71 +1867,63 @@ extern "C" int csn_lstm_forward(csnLstmPlan* Pp, const float* x, int64_t x_strid
   Call C(P, workspace, st, dlen);
   if ((rc = upload_views(Pp, st, &C.vrow, &C.vt0))) return rc;
   const FwdArgs A{x, x_stride_b, x_stride_t, w_ih, w_hh, b_ih, b_hh, h0, c0};
-  const WsLayout& w = P.w;
-  char* ws = C.ws;
-  const int B = C.B, H = C.H, dt = C.dt;
-  const size_t es = C.es;
-  if (dlen != nullptr) {
-    // Variable-length batch: every path runs its unchanged kernels over steps 0 .. max(lengths)-1 of ALL rows (short rows
-    // run on over zeroed padding), then each row's results are selected: slot n of h_all / c_all is its final state
-    if (C.T > 0) {
-      if ((rc = run_forward(C, A))) return rc;
-    } else {
-      // every row is empty: no recurrence launch; slot 0 (the initial state) is all the gathers below read
-      for (int l = 0; l < d->L; ++l)
-        if ((rc = install_slot0(C, l, h0, c0))) return rc;
-      if (h0 || c0) P.state_seen = true;      // (slot 0 is no longer the zeros csn_lstm_workspace_init left)
-      P.prof.have[0] = false;
-    }
-    const unsigned gbh = grid_for((int64_t)B * H);
-    auto gather_h = [&](const LayerWs& L, float* out) {
-      if (dt == CSN_BF16) gather_state_kernel<bf16_t><<<gbh, 256, 0, st>>>((const bf16_t*)(ws + L.h_all), dlen, out, B, H);
-      else gather_state_kernel<float><<<gbh, 256, 0, st>>>((const float*)(ws + L.h_all), dlen, out, B, H);
-    };
-    for (int l = 0; l < d->L; ++l) {
-      const LayerWs& L = w.layer[l];
-      if (h_n) gather_h(L, h_n + (size_t)l * B * H);
-      if (c_n) gather_state_kernel<float><<<gbh, 256, 0, st>>>((const float*)(ws + L.c_all), dlen, c_n + (size_t)l * B * H, B, H);
-    }
-    const LayerWs& top = w.layer[d->L - 1];
-    if (y_last) gather_h(top, y_last);
-    if (y_all) {
-      const int T = C.T_full;       // the caller's rows: zeros from each row's length on
-      const int64_t n = (int64_t)T * B * H;
-      if (P.reverse || P.y_pitch || P.out_drop_p > 0.f) {
-        if ((rc = gather_y_all_io(C, y_all))) return rc;
-      } else if (dt == CSN_BF16)
-        gather_y_all_len_kernel<bf16_t><<<grid_for(n), 256, 0, st>>>((const bf16_t*)(ws + top.h_all), y_all, dlen, B, T, H);
-      else
-        gather_y_all_len_kernel<float><<<grid_for(n), 256, 0, st>>>((const float*)(ws + top.h_all), y_all, dlen, B, T, H);
-    }
-    CSN_LAUNCH_CHECK();
-    return CSN_OK;
+  // Every path runs its kernels over steps 0 .. C.T - 1 of ALL rows (with lengths: the longest row's, short rows run on
+  // over zeroed padding), then each row's results are selected
+  if (C.T > 0) {
+    if ((rc = run_forward(C, A))) return rc;
+  } else {
+    // every row is empty: no recurrence launch; slot 0 (the initial state) is all the gathers below read
+    for (int l = 0; l < d->L; ++l)
+      if ((rc = install_slot0(C, l, h0, c0))) return rc;
+    if (h0 || c0) P.state_seen = true;      // (slot 0 is no longer the zeros csn_lstm_workspace_init left)
+    P.prof.have[0] = false;
   }
-  if ((rc = run_forward(C, A))) return rc;
-  const int T = C.T;
-  // final state of every layer: slot T of h_all (upcast of the h the next layer consumed) and of c_all
-  for (int l = 0; l < d->L && (h_n || c_n); ++l) {
-    const LayerWs& L = w.layer[l];
-    if (h_n && (rc = launch_upcast(ws + L.h_all + (size_t)T * B * H * es, dt, h_n + (size_t)l * B * H, (int64_t)B * H, st)))
-      return rc;
-    if (c_n)
-      CSN_HIP_CHECK(hipMemcpyAsync(c_n + (size_t)l * B * H, ws + L.c_all + (size_t)T * B * H * 4, (size_t)B * H * 4,
-                                   hipMemcpyDeviceToDevice, st));
+  for (int l = 0; l < d->L && (h_n || c_n); ++l)
+    if ((rc = emit_state(C, l, h_n, c_n))) return rc;
+  if (y_last && (rc = emit_y_last(C, y_last))) return rc;
+  if (y_all && (rc = emit_y_all(C, y_all))) return rc;
+  return CSN_OK;
+}
+
+// ---- the gradient w.r.t. the top layer's outputs as the paths take it: A.dy_tm, dense and time-major in the workspace
+// (dy_all, zero over the padding; then dy_last and the top layer's dh_n added at each row's last step, in this order), or,
+// for a call without lengths and without dy_all, A.dy_last alone: no T B H buffer is filled
+static int assemble_top_dy(const Call& C, BwdArgs& A, const float* dy_all) {
+  float* buf = (float*)(C.ws + C.w.dy_tm);
+  const size_t BH = (size_t)C.B * C.H;
+  const float* dh_top = A.dh_n ? A.dh_n + (C.NL - 1) * BH : nullptr;
+  int rc;
+  if (dy_all || C.dlen) {
+    OutDropCfg od;
+    if ((rc = launch_dy_in(dy_all, buf, row_map(C, C.H, C.P.dy_pitch), out_drop_of(C, od), C.st))) return rc;
+    if (A.dy_last && (rc = launch_add_at_end(A.dy_last, buf, C.dlen, C.T, 0, C.T - 1, C.B, C.H, C.st))) return rc;
+    if (dh_top && (rc = launch_add_at_end(dh_top, buf, C.dlen, C.T, 0, C.T - 1, C.B, C.H, C.st))) return rc;
+    A.dy_last = nullptr;
+    A.dy_tm = buf;
+  } else if (dh_top && A.dy_last) {
+    // (dy_last is caller memory: the sum goes into a workspace copy of it, one step at the front of the unused dy_tm region)
+    CSN_HIP_CHECK(hipMemcpyAsync(buf, A.dy_last, BH * 4, hipMemcpyDeviceToDevice, C.st));
+    if ((rc = launch_add_at_end(dh_top, buf, nullptr, 1, 0, 0, C.B, C.H, C.st))) return rc;
+    A.dy_last = buf;
+  } else if (dh_top) {
+    A.dy_last = dh_top;
   }
-  const LayerWs& top = w.layer[d->L - 1];
-  if (y_last)
-    if ((rc = launch_upcast(ws + top.h_all + (size_t)T * B * H * es, dt, y_last, (int64_t)B * H, st))) return rc;
-  if (y_all) {
-    const int64_t n = (int64_t)T * B * H;
-    if (P.reverse || P.y_pitch || P.out_drop_p > 0.f) {
-      if ((rc = gather_y_all_io(C, y_all))) return rc;
-    } else if (dt == CSN_BF16)
-      gather_y_all_kernel<bf16_t><<<grid_for(n), 256, 0, st>>>((const bf16_t*)(ws + top.h_all), y_all, B, T, H);
-    else
-      gather_y_all_kernel<float><<<grid_for(n), 256, 0, st>>>((const float*)(ws + top.h_all), y_all, B, T, H);
-    CSN_LAUNCH_CHECK();
+  return CSN_OK;
+}
+// every row is empty: no recurrence, no parameter contribution
+static int backward_all_empty(const Call& C, const BwdArgs& A) {
+  Plan& P = C.P;
+  if (A.dx && !P.dx_add) CSN_HIP_CHECK(hipMemsetAsync(A.dx, 0, (size_t)C.T_full * C.B * C.d.I * 4, C.st));
+  for (int l = C.NL - 1; l >= 0; --l) {
+    if (!P.grad_accumulate) {
+      CSN_HIP_CHECK(hipMemsetAsync(A.dw_ih[l], 0, (size_t)(C.G * C.in_width(l)) * 4, C.st));
+      CSN_HIP_CHECK(hipMemsetAsync(A.dw_hh[l], 0, (size_t)(C.G * C.H) * 4, C.st));
+      CSN_HIP_CHECK(hipMemsetAsync(A.db_ih[l], 0, (size_t)C.G * 4, C.st));
+      CSN_HIP_CHECK(hipMemsetAsync(A.db_hh[l], 0, (size_t)C.G * 4, C.st));
+    }
+    P.grads_ready(l);
   }
+  P.prof.have[1] = false;
   return CSN_OK;
 }
 
@@ -2134,110 +1959,36 @@ extern "C" int csn_lstm_backward(csnLstmPlan* Pp, const float* dy_last, const fl
   if ((rc = upload_lengths(Pp, st, &dlen))) return rc;
   Call C(P, workspace, st, dlen);
   BwdArgs A{dy_last, nullptr, dh_n, dc_n, dw_ih, dw_hh, db_ih, db_hh, dx};
-  const WsLayout& w = P.w;
-  char* ws = C.ws;
-  const int B = C.B, H = C.H, NL = C.NL;
-  const size_t BH = (size_t)B * H;
-  float* buf = (float*)(ws + w.dy_tm);       // dense time-major dy of the top layer
-
-  if (dlen != nullptr) {
-    // Variable-length batch (the lengths of the matching forward): the backward of the steps the forward ran, with the
-    // masked cell kernels; every gradient that enters at a row's end is added at that row's own last step
-    const int64_t G = C.G;
-    const int Te = C.T;
-    if (Te > 0) {
-      // zeros over the padding of dy
-      if (P.out_drop_p > 0.f) {
-        if ((rc = launch_bt_to_tb_drop(dy_all, buf, dlen, B, C.T_full, Te, H, P.dy_pitch ? P.dy_pitch : H, P.reverse, P.out_drop(), st))) return rc;
-      } else if (P.reverse || P.dy_pitch)
-        bt_to_tb_io_kernel<<<grid_for((int64_t)Te * B * H), 256, 0, st>>>(dy_all, buf, dlen, B, C.T_full, Te, H, P.dy_pitch ? P.dy_pitch : H, P.reverse);
-      else
-        bt_to_tb_len_kernel<<<grid_for((int64_t)Te * B * H), 256, 0, st>>>(dy_all, buf, dlen, B, C.T_full, Te, H);
-      if (dy_last) add_at_end_kernel<<<grid_for((int64_t)BH), 256, 0, st>>>(dy_last, buf, dlen, 0, Te - 1, B, H);
-      if (dh_n) add_at_end_kernel<<<grid_for((int64_t)BH), 256, 0, st>>>(dh_n + (NL - 1) * BH, buf, dlen, 0, Te - 1, B, H);
-      CSN_LAUNCH_CHECK();
-      A.dy_last = nullptr;
-      A.dy_tm = buf;
-      if ((rc = run_backward(C, A))) return rc;
-    } else {
-      // every row is empty: no recurrence, no parameter contribution
-      if (dx && !P.dx_add) CSN_HIP_CHECK(hipMemsetAsync(dx, 0, (size_t)C.T_full * B * d->I * 4, st));
-      for (int l = NL - 1; l >= 0; --l) {
-        if (!P.grad_accumulate) {
-          CSN_HIP_CHECK(hipMemsetAsync(dw_ih[l], 0, (size_t)(G * C.in_width(l)) * 4, st));
-          CSN_HIP_CHECK(hipMemsetAsync(dw_hh[l], 0, (size_t)(G * H) * 4, st));
-          CSN_HIP_CHECK(hipMemsetAsync(db_ih[l], 0, (size_t)G * 4, st));
-          CSN_HIP_CHECK(hipMemsetAsync(db_hh[l], 0, (size_t)G * 4, st));
-        }
-        P.grads_ready(l);
-      }
-      P.prof.have[1] = false;
-    }
-    for (int l = 0; l < NL && (dh0 || dc0); ++l) {
-      if (dh0) {
-        float* out = dh0 + l * BH;
-        if (Te > 0) {
-          if ((rc = launch_dh0(C, l, out))) return rc;
-        } else {
-          CSN_HIP_CHECK(hipMemsetAsync(out, 0, BH * 4, st));
-        }
-        // an empty row's dgates are zero at step 0: its dh0 is the gradient w.r.t. its h_n
-        if (dh_n) add_rows_len0_kernel<<<grid_for((int64_t)BH), 256, 0, st>>>(dh_n + l * BH, out, dlen, B, H);
-        // ... and y_last of an empty row is h_n of the top layer, that is its h0: dy_last reaches dh0 there
-        if (dy_last && l == NL - 1) add_rows_len0_kernel<<<grid_for((int64_t)BH), 256, 0, st>>>(dy_last, out, dlen, B, H);
-        CSN_LAUNCH_CHECK();
-      }
-      if (dc0) {
-        // the carried dc: an empty row's passed every (masked) step as it was
-        if (Te > 0)
-          CSN_HIP_CHECK(hipMemcpyAsync(dc0 + l * BH, ws + w.layer[l].dc_carry, BH * 4, hipMemcpyDeviceToDevice, st));
-        else if (dc_n)
-          CSN_HIP_CHECK(hipMemcpyAsync(dc0 + l * BH, dc_n + l * BH, BH * 4, hipMemcpyDeviceToDevice, st));
-        else
-          CSN_HIP_CHECK(hipMemsetAsync(dc0 + l * BH, 0, BH * 4, st));
-      }
-    }
-    return CSN_OK;
+  const size_t BH = (size_t)C.B * C.H;
+  if (C.T > 0) {
+    if ((rc = assemble_top_dy(C, A, dy_all))) return rc;
+    if ((rc = run_backward(C, A))) return rc;
+  } else if ((rc = backward_all_empty(C, A))) {
+    return rc;
   }
-
-  // gradient w.r.t. the top layer's outputs, time-major.  With only dy_last, no buffer is needed.
-  const int T = C.T;
-  if (dy_all) {
-    if (P.out_drop_p > 0.f) {
-      if ((rc = launch_bt_to_tb_drop(dy_all, buf, nullptr, B, T, T, H, P.dy_pitch ? P.dy_pitch : H, P.reverse, P.out_drop(), st))) return rc;
-    } else if (P.reverse || P.dy_pitch)
-      bt_to_tb_io_kernel<<<grid_for(C.TB * H), 256, 0, st>>>(dy_all, buf, nullptr, B, T, T, H, P.dy_pitch ? P.dy_pitch : H, P.reverse);
-    else
-      bt_to_tb_kernel<<<grid_for(C.TB * H), 256, 0, st>>>(dy_all, buf, B, T, H);
-    CSN_LAUNCH_CHECK();
-    if (dy_last) {
-      add_rows_kernel<<<grid_for((int64_t)BH), 256, 0, st>>>(dy_last, buf + (size_t)(T - 1) * BH, (int64_t)BH);
-      CSN_LAUNCH_CHECK();
-    }
-    A.dy_tm = buf;
-  }
-  // gradient w.r.t. the top layer's h_n: one more term of its dy at t = T-1 (dy_last is caller memory: added into a
-  // workspace copy of it, in the dy_tm region that is unused when dy_all is NULL)
-  if (dh_n) {
-    const float* dh_top = dh_n + (NL - 1) * BH;
-    if (A.dy_tm) {
-      add_rows_kernel<<<grid_for((int64_t)BH), 256, 0, st>>>(dh_top, buf + (size_t)(T - 1) * BH, (int64_t)BH);
-      CSN_LAUNCH_CHECK();
-    } else if (dy_last) {
-      CSN_HIP_CHECK(hipMemcpyAsync(buf, dy_last, BH * 4, hipMemcpyDeviceToDevice, st));
-      add_rows_kernel<<<grid_for((int64_t)BH), 256, 0, st>>>(dh_top, buf, (int64_t)BH);
-      CSN_LAUNCH_CHECK();
-      A.dy_last = buf;
-    } else {
-      A.dy_last = dh_top;
-    }
-  }
-  if ((rc = run_backward(C, A))) return rc;
   // gradients w.r.t. the initial state (CSN_LSTM_STATE plans only: paths 0 and 1, everything on `stream` by now)
-  for (int l = 0; l < NL && (dh0 || dc0); ++l) {
-    if (dh0 && (rc = launch_dh0(C, l, dh0 + l * BH))) return rc;
-    if (dc0)
-      CSN_HIP_CHECK(hipMemcpyAsync(dc0 + l * BH, ws + w.layer[l].dc_carry, BH * 4, hipMemcpyDeviceToDevice, st));
+  for (int l = 0; l < C.NL && (dh0 || dc0); ++l) {
+    if (dh0) {
+      float* out = dh0 + l * BH;
+      if (C.T > 0) {
+        if ((rc = launch_dh0(C, l, out))) return rc;
+      } else {
+        CSN_HIP_CHECK(hipMemsetAsync(out, 0, BH * 4, st));
+      }
+      // an empty row's dgates are zero at step 0: its dh0 is the gradient w.r.t. its h_n
+      if (dlen && dh_n && (rc = launch_add_rows_len0(dh_n + l * BH, out, dlen, C.B, C.H, st))) return rc;
+      // ... and y_last of an empty row is h_n of the top layer, that is its h0: dy_last reaches dh0 there
+      if (dlen && dy_last && l == C.NL - 1 && (rc = launch_add_rows_len0(dy_last, out, dlen, C.B, C.H, st))) return rc;
+    }
+    if (dc0) {
+      // the carried dc (an empty row's passed every masked step as it was); without a step, dc_n itself
+      if (C.T > 0)
+        CSN_HIP_CHECK(hipMemcpyAsync(dc0 + l * BH, C.ws + C.w.layer[l].dc_carry, BH * 4, hipMemcpyDeviceToDevice, st));
+      else if (dc_n)
+        CSN_HIP_CHECK(hipMemcpyAsync(dc0 + l * BH, dc_n + l * BH, BH * 4, hipMemcpyDeviceToDevice, st));
+      else
+        CSN_HIP_CHECK(hipMemsetAsync(dc0 + l * BH, 0, BH * 4, st));
+    }
   }
   return CSN_OK;
 }

@@ -1,0 +1,53 @@
+// The API boundary of the stacked LSTM (lstm_boundary.hip): everything that turns the caller's batch-first float32 tensors
+// into the time-major workspace and back around the recurrence -- one kernel per layout pass (y_all out, dy_all in, dx out)
+// whatever the plan's lengths, direction, pitch, adding store or output dropout (DESIGN.md sections 10, 16 and 23), and the
+// small per-row helpers of variable-length batches.  lstm.hip calls the launchers below and launches none of this itself.
+#pragma once
+#include "lstm_dropout.h"
+
+namespace csn {
+
+// One layout pass over rows of the caller's [B, Tn, .] tensor and steps of the time-major workspace.
+struct RowMap {
+  const int* len;      // [B] device, valid steps per row; null: every row has Tn
+  int B, Tn, Te, H;    // Tn: steps per row of the caller's tensor; Te: the steps the call ran (dy_in fills only those); H: row width
+  int64_t pitch;       // elements between two (b, t) rows of the caller's tensor (y_out, dy_in; dx is dense)
+  int rev;             // CSN_LSTM_REVERSE plan: the recurrence walked each row from its own last step
+  int add;             // dx_out: add to what the caller's tensor holds, and leave its padding alone
+};
+
+// THE index rule.  Row b has n = len[b] valid steps (Tn without lengths).  Step s of the recurrence
+// is the caller's t = rev ? n - 1 - s : s -- the same expression turns t into s --, and the output at t is slot
+// rev ? n - t : t + 1 of h_all (slot 0 is the initial state, slot n the final one).  Nothing at t >= n was computed.
+struct RowSteps {
+  int64_t n;
+  int rev;
+  __device__ __forceinline__ RowSteps(const int* __restrict__ len, int64_t b, int Tn, int rev_) : n(len != nullptr ? len[b] : Tn), rev(rev_) {}
+  __device__ __forceinline__ bool valid(int64_t t) const { return t < n; }
+  __device__ __forceinline__ int64_t flip(int64_t t) const { return rev ? n - 1 - t : t; }       // t <-> s
+  __device__ __forceinline__ int64_t slot(int64_t t) const { return rev ? n - t : t + 1; }
+};
+
+// The launchers.  od: output dropout (csn_lstm_plan_set_output_dropout), or null.  With it a thread moves four consecutive h
+// under one Philox call with 16-byte accesses of the caller's tensor, which must be 16-B aligned with pitch % 4 == 0;
+// without it one element, and the caller's tensor needs the 4 bytes of a float.  A dropped element is a selected zero.
+// y[(b Tn + t) pitch + h] = t < n ? [keep ? scale *] float(h_all[slot(t)][b][h]) : 0      (h_all: dtype, time-major)
+int launch_y_out(const void* h_all, int dtype, float* y, const RowMap& m, const OutDropCfg* od, hipStream_t st);
+// dy_tm[s][b][h], s < Te  =  s < n && dy ? [keep ? scale *] dy[(b Tn + t) pitch + h] : 0      (dy null: all zeros)
+int launch_dy_in(const float* dy, float* dy_tm, const RowMap& m, const OutDropCfg* od, hipStream_t st);
+// dx[b][t][i] = or += dx_tm[s][b][i] for t < n; from n on zero, or with add left as it is      (m.H: the input width)
+int launch_dx_out(const float* dx_tm, float* dx, const RowMap& m, hipStream_t st);
+
+// out[b][h] (f32) = all[n][b][h], n = len ? len[b] : T: slot n of h_all / c_all is the state after step n - 1, slot 0 the initial state
+int launch_gather_state(const void* all, int dtype, const int* len, int T, float* out, int B, int H, hipStream_t st);
+// dst_tm[n-1][b][:] += src[b][:] for the rows whose last step n - 1 lies in [t_lo, t_hi]: a gradient that enters at the
+// row's end.  Without lengths every row ends at T - 1, and no kernel is launched when that lies outside the window.
+int launch_add_at_end(const float* src, float* dst_tm, const int* len, int T, int t_lo, int t_hi, int B, int H, hipStream_t st);
+// dst[b][:] += src[b][:] for the rows of length 0 (their dh0 is dh_n)
+int launch_add_rows_len0(const float* src, float* dst, const int* len, int B, int H, hipStream_t st);
+// buf[t][b][:] = 0 where t >= len[b] (time-major input copy [Tn, B, W] in dtype: padding is never multiplied) ...
+int launch_mask_tm(void* buf, int dtype, const int* len, int B, int Tn, int W, hipStream_t st);
+// ... and the same on the fragment-major slabs [Tn][Bpad * I] of the fused input projection
+int launch_mask_x_blk(bf16_t* x_blk, const int* len, int B, int64_t Bpad, int Tn, int I, hipStream_t st);
+
+}  // namespace csn

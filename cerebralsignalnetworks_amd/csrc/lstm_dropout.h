@@ -53,20 +53,13 @@ int launch_lstm_dropout_fwd(const void* h, void* h_drop, int64_t n, uint64_t e0,
 int launch_lstm_dropout_bwd(float* dx, int64_t n, uint64_t e0, const DropoutCfg& cfg, hipStream_t st);
 
 // Output dropout (csn_lstm_plan_set_output_dropout): the mask on the caller's [B, Tn, .] tensor, applied by the layout
-// passes themselves.  Element (b, t, h) has the index first + (b Tn + t) index_pitch + h; first % 4 == 0,
-// index_pitch % 4 == 0 and H % 32 == 0 put every four consecutive h on one Philox call.
+// passes themselves (lstm_boundary.hip: y_out and dy_in).  Element (b, t, h) has the index
+// first + (b Tn + t) index_pitch + h; first % 4 == 0, index_pitch % 4 == 0 and H % 32 == 0 put every four consecutive h on
+// one Philox call.
 struct OutDropCfg {
   DropoutCfg cfg;
   uint64_t first;
   int64_t index_pitch;
 };
-// y[(b Tn + t) pitch + h] = t < n ? (keep ? float(h_all[slot][b][h]) * scale : 0) : 0, as gather_y_all_io_kernel walks it
-// (n = len[b] or Tn, slot = rev ? n - t : t + 1); h_all: dtype, time-major; y: float32, 16-B aligned, pitch % 4 == 0
-int launch_gather_y_all_drop(const void* h_all, int dtype, float* y, const int* len, int B, int Tn, int H, int64_t pitch, int rev,
-                             const OutDropCfg& od, hipStream_t st);
-// dst[s][b][h], s < Te  =  s < n && src ? (keep ? src[(b Tn + t) pitch + h] * scale : 0) : 0, as bt_to_tb_io_kernel walks it
-// (t = rev ? n - 1 - s : s); src: float32, 16-B aligned or null, pitch % 4 == 0; dst: dense time-major float32
-int launch_bt_to_tb_drop(const float* src, float* dst, const int* len, int B, int Tn, int Te, int H, int64_t pitch, int rev,
-                         const OutDropCfg& od, hipStream_t st);
 
 }  // namespace csn

@@ -77,81 +77,6 @@ int launch_lstm_dropout_bwd(float* dx, int64_t n, uint64_t e0, const DropoutCfg&
   return CSN_OK;
 }
 
-// ---- output dropout (csn_lstm_plan_set_output_dropout): the batch-first <-> time-major passes of
-// lstm.hip around the recurrence with the mask applied as they store / load, so the interface tensor of a stack of
-// single-layer plans is touched once per direction and pass.  One thread and trip: four consecutive h = one Philox call,
-// one 16-byte store, one 16-byte (float32) or 8-byte (bf16) load; the (b, t, h-group) arithmetic once per group.
-template <typename T> struct Quad;
-template <> struct Quad<bf16_t> { typedef bf16x4 type; };
-template <> struct Quad<float> { typedef f32x4 type; };
-
-template <typename T>
-__global__ void __launch_bounds__(256) gather_y_all_drop_kernel(const T* __restrict__ h_all, float* __restrict__ y, const int* __restrict__ len,
-                                                                 int B, int Tn, int H, int64_t pitch, int rev, OutDropCfg od) {
-  typedef typename Quad<T>::type V;
-  const int64_t hq = H >> 2, groups = (int64_t)B * Tn * hq;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += stride) {
-    const int64_t h = (g % hq) << 2, r = g / hq, t = r % Tn, b = r / Tn;
-    const int64_t n = len != nullptr ? len[b] : Tn;
-    f32x4 out = {0.f, 0.f, 0.f, 0.f};
-    if (t < n) {
-      const V v = *reinterpret_cast<const V*>(h_all + ((rev ? n - t : t + 1) * B + b) * (int64_t)H + h);
-      const Philox4 w = dropout_words(od.cfg, (od.first + (uint64_t)r * (uint64_t)od.index_pitch + (uint64_t)h) >> 2);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) out[j] = (uint64_t)w.w[j] >= od.cfg.thr ? to_f32((T)v[j]) * od.cfg.scale : 0.f;
-    }
-    *reinterpret_cast<f32x4*>(y + r * pitch + h) = out;
-  }
-}
-
-__global__ void __launch_bounds__(256) bt_to_tb_drop_kernel(const float* __restrict__ src, float* __restrict__ dst, const int* __restrict__ len,
-                                                             int B, int Tn, int Te, int H, int64_t pitch, int rev, OutDropCfg od) {
-  const int64_t hq = H >> 2, groups = (int64_t)B * Te * hq;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += stride) {
-    const int64_t h = (g % hq) << 2, r = g / hq, b = r % B, s = r / B;
-    const int64_t n = len != nullptr ? len[b] : Tn;
-    f32x4 out = {0.f, 0.f, 0.f, 0.f};
-    if (src != nullptr && s < n) {
-      const int64_t row = b * Tn + (rev ? n - 1 - s : s);
-      const f32x4 v = *reinterpret_cast<const f32x4*>(src + row * pitch + h);
-      const Philox4 w = dropout_words(od.cfg, (od.first + (uint64_t)row * (uint64_t)od.index_pitch + (uint64_t)h) >> 2);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) out[j] = (uint64_t)w.w[j] >= od.cfg.thr ? v[j] * od.cfg.scale : 0.f;
-    }
-    *reinterpret_cast<f32x4*>(dst + (g << 2)) = out;
-  }
-}
-
-static int check_out_drop(const char* fn, const void* caller, int H, int64_t pitch, const OutDropCfg& od) {
-  CSN_REQUIRE(H % 32 == 0 && pitch % 4 == 0 && pitch >= H, "%s: H = %d, pitch = %lld: groups of four h are not aligned", fn, H, (long long)pitch);
-  CSN_REQUIRE(od.first % 4 == 0 && od.index_pitch % 4 == 0 && od.index_pitch >= H, "%s: first = %llu, index_pitch = %lld split a Philox call", fn,
-              (unsigned long long)od.first, (long long)od.index_pitch);
-  CSN_REQUIRE((reinterpret_cast<uintptr_t>(caller) & 15) == 0, "%s: the caller's tensor must be 16-B aligned", fn);
-  return CSN_OK;
-}
-
-int launch_gather_y_all_drop(const void* h_all, int dtype, float* y, const int* len, int B, int Tn, int H, int64_t pitch, int rev,
-                             const OutDropCfg& od, hipStream_t st) {
-  if (int rc = check_out_drop("gather_y_all_drop", y, H, pitch, od)) return rc;
-  const unsigned grid = drop_grid((int64_t)B * Tn * (H >> 2));
-  if (dtype == CSN_BF16)
-    gather_y_all_drop_kernel<bf16_t><<<grid, 256, 0, st>>>((const bf16_t*)h_all, y, len, B, Tn, H, pitch, rev, od);
-  else
-    gather_y_all_drop_kernel<float><<<grid, 256, 0, st>>>((const float*)h_all, y, len, B, Tn, H, pitch, rev, od);
-  CSN_LAUNCH_CHECK();
-  return CSN_OK;
-}
-
-int launch_bt_to_tb_drop(const float* src, float* dst, const int* len, int B, int Tn, int Te, int H, int64_t pitch, int rev,
-                         const OutDropCfg& od, hipStream_t st) {
-  if (int rc = check_out_drop("bt_to_tb_drop", src, H, pitch, od)) return rc;
-  bt_to_tb_drop_kernel<<<drop_grid((int64_t)B * Te * (H >> 2)), 256, 0, st>>>(src, dst, len, B, Tn, Te, H, pitch, rev, od);
-  CSN_LAUNCH_CHECK();
-  return CSN_OK;
-}
-
 }  // namespace csn
 
 using namespace csn;

@@ -426,8 +426,8 @@ int csn_lstm_dropout_keep(uint64_t seed, uint32_t subsequence, float p, int64_t 
  *   get through.  dy_last, dh_n, dc_n are untouched.  The matching backward must run with its forward's setting, as for
  *   the lengths.
  * With p = 0 (the default) the plan enqueues the launches and writes the bits it did before this symbol existed.  With
- * p > 0 the two layout passes are the kernels of lstm_dropout.hip, whatever the plan's pitch or direction: no extra pass
- * and no extra launch.  They move 16 bytes per access, so with p > 0 csn_lstm_forward / csn_lstm_backward return
+ * p > 0 the two layout passes are the masked instantiations of the same kernels (y_out and dy_in of lstm_boundary.hip),
+ * whatever the plan's pitch or direction: no extra pass and no extra launch.  They move 16 bytes per access, so with p > 0 csn_lstm_forward / csn_lstm_backward return
  * CSN_ERR_INVALID_ARGUMENT, before enqueueing anything, for a y_all / dy_all that is not 16-byte aligned.
  * Null plan, p outside [0, 1] or NaN, or with p > 0: first % 4 != 0, index_pitch % 4 != 0, index_pitch < H:
  * CSN_ERR_INVALID_ARGUMENT (the setting is kept). */

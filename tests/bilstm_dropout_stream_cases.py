@@ -2,7 +2,7 @@
 PLAN_SETTERS table on import, as tests/channel_discovery_stream_cases.py joins the case table).
 
 The setter takes no stream: what it sets swaps the two layout passes of the forward and backward that follow for the masked
-ones of csrc/lstm_dropout.hip, on the stream of those calls.  BiLSTM sets it on every plan before every forward and
+instantiations of csrc/lstm_boundary.hip, on the stream of those calls.  BiLSTM sets it on every plan before every forward and
 backward (p = 0 on the top layer and outside train() mode), so the module's stream-order test runs those calls with the
 setting made between unsynchronised calls; tests/test_gpu_bilstm_dropout.py::test_bilstm_dropout_on_a_side_stream_with_
 late_inputs runs the same with p > 0."""

@@ -23,7 +23,7 @@ DEV, BF16, F32 = st.DEV, st.BF16, st.F32
 NAN, INF = float("nan"), float("inf")
 PS = (0.1, 0.5, 0.9, 1.0)
 FIRSTS = (0, 2 ** 32 - 64, 2 ** 40 + 4)
-# one trip of the two kernels' grid: drop_grid's 4096 blocks of 256 threads, four elements each (csrc/lstm_dropout.hip)
+# one trip of the two masked kernels' grid: 4096 blocks of 256 threads, four elements each (csrc/lstm_boundary.hip)
 ONE_TRIP = 4096 * 256 * 4
 
 

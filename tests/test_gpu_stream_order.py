@@ -509,7 +509,7 @@ def test_lstm_feature_forward_with_late_inputs(cuda, name, features):
     weights, h0 and c0 arrive behind the Delay and are overwritten behind the call; the [B, T, 2H] y buffer is filled with
     NaN on the stream in front of the call.  What a wrong stream would do here: a drop_fwd launch off the stream of the
     GEMM behind it (xproj_chunk_gemm on the side stream, the layer streams of forward_persist) masks h before the
-    recurrence wrote it; gather_y_all_io_kernel off the caller's stream writes the half before the NaN fill or after the
+    recurrence wrote it; y_out (lstm_boundary.hip) off the caller's stream writes the half before the NaN fill or after the
     snapshot; kPrepCastX / kPrepBlockifyX / cast_strided_kernel off it read the poisoned source; the windows upload on
     another stream than the layout kernels leaves them with the previous call's arrays -- which hold the same values here,
     so THAT one is test_lstm_settings_change_between_unsynchronised_calls'.  The stream is synchronised once between the
@@ -576,8 +576,8 @@ def test_lstm_feature_backward_with_late_inputs(cuda, name, features, mode):
     behind the Delay; the forward before it ran on the same stream and had its inputs (the window source included)
     overwritten directly behind it.  What a wrong stream would do: a drop_bwd launch off the stream of its GEMM
     (dx_chunk_gemm on the side stream; the caller's stream in backward_persist) masks dx before the GEMM produced it, or
-    the dh_n rows are added before the mask; bt_to_tb_io_kernel off the caller's stream reads the poisoned dy buffer;
-    tb_to_bt_io_kernel (emit_dx, on the side stream in backward_il) adds to a dx whose late values have not arrived --
+    the dh_n rows are added before the mask; dy_in off the caller's stream reads the poisoned dy buffer;
+    dx_out (emit_dx, on the side stream in backward_il) adds to a dx whose late values have not arrived --
     or, with the closing join missing, is overtaken by the snapshot, which overwrite_tail takes of dx last."""
     t0 = time.perf_counter()
     c = _lstm(name, features)

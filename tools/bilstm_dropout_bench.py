@@ -5,7 +5,7 @@
 Per shape, on the same inputs and parameter values, a gradient on every output step and the input gradient asked for:
   (p0)  BiLSTM with the attribute at 0: the layout passes the plans ran before csn_lstm_plan_set_output_dropout existed;
   (p05) the attribute at 0.5: the lower layers' plans store y_all and load dy_all through the masked passes
-        (gather_y_all_drop_kernel / bt_to_tb_drop_kernel) instead -- no further launch, no further pass;
+        (y_out<T, true> / dy_in<true> of csrc/lstm_boundary.hip) instead -- no further launch, no further pass;
   (p0 against the parent) with --parent_lib, the library built from the parent commit: leg (p0) once more in two fresh child
         processes, one on this tree's library and one on the parent's (CSN_LIB_PATH), run in turns.  The parent's library
         has no csn_lstm_plan_set_output_dropout: the child drops the symbol from the binding and answers the p = 0
