@@ -34,14 +34,106 @@ class _Lease:
     __del__ = release
 
 
-def _direct_grads(owner, params):
+class _PlanPool(dict):
+    """key -> list of plans; plan.busy marks a forward awaiting its backward.  Workspaces are large (10 GB at cfg2), so
+    only a few idle ones are kept."""
+
+    def checkout(self, key, make, max_idle):
+        """-> an idle plan of ``key``, or make() after dropping idle plans of OTHER keys, oldest first, while at least
+        ``max_idle`` of them are idle.  A busy plan and a plan of ``key`` are never dropped."""
+        plans = self.setdefault(key, [])
+        for plan in plans:
+            if not plan.busy:
+                return plan
+        idle = [(k, pl) for k, lst in self.items() for pl in lst if not pl.busy and k != key]
+        while len(idle) >= max_idle:
+            k, pl = idle.pop(0)
+            self[k].remove(pl)
+        plans.append(make())
+        return plans[-1]
+
+    def all(self):
+        return [pl for lst in self.values() for pl in lst]
+
+
+class _Call:
+    """What one forward asks of its plan(s).  Kept on ctx: the backward runs with the lengths and dropout of its forward.
+    ``B, T``: the plan's shape -- x's, or with ``views = (rows, starts)`` (x is then the source) the windows'.  ``drop``:
+    _draw_dropout's.  ``outputs``: which of (y_last, y_all, h_n, c_n) the entry point takes -- the library is asked for no
+    other, and only their gradients go to plan.backward.  ``state_plan``: HipLSTM._checkout's ``state``.  ``overwrite``: is
+    ``direct_grads = True`` honoured?  ``bi``: BiLSTM's (L, H)."""
+    __slots__ = ("B", "T", "training", "drop", "lengths", "views", "outputs", "state_plan", "overwrite", "bi")
+
+    def __init__(self, x, training, drop, lengths=None, views=None, outputs=(True, False, False, False), state_plan=None,
+                 overwrite=True, bi=None):
+        self.B, self.T = (x.shape[0], x.shape[1]) if views is None else (len(lengths), max(1, max(lengths)))
+        self.training, self.drop, self.lengths, self.views = training, drop, lengths, views
+        self.outputs, self.state_plan, self.overwrite, self.bi = outputs, state_plan, overwrite, bi
+
+
+def _armed(plan, call, fn, grad=None, k=None, src=None):
+    """fn() -- ``call``'s plan.forward or plan.backward -- with everything it depends on set on the plan first.  Plans are
+    shared between calls and every setter of cabi.LstmPlan is sticky, so a pooled plan still carries whatever its last
+    user set: nothing is assumed, all of it is set in front of every forward and backward.  That is: the lengths (None =
+    every row is T; on CSN_LSTM_STATE plans only, the library refuses set_lengths on others); on a stack's plan the
+    inter-layer dropout (None = p 0, which a plan without the bit takes too); on BiLSTM's plan ``k`` = 2 * layer +
+    direction the io pitches -- on a backward the reverse direction adds its dx to the forward one's -- and the output
+    dropout of its half of the [B,T,2H] interface (one Philox stream per call covers the concatenated interfaces, as torch
+    drops each once; the top layer's is never dropped); on a backward ``grad`` = (callback, accumulate).  ``src``: the
+    source tensor of a forward through input windows, which are cleared again, also when fn raises -- a backward reads no
+    x, so it sets none."""
+    if plan.state:
+        plan.set_lengths(call.lengths)
+    if k is None:
+        plan.set_dropout(*(call.drop or (0.0,)))
+    else:
+        (L, H), l, d = call.bi, k // 2, k % 2
+        plan.set_io(2 * H, 2 * H, grad is not None and d == 1)
+        if call.drop is None or l >= L - 1:
+            plan.set_output_dropout(0.0)
+        else:
+            plan.set_output_dropout(*call.drop, first=l * call.B * call.T * 2 * H + d * H, index_pitch=2 * H)
+    if grad is not None:
+        plan.set_grad_callback(grad[0])
+        plan.set_grad_mode(grad[1])
+    if src is None:
+        return fn()
+    plan.set_views(call.views[0], call.views[1], src.shape[0], src.shape[1])
+    try:
+        return fn()
+    finally:
+        plan.set_views(None)
+
+
+def _refuse_second_backward(owner, leases):
+    if not leases or leases[0].plan is None:
+        raise RuntimeError(f"{type(owner).__name__}: second backward through one forward -- its workspace was handed back "
+                           "after the first (retain_graph / double backward are not supported)")
+
+
+def _direct_grads(owner, params, overwrite=True):
     """-> (direct, accumulate): does this backward write into the parameters' .grad, and does it add to them?
-    ``owner.direct_grads``: False = temporaries handed to autograd; True = overwrite .grad (one forward per step);
-    "accumulate" = add to .grad in the library (any number of forwards between two zeroings of the buffer)."""
+    ``owner.direct_grads``: False = temporaries handed to autograd; True = the library OVERWRITES .grad -- valid while this
+    is the only forward of the step that uses these parameters, so a caller whose forwards are chained through their state
+    passes ``overwrite=False`` and gets temporaries; "accumulate" = it adds (CSN_GRAD_ACCUMULATE: the bits of autograd's
+    p.grad += g), for any number of forwards between two zeroings of the buffer."""
     mode = owner.direct_grads
-    if not mode or not all(p.grad is not None and p.grad.is_contiguous() and p.grad.dtype == torch.float32 for p in params):
+    accumulate = mode == "accumulate"
+    if not mode or not (accumulate or overwrite) or not all(p.grad is not None and p.grad.is_contiguous() and
+                                                            p.grad.dtype == torch.float32 for p in params):
         return False, False
-    return True, mode == "accumulate"
+    return True, accumulate
+
+
+def _grad_targets(params, direct):
+    """Where a backward writes the parameter gradients: straight into the parameters' .grad (the views into the trainer's
+    flat buffer: no temporaries, no accumulation pass), or into temporaries handed to autograd."""
+    return [p.grad for p in params] if direct else [torch.empty_like(p) for p in params]
+
+
+def _training(x, h0, c0, params):
+    """Is a backward coming?  (Grad mode is off inside Function.forward, so it is decided by the entry point.)"""
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, h0, c0, *params))
 
 
 def _dropout_p(owner):
@@ -80,63 +172,55 @@ def _draw_dropout(owner):
     return p, (hi << 32) | lo, int(sub)
 
 
-def _set_dropout(plan, drop):
-    """On every forward and backward: plans are shared between calls (a plan without the bit takes p = 0 only)."""
-    if drop is None:
-        plan.set_dropout(0.0)
-    else:
-        plan.set_dropout(*drop)
+def _adopt_lstm(module, input_size, hidden_size, num_layers, compute_dtype, dropout, bidirectional):
+    """The attributes HipLSTM and BiLSTM share, the parameters of a reference nn.LSTM (same init, key names and order) and
+    an empty plan pool."""
+    module.input_size, module.hidden_size, module.num_layers = input_size, hidden_size, num_layers
+    module.compute_dtype = compute_dtype
+    module.dropout, module.dropout_subsequence = dropout, None
+    ref = nn.LSTM(input_size, hidden_size, num_layers=num_layers, batch_first=True, bidirectional=bidirectional)
+    for name, p in ref.named_parameters():
+        module.register_parameter(name, nn.Parameter(p.detach().clone()))
+    module._plans = _PlanPool()
 
 
 class _LstmFunction(torch.autograd.Function):
-    """Stacked LSTM over libcsn_hip.  A training forward keeps its state in a workspace that stays
-    checked out until the matching backward has run, so several forwards (e.g. the multi-crop views of
-    the DINO trainer) can be outstanding at once."""
+    """Stacked LSTM over libcsn_hip: (x, h0, c0, params) -> (y_last, y_all, h_n, c_n), the ones ``call.outputs`` does not
+    take as empty placeholders.  A training forward keeps its state in a workspace that stays checked out until the
+    matching backward has run, so several forwards (e.g. the multi-crop views of the DINO trainer) can be outstanding at
+    once.  The entry points differ in their _Call alone: HipLSTM.forward takes y_last (y_all with want_all),
+    forward_views y_last of the windowed rows on a CSN_LSTM_STATE plan, LSTM.forward y_all and the final state and never
+    lets the library overwrite .grad."""
 
     @staticmethod
-    def forward(ctx, x, owner, want_all, training, drop, L, *params):
-        w_ih, w_hh, b_ih, b_hh = params[0:L], params[L:2 * L], params[2 * L:3 * L], params[3 * L:4 * L]
-        plan = owner._checkout(x.shape[0], x.shape[1], x.device, training, dropout=drop is not None)
-        _set_dropout(plan, drop)
-        ctx.drop = drop                     # kept with the node: the backward runs with the mask of its forward
-        y_last, y_all = plan.forward(x, w_ih, w_hh, b_ih, b_hh, want_all=want_all)
-        ctx.lease, ctx.L, ctx.want_all = _Lease(plan), L, want_all
-        ctx.owner = owner
-        ctx.need_dx = x.requires_grad
+    def forward(ctx, x, h0, c0, owner, call, L, *params):
+        plan = owner._checkout(call.B, call.T, x.device, call.training, dropout=call.drop is not None, state=call.state_plan)
+        got = _armed(plan, call, lambda: plan.forward(x, *(params[g * L:(g + 1) * L] for g in range(4)), want_all=call.outputs[1],
+                                                      h0=h0, c0=c0, want_state=call.outputs[2]),
+                     src=x if call.views is not None else None)
+        ctx.lease, ctx.owner, ctx.call, ctx.L, ctx.param_like = _Lease(plan), owner, call, L, params
+        ctx.need = tuple(t is not None and t.requires_grad for t in (x, h0, c0))
         ctx.x_shape = x.shape
-        ctx.param_like = params
-        if not training:
+        if not call.training:
             ctx.lease.release()
-        if want_all:
-            return y_last, y_all
-        return y_last, y_last.new_empty(0)
+        return tuple(t if take else got[0].new_empty(0) for t, take in zip((got + (None, None))[:4], call.outputs))
 
     @staticmethod
-    def backward(ctx, dy_last, dy_all):
-        L, plan = ctx.L, ctx.lease.plan
-        if plan is None:
-            raise RuntimeError("HipLSTM: second backward through one forward -- its workspace was handed back after the "
-                               "first (retain_graph / double backward are not supported)")
-        owner = ctx.owner
-        direct, accumulate = _direct_grads(owner, ctx.param_like)
-        if direct:
-            # written straight into the parameters' .grad (the views into the trainer's flat buffer) this forward's
-            # contribution needs no temporaries and no accumulation pass.  direct_grads = True: the library OVERWRITES --
-            # valid while this is the only forward of the step that uses these parameters; "accumulate": it adds
-            # (CSN_GRAD_ACCUMULATE: the bits of autograd's p.grad += g), for any number of forwards per step
-            grads = [[p.grad for p in ctx.param_like[g * L:(g + 1) * L]] for g in range(4)]
-        else:
-            grads = [[torch.empty_like(p) for p in ctx.param_like[g * L:(g + 1) * L]] for g in range(4)]
-        dx = torch.empty(ctx.x_shape, dtype=torch.float32, device=dy_last.device) if ctx.need_dx else None
-        plan.set_grad_callback(owner.grad_ready_hook if direct else None)
-        plan.set_grad_mode(accumulate)      # on every backward: plans are shared between calls
-        _set_dropout(plan, ctx.drop)
-        plan.backward(dy_last, dy_all if ctx.want_all else None, grads, dx=dx)
+    def backward(ctx, *dys):
+        owner, call, L, params = ctx.owner, ctx.call, ctx.L, ctx.param_like
+        _refuse_second_backward(owner, (ctx.lease,))
+        plan = ctx.lease.plan
+        direct, accumulate = _direct_grads(owner, params, call.overwrite)
+        grads = _grad_targets(params, direct)
+        state_shape = (L, plan.desc.B, plan.desc.H)
+        dx, dh0, dc0 = (torch.empty(shape, dtype=torch.float32, device=params[0].device) if need else None
+                        for need, shape in zip(ctx.need, (ctx.x_shape, state_shape, state_shape)))
+        dy_last, dy_all, dh_n, dc_n = (dy if take else None for dy, take in zip(dys, call.outputs))
+        _armed(plan, call, lambda: plan.backward(dy_last, dy_all, [grads[g * L:(g + 1) * L] for g in range(4)], dx=dx,
+                                                 dh_n=dh_n, dc_n=dc_n, dh0=dh0, dc0=dc0),
+               grad=(owner.grad_ready_hook if direct else None, accumulate))
         ctx.lease.release()
-        if direct:
-            return (dx, None, None, None, None, None, *([None] * (4 * L)))
-        flat = [g for group in grads for g in group]
-        return (dx, None, None, None, None, None, *flat)
+        return (dx, dh0, dc0, None, None, None, *([None] * (4 * L) if direct else grads))
 
 
 class HipLSTM(nn.Module):
@@ -160,20 +244,12 @@ class HipLSTM(nn.Module):
 
     def __init__(self, input_size, hidden_size, num_layers=1, compute_dtype=torch.bfloat16, dropout=0.0, resident=False):
         super().__init__()
-        self.input_size, self.hidden_size, self.num_layers = input_size, hidden_size, num_layers
-        self.compute_dtype = compute_dtype
         self.resident = _check_resident(type(self).__name__, resident, hidden_size)
-        self.dropout = dropout
-        _dropout_p(self)
+        _check_dropout_p(dropout)
         if dropout > 0 and num_layers == 1:
             warnings.warn("dropout option adds dropout after all but last recurrent layer, so non-zero dropout expects "
                           f"num_layers greater than 1, but got dropout={dropout} and num_layers={num_layers}")
-        self.dropout = float(dropout)
-        self.dropout_subsequence = None
-        ref = nn.LSTM(input_size, hidden_size, num_layers=num_layers, batch_first=True)   # same init + key names
-        for name, p in ref.named_parameters():
-            self.register_parameter(name, nn.Parameter(p.detach().clone()))
-        self._plans = {}        # key -> list of plans; plan.busy marks a forward awaiting its backward
+        _adopt_lstm(self, input_size, hidden_size, num_layers, compute_dtype, float(dropout), bidirectional=False)
         # set by a trainer that owns the gradient buffers (trainer.DistillTrainer): the backward writes each parameter's
         # gradient straight into its .grad and calls grad_ready_hook(layer) as soon as a layer's gradients are enqueued
         # direct_grads: False = temporaries; True = .grad is overwritten (one forward per step); "accumulate" = .grad is
@@ -186,21 +262,15 @@ class HipLSTM(nn.Module):
         state = self._STATE_PLANS if state is None else bool(state)
         key = ((B, T, str(device), bool(training), self.compute_dtype) + (("dropout plan",) if dropout else ()) +
                (("state plan",) if state != self._STATE_PLANS else ()) + (("resident plan",) if self.resident else ()))
-        pool = self._plans.setdefault(key, [])
-        for plan in pool:
-            if not plan.busy:
-                return plan
-        idle = [(k, pl) for k, lst in self._plans.items() for pl in lst if not pl.busy and k != key]
-        while len(idle) >= self.MAX_IDLE_PLANS:
-            k, pl = idle.pop(0)
-            self._plans[k].remove(pl)
-        plan = cabi.LstmPlan(B, T, self.input_size, self.hidden_size, self.num_layers, self.compute_dtype, device,
-                             training=training, state=state, dropout=dropout, resident=self.resident)
-        pool.append(plan)
-        return plan
+        return self._plans.checkout(key, lambda: cabi.LstmPlan(
+            B, T, self.input_size, self.hidden_size, self.num_layers, self.compute_dtype, device, training=training, state=state,
+            dropout=dropout, resident=self.resident), self.MAX_IDLE_PLANS)
 
     def all_plans(self):
-        return [pl for lst in self._plans.values() for pl in lst]
+        return self._plans.all()
+
+    def _flat_params(self):
+        return [getattr(self, f"{n}_l{k}") for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh") for k in range(self.num_layers)]
 
     def forward_views(self, x, views, lengths):
         """Input windows: ``x`` is a SOURCE [S, Tsrc, I]; row b of the LSTM batch is ``x[rows[b], starts[b]:starts[b] +
@@ -210,20 +280,17 @@ class HipLSTM(nn.Module):
         views of a batch are ONE recurrence pass.  No gradient reaches x (``x.requires_grad`` raises)."""
         _dropout_p(self)
         rows, starts, lengths = _check_views("HipLSTM", x, views, lengths, self.input_size)
-        L = self.num_layers
-        params = [getattr(self, f"{n}_l{k}") for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh") for k in range(L)]
-        training = torch.is_grad_enabled() and any(p.requires_grad for p in params)
-        return _LstmViewsFunction.apply(x, self, training, (rows, starts), lengths, _draw_dropout(self), L, *params)
+        params = self._flat_params()
+        call = _Call(x, _training(None, None, None, params), _draw_dropout(self), lengths, (rows, starts), state_plan=True)
+        return _LstmFunction.apply(x, None, None, self, call, self.num_layers, *params)[0]
 
     def forward(self, x, want_all=False):
         _dropout_p(self)
         if not x.is_cuda:
             raise cabi.CsnError("HipLSTM runs on the GPU only (no CPU fallback); move the module and input to cuda")
-        L = self.num_layers
-        params = [getattr(self, f"{n}_l{k}") for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh") for k in range(L)]
-        # (grad mode is off inside Function.forward, so "is a backward coming" is decided here)
-        training = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))
-        y_last, y_all = _LstmFunction.apply(x, self, want_all, training, _draw_dropout(self), L, *params)
+        params = self._flat_params()
+        call = _Call(x, _training(x, None, None, params), _draw_dropout(self), outputs=(True, bool(want_all), False, False))
+        y_last, y_all, _, _ = _LstmFunction.apply(x, None, None, self, call, self.num_layers, *params)
         return (y_all, y_last) if want_all else y_last
 
 
@@ -243,115 +310,6 @@ def _check_views(name, x, views, lengths, input_size):
     if len(rows) != len(starts) or not rows:
         raise ValueError(f"{name}: views = (rows, starts) with {len(rows)} rows and {len(starts)} starts")
     return tuple(rows), tuple(starts), _check_lengths(name, lengths, len(rows), x.shape[1])
-
-
-def _run_views(plan, x, views, lengths, call):
-    """call() between setting the windows and lengths of a pooled plan and clearing the windows again."""
-    plan.set_lengths(lengths)
-    plan.set_views(views[0], views[1], x.shape[0], x.shape[1])
-    try:
-        return call()
-    finally:
-        plan.set_views(None)
-
-
-class _LstmViewsFunction(torch.autograd.Function):
-    """HipLSTM.forward_views: (source x, params) -> y_last of the windowed rows, on a CSN_LSTM_STATE plan keyed by
-    (B', T' = max(lengths)).  x gets no gradient; the parameter gradients go where _LstmFunction's go."""
-
-    @staticmethod
-    def forward(ctx, x, owner, training, views, lengths, drop, L, *params):
-        w_ih, w_hh, b_ih, b_hh = params[0:L], params[L:2 * L], params[2 * L:3 * L], params[3 * L:4 * L]
-        plan = owner._checkout(len(lengths), max(1, max(lengths)), x.device, training, dropout=drop is not None, state=True)
-        _set_dropout(plan, drop)
-        ctx.drop, ctx.lengths = drop, lengths
-        y_last, _ = _run_views(plan, x, views, lengths, lambda: plan.forward(x, w_ih, w_hh, b_ih, b_hh))
-        ctx.lease, ctx.L, ctx.owner = _Lease(plan), L, owner
-        ctx.param_like = params
-        if not training:
-            ctx.lease.release()
-        return y_last
-
-    @staticmethod
-    def backward(ctx, dy_last):
-        L, plan = ctx.L, ctx.lease.plan
-        if plan is None:
-            raise RuntimeError("HipLSTM: second backward through one forward -- its workspace was handed back after the "
-                               "first (retain_graph / double backward are not supported)")
-        owner = ctx.owner
-        direct, accumulate = _direct_grads(owner, ctx.param_like)
-        if direct:
-            grads = [[p.grad for p in ctx.param_like[g * L:(g + 1) * L]] for g in range(4)]
-        else:
-            grads = [[torch.empty_like(p) for p in ctx.param_like[g * L:(g + 1) * L]] for g in range(4)]
-        plan.set_grad_callback(owner.grad_ready_hook if direct else None)
-        plan.set_grad_mode(accumulate)
-        plan.set_lengths(ctx.lengths)       # the backward runs with the lengths of its forward; it reads no x, so no views
-        _set_dropout(plan, ctx.drop)
-        plan.backward(dy_last, None, grads)
-        ctx.lease.release()
-        if direct:
-            return (None, None, None, None, None, None, None, *([None] * (4 * L)))
-        return (None, None, None, None, None, None, None, *[g for group in grads for g in group])
-
-
-class _LstmStateFunction(torch.autograd.Function):
-    """Stacked LSTM with an initial state in and the final state out: (x, h0, c0, params) -> (y_all, h_n, c_n).
-    The gradients go to temporaries, or with ``direct_grads = "accumulate"`` are added straight to the parameters' .grad
-    (never the overwriting ``direct_grads = True`` form, whose "one forward per step" contract does not hold when the
-    chunks of one recording are chained through their state)."""
-
-    @staticmethod
-    def forward(ctx, x, h0, c0, owner, training, lengths, views, drop, L, *params):
-        w_ih, w_hh, b_ih, b_hh = params[0:L], params[L:2 * L], params[2 * L:3 * L], params[3 * L:4 * L]
-        run = lambda: plan.forward(x, w_ih, w_hh, b_ih, b_hh, want_all=True, h0=h0, c0=c0, want_state=True)
-        if views is not None:               # input windows: x is the source, the batch is (len(rows), max(lengths))
-            plan = owner._checkout(len(lengths), max(1, max(lengths)), x.device, training, dropout=drop is not None)
-            _set_dropout(plan, drop)
-            _, y_all, h_n, c_n = _run_views(plan, x, views, lengths, run)
-        else:
-            plan = owner._checkout(x.shape[0], x.shape[1], x.device, training, dropout=drop is not None)
-            plan.set_lengths(lengths)       # on every forward: plans are shared between calls (None = every row is T)
-            _set_dropout(plan, drop)
-            _, y_all, h_n, c_n = run()
-        ctx.drop = drop
-        ctx.lease, ctx.L, ctx.owner = _Lease(plan), L, owner
-        ctx.lengths = lengths               # kept with the node: the backward runs with the lengths of its forward
-        ctx.need = (x.requires_grad, h0 is not None and h0.requires_grad, c0 is not None and c0.requires_grad)
-        ctx.x_shape = x.shape
-        ctx.param_like = params
-        if not training:
-            ctx.lease.release()
-        return y_all, h_n, c_n
-
-    @staticmethod
-    def backward(ctx, dy_all, dh_n, dc_n):
-        L, plan = ctx.L, ctx.lease.plan
-        if plan is None:
-            raise RuntimeError("LSTM: second backward through one forward -- its workspace was handed back after the "
-                               "first (retain_graph / double backward are not supported)")
-        direct, accumulate = _direct_grads(ctx.owner, ctx.param_like)
-        direct = direct and accumulate
-        if direct:
-            grads = [[p.grad for p in ctx.param_like[g * L:(g + 1) * L]] for g in range(4)]
-        else:
-            grads = [[torch.empty_like(p) for p in ctx.param_like[g * L:(g + 1) * L]] for g in range(4)]
-        dev = ctx.param_like[0].device
-        need_dx, need_dh0, need_dc0 = ctx.need
-        d = plan.desc
-        dx = torch.empty(ctx.x_shape, dtype=torch.float32, device=dev) if need_dx else None
-        dh0 = torch.empty((L, d.B, d.H), dtype=torch.float32, device=dev) if need_dh0 else None
-        dc0 = torch.empty((L, d.B, d.H), dtype=torch.float32, device=dev) if need_dc0 else None
-        plan.set_grad_callback(ctx.owner.grad_ready_hook if direct else None)
-        plan.set_grad_mode(direct)
-        plan.set_lengths(ctx.lengths)
-        _set_dropout(plan, ctx.drop)
-        plan.backward(None, dy_all, grads, dx=dx, dh_n=dh_n, dc_n=dc_n, dh0=dh0, dc0=dc0)
-        ctx.lease.release()
-        if direct:
-            return (dx, dh0, dc0, None, None, None, None, None, None, *([None] * (4 * L)))
-        flat = [g for group in grads for g in group]
-        return (dx, dh0, dc0, None, None, None, None, None, None, *flat)
 
 
 def _forward_packed(module, name, x, hx, lengths):
@@ -387,6 +345,38 @@ def _check_lengths(name, lengths, B, T):
     if bad:
         raise ValueError(f"{name}: length {bad[0]} outside [0, T = {T}]")
     return lengths
+
+
+def _forward_stateful(module, name, dirs, function, x, hx, lengths, views, **form):
+    """The call contract of LSTM (``dirs`` = 1) and BiLSTM (2) -- views, PackedSequence, x, hx [dirs * L, B, H], lengths,
+    the dropout attribute, the device -- and then the call: ``function`` on a _Call of ``form``."""
+    if views is not None:
+        rows, starts, lengths = _check_views(name, x, views, lengths, module.input_size)
+        views = (rows, starts)
+    if isinstance(x, nn.utils.rnn.PackedSequence):
+        return _forward_packed(module, name, x, hx, lengths)
+    if x.dim() != 3:
+        raise ValueError(f"{name}: input must be batched [B, T, {module.input_size}] (batch_first); got shape "
+                         f"{list(x.shape)} (unbatched input is not supported)")
+    if x.shape[2] != module.input_size:
+        raise ValueError(f"{name}: input has {x.shape[2]} features, expected {module.input_size}")
+    B, L, H = (x.shape[0] if views is None else len(views[0])), module.num_layers, module.hidden_size
+    h0 = c0 = None
+    if hx is not None:
+        h0, c0 = hx
+        for which, t in (("h0", h0), ("c0", c0)):
+            if tuple(t.shape) != (dirs * L, B, H):
+                raise ValueError(f"{name}: {which} must be [{'2 * ' if dirs == 2 else ''}num_layers, B, hidden_size] = "
+                                 f"{[dirs * L, B, H]}, got {list(t.shape)}")
+    if views is None:
+        lengths = _check_lengths(name, lengths, B, x.shape[1])
+    _dropout_p(module)
+    if not x.is_cuda:
+        raise cabi.CsnError(f"{name} runs on the GPU only (no CPU fallback); move the module and input to cuda")
+    params = module._flat_params()
+    call = _Call(x, _training(x, h0, c0, params), _draw_dropout(module), lengths, views, **form)
+    *_, output, h_n, c_n = function.apply(x, h0, c0, module, call, L, *params)
+    return output, (h_n, c_n)
 
 
 class LSTM(HipLSTM):
@@ -429,34 +419,8 @@ class LSTM(HipLSTM):
         row b of the LSTM batch is ``x[rows[b], starts[b]:starts[b] + lengths[b]]``, read in place.  The batch is then
         B' = len(rows), T' = max(lengths): output [B', T', H], hx and (h_n, c_n) [L, B', H], all with the bits of the call
         on the gathered rows.  No gradient reaches x through views (``x.requires_grad`` raises ValueError)."""
-        if views is not None:
-            rows, starts, lengths = _check_views("LSTM", x, views, lengths, self.input_size)
-            views = (rows, starts)
-        if isinstance(x, nn.utils.rnn.PackedSequence):
-            return _forward_packed(self, "LSTM", x, hx, lengths)
-        if x.dim() != 3:
-            raise ValueError(f"LSTM: input must be batched [B, T, {self.input_size}] (batch_first); got shape "
-                             f"{list(x.shape)} (unbatched input is not supported)")
-        if x.shape[2] != self.input_size:
-            raise ValueError(f"LSTM: input has {x.shape[2]} features, expected {self.input_size}")
-        B, L, H = (x.shape[0] if views is None else len(views[0])), self.num_layers, self.hidden_size
-        h0 = c0 = None
-        if hx is not None:
-            h0, c0 = hx
-            for name, t in (("h0", h0), ("c0", c0)):
-                if tuple(t.shape) != (L, B, H):
-                    raise ValueError(f"LSTM: {name} must be [num_layers, B, hidden_size] = {[L, B, H]}, got {list(t.shape)}")
-        if views is None:
-            lengths = _check_lengths("LSTM", lengths, B, x.shape[1])
-        _dropout_p(self)
-        if not x.is_cuda:
-            raise cabi.CsnError("LSTM runs on the GPU only (no CPU fallback); move the module and input to cuda")
-        params = [getattr(self, f"{n}_l{k}") for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh") for k in range(L)]
-        training = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params) or
-                                                any(t is not None and t.requires_grad for t in (h0, c0)))
-        y_all, h_n, c_n = _LstmStateFunction.apply(x, h0, c0, self, training, lengths, views, _draw_dropout(self), L,
-                                                   *params)
-        return y_all, (h_n, c_n)
+        return _forward_stateful(self, "LSTM", 1, _LstmFunction, x, hx, lengths, views, outputs=(False, True, True, True),
+                                 overwrite=False)
 
 
 class _BiLstmFunction(torch.autograd.Function):
@@ -466,24 +430,14 @@ class _BiLstmFunction(torch.autograd.Function):
     the backward reads the halves of its gradient in place and the second direction adds its input gradient to the
     first's.  No torch op touches a [B,T,.] tensor here apart from allocating it.
 
-    ``drop`` = (p, seed, subsequence) or None: inter-layer dropout.  The plans of every layer below the top one store their
-    half of the interface tensor masked and scaled, and read their half of its gradient masked and scaled, inside the
-    layout passes they run anyway (csn_lstm_plan_set_output_dropout): one Philox stream per call covers the concatenated
-    [B,T,2H] interfaces, as torch drops each once.  ``views`` = (rows, starts) or None: x is a source tensor and layer 0's
-    two plans read their rows' windows of it in place (csn_lstm_plan_set_views); the batch is (len(rows), max(lengths))."""
+    ``call.drop`` = (p, seed, subsequence) or None: inter-layer dropout.  The plans of every layer below the top one store
+    their half of the interface tensor masked and scaled, and read their half of its gradient masked and scaled, inside the
+    layout passes they run anyway (csn_lstm_plan_set_output_dropout; _armed).  ``call.views`` = (rows, starts) or None: x is
+    a source tensor and layer 0's two plans read their rows' windows of it in place (csn_lstm_plan_set_views)."""
 
     @staticmethod
-    def _set_output_dropout(plan, drop, l, d, L, B, T, H):
-        """On every forward and backward: plans are pooled, and the top layer's are never dropped."""
-        if drop is None or l >= L - 1:
-            plan.set_output_dropout(0.0)
-        else:
-            plan.set_output_dropout(*drop, first=l * B * T * 2 * H + d * H, index_pitch=2 * H)
-
-    @staticmethod
-    def forward(ctx, x, h0, c0, owner, training, lengths, views, drop, L, *params):
-        H = owner.hidden_size
-        B, T = (x.shape[0], x.shape[1]) if views is None else (len(lengths), max(1, max(lengths)))
+    def forward(ctx, x, h0, c0, owner, call, L, *params):
+        B, T, H = call.B, call.T, owner.hidden_size
         h_n = torch.empty((2 * L, B, H), dtype=torch.float32, device=x.device)
         c_n = torch.empty((2 * L, B, H), dtype=torch.float32, device=x.device)
         leases, inp = [], x
@@ -491,46 +445,37 @@ class _BiLstmFunction(torch.autograd.Function):
             out = torch.empty((B, T, 2 * H), dtype=torch.float32, device=x.device)
             for d in range(2):
                 k = 2 * l + d
-                w = [[params[4 * k + g]] for g in range(4)]
-                plan = owner._checkout(B, T, inp.shape[2], x.device, training, reverse=d == 1)
+                plan = owner._checkout(B, T, inp.shape[2], x.device, call.training, reverse=d == 1)
                 lease = _Lease(plan)        # (at once: the next direction / layer of the same shape must take another plan)
-                run = lambda: plan.forward(inp, *w, h0=None if h0 is None else h0[k:k + 1],              # noqa: E731
-                                           c0=None if c0 is None else c0[k:k + 1], want_state=True,
-                                           y_all=out[:, :, d * H:(d + 1) * H], state_out=(h_n[k:k + 1], c_n[k:k + 1]))
+                run = lambda: plan.forward(inp, *([p] for p in params[4 * k:4 * k + 4]),                   # noqa: E731
+                                           h0=None if h0 is None else h0[k:k + 1], c0=None if c0 is None else c0[k:k + 1],
+                                           want_state=True, y_all=out[:, :, d * H:(d + 1) * H],
+                                           state_out=(h_n[k:k + 1], c_n[k:k + 1]))
                 try:
-                    plan.set_io(2 * H, 2 * H, False)
-                    _BiLstmFunction._set_output_dropout(plan, drop, l, d, L, B, T, H)
-                    if views is not None and l == 0:
-                        _run_views(plan, x, views, lengths, run)
-                    else:
-                        plan.set_lengths(lengths)
-                        run()
+                    _armed(plan, call, run, k=k, src=x if call.views is not None and l == 0 else None)
                 except BaseException:
                     for held in leases + [lease]:       # (a refused call, e.g. a window past the source: nothing stays leased)
                         held.release()
                     raise
-                if training:
+                if call.training:
                     leases.append(lease)
                 else:
                     lease.release()
             inp = out
-        ctx.leases, ctx.L, ctx.owner, ctx.lengths, ctx.drop = leases, L, owner, lengths, drop
-        ctx.need = (x.requires_grad, h0 is not None and h0.requires_grad, c0 is not None and c0.requires_grad)
-        ctx.x_shape = (B, T, x.shape[2])
+        ctx.leases, ctx.L, ctx.owner, ctx.call = leases, L, owner, call
+        ctx.need = tuple(t is not None and t.requires_grad for t in (x, h0, c0))
+        ctx.x_width = x.shape[2]
         ctx.param_like = params
         return inp, h_n, c_n
 
     @staticmethod
     def backward(ctx, dy, dh_n, dc_n):
-        L, leases = ctx.L, ctx.leases
-        if not leases or leases[0].plan is None:
-            raise RuntimeError("BiLSTM: second backward through one forward -- its workspaces were handed back after the "
-                               "first (retain_graph / double backward are not supported)")
-        B, T, _ = ctx.x_shape
-        H = ctx.owner.hidden_size
+        L, leases, call = ctx.L, ctx.leases, ctx.call
+        _refuse_second_backward(ctx.owner, leases)
+        B, T, H = call.B, call.T, ctx.owner.hidden_size
         dev = ctx.param_like[0].device
         need_dx, need_dh0, need_dc0 = ctx.need
-        grads = [torch.empty_like(p) for p in ctx.param_like]
+        grads = _grad_targets(ctx.param_like, False)
         dh0 = torch.empty((2 * L, B, H), dtype=torch.float32, device=dev) if need_dh0 else None
         dc0 = torch.empty((2 * L, B, H), dtype=torch.float32, device=dev) if need_dc0 else None
         if dy.dtype != torch.float32 or not dy.is_contiguous():
@@ -539,22 +484,17 @@ class _BiLstmFunction(torch.autograd.Function):
             dy = dy.clone()                 # (a pitched dy_all is taken on 16 bytes, and the masked load moves 16: a dense gradient
                                             # at an odd storage offset is copied once)
         for l in range(L - 1, -1, -1):
-            width = ctx.x_shape[2] if l == 0 else 2 * H
-            dinp = torch.empty((B, T, width), dtype=torch.float32, device=dev) if (l > 0 or need_dx) else None
+            dinp = torch.empty((B, T, ctx.x_width if l == 0 else 2 * H), dtype=torch.float32, device=dev) if (l > 0 or need_dx) else None
             for d in range(2):
                 k = 2 * l + d
                 plan = leases[k].plan
-                plan.set_grad_callback(None)
-                plan.set_grad_mode(False)
-                plan.set_lengths(ctx.lengths)
-                plan.set_io(2 * H, 2 * H, d == 1)       # the reverse direction adds its dx to the forward one's
-                _BiLstmFunction._set_output_dropout(plan, ctx.drop, l, d, L, B, T, H)     # the mask of its forward
-                plan.backward(None, dy[:, :, d * H:(d + 1) * H], [[grads[4 * k + g]] for g in range(4)], dx=dinp,
-                              dh_n=dh_n[k:k + 1], dc_n=dc_n[k:k + 1], dh0=None if dh0 is None else dh0[k:k + 1],
-                              dc0=None if dc0 is None else dc0[k:k + 1])
+                _armed(plan, call, lambda: plan.backward(
+                    None, dy[:, :, d * H:(d + 1) * H], [[g] for g in grads[4 * k:4 * k + 4]], dx=dinp, dh_n=dh_n[k:k + 1],
+                    dc_n=dc_n[k:k + 1], dh0=None if dh0 is None else dh0[k:k + 1], dc0=None if dc0 is None else dc0[k:k + 1]),
+                       grad=(None, False), k=k)
                 leases[k].release()
             dy = dinp
-        return (dy, dh0, dc0, None, None, None, None, None, None, *grads)
+        return (dy, dh0, dc0, None, None, None, *grads)
 
 
 class BiLSTM(nn.Module):
@@ -594,67 +534,28 @@ class BiLSTM(nn.Module):
         if dropout != 0:
             raise ValueError("BiLSTM: dropout != 0 is not supported (the inter-layer dropout of this library lives "
                              "between the layers of one plan; a bidirectional stack runs one plan per layer and direction)")
-        self.input_size, self.hidden_size, self.num_layers = input_size, hidden_size, num_layers
-        self.compute_dtype = compute_dtype
-        self.bias, self.batch_first, self.dropout, self.bidirectional, self.proj_size = True, True, 0.0, True, 0
-        self.dropout_subsequence = None
-        ref = nn.LSTM(input_size, hidden_size, num_layers=num_layers, batch_first=True, bidirectional=True)
-        for name, p in ref.named_parameters():      # same init, key names and order
-            self.register_parameter(name, nn.Parameter(p.detach().clone()))
-        self._plans = {}        # key -> list of plans; plan.busy marks a forward awaiting its backward
+        _adopt_lstm(self, input_size, hidden_size, num_layers, compute_dtype, 0.0, bidirectional=True)
+        self.bias, self.batch_first, self.bidirectional, self.proj_size = True, True, True, 0
 
     def _checkout(self, B, T, I, device, training, reverse):
         key = (B, T, I, str(device), bool(training), self.compute_dtype, bool(reverse)) + (("resident plan",) if self.resident else ())
-        pool = self._plans.setdefault(key, [])
-        for plan in pool:
-            if not plan.busy:
-                return plan
-        idle = [(k, pl) for k, lst in self._plans.items() for pl in lst if not pl.busy and k != key]
-        while len(idle) >= self.MAX_IDLE_PLANS:
-            k, pl = idle.pop(0)
-            self._plans[k].remove(pl)
-        plan = cabi.LstmPlan(B, T, I, self.hidden_size, 1, self.compute_dtype, device, training=training, state=True,
-                             reverse=reverse, resident=self.resident)
-        pool.append(plan)
-        return plan
+        return self._plans.checkout(key, lambda: cabi.LstmPlan(
+            B, T, I, self.hidden_size, 1, self.compute_dtype, device, training=training, state=True, reverse=reverse,
+            resident=self.resident), self.MAX_IDLE_PLANS)
 
     def all_plans(self):
-        return [pl for lst in self._plans.values() for pl in lst]
+        return self._plans.all()
+
+    def _flat_params(self):
+        return [getattr(self, f"{n}_l{k}{sfx}") for k in range(self.num_layers) for sfx in ("", "_reverse")
+                for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
 
     def forward(self, x, hx=None, lengths=None, views=None):
         """``views = (rows, starts)``, each B' ints, with ``lengths`` (B' ints, required): x is a SOURCE [S, Tsrc, I] and
         row b of the batch is ``x[rows[b], starts[b]:starts[b] + lengths[b]]``, read in place by layer 0's two plans.  The
         batch is then B' = len(rows), T' = max(lengths): output [B', T', 2H], hx and (h_n, c_n) [2L, B', H], all with the
         bits of the call on the gathered rows.  No gradient reaches x through views (``x.requires_grad`` raises)."""
-        if views is not None:
-            rows, starts, lengths = _check_views("BiLSTM", x, views, lengths, self.input_size)
-            views = (rows, starts)
-        if isinstance(x, nn.utils.rnn.PackedSequence):
-            return _forward_packed(self, "BiLSTM", x, hx, lengths)
-        if x.dim() != 3:
-            raise ValueError(f"BiLSTM: input must be batched [B, T, {self.input_size}] (batch_first); got shape "
-                             f"{list(x.shape)} (unbatched input is not supported)")
-        if x.shape[2] != self.input_size:
-            raise ValueError(f"BiLSTM: input has {x.shape[2]} features, expected {self.input_size}")
-        B, L, H = (x.shape[0] if views is None else len(views[0])), self.num_layers, self.hidden_size
-        h0 = c0 = None
-        if hx is not None:
-            h0, c0 = hx
-            for name, t in (("h0", h0), ("c0", c0)):
-                if tuple(t.shape) != (2 * L, B, H):
-                    raise ValueError(f"BiLSTM: {name} must be [2 * num_layers, B, hidden_size] = {[2 * L, B, H]}, got "
-                                     f"{list(t.shape)}")
-        if views is None:
-            lengths = _check_lengths("BiLSTM", lengths, B, x.shape[1])
-        _dropout_p(self)
-        if not x.is_cuda:
-            raise cabi.CsnError("BiLSTM runs on the GPU only (no CPU fallback); move the module and input to cuda")
-        params = [getattr(self, f"{n}_l{k}{sfx}") for k in range(L) for sfx in ("", "_reverse")
-                  for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
-        training = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params) or
-                                                any(t is not None and t.requires_grad for t in (h0, c0)))
-        output, h_n, c_n = _BiLstmFunction.apply(x, h0, c0, self, training, lengths, views, _draw_dropout(self), L, *params)
-        return output, (h_n, c_n)
+        return _forward_stateful(self, "BiLSTM", 2, _BiLstmFunction, x, hx, lengths, views, bi=(self.num_layers, self.hidden_size))
 
 
 class Model(nn.Module):
