@@ -117,6 +117,13 @@ def build_parser(flavour=PERILS):
                         'to one)')
     p.add_argument('--fused_optimizer', action='store_true',
                    help='adamw / adam / lars as fused HIP steps over the flat parameter buffer (rmsprop always is)')
+    p.add_argument('--clip_grad_norm', type=float, default=0.0,
+                   help='clip the global gradient norm to this value once per optimiser step (the coefficient of '
+                        'torch.nn.utils.clip_grad_norm_, decided on the device); 0 = off')
+    p.add_argument('--skip_nonfinite', action='store_true',
+                   help='do not take an optimiser step whose gradient holds a NaN or an Inf (parameters and optimiser state '
+                        'stay as they were); the epoch line counts such steps; needs a flat optimiser (rmsprop, or '
+                        '--fused_optimizer)')
     p.add_argument('--fused_loss', action='store_true',
                    help='featdist / kd / barlow / contrastive: loss value and gradient from fused HIP calls in float64 '
                         '(csn_distill_loss, csn_barlow_corr + csn_barlow_grad, csn_contrastive_lse + csn_contrastive_grad) '
@@ -190,6 +197,8 @@ def main(argv=None, flavour=PERILS):
     FLAGS, _unparsed = build_parser(flavour).parse_known_args(argv)
     if FLAGS.accum_steps < 1 or FLAGS.batch_size % FLAGS.accum_steps != 0:
         raise SystemExit(f"--accum_steps {FLAGS.accum_steps}: must be >= 1 and divide --batch_size {FLAGS.batch_size}")
+    if not FLAGS.clip_grad_norm >= 0:
+        raise SystemExit(f"--clip_grad_norm {FLAGS.clip_grad_norm}: must be >= 0 (0 = off)")
     rank, world, local = init_distributed()
     is_main = rank == 0
     if is_main:
@@ -239,7 +248,8 @@ def main(argv=None, flavour=PERILS):
     trainer = DistillTrainer(model, sos, loss=FLAGS.loss, lr=FLAGS.learning_rate, optimizer=FLAGS.optimizer,
                              nepochs=max(FLAGS.num_epochs, HyperParams.warmup_teacher_temp_epochs + 1), kd_params=kd,
                              accum_steps=FLAGS.accum_steps, fused_optimizer=FLAGS.fused_optimizer,
-                             fused_loss=FLAGS.fused_loss, contrastive_temperature=FLAGS.contrastive_temperature)
+                             fused_loss=FLAGS.fused_loss, contrastive_temperature=FLAGS.contrastive_temperature,
+                             max_grad_norm=FLAGS.clip_grad_norm or None, skip_nonfinite=FLAGS.skip_nonfinite)
 
     def batches(idx, epoch, shuffle, multiple_of=1):
         shard = idx[shard_indices(len(idx), epoch, FLAGS.seed, rank, world, shuffle=shuffle).to(device)]
@@ -266,6 +276,7 @@ def main(argv=None, flavour=PERILS):
                                              **loss_kw(b)))
         trainer.check_device_status()      # per epoch: a timed-out in-kernel hand-off must not pass silently
         epoch_loss = float(torch.stack(losses).mean().item())                    # one sync per epoch, not per step
+        skipped = f" skipped {trainer.skipped_steps()}" if FLAGS.skip_nonfinite else ""       # (steps not taken so far)
         if EPOCH % FLAGS.validation_frequency == 0 and EPOCH > 0:
             model.eval()
             if FLAGS.compat_label_bug:
@@ -323,9 +334,9 @@ def main(argv=None, flavour=PERILS):
             if is_main:
                 print(f"Overall Recall :{r['Recall_Total']} Overall Precision: {r['Precision_Total']} top1: {r['top1']:.4f}")
                 print(f"EPOCH {EPOCH} train_loss: {round(epoch_loss, 6)} val_loss: {round(val_epoch_loss, 6)} "
-                      f"T: {HyperParams.T} best val loss: {best_val_loss} on epoch: {best_val_loss_epoch}")
+                      f"T: {HyperParams.T} best val loss: {best_val_loss} on epoch: {best_val_loss_epoch}{skipped}")
         elif is_main:
-            print(f"EPOCH {EPOCH} train_loss: {round(epoch_loss, 6)} T: {HyperParams.T}")
+            print(f"EPOCH {EPOCH} train_loss: {round(epoch_loss, 6)} T: {HyperParams.T}{skipped}")
         history.append(epoch_loss)
     if is_main and best_val_loss is None and flavour.name == "perils":
         torch.save(model.state_dict(), f"{FLAGS.log_dir}/lstm_dinov2_best_loss.pth")

@@ -35,6 +35,12 @@ def build_parser():
     p.add_argument('--weight_decay', type=float, default=0.04)
     p.add_argument('--weight_decay_end', type=float, default=0.4)
     p.add_argument('--clip_grad', type=float, default=3.0)
+    p.add_argument('--clip_grad_norm', type=float, default=0.0,
+                   help='clip the GLOBAL gradient norm to this value (torch.nn.utils.clip_grad_norm_\'s coefficient, decided '
+                        'on the device) in front of the per-tensor --clip_grad; 0 = off; needs --fused_optimizer')
+    p.add_argument('--skip_nonfinite', action='store_true',
+                   help='do not take an optimiser step whose gradient holds a NaN or an Inf, as fp16_scaler.step(optimizer) '
+                        'did in the reference; the epoch line counts such steps; needs --fused_optimizer')
     p.add_argument('--batch_size_per_gpu', default=8, type=int)
     p.add_argument('--epochs', default=200, type=int)
     p.add_argument('--freeze_last_layer', default=1, type=int)
@@ -95,6 +101,10 @@ def main(argv=None):
     FLAGS, _ = parser.parse_known_args(argv)
     if FLAGS.per_sample_crops and not FLAGS.fused_views:
         parser.error("--per_sample_crops needs --fused_views")
+    if (FLAGS.clip_grad_norm or FLAGS.skip_nonfinite) and not FLAGS.fused_optimizer:
+        parser.error("--clip_grad_norm and --skip_nonfinite work through the flat AdamW step: they need --fused_optimizer")
+    if not FLAGS.clip_grad_norm >= 0:
+        parser.error("--clip_grad_norm must be >= 0 (0 = off)")
     rank, world, local = init_distributed()
     device = torch.device("cuda", local)
     torch.manual_seed(FLAGS.seed)
@@ -139,7 +149,8 @@ def main(argv=None):
     not_reg = [p for n, p in student.named_parameters() if p.requires_grad and (n.endswith(".bias") or p.ndim == 1)]
     if FLAGS.fused_optimizer:       # the clip loop and the two-group AdamW below as three launches (flat_optim.FlatAdamW)
         from cerebralsignalnetworks_amd.flat_optim import FlatAdamW
-        optimizer = FlatAdamW(grads, no_decay=not_reg, clip=FLAGS.clip_grad or None)
+        optimizer = FlatAdamW(grads, no_decay=not_reg, clip=FLAGS.clip_grad or None,
+                              max_grad_norm=FLAGS.clip_grad_norm or None, skip_nonfinite=FLAGS.skip_nonfinite)
     else:
         optimizer = torch.optim.AdamW([{"params": regularized}, {"params": not_reg, "weight_decay": 0.}])
     per_rank = len(shard_indices(len(train_idx), 0, FLAGS.seed, rank, world))
@@ -190,7 +201,8 @@ def main(argv=None):
             ema_update(student, teacher, momentum_schedule[it])
             losses.append(loss.detach())
         epoch_loss = float(torch.stack(losses).mean().item())
-        check_device_status(student)       # per epoch (sticky word): student and teacher share no plans
+        # per epoch (sticky word): student and teacher share no plans; a skipped non-finite step is not a diverged run
+        check_device_status(student, tolerate_nonfinite=FLAGS.skip_nonfinite)
         check_device_status(teacher)
         history.append(epoch_loss)
         if rank == 0:
@@ -202,7 +214,8 @@ def main(argv=None):
                 torch.save(save_dict, os.path.join(FLAGS.log_dir, f'checkpoint{EPOCH:04}.pth'))
             with (Path(FLAGS.log_dir) / "log.txt").open("a") as f:
                 f.write(json.dumps({"train_loss": epoch_loss, "train_lr": float(lr_schedule[it]), "epoch": EPOCH}) + "\n")
-            print(f"Epoch: [{EPOCH}/{FLAGS.epochs}] loss: {epoch_loss:.6f} lr: {lr_schedule[it]:.6f}")
+            skipped = f" skipped {optimizer.skipped_steps()}" if FLAGS.skip_nonfinite else ""
+            print(f"Epoch: [{EPOCH}/{FLAGS.epochs}] loss: {epoch_loss:.6f} lr: {lr_schedule[it]:.6f}{skipped}")
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

@@ -7,4 +7,4 @@ from .lstm_model import Model, LSTMModel, CustomModel, LSTM, BiLSTM  # noqa: F40
 from .losses import (CosineSimilarityLoss, FeatureDistributionLoss, loss_fn_kd,  # noqa: F401
                      BarlowTwinsLoss, ContrastiveLoss, HyperParams)
 from .retrieval import evaluate, l2_search  # noqa: F401
-from .flat_optim import FlatAdamW, FlatLARS, flat_clip_gradients  # noqa: F401
+from .flat_optim import FlatAdamW, FlatLARS, flat_clip_gradients, flat_clip_grad_norm_  # noqa: F401

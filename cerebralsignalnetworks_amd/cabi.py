@@ -113,6 +113,15 @@ SIGNATURES = {
                                _c_void_p]),
     "csn_lars_step": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_i64, _c_int, _c_void_p, _c_double, _c_double,
                                _c_double, _c_double, _c_void_p]),
+    "csn_grad_guard_scratch_bytes": (_c_size_t, [_c_i64]),
+    "csn_grad_guard": (_c_int, [_c_void_p, _c_i64, _c_double, _c_void_p, _c_void_p, _c_void_p]),
+    "csn_rmsprop_step_guarded": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_i64, _c_float, _c_float, _c_float, _c_void_p,
+                                          _c_void_p]),
+    "csn_adam_step_guarded": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_i64, _c_int, _c_void_p, _c_i64,
+                                       _c_double, _c_double, _c_double, _c_double, _c_double, _c_int, _c_double, _c_void_p,
+                                       _c_void_p, _c_void_p]),
+    "csn_lars_step_guarded": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_i64, _c_int, _c_void_p, _c_double, _c_double,
+                                       _c_double, _c_double, _c_void_p, _c_void_p]),
     "csn_barlow_offdiag_sqsum": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_void_p]),
     "csn_barlow_saved_bytes": (_c_size_t, [_c_int]),
     "csn_barlow_scratch_bytes": (_c_size_t, [_c_int, _c_int]),
@@ -815,6 +824,80 @@ def lars_step(table, params, grads, mu, lr, weight_decay, momentum, eta):
     with torch.cuda.device(params.device):
         _check(load().csn_lars_step(_ptr(params), _ptr(grads), _ptr(mu), table.n, table.nseg, _ptr(table.buf), float(lr),
                                     float(weight_decay), float(momentum), float(eta), _stream()))
+
+
+# ---- global-norm clip and non-finite skip on the device (csn_grad_guard and the guarded steps) ---------------------------------
+class StepGuard:
+    """Owner of one csnStepGuard record (16 bytes, zeroed once here) and of the scratch of csn_grad_guard.  ``norm`` and
+    ``scale`` are 0-dim float32 DEVICE views into the record (no host read); ``finite`` a 0-dim int32 view;
+    ``skipped()`` is one blocking host read of the count of non-finite buffers measured so far."""
+
+    def __init__(self, device):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise CsnError("libcsn_hip needs device tensors (no CPU fallback)")
+        self.device = device
+        self.record = torch.zeros(4, dtype=torch.float32, device=device)       # (torch allocations are 256-B aligned)
+        self.norm, self.scale = self.record[0], self.record[1]
+        words = self.record.view(torch.int32)
+        self.finite, self._skipped = words[2], words[3]
+        self.scratch, self._n = None, 0
+
+    def measure(self, grads, max_norm=None):
+        """Enqueues csn_grad_guard over the contiguous float32 device buffer ``grads`` on the current stream;
+        ``max_norm`` None / inf: measure and gate only.  Returns ``self.norm``."""
+        _need_cuda(grads)
+        if grads.dtype != torch.float32 or not grads.is_contiguous() or grads.device != self.device:
+            raise CsnError("StepGuard: the gradient buffer must be contiguous float32 on the guard's device")
+        lib, n = load(), grads.numel()
+        if self.scratch is None or self._n != n:
+            nbytes = lib.csn_grad_guard_scratch_bytes(n)
+            if nbytes == 0:
+                raise CsnError(f"libcsn_hip: {lib.csn_last_error().decode()}")
+            self.scratch, self._n = torch.empty(nbytes // 8, dtype=torch.float64, device=self.device), n
+        with torch.cuda.device(self.device):
+            _check(lib.csn_grad_guard(_ptr(grads), n, float("inf") if max_norm is None else float(max_norm),
+                                      _ptr(self.scratch), _ptr(self.record), _stream()))
+        return self.norm
+
+    def skipped(self):
+        return int(self._skipped.item())
+
+    def set_skipped(self, count):
+        self._skipped.fill_(int(count))
+
+
+def rmsprop_step_guarded(guard, params_flat, grads_flat, square_avg_flat, lr, alpha=0.99, eps=1e-8):
+    """rmsprop_step behind ``guard`` (a StepGuard measured earlier on this stream): the step of scale * g, or nothing."""
+    _need_cuda(params_flat, grads_flat, square_avg_flat)
+    n = params_flat.numel()
+    assert grads_flat.numel() == n and square_avg_flat.numel() == n
+    assert params_flat.dtype == grads_flat.dtype == square_avg_flat.dtype == torch.float32
+    with torch.cuda.device(params_flat.device):
+        _check(load().csn_rmsprop_step_guarded(_ptr(params_flat), _ptr(grads_flat), _ptr(square_avg_flat), n, float(lr),
+                                               float(alpha), float(eps), _ptr(guard.record), _stream()))
+
+
+def adam_step_guarded(guard, table, params, grads, exp_avg, exp_avg_sq, step, lr, beta1, beta2, eps, weight_decay, decoupled,
+                      clip=None, norms_out=None):
+    """adam_step behind ``guard``; ``step`` counts the calls, skipped ones included; with ``clip`` the per-tensor clip
+    works on the globally scaled gradient and ``norms_out`` holds ITS norms (untouched by a skipped step)."""
+    _flat_check(table, params, grads, exp_avg, exp_avg_sq)
+    _need_cuda(norms_out)
+    with torch.cuda.device(params.device):
+        _check(load().csn_adam_step_guarded(_ptr(params), _ptr(grads), _ptr(exp_avg), _ptr(exp_avg_sq), table.n, table.nseg,
+                                            _ptr(table.buf), int(step), float(lr), float(beta1), float(beta2), float(eps),
+                                            float(weight_decay), int(bool(decoupled)), float(clip or 0.0), _ptr(norms_out),
+                                            _ptr(guard.record), _stream()))
+
+
+def lars_step_guarded(guard, table, params, grads, mu, lr, weight_decay, momentum, eta):
+    """lars_step behind ``guard``."""
+    _flat_check(table, params, grads, mu)
+    with torch.cuda.device(params.device):
+        _check(load().csn_lars_step_guarded(_ptr(params), _ptr(grads), _ptr(mu), table.n, table.nseg, _ptr(table.buf),
+                                            float(lr), float(weight_decay), float(momentum), float(eta), _ptr(guard.record),
+                                            _stream()))
 
 
 def barlow_offdiag_sqsum(c):

@@ -112,14 +112,31 @@ extern "C" int csn_barlow_offdiag_sqsum(const float* c, int D, float* out, csnSt
 // with that call's defaults (alpha 0.99, eps 1e-8, no momentum, not centred, no weight decay):
 //     v <- alpha v + (1 - alpha) g^2 ;   p <- p - lr g / (sqrt(v) + eps)
 // One pass over 3 x n floats in, 2 x n out (torch's multi-tensor path: five kernels per step).
+//
+// GUARD (csn_rmsprop_step_guarded): the step behind a csn_grad_guard record.  Non-finite: nothing is
+// written.  Otherwise every g is read as g' = fl32(scale g) -- the value of a call, a statement of its own, so
+// -ffp-contract=on cannot fuse that product into the multiply-adds below -- and the arithmetic is the unguarded one.
 namespace csn {
+template <bool GUARD>
 __global__ void __launch_bounds__(256) rmsprop_flat_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ v,
-                                                          int64_t n, float lr, float alpha, float eps) {
+                                                          int64_t n, float lr, float alpha, float eps,
+                                                          const csnStepGuard* __restrict__ guard) {
+  float gs = 1.0f;
+  if constexpr (GUARD) {
+    if (guard->finite == 0u) return;
+    gs = guard->scale;
+  }
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   const int64_t n4 = n >> 2;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
     float4 pv = reinterpret_cast<float4*>(p)[i];
-    const float4 gv = reinterpret_cast<const float4*>(g)[i];
+    float4 gv = reinterpret_cast<const float4*>(g)[i];
+    if constexpr (GUARD) {
+      gv.x = __fmul_rn(gs, gv.x);
+      gv.y = __fmul_rn(gs, gv.y);
+      gv.z = __fmul_rn(gs, gv.z);
+      gv.w = __fmul_rn(gs, gv.w);
+    }
     float4 vv = reinterpret_cast<float4*>(v)[i];
     vv.x = alpha * vv.x + (1.0f - alpha) * gv.x * gv.x;
     vv.y = alpha * vv.y + (1.0f - alpha) * gv.y * gv.y;
@@ -133,7 +150,8 @@ __global__ void __launch_bounds__(256) rmsprop_flat_kernel(float* __restrict__ p
     reinterpret_cast<float4*>(p)[i] = pv;
   }
   for (int64_t i = (n4 << 2) + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const float gi = g[i];
+    float gi = g[i];
+    if constexpr (GUARD) gi = __fmul_rn(gs, gi);
     const float vi = alpha * v[i] + (1.0f - alpha) * gi * gi;
     v[i] = vi;
     p[i] -= lr * gi / (sqrtf(vi) + eps);
@@ -141,15 +159,31 @@ __global__ void __launch_bounds__(256) rmsprop_flat_kernel(float* __restrict__ p
 }
 }  // namespace csn
 
-extern "C" int csn_rmsprop_step(float* params, const float* grads, float* square_avg, int64_t n, float lr, float alpha,
-                                float eps, csnStream_t stream) {
-  CSN_REQUIRE(params && grads && square_avg && n > 0, "csn_rmsprop_step: null pointer or empty buffer");
+// (one body for the entry point, guard == nullptr, and its _guarded twin, which has checked the record)
+static int rmsprop_step(const char* who, float* params, const float* grads, float* square_avg, int64_t n, float lr, float alpha,
+                        float eps, const csnStepGuard* guard, csnStream_t stream) {
+  CSN_REQUIRE(params && grads && square_avg && n > 0, "%s: null pointer or empty buffer", who);
   CSN_REQUIRE(((reinterpret_cast<uintptr_t>(params) | reinterpret_cast<uintptr_t>(grads) | reinterpret_cast<uintptr_t>(square_avg)) & 15) == 0,
-              "csn_rmsprop_step: buffers must be 16-byte aligned");
+              "%s: buffers must be 16-byte aligned", who);
   int64_t blocks = (n / 4 + 255) / 256;
   if (blocks < 1) blocks = 1;
   if (blocks > 2048) blocks = 2048;
-  csn::rmsprop_flat_kernel<<<(unsigned)blocks, 256, 0, csn::as_stream(stream)>>>(params, grads, square_avg, n, lr, alpha, eps);
+  if (guard)
+    csn::rmsprop_flat_kernel<true><<<(unsigned)blocks, 256, 0, csn::as_stream(stream)>>>(params, grads, square_avg, n, lr, alpha, eps, guard);
+  else
+    csn::rmsprop_flat_kernel<false><<<(unsigned)blocks, 256, 0, csn::as_stream(stream)>>>(params, grads, square_avg, n, lr, alpha, eps, nullptr);
   CSN_LAUNCH_CHECK();
   return CSN_OK;
+}
+
+extern "C" int csn_rmsprop_step(float* params, const float* grads, float* square_avg, int64_t n, float lr, float alpha,
+                                float eps, csnStream_t stream) {
+  return rmsprop_step("csn_rmsprop_step", params, grads, square_avg, n, lr, alpha, eps, nullptr, stream);
+}
+
+extern "C" int csn_rmsprop_step_guarded(float* params, const float* grads, float* square_avg, int64_t n, float lr, float alpha,
+                                        float eps, const csnStepGuard* guard, csnStream_t stream) {
+  CSN_REQUIRE(guard != nullptr, "csn_rmsprop_step_guarded: null guard record (the unguarded entry point exists for that)");
+  CSN_REQUIRE((reinterpret_cast<uintptr_t>(guard) & 15) == 0, "csn_rmsprop_step_guarded: the guard record must be 16-byte aligned");
+  return rmsprop_step("csn_rmsprop_step_guarded", params, grads, square_avg, n, lr, alpha, eps, guard, stream);
 }

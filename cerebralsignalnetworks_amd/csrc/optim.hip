@@ -18,6 +18,12 @@
 // The intersection of segment s (elements [a, e)) with chunk c owns partial slot seg_first[s] + c - a / kChunk, so the
 // slots of a segment are contiguous and stage two adds them in a fixed order: no floating-point atomics anywhere, two
 // runs give the same bits.
+//
+// The GUARD (csn_grad_guard) is one more pass of that kind over the whole gradient buffer: it leaves
+// the global L2 norm, clip_grad_norm_'s coefficient and a finiteness flag in a 16-byte device record.  Every step kernel
+// and norm pass below is a template on GUARD: the guarded instantiation returns at once when the record says non-finite,
+// and otherwise reads g' = fl32(scale g) wherever the unguarded one reads g; the unguarded instantiation is the kernel it
+// was before.
 #include "csn_common.h"
 
 #include <math.h>
@@ -112,6 +118,25 @@ __device__ __forceinline__ void block_sum(double (&v)[Q], double (*lds)[kThreads
   __syncthreads();
 }
 
+// ---- the guard's view of a gradient element: g' = fl32(scale g), one rounding of its own (the product is the value of a
+// call, so -ffp-contract=on cannot fuse it into the multiply-add that consumes it) ----------------------------------------
+template <bool GUARD>
+__device__ __forceinline__ float guarded(float g, float gs) {
+  if constexpr (GUARD) return __fmul_rn(gs, g);
+  else return g;
+}
+
+// false: the record says "non-finite", the kernel writes nothing.  (uniform: two scalar loads per workgroup)
+template <bool GUARD>
+__device__ __forceinline__ bool guard_open(const csnStepGuard* guard, float& gs) {
+  gs = 1.0f;
+  if constexpr (GUARD) {
+    if (guard->finite == 0u) return false;
+    gs = guard->scale;
+  }
+  return true;
+}
+
 // ---- stage one of the segment norms ------------------------------------------------------------------------------------
 // PAIR = false: sum a^2.  PAIR = true: sum a^2 and sum d^2, d = b + wd a on decayed segments, b elsewhere (LARS: a = p, b = g).
 template <bool PAIR>
@@ -123,11 +148,21 @@ __device__ __forceinline__ void sq_acc(double (&acc)[PAIR ? 2 : 1], float a, flo
   }
 }
 
-template <bool PAIR>
+// GUARD: the gradient is b with PAIR (LARS), a without (Adam's per-tensor clip)
+template <bool PAIR, bool GUARD>
+__device__ __forceinline__ void sq_acc_g(double (&acc)[PAIR ? 2 : 1], float a, float b, float wd, bool decay, float gs) {
+  if constexpr (PAIR) sq_acc<PAIR>(acc, a, guarded<GUARD>(b, gs), wd, decay);
+  else sq_acc<PAIR>(acc, guarded<GUARD>(a, gs), b, wd, decay);
+}
+
+template <bool PAIR, bool GUARD>
 __global__ void __launch_bounds__(kThreads) flat_sqsum_partial_kernel(const float* __restrict__ a, const float* __restrict__ b,
-                                                                     float wd, int64_t n, Table t) {
+                                                                     float wd, int64_t n, Table t,
+                                                                     const csnStepGuard* __restrict__ guard) {
   constexpr int Q = PAIR ? 2 : 1;
   __shared__ double lds[Q][kThreads / 64];
+  float gs;
+  if (!guard_open<GUARD>(guard, gs)) return;
   const int64_t nchunks = (n + kChunk - 1) / kChunk;
   for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
     const int64_t cs = c * kChunk;
@@ -146,13 +181,13 @@ __global__ void __launch_bounds__(kThreads) flat_sqsum_partial_kernel(const floa
           const float4 av = reinterpret_cast<const float4*>(a)[i];
           float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
           if constexpr (PAIR) bv = reinterpret_cast<const float4*>(b)[i];
-          sq_acc<PAIR>(acc, av.x, bv.x, wd, decay);
-          sq_acc<PAIR>(acc, av.y, bv.y, wd, decay);
-          sq_acc<PAIR>(acc, av.z, bv.z, wd, decay);
-          sq_acc<PAIR>(acc, av.w, bv.w, wd, decay);
+          sq_acc_g<PAIR, GUARD>(acc, av.x, bv.x, wd, decay, gs);
+          sq_acc_g<PAIR, GUARD>(acc, av.y, bv.y, wd, decay, gs);
+          sq_acc_g<PAIR, GUARD>(acc, av.z, bv.z, wd, decay, gs);
+          sq_acc_g<PAIR, GUARD>(acc, av.w, bv.w, wd, decay, gs);
         }
       } else {
-        for (int64_t i = lo + threadIdx.x; i < hi; i += kThreads) sq_acc<PAIR>(acc, a[i], PAIR ? b[i] : 0.f, wd, decay);
+        for (int64_t i = lo + threadIdx.x; i < hi; i += kThreads) sq_acc_g<PAIR, GUARD>(acc, a[i], PAIR ? b[i] : 0.f, wd, decay, gs);
       }
       block_sum<Q>(acc, lds);
       if (threadIdx.x == 0) {
@@ -168,7 +203,11 @@ __global__ void __launch_bounds__(kThreads) flat_sqsum_partial_kernel(const floa
 }
 
 // ---- stage two: one wave per (segment, quantity) adds that segment's partials, lane-strided, then across the lanes -----
-__global__ void __launch_bounds__(64) flat_sqsum_final_kernel(Table t, int nseg, float* __restrict__ norms_out) {
+template <bool GUARD>
+__global__ void __launch_bounds__(64) flat_sqsum_final_kernel(Table t, int nseg, float* __restrict__ norms_out,
+                                                              const csnStepGuard* __restrict__ guard) {
+  float gs;
+  if (!guard_open<GUARD>(guard, gs)) return;       // (stage one wrote no partials)
   const int s = blockIdx.x, q = blockIdx.y;
   const int first = t.seg_first[s], last = t.seg_first[s + 1];
   double acc = 0.0;
@@ -249,8 +288,12 @@ __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, 
   p = fmaf(a.neg_step, __fdiv_rn(m, denom), p);
 }
 
+template <bool GUARD>
 __global__ void __launch_bounds__(kThreads) flat_adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                            float* __restrict__ v, int64_t n, Table t, AdamArgs a) {
+                                                            float* __restrict__ v, int64_t n, Table t, AdamArgs a,
+                                                            const csnStepGuard* __restrict__ guard) {
+  float gs;
+  if (!guard_open<GUARD>(guard, gs)) return;
   const int64_t nchunks = (n + kChunk - 1) / kChunk;
   const bool clip = a.clip > 0.0f;
   for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
@@ -274,10 +317,10 @@ __global__ void __launch_bounds__(kThreads) flat_adam_kernel(float* __restrict__
 #pragma unroll
       for (int k = 0; k < 2; ++k) {
         const int64_t i = cs / 4 + k * kThreads + threadIdx.x;
-        adam_one(pv[k].x, gv[k].x, mv[k].x, vv[k].x, a, coef, clipped, decay);
-        adam_one(pv[k].y, gv[k].y, mv[k].y, vv[k].y, a, coef, clipped, decay);
-        adam_one(pv[k].z, gv[k].z, mv[k].z, vv[k].z, a, coef, clipped, decay);
-        adam_one(pv[k].w, gv[k].w, mv[k].w, vv[k].w, a, coef, clipped, decay);
+        adam_one(pv[k].x, guarded<GUARD>(gv[k].x, gs), mv[k].x, vv[k].x, a, coef, clipped, decay);
+        adam_one(pv[k].y, guarded<GUARD>(gv[k].y, gs), mv[k].y, vv[k].y, a, coef, clipped, decay);
+        adam_one(pv[k].z, guarded<GUARD>(gv[k].z, gs), mv[k].z, vv[k].z, a, coef, clipped, decay);
+        adam_one(pv[k].w, guarded<GUARD>(gv[k].w, gs), mv[k].w, vv[k].w, a, coef, clipped, decay);
         reinterpret_cast<float4*>(m)[i] = mv[k];
         reinterpret_cast<float4*>(v)[i] = vv[k];
         reinterpret_cast<float4*>(p)[i] = pv[k];
@@ -291,7 +334,7 @@ __global__ void __launch_bounds__(kThreads) flat_adam_kernel(float* __restrict__
         const bool decay = a.has_wd && (flags & kDecayed);
         const float coef = clipped ? clip_coef(t, si, a.clip) : 1.0f;
         float pi = p[i], mi = m[i], vi = v[i];
-        adam_one(pi, g[i], mi, vi, a, coef, clipped, decay);
+        adam_one(pi, guarded<GUARD>(g[i], gs), mi, vi, a, coef, clipped, decay);
         m[i] = mi;
         v[i] = vi;
         p[i] = pi;
@@ -321,8 +364,12 @@ __device__ __forceinline__ void lars_one(float& p, float g, float& mu, const Lar
   p = fmaf(a.neg_lr, mu, p);
 }
 
+template <bool GUARD>
 __global__ void __launch_bounds__(kThreads) flat_lars_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ mu,
-                                                            int64_t n, int nseg, Table t, LarsArgs a) {
+                                                            int64_t n, int nseg, Table t, LarsArgs a,
+                                                            const csnStepGuard* __restrict__ guard) {
+  float gs;
+  if (!guard_open<GUARD>(guard, gs)) return;
   const int64_t nchunks = (n + kChunk - 1) / kChunk;
   for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
     const int64_t cs = c * kChunk;
@@ -344,10 +391,10 @@ __global__ void __launch_bounds__(kThreads) flat_lars_kernel(float* __restrict__
 #pragma unroll
       for (int k = 0; k < 2; ++k) {
         const int64_t i = cs / 4 + k * kThreads + threadIdx.x;
-        lars_one(pv[k].x, gv[k].x, mv[k].x, a, trust, scaled, decay);
-        lars_one(pv[k].y, gv[k].y, mv[k].y, a, trust, scaled, decay);
-        lars_one(pv[k].z, gv[k].z, mv[k].z, a, trust, scaled, decay);
-        lars_one(pv[k].w, gv[k].w, mv[k].w, a, trust, scaled, decay);
+        lars_one(pv[k].x, guarded<GUARD>(gv[k].x, gs), mv[k].x, a, trust, scaled, decay);
+        lars_one(pv[k].y, guarded<GUARD>(gv[k].y, gs), mv[k].y, a, trust, scaled, decay);
+        lars_one(pv[k].z, guarded<GUARD>(gv[k].z, gs), mv[k].z, a, trust, scaled, decay);
+        lars_one(pv[k].w, guarded<GUARD>(gv[k].w, gs), mv[k].w, a, trust, scaled, decay);
         reinterpret_cast<float4*>(mu)[i] = mv[k];
         reinterpret_cast<float4*>(p)[i] = pv[k];
       }
@@ -360,11 +407,64 @@ __global__ void __launch_bounds__(kThreads) flat_lars_kernel(float* __restrict__
         const bool decay = a.has_wd && (flags & kDecayed);
         const float trust = scaled ? lars_trust(t, si, nseg, a.eta) : 1.0f;
         float pi = p[i], mi = mu[i];
-        lars_one(pi, g[i], mi, a, trust, scaled, decay);
+        lars_one(pi, guarded<GUARD>(g[i], gs), mi, a, trust, scaled, decay);
         mu[i] = mi;
         p[i] = pi;
       }
     }
+  }
+}
+
+// ---- the guard: global sum of squares, norm, clip coefficient, finiteness ------------------------------------------------
+// Stage one: partials[c] = sum over chunk c of (double)g^2 -- exact products, so a partial is non-finite exactly when an
+// element of its chunk is.  Whole chunks take two 16-byte loads per thread, the last (short) one the scalar loop.
+__global__ void __launch_bounds__(kThreads) grad_guard_partial_kernel(const float* __restrict__ g, int64_t n, double* __restrict__ partials) {
+  __shared__ double lds[1][kThreads / 64];
+  const int64_t nchunks = (n + kChunk - 1) / kChunk;
+  for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
+    const int64_t cs = c * kChunk;
+    const int64_t ce = cs + kChunk < n ? cs + kChunk : n;
+    double acc[1] = {};
+    if (ce == cs + kChunk) {
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        const float4 gv = reinterpret_cast<const float4*>(g)[cs / 4 + k * kThreads + threadIdx.x];
+        sq_acc<false>(acc, gv.x, 0.f, 0.f, false);
+        sq_acc<false>(acc, gv.y, 0.f, 0.f, false);
+        sq_acc<false>(acc, gv.z, 0.f, 0.f, false);
+        sq_acc<false>(acc, gv.w, 0.f, 0.f, false);
+      }
+    } else {
+      for (int64_t i = cs + threadIdx.x; i < ce; i += kThreads) sq_acc<false>(acc, g[i], 0.f, 0.f, false);
+    }
+    block_sum<1>(acc, lds);
+    if (threadIdx.x == 0) partials[c] = acc[0];
+  }
+}
+
+__device__ __forceinline__ double read_lane(double v, int lane) {      // (lane: a compile-time constant after unrolling)
+  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane), __builtin_amdgcn_readlane(__double2loint(v), lane));
+}
+
+// Stage two, ONE wave: S = (((p_0 + p_1) + p_2) + ...) in ascending chunk order -- 64 partials per coalesced load, then a
+// chain of 64 additions that every lane performs alike on values read lane by lane (a slot behind the last chunk holds
+// +0, and x + 0 == x for the x >= 0 or NaN that a sum of squares is).  Lane 0 writes the record with ordinary stores.
+__global__ void __launch_bounds__(64) grad_guard_final_kernel(const double* __restrict__ partials, int64_t nchunks, double max_norm,
+                                                              csnStepGuard* __restrict__ guard) {
+  double sum = 0.0;
+  for (int64_t base = 0; base < nchunks; base += 64) {
+    const int64_t i = base + threadIdx.x;
+    const double v = i < nchunks ? partials[i] : 0.0;
+#pragma unroll
+    for (int j = 0; j < 64; ++j) sum += read_lane(v, j);
+  }
+  if (threadIdx.x == 0) {
+    const bool finite = isfinite(sum);
+    const double root = sqrt(sum);
+    guard->norm = (float)root;
+    guard->scale = finite ? (float)fmin(1.0, max_norm / (root + 1e-6)) : 0.0f;      // clip_grad_norm_'s clip_coef_clamped
+    guard->finite = finite ? 1u : 0u;
+    guard->skipped += finite ? 0u : 1u;
   }
 }
 
@@ -376,11 +476,15 @@ static inline bool unit_interval(double b) { return b >= 0.0 && b < 1.0; }      
 
 using namespace csn;
 
-#define CSN_FLAT_COMMON(name, table)                                                                              \
-  CSN_REQUIRE(nseg >= 1, name ": nseg must be >= 1, got %d", nseg);                                                \
-  CSN_REQUIRE(n >= nseg && n <= ((int64_t)1 << 40), name ": n = %lld elements for %d segments", (long long)n, nseg); \
-  CSN_REQUIRE(table != nullptr, name ": null segment table");                                                       \
-  CSN_REQUIRE(aligned16(table), name ": the segment table must be 16-byte aligned")
+// (name: a const char*, so that an entry point and its _guarded twin share one body and each speaks under its own name)
+#define CSN_FLAT_COMMON(name, table)                                                                                 \
+  CSN_REQUIRE(nseg >= 1, "%s: nseg must be >= 1, got %d", name, nseg);                                                \
+  CSN_REQUIRE(n >= nseg && n <= ((int64_t)1 << 40), "%s: n = %lld elements for %d segments", name, (long long)n, nseg); \
+  CSN_REQUIRE(table != nullptr, "%s: null segment table", name);                                                       \
+  CSN_REQUIRE(aligned16(table), "%s: the segment table must be 16-byte aligned", name)
+#define CSN_GUARD_RECORD(name, guard)                                                                                \
+  CSN_REQUIRE(guard != nullptr, "%s: null guard record (the unguarded entry point exists for that)", name);            \
+  CSN_REQUIRE(aligned16(guard), "%s: the guard record must be 16-byte aligned", name)
 
 extern "C" size_t csn_flat_segments_scratch_bytes(int nseg, int64_t n) {
   if (nseg < 1 || n < nseg || n > ((int64_t)1 << 40)) {
@@ -425,21 +529,35 @@ extern "C" int csn_flat_segments_prepare(const int64_t* seg_end, const int32_t* 
   return CSN_OK;
 }
 
-extern "C" int csn_flat_segment_norms(const float* a, const float* b, float weight_decay, int64_t n, int nseg, void* table,
-                                      float* norms_out, csnStream_t stream) {
-  CSN_FLAT_COMMON("csn_flat_segment_norms", table);
-  CSN_REQUIRE(a != nullptr, "csn_flat_segment_norms: null buffer");
-  CSN_REQUIRE(aligned16(a) && aligned16(b), "csn_flat_segment_norms: buffers must be 16-byte aligned");
-  const Table t = table_layout(table, nseg, n);
-  hipStream_t st = as_stream(stream);
-  if (b)
-    flat_sqsum_partial_kernel<true><<<grid_for(n), kThreads, 0, st>>>(a, b, weight_decay, n, t);
-  else
-    flat_sqsum_partial_kernel<false><<<grid_for(n), kThreads, 0, st>>>(a, nullptr, 0.0f, n, t);
+// The bodies below serve an entry point (guard == nullptr) and its _guarded twin (the record checked by the twin).
+template <bool PAIR, bool GUARD>
+static int launch_segment_norms(const float* a, const float* b, float wd, int64_t n, int nseg, const Table& t, float* norms_out,
+                                const csnStepGuard* guard, hipStream_t st) {
+  flat_sqsum_partial_kernel<PAIR, GUARD><<<grid_for(n), kThreads, 0, st>>>(a, b, wd, n, t, guard);
   CSN_LAUNCH_CHECK();
-  flat_sqsum_final_kernel<<<dim3((unsigned)nseg, b ? 2 : 1), 64, 0, st>>>(t, nseg, norms_out);
+  flat_sqsum_final_kernel<GUARD><<<dim3((unsigned)nseg, PAIR ? 2 : 1), 64, 0, st>>>(t, nseg, norms_out, guard);
   CSN_LAUNCH_CHECK();
   return CSN_OK;
+}
+
+static int segment_norms(const char* who, const float* a, const float* b, float weight_decay, int64_t n, int nseg, void* table,
+                         float* norms_out, const csnStepGuard* guard, csnStream_t stream) {
+  CSN_FLAT_COMMON(who, table);
+  CSN_REQUIRE(a != nullptr, "%s: null buffer", who);
+  CSN_REQUIRE(aligned16(a) && aligned16(b), "%s: buffers must be 16-byte aligned", who);
+  const Table t = table_layout(table, nseg, n);
+  hipStream_t st = as_stream(stream);
+  if (b) {
+    return guard ? launch_segment_norms<true, true>(a, b, weight_decay, n, nseg, t, norms_out, guard, st)
+                 : launch_segment_norms<true, false>(a, b, weight_decay, n, nseg, t, norms_out, nullptr, st);
+  }
+  return guard ? launch_segment_norms<false, true>(a, nullptr, 0.0f, n, nseg, t, norms_out, guard, st)
+               : launch_segment_norms<false, false>(a, nullptr, 0.0f, n, nseg, t, norms_out, nullptr, st);
+}
+
+extern "C" int csn_flat_segment_norms(const float* a, const float* b, float weight_decay, int64_t n, int nseg, void* table,
+                                      float* norms_out, csnStream_t stream) {
+  return segment_norms("csn_flat_segment_norms", a, b, weight_decay, n, nseg, table, norms_out, nullptr, stream);
 }
 
 extern "C" int csn_flat_clip(float* grads, int64_t n, int nseg, void* table, float clip, float* norms_out, csnStream_t stream) {
@@ -454,19 +572,19 @@ extern "C" int csn_flat_clip(float* grads, int64_t n, int nseg, void* table, flo
   return CSN_OK;
 }
 
-extern "C" int csn_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, int nseg,
-                             void* table, int64_t t, double lr, double beta1, double beta2, double eps, double weight_decay,
-                             int decoupled, double clip, float* norms_out, csnStream_t stream) {
-  CSN_FLAT_COMMON("csn_adam_step", table);
-  CSN_REQUIRE(params && grads && exp_avg && exp_avg_sq, "csn_adam_step: null pointer");
+static int adam_step(const char* who, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, int nseg,
+                     void* table, int64_t t, double lr, double beta1, double beta2, double eps, double weight_decay,
+                     int decoupled, double clip, float* norms_out, const csnStepGuard* guard, csnStream_t stream) {
+  CSN_FLAT_COMMON(who, table);
+  CSN_REQUIRE(params && grads && exp_avg && exp_avg_sq, "%s: null pointer", who);
   CSN_REQUIRE(aligned16(params) && aligned16(grads) && aligned16(exp_avg) && aligned16(exp_avg_sq),
-              "csn_adam_step: buffers must be 16-byte aligned");
-  CSN_REQUIRE(t >= 1, "csn_adam_step: step count t must be >= 1, got %lld", (long long)t);
-  CSN_REQUIRE(unit_interval(beta1) && unit_interval(beta2), "csn_adam_step: betas must lie in [0, 1), got (%g, %g)", beta1, beta2);
-  CSN_REQUIRE(lr >= 0.0 && eps >= 0.0 && weight_decay >= 0.0, "csn_adam_step: lr, eps and weight_decay must be >= 0 (%g, %g, %g)",
+              "%s: buffers must be 16-byte aligned", who);
+  CSN_REQUIRE(t >= 1, "%s: step count t must be >= 1, got %lld", who, (long long)t);
+  CSN_REQUIRE(unit_interval(beta1) && unit_interval(beta2), "%s: betas must lie in [0, 1), got (%g, %g)", who, beta1, beta2);
+  CSN_REQUIRE(lr >= 0.0 && eps >= 0.0 && weight_decay >= 0.0, "%s: lr, eps and weight_decay must be >= 0 (%g, %g, %g)", who,
               lr, eps, weight_decay);
   if (clip > 0.0) {       // per-tensor norms of the gradient first; the step scales g on the fly and leaves the buffer alone
-    int rc = csn_flat_segment_norms(grads, nullptr, 0.0f, n, nseg, table, norms_out, stream);
+    int rc = segment_norms(who, grads, nullptr, 0.0f, n, nseg, table, norms_out, guard, stream);      // (guarded: norms of g')
     if (rc) return rc;
   }
   const double bc1 = 1.0 - pow(beta1, (double)t), bc2 = 1.0 - pow(beta2, (double)t);
@@ -482,17 +600,37 @@ extern "C" int csn_adam_step(float* params, const float* grads, float* exp_avg, 
   a.clip = clip > 0.0 ? (float)clip : 0.0f;
   a.decoupled = decoupled != 0;
   a.has_wd = weight_decay != 0.0;
-  flat_adam_kernel<<<grid_for(n), kThreads, 0, as_stream(stream)>>>(params, grads, exp_avg, exp_avg_sq, n, table_layout(table, nseg, n), a);
+  const Table tb = table_layout(table, nseg, n);
+  if (guard)
+    flat_adam_kernel<true><<<grid_for(n), kThreads, 0, as_stream(stream)>>>(params, grads, exp_avg, exp_avg_sq, n, tb, a, guard);
+  else
+    flat_adam_kernel<false><<<grid_for(n), kThreads, 0, as_stream(stream)>>>(params, grads, exp_avg, exp_avg_sq, n, tb, a, nullptr);
   CSN_LAUNCH_CHECK();
   return CSN_OK;
 }
 
-extern "C" int csn_lars_step(float* params, const float* grads, float* mu, int64_t n, int nseg, void* table, double lr,
-                             double weight_decay, double momentum, double eta, csnStream_t stream) {
-  CSN_FLAT_COMMON("csn_lars_step", table);
-  CSN_REQUIRE(params && grads && mu, "csn_lars_step: null pointer");
-  CSN_REQUIRE(aligned16(params) && aligned16(grads) && aligned16(mu), "csn_lars_step: buffers must be 16-byte aligned");
-  int rc = csn_flat_segment_norms(params, grads, (float)weight_decay, n, nseg, table, nullptr, stream);
+extern "C" int csn_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, int nseg,
+                             void* table, int64_t t, double lr, double beta1, double beta2, double eps, double weight_decay,
+                             int decoupled, double clip, float* norms_out, csnStream_t stream) {
+  return adam_step("csn_adam_step", params, grads, exp_avg, exp_avg_sq, n, nseg, table, t, lr, beta1, beta2, eps, weight_decay,
+                   decoupled, clip, norms_out, nullptr, stream);
+}
+
+extern "C" int csn_adam_step_guarded(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, int nseg,
+                                     void* table, int64_t t, double lr, double beta1, double beta2, double eps,
+                                     double weight_decay, int decoupled, double clip, float* norms_out, const csnStepGuard* guard,
+                                     csnStream_t stream) {
+  CSN_GUARD_RECORD("csn_adam_step_guarded", guard);
+  return adam_step("csn_adam_step_guarded", params, grads, exp_avg, exp_avg_sq, n, nseg, table, t, lr, beta1, beta2, eps,
+                   weight_decay, decoupled, clip, norms_out, guard, stream);
+}
+
+static int lars_step(const char* who, float* params, const float* grads, float* mu, int64_t n, int nseg, void* table, double lr,
+                     double weight_decay, double momentum, double eta, const csnStepGuard* guard, csnStream_t stream) {
+  CSN_FLAT_COMMON(who, table);
+  CSN_REQUIRE(params && grads && mu, "%s: null pointer", who);
+  CSN_REQUIRE(aligned16(params) && aligned16(grads) && aligned16(mu), "%s: buffers must be 16-byte aligned", who);
+  int rc = segment_norms(who, params, grads, (float)weight_decay, n, nseg, table, nullptr, guard, stream);
   if (rc) return rc;
   LarsArgs a{};
   a.wd = (float)weight_decay;
@@ -500,7 +638,49 @@ extern "C" int csn_lars_step(float* params, const float* grads, float* mu, int64
   a.eta = (float)eta;
   a.neg_lr = (float)(-lr);
   a.has_wd = weight_decay != 0.0;
-  flat_lars_kernel<<<grid_for(n), kThreads, 0, as_stream(stream)>>>(params, grads, mu, n, nseg, table_layout(table, nseg, n), a);
+  const Table tb = table_layout(table, nseg, n);
+  if (guard)
+    flat_lars_kernel<true><<<grid_for(n), kThreads, 0, as_stream(stream)>>>(params, grads, mu, n, nseg, tb, a, guard);
+  else
+    flat_lars_kernel<false><<<grid_for(n), kThreads, 0, as_stream(stream)>>>(params, grads, mu, n, nseg, tb, a, nullptr);
+  CSN_LAUNCH_CHECK();
+  return CSN_OK;
+}
+
+extern "C" int csn_lars_step(float* params, const float* grads, float* mu, int64_t n, int nseg, void* table, double lr,
+                             double weight_decay, double momentum, double eta, csnStream_t stream) {
+  return lars_step("csn_lars_step", params, grads, mu, n, nseg, table, lr, weight_decay, momentum, eta, nullptr, stream);
+}
+
+extern "C" int csn_lars_step_guarded(float* params, const float* grads, float* mu, int64_t n, int nseg, void* table, double lr,
+                                     double weight_decay, double momentum, double eta, const csnStepGuard* guard,
+                                     csnStream_t stream) {
+  CSN_GUARD_RECORD("csn_lars_step_guarded", guard);
+  return lars_step("csn_lars_step_guarded", params, grads, mu, n, nseg, table, lr, weight_decay, momentum, eta, guard, stream);
+}
+
+// ---- the guard ------------------------------------------------------------------------------------------------------------
+extern "C" size_t csn_grad_guard_scratch_bytes(int64_t n) {
+  if (n <= 0 || n > ((int64_t)1 << 40)) {
+    fail(CSN_ERR_INVALID_ARGUMENT, "csn_grad_guard_scratch_bytes: bad n=%lld", (long long)n);
+    return 0;
+  }
+  return align_up((size_t)num_chunks(n) * 8, 16);
+}
+
+extern "C" int csn_grad_guard(const float* grads, int64_t n, double max_norm, void* scratch, csnStepGuard* guard,
+                              csnStream_t stream) {
+  CSN_REQUIRE(n > 0 && n <= ((int64_t)1 << 40), "csn_grad_guard: n = %lld elements", (long long)n);
+  CSN_REQUIRE(grads != nullptr, "csn_grad_guard: null gradient buffer");
+  CSN_REQUIRE(scratch != nullptr, "csn_grad_guard: null scratch");
+  CSN_REQUIRE(aligned16(grads) && aligned16(scratch), "csn_grad_guard: the gradient buffer and the scratch must be 16-byte aligned");
+  CSN_GUARD_RECORD("csn_grad_guard", guard);
+  CSN_REQUIRE(max_norm > 0.0, "csn_grad_guard: max_norm must be > 0 (+INFINITY: measure and gate only), got %g", max_norm);      // (false for NaN)
+  hipStream_t st = as_stream(stream);
+  double* partials = static_cast<double*>(scratch);
+  grad_guard_partial_kernel<<<grid_for(n), kThreads, 0, st>>>(grads, n, partials);
+  CSN_LAUNCH_CHECK();
+  grad_guard_final_kernel<<<1, 64, 0, st>>>(partials, num_chunks(n), max_norm, guard);
   CSN_LAUNCH_CHECK();
   return CSN_OK;
 }

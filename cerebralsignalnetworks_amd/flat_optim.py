@@ -44,10 +44,86 @@ def _plain(v):
     return v.item() if hasattr(v, "item") else v
 
 
-class _FlatOptimizer:
+def check_max_grad_norm(max_grad_norm):
+    """None (off) or a number > 0 (inf: measure and gate only), as csn_grad_guard accepts it."""
+    if max_grad_norm is None:
+        return None
+    if isinstance(max_grad_norm, bool) or not float(max_grad_norm) > 0.0:          # (False for NaN)
+        raise ValueError(f"max_grad_norm must be None or > 0, got {max_grad_norm!r}")
+    return max_grad_norm
+
+
+def guard_restatement(grads, max_norm=None):
+    """csn_grad_guard restated in torch (any device): ``(norm, scale, finite)`` as 0-dim tensors -- the float64 sum of
+    squares S, norm = float32(sqrt S), scale = float32(min(1, max_norm / (sqrt S + 1e-6))) where S is finite and 0 where it
+    is not; ``max_norm`` None: infinite (scale 1 or 0).  What DistillTrainer steps with on CPU buffers, and the oracle of
+    the device record's tests."""
+    s = grads.detach().double().pow(2).sum()
+    finite = torch.isfinite(s)
+    root = s.sqrt()
+    coef = torch.clamp((float("inf") if max_norm is None else float(max_norm)) / (root + 1e-6), max=1.0)
+    return root.float(), torch.where(finite, coef, torch.zeros_like(coef)).float(), finite
+
+
+class StepGuarded:
+    """``max_grad_norm`` / ``skip_nonfinite`` of the flat optimisers.  With either set, ``step()``
+    enqueues csn_grad_guard over the flat gradient buffer -- the global L2 norm, the coefficient of
+    ``torch.nn.utils.clip_grad_norm_`` and a finiteness flag, left in a 16-byte device record -- and then the GUARDED step,
+    which reads scale * g wherever the plain step reads g and writes NOTHING (parameters and state keep their bits) when
+    the gradient holds a NaN or an Inf: the step that ``fp16_scaler.step(optimizer)`` would not take
+    (LstmDistillation.py:606-613).  No host read: ``last_grad_norm`` is a 0-dim device tensor (the pre-clip norm of the
+    last step), ``skipped_steps()`` the one blocking read.  The gradient buffer is never written.
+
+    ``max_grad_norm`` lives in ``param_groups[0]`` and is read on every step, like ``lr``; None there means "measure and
+    gate only".  A non-finite gradient is skipped whenever the guard is on, ALSO with a finite ``max_grad_norm`` and
+    ``skip_nonfinite=False``: its coefficient is 0, and 0 * Inf would write NaN into every parameter.  ``skip_nonfinite``
+    itself only decides whether DistillTrainer's status check tolerates such steps or reports the run as diverged.
+    The guard cannot be switched on after construction (``step()`` raises); with both options off nothing changes: the
+    same launches, the same bits, the same ``state_dict`` keys."""
+
+    guard = None
+    skip_nonfinite = False
+    last_grad_norm = None
+
+    def _init_guard(self, max_grad_norm, skip_nonfinite):
+        check_max_grad_norm(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        if max_grad_norm is not None or self.skip_nonfinite:
+            self.guard = cabi.StepGuard(self.flat.flat.device)
+            self.last_grad_norm = self.guard.norm
+            self.param_groups[0]["max_grad_norm"] = max_grad_norm
+
+    def _measure(self):
+        """The measured guard of this step, or None when the guard is off."""
+        max_norm = self.param_groups[0].get("max_grad_norm")
+        if self.guard is None:
+            if max_norm is not None:
+                raise ValueError(f"{type(self).__name__}: max_grad_norm can be changed through param_groups, not switched "
+                                 "on: build the optimiser with max_grad_norm= or skip_nonfinite=")
+            return None
+        self.guard.measure(self.flat.flat, check_max_grad_norm(max_norm))
+        return self.guard
+
+    def skipped_steps(self):
+        """Steps not taken because the gradient was non-finite (one blocking host read; 0 with the guard off)."""
+        return self.guard.skipped() if self.guard is not None else 0
+
+    def _guard_state(self, sd):
+        if self.guard is not None:
+            sd.update(max_grad_norm=_plain(self.param_groups[0]["max_grad_norm"]), skip_nonfinite=self.skip_nonfinite,
+                      skipped=self.guard.skipped())
+        return sd
+
+    def _guard_load(self, sd):
+        if self.guard is not None and "skipped" in sd:
+            self.guard.set_skipped(sd["skipped"])
+            self.param_groups[0]["max_grad_norm"] = sd["max_grad_norm"]
+
+
+class _FlatOptimizer(StepGuarded):
     """What the fused optimisers share: the FlatGrads, its segment table, the re-homing check and zero_grad."""
 
-    def __init__(self, flat, flags, defaults):
+    def __init__(self, flat, flags, defaults, max_grad_norm=None, skip_nonfinite=False):
         if flat.flat_params is None:
             raise ValueError(f"{type(self).__name__} needs FlatGrads(..., flatten_params=True)")
         if not flat.flat.is_cuda:
@@ -56,6 +132,7 @@ class _FlatOptimizer:
         self.flags = list(flags)
         self.table = cabi.SegmentTable(segment_ends(flat), self.flags, flat.flat.device)
         self.param_groups = [dict(defaults, params=flat.params)]
+        self._init_guard(max_grad_norm, skip_nonfinite)
 
     def check_views(self):
         """The parameters must still BE the views into the flat buffer this optimiser steps (model.float() / .to(dtype)
@@ -76,7 +153,7 @@ class _FlatOptimizer:
         sd = {k: _plain(v) for k, v in self.param_groups[0].items() if k != "params"}
         sd.update(tensors)
         sd["flags"] = list(self.flags)
-        return sd
+        return self._guard_state(sd) if getattr(self, "guard", None) is not None else sd
 
     def _load(self, sd, tensors):
         if list(sd["flags"]) != self.flags:        # (which tensors decay / are scaled is part of the state)
@@ -85,8 +162,9 @@ class _FlatOptimizer:
         for name in tensors:
             getattr(self, name).copy_(sd[name])
         for k in self.param_groups[0]:
-            if k != "params":
+            if k not in ("params", "max_grad_norm"):
                 self.param_groups[0][k] = sd[k]
+        self._guard_load(sd)
 
 
 class FlatAdamW(_FlatOptimizer):
@@ -97,12 +175,18 @@ class FlatAdamW(_FlatOptimizer):
     the step scales each tensor's gradient on the fly; the gradient buffer itself is left as it was, and
     ``last_grad_norms`` is the device tensor of the pre-clip norms (no host round trip).
     ``param_groups[0]`` (lr, betas, eps, weight_decay, clip) is read on every step; a ``clip`` given at construction can
-    be changed or set to None there, one that was not given cannot be switched on later (``step()`` raises)."""
+    be changed or set to None there, one that was not given cannot be switched on later (``step()`` raises).
+    ``max_grad_norm`` / ``skip_nonfinite``: the global-norm clip and the non-finite skip of ``StepGuarded`` (csn_grad_guard
+    + csn_adam_step_guarded, two launches more).  With ``clip`` as well the two compose in sequence: the global clip first,
+    then the per-tensor clip of the scaled gradient (``last_grad_norms`` are then the norms of the SCALED gradient, and a
+    skipped step leaves them as they were).  ``steps`` -- the t of the bias corrections -- counts every ``step()`` call,
+    skipped ones included: counting only the steps taken would need a host read of the record."""
 
     def __init__(self, flat, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, decoupled=True, no_decay=None,
-                 clip=None):
+                 clip=None, max_grad_norm=None, skip_nonfinite=False):
         flags = adam_segment_flags(flat.params, no_decay, clip)
-        super().__init__(flat, flags, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, clip=clip))
+        super().__init__(flat, flags, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, clip=clip),
+                         max_grad_norm, skip_nonfinite)
         self.decoupled = bool(decoupled)
         self.exp_avg = torch.zeros_like(flat.flat)
         self.exp_avg_sq = torch.zeros_like(flat.flat)
@@ -117,9 +201,14 @@ class FlatAdamW(_FlatOptimizer):
             raise ValueError("FlatAdamW: clip can be changed or switched off through param_groups, not switched on: "
                              "build the optimiser with clip= (the segments carry the flag)")
         clip = g["clip"] if self.last_grad_norms is not None else None
-        cabi.adam_step(self.table, self.flat.flat_params, self.flat.flat, self.exp_avg, self.exp_avg_sq, self.steps + 1,
-                       g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], self.decoupled, clip,
-                       self.last_grad_norms if clip else None)
+        guard = self._measure()
+        args = (self.table, self.flat.flat_params, self.flat.flat, self.exp_avg, self.exp_avg_sq, self.steps + 1, g["lr"],
+                g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], self.decoupled, clip,
+                self.last_grad_norms if clip else None)
+        if guard is None:
+            cabi.adam_step(*args)
+        else:
+            cabi.adam_step_guarded(guard, *args)
         self.steps += 1
 
     def state_dict(self):
@@ -138,22 +227,28 @@ class FlatAdamW(_FlatOptimizer):
 class FlatLARS(_FlatOptimizer):
     """``losses.LARS`` (EEG-BarlowNetworks/optim.py:5-44) as a norm pass and ONE fused update over the flat buffers
     (csn_lars_step: three launches) instead of about ten multi-tensor launches and a gradient clone per parameter.
-    ``param_groups[0]`` (lr, weight_decay, momentum, eta) is read on every step."""
+    ``param_groups[0]`` (lr, weight_decay, momentum, eta) is read on every step.
+    ``max_grad_norm`` / ``skip_nonfinite``: the global-norm clip and the non-finite skip of ``StepGuarded`` (csn_grad_guard
+    + csn_lars_step_guarded: the trust ratios are those of the scaled gradient)."""
 
     def __init__(self, flat, lr, weight_decay=0, momentum=0.9, eta=0.001, weight_decay_filter=False,
-                 lars_adaptation_filter=False):
+                 lars_adaptation_filter=False, max_grad_norm=None, skip_nonfinite=False):
         flags = lars_segment_flags(flat.params, weight_decay_filter, lars_adaptation_filter)
         super().__init__(flat, flags, dict(lr=lr, weight_decay=weight_decay, momentum=momentum, eta=eta,
                                            weight_decay_filter=weight_decay_filter,
-                                           lars_adaptation_filter=lars_adaptation_filter))
+                                           lars_adaptation_filter=lars_adaptation_filter), max_grad_norm, skip_nonfinite)
         self.mu = torch.zeros_like(flat.flat)
 
     @torch.no_grad()
     def step(self):
         self.check_views()
         g = self.param_groups[0]
-        cabi.lars_step(self.table, self.flat.flat_params, self.flat.flat, self.mu, g["lr"], g["weight_decay"], g["momentum"],
-                       g["eta"])
+        guard = self._measure()
+        args = (self.table, self.flat.flat_params, self.flat.flat, self.mu, g["lr"], g["weight_decay"], g["momentum"], g["eta"])
+        if guard is None:
+            cabi.lars_step(*args)
+        else:
+            cabi.lars_step_guarded(guard, *args)
 
     def state_dict(self):
         return self._state({"mu": self.mu})
@@ -174,3 +269,20 @@ def flat_clip_gradients(flat, clip):
         table = flat.clip_table = cabi.SegmentTable(segment_ends(flat), [cabi.SEG_SCALED] * len(flat.params),
                                                      flat.flat.device)
     return cabi.flat_clip(table, flat.flat, clip)
+
+
+def flat_clip_grad_norm_(flat, max_norm):
+    """``torch.nn.utils.clip_grad_norm_(params, max_norm)`` on the flat gradient buffer of a FlatGrads, in place, for an
+    optimiser that reads the gradients itself (the torch ones): csn_grad_guard (two launches), then one multiply of the
+    buffer by the DEVICE coefficient.  Returns the pre-clip global norm as a 0-dim device tensor; nothing is copied to the
+    host.  As with ``error_if_nonfinite=False`` a non-finite buffer stays non-finite (its coefficient is 0, and
+    0 * Inf = NaN): skipping such a step takes a flat optimiser (``skip_nonfinite``).  The record is kept on ``flat``."""
+    if not flat.flat.is_cuda:
+        raise cabi.CsnError("flat_clip_grad_norm_: libcsn_hip needs device tensors (no CPU fallback)")
+    if check_max_grad_norm(max_norm) is None:
+        raise ValueError("flat_clip_grad_norm_: max_norm must be > 0")
+    if flat.step_guard is None:
+        flat.step_guard = cabi.StepGuard(flat.flat.device)
+    flat.step_guard.measure(flat.flat, max_norm)
+    flat.flat.mul_(flat.step_guard.scale)
+    return flat.step_guard.norm

@@ -19,6 +19,7 @@ import torch.distributed as dist
 import torch.nn as nn
 
 from . import filters
+from .flat_optim import StepGuarded, check_max_grad_norm, guard_restatement
 from .losses import (CosineSimilarityLoss, FeatureDistributionLoss, HyperParams, loss_fn_kd, BarlowTwinsLoss, ContrastiveLoss,
                      LARS)
 
@@ -59,6 +60,7 @@ class FlatGrads:
         self.segments = None    # [(start, end)] in readiness order, or None = one blocking collective
         self._pending, self._works = None, []
         self.clip_table = None  # flat_optim.flat_clip_gradients' segment table, built on its first call
+        self.step_guard = None  # flat_optim.flat_clip_grad_norm_'s device record, built on its first call
         off = 0
         for p in self.params:
             n = p.numel()
@@ -126,16 +128,19 @@ class FlatGrads:
         return sum(a.elapsed_time(b) for a, b in self.timing) / len(self.timing)
 
 
-class FlatRMSprop:
+class FlatRMSprop(StepGuarded):
     """``torch.optim.RMSprop(params, lr)`` (LstmDistillFromDinoV2Train.py:329: alpha 0.99, eps 1e-8, no momentum, not
     centred) as ONE fused HIP pass over the flat parameter / gradient / state buffers of a ``FlatGrads`` (csn_rmsprop_step)
-    instead of torch's five multi-tensor kernels per step.  ``state_dict`` keeps the optimiser resumable."""
+    instead of torch's five multi-tensor kernels per step.  ``state_dict`` keeps the optimiser resumable.
+    ``max_grad_norm`` / ``skip_nonfinite``: the global-norm clip and the non-finite skip of ``flat_optim.StepGuarded``
+    (csn_grad_guard + csn_rmsprop_step_guarded: three launches, no host read)."""
 
-    def __init__(self, flat, lr=1e-3, alpha=0.99, eps=1e-8):
+    def __init__(self, flat, lr=1e-3, alpha=0.99, eps=1e-8, max_grad_norm=None, skip_nonfinite=False):
         assert flat.flat_params is not None, "FlatRMSprop needs FlatGrads(..., flatten_params=True)"
         self.flat, self.lr, self.alpha, self.eps = flat, lr, alpha, eps
         self.square_avg = torch.zeros_like(flat.flat)
         self.param_groups = [{"lr": lr, "params": flat.params}]
+        self._init_guard(max_grad_norm, skip_nonfinite)
 
     def check_views(self):
         """The parameters must still BE the views into the flat buffer this optimiser steps (model.float() / .to(dtype)
@@ -151,17 +156,24 @@ class FlatRMSprop:
     def step(self):
         from . import cabi
         self.check_views()      # (a dozen data_ptr() compares on the host: every step, so that a re-homed parameter is caught at once)
-        cabi.rmsprop_step(self.flat.flat_params, self.flat.flat, self.square_avg, self.param_groups[0]["lr"], self.alpha, self.eps)
+        guard = self._measure()
+        args = (self.flat.flat_params, self.flat.flat, self.square_avg, self.param_groups[0]["lr"], self.alpha, self.eps)
+        if guard is None:
+            cabi.rmsprop_step(*args)
+        else:
+            cabi.rmsprop_step_guarded(guard, *args)
 
     def zero_grad(self, set_to_none=False):
         self.flat.zero()
 
     def state_dict(self):
-        return {"square_avg": self.square_avg, "lr": self.param_groups[0]["lr"], "alpha": self.alpha, "eps": self.eps}
+        return self._guard_state({"square_avg": self.square_avg, "lr": self.param_groups[0]["lr"], "alpha": self.alpha,
+                                  "eps": self.eps})
 
     def load_state_dict(self, sd):
         self.square_avg.copy_(sd["square_avg"])
         self.param_groups[0]["lr"], self.alpha, self.eps = sd["lr"], sd["alpha"], sd["eps"]
+        self._guard_load(sd)
 
 
 
@@ -190,14 +202,15 @@ def shard_indices(n, epoch, seed, rank, world, shuffle=True, device="cpu"):
     return idx[rank:total:world].to(device)
 
 
-def check_device_status(model, collective=True):
+def check_device_status(model, collective=True, tolerate_nonfinite=False):
     """Blocking: raises if an in-kernel hand-off of a weight-stationary LSTM kernel timed out, or a non-finite gradient
     reached the backward recurrence, in ANY forward / backward of ``model`` since the last check (the status word is
     sticky).  Call it at epoch ends / after a timed region / after an evaluation pass, not per step.  Cleared once
     reported.  With torch.distributed initialised the verdict is all-reduced (MAX) first, so every rank raises together
     instead of one rank leaving the others in the next collective -- which makes the call itself a COLLECTIVE: every
     rank must reach it.  ``collective=False``: this rank's verdict only (work that one rank does alone, e.g. rank 0's
-    fixture check before a benchmark's timed region)."""
+    fixture check before a benchmark's timed region).  ``tolerate_nonfinite=True``: CSN_STATUS_NONFINITE does not raise (a
+    trainer with ``skip_nonfinite`` did not take those steps; the bit is cleared like the others); time-outs still do."""
     from . import cabi
     from .lstm_model import BiLSTM, HipLSTM
     torch.cuda.synchronize()
@@ -220,7 +233,7 @@ def check_device_status(model, collective=True):
                            "(is another process using this GPU's CUs?); results are invalid")
     if bad & cabi.STATUS_STALE_SLOT:      # only the debug library (make tags) can raise this
         raise RuntimeError("libcsn_hip (tags build): a hand-off ring slot served its previous occupant; results are invalid")
-    if bad & cabi.STATUS_NONFINITE:
+    if bad & cabi.STATUS_NONFINITE and not tolerate_nonfinite:
         raise FloatingPointError("libcsn_hip: a non-finite (NaN / Inf) gradient reached the LSTM backward: the run has "
                                  "diverged (the reference would carry the NaN through its loss and weights)")
 
@@ -228,7 +241,7 @@ def check_device_status(model, collective=True):
 class DistillTrainer:
     def __init__(self, model, sos, ddof=0, loss="cosine", lr=1e-3, optimizer="rmsprop", nepochs=100,
                  kd_params=None, preprocess=True, accum_steps=1, fused_optimizer=False, fused_loss=False,
-                 contrastive_temperature=0.07):
+                 contrastive_temperature=0.07, max_grad_norm=None, skip_nonfinite=False):
         """``fused_optimizer=True`` (on a GPU): adamw / adam / lars step the flat buffers in one to three HIP launches
         (flat_optim.FlatAdamW / FlatLARS) instead of the torch optimisers; rmsprop is fused either way.
 
@@ -243,7 +256,20 @@ class DistillTrainer:
         loss scaled by 1 / k) in the flat buffer before the one all-reduce and optimiser step -- the step of the whole
         batch in 1 / k of the workspace.  That equals the full batch only for a loss that is a mean over rows (cosine,
         featdist, kd); barlow normalises with batch statistics and contrastive takes its negatives from the batch: both
-        are refused."""
+        are refused.
+
+        ``max_grad_norm=m``: the GLOBAL gradient norm is clipped to m, with the coefficient of
+        ``torch.nn.utils.clip_grad_norm_``, once per optimiser step: after the last micro-batch of ``accum_steps`` and after
+        ``all_reduce_mean()``, so every rank decides on the same averaged gradient and no further collective is needed.
+        ``skip_nonfinite=True``: a step whose gradient holds a NaN or an Inf is not taken (parameters and optimiser state
+        keep their bits, as under the reference's ``fp16_scaler.step``, LstmDistillation.py:606-613), ``skipped_steps()``
+        counts them and ``check_device_status()`` no longer reports them as a diverged run.  The flat optimisers (rmsprop;
+        adamw / adam / lars with ``fused_optimizer``) decide both on the device inside ``step()`` (flat_optim.StepGuarded;
+        with a finite ``max_grad_norm`` they skip a non-finite step also without ``skip_nonfinite``).  A torch optimiser
+        on the GPU gets ``flat_clip_grad_norm_`` in front of its step and cannot skip: ``skip_nonfinite`` with one is
+        refused.  On CPU buffers the trainer steps with the torch restatement ``flat_optim.guard_restatement``."""
+        check_max_grad_norm(max_grad_norm)
+        self.max_grad_norm, self.skip_nonfinite = max_grad_norm, bool(skip_nonfinite)
         if not isinstance(accum_steps, int) or isinstance(accum_steps, bool) or accum_steps < 1:
             raise ValueError(f"accum_steps must be an integer >= 1, got {accum_steps!r}")
         if accum_steps > 1 and loss == "barlow":
@@ -259,18 +285,23 @@ class DistillTrainer:
         self.loss_name = loss
         on_gpu = next(model.parameters()).is_cuda
         fused = bool(fused_optimizer) and on_gpu and optimizer in ("adamw", "adam", "lars")
+        if self.skip_nonfinite and optimizer in ("adamw", "adam", "lars") and not fused_optimizer:
+            raise ValueError(f"skip_nonfinite needs a flat optimiser (rmsprop, or {optimizer} with fused_optimizer=True): a "
+                             "torch optimiser reads the gradients itself and cannot be gated on the device")
+        guard = dict(max_grad_norm=max_grad_norm, skip_nonfinite=self.skip_nonfinite)
         self.grads = FlatGrads(model.parameters(), flatten_params=((optimizer == "rmsprop" or fused) and on_gpu))
         params = self.grads.params
         if optimizer == "rmsprop" and on_gpu:   # LstmDistillFromDinoV2Train.py:329 -- one fused pass over the flat buffers
-            self.opt = FlatRMSprop(self.grads, lr=lr)
+            self.opt = FlatRMSprop(self.grads, lr=lr, **guard)
         elif fused:                             # the same optimisers as below, arguments included, on the flat buffers
             from .flat_optim import FlatAdamW, FlatLARS
             if optimizer == "adamw":
-                self.opt = FlatAdamW(self.grads, lr=lr)
+                self.opt = FlatAdamW(self.grads, lr=lr, **guard)
             elif optimizer == "adam":
-                self.opt = FlatAdamW(self.grads, lr=lr, decoupled=False, weight_decay=0)
+                self.opt = FlatAdamW(self.grads, lr=lr, decoupled=False, weight_decay=0, **guard)
             else:
-                self.opt = FlatLARS(self.grads, lr=lr, weight_decay=1e-6, weight_decay_filter=True, lars_adaptation_filter=True)
+                self.opt = FlatLARS(self.grads, lr=lr, weight_decay=1e-6, weight_decay_filter=True, lars_adaptation_filter=True,
+                                    **guard)
         elif optimizer == "rmsprop":
             self.opt = torch.optim.RMSprop(params, lr=lr)
         elif optimizer == "adamw":      # LstmDistillFromDinoV2TrainSpampinato.py:378
@@ -281,6 +312,9 @@ class DistillTrainer:
             self.opt = LARS(params, lr=lr, weight_decay=1e-6, weight_decay_filter=True, lars_adaptation_filter=True)
         else:
             raise ValueError(optimizer)
+        self._flat_opt = isinstance(self.opt, StepGuarded)
+        self._restated_skips = torch.zeros((), dtype=torch.int64)        # (CPU buffers: steps the restatement did not take)
+        self.last_grad_norm = None      # pre-clip global norm of the last step: a 0-dim tensor where the buffers live
         self.cosine = CosineSimilarityLoss()
         self.featdist = FeatureDistributionLoss(nepochs, HyperParams.warmup_teacher_temp, HyperParams.teacher_temp,
                                                 HyperParams.warmup_teacher_temp_epochs, fused=fused_loss)
@@ -395,8 +429,52 @@ class DistillTrainer:
             err, self._hook_error = self._hook_error, None
             raise err
         self.grads.all_reduce_mean()
-        self.opt.step()
+        self._optimizer_step()
         return loss.detach()
+
+    def _optimizer_step(self):
+        """The optimiser step behind the guard (``max_grad_norm`` / ``skip_nonfinite``), measured ONCE per step on the
+        summed, averaged gradient.  Both off: ``opt.step()`` and nothing else."""
+        if self.max_grad_norm is None and not self.skip_nonfinite:
+            self.opt.step()
+        elif self._flat_opt:                    # decided on the device inside step()
+            self.opt.step()
+            self.last_grad_norm = self.opt.last_grad_norm
+        elif self.grads.flat.is_cuda:           # a torch optimiser: clip in place in front of it (skip_nonfinite was refused)
+            from .flat_optim import flat_clip_grad_norm_
+            self.last_grad_norm = flat_clip_grad_norm_(self.grads, self.max_grad_norm)
+            self.opt.step()
+        else:
+            self._restated_step()
+
+    @torch.no_grad()
+    def _restated_step(self):
+        """CPU buffers: csn_grad_guard and the guarded step restated in torch around a torch optimiser -- the gradient
+        scaled in place by ``guard_restatement``'s coefficient, the step, and ``torch.where`` on the finiteness flag putting
+        back the parameters and the state tensors of a step that must not be taken (the optimiser's own ``step`` count keeps
+        counting calls, as FlatAdamW's does)."""
+        norm, scale, finite = guard_restatement(self.grads.flat, self.max_grad_norm)
+        self.last_grad_norm = norm
+        self._restated_skips += (~finite).to(torch.int64)
+        params = self.grads.params
+        old_p = [p.detach().clone() for p in params]
+        old_s = {(id(p), k): v.clone() for p, st in self.opt.state.items() for k, v in st.items()
+                 if torch.is_tensor(v) and k != "step"}
+        self.grads.flat.mul_(scale)
+        self.opt.step()
+        for p, old in zip(params, old_p):
+            p.copy_(torch.where(finite, p, old))
+        for p, st in self.opt.state.items():
+            for k, v in st.items():
+                if torch.is_tensor(v) and k != "step":
+                    old = old_s.get((id(p), k))
+                    v.copy_(torch.where(finite, v, torch.zeros_like(v) if old is None else old))
+
+    def skipped_steps(self):
+        """Optimiser steps not taken because the gradient was non-finite (one blocking host read on the GPU)."""
+        if self._flat_opt:
+            return self.opt.skipped_steps()
+        return int(self._restated_skips)
 
     def _micro_batches(self, eeg_bct, targets, labels, epoch, k):
         """embed -> forward -> loss / k -> backward per micro-batch, all into the flat buffer.  The gradient-ready hook is
@@ -427,9 +505,11 @@ class DistillTrainer:
         them) AND, for every path -- the exact-f32 / per-diagonal kernels raise no status bit -- a finiteness test of the
         parameters and of the last step's gradients: a NaN that any earlier step produced is still in the parameters.
         Like the status word it reports ONCE: a state already reported (by this test or by the status word: a timed-out
-        run leaves garbage) is not raised again at the next check."""
-        bufs = [self.grads.flat] + ([self.grads.flat_params] if self.grads.flat_params is not None else
-                                    [p.data for p in self.grads.params])
+        run leaves garbage) is not raised again at the next check.  With ``skip_nonfinite`` a non-finite GRADIENT is not a
+        diverged run -- that step was not taken -- so neither the status bit nor the gradient buffer raises; time-outs and
+        non-finite parameters still do."""
+        bufs = ([] if self.skip_nonfinite else [self.grads.flat]) + \
+            ([self.grads.flat_params] if self.grads.flat_params is not None else [p.data for p in self.grads.params])
         finite = torch.stack([torch.isfinite(b).all() for b in bufs]).all()
         _, world = dist_info()
         if world > 1:
@@ -440,7 +520,7 @@ class DistillTrainer:
         finite = bool(finite)
         reported_before = getattr(self, "_nonfinite_reported", False)
         self._nonfinite_reported = not finite
-        check_device_status(self.model)          # (raises for a time-out / a non-finite gradient seen on the device)
+        check_device_status(self.model, tolerate_nonfinite=self.skip_nonfinite)          # (raises for a time-out / a non-finite gradient seen on the device)
         if not finite and not reported_before:
             raise FloatingPointError("non-finite (NaN / Inf) parameters or gradients: the run has diverged")
 

@@ -96,7 +96,8 @@ enum csnDtype { CSN_F32 = 0, CSN_BF16 = 1 };
 /* ABI version of this header; bumped on any signature change.  A symbol added beside the existing ones
  * (csn_lstm_plan_set_grad_mode, csn_lstm_plan_set_lengths, csn_lstm_plan_set_views, csn_lstm_plan_set_io, csn_lstm_plan_half_tile_launches, the
  * csn_flat_* family, csn_adam_step, csn_lars_step, csn_eeg_bandpass_stream and its _path, csn_distill_loss,
- * csn_dino_loss, csn_barlow_corr, csn_barlow_grad, csn_contrastive_lse, csn_contrastive_grad, csn_topk_merge and its _staged_max, csn_topk_class_metrics) breaks no caller and does not bump it; neither does a new bit of csn_lstm_plan_create's `training` word. */
+ * csn_dino_loss, csn_barlow_corr, csn_barlow_grad, csn_contrastive_lse, csn_contrastive_grad, csn_topk_merge and its _staged_max, csn_topk_class_metrics, csn_grad_guard, its _scratch_bytes and the three
+ * csn_*_step_guarded) breaks no caller and does not bump it; neither does a new bit of csn_lstm_plan_create's `training` word. */
 #define CSN_ABI_VERSION 6
 int csn_abi_version(void);
 /* Thread-local message for the last non-zero status returned on this thread. */
@@ -611,6 +612,45 @@ int csn_adam_step(float* params, const float* grads, float* exp_avg, float* exp_
  * Replaces: LARS.step, EEG-BarlowNetworks/optim.py:17-44. */
 int csn_lars_step(float* params, const float* grads, float* mu, int64_t n, int nseg, void* table, double lr,
                   double weight_decay, double momentum, double eta, csnStream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * Global-norm gradient clipping and the non-finite step skip, decided ON THE DEVICE: one pass
+ * over the flat gradient buffer leaves a 16-byte record, and the guarded optimiser steps read their coefficient from it.
+ * The host never sees the norm, so the feature costs no round trip.
+ * Replaces: torch.nn.utils.clip_grad_norm_(params, max_norm) (its coefficient min(1, max_norm / (|g| + 1e-6))), and the
+ * step that fp16_scaler.step(optimizer) does NOT take when a gradient is non-finite, LstmDistillation.py:606-613.
+ *
+ * csnStepGuard: 16 bytes of caller-owned device memory, 16-byte aligned, zeroed ONCE by the caller (skipped counts up
+ * over the record's life; the other three words are overwritten by every csn_grad_guard).
+ * ---------------------------------------------------------------------------------- */
+typedef struct { float norm; float scale; uint32_t finite; uint32_t skipped; } csnStepGuard;
+/* Bytes of caller-owned device scratch (16-byte aligned) for a buffer of n elements; 0 (and an error message) for n <= 0. */
+size_t csn_grad_guard_scratch_bytes(int64_t n);
+/* S = sum (double)g_i^2, two-stage: one float64 partial per 2048-element chunk, the partials added in ascending chunk
+ * order by one wave -- no floating-point atomics, two runs give the same bits; a float squared is exact in double, so S is
+ * non-finite exactly when some g_i is.  Two launches.  The record then holds
+ *     norm = (float)sqrt(S),  finite = isfinite(S),  skipped += !finite,
+ *     scale = finite ? (float)min(1.0, max_norm / (sqrt(S) + 1e-6)) : 0     (clip_grad_norm_'s coefficient).
+ * max_norm = +INFINITY: measure and gate only (scale is exactly 1.0f or 0).  max_norm <= 0 and NaN are refused.
+ * grads (16-byte aligned) is read, never written. */
+int csn_grad_guard(const float* grads, int64_t n, double max_norm, void* scratch, csnStepGuard* guard, csnStream_t stream);
+/* The steps above behind a record that a csn_grad_guard earlier on `stream` filled.  Wherever the unguarded step reads g
+ * -- the norm passes of LARS and of Adam's per-tensor clip included -- the guarded one reads g' = fl32(scale g), rounded
+ * once (never contracted into a following multiply-add), then runs the identical arithmetic:
+ *     step_guarded(g) == step(g') bit for bit.
+ * Adam with a finite max_norm and clip > 0 is the sequential composition: the global clip, then the per-tensor clip of g'.
+ * finite == 0: the step writes NOTHING -- parameters, every state buffer, norms_out and the table's sums keep their bits.
+ * grads is never written.  guard == NULL is refused (the unguarded entry points exist for that).
+ * csn_adam_step_guarded: t stays the HOST's count of calls, skipped calls included (the bias corrections of the steps
+ * after a skip are those of t, not of the number of steps taken): the host does not read the record back.
+ * Replaces: clip_grad_norm_ + optimizer.step(), and the skip of fp16_scaler.step(optimizer), LstmDistillation.py:606-613. */
+int csn_rmsprop_step_guarded(float* params, const float* grads, float* square_avg, int64_t n, float lr, float alpha,
+                             float eps, const csnStepGuard* guard, csnStream_t stream);
+int csn_adam_step_guarded(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, int nseg,
+                          void* table, int64_t t, double lr, double beta1, double beta2, double eps, double weight_decay,
+                          int decoupled, double clip, float* norms_out, const csnStepGuard* guard, csnStream_t stream);
+int csn_lars_step_guarded(float* params, const float* grads, float* mu, int64_t n, int nseg, void* table, double lr,
+                          double weight_decay, double momentum, double eta, const csnStepGuard* guard, csnStream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * K7  Barlow-Twins reduction over the cross-correlation matrix c[D,D] (float32):
