@@ -49,6 +49,7 @@
 #include "lstm_cell_common.h"
 #include "lstm_dropout.h"
 #include "lstm_f32_persist.h"
+#include "lstm_handoff.h"
 #include "lstm_resident.h"
 #include "lstm_schedule.h"
 
@@ -130,7 +131,7 @@ static WsLayout make_layout(const csnLstmDesc& d, int training, bool dropout, co
     if (b > tn_bytes) tn_bytes = b;
   }
   w.x_c = take(TB * d.I * es);
-  w.status = take(256);
+  w.status = take(kStatusBytes);
   // (H = 512 excluded: its 64 x 32-unit tile leaves no registers for the W_ih fragments.  N-split kernel at H = 1024: W_hh
   // fills the 256 AGPRs, W_ih's 32 registers are VGPR operands of their MFMAs -- round 3's fused instantiation asked for
   // AGPRs there too and the compiler's copies ran into an MFMA read hazard the recogniser cannot see inside inline asm
@@ -748,7 +749,7 @@ extern "C" int csn_lstm_workspace_init(const csnLstmPlan* P, void* workspace, cs
   char* ws = (char*)workspace;
   const WsLayout& w = P->w;
   const size_t es = dtype_size(P->d.dtype);
-  CSN_HIP_CHECK(hipMemsetAsync(ws + w.status, 0, 256, st));
+  CSN_HIP_CHECK(hipMemsetAsync(ws + w.status, 0, kStatusBytes, st));
   for (int l = 0; l < P->d.L; ++l) {
     CSN_HIP_CHECK(hipMemsetAsync(ws + w.layer[l].h_all, 0, (size_t)P->d.B * P->d.H * es, st));
     CSN_HIP_CHECK(hipMemsetAsync(ws + w.layer[l].c_all, 0, (size_t)P->d.B * P->d.H * 4, st));
@@ -761,25 +762,27 @@ extern "C" int csn_lstm_workspace_init(const csnLstmPlan* P, void* workspace, cs
 // The workspace's status word (sticky; see include/csn_hip.h)
 extern "C" int csn_lstm_status_clear(const csnLstmPlan* P, void* workspace, csnStream_t stream) {
   CSN_REQUIRE(P && workspace, "csn_lstm_status_clear: null pointer");
-  CSN_HIP_CHECK(hipMemsetAsync((char*)workspace + P->w.status, 0, 256, as_stream(stream)));
+  CSN_HIP_CHECK(hipMemsetAsync((char*)workspace + P->w.status, 0, kStatusBytes, as_stream(stream)));
   return CSN_OK;
 }
 extern "C" int csn_lstm_status_raise(const csnLstmPlan* P, void* workspace, csnStream_t stream) {
   CSN_REQUIRE(P && workspace, "csn_lstm_status_raise: null pointer");
-  CSN_HIP_CHECK(hipMemsetAsync((char*)workspace + P->w.status, 1, 1, as_stream(stream)));   // word = 1, as a timed-out wait leaves it
+  CSN_HIP_CHECK(hipMemsetAsync((char*)workspace + P->w.status + 4 * kStatusTimeout, 1, 1, as_stream(stream)));   // word = 1, as a timed-out wait leaves it
   return CSN_OK;
 }
 extern "C" int csn_lstm_status_read(const csnLstmPlan* P, const void* workspace, int* status) {
   CSN_REQUIRE(P && workspace && status, "csn_lstm_status_read: null pointer");
-  // word 0: a bounded wait timed out; word 1: a non-finite gradient reached the backward; word 2 (debug library built
-  // with -DCSN_SLAB_TAGS only): a consumer was served a stale occupant of a hand-off ring slot
-  unsigned flag[3] = {0u, 0u, 0u};
+  // the status words of lstm_handoff.h: a bounded wait timed out; a non-finite gradient reached the backward; (debug
+  // library built with -DCSN_SLAB_TAGS only) a consumer was served a stale occupant of a hand-off ring slot
+  unsigned flag[kStatusStaleSlot + 1] = {};
   CSN_HIP_CHECK(hipMemcpy(flag, (const char*)workspace + P->w.status, sizeof(flag), hipMemcpyDeviceToHost));
-  *status = (flag[0] ? CSN_STATUS_TIMEOUT : 0) | (flag[1] ? CSN_STATUS_NONFINITE : 0) | (flag[2] ? CSN_STATUS_STALE_SLOT : 0);
+  *status = (flag[kStatusTimeout] ? CSN_STATUS_TIMEOUT : 0) | (flag[kStatusNonFinite] ? CSN_STATUS_NONFINITE : 0) |
+            (flag[kStatusStaleSlot] ? CSN_STATUS_STALE_SLOT : 0);
 #ifdef CSN_SLAB_TAGS
-  if (flag[2] && getenv("CSN_TAGS_VERBOSE")) {
-    unsigned dbg[24];
-    CSN_HIP_CHECK(hipMemcpy(dbg, (const char*)workspace + P->w.status + 28, sizeof(dbg), hipMemcpyDeviceToHost));
+  if (flag[kStatusStaleSlot] && getenv("CSN_TAGS_VERBOSE")) {
+    unsigned dbg[24];      // the claim word, then the dump
+    static_assert(kStatusDump == kStatusDumpClaim + 1 && 4 * kStatusDumpClaim + sizeof(dbg) <= kStatusBytes, "the dump follows its claim");
+    CSN_HIP_CHECK(hipMemcpy(dbg, (const char*)workspace + P->w.status + 4 * kStatusDumpClaim, sizeof(dbg), hipMemcpyDeviceToHost));
     if (dbg[0])
       fprintf(stderr, "stale piece (backward): t=%u step-in-launch=%u group=%u slice=%u wave=%u lane=%u kb*4+rg=%u u0=%08x local=%u redone=%u "
               "single=%u phase=%u rot=%u nsteps=%u xcc=%u lanes=%u\n", dbg[1], dbg[2], dbg[3], dbg[4], dbg[5], dbg[6], dbg[7], dbg[8],

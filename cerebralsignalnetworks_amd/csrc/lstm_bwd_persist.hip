@@ -26,36 +26,19 @@
 // carried dc and ring position, so the host issues them as ONE launch and the kernel loops over them around its step
 // loop.  What a kernel boundary did for the input-gradient GEMM between two diagonals -- make a chunk's row-major dgates
 // visible to the workers, and their dx to the layer below -- two chunk-level counters do: round_publish / round_wait
-// below.  Nothing inside a chunk changes; a launch of one round is the launch it always was.
+// of lstm_handoff.h.  Nothing inside a chunk changes; a launch of one round is the launch it always was.
 #include "csn_common.h"
 #include "lstm_cell_common.h"
 #include "lstm_cell_blk.h"
 #include "gemm_beside.h"
+#include "lstm_handoff.h"
 
+#define CSN_BSTAMP(i) CSN_HANDOFF_STAMP(g_bstamps, CSN_STAMP_BLOCK, i)
 #ifdef CSN_PSTAMPS
-#ifndef CSN_STAMP_BLOCK
-#define CSN_STAMP_BLOCK 11     // group 3 (layer 0 at cfg2), slice 1; 15 = group 7 (layer 1)
-#endif
 __device__ unsigned long long g_bstamps[16];
-#define CSN_BSTAMP(i)                                                          \
-  do {                                                                         \
-    __builtin_amdgcn_sched_barrier(0);                                         \
-    if (tid == 0 && blockIdx.x == CSN_STAMP_BLOCK) {                           \
-      const unsigned long long now_ = wall_clock64();                          \
-      atomicAdd(&g_bstamps[i], now_ - last_);                                  \
-      last_ = now_;                                                            \
-    }                                                                          \
-    __builtin_amdgcn_sched_barrier(0);                                         \
-  } while (0)
-#else
-#define CSN_BSTAMP(i)
 #endif
 
 namespace csn {
-
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-
-static constexpr unsigned long long kBwdSpinTimeoutTicks = 20000000ull;
 
 // Reduction buffer: float4 slot of (batch row r of the 16-row group, unit q of the 4-unit tile) inside an accumulator
 // tile.  The accumulator layout would put it at r + 16 q -- but the epilogue's 16-lane groups are 2 consecutive rows x
@@ -64,22 +47,7 @@ static constexpr unsigned long long kBwdSpinTimeoutTicks = 20000000ull;
 // pi(r) = r / 2 + 8 (r mod 2) and a tile pitch of 4 mod 16 gives the 16 lanes 16 different groups, and a writing
 // 16-lane group (q fixed, r = 0..15) as well.
 static constexpr int kBwdRedTile = 68;
-__device__ __forceinline__ int bwd_red_pos(int r, int q) { return (r >> 1) + 8 * (r & 1) + 17 * q; }   // 0.2 s of the 100 MHz wall clock
-
-typedef __attribute__((ext_vector_type(4))) unsigned bu32x4;
-
-__device__ __forceinline__ bf16x8 bload_sc1_b128(__amdgpu_buffer_rsrc_t rsrc, unsigned byte_off, int soff = 0) {
-  bu32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)byte_off, soff, 16);   // aux 16 = sc1: L1 bypassed
-  union { bu32x4 u; bf16x8 b; } cvt;
-  cvt.u = v;
-  return cvt.b;
-}
-template <bool WT>
-__device__ __forceinline__ void bstore_b128(__amdgpu_buffer_rsrc_t rsrc, unsigned byte_off, const bf16x8& v, int soff = 0) {
-  union { bu32x4 u; bf16x8 b; } cvt;
-  cvt.b = v;
-  __builtin_amdgcn_raw_buffer_store_b128(cvt.u, rsrc, (int)byte_off, soff, WT ? 16 : 0);   // sc1 = write-through
-}
+__device__ __forceinline__ int bwd_red_pos(int r, int q) { return (r >> 1) + 8 * (r & 1) + 17 * q; }
 
 // MASK (variable-length batches): `lens` = the rows' lengths [B]; a cell at t >= lengths[row] publishes zero gate gradients
 // and keeps the carried dc.  The row's length is loaded once per launch, beside the carried dc.
@@ -87,46 +55,6 @@ struct PersistLens { const int* lengths; };
 struct PersistNoLens {};
 template <bool MASK> struct PersistLensArg { typedef PersistNoLens type; };
 template <> struct PersistLensArg<true> { typedef PersistLens type; };
-
-// Chunk-level hand-off between the rounds of a merged launch (PersistBwdArgs::nrounds): row-major dgates and dx cross
-// XCDs through plain / nt stores, so visibility is an agent-scope release by the producers and an agent-scope acquire by
-// every consuming workgroup.  Both are called by ALL threads of a workgroup, under a uniform condition.
-// Publish: every wave's stores have left it, then ONE lane writes the XCD's L2 back and counts the workgroup in.
-// (the one lane: compared afresh at every use -- as a loop invariant the lane mask was a pair of SGPRs kept, and spilled,
-// across the step loop)
-__device__ __forceinline__ bool round_leader() {
-  unsigned t = threadIdx.x;
-  asm volatile("" : "+v"(t));
-  return t == 0u;
-}
-__device__ __forceinline__ void round_publish(unsigned* word) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (round_leader()) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // (the fence's own wait can be dropped by the compiler)
-    __hip_atomic_fetch_add(word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-// Wait: ONE lane polls the counter (the kernel's bounded spin: same time-out, same sticky status word, gives up when it
-// is set), then the acquire; the barrier holds the other waves until the invalidate has completed.  No load of the
-// handed-off bytes may be issued in front of this.
-__device__ __forceinline__ void round_wait(const unsigned* word, unsigned want, unsigned* error_flag) {
-  if (round_leader()) {
-    const unsigned long long t_begin = wall_clock64();
-    while (__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < want) {
-      __builtin_amdgcn_s_sleep(1);
-      if (__hip_atomic_load(error_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) break;
-      if (wall_clock64() - t_begin > kBwdSpinTimeoutTicks) {
-        __hip_atomic_store(error_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        break;
-      }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  }
-  __syncthreads();
-}
 
 template <int NUT, int KS, bool DPOLL, bool MASK = false, int RG = 4>
 __global__ void __launch_bounds__(256) lstm_bwd_persist_kernel(PersistBwdArgs a, typename PersistLensArg<MASK>::type lens) {
@@ -225,30 +153,9 @@ __global__ void __launch_bounds__(256) lstm_bwd_persist_kernel(PersistBwdArgs a,
   // all-ones sentinel; no store drain and no flag on the producer side
   constexpr bool dpoll = DPOLL;
 
-  // ---- is this group on one XCD?  (see lstm_fwd_persist.hip)
+  // ---- is this group on one XCD?  (lstm_handoff.h)
   bool local = false;
-  if (a.xcd_groups && a.agree != nullptr) {
-    if (tid == 0) {
-      const unsigned xcc = __builtin_amdgcn_s_getreg(6164) & 7u;        // hwreg(HW_REG_XCC_ID, 0, 4)
-      const unsigned long long mine = 1ull | (1ull << (8 + 6 * xcc));
-      __hip_atomic_fetch_add(a.agree + grp, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const unsigned long long t_begin = wall_clock64();
-      unsigned long long v;
-      while (((v = __hip_atomic_load(a.agree + grp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) & 0xffull) <
-             (unsigned long long)nslices) {
-        __builtin_amdgcn_s_sleep(1);
-        if (__hip_atomic_load(a.error_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) break;
-        if (wall_clock64() - t_begin > kBwdSpinTimeoutTicks) {
-          __hip_atomic_store(a.error_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          break;
-        }
-      }
-      ((__attribute__((address_space(3))) int*)(__attribute__((address_space(3))) void*)red)[0] = (int)(((v >> (8 + 6 * xcc)) & 63ull) == (unsigned long long)nslices);
-    }
-    __syncthreads();
-    local = ((__attribute__((address_space(3))) int*)(__attribute__((address_space(3))) void*)red)[0] != 0;    // (LDS address space: no flat_ instruction in these kernels -- FLAT retires out of order)
-    __syncthreads();
-  }
+  if (a.xcd_groups && a.agree != nullptr) local = CSN_XCD_GROUP_IS_LOCAL(unsigned long long, a, grp, nslices, red);
 
   // ---- stationary operand: this wave's K' quarter of the workgroup's rows of W_hh^T ----------------
   // The workgroups of a group all stream the same slab; each starts its walk over the k-blocks at its own
@@ -328,11 +235,11 @@ __global__ void __launch_bounds__(256) lstm_bwd_persist_kernel(PersistBwdArgs a,
       const unsigned o0 = (unsigned)(blk_offset(prow[ps], 4 * (int64_t)puq[ps], K) * 2);
       const unsigned o1 = (unsigned)(blk_offset(prow[ps], 4 * (int64_t)puq[ps] + 8, K) * 2);
       if (local) {
-        bstore_b128<false>(ring_rsrc, o0, sent, arm_off);
-        bstore_b128<false>(ring_rsrc, o1, sent, arm_off);
+        store_b128<false>(ring_rsrc, o0, sent, arm_off);
+        store_b128<false>(ring_rsrc, o1, sent, arm_off);
       } else {
-        bstore_b128<true>(ring_rsrc, o0, sent, arm_off);
-        bstore_b128<true>(ring_rsrc, o1, sent, arm_off);
+        store_b128<true>(ring_rsrc, o0, sent, arm_off);
+        store_b128<true>(ring_rsrc, o1, sent, arm_off);
       }
     }
   };
@@ -395,18 +302,13 @@ __global__ void __launch_bounds__(256) lstm_bwd_persist_kernel(PersistBwdArgs a,
           fl = flags + (size_t)(t + 1) * flag_step + wave * npw + (lane < npw ? lane : 0);
         }
         const unsigned not_yet = dpoll ? 0xffffffffu : 0u;
-        const unsigned long long t_begin = wall_clock64();
         // (data_polls == 2, a test switch: no hint, load straight away -- every step then goes through the re-read path)
         // (flags: the first step of a launch reads what an EARLIER launch published -- a kernel boundary, no wait; the
         // flag lines of the two tile heights are separate, so a launch never polls a line of the other height)
-        while (!(dpoll && CSN_DPOLL_MODE(a.data_polls) == 2) && (dpoll || s > 0) && !__all(__hip_atomic_load(fl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != not_yet)) {
-          __builtin_amdgcn_s_sleep(1);
-          if (__hip_atomic_load(a.error_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) break;
-          if (wall_clock64() - t_begin > kBwdSpinTimeoutTicks) {
-            __hip_atomic_store(a.error_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            break;
-          }
-        }
+        const bool spin = !(dpoll && CSN_DPOLL_MODE(a.data_polls) == 2) && (dpoll || s > 0);
+        bounded_spin(a.error_flag, [fl, not_yet, spin] {
+          return !spin || __all(__hip_atomic_load(fl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != not_yet);
+        });
       }
       CSN_BSTAMP(0);   // wait for dgates_{t+1}
       const __amdgpu_buffer_rsrc_t slabs_rsrc = dpoll ? ring_rsrc : __builtin_amdgcn_make_buffer_rsrc(
@@ -440,7 +342,7 @@ __global__ void __launch_bounds__(256) lstm_bwd_persist_kernel(PersistBwdArgs a,
         auto issue_group = [&](int slot) {
 #pragma unroll
           for (int rg = 0; rg < RG; ++rg)
-            df[slot][rg] = bload_sc1_b128(slabs_rsrc, base + (unsigned)(rg * kblocks) * 1024u, src_off + kbo);
+            df[slot][rg] = load_sc1_b128<bf16x8>(slabs_rsrc, base + (unsigned)(rg * kblocks) * 1024u, src_off + kbo);
           kbo = kbo + 1024 == KS * 1024 ? 0 : kbo + 1024;
         };
 #pragma unroll
@@ -483,15 +385,15 @@ __global__ void __launch_bounds__(256) lstm_bwd_persist_kernel(PersistBwdArgs a,
           }
         }
 #ifdef CSN_SLAB_TAGS
-        if (__any(stale) && lane == 0) __hip_atomic_store(a.error_flag + 2, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (__any(stale) && lane == 0) raise_status(a.error_flag, kStatusStaleSlot);
 #ifdef CSN_SLAB_TAGS_DUMP
         if (stale) {     // first detection of the workspace: where it was (read back by csn_lstm_status_read of the debug library)
-          if (atomicCAS(a.error_flag + 7, 0u, 1u) == 0u) {
-            unsigned* dbg = a.error_flag + 8;
+          if (atomicCAS(a.error_flag + kStatusDumpClaim, 0u, 1u) == 0u) {
+            unsigned* dbg = a.error_flag + kStatusDump;
             dbg[0] = (unsigned)t; dbg[1] = (unsigned)s; dbg[2] = (unsigned)grp; dbg[3] = (unsigned)slice; dbg[4] = (unsigned)wave;
             dbg[5] = (unsigned)lane; dbg[6] = (unsigned)stale_kb; dbg[7] = stale_u0; dbg[8] = (unsigned)local; dbg[9] = (unsigned)redone;
             dbg[10] = 0u; dbg[11] = (unsigned)(((t + 1) >> 2) & 1); dbg[12] = (unsigned)rot_t; dbg[13] = (unsigned)nsteps;
-            dbg[14] = __builtin_amdgcn_s_getreg(6164) & 7u; dbg[15] = (unsigned)__popcll(__ballot(stale));
+            dbg[14] = xcc_id(); dbg[15] = (unsigned)__popcll(__ballot(stale));
           }
         }
 #endif
@@ -513,7 +415,7 @@ __global__ void __launch_bounds__(256) lstm_bwd_persist_kernel(PersistBwdArgs a,
               // the operand was all data and the product is still not finite: a genuine non-finite gradient (NaN / Inf
               // input, Inf - Inf in the accumulators).  The reference propagates it; so do we -- no spin, and a status
               // bit of its own (word 1) so that the host can tell it from a hand-off that timed out (word 0)
-              if (lane == 0) __hip_atomic_store(a.error_flag + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+              if (lane == 0) raise_status(a.error_flag, kStatusNonFinite);
             } else {
               if (++redone >= 2) {
                 // cold path: re-read every piece this wave multiplies and look for the sentinel by bit pattern (a piece
@@ -524,16 +426,16 @@ __global__ void __launch_bounds__(256) lstm_bwd_persist_kernel(PersistBwdArgs a,
                 for (int kb = 0; kb < KS; ++kb) {
 #pragma unroll
                   for (int rg = 0; rg < RG; ++rg) {
-                    const u32x4 u = __builtin_bit_cast(u32x4, bload_sc1_b128(slabs_rsrc, base + (unsigned)(rg * kblocks) * 1024u, src_off + kbo2));
+                    const u32x4 u = __builtin_bit_cast(u32x4, load_sc1_b128<bf16x8>(slabs_rsrc, base + (unsigned)(rg * kblocks) * 1024u, src_off + kbo2));
                     sentinel |= (u[0] == 0xffffffffu) | (u[3] == 0xffffffffu);
                   }
                   kbo2 = kbo2 + 1024 == KS * 1024 ? 0 : kbo2 + 1024;
                 }
                 proven = !__any(sentinel);     // a written piece stays written until this workgroup publishes dgates_t
               }
-              again = __hip_atomic_load(a.error_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u;
-              if (wall_clock64() - t_phase > kBwdSpinTimeoutTicks) {
-                __hip_atomic_store(a.error_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+              again = status_clear(a.error_flag);
+              if (spin_expired(t_phase)) {
+                raise_timeout(a.error_flag);
                 again = false;
               }
             }
@@ -579,11 +481,11 @@ __global__ void __launch_bounds__(256) lstm_bwd_persist_kernel(PersistBwdArgs a,
           const unsigned z0 = (unsigned)(blk_offset(prow[ps], 4 * (int64_t)puq[ps], K) * 2);
           const unsigned z1 = (unsigned)(blk_offset(prow[ps], 4 * (int64_t)puq[ps] + 8, K) * 2);
           if (local) {
-            bstore_b128<false>(slabs_rsrc, z0, z, dst_off);
-            bstore_b128<false>(slabs_rsrc, z1, z, dst_off);
+            store_b128<false>(slabs_rsrc, z0, z, dst_off);
+            store_b128<false>(slabs_rsrc, z1, z, dst_off);
           } else {
-            bstore_b128<true>(slabs_rsrc, z0, z, dst_off);
-            bstore_b128<true>(slabs_rsrc, z1, z, dst_off);
+            store_b128<true>(slabs_rsrc, z0, z, dst_off);
+            store_b128<true>(slabs_rsrc, z1, z, dst_off);
           }
         }
         continue;
@@ -639,11 +541,11 @@ __global__ void __launch_bounds__(256) lstm_bwd_persist_kernel(PersistBwdArgs a,
       }
 #endif
       if (local) {
-        bstore_b128<false>(slabs_rsrc, o0, lo, dst_off);
-        bstore_b128<false>(slabs_rsrc, o1, hi, dst_off);
+        store_b128<false>(slabs_rsrc, o0, lo, dst_off);
+        store_b128<false>(slabs_rsrc, o1, hi, dst_off);
       } else {
-        bstore_b128<true>(slabs_rsrc, o0, lo, dst_off);
-        bstore_b128<true>(slabs_rsrc, o1, hi, dst_off);
+        store_b128<true>(slabs_rsrc, o0, lo, dst_off);
+        store_b128<true>(slabs_rsrc, o1, hi, dst_off);
       }
       bf16x8* op = reinterpret_cast<bf16x8*>(dgates + ((size_t)t * B + row) * K + 4 * (size_t)uq);
       nt_store(op, lo);

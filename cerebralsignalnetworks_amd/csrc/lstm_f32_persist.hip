@@ -26,41 +26,20 @@
 #include "lstm_f32_persist.h"
 
 #include "lstm_cell_common.h"
+#include "lstm_handoff.h"
 
+#define CSN_F32STAMP(i) CSN_HANDOFF_STAMP(g_f32stamps, 5, i)
 #ifdef CSN_PSTAMPS        // `make diag`: phase times of ONE workgroup's wave 0, summed over the steps of a launch (tools/insitu_stamps.py)
 __device__ unsigned long long g_f32stamps[16];      // forward 0..6, backward 8..14: wait | loads + MFMA | partials + barrier | sums + gate math + store issue | drain | barrier + flag
-#define CSN_F32STAMP(i)                                                        \
-  do {                                                                         \
-    __builtin_amdgcn_sched_barrier(0);                                         \
-    if (tid == 0 && blockIdx.x == 5) {                                         \
-      const unsigned long long now_ = wall_clock64();                          \
-      atomicAdd(&g_f32stamps[i], now_ - last_);                                \
-      last_ = now_;                                                            \
-    }                                                                          \
-    __builtin_amdgcn_sched_barrier(0);                                         \
-  } while (0)
-#else
-#define CSN_F32STAMP(i)
 #endif
 
 namespace csn {
 
-typedef __attribute__((ext_vector_type(4))) unsigned fu32x4;
-static constexpr unsigned long long kF32SpinTimeoutTicks = 20000000ull;   // 0.2 s of the 100 MHz wall clock
-
 #ifndef CSN_F32_ABL
 #define CSN_F32_ABL 0      // timing-only ablations (tools/abl_build.sh): 1 no MFMAs, 2 no operand loads, 4 cheap gate math, 8 no polls, 16 no drain, 32 saved-tensor stores in front of the drain
 #endif
-__device__ __forceinline__ f32x4 f32p_load_sc1(__amdgpu_buffer_rsrc_t rsrc, int byte_off) {
-#if CSN_F32_ABL & 2
-  return (f32x4){1e-3f * (float)(byte_off & 7), 1e-3f, -1e-3f, 2e-3f};
-#endif
-  const fu32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, byte_off, 0, 16);      // aux 16 = sc1
-  return __builtin_bit_cast(f32x4, v);
-}
-__device__ __forceinline__ void f32p_store_wt(__amdgpu_buffer_rsrc_t rsrc, int byte_off, const f32x4& v) {
-  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(fu32x4, v), rsrc, byte_off, 0, 16);   // sc1 = write-through
-}
+// (ablation 2: what stands in for an operand fragment that is not loaded)
+__device__ __forceinline__ f32x4 f32p_no_operand(int byte_off) { return (f32x4){1e-3f * (float)(byte_off & 7), 1e-3f, -1e-3f, 2e-3f}; }
 __device__ __forceinline__ f32x4 f32p_mfma(float a, float b, const f32x4& c) {
 #if CSN_F32_ABL & 1
   return (f32x4){c[0] + a * b, c[1], c[2], c[3]};
@@ -83,15 +62,7 @@ __device__ __forceinline__ void f32p_wait_flags(const unsigned* line, int n, int
   return;
 #endif
   const unsigned* fl = line + (lane < n ? lane : 0);
-  const unsigned long long t_begin = wall_clock64();
-  while (!__all(__hip_atomic_load(fl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u)) {
-    __builtin_amdgcn_s_sleep(1);
-    if (__hip_atomic_load(error_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) break;
-    if (wall_clock64() - t_begin > kF32SpinTimeoutTicks) {
-      __hip_atomic_store(error_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      break;
-    }
-  }
+  bounded_spin(error_flag, [fl] { return __all(__hip_atomic_load(fl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u); });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -164,7 +135,10 @@ __global__ void __launch_bounds__(256) lstm_fwd_f32_persist_kernel(F32PersistFwd
       f32x4 hf[RING][4];
       auto issue = [&](int i) {
 #pragma unroll
-        for (int rg = 0; rg < 4; ++rg) hf[i % RING][rg] = f32p_load_sc1(hsrc, hoff + (rg * (H / 16) + i) * 1024);
+        for (int rg = 0; rg < 4; ++rg) {
+          const int o = hoff + (rg * (H / 16) + i) * 1024;
+          hf[i % RING][rg] = (CSN_F32_ABL & 2) ? f32p_no_operand(o) : load_sc1_b128<f32x4>(hsrc, o);
+        }
       };
 #pragma unroll
       for (int i = 0; i < RING; ++i) {
@@ -259,7 +233,7 @@ __global__ void __launch_bounds__(256) lstm_fwd_f32_persist_kernel(F32PersistFwd
       // whatever the clamped inputs gave -- finite, read only into their own, never stored, columns)
       const __amdgpu_buffer_rsrc_t hdst =
           __builtin_amdgcn_make_buffer_rsrc((void*)(a.h_blk + (size_t)(t + 1) * (bslot_bytes / 4)), 0, bslot_bytes, 0x00020000);
-      f32p_store_wt(hdst, ((((m0 >> 4) + wave) * (H / 16)) + slice) * 1024 + lane * 16, (f32x4){hn[0], hn[1], hn[2], hn[3]});
+      store_b128<true>(hdst, ((((m0 >> 4) + wave) * (H / 16)) + slice) * 1024 + lane * 16, (f32x4){hn[0], hn[1], hn[2], hn[3]});
     }
     CSN_F32STAMP(3);
     // publish: every storing wave drains, workgroup barrier (also frees `part`), one lane signals
@@ -347,7 +321,10 @@ __global__ void __launch_bounds__(256) lstm_bwd_f32_persist_kernel(F32PersistBwd
       f32x4 df[RING][4];
       auto issue = [&](int i) {
 #pragma unroll
-        for (int rg = 0; rg < 4; ++rg) df[i % RING][rg] = f32p_load_sc1(dsrc_r, doff + (rg * (G / 16) + i) * 1024);
+        for (int rg = 0; rg < 4; ++rg) {
+          const int o = doff + (rg * (G / 16) + i) * 1024;
+          df[i % RING][rg] = (CSN_F32_ABL & 2) ? f32p_no_operand(o) : load_sc1_b128<f32x4>(dsrc_r, o);
+        }
       };
 #pragma unroll
       for (int i = 0; i < RING; ++i) {
@@ -411,10 +388,10 @@ __global__ void __launch_bounds__(256) lstm_bwd_f32_persist_kernel(F32PersistBwd
       const __amdgpu_buffer_rsrc_t ddst =
           __builtin_amdgcn_make_buffer_rsrc((void*)(a.dg_blk + (size_t)t * (bslot_bytes / 4)), 0, bslot_bytes, 0x00020000);
       const int o = ((((m0 >> 4) + wave) * (G / 16)) + slice) * 1024 + lane * 16;
-      f32p_store_wt(ddst, o, (f32x4){dai[0], dai[1], dai[2], dai[3]});
-      f32p_store_wt(ddst, o + KSB * 1024, (f32x4){daf[0], daf[1], daf[2], daf[3]});
-      f32p_store_wt(ddst, o + 2 * KSB * 1024, (f32x4){dag[0], dag[1], dag[2], dag[3]});
-      f32p_store_wt(ddst, o + 3 * KSB * 1024, (f32x4){dao[0], dao[1], dao[2], dao[3]});
+      store_b128<true>(ddst, o, (f32x4){dai[0], dai[1], dai[2], dai[3]});
+      store_b128<true>(ddst, o + KSB * 1024, (f32x4){daf[0], daf[1], daf[2], daf[3]});
+      store_b128<true>(ddst, o + 2 * KSB * 1024, (f32x4){dag[0], dag[1], dag[2], dag[3]});
+      store_b128<true>(ddst, o + 3 * KSB * 1024, (f32x4){dao[0], dao[1], dao[2], dao[3]});
     }
     auto cold_stores = [&]() {
     if (row_ok) {      // the row-major result the GEMMs behind the recurrence read

@@ -32,25 +32,12 @@
 #include "csn_common.h"
 #include "lstm_cell_common.h"
 #include "lstm_cell_blk.h"
+#include "lstm_handoff.h"
 #include "lstm_ns_util.h"
 
+#define CSN_NSTAMP(i) CSN_HANDOFF_STAMP(g_nstamps, CSN_STAMP_BLOCK, i)
 #ifdef CSN_PSTAMPS
-#ifndef CSN_STAMP_BLOCK
-#define CSN_STAMP_BLOCK 11
-#endif
 __device__ unsigned long long g_nstamps[16];
-#define CSN_NSTAMP(i)                                                          \
-  do {                                                                         \
-    __builtin_amdgcn_sched_barrier(0);                                         \
-    if (tid == 0 && blockIdx.x == CSN_STAMP_BLOCK) {                           \
-      const unsigned long long now_ = wall_clock64();                          \
-      atomicAdd(&g_nstamps[i], now_ - last_);                                  \
-      last_ = now_;                                                            \
-    }                                                                          \
-    __builtin_amdgcn_sched_barrier(0);                                         \
-  } while (0)
-#else
-#define CSN_NSTAMP(i)
 #endif
 
 namespace csn {
@@ -262,7 +249,7 @@ __device__ __forceinline__ void ns_recurrence(const PersistFwdArgs& a, const Per
 #endif
 #pragma unroll
       for (int i = 0; i < GI; ++i) {
-        stg[buf][i] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(hdst_rsrc, lane * 16, sbase + kb_next * 1024, 16));
+        stg[buf][i] = load_sc1_b128<bf16x8>(hdst_rsrc, lane * 16, sbase + kb_next * 1024);
         kb_next = kb_next + 1 == KB ? 0 : kb_next + 1;
       }
     };
@@ -271,15 +258,7 @@ __device__ __forceinline__ void ns_recurrence(const PersistFwdArgs& a, const Per
       // (t = 0 with a state: h0 in slot 0 was written before the launch -- no wait)
       if (t > 0) {
         const unsigned* fl = flags + (size_t)t * flag_step + (lane < nslices ? lane : 0);
-        const unsigned long long t_begin = wall_clock64();
-        while (!__all(__hip_atomic_load(fl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u)) {
-          __builtin_amdgcn_s_sleep(1);
-          if (__hip_atomic_load(a.error_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) break;
-          if (wall_clock64() - t_begin > kNsSpinTimeoutTicks) {
-            __hip_atomic_store(a.error_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            break;
-          }
-        }
+        bounded_spin(a.error_flag, [fl] { return __all(__hip_atomic_load(fl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u); });
       }
       CSN_NSTAMP(0);   // wait for h_{t-1}
       if constexpr (HDMA) {
@@ -417,31 +396,31 @@ __device__ __forceinline__ void ns_recurrence(const PersistFwdArgs& a, const Per
       // the hand-off payload first: plain stores stay in this XCD's L2 (L2-local groups), write-through otherwise
       {
         const int rg = tid >> 6, r15 = tid & 15, q = (tid >> 4) & 3;
-        const nu32x4 v = *reinterpret_cast<const nu32x4*>(sh + (rg * 16 + r15) * 80 + q * 16);
+        const u32x4 v = *reinterpret_cast<const u32x4*>(sh + (rg * 16 + r15) * 80 + q * 16);
         const unsigned hoff = (unsigned)(((size_t)(t + 1 - t_first) * slab + ((size_t)((m0 >> 4) + rg) * KB + slice) * 512) * 2) + (unsigned)(tid & 63) * 16u;
-        if (local) ns_store_b128<false>(hdst_rsrc, hoff, v);
-        else ns_store_b128<true>(hdst_rsrc, hoff, v);
+        if (local) store_b128<false>(hdst_rsrc, hoff, v);
+        else store_b128<true>(hdst_rsrc, hoff, v);
       }
       {
         const int row = tid >> 2, q = tid & 3;
         if (m0 + row < B)
-          nt_store(reinterpret_cast<nu32x4*>(h_all + ((size_t)(t + 1) * B + m0 + row) * H + u0 + 8 * q),
-                   *reinterpret_cast<const nu32x4*>(sh + row * 80 + q * 16));
+          nt_store(reinterpret_cast<u32x4*>(h_all + ((size_t)(t + 1) * B + m0 + row) * H + u0 + 8 * q),
+                   *reinterpret_cast<const u32x4*>(sh + row * 80 + q * 16));
       }
 #pragma unroll
       for (int k = 0; k < 2; ++k) {
         const int idx = tid + 256 * k, row = idx >> 3, ch = idx & 7;
         if (m0 + row < B)
-          nt_store(reinterpret_cast<nu32x4*>(c_all + ((size_t)(t + 1) * B + m0 + row) * H + u0 + 4 * ch),
-                   *reinterpret_cast<const nu32x4*>(sc + row * 144 + ch * 16));
+          nt_store(reinterpret_cast<u32x4*>(c_all + ((size_t)(t + 1) * B + m0 + row) * H + u0 + 4 * ch),
+                   *reinterpret_cast<const u32x4*>(sc + row * 144 + ch * 16));
       }
       if (gates != nullptr) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           const int idx = tid + 256 * k, row = idx >> 4, ch = idx & 15;
           if (m0 + row < B)
-            nt_store(reinterpret_cast<nu32x4*>(gates + ((size_t)t * B + m0 + row) * 4 * H + 4 * (size_t)u0 + 8 * ch),
-                     *reinterpret_cast<const nu32x4*>(sg + row * 288 + ch * 16));
+            nt_store(reinterpret_cast<u32x4*>(gates + ((size_t)t * B + m0 + row) * 4 * H + 4 * (size_t)u0 + 8 * ch),
+                     *reinterpret_cast<const u32x4*>(sg + row * 288 + ch * 16));
         }
       }
     }
@@ -487,30 +466,9 @@ __global__ void __launch_bounds__(256) lstm_fwd_ns_kernel(PersistFwdArgs a) {
   const PersistFwdSlot& S = a.slot[grp / MT];
   const int mt = grp % MT;
 
-  // ---- is this group on one XCD?  (lstm_fwd_persist.hip)
+  // ---- is this group on one XCD?  (lstm_handoff.h)
   bool local = false;
-  if (a.xcd_groups && a.agree != nullptr) {
-    if (tid == 0) {
-      const unsigned xcc = __builtin_amdgcn_s_getreg(6164) & 7u;        // hwreg(HW_REG_XCC_ID, 0, 4)
-      const unsigned long long mine = 1ull | (1ull << (8 + 6 * xcc));
-      __hip_atomic_fetch_add(a.agree + grp, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const unsigned long long t_begin = wall_clock64();
-      unsigned long long v;
-      while (((v = __hip_atomic_load(a.agree + grp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) & 0xffull) <
-             (unsigned long long)nslices) {
-        __builtin_amdgcn_s_sleep(1);
-        if (__hip_atomic_load(a.error_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) break;
-        if (wall_clock64() - t_begin > kNsSpinTimeoutTicks) {
-          __hip_atomic_store(a.error_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          break;
-        }
-      }
-      ((__attribute__((address_space(3))) int*)(__attribute__((address_space(3))) void*)smem)[0] = (int)(((v >> (8 + 6 * xcc)) & 63ull) == (unsigned long long)nslices);
-    }
-    __syncthreads();
-    local = ((__attribute__((address_space(3))) int*)(__attribute__((address_space(3))) void*)smem)[0] != 0;    // (LDS address space: no flat_ instruction in these kernels -- FLAT retires out of order)
-    __syncthreads();
-  }
+  if (a.xcd_groups && a.agree != nullptr) local = CSN_XCD_GROUP_IS_LOCAL(unsigned long long, a, grp, nslices, smem);
 #ifdef CSN_PSTAMPS
   if (tid == 0 && blockIdx.x == CSN_STAMP_BLOCK) atomicAdd(&g_nstamps[6], wall_clock64() - t_entry_);
 #endif

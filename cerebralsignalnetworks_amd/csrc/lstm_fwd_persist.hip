@@ -37,33 +37,20 @@
 // (12.8 us per step: the half-size loads are latency-bound), so the whole tile advances together.
 // All workgroups of a launch must be co-resident (1 per CU);
 // every spin is bounded: after kSpinTimeoutTicks the workgroup raises *error_flag (sticky: later
-// waits return immediately) so a scheduling accident ends in a reported error, never in a hang.
+// waits return immediately) so a scheduling accident ends in a reported error, never in a hang.  The waits, the
+// agreement and the status words are those of lstm_handoff.h, for all four weight-stationary kernels: no wait in them is
+// written by hand.
 #include "csn_common.h"
 #include "lstm_cell_common.h"
 #include "lstm_cell_blk.h"
+#include "lstm_handoff.h"
 
+#define CSN_PSTAMP(i) CSN_HANDOFF_STAMP(g_pstamps, CSN_STAMP_BLOCK, i)
 #ifdef CSN_PSTAMPS
-#ifndef CSN_STAMP_BLOCK
-#define CSN_STAMP_BLOCK 11     // group 3 (layer 0 at cfg2), slice 1; 15 = group 7 (layer 1)
-#endif
-// diagnostic build only (tools/persist_bench.hip): per-phase wall-clock sums of workgroup (0,0)
+// diagnostic build only (tools/persist_bench.hip): per-phase wall-clock sums of workgroup CSN_STAMP_BLOCK
 __device__ unsigned long long g_pstamps[16];
 __device__ unsigned long long g_span[5] = {~0ull, 0ull, ~0ull, 0ull, 0ull};
 __device__ unsigned long long g_grp_alive[32];      // [0..7] ticks alive summed per group (slice 0 only), [8..15] launches, [16..23] ticks in the step loop, [24..31] steps
-#define CSN_PSTAMP(i)                                                          \
-  do {                                                                         \
-    __builtin_amdgcn_sched_barrier(0);                                         \
-    if (tid == 0 && blockIdx.x == CSN_STAMP_BLOCK) {                           \
-      const unsigned long long now_ = wall_clock64();                          \
-      atomicAdd(&g_pstamps[i], now_ - last_);                                  \
-      last_ = now_;                                                            \
-    }                                                                          \
-    __builtin_amdgcn_sched_barrier(0);                                         \
-  } while (0)
-#else
-#define CSN_PSTAMP(i)
-#endif
-#ifdef CSN_PSTAMPS
 // (diagnostic: how long the launch's waves were alive -- first entry to last exit over all workgroups -- to set against
 // the duration rocprofv3 reports for the dispatch, which also holds the dispatch itself and the end-of-kernel cache
 // write-back)
@@ -92,18 +79,7 @@ __device__ __forceinline__ void span_exit(unsigned long long t_entry) {
 
 namespace csn {
 
-static constexpr unsigned long long kSpinTimeoutTicks = 20000000ull;   // 0.2 s of the 100 MHz wall clock
-
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 typedef __attribute__((ext_vector_type(2))) float f32x2;
-
-__device__ __forceinline__ bf16x8 load_sc1_b128(__amdgpu_buffer_rsrc_t rsrc, int byte_off, int soff = 0) {
-  // aux = 16: sc1 (agent-coherent, bypasses this CU's L1; MI355X_MICROARCH.md visibility table)
-  u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, byte_off, soff, 16);
-  union { u32x4 u; bf16x8 b; } cvt;
-  cvt.u = v;
-  return cvt.b;
-}
 
 // CSN_SLAB_TAGS (`make tags`, a DEBUG library): every 8-byte hand-off piece carries, in the lowest mantissa bit of
 // its first element, bit 2 of the step it belongs to.  The previous occupant of a ring slot is the piece of step
@@ -125,23 +101,6 @@ __device__ __forceinline__ void store_wt_b64(bf16_t* p, const float (&v)[4], int
 
 __device__ __forceinline__ void store_plain_b64(bf16_t* p, const float (&v)[4], int tag) {
   *reinterpret_cast<unsigned long long*>(p) = pack_h_piece(v, tag);
-}
-
-// Bounded wait of one lane until *p (read with relaxed agent-scope = sc1 loads, which bypass this CU's L1)
-// satisfies `done`; returns the last value read.  On time-out raises the sticky error flag.
-template <typename T, typename Pred>
-__device__ __forceinline__ T bounded_poll(const T* p, unsigned* error_flag, Pred done) {
-  const unsigned long long t_begin = wall_clock64();
-  T v;
-  while (!done(v = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
-    __builtin_amdgcn_s_sleep(1);
-    if (__hip_atomic_load(error_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) break;
-    if (wall_clock64() - t_begin > kSpinTimeoutTicks) {
-      __hip_atomic_store(error_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      break;
-    }
-  }
-  return v;
 }
 
 #ifndef CSN_FWD_RING
@@ -228,23 +187,9 @@ __global__ void __launch_bounds__(256) lstm_fwd_persist_kernel(PersistFwdArgs a)
   // EXEC, so under a mere EXEC mask it would execute in every wave)
   const bool xwave = fused && __builtin_amdgcn_readfirstlane(wave) < xkb;
 
-  // ---- is this group on one XCD?  Every workgroup adds (1, 1 << its XCC field) to the group's word and
-  // waits for all `nslices` arrivals; all of them then see the same word and take the same decision.
+  // ---- is this group on one XCD?  (lstm_handoff.h)
   bool local = false;
-  if (a.xcd_groups && a.agree != nullptr) {
-    if (tid == 0) {
-      const unsigned xcc = __builtin_amdgcn_s_getreg(6164) & 7u;        // hwreg(HW_REG_XCC_ID, 0, 4)
-      const unsigned long long mine = 1ull | (1ull << (8 + 6 * xcc));
-      __hip_atomic_fetch_add(a.agree + grp, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const unsigned long long v = bounded_poll(a.agree + grp, a.error_flag, [&](unsigned long long x) {
-        return (unsigned)(x & 0xffull) >= (unsigned)nslices;
-      });
-      ((__attribute__((address_space(3))) int*)(__attribute__((address_space(3))) void*)red)[0] = (int)(((v >> (8 + 6 * xcc)) & 63ull) == (unsigned long long)nslices);
-    }
-    __syncthreads();
-    local = ((__attribute__((address_space(3))) int*)(__attribute__((address_space(3))) void*)red)[0] != 0;    // (LDS address space: no flat_ instruction in these kernels -- FLAT retires out of order)
-    __syncthreads();
-  }
+  if (a.xcd_groups && a.agree != nullptr) local = CSN_XCD_GROUP_IS_LOCAL(unsigned, a, grp, nslices, red);
 
   // ---- stationary operands: this wave's K quarter of the workgroup's W_hh rows --------------
   // The workgroups of a group all read the same h slab; each walks its k-blocks from its own offset (register i
@@ -423,16 +368,11 @@ __global__ void __launch_bounds__(256) lstm_fwd_persist_kernel(PersistFwdArgs a)
           fl = flags + (size_t)t * flag_step + wave * npw + (lane < npw ? lane : 0);
         }
         const unsigned not_yet = dpoll ? 0xffffffffu : 0u;
-        const unsigned long long t_begin = wall_clock64();
         // (data_polls == 2, a test switch: no hint, load straight away -- every step then goes through the re-read path)
-        while (wait && !(dpoll && CSN_DPOLL_MODE(a.data_polls) == 2) && !__all(__hip_atomic_load(fl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != not_yet)) {
-          __builtin_amdgcn_s_sleep(1);
-          if (__hip_atomic_load(a.error_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) break;
-          if (wall_clock64() - t_begin > kSpinTimeoutTicks) {
-            __hip_atomic_store(a.error_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            break;
-          }
-        }
+        const bool spin = wait && !(dpoll && CSN_DPOLL_MODE(a.data_polls) == 2);
+        bounded_spin(a.error_flag, [fl, not_yet, spin] {
+          return !spin || __all(__hip_atomic_load(fl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != not_yet);
+        });
       }
       CSN_PSTAMP(0);   // wait for h_{t-1}
       const int base = (int)((slot_in * slab + ((size_t)(m0 >> 4) * kblocks + ks_beg) * 512 + lane * 8) * 2);
@@ -453,7 +393,7 @@ __global__ void __launch_bounds__(256) lstm_fwd_persist_kernel(PersistFwdArgs a)
       int kbo = rot_t * 1024;
       auto issue_group = [&](int slot) {
 #pragma unroll
-        for (int rg = 0; rg < RG; ++rg) hf[slot][rg] = load_sc1_b128(hsrc, base + rg * kblocks * 1024, kbo);
+        for (int rg = 0; rg < RG; ++rg) hf[slot][rg] = load_sc1_b128<bf16x8>(hsrc, base + rg * kblocks * 1024, kbo);
         kbo = kbo + 1024 == KS * 1024 ? 0 : kbo + 1024;
       };
 #pragma unroll
@@ -476,16 +416,16 @@ __global__ void __launch_bounds__(256) lstm_fwd_persist_kernel(PersistFwdArgs a)
             return __all(ok);
           };
           if (wait && __builtin_expect(!whole(), 0)) {
-            const unsigned long long t_begin = wall_clock64();
+            const unsigned long long t0 = wall_clock64();
             do {
               __builtin_amdgcn_s_sleep(1);
 #pragma unroll
-              for (int rg = 0; rg < RG; ++rg) hf[ks % RING][rg] = load_sc1_b128(hsrc, base + (rg * kblocks + (ks + rot) % KS) * 1024);
-              if (wall_clock64() - t_begin > kSpinTimeoutTicks) {
-                __hip_atomic_store(a.error_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+              for (int rg = 0; rg < RG; ++rg) hf[ks % RING][rg] = load_sc1_b128<bf16x8>(hsrc, base + (rg * kblocks + (ks + rot) % KS) * 1024);
+              if (spin_expired(t0)) {
+                raise_timeout(a.error_flag);
                 break;
               }
-            } while (!whole() && __hip_atomic_load(a.error_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u);
+            } while (!whole() && status_clear(a.error_flag));
           }
         }
 #ifdef CSN_SLAB_TAGS
@@ -497,7 +437,7 @@ __global__ void __launch_bounds__(256) lstm_fwd_persist_kernel(PersistFwdArgs a)
             const u32x4 u = __builtin_bit_cast(u32x4, hf[ks % RING][rg]);
             stale |= (u[0] != 0xffffffffu && (u[0] & 1u) != want) | (u[2] != 0xffffffffu && (u[2] & 1u) != want);
           }
-          if (__any(stale) && lane == 0) __hip_atomic_store(a.error_flag + 2, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          if (__any(stale) && lane == 0) raise_status(a.error_flag, kStatusStaleSlot);
         }
 #endif
 #pragma unroll

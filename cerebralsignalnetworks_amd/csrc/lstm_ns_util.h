@@ -1,13 +1,11 @@
 // Device helpers of the N-split weight-stationary forward kernel (lstm_fwd_ns.hip).
 #pragma once
 #include "csn_common.h"
+#include "lstm_handoff.h"
 
 namespace csn {
 
-static constexpr unsigned long long kNsSpinTimeoutTicks = 20000000ull;   // 0.2 s of the 100 MHz wall clock
 static constexpr int kNsStageBytes = 64 * (288 + 144 + 80);               // padded rows of gates (bf16 x 4) + c (f32) + h (bf16) of 64 x 32 cells
-
-typedef __attribute__((ext_vector_type(4))) unsigned nu32x4;
 
 // (OFF: instruction offset, added to the global AND the LDS address: four consecutive 1 KB pieces share one M0 / soffset;
 // AUX: cache policy bits of the load -- 16 = sc1 for hand-off data, 0 = default for data that should stay in L2)
@@ -19,13 +17,13 @@ __device__ __forceinline__ void ns_dma16_sc1(__amdgpu_buffer_rsrc_t rsrc, void* 
   __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds, 16, voffset, soffset, OFF, AUX);
 }
 __device__ __forceinline__ f32x4 ns_bload_nt_f32x4(__amdgpu_buffer_rsrc_t rsrc, int voffset, int soffset) {
-  nu32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voffset, soffset, 2);     // aux 2 = nt (streamed once)
+  u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voffset, soffset, 2);     // aux 2 = nt (streamed once)
   return __builtin_bit_cast(f32x4, v);
 }
 __device__ __forceinline__ bf16x8 ns_lds_read_b128(unsigned addr) {
   bf16x8 v;
 #if defined(CSN_NS_ABL) && CSN_NS_ABL >= 2
-  v = __builtin_bit_cast(bf16x8, (nu32x4){addr, addr + 1u, addr + 2u, addr + 3u});   // ablation (timing only): no LDS reads
+  v = __builtin_bit_cast(bf16x8, (u32x4){addr, addr + 1u, addr + 2u, addr + 3u});   // ablation (timing only): no LDS reads
 #else
   asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr) : "memory");
 #endif
@@ -60,11 +58,6 @@ __device__ __forceinline__ void ns_mfma(f32x4& acc, const bf16x8& w, const bf16x
 // (the hazard recogniser does not see inside inline asm: explicit wait states where a VALU result feeds the first MFMA
 // of a phase, and where the last MFMA's result is read back -- 16-pass MFMA: up to 18 wait states)
 __device__ __forceinline__ void ns_mfma_fence() { asm volatile("s_nop 15\n\ts_nop 7" ::: "memory"); }
-
-template <bool WT>
-__device__ __forceinline__ void ns_store_b128(__amdgpu_buffer_rsrc_t rsrc, unsigned byte_off, const nu32x4& v) {
-  __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, (int)byte_off, 0, WT ? 16 : 0);   // sc1 = write-through
-}
 
 // A pointer that is the same in every lane, told to the compiler (it arrives through a dynamically indexed kernel
 // argument, which the compiler otherwise keeps in VGPRs: a buffer resource built from it would be "divergent" and every

@@ -61,16 +61,29 @@ def test_a_diff_prints_both_histograms(tmp_path):
     rc, text = _run([old, "--", regs])
     assert rc == 0 and "DIFF  _Z9gemm_nt_av" in text and "histograms equal: 4 instructions, 4 mnemonics" in text, text
     assert "SAME  _Z9gemm_tn_bv" in text
+    assert "lines changed: 2" in text and "descriptor equal: 1 directives" in text, text      # one line out, one line in
     assert _run(["--strict", old, "--", regs])[0] == 1
+    # two instructions that swapped places: the histogram cannot tell, the line count and the descriptor can
+    swapped = BODY_A.replace("\tv_add_u32_e32 v1, v2, v3\n\ts_cbranch_execz .LBB{n}_2\n", "\ts_cbranch_execz .LBB{n}_2\n\tv_add_u32_e32 v1, v2, v3\n")
+    assert swapped != BODY_A
+    swap = _listing(tmp_path, "swap.s", [("_Z9gemm_nt_av", swapped), ("_Z9gemm_tn_bv", BODY_B)])
+    rc, text = _run([old, "--", swap])
+    assert "histograms equal" in text and "lines changed: 2" in text and "descriptor equal" in text, text
     more = _listing(tmp_path, "more.s", [("_Z9gemm_nt_av", BODY_A), ("_Z9gemm_tn_bv", "\ts_nop 0\n" + BODY_B)])
     rc, text = _run([old, "--", more])
     lines = text.splitlines()
     at = lines.index(next(ln for ln in lines if ln.startswith("DIFF  _Z9gemm_tn_bv")))
     assert lines[at + 1].split() == ["s_nop", "0", "->", "1"], text
+    assert lines[at + 2].split() == ["lines", "changed:", "1"] and lines[at + 3].split()[:2] == ["descriptor", "equal:"], text
     # the resource descriptor counts: the same instructions on more registers are not the same kernel
     wider = _listing(tmp_path, "wider.s", [("_Z9gemm_nt_av", BODY_A), ("_Z9gemm_tn_bv", BODY_B)], vgprs={"_Z9gemm_tn_bv": 16})
     rc, text = _run([old, "--", wider])
     assert "DIFF  _Z9gemm_tn_bv" in text and "histograms equal" in text
+    assert "descriptor equal" not in text, text
+    at = text.splitlines().index(next(ln for ln in text.splitlines() if ln.startswith("DIFF  _Z9gemm_tn_bv")))
+    assert [ln.split() for ln in text.splitlines()[at + 1:at + 4]] == [
+        ["histograms", "equal:", "3", "instructions,", "3", "mnemonics"], ["lines", "changed:", "2"],
+        [".amdhsa_next_free_vgpr", "8", "->", "16"]], text
     # --match narrows what is compared
     rc, text = _run(["--match", "gemm_nt", old, "--", more])
     assert rc == 0 and "gemm_tn" not in text and "1 kernels: 0 missing, 0 differ" in text

@@ -8,12 +8,16 @@ objects.  A kernel is the text from its label to its `.Lfunc_end`, plus its `.am
 scratch).  Before comparing, comments are stripped and the function ordinal is dropped from local labels (`.LBB12_3` ->
 `.LBB_3`, `.Lfunc_end12` -> `.Lfunc_end`): the ordinal is the function's position in its file and changes when a file is
 split or a function moves.  One line per kernel: SAME or DIFF; for a DIFF the instruction-mnemonic histogram of both
-sides (the mnemonics whose counts differ, or `histograms equal` when only registers or the order changed).
+sides (the mnemonics whose counts differ, or `histograms equal` when only registers or the order changed), then the
+number of lines that changed (lines only in the old text + lines only in the new one: two instructions that swapped
+places are 2) and the `.amdhsa_*` descriptor lines that changed, or `descriptor equal` -- which is what tells a swapped
+instruction pair from another register allocation.
 
 Exit status: 1 when a kernel that matches is present on one side only (--rename maps an old name to its new one first),
 or with --strict when any kernel differs; 0 otherwise."""
 import argparse
 import collections
+import difflib
 import re
 import sys
 
@@ -60,6 +64,17 @@ def histogram(lines):
     return h
 
 
+def changed_lines(old, new):
+    """Lines of `old` that are not in `new` at their place + lines of `new` that are not in `old`."""
+    ops = difflib.SequenceMatcher(None, old, new, autojunk=False).get_opcodes()
+    return sum((i2 - i1) + (j2 - j1) for tag, i1, i2, j1, j2 in ops if tag != "equal")
+
+
+def descriptor(lines):
+    """{.amdhsa_* directive: its operand text} of a kernel."""
+    return {ln.split()[0]: " ".join(ln.split()[1:]) for ln in lines if ln.startswith(".amdhsa_") and not ln.startswith(".amdhsa_kernel")}
+
+
 def _side(paths, match, renames):
     out = {}
     for p in paths:
@@ -90,6 +105,13 @@ def compare(old_paths, new_paths, match=DEFAULT_MATCH, renames=None, out=None):
             for m in sorted(set(ho) | set(hn)):
                 if ho[m] != hn[m]:
                     print(f"      {m:40s} {ho[m]:6d} -> {hn[m]:6d}", file=out)
+            print(f"      lines changed: {changed_lines(old[name], new[name])}", file=out)
+            do, dn = descriptor(old[name]), descriptor(new[name])
+            if do == dn:
+                print(f"      descriptor equal: {len(dn)} directives", file=out)
+            for d in sorted(set(do) | set(dn)):
+                if do.get(d) != dn.get(d):
+                    print(f"      {d:40s} {do.get(d, '-'):>6s} -> {dn.get(d, '-'):>6s}", file=out)
     print(f"{len(set(old) | set(new))} kernels: {len(missing)} missing, {len(differing)} differ", file=out)
     return missing, differing
 
