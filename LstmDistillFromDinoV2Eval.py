@@ -58,7 +58,7 @@ def main(argv=None):
     dtype = torch.bfloat16 if FLAGS.dtype == "bf16" else torch.float32
     model = Model(input_size=C, lstm_size=FLAGS.hidden_size, lstm_layers=FLAGS.lstm_layers,
                   output_size=FLAGS.output_size, include_top=False, compute_dtype=dtype,
-                  resident=FLAGS.resident_lstm).to(device)
+                  resident=FLAGS.resident_lstm, readout=FLAGS.readout).to(device)
     if FLAGS.custom_model_weights:
         print(load_checkpoint_into(model, FLAGS.custom_model_weights))
     sos = EEGFilters(FLAGS.fs, order=FLAGS.filter_order).sos if FLAGS.filter_order else None

@@ -97,6 +97,9 @@ def build_parser(flavour=PERILS):
     p.add_argument('--resident_lstm', action='store_true',
                    help='hidden_size <= 128: the LSTM runs the steps of a chunk inside one launch per layer, W_hh in '
                         'registers (CSN_LSTM_RESIDENT plans), with the bits of the per-step cell kernels')
+    p.add_argument('--readout', type=str, default="last", choices=["last", "mean", "max"],
+                   help='what fc reads of the LSTM output sequence: its last step, or its mean / maximum over time, reduced '
+                        'inside the library (no parameter depends on it; evaluate a checkpoint with the readout it was trained with)')
     p.add_argument('--output_size', type=int, default=384)
     p.add_argument('--loss', type=str, default=flavour.loss, choices=["featdist", "cosine", "kd", "barlow", "contrastive"])
     p.add_argument('--contrastive_temperature', type=float, default=0.07,
@@ -235,7 +238,8 @@ def main(argv=None, flavour=PERILS):
     include_top = FLAGS.loss == "featdist"
     model = Model(input_size=C, lstm_size=FLAGS.hidden_size, lstm_layers=FLAGS.lstm_layers,
                   output_size=features_length, include_top=include_top, compute_dtype=dtype,
-                  dropout=FLAGS.lstm_dropout, bidirectional=FLAGS.bidirectional, resident=FLAGS.resident_lstm).to(device)
+                  dropout=FLAGS.lstm_dropout, bidirectional=FLAGS.bidirectional, resident=FLAGS.resident_lstm,
+                  readout=FLAGS.readout).to(device)
     if flavour.name == "spampinato":
         if os.path.exists(FLAGS.custom_model_weights):           # :369-371: resume only if the file is there, strict keys
             model.load_state_dict(torch.load(FLAGS.custom_model_weights, map_location="cpu", weights_only=True))

@@ -70,6 +70,9 @@ def build_parser():
     p.add_argument('--resident_lstm', action='store_true',
                    help='embed_dim <= 128: student and teacher LSTMs run the steps of a chunk inside one launch per layer, '
                         'W_hh in registers (CSN_LSTM_RESIDENT plans), with the bits of the per-step cell kernels')
+    p.add_argument('--readout', type=str, default="last", choices=["last", "mean", "max"],
+                   help='what the heads read of the LSTM output sequence of student and teacher: its last step, or its mean / '
+                        'maximum over time, reduced inside the library')
     p.add_argument('--dtype', type=str, default="bf16", choices=["bf16", "f32"])
     p.add_argument('--time_low', type=int, default=0)
     p.add_argument('--time_high', type=int, default=495)
@@ -123,7 +126,7 @@ def main(argv=None):
     def make(dropout=0.0):
         backbone = Model(input_size=C, lstm_size=FLAGS.embed_dim, lstm_layers=FLAGS.lstm_layers,
                          output_size=FLAGS.embed_dim, include_top=False, compute_dtype=dtype, dropout=dropout,
-                         bidirectional=FLAGS.bidirectional, resident=FLAGS.resident_lstm)
+                         bidirectional=FLAGS.bidirectional, resident=FLAGS.resident_lstm, readout=FLAGS.readout)
         return backbone
     # (MultiCropWrapper replaces the backbone's fc by the identity: the head reads the encoder's feature itself)
     feat_dim = (2 if FLAGS.bidirectional else 1) * FLAGS.embed_dim

@@ -61,6 +61,7 @@ SIGNATURES = {
     "csn_lstm_plan_set_views": (_c_int, [_c_void_p, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
                                          ctypes.c_int32, ctypes.c_int32]),
     "csn_lstm_plan_set_io": (_c_int, [_c_void_p, _c_i64, _c_i64, _c_int]),
+    "csn_lstm_plan_set_readout": (_c_int, [_c_void_p, _c_int]),
     "csn_lstm_plan_set_dropout": (_c_int, [_c_void_p, _c_float, ctypes.c_uint64, ctypes.c_uint32]),
     "csn_lstm_plan_set_output_dropout": (_c_int, [_c_void_p, _c_float, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint64,
                                                   _c_i64]),
@@ -396,6 +397,19 @@ def _ptr_array(tensors):
     return arr
 
 
+READOUT_LAST, READOUT_MEAN, READOUT_MAX = 0, 1, 2      # csn_lstm_plan_set_readout (include/csn_hip.h)
+READOUTS = {"last": READOUT_LAST, "mean": READOUT_MEAN, "max": READOUT_MAX}
+
+
+def readout_mode(readout):
+    """"last" / "mean" / "max" (or a READOUT_* integer) -> the mode of csn_lstm_plan_set_readout; anything else is refused."""
+    if isinstance(readout, str) and readout in READOUTS:
+        return READOUTS[readout]
+    if isinstance(readout, int) and not isinstance(readout, bool) and readout in READOUTS.values():
+        return readout
+    raise CsnError(f"LSTM readout must be one of {sorted(READOUTS)}, got {readout!r}")
+
+
 class LstmPlan:
     """One stacked-LSTM problem: a native plan handle (csn_lstm_plan_create: layout, switches, side streams, events
     -- all per plan, the library has no global state) + one workspace; forward()/backward() enqueue on the
@@ -508,6 +522,12 @@ class LstmPlan:
         gradient to dx over the valid steps.  Sticky until set again."""
         _check(load().csn_lstm_plan_set_io(self._plan, int(y_all_pitch), int(dy_all_pitch), int(bool(dx_add))))
         self._io = (int(y_all_pitch), int(dy_all_pitch), bool(dx_add))
+
+    def set_readout(self, mode):
+        """What y_last of the following forward() calls is and where dy_last of the following backward() calls enters
+        (csn_lstm_plan_set_readout): "last" (the default), "mean" or "max" over each row's valid steps, or the
+        READOUT_* integer.  Sticky until set again; a backward must run with the setting of its forward."""
+        _check(load().csn_lstm_plan_set_readout(self._plan, readout_mode(mode)))
 
     def _pitched(self, t, pitch, name):
         """t must be a float32 [B,T,H] device view with strides (T * pitch, pitch, 1), 16-byte aligned."""

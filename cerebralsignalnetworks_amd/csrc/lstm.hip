@@ -370,6 +370,8 @@ struct csnLstmPlan {
   int resident = 0;                      // created with CSN_LSTM_RESIDENT: path 0's layout, the recurrence of lstm_resident.hip
   int64_t y_pitch = 0, dy_pitch = 0;     // csn_lstm_plan_set_io: elements per (b, t) row of y_all / dy_all, 0 = dense (H)
   int dx_add = 0;                        // csn_lstm_plan_set_io: dx is added to over the valid steps, not overwritten
+  int readout = CSN_READOUT_LAST;        // csn_lstm_plan_set_readout: what y_last is, and where dy_last enters
+  int32_t* argmax_dev = nullptr;         // [B, H] int32 owned by the plan: the MAX backward's argmax, written and read in stream order
   // csn_lstm_plan_set_output_dropout (sticky; p = 0 = off): the mask the layout passes apply to y_all as they store it and
   // to dy_all as they load it, indexed on the caller's tensor
   float out_drop_p = 0.f;
@@ -452,6 +454,7 @@ extern "C" void csn_lstm_plan_destroy(csnLstmPlan* P) {
   if (P->view_ev) (void)hipEventDestroy(P->view_ev);
   if (P->view_pin) (void)hipHostFree(P->view_pin);
   if (P->view_dev) (void)hipFree(P->view_dev);
+  if (P->argmax_dev) (void)hipFree(P->argmax_dev);
   if (switched) (void)hipSetDevice(cur);
   delete P;
 }
@@ -596,6 +599,13 @@ extern "C" int csn_lstm_plan_set_io(csnLstmPlan* P, int64_t y_all_pitch, int64_t
   P->y_pitch = y_all_pitch == P->d.H ? 0 : y_all_pitch;
   P->dy_pitch = dy_all_pitch == P->d.H ? 0 : dy_all_pitch;
   P->dx_add = dx_add != 0;
+  return CSN_OK;
+}
+
+extern "C" int csn_lstm_plan_set_readout(csnLstmPlan* P, int mode) {
+  CSN_REQUIRE(P != nullptr, "csn_lstm_plan_set_readout: null plan");
+  CSN_REQUIRE(mode == CSN_READOUT_LAST || mode == CSN_READOUT_MEAN || mode == CSN_READOUT_MAX, "csn_lstm_plan_set_readout: unknown mode %d", mode);
+  P->readout = mode;
   return CSN_OK;
 }
 
@@ -1825,6 +1835,8 @@ static int emit_state(const Call& C, int l, float* h_n, float* c_n) {
   return CSN_OK;
 }
 static int emit_y_last(const Call& C, float* y_last) {
+  if (C.P.readout != CSN_READOUT_LAST)
+    return launch_pool_readout(C.ws + C.w.layer[C.NL - 1].h_all, C.dt, C.P.readout, y_last, row_map(C, C.H, 0), C.st);
   return launch_gather_state(C.ws + C.w.layer[C.NL - 1].h_all, C.dt, C.dlen, C.T, y_last, C.B, C.H, C.st);
 }
 static int emit_y_all(const Call& C, float* y_all) {
@@ -1896,9 +1908,24 @@ static int assemble_top_dy(const Call& C, BwdArgs& A, const float* dy_all) {
   const size_t BH = (size_t)C.B * C.H;
   const float* dh_top = A.dh_n ? A.dh_n + (C.NL - 1) * BH : nullptr;
   int rc;
-  if (dy_all || C.dlen) {
+  if (A.dy_last && C.P.readout != CSN_READOUT_LAST) {
+    // the pooled readout: dy_last reaches every valid step (MEAN) or the first maximum (MAX, found again in the saved h),
+    // inside the layout pass; then the top layer's dh_n at each row's end, as below
+    PoolIn pool{C.P.readout, A.dy_last, nullptr};
+    const RowMap m = row_map(C, C.H, C.P.dy_pitch);
+    if (pool.mode == CSN_READOUT_MAX) {
+      if (C.P.argmax_dev == nullptr) CSN_HIP_CHECK(hipMalloc((void**)&C.P.argmax_dev, BH * 4));
+      if ((rc = launch_pool_argmax(C.ws + C.w.layer[C.NL - 1].h_all, C.dt, C.P.argmax_dev, m, C.st))) return rc;
+      pool.argmax = C.P.argmax_dev;
+    }
     OutDropCfg od;
-    if ((rc = launch_dy_in(dy_all, buf, row_map(C, C.H, C.P.dy_pitch), out_drop_of(C, od), C.st))) return rc;
+    if ((rc = launch_dy_in(dy_all, buf, m, out_drop_of(C, od), &pool, C.st))) return rc;
+    if (dh_top && (rc = launch_add_at_end(dh_top, buf, C.dlen, C.T, 0, C.T - 1, C.B, C.H, C.st))) return rc;
+    A.dy_last = nullptr;
+    A.dy_tm = buf;
+  } else if (dy_all || C.dlen) {
+    OutDropCfg od;
+    if ((rc = launch_dy_in(dy_all, buf, row_map(C, C.H, C.P.dy_pitch), out_drop_of(C, od), nullptr, C.st))) return rc;
     if (A.dy_last && (rc = launch_add_at_end(A.dy_last, buf, C.dlen, C.T, 0, C.T - 1, C.B, C.H, C.st))) return rc;
     if (dh_top && (rc = launch_add_at_end(dh_top, buf, C.dlen, C.T, 0, C.T - 1, C.B, C.H, C.st))) return rc;
     A.dy_last = nullptr;
@@ -1980,8 +2007,9 @@ extern "C" int csn_lstm_backward(csnLstmPlan* Pp, const float* dy_last, const fl
       }
       // an empty row's dgates are zero at step 0: its dh0 is the gradient w.r.t. its h_n
       if (dlen && dh_n && (rc = launch_add_rows_len0(dh_n + l * BH, out, dlen, C.B, C.H, st))) return rc;
-      // ... and y_last of an empty row is h_n of the top layer, that is its h0: dy_last reaches dh0 there
-      if (dlen && dy_last && l == C.NL - 1 && (rc = launch_add_rows_len0(dy_last, out, dlen, C.B, C.H, st))) return rc;
+      // ... and y_last of an empty row is h_n of the top layer, that is its h0: dy_last reaches dh0 there (a pooled
+      // readout of an empty row is zero instead)
+      if (dlen && dy_last && P.readout == CSN_READOUT_LAST && l == C.NL - 1 && (rc = launch_add_rows_len0(dy_last, out, dlen, C.B, C.H, st))) return rc;
     }
     if (dc0) {
       // the carried dc (an empty row's passed every masked step as it was); without a step, dc_n itself

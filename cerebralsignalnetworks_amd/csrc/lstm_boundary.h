@@ -1,7 +1,8 @@
 // The API boundary of the stacked LSTM (lstm_boundary.hip): everything that turns the caller's batch-first float32 tensors
 // into the time-major workspace and back around the recurrence -- one kernel per layout pass (y_all out, dy_all in, dx out)
-// whatever the plan's lengths, direction, pitch, adding store or output dropout (DESIGN.md sections 10, 16 and 23), and the
-// small per-row helpers of variable-length batches.  lstm.hip calls the launchers below and launches none of this itself.
+// whatever the plan's lengths, direction, pitch, adding store or output dropout (DESIGN.md sections 10, 16 and 23), the
+// pooled readout (mean / max over time in place of the last step, section 26), and the small per-row helpers of
+// variable-length batches.  lstm.hip calls the launchers below and launches none of this itself.
 #pragma once
 #include "lstm_dropout.h"
 
@@ -28,13 +29,28 @@ struct RowSteps {
   __device__ __forceinline__ int64_t slot(int64_t t) const { return rev ? n - t : t + 1; }
 };
 
+// The pooled term of dy_in (csn_lstm_plan_set_readout): the gradient w.r.t. the pooled y_last, and under MAX the caller time
+// per (b, h) that receives it (launch_pool_argmax)
+struct PoolIn {
+  int mode;                // CSN_READOUT_*
+  const float* dy_last;    // [B, H]
+  const int* argmax;       // [B, H] int32, MAX only
+};
+
 // The launchers.  od: output dropout (csn_lstm_plan_set_output_dropout), or null.  With it a thread moves four consecutive h
 // under one Philox call with 16-byte accesses of the caller's tensor, which must be 16-B aligned with pitch % 4 == 0;
 // without it one element, and the caller's tensor needs the 4 bytes of a float.  A dropped element is a selected zero.
 // y[(b Tn + t) pitch + h] = t < n ? [keep ? scale *] float(h_all[slot(t)][b][h]) : 0      (h_all: dtype, time-major)
 int launch_y_out(const void* h_all, int dtype, float* y, const RowMap& m, const OutDropCfg* od, hipStream_t st);
 // dy_tm[s][b][h], s < Te  =  s < n && dy ? [keep ? scale *] dy[(b Tn + t) pitch + h] : 0      (dy null: all zeros)
-int launch_dy_in(const float* dy, float* dy_tm, const RowMap& m, const OutDropCfg* od, hipStream_t st);
+// pool (or null): + dy_last[b][h] / n (MEAN), + (argmax[b][h] == t ? dy_last[b][h] : 0) (MAX) for s < n, one float32 add behind
+// the dy element -- the term itself where dy is null
+int launch_dy_in(const float* dy, float* dy_tm, const RowMap& m, const OutDropCfg* od, const PoolIn* pool, hipStream_t st);
+// y[b][h] = mean (float64 sums, one rounding) or max (first maximum, a NaN wins) over t < n of float(h_all[slot(t)][b][h]);
+// zeros for n = 0.  m.pitch and m.Te are not read.  A fixed split of the steps: the same bits every call
+int launch_pool_readout(const void* h_all, int dtype, int mode, float* y, const RowMap& m, hipStream_t st);
+// argmax[b][h] = the first caller time t < n that attains that maximum (-1 for n = 0)
+int launch_pool_argmax(const void* h_all, int dtype, int* argmax, const RowMap& m, hipStream_t st);
 // dx[b][t][i] = or += dx_tm[s][b][i] for t < n; from n on zero, or with add left as it is      (m.H: the input width)
 int launch_dx_out(const float* dx_tm, float* dx, const RowMap& m, hipStream_t st);
 

@@ -1,6 +1,7 @@
 // The API boundary of the stacked LSTM: the batch-first <-> time-major layout passes around the recurrence and the per-row
-// helpers of variable-length batches (lstm_boundary.h; DESIGN.md sections 10, 16 and 23).  All of it is bandwidth-bound
-// element movement; the only arithmetic is the float32 multiply of output dropout and the adding stores.
+// helpers of variable-length batches (lstm_boundary.h; DESIGN.md sections 10, 16, 23 and 26).  All of it is bandwidth-bound
+// element movement; the only arithmetic is the float32 multiply of output dropout, the adding stores, and the pooled
+// readout: its reduction over time and the one float32 add (and, for the mean, one division) of its gradient.
 #include "lstm_boundary.h"
 
 namespace csn {
@@ -43,9 +44,18 @@ __global__ void __launch_bounds__(256) y_out(const T* __restrict__ h_all, float*
   }
 }
 
-// dy_tm[s][b][h] (dense, time-major), s < Te  <-  dy_all[b][t][h] (batch-first, pitched, or null); zeros from a row's length on
-template <bool DROP>
-__global__ void __launch_bounds__(256) dy_in(const float* __restrict__ dy, float* __restrict__ dy_tm, RowMap m, OutDropCfg od) {
+// dy_tm[s][b][h] (dense, time-major), s < Te  <-  dy_all[b][t][h] (batch-first, pitched, or null); zeros from a row's length on.
+// POOL (csn_lstm_plan_set_readout): the gradient of the pooled y_last joins every valid step in the same store -- one float32
+// add behind the (masked) dy_all element, or the term itself where dy is null: dy_last / n under MEAN, dy_last at the caller
+// time argmax[b][h] and +0 elsewhere under MAX
+template <int POOL>
+__device__ __forceinline__ float pool_term(const PoolIn& pl, const RowSteps& row, int64_t b, int64_t t, int64_t h, int H) {
+  const float g = pl.dy_last[b * H + h];
+  if constexpr (POOL == CSN_READOUT_MEAN) return g / (float)row.n;
+  else return pl.argmax[b * H + h] == (int)t ? g : 0.f;
+}
+template <bool DROP, int POOL>
+__global__ void __launch_bounds__(256) dy_in(const float* __restrict__ dy, float* __restrict__ dy_tm, RowMap m, OutDropCfg od, PoolIn pl) {
   constexpr int W = DROP ? 4 : 1;
   const int64_t hw = m.H / W, total = (int64_t)m.B * m.Te * hw;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -53,16 +63,118 @@ __global__ void __launch_bounds__(256) dy_in(const float* __restrict__ dy, float
     const int64_t h = (i % hw) * W, r = i / hw, b = r % m.B, s = r / m.B;
     const RowSteps row(m.len, b, m.Tn, m.rev);
     const bool in = dy != nullptr && row.valid(s);
-    const int64_t brow = b * m.Tn + row.flip(s);
+    const int64_t t = row.flip(s), brow = b * m.Tn + t;
     const float* src = dy + brow * m.pitch + h;
     float* dst = dy_tm + i * W;
     if constexpr (DROP) {
       f32x4 out = {0.f, 0.f, 0.f, 0.f};
       if (in) out = drop_quad(*reinterpret_cast<const f32x4*>(src), od, brow, h);
+      if constexpr (POOL != CSN_READOUT_LAST) {
+        if (row.valid(s)) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const float g = pool_term<POOL>(pl, row, b, t, h + j, m.H);
+            out[j] = in ? out[j] + g : g;
+          }
+        }
+      }
       *reinterpret_cast<f32x4*>(dst) = out;
     } else {
-      *dst = in ? *src : 0.f;
+      float out = in ? *src : 0.f;
+      if constexpr (POOL != CSN_READOUT_LAST) {
+        if (row.valid(s)) {
+          const float g = pool_term<POOL>(pl, row, b, t, h, m.H);
+          out = in ? out + g : g;
+        }
+      }
+      *dst = out;
     }
+  }
+}
+
+// ---- the pooled readout (csn_lstm_plan_set_readout).  A workgroup owns row b and a strip of kPoolLanes
+// 16-byte pieces of h; its 256 threads are kPoolLanes lanes along h times kPoolSplit parts of the row's n steps: part k
+// takes the caller times t = k, k + kPoolSplit, ... in rising order, the parts are combined through LDS in the order
+// k = 0, 1, ... by one thread per column -- a fixed split, so a call gives the same bits every time.
+//   MEAN    float64 partial sums, one rounding of sum / n to float32
+//   MAX     the value at the first caller time that attains the maximum; a NaN beats every number, the first NaN wins
+//   ARGMAX  that caller time as int32 (-1 for an empty row): what dy_in<., MAX> reads, recomputed by the backward
+// Empty rows give zeros.
+constexpr int kPoolLanes = 8, kPoolSplit = 256 / kPoolLanes;
+constexpr int kPoolArgmax = 3;
+// does (v, t) come before (bv, bt) as the row's maximum?  (bt < 0: nothing yet)
+__device__ __forceinline__ bool pool_before(float v, int t, float bv, int bt) {
+  if (bt < 0) return true;
+  const bool vn = v != v, bn = bv != bv;
+  if (vn != bn) return vn;
+  if (!vn && v != bv) return v > bv;
+  return t < bt;
+}
+template <typename T, int MODE>
+__global__ void __launch_bounds__(256) pool_readout(const T* __restrict__ h_all, void* __restrict__ out, RowMap m) {
+  constexpr int VEC = 16 / (int)sizeof(T), COLS = kPoolLanes * VEC;
+  typedef T Piece __attribute__((ext_vector_type(VEC)));
+  __shared__ double lds[kPoolSplit * COLS];      // MEAN: [part][col] sums; else [part][col] float values, then int times
+  const int lane = threadIdx.x % kPoolLanes, k = threadIdx.x / kPoolLanes;
+  const int64_t b = blockIdx.y, h0 = (int64_t)blockIdx.x * COLS + lane * VEC;
+  const RowSteps row(m.len, b, m.Tn, m.rev);
+  const int n = (int)row.n;
+  const bool live = h0 < m.H;      // (H % 32 == 0: a piece lies inside the row or outside it)
+  double sum[VEC];
+  float best[VEC];
+  int at[VEC];
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) {
+    sum[j] = 0.0;
+    best[j] = 0.f;
+    at[j] = -1;
+  }
+  for (int t = k; live && t < n; t += kPoolSplit) {
+    const Piece v = *reinterpret_cast<const Piece*>(h_all + (row.slot(t) * m.B + b) * (int64_t)m.H + h0);
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) {
+      const float f = to_f32((T)v[j]);
+      if constexpr (MODE == CSN_READOUT_MEAN) {
+        sum[j] += (double)f;
+      } else if (pool_before(f, t, best[j], at[j])) {
+        best[j] = f;
+        at[j] = t;
+      }
+    }
+  }
+  float* lds_v = reinterpret_cast<float*>(lds);
+  int* lds_t = reinterpret_cast<int*>(lds_v + kPoolSplit * COLS);
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) {
+    const int c = k * COLS + lane * VEC + j;
+    if constexpr (MODE == CSN_READOUT_MEAN) {
+      lds[c] = sum[j];
+    } else {
+      lds_v[c] = best[j];
+      lds_t[c] = at[j];
+    }
+  }
+  __syncthreads();
+  const int c = threadIdx.x;
+  const int64_t h = (int64_t)blockIdx.x * COLS + c;
+  if (c >= COLS || h >= m.H) return;
+  if constexpr (MODE == CSN_READOUT_MEAN) {
+    double s = 0.0;
+    for (int p = 0; p < kPoolSplit; ++p) s += lds[p * COLS + c];
+    static_cast<float*>(out)[b * m.H + h] = n > 0 ? (float)(s / (double)n) : 0.f;
+  } else {
+    float bv = 0.f;
+    int bt = -1;
+    for (int p = 0; p < kPoolSplit; ++p) {
+      const float v = lds_v[p * COLS + c];
+      const int t = lds_t[p * COLS + c];
+      if (t >= 0 && pool_before(v, t, bv, bt)) {
+        bv = v;
+        bt = t;
+      }
+    }
+    if constexpr (MODE == CSN_READOUT_MAX) static_cast<float*>(out)[b * m.H + h] = bv;
+    else static_cast<int*>(out)[b * m.H + h] = bt;
   }
 }
 
@@ -161,16 +273,47 @@ int launch_y_out(const void* h_all, int dtype, float* y, const RowMap& m, const 
   return CSN_OK;
 }
 
-int launch_dy_in(const float* dy, float* dy_tm, const RowMap& m, const OutDropCfg* od, hipStream_t st) {
+template <int POOL>
+static void launch_dy_in_t(const float* dy, float* dy_tm, const RowMap& m, const OutDropCfg* od, const PoolIn& pl, hipStream_t st) {
   const int64_t n = (int64_t)m.B * m.Te * m.H;
-  if (od) {
+  if (od) dy_in<true, POOL><<<grid_for(n >> 2, kDropBlocks), 256, 0, st>>>(dy, dy_tm, m, *od, pl);
+  else dy_in<false, POOL><<<grid_for(n), 256, 0, st>>>(dy, dy_tm, m, OutDropCfg{}, pl);
+}
+int launch_dy_in(const float* dy, float* dy_tm, const RowMap& m, const OutDropCfg* od, const PoolIn* pool, hipStream_t st) {
+  if (od)
     if (int rc = check_out_drop("lstm dy_in", dy, m, *od)) return rc;
-    dy_in<true><<<grid_for(n >> 2, kDropBlocks), 256, 0, st>>>(dy, dy_tm, m, *od);
+  if (pool == nullptr || pool->mode == CSN_READOUT_LAST) {
+    launch_dy_in_t<CSN_READOUT_LAST>(dy, dy_tm, m, od, PoolIn{}, st);
   } else {
-    dy_in<false><<<grid_for(n), 256, 0, st>>>(dy, dy_tm, m, OutDropCfg{});
+    CSN_REQUIRE(pool->dy_last != nullptr && (pool->mode == CSN_READOUT_MEAN || pool->argmax != nullptr), "lstm dy_in: pooled term without its inputs");
+    if (pool->mode == CSN_READOUT_MEAN) launch_dy_in_t<CSN_READOUT_MEAN>(dy, dy_tm, m, od, *pool, st);
+    else launch_dy_in_t<CSN_READOUT_MAX>(dy, dy_tm, m, od, *pool, st);
   }
   CSN_LAUNCH_CHECK();
   return CSN_OK;
+}
+
+template <typename T>
+static void launch_pool_t(const void* h_all, int mode, void* out, const RowMap& m, hipStream_t st) {
+  constexpr int cols = kPoolLanes * (16 / (int)sizeof(T));
+  const dim3 grid((unsigned)((m.H + cols - 1) / cols), (unsigned)m.B);
+  if (mode == CSN_READOUT_MEAN) pool_readout<T, CSN_READOUT_MEAN><<<grid, 256, 0, st>>>((const T*)h_all, out, m);
+  else if (mode == CSN_READOUT_MAX) pool_readout<T, CSN_READOUT_MAX><<<grid, 256, 0, st>>>((const T*)h_all, out, m);
+  else pool_readout<T, kPoolArgmax><<<grid, 256, 0, st>>>((const T*)h_all, out, m);
+}
+static int launch_pool(const void* h_all, int dtype, int mode, void* out, const RowMap& m, hipStream_t st) {
+  CSN_REQUIRE(m.B <= 65535, "lstm pooled readout: B = %d rows exceed the grid", m.B);
+  if (dtype == CSN_BF16) launch_pool_t<bf16_t>(h_all, mode, out, m, st);
+  else launch_pool_t<float>(h_all, mode, out, m, st);
+  CSN_LAUNCH_CHECK();
+  return CSN_OK;
+}
+int launch_pool_readout(const void* h_all, int dtype, int mode, float* y, const RowMap& m, hipStream_t st) {
+  CSN_REQUIRE(mode == CSN_READOUT_MEAN || mode == CSN_READOUT_MAX, "lstm pooled readout: mode %d", mode);
+  return launch_pool(h_all, dtype, mode, y, m, st);
+}
+int launch_pool_argmax(const void* h_all, int dtype, int* argmax, const RowMap& m, hipStream_t st) {
+  return launch_pool(h_all, dtype, kPoolArgmax, argmax, m, st);
 }
 
 int launch_dx_out(const float* dx_tm, float* dx, const RowMap& m, hipStream_t st) {

@@ -61,11 +61,13 @@ class _Call:
     ``B, T``: the plan's shape -- x's, or with ``views = (rows, starts)`` (x is then the source) the windows'.  ``drop``:
     _draw_dropout's.  ``outputs``: which of (y_last, y_all, h_n, c_n) the entry point takes -- the library is asked for no
     other, and only their gradients go to plan.backward.  ``state_plan``: HipLSTM._checkout's ``state``.  ``overwrite``: is
-    ``direct_grads = True`` honoured?  ``bi``: BiLSTM's (L, H)."""
-    __slots__ = ("B", "T", "training", "drop", "lengths", "views", "outputs", "state_plan", "overwrite", "bi")
+    ``direct_grads = True`` honoured?  ``bi``: BiLSTM's (L, H).  ``readout``: what y_last is -- "last", "mean" or "max" over
+    each row's valid steps (csn_lstm_plan_set_readout); BiLSTM's top-layer plans then hand back their pooled halves."""
+    __slots__ = ("B", "T", "training", "drop", "lengths", "views", "outputs", "state_plan", "overwrite", "bi", "readout")
 
     def __init__(self, x, training, drop, lengths=None, views=None, outputs=(True, False, False, False), state_plan=None,
-                 overwrite=True, bi=None):
+                 overwrite=True, bi=None, readout="last"):
+        self.readout = _check_readout("LSTM call", readout)
         self.B, self.T = (x.shape[0], x.shape[1]) if views is None else (len(lengths), max(1, max(lengths)))
         self.training, self.drop, self.lengths, self.views = training, drop, lengths, views
         self.outputs, self.state_plan, self.overwrite, self.bi = outputs, state_plan, overwrite, bi
@@ -74,7 +76,8 @@ class _Call:
 def _armed(plan, call, fn, grad=None, k=None, src=None):
     """fn() -- ``call``'s plan.forward or plan.backward -- with everything it depends on set on the plan first.  Plans are
     shared between calls and every setter of cabi.LstmPlan is sticky, so a pooled plan still carries whatever its last
-    user set: nothing is assumed, all of it is set in front of every forward and backward.  That is: the lengths (None =
+    user set: nothing is assumed, all of it is set in front of every forward and backward.  That is: the readout (on
+    BiLSTM's plans below the top layer always "last": their y_last is not used); the lengths (None =
     every row is T; on CSN_LSTM_STATE plans only, the library refuses set_lengths on others); on a stack's plan the
     inter-layer dropout (None = p 0, which a plan without the bit takes too); on BiLSTM's plan ``k`` = 2 * layer +
     direction the io pitches -- on a backward the reverse direction adds its dx to the forward one's -- and the output
@@ -82,6 +85,7 @@ def _armed(plan, call, fn, grad=None, k=None, src=None):
     drops each once; the top layer's is never dropped); on a backward ``grad`` = (callback, accumulate).  ``src``: the
     source tensor of a forward through input windows, which are cleared again, also when fn raises -- a backward reads no
     x, so it sets none."""
+    plan.set_readout(call.readout if k is None or k // 2 == call.bi[0] - 1 else "last")
     if plan.state:
         plan.set_lengths(call.lengths)
     if k is None:
@@ -146,6 +150,14 @@ def _check_dropout_p(p):
         raise ValueError(f"dropout should be a number in range [0, 1] representing the probability of an element being "
                          f"zeroed, got {p!r}")
     return float(p)
+
+
+def _check_readout(name, readout):
+    """``readout``: which summary of the top layer's output sequence a module hands back -- "last" (each row's last valid
+    step), or "mean" / "max" over each row's valid steps, reduced inside the library (csn_lstm_plan_set_readout)."""
+    if not isinstance(readout, str) or readout not in cabi.READOUTS:
+        raise ValueError(f"{name}: readout must be one of {sorted(cabi.READOUTS)}, got {readout!r}")
+    return readout
 
 
 def _check_resident(name, resident, hidden_size):
@@ -237,13 +249,19 @@ class HipLSTM(nn.Module):
     ``resident=True`` (hidden_size <= 128): every plan of the module is a CSN_LSTM_RESIDENT one -- the steps of a chunk
     run inside one launch per layer, W_hh in registers, with the results of the per-step cells bit for bit (DESIGN.md
     section 21).  A property of the plans, not of the parameters: state_dicts are unchanged.
+
+    ``readout``: "last" (the default), "mean" or "max" -- what ``forward`` and ``forward_views`` return as [B, H]: the top
+    layer's output at each row's last step, or its mean / maximum over the row's steps, reduced from the workspace inside
+    the library with no [B, T, H] tensor written or read.  No parameter depends on it.
     """
 
     MAX_IDLE_PLANS = 4      # workspaces are large (10 GB at cfg2): keep only a few idle ones
     _STATE_PLANS = False    # LSTM: plans created with CSN_LSTM_STATE
 
-    def __init__(self, input_size, hidden_size, num_layers=1, compute_dtype=torch.bfloat16, dropout=0.0, resident=False):
+    def __init__(self, input_size, hidden_size, num_layers=1, compute_dtype=torch.bfloat16, dropout=0.0, resident=False,
+                 readout="last"):
         super().__init__()
+        self.readout = _check_readout(type(self).__name__, readout)
         self.resident = _check_resident(type(self).__name__, resident, hidden_size)
         _check_dropout_p(dropout)
         if dropout > 0 and num_layers == 1:
@@ -281,7 +299,8 @@ class HipLSTM(nn.Module):
         _dropout_p(self)
         rows, starts, lengths = _check_views("HipLSTM", x, views, lengths, self.input_size)
         params = self._flat_params()
-        call = _Call(x, _training(None, None, None, params), _draw_dropout(self), lengths, (rows, starts), state_plan=True)
+        call = _Call(x, _training(None, None, None, params), _draw_dropout(self), lengths, (rows, starts), state_plan=True,
+                     readout=self.readout)
         return _LstmFunction.apply(x, None, None, self, call, self.num_layers, *params)[0]
 
     def forward(self, x, want_all=False):
@@ -289,7 +308,8 @@ class HipLSTM(nn.Module):
         if not x.is_cuda:
             raise cabi.CsnError("HipLSTM runs on the GPU only (no CPU fallback); move the module and input to cuda")
         params = self._flat_params()
-        call = _Call(x, _training(x, None, None, params), _draw_dropout(self), outputs=(True, bool(want_all), False, False))
+        call = _Call(x, _training(x, None, None, params), _draw_dropout(self), outputs=(True, bool(want_all), False, False),
+                     readout=self.readout)
         y_last, y_all, _, _ = _LstmFunction.apply(x, None, None, self, call, self.num_layers, *params)
         return (y_all, y_last) if want_all else y_last
 
@@ -375,8 +395,22 @@ def _forward_stateful(module, name, dirs, function, x, hx, lengths, views, **for
         raise cabi.CsnError(f"{name} runs on the GPU only (no CPU fallback); move the module and input to cuda")
     params = module._flat_params()
     call = _Call(x, _training(x, h0, c0, params), _draw_dropout(module), lengths, views, **form)
-    *_, output, h_n, c_n = function.apply(x, h0, c0, module, call, L, *params)
+    got = function.apply(x, h0, c0, module, call, L, *params)
+    if call.readout != "last":
+        return got[0]       # (pooled: the [B, H] / [B, 2H] readout alone)
+    *_, output, h_n, c_n = got
     return output, (h_n, c_n)
+
+
+def _pooled(module, name, x, hx, lengths, views, readout):
+    """``pooled`` of LSTM / BiLSTM: a PackedSequence is padded with the lengths it carries, the readout is checked."""
+    if _check_readout(name, readout) == "last":
+        raise ValueError(f"{name}.pooled: readout must be 'mean' or 'max' (the last step is what forward's h_n[-1] holds)")
+    if isinstance(x, nn.utils.rnn.PackedSequence):
+        if lengths is not None or views is not None:
+            raise ValueError(f"{name}: lengths or views given together with a PackedSequence (it carries its own lengths)")
+        x, lengths = nn.utils.rnn.pad_packed_sequence(x, batch_first=True)
+    return x, lengths
 
 
 class LSTM(HipLSTM):
@@ -422,6 +456,16 @@ class LSTM(HipLSTM):
         return _forward_stateful(self, "LSTM", 1, _LstmFunction, x, hx, lengths, views, outputs=(False, True, True, True),
                                  overwrite=False)
 
+    def pooled(self, x, hx=None, lengths=None, views=None, readout="mean"):
+        """-> [B, H]: the mean (``readout="mean"``) or maximum ("max") of ``forward``'s output over each row's valid steps --
+        ``output.sum(1) / n`` in float64 rounded once, or ``output.max over t < n``; rows of length 0 give zeros.  The
+        library reduces the top layer's saved steps itself: no [B, T, H] output is written, and the backward expands the
+        gradient inside the pass that lays it out for the recurrence.  Arguments as in ``forward``; gradients reach x, h0,
+        c0 and every parameter (under "max" at the first step that attains the maximum, as torch.max's)."""
+        x, lengths = _pooled(self, "LSTM", x, hx, lengths, views, readout)
+        return _forward_stateful(self, "LSTM", 1, _LstmFunction, x, hx, lengths, views, outputs=(True, False, False, False),
+                                 overwrite=False, readout=readout)
+
 
 class _BiLstmFunction(torch.autograd.Function):
     """Bidirectional stacked LSTM: (x, h0, c0, params) -> (output[B,T,2H], h_n[2L,B,H], c_n[2L,B,H]) as 2L single-layer
@@ -433,26 +477,30 @@ class _BiLstmFunction(torch.autograd.Function):
     ``call.drop`` = (p, seed, subsequence) or None: inter-layer dropout.  The plans of every layer below the top one store
     their half of the interface tensor masked and scaled, and read their half of its gradient masked and scaled, inside the
     layout passes they run anyway (csn_lstm_plan_set_output_dropout; _armed).  ``call.views`` = (rows, starts) or None: x is
-    a source tensor and layer 0's two plans read their rows' windows of it in place (csn_lstm_plan_set_views)."""
+    a source tensor and layer 0's two plans read their rows' windows of it in place (csn_lstm_plan_set_views).
+    ``call.readout`` "mean" / "max" (BiLSTM.pooled): the first result is the pooled [B,2H] instead -- the two top-layer plans
+    write no y_all and hand back their pooled y_last, which are concatenated, and the backward gives each its half of the
+    [B,2H] gradient as dy_last."""
 
     @staticmethod
     def forward(ctx, x, h0, c0, owner, call, L, *params):
         B, T, H = call.B, call.T, owner.hidden_size
         h_n = torch.empty((2 * L, B, H), dtype=torch.float32, device=x.device)
         c_n = torch.empty((2 * L, B, H), dtype=torch.float32, device=x.device)
-        leases, inp = [], x
+        leases, inp, halves = [], x, []
         for l in range(L):
-            out = torch.empty((B, T, 2 * H), dtype=torch.float32, device=x.device)
+            pooled = call.readout != "last" and l == L - 1
+            out = None if pooled else torch.empty((B, T, 2 * H), dtype=torch.float32, device=x.device)
             for d in range(2):
                 k = 2 * l + d
                 plan = owner._checkout(B, T, inp.shape[2], x.device, call.training, reverse=d == 1)
                 lease = _Lease(plan)        # (at once: the next direction / layer of the same shape must take another plan)
                 run = lambda: plan.forward(inp, *([p] for p in params[4 * k:4 * k + 4]),                   # noqa: E731
                                            h0=None if h0 is None else h0[k:k + 1], c0=None if c0 is None else c0[k:k + 1],
-                                           want_state=True, y_all=out[:, :, d * H:(d + 1) * H],
+                                           want_state=True, y_all=None if pooled else out[:, :, d * H:(d + 1) * H],
                                            state_out=(h_n[k:k + 1], c_n[k:k + 1]))
                 try:
-                    _armed(plan, call, run, k=k, src=x if call.views is not None and l == 0 else None)
+                    halves.append(_armed(plan, call, run, k=k, src=x if call.views is not None and l == 0 else None)[0])
                 except BaseException:
                     for held in leases + [lease]:       # (a refused call, e.g. a window past the source: nothing stays leased)
                         held.release()
@@ -461,7 +509,7 @@ class _BiLstmFunction(torch.autograd.Function):
                     leases.append(lease)
                 else:
                     lease.release()
-            inp = out
+            inp = torch.cat(halves[-2:], dim=1) if pooled else out
         ctx.leases, ctx.L, ctx.owner, ctx.call = leases, L, owner, call
         ctx.need = tuple(t is not None and t.requires_grad for t in (x, h0, c0))
         ctx.x_width = x.shape[2]
@@ -484,12 +532,13 @@ class _BiLstmFunction(torch.autograd.Function):
             dy = dy.clone()                 # (a pitched dy_all is taken on 16 bytes, and the masked load moves 16: a dense gradient
                                             # at an odd storage offset is copied once)
         for l in range(L - 1, -1, -1):
+            pooled = call.readout != "last" and l == L - 1
             dinp = torch.empty((B, T, ctx.x_width if l == 0 else 2 * H), dtype=torch.float32, device=dev) if (l > 0 or need_dx) else None
             for d in range(2):
                 k = 2 * l + d
                 plan = leases[k].plan
                 _armed(plan, call, lambda: plan.backward(
-                    None, dy[:, :, d * H:(d + 1) * H], [[g] for g in grads[4 * k:4 * k + 4]], dx=dinp, dh_n=dh_n[k:k + 1],
+                    dy[:, d * H:(d + 1) * H] if pooled else None, None if pooled else dy[:, :, d * H:(d + 1) * H], [[g] for g in grads[4 * k:4 * k + 4]], dx=dinp, dh_n=dh_n[k:k + 1],
                     dc_n=dc_n[k:k + 1], dh0=None if dh0 is None else dh0[k:k + 1], dc0=None if dc0 is None else dc0[k:k + 1]),
                        grad=(None, False), k=k)
                 leases[k].release()
@@ -557,18 +606,30 @@ class BiLSTM(nn.Module):
         bits of the call on the gathered rows.  No gradient reaches x through views (``x.requires_grad`` raises)."""
         return _forward_stateful(self, "BiLSTM", 2, _BiLstmFunction, x, hx, lengths, views, bi=(self.num_layers, self.hidden_size))
 
+    def pooled(self, x, hx=None, lengths=None, views=None, readout="mean"):
+        """-> [B, 2H]: the mean ("mean") or maximum ("max") of ``forward``'s output over each row's valid steps, as
+        ``LSTM.pooled``: each direction's top-layer plan pools its half and the two [B, H] results are concatenated, which
+        equals pooling the [B, T, 2H] output.  The top layer writes no output tensor.  Arguments as in ``forward``."""
+        x, lengths = _pooled(self, "BiLSTM", x, hx, lengths, views, readout)
+        return _forward_stateful(self, "BiLSTM", 2, _BiLstmFunction, x, hx, lengths, views, bi=(self.num_layers, self.hidden_size),
+                                 readout=readout)
+
 
 class Model(nn.Module):
     """``models.lstm.Model``.  ``head``/``fc`` may be reassigned by
     ``MultiCropWrapper`` (utils/utils.py:607-612) without breaking forward."""
 
     def __init__(self, input_size=128, lstm_size=128, lstm_layers=1, output_size=128, include_top=True,
-                 n_classes=40, compute_dtype=torch.bfloat16, dropout=0.0, bidirectional=False, resident=False):
+                 n_classes=40, compute_dtype=torch.bfloat16, dropout=0.0, bidirectional=False, resident=False,
+                 readout="last"):
         """``bidirectional=True``: the encoder is a ``BiLSTM`` and ``fc`` has 2 * lstm_size inputs.  The feature fed to
         ``fc`` is then ``cat(h_n[-2], h_n[-1])``, the top layer's FINAL state in each direction -- not ``output[:, -1]``,
         whose reverse half has seen one step only.  ``resident=True`` (lstm_size <= 128): the encoder's plans run the
-        CU-resident recurrence (HipLSTM)."""
+        CU-resident recurrence (HipLSTM).  ``readout`` "mean" / "max": the feature fed to ``fc`` is the top layer's output
+        pooled over each row's steps instead (HipLSTM's ``readout``; bidirectional: ``BiLSTM.pooled``).  It adds no
+        parameter: checkpoints are unchanged."""
         super().__init__()
+        self.readout = _check_readout("Model", readout)
         self.input_size, self.lstm_size, self.lstm_layers = input_size, lstm_size, lstm_layers
         self.output_size, self.include_top, self.bidirectional = output_size, include_top, bool(bidirectional)
         if self.bidirectional:
@@ -576,7 +637,8 @@ class Model(nn.Module):
             # (the attribute, as on the LSTM drop-in: its constructor takes 0 only)
             self.lstm.dropout = _check_dropout_p(dropout)
         else:
-            self.lstm = HipLSTM(input_size, lstm_size, lstm_layers, compute_dtype=compute_dtype, dropout=dropout, resident=resident)
+            self.lstm = HipLSTM(input_size, lstm_size, lstm_layers, compute_dtype=compute_dtype, dropout=dropout, resident=resident,
+                                readout=readout)
         self.fc = nn.Linear((2 if self.bidirectional else 1) * lstm_size, output_size)
         if include_top:
             self.class_pred = nn.Linear(output_size, n_classes)
@@ -587,7 +649,9 @@ class Model(nn.Module):
         include_top."""
         if views is None and lengths is not None:
             raise ValueError("Model: lengths are taken with views only")
-        if self.bidirectional:
+        if self.bidirectional and self.readout != "last":
+            last = self.lstm.pooled(x, None, lengths, views, readout=self.readout)      # [B, 2H]
+        elif self.bidirectional:
             _, (h_n, _) = self.lstm(x, None, lengths, views)
             last = torch.cat((h_n[-2], h_n[-1]), dim=1)    # [B, 2H]
         elif views is not None:
@@ -609,10 +673,15 @@ class LSTMModel(nn.Module):
     """
 
     def __init__(self, input_size, hidden_size, n_layers=2, out_features=384, number_of_classes=None,
-                 all_steps=False, compute_dtype=torch.bfloat16, dropout=0.0, resident=False):
+                 all_steps=False, compute_dtype=torch.bfloat16, dropout=0.0, resident=False, readout="last"):
+        """``readout`` "mean" / "max" (the form without ``all_steps`` only): ``fc`` reads the LSTM output pooled over the
+        sequence instead of its last step (HipLSTM's ``readout``)."""
         super().__init__()
+        if _check_readout("LSTMModel", readout) != "last" and all_steps:
+            raise ValueError("LSTMModel: readout applies to the form without all_steps (all_steps feeds every step to fc)")
         self.hidden_size, self.n_layer, self.input_size, self.all_steps = hidden_size, n_layers, input_size, all_steps
-        self.lstm = HipLSTM(input_size, hidden_size, n_layers, compute_dtype=compute_dtype, dropout=dropout, resident=resident)
+        self.lstm = HipLSTM(input_size, hidden_size, n_layers, compute_dtype=compute_dtype, dropout=dropout, resident=resident,
+                            readout=readout)
         self.fc = nn.Linear(hidden_size, out_features)
         if number_of_classes:
             self.class_pred = nn.Linear(out_features, number_of_classes)

@@ -94,7 +94,7 @@ enum csnStatus {
 enum csnDtype { CSN_F32 = 0, CSN_BF16 = 1 };
 
 /* ABI version of this header; bumped on any signature change.  A symbol added beside the existing ones
- * (csn_lstm_plan_set_grad_mode, csn_lstm_plan_set_lengths, csn_lstm_plan_set_views, csn_lstm_plan_set_io, csn_lstm_plan_half_tile_launches, the
+ * (csn_lstm_plan_set_grad_mode, csn_lstm_plan_set_lengths, csn_lstm_plan_set_views, csn_lstm_plan_set_io, csn_lstm_plan_set_readout, csn_lstm_plan_half_tile_launches, the
  * csn_flat_* family, csn_adam_step, csn_lars_step, csn_eeg_bandpass_stream and its _path, csn_distill_loss,
  * csn_dino_loss, csn_barlow_corr, csn_barlow_grad, csn_contrastive_lse, csn_contrastive_grad, csn_topk_merge and its _staged_max, csn_topk_class_metrics, csn_grad_guard, its _scratch_bytes and the three
  * csn_*_step_guarded) breaks no caller and does not bump it; neither does a new bit of csn_lstm_plan_create's `training` word. */
@@ -260,13 +260,13 @@ int csn_lstm_workspace_init(const csnLstmPlan* plan, void* workspace, csnStream_
  * w_ih/w_hh/b_ih/b_hh: [host] arrays of L device pointers to float32 parameters
  *   weight_ih_l{k}[4H,I_k], weight_hh_l{k}[4H,H], bias_ih_l{k}[4H], bias_hh_l{k}[4H].
  * h0, c0: optional [L,B,H] float32 initial state (NULL = zeros), dense, 16-B aligned.
- * y_last: [B,H] float32 = output of the top layer at t = T-1.
+ * y_last: [B,H] float32 = output of the top layer at t = T-1, or its mean / maximum over time (csn_lstm_plan_set_readout).
  * y_all : optional (may be NULL) [B,T,H] float32, every step of the top layer.
  * h_n, c_n: optional [L,B,H] float32 final state of every layer (may be NULL), dense, 16-B aligned.
  * At least one of y_last, y_all, h_n, c_n must be given.
  * State (only on a CSN_LSTM_STATE plan; any non-NULL state argument on another plan is CSN_ERR_INVALID_ARGUMENT):
  *   CSN_BF16: h0 is rounded to bf16 as every h is; c0 stays float32.  h_n[l] is the upcast of the bf16 h that layer
- *   l+1 and y_all consumed, so h_n[L-1] == y_last bit for bit; c_n is the float32 cell state.  Feeding (h_n, c_n) of
+ *   l+1 and y_all consumed, so under CSN_READOUT_LAST h_n[L-1] == y_last bit for bit; c_n is the float32 cell state.  Feeding (h_n, c_n) of
  *   one call into the next as (h0, c0) is therefore exact: a sequence run as consecutive chunks carries the same
  *   state as one run over all of it.  CSN_F32: everything float32.
  *   With every state argument NULL, a CSN_BF16 state plan computes the same bits as a plan without the bit (a float32
@@ -280,7 +280,7 @@ int csn_lstm_forward(csnLstmPlan* plan,
                      void* workspace, float* y_last, float* y_all,
                      float* h_n, float* c_n, csnStream_t stream);
 
-/* dy_last: [B,H] float32 gradient w.r.t. y_last (may be NULL).
+/* dy_last: [B,H] float32 gradient w.r.t. y_last (may be NULL); it enters where the plan's readout took y_last from.
  * dy_all : optional [B,T,H] float32 gradient w.r.t. y_all (may be NULL).
  * dh_n, dc_n: optional [L,B,H] float32 gradients w.r.t. h_n / c_n (may be NULL).
  * At least one of dy_last, dy_all, dh_n, dc_n must be given.
@@ -378,6 +378,39 @@ int csn_lstm_plan_set_views(csnLstmPlan* plan, const int32_t* src_row, const int
  * default, a plan without CSN_LSTM_REVERSE enqueues the launches and writes the bits it did before this symbol existed.
  * Null plan or a pitch that is neither 0 nor a multiple of 4 >= H: CSN_ERR_INVALID_ARGUMENT (the setting is kept). */
 int csn_lstm_plan_set_io(csnLstmPlan* plan, int64_t y_all_pitch, int64_t dy_all_pitch, int dx_add);
+
+/* What y_last is: the readout of the top layer's output sequence.  Host only and sticky until set again, like
+ * csn_lstm_plan_set_io; a call uses the setting it finds when it is CALLED, and the matching backward must run with its
+ * forward's setting.  Every plan and every path (0-5), training and inference, with or without CSN_LSTM_STATE,
+ * CSN_LSTM_DROPOUT, CSN_LSTM_REVERSE or CSN_LSTM_RESIDENT.  The mode changes only the meaning of y_last in csn_lstm_forward
+ * and of dy_last in csn_lstm_backward: y_all, h_n, c_n, every workspace buffer, csn_lstm_plan_workspace_bytes and the
+ * workspace layout keep their bits.  Under CSN_READOUT_LAST (the default) a plan enqueues the launches and writes the bits
+ * it did before this symbol existed.  
+ * With v[b, t, h] the float32 upcast of the top layer's h at the CALLER's time t (what a y_all without output dropout
+ * holds) and n = lengths[b] (T without lengths):
+ *   FORWARD.   MEAN: y_last[b, h] = fl32((sum over t < n of (double)v[b, t, h]) / n): float64 partial sums over a fixed
+ *              split of the steps (the same call gives the same bits every time), one rounding at the end.
+ *              MAX:  y_last[b, h] = max over t < n of v[b, t, h], exact; a NaN wins, as in torch.max.
+ *              Rows with n = 0 give zeros in both modes (NOT the h0 pass-through of LAST).  Output dropout does not touch
+ *              the pooled value, as it does not touch y_last under LAST.
+ *   BACKWARD.  dy_last enters every valid step of its row.  MEAN: each step t < n receives g = dy_last[b, h] / (float)n,
+ *              an IEEE float32 division.  MAX: dy_last[b, h] enters at the FIRST caller time t that attains the maximum
+ *              (the smallest t, also on a CSN_LSTM_REVERSE plan -- torch's tie rule; with a NaN the first NaN), and +0
+ *              joins the other valid steps.  The argmax is recomputed from the workspace's h at backward time into a
+ *              [B, H] int32 array the plan owns, under the ordering contract of the lengths upload; the forward saves
+ *              nothing.  Into the top layer's gradient go, in this order: the (masked) dy_all element or 0; the pooled
+ *              term, as one float32 add; the top layer's dh_n at the row's end.  Rows with n = 0 receive nothing from
+ *              dy_last.
+ *   IDENTITY.  A backward under MEAN or MAX has, bit for bit, every gradient of the same plan called under LAST with
+ *              dy_last = NULL and dy_all' = fl32(dy_all + G), G[b, t, :] the expanded term above (plain G where dy_all is
+ *              NULL).
+ * Cost: the forward launches one reduction over the top layer's saved h in place of the gather of the last step; the
+ * backward's term rides in the dy_all layout pass (a further instantiation of dy_in), plus for MAX one argmax pre-pass.
+ * Null plan or unknown mode: CSN_ERR_INVALID_ARGUMENT (the setting is kept). */
+#define CSN_READOUT_LAST 0
+#define CSN_READOUT_MEAN 1
+#define CSN_READOUT_MAX  2
+int csn_lstm_plan_set_readout(csnLstmPlan* plan, int mode);
 
 /* Inter-layer dropout, with torch.nn.LSTM(dropout=p)'s meaning: for every layer l < L-1 the output sequence of layer l is
  * multiplied element-wise by an independent Bernoulli(1-p) mask and by 1/(1-p) before layer l+1's input projection.
