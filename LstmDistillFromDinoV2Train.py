@@ -101,12 +101,15 @@ def build_parser(flavour=PERILS):
                    help='what fc reads of the LSTM output sequence: its last step, or its mean / maximum over time, reduced '
                         'inside the library (no parameter depends on it; evaluate a checkpoint with the readout it was trained with)')
     p.add_argument('--output_size', type=int, default=384)
-    p.add_argument('--loss', type=str, default=flavour.loss, choices=["featdist", "cosine", "kd", "barlow", "contrastive"])
+    p.add_argument('--loss', type=str, default=flavour.loss, choices=["featdist", "cosine", "kd", "barlow", "contrastive", "contrastive_bank"],
+                   help='contrastive_bank: InfoNCE against the bank of every image\'s teacher row (all images are negatives at every '
+                        'step; a mean over rows, so --accum_steps and ragged shards work)')
     p.add_argument('--contrastive_temperature', type=float, default=0.07,
-                   help='--loss contrastive: the fixed temperature of the symmetric InfoNCE loss (logit scale = 1 / temperature)')
+                   help='--loss contrastive / contrastive_bank: the fixed temperature of the InfoNCE loss (logit scale = 1 / temperature)')
     p.add_argument('--contrastive_mask', type=str, default="image", choices=["image", "class", "none"],
                    help='--loss contrastive: rows that are not each other\'s negatives -- the same image (shown to several '
-                        'subjects), the same class, or none')
+                        'subjects), the same class, or none; --loss contrastive_bank: class = the other images of the '
+                        'positive\'s class are not negatives, image / none = every other image is (a bank row is one image)')
     p.add_argument('--optimizer', type=str, default=flavour.optimizer, choices=["rmsprop", "adamw", "adam", "lars"])
     p.add_argument('--dtype', type=str, default="bf16", choices=["bf16", "f32"])
     p.add_argument('--fs', type=float, default=1000.0, help='sampling rate for the band-pass design')
@@ -128,8 +131,9 @@ def build_parser(flavour=PERILS):
                         'stay as they were); the epoch line counts such steps; needs a flat optimiser (rmsprop, or '
                         '--fused_optimizer)')
     p.add_argument('--fused_loss', action='store_true',
-                   help='featdist / kd / barlow / contrastive: loss value and gradient from fused HIP calls in float64 '
-                        '(csn_distill_loss, csn_barlow_corr + csn_barlow_grad, csn_contrastive_lse + csn_contrastive_grad) '
+                   help='featdist / kd / barlow / contrastive / contrastive_bank: loss value and gradient from fused HIP calls in float64 '
+                        '(csn_distill_loss, csn_barlow_corr + csn_barlow_grad, csn_contrastive_lse + csn_contrastive_grad, '
+                        'csn_bank_contrastive) '
                         'instead of a chain of torch ops; does nothing with --loss cosine (always fused)')
     p.add_argument('--compat_label_bug', action='store_true',
                    help='reproduce the batch-local label lookup of transformEEGDataLSTMByList')
@@ -255,6 +259,13 @@ def main(argv=None, flavour=PERILS):
                              fused_loss=FLAGS.fused_loss, contrastive_temperature=FLAGS.contrastive_temperature,
                              max_grad_norm=FLAGS.clip_grad_norm or None, skip_nonfinite=FLAGS.skip_nonfinite)
 
+    pos_all = None
+    if FLAGS.loss == "contrastive_bank":        # the bank of the WHOLE dataset's images, once: the teacher is frozen
+        bank, pos_all, bank_class = dataset.image_bank()
+        trainer.set_bank(bank, bank_class if FLAGS.contrastive_mask == "class" else None)
+        if is_main:
+            print(f"contrastive_bank: {bank.shape[0]} images in the bank, mask {FLAGS.contrastive_mask}")
+
     def batches(idx, epoch, shuffle, multiple_of=1):
         shard = idx[shard_indices(len(idx), epoch, FLAGS.seed, rank, world, shuffle=shuffle).to(device)]
         for s in range(0, len(shard), FLAGS.batch_size):
@@ -264,7 +275,9 @@ def main(argv=None, flavour=PERILS):
                 yield b
 
     def loss_kw(b):
-        """--loss contrastive: the group ids of the batch, by --contrastive_mask."""
+        """--loss contrastive: the group ids of the batch, by --contrastive_mask; contrastive_bank: the rows' positives."""
+        if FLAGS.loss == "contrastive_bank":
+            return {"positives": pos_all[b]}
         if FLAGS.loss != "contrastive" or FLAGS.contrastive_mask == "none":
             return {}
         return {"groups": (dataset.image_ids_dev if FLAGS.contrastive_mask == "image" else dataset.labels_dev)[b]}

@@ -5,6 +5,6 @@ from . import cabi  # noqa: F401
 from .filters import EEGFilters, BandpassStream, eeg_bandpass_znorm, remove_noise  # noqa: F401
 from .lstm_model import Model, LSTMModel, CustomModel, LSTM, BiLSTM  # noqa: F401
 from .losses import (CosineSimilarityLoss, FeatureDistributionLoss, loss_fn_kd,  # noqa: F401
-                     BarlowTwinsLoss, ContrastiveLoss, HyperParams)
+                     BarlowTwinsLoss, ContrastiveLoss, BankContrastiveLoss, HyperParams)
 from .retrieval import evaluate, l2_search  # noqa: F401
 from .flat_optim import FlatAdamW, FlatLARS, flat_clip_gradients, flat_clip_grad_norm_  # noqa: F401

@@ -135,6 +135,10 @@ SIGNATURES = {
                                      _c_double, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
     "csn_contrastive_grad": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_double, _c_void_p,
                                       _c_void_p, _c_double, _c_double, _c_double, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+    "csn_bank_norms": (_c_int, [_c_void_p, _c_int, _c_int, _c_void_p, _c_void_p]),
+    "csn_bank_contrastive_scratch_bytes": (_c_size_t, [_c_int, _c_int, _c_int]),
+    "csn_bank_contrastive": (_c_int, [_c_void_p, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_double,
+                                      _c_double, _c_double, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
     "csn_l2_topk_scratch_bytes": (_c_size_t, [_c_i64, _c_i64]),
     "csn_l2_topk": (_c_int, [_c_void_p, _c_void_p, _c_i64, _c_i64, _c_int, _c_int, _c_void_p, _c_void_p,
                              _c_void_p, _c_void_p]),
@@ -1035,6 +1039,46 @@ def contrastive_grad(s_all, t_all, logit_scale, lse_a_local, lse_b_all, group_al
                                         _ptr(lse_b_all), float(w_a), float(w_b), float(grad_scale), _ptr(ds), _ptr(dscale),
                                         _ptr(scratch), _stream()))
     return ds, dscale
+
+
+def bank_norms(bank):
+    """csn_bank_norms on bank [M,D] float32 -> inv_norm [M] float64 = 1 / max(|t_m|, 1e-12); once per bank."""
+    _need_cuda(bank)
+    b = _f32_rows(bank, "bank", 2)
+    M, D = b.shape
+    inv = torch.empty(max(M, 0), dtype=torch.float64, device=b.device)
+    with torch.cuda.device(b.device):
+        _check(load().csn_bank_norms(_ptr(b), M, D, _ptr(inv), _stream()))
+    return inv
+
+
+def bank_contrastive(student, bank, bank_inv_norm, pos, logit_scale, bank_group=None, inv_rows=None, grad_scale=1.0,
+                     want_grad=True, want_dscale=False):
+    """csn_bank_contrastive on student [B,D] and bank [M,D] float32, bank_inv_norm [M] float64 (bank_norms), pos int32 [B]
+    (bank_group: int32 [M] or None) -> (rows_out [2,B] float64: l, p; loss_part [1] float64; ds [B,D] float32 holding
+    grad_scale | None; dscale_part [1] float64 | None).  ``inv_rows``: 1 / the rows the mean is over (default 1 / B)."""
+    _need_cuda(student, bank, bank_inv_norm, pos, bank_group)
+    s, b = _f32_rows(student, "student", 2), _f32_rows(bank, "bank", 2)
+    B, D = s.shape
+    M = b.shape[0]
+    if b.shape[1] != D or b.device != s.device:
+        raise CsnError(f"bank_contrastive: bank {tuple(b.shape)} on {b.device} against student {tuple(s.shape)} on {s.device}")
+    for name, v, dtype, n in (("bank_inv_norm", bank_inv_norm, torch.float64, M), ("pos", pos, torch.int32, B),
+                              ("bank_group", bank_group, torch.int32, M)):
+        if v is not None and (v.dtype != dtype or tuple(v.shape) != (n,) or not v.is_contiguous() or v.device != s.device):
+            raise CsnError(f"bank_contrastive: {name} must be a contiguous {dtype} [{n}] tensor on {s.device}, "
+                           f"got {v.dtype} {tuple(v.shape)} on {v.device}")
+    lib = load()
+    rows_out = torch.empty((2, max(B, 0)), dtype=torch.float64, device=s.device)
+    loss_part = torch.empty(1, dtype=torch.float64, device=s.device)
+    ds = torch.empty((max(B, 0), D), dtype=torch.float32, device=s.device) if want_grad else None
+    dscale = torch.empty(1, dtype=torch.float64, device=s.device) if want_dscale else None
+    scratch = torch.empty(lib.csn_bank_contrastive_scratch_bytes(B, M, D) // 8, dtype=torch.float64, device=s.device)   # caller-owned
+    with torch.cuda.device(s.device):
+        _check(lib.csn_bank_contrastive(_ptr(s), B, D, _ptr(b), _ptr(bank_inv_norm), _ptr(bank_group), M, _ptr(pos),
+                                        float(logit_scale), float(1.0 / B if inv_rows is None else inv_rows), float(grad_scale),
+                                        _ptr(rows_out), _ptr(loss_part), _ptr(ds), _ptr(dscale), _ptr(scratch), _stream()))
+    return rows_out, loss_part, ds, dscale
 
 
 def l2_topk(gallery, query, k):

@@ -189,6 +189,28 @@ class EEGDataset(Dataset):
         self.image_features_extracted = True
 
     @torch.no_grad()
+    def image_bank(self):
+        """The teacher rows of the M distinct images, for BankContrastiveLoss -> (bank [M,D] float32, pos_all [N] int32: every
+        sample's row of the bank, bank_class [M] int32: the class of each image), on the dataset's device.  The distinct
+        ``image_ids`` are taken in ascending order; a bank row is the ``features_all`` row of the FIRST sample showing that
+        image.  ValueError if no features are set, or if two samples of one image carry different feature rows."""
+        if not self.image_features_extracted or self.features_all is None:
+            raise ValueError("image_bank: the dataset has no teacher features (set_features / extract_features first)")
+        ids = self.image_ids_dev
+        N = ids.shape[0]
+        uniq, inverse = torch.unique(ids, sorted=True, return_inverse=True)
+        first = torch.full((uniq.shape[0],), N, dtype=torch.long, device=ids.device)
+        first.scatter_reduce_(0, inverse, torch.arange(N, device=ids.device), reduce="amin")
+        feats = self.features_all.float()
+        bank = feats[first].contiguous()
+        differs = (bank[inverse] != feats).any(dim=1)
+        if bool(differs.any()):
+            i = int(differs.nonzero()[0])
+            raise ValueError(f"image_bank: sample {i} and sample {int(first[inverse[i]])} show image {int(ids[i])} but carry "
+                             "different feature rows")
+        return bank, inverse.to(torch.int32), self.labels_dev[first].to(torch.int32)
+
+    @torch.no_grad()
     def extract_features(self, model, data_loader=None, use_cuda=True, multiscale=False, replace_eeg=False,
                          batch_size=64):
         """Runs the frozen teacher once over all images; one all_gather after the local loop."""

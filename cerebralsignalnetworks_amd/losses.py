@@ -10,6 +10,8 @@
   LARS, barlow_learning_rate EEG-BarlowNetworks/optim.py:5-44, barlow_utils.py:8-21
   ContrastiveLoss            not in the reference: the symmetric InfoNCE loss against frozen teacher rows, global negatives
                              (torch ops; fused=True: csn_contrastive_lse + csn_contrastive_grad)
+  BankContrastiveLoss        not in the reference: InfoNCE against the fixed bank of every image's teacher row
+                             (torch ops; fused=True: csn_bank_contrastive)
 Every class is checked against values and gradients obtained by executing the reference's own definition
 (tests/golden/ref_losses.npz, tests/test_ref_pinned.py).
 Reference quirks are kept on purpose.
@@ -21,6 +23,8 @@ device tensor; anything else (CPU tensors, float64) takes the torch form.  Opt-i
 (float64 arithmetic, five launches) under the same rule, in training mode.
 ``fused=True`` on ContrastiveLoss: value and gradient from csn_contrastive_lse + csn_contrastive_grad (float64 arithmetic,
 seven launches) under the same rule.
+``fused=True`` on BankContrastiveLoss: value and gradient from one csn_bank_contrastive call (float64 arithmetic, six
+launches) under the same rule.
 """
 import numpy as np
 import torch
@@ -434,6 +438,122 @@ class ContrastiveLoss(nn.Module):
         scale, below = self.scale()
         fused = self.fused and _fusable(student, teacher) and (groups is None or groups.is_cuda)
         return _ContrastiveFn.apply(student, teacher, groups, self.log_scale, scale, below, self.w_s2t, self.w_t2s, fused)
+
+
+class _BankContrastiveFn(torch.autograd.Function):
+    """csn_bank_contrastive: like _ContrastiveFn the gradient is computed in the forward, saved, and multiplied by the
+    incoming scalar; nothing crosses ranks.  ``log_scale`` is the learnable parameter or None; ``scale`` is the logit scale
+    in effect and ``scale_grad`` whether the clamp lets a gradient through to ``log_scale``."""
+
+    @staticmethod
+    def forward(ctx, student, log_scale, pos, bank, inv_norm, group, scale, scale_grad):
+        want_ds = ctx.needs_input_grad[0]
+        want_dscale = log_scale is not None and ctx.needs_input_grad[1]
+        _, loss, ds, dscale = cabi.bank_contrastive(student.detach(), bank, inv_norm, pos, scale, group, want_grad=want_ds,
+                                                    want_dscale=want_dscale)
+        ctx.want_ds, ctx.want_dscale = want_ds, want_dscale
+        saved = [ds] if want_ds else []
+        if want_dscale:         # d L / d log_scale = scale dL/dscale where the clamp at log(max_scale) is not in effect
+            saved.append((dscale[0] * (scale if scale_grad else 0.0)).to(log_scale.dtype).reshape(log_scale.shape))
+        ctx.save_for_backward(*saved)
+        return loss[0].to(student.dtype)
+
+    @staticmethod
+    def backward(ctx, g):
+        saved = ctx.saved_tensors
+        ds = saved[0] * g if ctx.want_ds else None
+        dlog = saved[-1] * g.to(saved[-1].dtype) if ctx.want_dscale else None
+        return ds, dlog, None, None, None, None, None, None
+
+
+class BankContrastiveLoss(nn.Module):
+    """The contrastive loss (InfoNCE) of student rows against a fixed BANK: the frozen teacher's rows of the M distinct
+    images of the dataset, L2-normalised like the student rows, at logit scale 1 / temperature:
+        L = (1/B) sum_i [ lse_{m allowed}(a s^_i . t^_m) - a s^_i . t^_pos_i ].
+    Every image is a negative of every query at every step, and with a frozen teacher the bank is exact, never stale.
+    ``set_bank(bank[M,D], bank_group=None)`` keeps the bank (no copy) and computes its inverse norms once; they are computed
+    again when another tensor is set or the tensor's ``_version`` changes.  ``bank_group`` ([M] integers, e.g. the class):
+    key m is left out of query i when bank_group[m] == bank_group[pos_i] and m != pos_i.
+    ``forward(student[B,D], pos[B])`` (``pos``: each row's positive as an index into the bank) returns the mean over the
+    given rows.  The loss is a plain mean over rows, as the cosine loss is: micro-batches sum to the full batch, a ragged
+    batch is fine, and there is no collective -- the mean all-reduce of the parameter gradients that FlatGrads / DDP perform
+    gives the gradient of the global mean.  The bank gets no gradient.
+
+    ``learnable_temperature=True`` keeps ``log_scale`` = log(1 / temperature) as an nn.Parameter, as ContrastiveLoss does:
+    the scale in effect is exp(min(log_scale, log(max_scale))), its gradient scale * dL/dscale of the local rows.
+
+    Default, and always for CPU or non-float32 tensors: torch ops in the dtype of the student rows (F.normalize x 2, one
+    matmul, masked_fill(-inf), cross_entropy).  ``fused=True`` on float32 device tensors: value and gradient in float64
+    from one csn_bank_contrastive call (six launches; four under no_grad), each float32 output rounded once."""
+
+    def __init__(self, temperature=0.07, learnable_temperature=False, max_scale=100.0, fused=False):
+        super().__init__()
+        if not (temperature > 0 and np.isfinite(temperature)) or not (max_scale > 0 and np.isfinite(max_scale)):
+            raise ValueError(f"BankContrastiveLoss: temperature {temperature} and max_scale {max_scale} must be finite and positive")
+        self.max_scale, self.fused = float(max_scale), bool(fused)
+        log_scale = torch.tensor(float(np.log(1.0 / temperature)))
+        if learnable_temperature:
+            self.log_scale = nn.Parameter(log_scale)
+        else:
+            self.log_scale = None
+            self._scale = min(1.0 / float(temperature), self.max_scale)
+        self.bank = self.bank_group = self._inv_norm = self._normed = None
+
+    def scale(self):
+        """(the logit scale in effect, whether log_scale is below the clamp)."""
+        if self.log_scale is None:
+            return self._scale, False
+        v, top = float(self.log_scale.detach()), float(np.log(self.max_scale))
+        return (float(np.exp(v)), True) if v <= top else (self.max_scale, False)
+
+    def set_bank(self, bank, bank_group=None):
+        if bank.dim() != 2 or bank.shape[0] < 1:
+            raise ValueError(f"BankContrastiveLoss: bank {tuple(bank.shape)} must be [M,D]")
+        if bank_group is not None:
+            if tuple(bank_group.shape) != (bank.shape[0],) or bank_group.is_floating_point():
+                raise ValueError(f"BankContrastiveLoss: bank_group {tuple(bank_group.shape)} {bank_group.dtype} must be "
+                                 f"[{bank.shape[0]}] integers")
+            bank_group = bank_group.to(device=bank.device, dtype=torch.int32).contiguous()
+        self.bank, self.bank_group = bank.detach(), bank_group
+        self._inv_norm = self._normed = None
+        self.bank_inv_norm()
+
+    def bank_inv_norm(self):
+        """1 / max(|t_m|, 1e-12) of the bank rows, float64 [M]: csn_bank_norms for a float32 device bank, torch ops
+        otherwise; computed once per (tensor, version)."""
+        if self.bank is None:
+            raise ValueError("BankContrastiveLoss: set_bank() first")
+        key = (self.bank.data_ptr(), tuple(self.bank.shape), self.bank._version)
+        if self._normed != key:
+            if self.bank.is_cuda and self.bank.dtype == torch.float32:
+                self._inv_norm = cabi.bank_norms(self.bank)
+            else:
+                self._inv_norm = 1.0 / self.bank.double().norm(dim=1).clamp_min(1e-12)
+            self._normed = key
+        return self._inv_norm
+
+    def forward(self, student, pos):
+        if self.bank is None:
+            raise ValueError("BankContrastiveLoss: set_bank() first")
+        if student.dim() != 2 or student.shape[1] != self.bank.shape[1]:
+            raise ValueError(f"BankContrastiveLoss: student {tuple(student.shape)} must be [B,{self.bank.shape[1]}]")
+        if tuple(pos.shape) != (student.shape[0],) or pos.is_floating_point():
+            raise ValueError(f"BankContrastiveLoss: pos {tuple(pos.shape)} {pos.dtype} must be [{student.shape[0]}] integers")
+        scale, below = self.scale()
+        if self.fused and _fusable(student, self.bank, pos) and student.device == self.bank.device:
+            inv_norm = self.bank_inv_norm()
+            return _BankContrastiveFn.apply(student, self.log_scale, pos.to(torch.int32).contiguous(), self.bank, inv_norm,
+                                            self.bank_group, scale, below)
+        if self.log_scale is not None:
+            scale = torch.exp(torch.clamp(self.log_scale, max=float(np.log(self.max_scale)))).to(student.dtype)
+        pos = pos.long()
+        bank = self.bank.to(student.dtype)
+        z = scale * (F.normalize(student, dim=1, eps=1e-12) @ F.normalize(bank, dim=1, eps=1e-12).T)
+        if self.bank_group is not None:
+            keys = torch.arange(bank.shape[0], device=pos.device)
+            out = (self.bank_group[None, :] == self.bank_group[pos][:, None]) & (keys[None, :] != pos[:, None])
+            z = z.masked_fill(out, float("-inf"))
+        return F.cross_entropy(z, pos)
 
 
 class LARS(torch.optim.Optimizer):

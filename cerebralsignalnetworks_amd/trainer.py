@@ -20,7 +20,7 @@ import torch.nn as nn
 
 from . import filters
 from .flat_optim import StepGuarded, check_max_grad_norm, guard_restatement
-from .losses import (CosineSimilarityLoss, FeatureDistributionLoss, HyperParams, loss_fn_kd, BarlowTwinsLoss, ContrastiveLoss,
+from .losses import (CosineSimilarityLoss, FeatureDistributionLoss, HyperParams, loss_fn_kd, BarlowTwinsLoss, ContrastiveLoss, BankContrastiveLoss,
                      LARS)
 
 
@@ -251,11 +251,16 @@ class DistillTrainer:
         the FIXED ``contrastive_temperature`` (the loss module's parameters are not in the model's flat buffer, so a learnable
         temperature would never be stepped), over the global batch of all ranks; ``fused_loss=True`` selects
         csn_contrastive_lse + csn_contrastive_grad (float64, seven launches).  train_step's ``groups`` are its group ids.
+        ``loss="contrastive_bank"``: BankContrastiveLoss at the same fixed temperature against the bank given to
+        ``set_bank`` -- every image's teacher row a negative at every step; train_step's ``positives`` are each row's index
+        into the bank (``targets`` is not read).  It is a mean over rows: micro-batches and ragged shards are fine, and
+        nothing but the gradient all-reduce crosses ranks.  ``fused_loss=True`` selects csn_bank_contrastive (float64, six
+        launches).
 
         ``accum_steps = k > 1``: train_step splits its batch into k equal micro-batches and sums their gradients (each
         loss scaled by 1 / k) in the flat buffer before the one all-reduce and optimiser step -- the step of the whole
         batch in 1 / k of the workspace.  That equals the full batch only for a loss that is a mean over rows (cosine,
-        featdist, kd); barlow normalises with batch statistics and contrastive takes its negatives from the batch: both
+        featdist, kd, contrastive_bank); barlow normalises with batch statistics and contrastive takes its negatives from the batch: both
         are refused.
 
         ``max_grad_norm=m``: the GLOBAL gradient norm is clipped to m, with the coefficient of
@@ -322,6 +327,8 @@ class DistillTrainer:
         self.kd_params = kd_params
         self.barlow = None
         self.contrastive = ContrastiveLoss(temperature=contrastive_temperature, fused=fused_loss) if loss == "contrastive" else None
+        self.contrastive_bank = BankContrastiveLoss(temperature=contrastive_temperature, fused=fused_loss) \
+            if loss == "contrastive_bank" else None
         rank, world = dist_info()
         if world > 1:   # identical initial weights on every rank
             for p in model.parameters():
@@ -373,6 +380,13 @@ class DistillTrainer:
                 self._hook_error = e
         lstm.grad_ready_hook = layer_ready
 
+    def set_bank(self, bank, bank_group=None):
+        """loss="contrastive_bank": the bank [M,D] of teacher rows (EEGDataset.image_bank) and, optionally, the group id
+        of each row (rows of the positive's group are not negatives)."""
+        if self.contrastive_bank is None:
+            raise ValueError(f'set_bank needs loss="contrastive_bank", this trainer has loss="{self.loss_name}"')
+        self.contrastive_bank.set_bank(bank, bank_group)
+
     def embed(self, eeg_bct):
         """raw EEG [B,C,T] (device, float32) -> model input [B,T,C]."""
         if self.preprocess:
@@ -381,7 +395,7 @@ class DistillTrainer:
             return filters.eeg_bandpass_znorm(eeg_bct, self.sos, ddof=self.ddof, time_major=True).transpose(0, 1)
         return eeg_bct.transpose(1, 2).contiguous()
 
-    def compute_loss(self, out, targets, labels, epoch, groups=None):
+    def compute_loss(self, out, targets, labels, epoch, groups=None, positives=None):
         if self.loss_name == "cosine":
             feat = out[0] if isinstance(out, tuple) else out
             return self.cosine(feat, targets)
@@ -402,11 +416,17 @@ class DistillTrainer:
         if self.loss_name == "contrastive":
             feat = out[0] if isinstance(out, tuple) else out
             return self.contrastive(feat, targets, groups)
+        if self.loss_name == "contrastive_bank":
+            feat = out[0] if isinstance(out, tuple) else out
+            if positives is None:
+                raise ValueError('loss="contrastive_bank" needs positives: each row\'s index into the bank')
+            return self.contrastive_bank(feat, positives)
         raise ValueError(self.loss_name)
 
-    def train_step(self, eeg_bct, targets, labels=None, epoch=0, groups=None):
+    def train_step(self, eeg_bct, targets, labels=None, epoch=0, groups=None, positives=None):
         """One optimisation step on this rank's shard of the global batch; returns the (device) loss.  ``groups`` ([B]
-        integers): the group ids of loss="contrastive" (rows of one group are not each other's negatives).  With
+        integers): the group ids of loss="contrastive" (rows of one group are not each other's negatives).  ``positives``
+        ([B] integers): each row's index into the bank of loss="contrastive_bank".  With
         ``accum_steps = k > 1`` the shard runs as k equal micro-batches whose gradients are summed in the flat buffer (the
         returned loss is the sum of their losses / k); all-reduce and optimiser step follow the last one."""
         k = self.accum_steps
@@ -420,11 +440,13 @@ class DistillTrainer:
                 self._others_left = self._n_others
             x = self.embed(eeg_bct)
             out = self.model(x)
-            loss = self.compute_loss(out, targets, labels, epoch) if groups is None else \
-                self.compute_loss(out, targets, labels, epoch, groups=groups)
+            kw = {} if groups is None else {"groups": groups}
+            if positives is not None:
+                kw["positives"] = positives
+            loss = self.compute_loss(out, targets, labels, epoch, **kw)
             loss.backward()
         else:
-            loss = self._micro_batches(eeg_bct, targets, labels, epoch, k)
+            loss = self._micro_batches(eeg_bct, targets, labels, epoch, k, positives)
         if self._hook_error is not None:
             err, self._hook_error = self._hook_error, None
             raise err
@@ -476,7 +498,7 @@ class DistillTrainer:
             return self.opt.skipped_steps()
         return int(self._restated_skips)
 
-    def _micro_batches(self, eeg_bct, targets, labels, epoch, k):
+    def _micro_batches(self, eeg_bct, targets, labels, epoch, k, positives=None):
         """embed -> forward -> loss / k -> backward per micro-batch, all into the flat buffer.  The gradient-ready hook is
         armed for the last backward only: an overlapped all-reduce must not start on partial sums."""
         mb = eeg_bct.shape[0] // k
@@ -492,7 +514,8 @@ class DistillTrainer:
                 if last and self.grads.segments is not None:
                     self._others_left = self._n_others
                 out = self.model(self.embed(eeg_bct[rows]))
-                loss = self.compute_loss(out, targets[rows], None if labels is None else labels[rows], epoch) / k
+                kw = {} if positives is None else {"positives": positives[rows]}
+                loss = self.compute_loss(out, targets[rows], None if labels is None else labels[rows], epoch, **kw) / k
                 loss.backward()
                 total = loss.detach() if total is None else total + loss.detach()
         finally:

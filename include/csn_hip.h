@@ -96,7 +96,7 @@ enum csnDtype { CSN_F32 = 0, CSN_BF16 = 1 };
 /* ABI version of this header; bumped on any signature change.  A symbol added beside the existing ones
  * (csn_lstm_plan_set_grad_mode, csn_lstm_plan_set_lengths, csn_lstm_plan_set_views, csn_lstm_plan_set_io, csn_lstm_plan_set_readout, csn_lstm_plan_half_tile_launches, the
  * csn_flat_* family, csn_adam_step, csn_lars_step, csn_eeg_bandpass_stream and its _path, csn_distill_loss,
- * csn_dino_loss, csn_barlow_corr, csn_barlow_grad, csn_contrastive_lse, csn_contrastive_grad, csn_topk_merge and its _staged_max, csn_topk_class_metrics, csn_grad_guard, its _scratch_bytes and the three
+ * csn_dino_loss, csn_barlow_corr, csn_barlow_grad, csn_contrastive_lse, csn_contrastive_grad, csn_bank_norms, csn_bank_contrastive and its _scratch_bytes, csn_topk_merge and its _staged_max, csn_topk_class_metrics, csn_grad_guard, its _scratch_bytes and the three
  * csn_*_step_guarded) breaks no caller and does not bump it; neither does a new bit of csn_lstm_plan_create's `training` word. */
 #define CSN_ABI_VERSION 6
 int csn_abi_version(void);
@@ -775,6 +775,49 @@ int csn_contrastive_lse(const float* s_all, const float* t_all, const int* group
 int csn_contrastive_grad(const float* s_all, const float* t_all, const int* group_all, int N, int D, int row0, int B,
                          double logit_scale, const double* lse_a_local, const double* lse_b_all, double w_a, double w_b,
                          double grad_scale, float* ds, double* dscale_part, void* scratch, csnStream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * K7d  the contrastive (InfoNCE) loss of student rows against a fixed BANK of frozen teacher rows: every row of the bank
+ * is a key of every query, so every image of the dataset is a negative at every step.
+ * bank [M,D] float32; bank_inv_norm [M] float64 = 1 / max(|t_m|, 1e-12), computed once per bank by csn_bank_norms (a NaN
+ * norm stays NaN); bank_group [M] int32 or NULL; s [B,D] float32; pos [B] int32: row i's positive as an index into the
+ * bank; a = logit_scale.  Key m is left out of query i when bank_group[m] == bank_group[pos_i] and m != pos_i (the
+ * positive itself never is); NULL leaves nothing out.
+ *     s^_i = s_i / max(|s_i|, 1e-12),  t^_m = t_m bank_inv_norm[m]          (F.normalize)
+ *     l_i = log sum_{m allowed} exp(a s^_i . t^_m)        p_i = a s^_i . t^_pos_i
+ *     loss_part = inv_rows sum_i (l_i - p_i)
+ *     dL/ds^_i = a inv_rows (sum_m P_im t^_m - t^_pos_i),      P_im = exp(a s^_i . t^_m - l_i), 0 where left out
+ *     ds_i = grad_scale (dL/ds^_i - s^_i (s^_i . dL/ds^_i)) / max(|s_i|, 1e-12)      the projection only where |s_i| > 1e-12
+ *     dscale_part = inv_rows sum_i (sum_m P_im s^_i . t^_m - s^_i . t^_pos_i)        not scaled by grad_scale
+ * One call: against a fixed bank the loss is a plain mean over rows, nothing crosses ranks (inv_rows = 1 / the rows the
+ * mean is over: the local batch, or the whole batch when the call sees a micro-batch of it).  The bank gets no gradient.
+ *   rows_out float64 [2][B]: l, p;  loss_part float64 [1];  ds float32 [B,D] or NULL: the value part only (4 launches
+ *   instead of 6);  dscale_part float64 [1] or NULL.
+ * Float64 arithmetic on the float32 inputs, every float32 output rounded once; the logit is the product a (s^ . t^) rounded
+ * on its own; every log-sum-exp subtracts its maximum.  A row's l, p and ds depend on (M, D), the scalars and the data
+ * alone, not on B or on the row's place in the batch: the sums over keys run per row, thread x of 256 over keys x, x + 256,
+ * ... in ascending order and then a fixed tree, and the ds contraction in ceil(M / w) splits of w = max(64, 32 ceil(M / 2048))
+ * keys merged in ascending order.  loss_part and dscale_part add the rows in an order that depends on B only.  Two calls
+ * give the same bits.
+ * A key that is left out never goes through exp (a NaN there propagates nothing, into no output); a NaN in an allowed
+ * key makes that query's l, p-term and ds row NaN and no other row's; a pos_i outside [0, M) gives row i a NaN l, p and
+ * ds row and indexes nothing (csn_distill_loss's convention for a bad label; no device assert).  A query whose only
+ * allowed key is its positive has l == p bit for bit, loss term 0 and a ds row of zeros.
+ * scratch: caller-owned, 8-byte aligned, csn_bank_contrastive_scratch_bytes(B, M, D) =
+ *     8 * (4 B + B M + ceil(M / w) B D)  bytes,  w as above
+ *   (norms and per-row terms | the B x M dot products, then weights | the ds splits).  0 for arguments the call refuses.
+ *   No library state; everything is enqueued on `stream`.
+ * Refused on the host before any launch: a null pointer other than bank_group / ds / dscale_part; B, M or D <= 0 (B above
+ * 1 048 560); logit_scale not finite or <= 0; inv_rows or grad_scale not finite; bank_inv_norm, rows_out, loss_part,
+ * dscale_part or scratch not 8-byte aligned (csn_bank_norms: inv_norm).
+ * Replaces: nothing in the reference; the torch expression is F.normalize x 2, one matmul, masked_fill, cross_entropy.
+ * ---------------------------------------------------------------------------------- */
+int csn_bank_norms(const float* bank, int M, int D, double* inv_norm, csnStream_t stream);
+size_t csn_bank_contrastive_scratch_bytes(int B, int M, int D);
+int csn_bank_contrastive(const float* s, int B, int D, const float* bank, const double* bank_inv_norm,
+                         const int32_t* bank_group, int M, const int32_t* pos, double logit_scale, double inv_rows,
+                         double grad_scale, double* rows_out, double* loss_part, float* ds, double* dscale_part, void* scratch,
+                         csnStream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * K8  exact squared-L2 top-k.  Replaces: faiss.IndexFlatL2(d).add / .search(k),
