@@ -97,9 +97,10 @@ def build_parser(flavour=PERILS):
     p.add_argument('--resident_lstm', action='store_true',
                    help='hidden_size <= 128: the LSTM runs the steps of a chunk inside one launch per layer, W_hh in '
                         'registers (CSN_LSTM_RESIDENT plans), with the bits of the per-step cell kernels')
-    p.add_argument('--readout', type=str, default="last", choices=["last", "mean", "max"],
+    p.add_argument('--readout', type=str, default="last", choices=["last", "mean", "max", "attn"],
                    help='what fc reads of the LSTM output sequence: its last step, or its mean / maximum over time, reduced '
-                        'inside the library (no parameter depends on it; evaluate a checkpoint with the readout it was trained with)')
+                        'inside the library (no parameter depends on these), or "attn": their weighted mean under a learned query '
+                        '(the checkpoint then holds lstm.attn_query); evaluate a checkpoint with the readout it was trained with')
     p.add_argument('--output_size', type=int, default=384)
     p.add_argument('--loss', type=str, default=flavour.loss, choices=["featdist", "cosine", "kd", "barlow", "contrastive", "contrastive_bank"],
                    help='contrastive_bank: InfoNCE against the bank of every image\'s teacher row (all images are negatives at every '

@@ -70,9 +70,9 @@ def build_parser():
     p.add_argument('--resident_lstm', action='store_true',
                    help='embed_dim <= 128: student and teacher LSTMs run the steps of a chunk inside one launch per layer, '
                         'W_hh in registers (CSN_LSTM_RESIDENT plans), with the bits of the per-step cell kernels')
-    p.add_argument('--readout', type=str, default="last", choices=["last", "mean", "max"],
+    p.add_argument('--readout', type=str, default="last", choices=["last", "mean", "max", "attn"],
                    help='what the heads read of the LSTM output sequence of student and teacher: its last step, or its mean / '
-                        'maximum over time, reduced inside the library')
+                        'maximum over time, reduced inside the library, or "attn": their weighted mean under a learned query')
     p.add_argument('--dtype', type=str, default="bf16", choices=["bf16", "f32"])
     p.add_argument('--time_low', type=int, default=0)
     p.add_argument('--time_high', type=int, default=495)

@@ -62,6 +62,7 @@ SIGNATURES = {
                                          ctypes.c_int32, ctypes.c_int32]),
     "csn_lstm_plan_set_io": (_c_int, [_c_void_p, _c_i64, _c_i64, _c_int]),
     "csn_lstm_plan_set_readout": (_c_int, [_c_void_p, _c_int]),
+    "csn_lstm_plan_set_attention": (_c_int, [_c_void_p, _c_void_p, ctypes.c_float, _c_void_p, _c_void_p, _c_void_p]),
     "csn_lstm_plan_set_dropout": (_c_int, [_c_void_p, _c_float, ctypes.c_uint64, ctypes.c_uint32]),
     "csn_lstm_plan_set_output_dropout": (_c_int, [_c_void_p, _c_float, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint64,
                                                   _c_i64]),
@@ -532,6 +533,33 @@ class LstmPlan:
         (csn_lstm_plan_set_readout): "last" (the default), "mean" or "max" over each row's valid steps, or the
         READOUT_* integer.  Sticky until set again; a backward must run with the setting of its forward."""
         _check(load().csn_lstm_plan_set_readout(self._plan, readout_mode(mode)))
+
+    def set_attention(self, q=None, scale=None, dq=None, attn_out=None, dscore_out=None):
+        """The attention readout of the following forward() / backward() calls (csn_lstm_plan_set_attention): with a query
+        ``q`` ([H] float32 on the device) y_last is the weighted mean over each row's valid steps under the weights
+        softmax_t(scale <h_t, q>) (scale: H ** -0.5 unless given), whatever set_readout says, and backward() takes
+        dy_last as its gradient.  dq: [H] float32 that backward() writes the query's gradient into (added to after
+        set_grad_mode(True)), or None for a frozen query.  attn_out / dscore_out: dense [B,T] float32 tensors that
+        receive the weights (forward and backward) and the score gradients (backward), or None.  ``set_attention()``
+        turns it off.  Sticky until set again; the tensors must stay alive while the setting is in use, and a backward
+        must run with the setting of its forward."""
+        d = self.desc
+        if q is None:
+            if dq is not None or attn_out is not None or dscore_out is not None:
+                raise CsnError("LSTM attention: dq, attn_out or dscore_out without a query")
+            _check(load().csn_lstm_plan_set_attention(self._plan, None, 0.0, None, None, None))
+            return
+        for t, shape, name in ((q, (d.H,), "q"), (dq, (d.H,), "dq"), (attn_out, (d.B, d.T), "attn_out"),
+                               (dscore_out, (d.B, d.T), "dscore_out")):
+            if t is None:
+                continue
+            _need_cuda(t)
+            if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous():
+                raise CsnError(f"LSTM attention {name}: a dense float32 tensor of shape {list(shape)} is needed, got "
+                               f"{t.dtype} {list(t.shape)}")
+        scale = float(d.H) ** -0.5 if scale is None else float(scale)
+        _check(load().csn_lstm_plan_set_attention(self._plan, _ptr(q.detach()), scale, _ptr(dq), _ptr(attn_out),
+                                                  _ptr(dscore_out)))
 
     def _pitched(self, t, pitch, name):
         """t must be a float32 [B,T,H] device view with strides (T * pitch, pitch, 1), 16-byte aligned."""

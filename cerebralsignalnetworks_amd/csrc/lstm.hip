@@ -40,6 +40,7 @@
 //              buffers of h and dgates.  In paths 1 - 3 every 4H axis is gate-interleaved
 //              (n' = 4 unit + gate); parameters and their gradients are (un)permuted at the API.
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <vector>
 
@@ -372,6 +373,13 @@ struct csnLstmPlan {
   int dx_add = 0;                        // csn_lstm_plan_set_io: dx is added to over the valid steps, not overwritten
   int readout = CSN_READOUT_LAST;        // csn_lstm_plan_set_readout: what y_last is, and where dy_last enters
   int32_t* argmax_dev = nullptr;         // [B, H] int32 owned by the plan: the MAX backward's argmax, written and read in stream order
+  // csn_lstm_plan_set_attention (sticky; q = null = off): the learned-query readout in place of the mode above.  attn_dev:
+  // the [B, T] arrays and the dq partials of one call (AttnArgs), owned by the plan, allocated on first use, written and
+  // read in stream order inside the one call like argmax_dev
+  const float* attn_q = nullptr;
+  float attn_scale = 0.f;
+  float *attn_dq = nullptr, *attn_out = nullptr, *attn_dscore = nullptr;
+  char* attn_dev = nullptr;
   // csn_lstm_plan_set_output_dropout (sticky; p = 0 = off): the mask the layout passes apply to y_all as they store it and
   // to dy_all as they load it, indexed on the caller's tensor
   float out_drop_p = 0.f;
@@ -455,6 +463,7 @@ extern "C" void csn_lstm_plan_destroy(csnLstmPlan* P) {
   if (P->view_pin) (void)hipHostFree(P->view_pin);
   if (P->view_dev) (void)hipFree(P->view_dev);
   if (P->argmax_dev) (void)hipFree(P->argmax_dev);
+  if (P->attn_dev) (void)hipFree(P->attn_dev);
   if (switched) (void)hipSetDevice(cur);
   delete P;
 }
@@ -599,6 +608,19 @@ extern "C" int csn_lstm_plan_set_io(csnLstmPlan* P, int64_t y_all_pitch, int64_t
   P->y_pitch = y_all_pitch == P->d.H ? 0 : y_all_pitch;
   P->dy_pitch = dy_all_pitch == P->d.H ? 0 : dy_all_pitch;
   P->dx_add = dx_add != 0;
+  return CSN_OK;
+}
+
+extern "C" int csn_lstm_plan_set_attention(csnLstmPlan* P, const float* q, float scale, float* dq, float* attn_out, float* dscore_out) {
+  CSN_REQUIRE(P != nullptr, "csn_lstm_plan_set_attention: null plan");
+  CSN_REQUIRE(std::isfinite(scale), "csn_lstm_plan_set_attention: scale is not finite");
+  CSN_REQUIRE(q != nullptr || (dq == nullptr && attn_out == nullptr && dscore_out == nullptr),
+              "csn_lstm_plan_set_attention: dq, attn_out or dscore_out without q");
+  P->attn_q = q;
+  P->attn_scale = scale;
+  P->attn_dq = dq;
+  P->attn_out = attn_out;
+  P->attn_dscore = dscore_out;
   return CSN_OK;
 }
 
@@ -1834,7 +1856,27 @@ static int emit_state(const Call& C, int l, float* h_n, float* c_n) {
   if (c_n) return launch_gather_state(C.ws + L.c_all, CSN_F32, C.dlen, C.T, c_n + at, C.B, C.H, C.st);
   return CSN_OK;
 }
+// the attention readout's arrays of this call: the caller's attn_out / dscore_out where given, else plan-owned like the rest
+static int attn_args(const Call& C, AttnArgs& A) {
+  Plan& P = C.P;
+  const size_t BT = (size_t)C.B * C.T_full, r8 = (BT * 8 + 255) / 256 * 256, r4 = (BT * 4 + 255) / 256 * 256;
+  if (P.attn_dev == nullptr) CSN_HIP_CHECK(hipMalloc((void**)&P.attn_dev, 2 * r8 + 2 * r4 + (size_t)kAttnDqParts * C.H * 8));
+  char* p = P.attn_dev;
+  A.q = P.attn_q;
+  A.scale = P.attn_scale;
+  A.a64 = (double*)p;
+  A.g64 = (double*)(p + r8);
+  A.a32 = P.attn_out ? P.attn_out : (float*)(p + 2 * r8);
+  A.w32 = P.attn_dscore ? P.attn_dscore : (float*)(p + 2 * r8 + r4);
+  A.dq_part = (double*)(p + 2 * r8 + 2 * r4);
+  return CSN_OK;
+}
 static int emit_y_last(const Call& C, float* y_last) {
+  if (C.P.attn_q != nullptr) {
+    AttnArgs A;
+    if (int rc = attn_args(C, A)) return rc;
+    return launch_attn_forward(C.ws + C.w.layer[C.NL - 1].h_all, C.dt, A, y_last, row_map(C, C.H, 0), C.st);
+  }
   if (C.P.readout != CSN_READOUT_LAST)
     return launch_pool_readout(C.ws + C.w.layer[C.NL - 1].h_all, C.dt, C.P.readout, y_last, row_map(C, C.H, 0), C.st);
   return launch_gather_state(C.ws + C.w.layer[C.NL - 1].h_all, C.dt, C.dlen, C.T, y_last, C.B, C.H, C.st);
@@ -1908,12 +1950,19 @@ static int assemble_top_dy(const Call& C, BwdArgs& A, const float* dy_all) {
   const size_t BH = (size_t)C.B * C.H;
   const float* dh_top = A.dh_n ? A.dh_n + (C.NL - 1) * BH : nullptr;
   int rc;
-  if (A.dy_last && C.P.readout != CSN_READOUT_LAST) {
+  if (A.dy_last && (C.P.attn_q != nullptr || C.P.readout != CSN_READOUT_LAST)) {
     // the pooled readout: dy_last reaches every valid step (MEAN) or the first maximum (MAX, found again in the saved h),
     // inside the layout pass; then the top layer's dh_n at each row's end, as below
-    PoolIn pool{C.P.readout, A.dy_last, nullptr};
+    PoolIn pool{C.P.readout, A.dy_last, nullptr, nullptr, nullptr, nullptr};
     const RowMap m = row_map(C, C.H, C.P.dy_pitch);
-    if (pool.mode == CSN_READOUT_MAX) {
+    if (C.P.attn_q != nullptr) {
+      // the attention readout: the weights are computed again from the saved h and q, with the score gradients and dq
+      // (all of it in front of the recurrence: dq is complete when the first gradient-ready callback fires)
+      AttnArgs at;
+      if ((rc = attn_args(C, at))) return rc;
+      if ((rc = launch_attn_backward(C.ws + C.w.layer[C.NL - 1].h_all, C.dt, at, A.dy_last, C.P.attn_dq, C.P.grad_accumulate, m, C.st))) return rc;
+      pool = PoolIn{kPoolAttention, A.dy_last, nullptr, at.a32, at.w32, at.q};
+    } else if (pool.mode == CSN_READOUT_MAX) {
       if (C.P.argmax_dev == nullptr) CSN_HIP_CHECK(hipMalloc((void**)&C.P.argmax_dev, BH * 4));
       if ((rc = launch_pool_argmax(C.ws + C.w.layer[C.NL - 1].h_all, C.dt, C.P.argmax_dev, m, C.st))) return rc;
       pool.argmax = C.P.argmax_dev;
@@ -1990,6 +2039,13 @@ extern "C" int csn_lstm_backward(csnLstmPlan* Pp, const float* dy_last, const fl
   Call C(P, workspace, st, dlen);
   BwdArgs A{dy_last, nullptr, dh_n, dc_n, dw_ih, dw_hh, db_ih, db_hh, dx};
   const size_t BH = (size_t)C.B * C.H;
+  // (the attention readout without a dy_last, or with every row empty: nothing reaches the query, and the weights are zero)
+  if (P.attn_q != nullptr && (dy_last == nullptr || C.T == 0)) {
+    const size_t BT = (size_t)C.B * C.T_full;
+    if (P.attn_dq && !P.grad_accumulate) CSN_HIP_CHECK(hipMemsetAsync(P.attn_dq, 0, (size_t)C.H * 4, st));
+    if (dy_last && P.attn_out) CSN_HIP_CHECK(hipMemsetAsync(P.attn_out, 0, BT * 4, st));
+    if (dy_last && P.attn_dscore) CSN_HIP_CHECK(hipMemsetAsync(P.attn_dscore, 0, BT * 4, st));
+  }
   if (C.T > 0) {
     if ((rc = assemble_top_dy(C, A, dy_all))) return rc;
     if ((rc = run_backward(C, A))) return rc;
@@ -2009,7 +2065,7 @@ extern "C" int csn_lstm_backward(csnLstmPlan* Pp, const float* dy_last, const fl
       if (dlen && dh_n && (rc = launch_add_rows_len0(dh_n + l * BH, out, dlen, C.B, C.H, st))) return rc;
       // ... and y_last of an empty row is h_n of the top layer, that is its h0: dy_last reaches dh0 there (a pooled
       // readout of an empty row is zero instead)
-      if (dlen && dy_last && P.readout == CSN_READOUT_LAST && l == C.NL - 1 && (rc = launch_add_rows_len0(dy_last, out, dlen, C.B, C.H, st))) return rc;
+      if (dlen && dy_last && P.readout == CSN_READOUT_LAST && P.attn_q == nullptr && l == C.NL - 1 && (rc = launch_add_rows_len0(dy_last, out, dlen, C.B, C.H, st))) return rc;
     }
     if (dc0) {
       // the carried dc (an empty row's passed every masked step as it was); without a step, dc_n itself

@@ -1,8 +1,9 @@
 // The API boundary of the stacked LSTM (lstm_boundary.hip): everything that turns the caller's batch-first float32 tensors
 // into the time-major workspace and back around the recurrence -- one kernel per layout pass (y_all out, dy_all in, dx out)
 // whatever the plan's lengths, direction, pitch, adding store or output dropout (DESIGN.md sections 10, 16 and 23), the
-// pooled readout (mean / max over time in place of the last step, section 26), and the small per-row helpers of
-// variable-length batches.  lstm.hip calls the launchers below and launches none of this itself.
+// pooled readout (mean / max over time in place of the last step, section 26), the attention readout (a learned-query
+// weighted mean over time, section 28), and the small per-row helpers of variable-length batches.  lstm.hip calls the
+// launchers below and launches none of this itself.
 #pragma once
 #include "lstm_dropout.h"
 
@@ -32,10 +33,28 @@ struct RowSteps {
 // The pooled term of dy_in (csn_lstm_plan_set_readout): the gradient w.r.t. the pooled y_last, and under MAX the caller time
 // per (b, h) that receives it (launch_pool_argmax)
 struct PoolIn {
-  int mode;                // CSN_READOUT_*
+  int mode;                // CSN_READOUT_*, or kPoolAttention
   const float* dy_last;    // [B, H]
   const int* argmax;       // [B, H] int32, MAX only
+  const float* a32;        // [B, Tn] attention weights, w32: [B, Tn] score gradients, q: [H] the query -- kPoolAttention only
+  const float* w32;
+  const float* q;
 };
+// the attention readout's tag in PoolIn::mode (csn_lstm_plan_set_attention): internal, not a CSN_READOUT_* value
+constexpr int kPoolAttention = 16;
+
+// The attention readout (csn_lstm_plan_set_attention): the query, and the [B, Tn] arrays of one call.
+// a64 / g64 / dq_part are plan-owned scratch; a32 / w32 are the caller's attn_out / dscore_out, or plan-owned scratch too.
+struct AttnArgs {
+  const float* q;      // [H]
+  float scale;
+  double* a64;         // [B, Tn]: the scaled scores z, then exp(z - max), then the weights, in place
+  double* g64;         // [B, Tn]: <dy_last[b], v[b, t]> (backward)
+  float* a32;          // [B, Tn]: fl32 of the weights, 0 from a row's length on
+  float* w32;          // [B, Tn]: fl32(scale a (g - s)), 0 from a row's length on (backward)
+  double* dq_part;     // [kAttnDqParts, H]: the query gradient's partial sums (backward with dq)
+};
+constexpr int kAttnDqParts = 64;
 
 // The launchers.  od: output dropout (csn_lstm_plan_set_output_dropout), or null.  With it a thread moves four consecutive h
 // under one Philox call with 16-byte accesses of the caller's tensor, which must be 16-B aligned with pitch % 4 == 0;
@@ -44,13 +63,23 @@ struct PoolIn {
 int launch_y_out(const void* h_all, int dtype, float* y, const RowMap& m, const OutDropCfg* od, hipStream_t st);
 // dy_tm[s][b][h], s < Te  =  s < n && dy ? [keep ? scale *] dy[(b Tn + t) pitch + h] : 0      (dy null: all zeros)
 // pool (or null): + dy_last[b][h] / n (MEAN), + (argmax[b][h] == t ? dy_last[b][h] : 0) (MAX) for s < n, one float32 add behind
-// the dy element -- the term itself where dy is null
+// the dy element -- the term itself where dy is null; kPoolAttention: + fl32(fl32(a32[b][t] dy_last[b][h]) + fl32(w32[b][t] q[h]))
 int launch_dy_in(const float* dy, float* dy_tm, const RowMap& m, const OutDropCfg* od, const PoolIn* pool, hipStream_t st);
 // y[b][h] = mean (float64 sums, one rounding) or max (first maximum, a NaN wins) over t < n of float(h_all[slot(t)][b][h]);
 // zeros for n = 0.  m.pitch and m.Te are not read.  A fixed split of the steps: the same bits every call
 int launch_pool_readout(const void* h_all, int dtype, int mode, float* y, const RowMap& m, hipStream_t st);
 // argmax[b][h] = the first caller time t < n that attains that maximum (-1 for n = 0)
 int launch_pool_argmax(const void* h_all, int dtype, int* argmax, const RowMap& m, hipStream_t st);
+// The attention readout, forward: z[b][t] = scale <v[b][t], q> (float64 partials per lane, a fixed lane tree), its softmax
+// over t < n (float64, max-subtracted) into A.a64 and A.a32, and y[b][h] = fl32(sum over t < n of a64 v) with the split and
+// the LDS combine of the pooled readout.  Three launches, two reads of h_all; zeros for n = 0; the same bits every call
+int launch_attn_forward(const void* h_all, int dtype, const AttnArgs& A, float* y, const RowMap& m, hipStream_t st);
+// ... and the backward's pre-passes: the scores again with g[b][t] = <dy_last[b], v[b][t]> from the same load, the row
+// kernel with s = sum a g and A.w32 = fl32(scale a (g - s)), then (dq != null) dq[h] = or += fl32(sum over b, t < n of
+// w32 v): float64 partials per workgroup into A.dq_part, combined in a fixed order.  Two or four launches, at most two
+// reads of h_all.  What dy_in adds comes through PoolIn{kPoolAttention, dy_last, nullptr, A.a32, A.w32, A.q}
+int launch_attn_backward(const void* h_all, int dtype, const AttnArgs& A, const float* dy_last, float* dq, int accumulate, const RowMap& m,
+                         hipStream_t st);
 // dx[b][t][i] = or += dx_tm[s][b][i] for t < n; from n on zero, or with add left as it is      (m.H: the input width)
 int launch_dx_out(const float* dx_tm, float* dx, const RowMap& m, hipStream_t st);
 

@@ -62,22 +62,36 @@ class _Call:
     _draw_dropout's.  ``outputs``: which of (y_last, y_all, h_n, c_n) the entry point takes -- the library is asked for no
     other, and only their gradients go to plan.backward.  ``state_plan``: HipLSTM._checkout's ``state``.  ``overwrite``: is
     ``direct_grads = True`` honoured?  ``bi``: BiLSTM's (L, H).  ``readout``: what y_last is -- "last", "mean" or "max" over
-    each row's valid steps (csn_lstm_plan_set_readout); BiLSTM's top-layer plans then hand back their pooled halves."""
-    __slots__ = ("B", "T", "training", "drop", "lengths", "views", "outputs", "state_plan", "overwrite", "bi", "readout")
+    each row's valid steps (csn_lstm_plan_set_readout); BiLSTM's top-layer plans then hand back their pooled halves.
+    "attn": the attention readout (csn_lstm_plan_set_attention) with ``attn``, the query of each direction ([H] float32
+    parameters: one, or BiLSTM's two); ``want_weights``: the forward also fills ``attn_out``, one [B, T] float32 tensor of
+    attention weights per direction (the backward writes the same bits into them again)."""
+    __slots__ = ("B", "T", "training", "drop", "lengths", "views", "outputs", "state_plan", "overwrite", "bi", "readout", "attn",
+                 "want_weights", "attn_out")
 
     def __init__(self, x, training, drop, lengths=None, views=None, outputs=(True, False, False, False), state_plan=None,
-                 overwrite=True, bi=None, readout="last"):
+                 overwrite=True, bi=None, readout="last", attn=None, want_weights=False):
         self.readout = _check_readout("LSTM call", readout)
+        self.attn = tuple(attn) if readout == "attn" and attn is not None else None
+        if readout == "attn" and (self.attn is None or len(self.attn) != (1 if bi is None else 2)):
+            raise ValueError("LSTM call: the attention readout needs one query per direction")
+        self.want_weights, self.attn_out = bool(want_weights) and self.attn is not None, None
         self.B, self.T = (x.shape[0], x.shape[1]) if views is None else (len(lengths), max(1, max(lengths)))
         self.training, self.drop, self.lengths, self.views = training, drop, lengths, views
         self.outputs, self.state_plan, self.overwrite, self.bi = outputs, state_plan, overwrite, bi
 
+    def weights(self):
+        """The attention weights of the call's forward, detached: [B, T], or [B, T, 2] for the two directions."""
+        return self.attn_out[0] if len(self.attn_out) == 1 else torch.stack(self.attn_out, dim=2)
 
-def _armed(plan, call, fn, grad=None, k=None, src=None):
+
+def _armed(plan, call, fn, grad=None, k=None, src=None, dq=None):
     """fn() -- ``call``'s plan.forward or plan.backward -- with everything it depends on set on the plan first.  Plans are
     shared between calls and every setter of cabi.LstmPlan is sticky, so a pooled plan still carries whatever its last
     user set: nothing is assumed, all of it is set in front of every forward and backward.  That is: the readout (on
-    BiLSTM's plans below the top layer always "last": their y_last is not used); the lengths (None =
+    BiLSTM's plans below the top layer always "last": their y_last is not used) and the attention readout -- the query of
+    the plan's direction, the call's weights tensor and, on a backward, ``dq`` (where the query's gradient goes) on the top
+    plan(s) of an "attn" call, off on every other plan and call; the lengths (None =
     every row is T; on CSN_LSTM_STATE plans only, the library refuses set_lengths on others); on a stack's plan the
     inter-layer dropout (None = p 0, which a plan without the bit takes too); on BiLSTM's plan ``k`` = 2 * layer +
     direction the io pitches -- on a backward the reverse direction adds its dx to the forward one's -- and the output
@@ -85,7 +99,14 @@ def _armed(plan, call, fn, grad=None, k=None, src=None):
     drops each once; the top layer's is never dropped); on a backward ``grad`` = (callback, accumulate).  ``src``: the
     source tensor of a forward through input windows, which are cleared again, also when fn raises -- a backward reads no
     x, so it sets none."""
-    plan.set_readout(call.readout if k is None or k // 2 == call.bi[0] - 1 else "last")
+    top = k is None or k // 2 == call.bi[0] - 1
+    attn = top and call.readout == "attn"
+    plan.set_readout(call.readout if top and not attn else "last")
+    if attn:
+        d = 0 if k is None else k % 2
+        plan.set_attention(call.attn[d], None, dq, None if call.attn_out is None else call.attn_out[d])
+    else:
+        plan.set_attention()
     if plan.state:
         plan.set_lengths(call.lengths)
     if k is None:
@@ -154,10 +175,19 @@ def _check_dropout_p(p):
 
 def _check_readout(name, readout):
     """``readout``: which summary of the top layer's output sequence a module hands back -- "last" (each row's last valid
-    step), or "mean" / "max" over each row's valid steps, reduced inside the library (csn_lstm_plan_set_readout)."""
-    if not isinstance(readout, str) or readout not in cabi.READOUTS:
-        raise ValueError(f"{name}: readout must be one of {sorted(cabi.READOUTS)}, got {readout!r}")
+    step), "mean" / "max" over each row's valid steps, reduced inside the library (csn_lstm_plan_set_readout), or "attn":
+    their weighted mean under a learned query (csn_lstm_plan_set_attention; the module owns ``attn_query``)."""
+    if not isinstance(readout, str) or (readout not in cabi.READOUTS and readout != "attn"):
+        raise ValueError(f"{name}: readout must be one of {sorted([*cabi.READOUTS, 'attn'])}, got {readout!r}")
     return readout
+
+
+def _attn_queries(module, name):
+    """The attention queries a module owns, one per direction -- or ValueError: it was built without them."""
+    qs = [getattr(module, n, None) for n in (("attn_query", "attn_query_reverse") if getattr(module, "bidirectional", False) else ("attn_query",))]
+    if any(q is None for q in qs):
+        raise ValueError(f'{name}: readout="attn" on a module built without the attention parameter (attention=True)')
+    return qs
 
 
 def _check_resident(name, resident, hidden_size):
@@ -206,7 +236,11 @@ class _LstmFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, h0, c0, owner, call, L, *params):
+        """``params``: the 4 L parameters of the stack, then under "attn" the query (an input so that autograd asks for its
+        gradient; the plan reads ``call.attn``)."""
         plan = owner._checkout(call.B, call.T, x.device, call.training, dropout=call.drop is not None, state=call.state_plan)
+        if call.want_weights:
+            call.attn_out = [torch.empty((call.B, call.T), dtype=torch.float32, device=x.device)]
         got = _armed(plan, call, lambda: plan.forward(x, *(params[g * L:(g + 1) * L] for g in range(4)), want_all=call.outputs[1],
                                                       h0=h0, c0=c0, want_state=call.outputs[2]),
                      src=x if call.views is not None else None)
@@ -228,11 +262,12 @@ class _LstmFunction(torch.autograd.Function):
         dx, dh0, dc0 = (torch.empty(shape, dtype=torch.float32, device=params[0].device) if need else None
                         for need, shape in zip(ctx.need, (ctx.x_shape, state_shape, state_shape)))
         dy_last, dy_all, dh_n, dc_n = (dy if take else None for dy, take in zip(dys, call.outputs))
+        # (the query's gradient is written like the weights': into attn_query.grad -- overwritten or added to -- or a temporary)
         _armed(plan, call, lambda: plan.backward(dy_last, dy_all, [grads[g * L:(g + 1) * L] for g in range(4)], dx=dx,
                                                  dh_n=dh_n, dc_n=dc_n, dh0=dh0, dc0=dc0),
-               grad=(owner.grad_ready_hook if direct else None, accumulate))
+               grad=(owner.grad_ready_hook if direct else None, accumulate), dq=grads[4 * L] if len(grads) > 4 * L else None)
         ctx.lease.release()
-        return (dx, dh0, dc0, None, None, None, *([None] * (4 * L) if direct else grads))
+        return (dx, dh0, dc0, None, None, None, *([None] * len(params) if direct else grads))
 
 
 class HipLSTM(nn.Module):
@@ -252,14 +287,18 @@ class HipLSTM(nn.Module):
 
     ``readout``: "last" (the default), "mean" or "max" -- what ``forward`` and ``forward_views`` return as [B, H]: the top
     layer's output at each row's last step, or its mean / maximum over the row's steps, reduced from the workspace inside
-    the library with no [B, T, H] tensor written or read.  No parameter depends on it.
+    the library with no [B, T, H] tensor written or read.  No parameter depends on these three.
+    "attn": the weighted mean over the row's steps under the weights softmax_t(hidden_size ** -0.5 <h_t, attn_query>),
+    fused in the library likewise.  The module then owns ``attn_query`` [H], initialised to zeros --
+    mean pooling at the start --, and its state_dict holds that key; ``attention=True`` gives the parameter to a module
+    whose ``readout`` is another (LSTM.pooled).  ``forward(x, return_weights=True)`` also returns the detached weights.
     """
 
     MAX_IDLE_PLANS = 4      # workspaces are large (10 GB at cfg2): keep only a few idle ones
     _STATE_PLANS = False    # LSTM: plans created with CSN_LSTM_STATE
 
     def __init__(self, input_size, hidden_size, num_layers=1, compute_dtype=torch.bfloat16, dropout=0.0, resident=False,
-                 readout="last"):
+                 readout="last", attention=False):
         super().__init__()
         self.readout = _check_readout(type(self).__name__, readout)
         self.resident = _check_resident(type(self).__name__, resident, hidden_size)
@@ -268,6 +307,8 @@ class HipLSTM(nn.Module):
             warnings.warn("dropout option adds dropout after all but last recurrent layer, so non-zero dropout expects "
                           f"num_layers greater than 1, but got dropout={dropout} and num_layers={num_layers}")
         _adopt_lstm(self, input_size, hidden_size, num_layers, compute_dtype, float(dropout), bidirectional=False)
+        if attention or readout == "attn":
+            self.attn_query = nn.Parameter(torch.zeros(hidden_size))
         # set by a trainer that owns the gradient buffers (trainer.DistillTrainer): the backward writes each parameter's
         # gradient straight into its .grad and calls grad_ready_hook(layer) as soon as a layer's gradients are enqueued
         # direct_grads: False = temporaries; True = .grad is overwritten (one forward per step); "accumulate" = .grad is
@@ -290,6 +331,10 @@ class HipLSTM(nn.Module):
     def _flat_params(self):
         return [getattr(self, f"{n}_l{k}") for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh") for k in range(self.num_layers)]
 
+    def _own_queries(self):
+        """[attn_query] under the attention readout (an input of the autograd function behind the stack's parameters), else []."""
+        return _attn_queries(self, type(self).__name__) if self.readout == "attn" else []
+
     def forward_views(self, x, views, lengths):
         """Input windows: ``x`` is a SOURCE [S, Tsrc, I]; row b of the LSTM batch is ``x[rows[b], starts[b]:starts[b] +
         lengths[b]]`` with ``views = (rows, starts)``, read in place (csn_lstm_plan_set_views: no slice, no copy, no read
@@ -298,20 +343,27 @@ class HipLSTM(nn.Module):
         views of a batch are ONE recurrence pass.  No gradient reaches x (``x.requires_grad`` raises)."""
         _dropout_p(self)
         rows, starts, lengths = _check_views("HipLSTM", x, views, lengths, self.input_size)
-        params = self._flat_params()
+        params = self._flat_params() + self._own_queries()
         call = _Call(x, _training(None, None, None, params), _draw_dropout(self), lengths, (rows, starts), state_plan=True,
-                     readout=self.readout)
+                     readout=self.readout, attn=self._own_queries())
         return _LstmFunction.apply(x, None, None, self, call, self.num_layers, *params)[0]
 
-    def forward(self, x, want_all=False):
+    def forward(self, x, want_all=False, return_weights=False):
+        """-> y_last [B, H] (the readout); with ``want_all`` (y_all, y_last); with ``return_weights`` (readout "attn" only)
+        the detached attention weights [B, T] come last."""
         _dropout_p(self)
+        if return_weights and self.readout != "attn":
+            raise ValueError(f'{type(self).__name__}: return_weights needs readout="attn"')
         if not x.is_cuda:
             raise cabi.CsnError("HipLSTM runs on the GPU only (no CPU fallback); move the module and input to cuda")
-        params = self._flat_params()
+        params = self._flat_params() + self._own_queries()
         call = _Call(x, _training(x, None, None, params), _draw_dropout(self), outputs=(True, bool(want_all), False, False),
-                     readout=self.readout)
+                     readout=self.readout, attn=self._own_queries(), want_weights=return_weights)
         y_last, y_all, _, _ = _LstmFunction.apply(x, None, None, self, call, self.num_layers, *params)
-        return (y_all, y_last) if want_all else y_last
+        out = (y_all, y_last) if want_all else (y_last,)
+        if return_weights:
+            out += (call.weights(),)
+        return out if len(out) > 1 else out[0]
 
 
 def _check_views(name, x, views, lengths, input_size):
@@ -393,24 +445,31 @@ def _forward_stateful(module, name, dirs, function, x, hx, lengths, views, **for
     _dropout_p(module)
     if not x.is_cuda:
         raise cabi.CsnError(f"{name} runs on the GPU only (no CPU fallback); move the module and input to cuda")
-    params = module._flat_params()
+    params = module._flat_params() + list(form.get("attn") or ())
     call = _Call(x, _training(x, h0, c0, params), _draw_dropout(module), lengths, views, **form)
     got = function.apply(x, h0, c0, module, call, L, *params)
     if call.readout != "last":
-        return got[0]       # (pooled: the [B, H] / [B, 2H] readout alone)
+        return (got[0], call.weights()) if call.want_weights else got[0]       # (pooled: the [B, H] / [B, 2H] readout alone)
     *_, output, h_n, c_n = got
     return output, (h_n, c_n)
 
 
-def _pooled(module, name, x, hx, lengths, views, readout):
-    """``pooled`` of LSTM / BiLSTM: a PackedSequence is padded with the lengths it carries, the readout is checked."""
+def _pooled(module, name, x, hx, lengths, views, readout, return_weights=False):
+    """``pooled`` of LSTM / BiLSTM: a PackedSequence is padded with the lengths it carries, the readout is checked.
+    -> (x, lengths, what the readout adds to the call's form)."""
     if _check_readout(name, readout) == "last":
-        raise ValueError(f"{name}.pooled: readout must be 'mean' or 'max' (the last step is what forward's h_n[-1] holds)")
+        raise ValueError(f"{name}.pooled: readout must be 'mean' or 'max', or 'attn' on a module built with attention=True "
+                         "(the last step is what forward's h_n[-1] holds)")
+    if return_weights and readout != "attn":
+        raise ValueError(f'{name}.pooled: return_weights needs readout="attn"')
+    form = dict(readout=readout)
+    if readout == "attn":
+        form.update(attn=_attn_queries(module, f"{name}.pooled"), want_weights=return_weights)
     if isinstance(x, nn.utils.rnn.PackedSequence):
         if lengths is not None or views is not None:
             raise ValueError(f"{name}: lengths or views given together with a PackedSequence (it carries its own lengths)")
         x, lengths = nn.utils.rnn.pad_packed_sequence(x, batch_first=True)
-    return x, lengths
+    return x, lengths, form
 
 
 class LSTM(HipLSTM):
@@ -438,14 +497,14 @@ class LSTM(HipLSTM):
     _STATE_PLANS = True
 
     def __init__(self, input_size, hidden_size, num_layers=1, bias=True, batch_first=True, dropout=0.0,
-                 bidirectional=False, proj_size=0, compute_dtype=torch.bfloat16, resident=False):
+                 bidirectional=False, proj_size=0, compute_dtype=torch.bfloat16, resident=False, attention=False):
         unsupported = [name for name, bad in (("bias=False", not bias), ("batch_first=False", not batch_first),
                                               ("dropout != 0", dropout != 0), ("bidirectional=True", bidirectional),
                                               ("proj_size != 0", proj_size != 0)) if bad]
         if unsupported:
             raise ValueError(f"LSTM: {', '.join(unsupported)} is not supported (batch-first, biased, unidirectional "
                              f"stacks without projection or inter-layer dropout only; for bidirectional=True use BiLSTM)")
-        super().__init__(input_size, hidden_size, num_layers, compute_dtype=compute_dtype, resident=resident)
+        super().__init__(input_size, hidden_size, num_layers, compute_dtype=compute_dtype, resident=resident, attention=attention)
         self.bias, self.batch_first, self.dropout, self.bidirectional, self.proj_size = True, True, 0.0, False, 0
 
     def forward(self, x, hx=None, lengths=None, views=None):
@@ -456,15 +515,19 @@ class LSTM(HipLSTM):
         return _forward_stateful(self, "LSTM", 1, _LstmFunction, x, hx, lengths, views, outputs=(False, True, True, True),
                                  overwrite=False)
 
-    def pooled(self, x, hx=None, lengths=None, views=None, readout="mean"):
+    def pooled(self, x, hx=None, lengths=None, views=None, readout="mean", return_weights=False):
         """-> [B, H]: the mean (``readout="mean"``) or maximum ("max") of ``forward``'s output over each row's valid steps --
         ``output.sum(1) / n`` in float64 rounded once, or ``output.max over t < n``; rows of length 0 give zeros.  The
         library reduces the top layer's saved steps itself: no [B, T, H] output is written, and the backward expands the
         gradient inside the pass that lays it out for the recurrence.  Arguments as in ``forward``; gradients reach x, h0,
-        c0 and every parameter (under "max" at the first step that attains the maximum, as torch.max's)."""
-        x, lengths = _pooled(self, "LSTM", x, hx, lengths, views, readout)
+        c0 and every parameter (under "max" at the first step that attains the maximum, as torch.max's).
+        ``readout="attn"`` (a module built with ``attention=True``): the weighted mean under softmax_t(H ** -0.5 <output_t,
+        attn_query>) over the valid steps, float64 inside and rounded once; gradients also reach ``attn_query``.  With
+        ``return_weights`` -> (pooled, weights [B, T]): the detached float32 weights, zero past each row's length (no
+        gradient flows through them)."""
+        x, lengths, form = _pooled(self, "LSTM", x, hx, lengths, views, readout, return_weights)
         return _forward_stateful(self, "LSTM", 1, _LstmFunction, x, hx, lengths, views, outputs=(True, False, False, False),
-                                 overwrite=False, readout=readout)
+                                 overwrite=False, **form)
 
 
 class _BiLstmFunction(torch.autograd.Function):
@@ -480,7 +543,8 @@ class _BiLstmFunction(torch.autograd.Function):
     a source tensor and layer 0's two plans read their rows' windows of it in place (csn_lstm_plan_set_views).
     ``call.readout`` "mean" / "max" (BiLSTM.pooled): the first result is the pooled [B,2H] instead -- the two top-layer plans
     write no y_all and hand back their pooled y_last, which are concatenated, and the backward gives each its half of the
-    [B,2H] gradient as dy_last."""
+    [B,2H] gradient as dy_last.  Under "attn" the two queries follow the 8 L parameters, and each top-layer plan pools its
+    half under its own query and its own softmax."""
 
     @staticmethod
     def forward(ctx, x, h0, c0, owner, call, L, *params):
@@ -488,6 +552,8 @@ class _BiLstmFunction(torch.autograd.Function):
         h_n = torch.empty((2 * L, B, H), dtype=torch.float32, device=x.device)
         c_n = torch.empty((2 * L, B, H), dtype=torch.float32, device=x.device)
         leases, inp, halves = [], x, []
+        if call.want_weights:
+            call.attn_out = [torch.empty((B, T), dtype=torch.float32, device=x.device) for _ in range(2)]
         for l in range(L):
             pooled = call.readout != "last" and l == L - 1
             out = None if pooled else torch.empty((B, T, 2 * H), dtype=torch.float32, device=x.device)
@@ -540,7 +606,7 @@ class _BiLstmFunction(torch.autograd.Function):
                 _armed(plan, call, lambda: plan.backward(
                     dy[:, d * H:(d + 1) * H] if pooled else None, None if pooled else dy[:, :, d * H:(d + 1) * H], [[g] for g in grads[4 * k:4 * k + 4]], dx=dinp, dh_n=dh_n[k:k + 1],
                     dc_n=dc_n[k:k + 1], dh0=None if dh0 is None else dh0[k:k + 1], dc0=None if dc0 is None else dc0[k:k + 1]),
-                       grad=(None, False), k=k)
+                       grad=(None, False), k=k, dq=grads[8 * L + d] if pooled and call.readout == "attn" else None)
                 leases[k].release()
             dy = dinp
         return (dy, dh0, dc0, None, None, None, *grads)
@@ -577,7 +643,8 @@ class BiLSTM(nn.Module):
 
     MAX_IDLE_PLANS = 4
 
-    def __init__(self, input_size, hidden_size, num_layers=1, compute_dtype=torch.bfloat16, dropout=0.0, resident=False):
+    def __init__(self, input_size, hidden_size, num_layers=1, compute_dtype=torch.bfloat16, dropout=0.0, resident=False,
+                 attention=False):
         super().__init__()
         self.resident = _check_resident("BiLSTM", resident, hidden_size)     # passed to all 2L single-layer plans
         if dropout != 0:
@@ -585,6 +652,9 @@ class BiLSTM(nn.Module):
                              "between the layers of one plan; a bidirectional stack runs one plan per layer and direction)")
         _adopt_lstm(self, input_size, hidden_size, num_layers, compute_dtype, 0.0, bidirectional=True)
         self.bias, self.batch_first, self.bidirectional, self.proj_size = True, True, True, 0
+        if attention:
+            self.attn_query = nn.Parameter(torch.zeros(hidden_size))
+            self.attn_query_reverse = nn.Parameter(torch.zeros(hidden_size))
 
     def _checkout(self, B, T, I, device, training, reverse):
         key = (B, T, I, str(device), bool(training), self.compute_dtype, bool(reverse)) + (("resident plan",) if self.resident else ())
@@ -606,13 +676,18 @@ class BiLSTM(nn.Module):
         bits of the call on the gathered rows.  No gradient reaches x through views (``x.requires_grad`` raises)."""
         return _forward_stateful(self, "BiLSTM", 2, _BiLstmFunction, x, hx, lengths, views, bi=(self.num_layers, self.hidden_size))
 
-    def pooled(self, x, hx=None, lengths=None, views=None, readout="mean"):
+    def pooled(self, x, hx=None, lengths=None, views=None, readout="mean", return_weights=False):
         """-> [B, 2H]: the mean ("mean") or maximum ("max") of ``forward``'s output over each row's valid steps, as
         ``LSTM.pooled``: each direction's top-layer plan pools its half and the two [B, H] results are concatenated, which
-        equals pooling the [B, T, 2H] output.  The top layer writes no output tensor.  Arguments as in ``forward``."""
-        x, lengths = _pooled(self, "BiLSTM", x, hx, lengths, views, readout)
+        equals pooling the [B, T, 2H] output.  The top layer writes no output tensor.  Arguments as in ``forward``.
+        ``readout="attn"`` (a module built with ``attention=True``, which owns ``attn_query`` and ``attn_query_reverse``):
+        each direction's top-layer plan pools ITS half with its own query and its own softmax over time, and the two
+        [B, H] halves are concatenated.  This is NOT one softmax over the concatenated [B, T, 2H] output (one query of 2H
+        entries scoring both halves together): that joint form is left out.  With ``return_weights`` -> (pooled, weights
+        [B, T, 2]), the detached weights of the forward and the reverse direction, both indexed by the caller's time."""
+        x, lengths, form = _pooled(self, "BiLSTM", x, hx, lengths, views, readout, return_weights)
         return _forward_stateful(self, "BiLSTM", 2, _BiLstmFunction, x, hx, lengths, views, bi=(self.num_layers, self.hidden_size),
-                                 readout=readout)
+                                 **form)
 
 
 class Model(nn.Module):
@@ -626,14 +701,17 @@ class Model(nn.Module):
         ``fc`` is then ``cat(h_n[-2], h_n[-1])``, the top layer's FINAL state in each direction -- not ``output[:, -1]``,
         whose reverse half has seen one step only.  ``resident=True`` (lstm_size <= 128): the encoder's plans run the
         CU-resident recurrence (HipLSTM).  ``readout`` "mean" / "max": the feature fed to ``fc`` is the top layer's output
-        pooled over each row's steps instead (HipLSTM's ``readout``; bidirectional: ``BiLSTM.pooled``).  It adds no
-        parameter: checkpoints are unchanged."""
+        pooled over each row's steps instead (HipLSTM's ``readout``; bidirectional: ``BiLSTM.pooled``).  These add no
+        parameter: checkpoints are unchanged.  ``readout="attn"``: the attention readout; the encoder then owns
+        ``lstm.attn_query`` (and ``lstm.attn_query_reverse``, each direction pooling its half under its own softmax), which
+        the state_dict holds -- a checkpoint is evaluated with the readout it was trained with."""
         super().__init__()
         self.readout = _check_readout("Model", readout)
         self.input_size, self.lstm_size, self.lstm_layers = input_size, lstm_size, lstm_layers
         self.output_size, self.include_top, self.bidirectional = output_size, include_top, bool(bidirectional)
         if self.bidirectional:
-            self.lstm = BiLSTM(input_size, lstm_size, lstm_layers, compute_dtype=compute_dtype, resident=resident)
+            self.lstm = BiLSTM(input_size, lstm_size, lstm_layers, compute_dtype=compute_dtype, resident=resident,
+                               attention=readout == "attn")
             # (the attribute, as on the LSTM drop-in: its constructor takes 0 only)
             self.lstm.dropout = _check_dropout_p(dropout)
         else:
@@ -674,8 +752,8 @@ class LSTMModel(nn.Module):
 
     def __init__(self, input_size, hidden_size, n_layers=2, out_features=384, number_of_classes=None,
                  all_steps=False, compute_dtype=torch.bfloat16, dropout=0.0, resident=False, readout="last"):
-        """``readout`` "mean" / "max" (the form without ``all_steps`` only): ``fc`` reads the LSTM output pooled over the
-        sequence instead of its last step (HipLSTM's ``readout``)."""
+        """``readout`` "mean" / "max" / "attn" (the form without ``all_steps`` only): ``fc`` reads the LSTM output pooled over
+        the sequence instead of its last step (HipLSTM's ``readout``; "attn" adds ``lstm.attn_query`` to the state_dict)."""
         super().__init__()
         if _check_readout("LSTMModel", readout) != "last" and all_steps:
             raise ValueError("LSTMModel: readout applies to the form without all_steps (all_steps feeds every step to fc)")

@@ -361,7 +361,10 @@ class DistillTrainer:
         total = self.grads.flat.numel()
         # segments: LSTM layer k = k, everything behind the LSTM's parameters (fc, class_pred) = L
         self.grads.segments = [(first[k], first[k + 1] if k + 1 < L else lstm_end) for k in range(L)] + [(lstm_end, total)]
-        others = [p for p in self.grads.params if self.grads.offsets[id(p)][0] >= lstm_end]
+        # (the attention readout's query lies behind the stack's parameters, in the head's range; the library writes its
+        # gradient in front of the recurrence -- complete before the first callback --, so no autograd hook waits for it)
+        own = {id(p) for p in lstm.parameters()}
+        others = [p for p in self.grads.params if self.grads.offsets[id(p)][0] >= lstm_end and id(p) not in own]
         self._others_left = len(others)
         self._n_others = len(others)
 

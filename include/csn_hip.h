@@ -94,7 +94,7 @@ enum csnStatus {
 enum csnDtype { CSN_F32 = 0, CSN_BF16 = 1 };
 
 /* ABI version of this header; bumped on any signature change.  A symbol added beside the existing ones
- * (csn_lstm_plan_set_grad_mode, csn_lstm_plan_set_lengths, csn_lstm_plan_set_views, csn_lstm_plan_set_io, csn_lstm_plan_set_readout, csn_lstm_plan_half_tile_launches, the
+ * (csn_lstm_plan_set_grad_mode, csn_lstm_plan_set_lengths, csn_lstm_plan_set_views, csn_lstm_plan_set_io, csn_lstm_plan_set_readout, csn_lstm_plan_set_attention, csn_lstm_plan_half_tile_launches, the
  * csn_flat_* family, csn_adam_step, csn_lars_step, csn_eeg_bandpass_stream and its _path, csn_distill_loss,
  * csn_dino_loss, csn_barlow_corr, csn_barlow_grad, csn_contrastive_lse, csn_contrastive_grad, csn_bank_norms, csn_bank_contrastive and its _scratch_bytes, csn_topk_merge and its _staged_max, csn_topk_class_metrics, csn_grad_guard, its _scratch_bytes and the three
  * csn_*_step_guarded) breaks no caller and does not bump it; neither does a new bit of csn_lstm_plan_create's `training` word. */
@@ -411,6 +411,42 @@ int csn_lstm_plan_set_io(csnLstmPlan* plan, int64_t y_all_pitch, int64_t dy_all_
 #define CSN_READOUT_MEAN 1
 #define CSN_READOUT_MAX  2
 int csn_lstm_plan_set_readout(csnLstmPlan* plan, int mode);
+
+/* The attention readout: y_last as a weighted mean over time whose weights come from a learned query,
+ * a[b, t] = softmax over t < n of scale <v[b, t, :], q>, in place of the last / mean / max of csn_lstm_plan_set_readout.
+ * Host only and sticky until set again, like the other setters; it takes no stream.  All pointers are device memory:
+ * q [H]; dq [H] or NULL (a frozen query); attn_out and dscore_out dense [B, T] float32 (T the descriptor's) or NULL.
+ * q != NULL turns the attention readout on: it then defines y_last in csn_lstm_forward and dy_last in csn_lstm_backward,
+ * whatever csn_lstm_plan_set_readout says; q == NULL turns it off and the plan's readout mode governs again.  Every plan
+ * and every path (0-5), training and inference, with every plan bit and feature (state and lengths, reverse, dropout and
+ * output dropout, views and io pitches, accumulation and the callback).  y_all, h_n, c_n, the workspace layout and
+ * csn_lstm_plan_workspace_bytes do not change, and a plan that never calls this enqueues the launches and writes the bits
+ * it did before this symbol existed.  q is read at forward and again at backward: keeping it unchanged between the two
+ * is the caller's contract, as for the weights.  A forward computes the readout (and writes attn_out) only when y_last
+ * is asked for.  
+ * With v and n as above:
+ *   FORWARD.   z64[b, t] = (double)scale * sum over h of (double)v (double)q[h]; a64 = softmax of z64 over t < n,
+ *              max-subtracted, in float64; y_last[b, h] = fl32(sum over t < n of a64[b, t] (double)v[b, t, h]), one rounding;
+ *              attn_out[b, t] = a32 = fl32(a64), and 0 for t >= n.  Rows with n = 0 give zero y_last and zero weights.
+ *              Output dropout does not touch the pooled value.  Nothing past a row's length is read.
+ *   BACKWARD.  g64[b, t] = sum over h of (double)dy_last[b, h] (double)v[b, t, h]; s64[b] = sum over t of a64 g64;
+ *              dscore_out[b, t] = w32 = fl32((double)scale a64 (g64 - s64)), 0 for t >= n.  Every valid step receives
+ *              G[b, t, h] = fl32(fl32(a32 dy_last[b, h]) + fl32(w32 q[h])): three separately rounded float32 operations.
+ *              Into the top layer's gradient go, in this order: the (masked) dy_all element or 0; G, as ONE float32 add;
+ *              the top layer's dh_n at the row's end.  dq[h] = fl32(sum over b, t < n of (double)w32[b, t] (double)v[b, t, h]),
+ *              under CSN_GRAD_ACCUMULATE fl32(dq[h] + that); it is enqueued in front of the recurrence, so it is complete
+ *              when the first gradient-ready callback fires.  Rows with n = 0 receive nothing from dy_last.  A backward
+ *              without dy_last (or with every row empty) zeroes dq (leaves it, accumulating).
+ *   RECOMPUTE. The backward computes a again from the workspace and q -- the forward saves nothing -- and writes the same
+ *              attn_out bits the forward wrote.  The [B, T] scratch the plan owns is allocated on first use and written and
+ *              read in stream order inside the one call.  Every split of a sum is fixed: the same call gives the same bits.
+ *   IDENTITY.  A backward under attention has, bit for bit, every LSTM gradient (dx, dh0, dc0, all weight and bias
+ *              gradients) of the same plan with attention off under CSN_READOUT_LAST, called with dy_last = NULL and
+ *              dy_all' = fl32(dy_all + G) (plain G where dy_all is NULL).
+ * Cost: three launches in the forward (scores, rows, weighted sum; two reads of the top layer's saved h), two pre-pass
+ * launches in the backward plus two for dq (two reads), and the term rides in the dy_all layout pass.
+ * Null plan, a non-finite scale, or dq / attn_out / dscore_out without q: CSN_ERR_INVALID_ARGUMENT (the setting is kept). */
+int csn_lstm_plan_set_attention(csnLstmPlan* plan, const float* q, float scale, float* dq, float* attn_out, float* dscore_out);
 
 /* Inter-layer dropout, with torch.nn.LSTM(dropout=p)'s meaning: for every layer l < L-1 the output sequence of layer l is
  * multiplied element-wise by an independent Bernoulli(1-p) mask and by 1/(1-p) before layer l+1's input projection.

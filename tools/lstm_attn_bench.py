@@ -1,26 +1,25 @@
-"""What the pooled readout (csn_lstm_plan_set_readout) costs and saves on a training step's forward +
-backward of `Model`:
+"""What the attention readout (csn_lstm_plan_set_attention) costs on a training step's forward + backward
+of `Model`:
 
-    python tools/lstm_readout_bench.py [--out profiles/lstm_readout_bench.json] [--reps 20] [--parent_lib PATH]
+    python tools/lstm_attn_bench.py [--out profiles/lstm_attn_bench.json] [--reps 20] [--parent_lib PATH]
 
-Per shape, on the same inputs and parameter values, one `Model` (include_top=False, bf16) and a gradient on its features:
-  (last)        Model(readout="last"): the gather of the last step, dy_last into the last step;
-  (mean, max)   Model(readout=...): the pooling reduction behind the recurrence, dy_last expanded inside the dy layout pass;
-  (torch_mean,  the same pooling written in torch on the same parameters: y_all asked of the library (a float32 [B,T,H]
-   torch_max)   tensor), `y_all.mean(1)` / `y_all.max(1).values`, fc; autograd materialises the [B,T,H] gradient and the
-                library's dy layout pass reads it;
+Per shape of tools/lstm_readout_bench.py, on the same inputs and parameter values, one `Model` (include_top=False, bf16) and a
+gradient on its features:
+  (last)        Model(readout="last"), attention off: the gather of the last step;
+  (mean)        Model(readout="mean"): the fused pooling reduction;
+  (attn)        Model(readout="attn") with a non-zero query: the score, row and weighted-sum kernels behind the recurrence, the
+                pre-passes, dq and the attention term of the dy layout pass in front of the backward's;
+  (torch_attn)  the same attention in torch ops on the same parameters: y_all asked of the library (a float32 [B,T,H] tensor),
+                softmax(scale (y_all @ q), dim=1), the weighted sum, fc; autograd materialises the [B,T,H] gradient;
   (last against the parent) with --parent_lib, the library built from the parent commit: leg (last) once more in fresh child
                 processes, on this tree's library and on the parent's (CSN_LIB_PATH) in turns.  The parent's library has no
-                csn_lstm_plan_set_readout: the child drops the symbol from the binding and answers "last" itself.
-Timing: one pair of device events around one forward + backward, the legs alternating sample by sample in one process after a
-warm-up of all of them; per leg the median over the repetitions, min / max.  Per leg also the peak of torch's allocated
-memory over one step above what was allocated before it (the plans' workspaces are allocated before: they are the same in
-every leg), and the device kernels of one step as torch.profiler counts them ("not measured" where it gives none).
+                csn_lstm_plan_set_attention: the child drops the symbol from the binding and takes "off" only.
+Timing, peak allocation and kernel counts as in tools/lstm_readout_bench.py: one pair of device events around one forward +
+backward, the legs alternating sample by sample after a warm-up of all of them, median of the repetitions with min / max.
 Needs a GPU: there is no fallback."""
 import argparse
 import json
 import os
-import statistics
 import subprocess
 import sys
 
@@ -29,56 +28,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from tools.l2_topk_bench import csrc_sha16      # noqa: E402
-
-# (name, B, T, I, H, L, resident): bench.py --config cfg2's LSTM shape, and the reference's H = 96 model on resident plans
-CASES = [("cfg2", 256, 500, 128, 768, 2, False), ("ref_h96_resident", 16, 460, 96, 96, 2, True)]
-D = 384
-
-
-def _stats(ms):
-    return dict(median_ms=statistics.median(ms), min_ms=min(ms), max_ms=max(ms), spread_ms=max(ms) - min(ms))
-
-
-def _time_legs(legs, reps):
-    """{name: fn} -> {name: [ms] * reps}, the legs in turns after two warm-up rounds of all of them."""
-    for _ in range(2):
-        for fn in legs.values():
-            fn()
-    torch.cuda.synchronize()
-    ms = {n: [] for n in legs}
-    for _ in range(reps):
-        for n, fn in legs.items():
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            b.record()
-            b.synchronize()
-            ms[n].append(a.elapsed_time(b))
-    return ms
-
-
-def _peak_bytes(fn):
-    torch.cuda.synchronize()
-    before = torch.cuda.memory_allocated()
-    torch.cuda.reset_peak_memory_stats()
-    fn()
-    torch.cuda.synchronize()
-    return torch.cuda.max_memory_allocated() - before
-
-
-def _kernels(fn):
-    """Device kernels of one fn() as torch.profiler counts them, or None."""
-    try:
-        from torch.profiler import ProfilerActivity, profile
-        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-            fn()
-            torch.cuda.synchronize()
-        n = sum(1 for e in prof.events() if str(e.device_type).endswith("CUDA") and "memcpy" not in e.name.lower()
-                and "memset" not in e.name.lower())
-        return n or None
-    except Exception as e:      # noqa: BLE001  (a profiler that does not start: the timing stands without the count)
-        print(f"lstm_readout_bench: no kernel count ({type(e).__name__}: {e})", file=sys.stderr)
-        return None
+from tools.lstm_readout_bench import CASES, D, _kernels, _peak_bytes, _stats, _time_legs      # noqa: E402
 
 
 def _case(case, dev, readouts):
@@ -88,9 +38,12 @@ def _case(case, dev, readouts):
     models = {}
     for r in readouts:
         models[r] = Model(I, H, L, D, include_top=False, resident=resident, readout=r).to(dev).train()
-        models[r].load_state_dict(models[readouts[0]].state_dict())
+        models[r].load_state_dict(models[readouts[0]].state_dict(), strict=False)
     x = torch.randn(B, T, I, device=dev)
     dy = torch.randn(B, D, device=dev)
+    if "attn" in models:
+        with torch.no_grad():
+            models["attn"].lstm.attn_query.copy_(torch.randn(H, device=dev))
 
     def fused(r):
         def step():
@@ -98,17 +51,19 @@ def _case(case, dev, readouts):
             models[r](x).backward(dy)
         return step
 
-    def in_torch(r):
-        m = models["last"]
+    def in_torch():
+        m, q = models["last"], models["attn"].lstm.attn_query.detach().clone().requires_grad_(True)
 
         def step():
             m.zero_grad(set_to_none=True)
+            q.grad = None
             y_all, _ = m.lstm(x, want_all=True)
-            m.fc(y_all.mean(1) if r == "mean" else y_all.max(1).values).backward(dy)
+            a = torch.softmax(H ** -0.5 * (y_all @ q), dim=1)
+            m.fc((a[:, :, None] * y_all).sum(1)).backward(dy)
         return step
     legs = {r: fused(r) for r in readouts}
-    if "mean" in readouts:
-        legs.update(torch_mean=in_torch("mean"), torch_max=in_torch("max"))
+    if "attn" in readouts:
+        legs["torch_attn"] = in_torch()
     return models, legs
 
 
@@ -116,15 +71,12 @@ def child(args):
     """Leg (last) alone, on whatever library CSN_LIB_PATH names; one JSON line per case."""
     from cerebralsignalnetworks_amd import cabi
     if args.child == "parent":
-        cabi.SIGNATURES.pop("csn_lstm_plan_set_readout")
+        cabi.SIGNATURES.pop("csn_lstm_plan_set_attention")
 
-        def last_only(self, mode):
-            if cabi.readout_mode(mode) != cabi.READOUT_LAST:
-                raise RuntimeError("the parent's library has no pooled readout")
-        cabi.LstmPlan.set_readout = last_only
-        # (nor the attention readout that came after it, which the modules turn off on every plan)
-        cabi.SIGNATURES.pop("csn_lstm_plan_set_attention", None)
-        cabi.LstmPlan.set_attention = lambda self, q=None, *rest, **kw: None
+        def off_only(self, q=None, *rest, **kw):
+            if q is not None:
+                raise RuntimeError("the parent's library has no attention readout")
+        cabi.LstmPlan.set_attention = off_only
     dev = torch.device("cuda:0")
     for case in CASES:
         models, legs = _case(case, dev, ["last"])
@@ -148,22 +100,22 @@ def _run_child(which, lib, reps):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "lstm_readout_bench.json"))
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "lstm_attn_bench.json"))
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--parent_lib", default=None, help="libcsn_hip.so built from the parent commit: adds the last leg")
     ap.add_argument("--child", default=None, choices=["new", "parent"], help=argparse.SUPPRESS)
     args = ap.parse_args()
     if not torch.cuda.is_available():
-        sys.exit("lstm_readout_bench: no GPU is visible (there is no fallback)")
+        sys.exit("lstm_attn_bench: no GPU is visible (there is no fallback)")
     if args.child:
         return child(args)
     if args.reps < 20:
-        sys.exit("lstm_readout_bench: at least 20 timed repetitions per shape")
+        sys.exit("lstm_attn_bench: at least 20 timed repetitions per shape")
     dev = torch.device("cuda:0")
     out = []
     for case in CASES:
         name, B, T, I, H, L, resident = case
-        models, legs = _case(case, dev, ["last", "mean", "max"])
+        models, legs = _case(case, dev, ["last", "mean", "attn"])
         ms = _time_legs(legs, args.reps)
         torch.cuda.synchronize()
         plans = [pl for m in models.values() for pl in m.lstm.all_plans()]
@@ -172,9 +124,9 @@ def main():
                    y_all_bytes=B * T * H * 4, legs={n: _stats(v) for n, v in ms.items()},
                    peak_allocated_bytes_above_start={n: _peak_bytes(fn) for n, fn in legs.items()},
                    device_kernels_per_step={n: _kernels(fn) or "not measured" for n, fn in legs.items()})
-        for r in ("mean", "max"):
-            res[f"torch_{r}_over_fused_{r}"] = res["legs"][f"torch_{r}"]["median_ms"] / res["legs"][r]["median_ms"]
-            res[f"fused_{r}_minus_last_ms"] = res["legs"][r]["median_ms"] - res["legs"]["last"]["median_ms"]
+        res["torch_attn_over_fused_attn"] = res["legs"]["torch_attn"]["median_ms"] / res["legs"]["attn"]["median_ms"]
+        res["fused_attn_minus_last_ms"] = res["legs"]["attn"]["median_ms"] - res["legs"]["last"]["median_ms"]
+        res["fused_attn_minus_mean_ms"] = res["legs"]["attn"]["median_ms"] - res["legs"]["mean"]["median_ms"]
         print(json.dumps(res), flush=True)
         out.append(res)
         del models, legs, plans
@@ -194,7 +146,7 @@ def main():
             res["last_new_inside_the_recorded_spread_of_the_parent"] = bool(par["min_ms"] <= new["median_ms"] <= par["max_ms"])
             print(json.dumps({k: res[k] for k in ("case", "last_child_new", "last_child_parent", "last_new_minus_parent_ms",
                                                   "last_new_inside_the_recorded_spread_of_the_parent")}), flush=True)
-    result = dict(tool="tools/lstm_readout_bench.py", device=torch.cuda.get_device_name(0), csrc_sha16=csrc_sha16(),
+    result = dict(tool="tools/lstm_attn_bench.py", device=torch.cuda.get_device_name(0), csrc_sha16=csrc_sha16(),
                   parent_leg="measured" if args.parent_lib else "not measured", cases=out)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
